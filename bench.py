@@ -12,8 +12,15 @@ instance, 176 B of HBM traffic per solve); `achieved` is algorithmic FP64
 FLOP/s = sum(iters) * F_iter / mean kernel time, F_iter = 6.0e4 FLOP per
 IPM iteration per instance, against the 78.6 TFLOP/s FP64 peak.
 
-cpu_baseline: the C oracle (oracle/pmpc_ipm.c: IPOPT-style filter IPM on the
-full 6-state NLP), timed on rank 0 over a bounded sample.
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the result line; with --dump-outputs DIR it also writes the
+arrays the last timed step returned.  Everything else -- the accuracy check against
+the C oracle, the CPU baselines, the saturated / host-inclusive / C3 / C4 / C5 /
+arm-QP / restoration / long-horizon lines -- runs only with --full (their fields
+are null in a plain run's line).
+
+cpu_baseline (--full): the C oracle (oracle/pmpc_ipm.c: IPOPT-style filter IPM on
+the full 6-state NLP), timed on rank 0 over a bounded sample.
 """
 from __future__ import annotations
 
@@ -47,6 +54,12 @@ def parse():
     ap.add_argument("--plumbing-only", action="store_true",
                     help="run the multi-rank plumbing (process group, barrier + max-over-ranks timing, the C4 "
                          "shard / gather) on the CPU without solving: a launcher self-test")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the accuracy check against the C oracle, "
+                         "the CPU baselines and every supplementary line (the options below them apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (u0, f, status, iters of its "
+                         "batch) as DIR/<name>.npy in float64; ranks above 0 write <name>_rank<r>.npy")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=18, help="instances per step per GPU (18 = the metric's config)")
@@ -1029,6 +1042,10 @@ def main():
         dist.init_process_group(backend, **({} if host_coll else {"device_id": dev}))
 
     B, N, K, W = args.batch, args.N, args.steps, args.warmup
+    if K < 1 or W < 0:
+        sys.stderr.write("bench.py: --steps must be at least 1 and --warmup at least 0\n")
+        sys.exit(2)
+    full = args.full
     n_seeds_step = max(1, -(-B // 18))
     # fresh seeded inputs for every step, all resident in HBM before timing
     steps_in = []
@@ -1101,10 +1118,18 @@ def main():
     ok_frac = float(np.mean(st == 0))
     iters_sum_per_launch = float(its.sum(axis=1).mean())
 
+    if args.dump_outputs:
+        # the last timed step's outputs as solve_batch_dev's caller finds them (the inputs are seeded by rank and
+        # step index alone, so two builds run with the same arguments solve the same instances)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = "" if rank == 0 else f"_rank{rank}"
+        for name, a in (("u0", u0[-1]), ("f", FV[W + K - 1].cpu().numpy()), ("status", st[-1]), ("iters", its[-1])):
+            np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
     # accuracy: max |u0 - u0_ref| against the C oracle on the first timed step (rank 0)
     max_du = None
     cpu_baseline = None
-    if rank == 0:
+    if rank == 0 and full:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_lib   # checker + CPU baseline only
         S, T, P = steps_in[W]
@@ -1140,7 +1165,7 @@ def main():
 
     # supplementary saturated rate: one launch over a large batch (not the headline value)
     saturation = None
-    if args.saturation_batch > 0:
+    if full and args.saturation_batch > 0:
         Bs = args.saturation_batch
         S, T, P = pmpc_batch(n_seeds=-(-Bs // 18), seed0=500000 + 1000 * rank)
         sx = torch.tensor(S[:Bs], device=dev); st_ = torch.tensor(T[:Bs], device=dev); spr = torch.tensor(P[:Bs], device=dev)
@@ -1168,7 +1193,7 @@ def main():
     # The task's bench contract makes `value` the device-resident rate (inputs in HBM when the timed
     # region starts), so this is reported beside it as `value_host_inclusive_8d`.
     host_incl = None
-    if args.host_calls > 0:
+    if full and args.host_calls > 0:
         Kh = min(K, args.host_calls)
         bufs = dict(u0=np.empty((B, 2)), f=np.empty(B), status=np.empty(B, np.int32), iters=np.empty(B, np.int32))
 
@@ -1222,7 +1247,7 @@ def main():
 
     # supplementary host-pointer path (dart_mpc_solve_batch): H2D copies + solve + D2H + sync per call
     host_path = None
-    if rank == 0 and args.host_calls > 0:
+    if full and rank == 0 and args.host_calls > 0:
         hs = dart_mpc.Solver(N=N, Ts=0.002, tol=args.tol, B_max=B, device=local, path=args.pmpc_path)
         S, T, P = steps_in[W]
         for _ in range(5):
@@ -1246,38 +1271,38 @@ def main():
         hs.close()
 
     # supplementary C4 (BASELINE.json configs[3]): 1152 instances sharded over the ranks + result gather
-    c4 = bench_c4(args, torch, dev, stream, dart_mpc, world, rank, host_coll, coll) if args.c4_steps > 0 else None
+    c4 = bench_c4(args, torch, dev, stream, dart_mpc, world, rank, host_coll, coll) if full and args.c4_steps > 0 else None
 
     # supplementary: PMPC launches holding instances that need IPOPT's restoration phases
     pmpc_resto = None
-    if rank == 0 and args.resto_steps > 0:
+    if full and rank == 0 and args.resto_steps > 0:
         pmpc_resto = bench_pmpc_restoration(args, torch, dev, stream, dart_mpc)
 
     # supplementary: horizons beyond 31 on all three variants
     long_h = None
-    if rank == 0 and args.long_steps > 0:
+    if full and rank == 0 and args.long_steps > 0:
         long_h = bench_long_horizons(args, dart_mpc)
 
     # supplementary PMPC line at the DART driver's horizon (N = 15)
     n15 = None
-    if rank == 0 and args.n15_steps > 0:
+    if full and rank == 0 and args.n15_steps > 0:
         n15 = bench_pmpc_driver_horizon(args, torch, dev, stream, dart_mpc)
 
     # supplementary C3 (BASELINE.json configs[2]): RMPC batch=18 with the RLS update fused into the launch
     rmpc = None
-    if rank == 0 and args.rmpc_steps > 0:
+    if full and rank == 0 and args.rmpc_steps > 0:
         rmpc = bench_rmpc(args, torch, dev, stream, dart_mpc)
 
     # supplementary C5 (BASELINE.json configs[4]): LMPC batch=18, N=30, pvec as input
     lmpc = None
-    if rank == 0 and args.lmpc_steps > 0:
+    if full and rank == 0 and args.lmpc_steps > 0:
         lmpc = bench_lmpc(args, torch, dev, stream, dart_mpc)
         if args.lmpc_policy_steps > 0:
             lmpc["policy_fused"] = bench_lmpc_policy(args, torch, dev, stream, dart_mpc)
 
     # supplementary: per-arm impedance QP
     arm = None
-    if rank == 0 and args.arm_steps > 0:
+    if full and rank == 0 and args.arm_steps > 0:
         arm = bench_arm(args, torch, dev, stream, dart_mpc)
 
     # HBM traffic per launch from the committed rocprofv3 PMC passes of this build (tools/profile_round.sh)
@@ -1318,6 +1343,7 @@ def main():
             "n_gpus": world,
             "steps": K,
             "warmup": W,
+            "full": full,
             "ms_per_step": elapsed / K * 1e3,
             "higher_is_better": True,
             "scaling": "weak",

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 DART_PMPC_OCC2_MIN_B=1 timeout -k 10 400 python -u -m pytest tests/test_gpu_pmpc.py -m gpu -x -q --timeout 180 \
     --timeout-method thread > gpurun_out/occ2_tests.log 2>&1 || { echo TESTS_FAILED; tail -30 gpurun_out/occ2_tests.log; exit 1; }
 echo "occ2 parity: $(tail -1 gpurun_out/occ2_tests.log)"
-ARGS="--steps 200 --warmup 20 --no-cpu-baseline --host-calls 0 --n15-steps 0 --rmpc-steps 0 --lmpc-steps 0 --lmpc-policy-steps 0 --arm-steps 0 --c4-steps 50"
+ARGS="--full --steps 200 --warmup 20 --no-cpu-baseline --host-calls 0 --n15-steps 0 --rmpc-steps 0 --lmpc-steps 0 --lmpc-policy-steps 0 --arm-steps 0 --c4-steps 50"
 for r in $(seq 1 $REPS); do
   for th in off 1024; do
     for sb in 4096 18432; do

@@ -6,7 +6,7 @@ BS=${1:-"1536 2048 2560 3072"}
 REPS=${2:-2}
 HN=${3:-20}
 mkdir -p gpurun_out
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --host-calls 0 --n15-steps 0 --rmpc-steps 0 --lmpc-steps 0 --lmpc-policy-steps 0 --arm-steps 0 --c4-steps 0 --N $HN"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --host-calls 0 --n15-steps 0 --rmpc-steps 0 --lmpc-steps 0 --lmpc-policy-steps 0 --arm-steps 0 --c4-steps 0 --N $HN"
 for r in $(seq 1 $REPS); do
   for sb in $BS; do
     for th in off 1; do

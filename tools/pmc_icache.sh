@@ -19,6 +19,6 @@ for c in SQC_ICACHE_MISSES SQC_ICACHE_HITS SQC_ICACHE_REQ SQC_ICACHE_MISSES_DUPL
 done
 echo "counters: $CTRS" | tee $OUT/counters.txt
 timeout -s KILL 120 rocprofv3 --pmc $CTRS --kernel-trace -d $OUT -o run --output-format csv -- \
-    python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline --saturation-batch 0 --host-calls 0 --c4-steps 0 --n15-steps 0 \
+    python3 bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --saturation-batch 0 --host-calls 0 --c4-steps 0 --n15-steps 0 \
     --rmpc-steps 30 --lmpc-steps 30 --lmpc-policy-steps 30 --arm-steps 0 > $OUT/bench.json 2> $OUT/err.log || exit $?
 echo icache_done
