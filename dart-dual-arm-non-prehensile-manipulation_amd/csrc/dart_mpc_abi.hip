@@ -9,6 +9,7 @@
 #include <cstring>
 #include <chrono>
 #include <mutex>
+#include <initializer_list>
 #include <vector>
 #include <string>
 
@@ -20,6 +21,7 @@
 #include "lmpc_ipm.h"
 #include "lmpc_policy.h"
 #include "arm_qp.h"
+#include "loop_step.h"
 
 #include <cmath>
 
@@ -207,6 +209,11 @@ struct dart_mpc_handle {
     };
     std::vector<RestoArea> resto;
     unsigned xcd_next = 0;
+    // closed-loop rollouts (dart_*_rollout*): the solve's per-step arrays for B_max instances, allocated on first
+    // use, and the device arena of the host entries (state and logs), grown on demand
+    char* loop_buf = nullptr;
+    char* roll_buf = nullptr;
+    size_t roll_cap = 0;
 };
 
 namespace {
@@ -1159,6 +1166,8 @@ void dart_mpc_destroy(dart_mpc_handle* h) {
     if (h->hdone) (void)hipHostFree(h->hdone);
     for (auto& e : h->resto)
         if (e.buf) (void)hipFree(e.buf);       // (synchronises with the area's last use)
+    if (h->loop_buf) (void)hipFree(h->loop_buf);
+    if (h->roll_buf) (void)hipFree(h->roll_buf);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1224,5 +1233,339 @@ int dart_arm_solve_batch(const dart_arm_config* cfg, int B, int n, const double*
     if (e != hipSuccess) return DART_MPC_EHIP;
     S.take(qdd, a.qdd, (size_t)n * B); S.take(tau, a.tau, (size_t)n * B); S.take(loss, a.loss, B);
     S.take(status, a.status, B); S.take(iters, a.iters, B);
+    return DART_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// device-resident closed-loop rollouts (loop_step.hip between the unchanged solves)
+void dart_plant_config_default(dart_plant_config* c) {
+    if (!c) return;
+    c->tau = 0.03; c->mu_c = 0.02; c->v_c = 0.01;       // harness.TrayPlant
+}
+
+void dart_rmpc_loop_config_default(dart_rmpc_loop_config* c) {
+    if (!c) return;
+    c->dr_max = 0.01; c->alpha_rg = 0.5; c->step_fraction = 0.2; c->rls_lambda = 0.995; c->pos_tol = 0.01;
+}
+
+namespace {
+
+bool any_null(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (!p) return true;
+    return false;
+}
+
+dartmpc::PlantArgs plant_args(const dart_mpc_handle* h, const dart_plant_config* p) {
+    dartmpc::PlantArgs a;
+    a.a_lag = p->tau > 0.0 ? 1.0 - std::exp(-h->cfg.Ts / p->tau) : 1.0;
+    a.mu_c = p->mu_c; a.v_c = p->v_c; a.dt = h->cfg.Ts; a.g = h->cfg.gravity;
+    return a;
+}
+
+// the checks every rollout / loop-step entry shares: the call writes the log rows k .. k + steps - 1
+int loop_check(dart_mpc_handle* h, int variant, const dart_plant_config* plant, int B, int k, int steps, int log_rows) {
+    if (h->cfg.variant != variant)
+        return fail(h, DART_MPC_EINVAL, variant == DART_MPC_RMPC ? "handle is not an RMPC handle" : "handle is not a PMPC handle");
+    if (!plant) return fail(h, DART_MPC_EINVAL, "null plant config");
+    if (!(plant->v_c > 0.0) || !(plant->mu_c >= 0.0)) return fail(h, DART_MPC_EINVAL, "plant config: v_c > 0, mu_c >= 0");
+    if (B < 0 || k < 0 || steps < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
+    if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
+    if ((long long)k + steps > log_rows) return fail(h, DART_MPC_EINVAL, "k0 + steps exceeds log_rows");
+    return DART_MPC_OK;
+}
+
+int rmpc_loop_cfg_check(dart_mpc_handle* h, const dart_rmpc_loop_config* c) {
+    if (!c) return fail(h, DART_MPC_EINVAL, "null loop config");
+    if (!(c->rls_lambda > 0.0) || !(c->dr_max >= 0.0) || !(c->step_fraction >= 0.0 && c->step_fraction <= 1.0))
+        return fail(h, DART_MPC_EINVAL, "loop config: rls_lambda > 0, dr_max >= 0, 0 <= step_fraction <= 1");
+    return DART_MPC_OK;
+}
+
+// the solve's per-step arrays of a rollout, in the handle (B_max instances)
+struct LoopScratch {
+    double *x0, *Rref, *phi, *y, *u0, *f;
+    int32_t *status, *iters;
+};
+
+int loop_scratch(dart_mpc_handle* h, LoopScratch& L) {
+    const size_t Bm = (size_t)h->cfg.B_max, N1 = (size_t)h->cfg.N + 1;
+    const bool rm = h->cfg.variant == DART_MPC_RMPC;
+    const size_t n_x0 = rm ? 4 : 6, n_R = rm ? 4 * N1 : 0, n_phi = rm ? 7 : 0, n_y = rm ? 2 : 0;
+    auto al = [](size_t n) { return (n + 255) & ~size_t(255); };
+    size_t off[9];
+    const size_t cnt[8] = {8 * n_x0, 8 * n_R, 8 * n_phi, 8 * n_y, 8 * 2, 8, 4, 4};
+    off[0] = 0;
+    for (int i = 0; i < 8; ++i) off[i + 1] = off[i] + al(cnt[i] * Bm);
+    // (no initialisation: pre writes what the solve reads, the solve writes what post reads)
+    if (!h->loop_buf) HIPCHK(h, hipMalloc((void**)&h->loop_buf, off[8]), "hipMalloc (rollout scratch)");
+    char* p = h->loop_buf;
+    L.x0 = (double*)(p + off[0]); L.Rref = (double*)(p + off[1]); L.phi = (double*)(p + off[2]);
+    L.y = (double*)(p + off[3]); L.u0 = (double*)(p + off[4]); L.f = (double*)(p + off[5]);
+    L.status = (int32_t*)(p + off[6]); L.iters = (int32_t*)(p + off[7]);
+    return DART_MPC_OK;
+}
+
+// device arena of the host rollout entries: arrays laid out 256-byte aligned, copied up / down in part
+struct RollArr {
+    void* host;
+    size_t bytes;         // whole array
+    size_t lo, n;         // the byte range that travels
+    bool up, down;
+    size_t off;
+};
+
+struct RollStage {
+    std::vector<RollArr> arr;
+    size_t total = 0;
+    // whole array, both ways (state) or up only (inputs)
+    int add(const void* host, size_t bytes, bool down) {
+        arr.push_back({const_cast<void*>(host), bytes, 0, bytes, true, down, total});
+        total += (bytes + 255) & ~size_t(255);
+        return (int)arr.size() - 1;
+    }
+    // a log: rows [r0, r1) of `rowbytes` each travel (up only where the call may leave entries of them untouched)
+    int add_log(void* host, size_t rows, size_t rowbytes, size_t r0, size_t r1, bool up) {
+        arr.push_back({host, rows * rowbytes, r0 * rowbytes, (r1 - r0) * rowbytes, up, true, total});
+        total += (rows * rowbytes + 255) & ~size_t(255);
+        return (int)arr.size() - 1;
+    }
+    template <class T> T* dev(const dart_mpc_handle* h, int i) const { return reinterpret_cast<T*>(h->roll_buf + arr[i].off); }
+    int reserve(dart_mpc_handle* h) {
+        if (total <= h->roll_cap) return DART_MPC_OK;
+        if (h->roll_buf) HIPCHK(h, hipFree(h->roll_buf), "hipFree (rollout arena)");
+        h->roll_buf = nullptr; h->roll_cap = 0;
+        HIPCHK(h, hipMalloc((void**)&h->roll_buf, total), "hipMalloc (rollout arena)");
+        h->roll_cap = total;
+        return DART_MPC_OK;
+    }
+    int upload(dart_mpc_handle* h, hipStream_t s) const {
+        for (const auto& a : arr)
+            if (a.up && a.n)
+                HIPCHK(h, hipMemcpyAsync(h->roll_buf + a.off + a.lo, (const char*)a.host + a.lo, a.n, hipMemcpyHostToDevice, s),
+                       "copy rollout state");
+        return DART_MPC_OK;
+    }
+    int download(dart_mpc_handle* h, hipStream_t s) const {
+        for (const auto& a : arr)
+            if (a.down && a.n)
+                HIPCHK(h, hipMemcpyAsync((char*)a.host + a.lo, h->roll_buf + a.off + a.lo, a.n, hipMemcpyDeviceToHost, s),
+                       "copy rollout logs");
+        return DART_MPC_OK;
+    }
+};
+
+}  // namespace
+
+int dart_rmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                            int B, int k, int do_post, int do_pre, int log_rows,
+                            const double* target, const double* prm, const double* mu,
+                            double* x, double* tilt, double* prev, double* u_prev, double* r_v, const double* theta,
+                            int32_t* done, int32_t* nlog,
+                            double* x0, double* Rref, double* phi, double* y,
+                            const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                            double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                            double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                            int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_RMPC, plant, B, k, do_post ? 1 : 0, log_rows)) return rc;
+    if (int rc = rmpc_loop_cfg_check(h, loop)) return rc;
+    if (any_null({target, prm, mu, x, tilt, prev, u_prev, r_v, theta, done, nlog, x0, Rref, phi, y, u0, f, status, iters,
+                  log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v, log_f, log_status,
+                  log_iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    dartmpc::RmpcLoopArgs a;
+    a.B = B; a.N = h->cfg.N; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+    a.plant = plant_args(h, plant);
+    a.Ts = h->cfg.Ts; a.dr_max = loop->dr_max; a.alpha_rg = loop->alpha_rg; a.step_fraction = loop->step_fraction;
+    a.pos_tol = loop->pos_tol;
+    a.target = target; a.prm = prm; a.mu = mu;
+    a.x = x; a.tilt = tilt; a.prev = prev; a.u_prev = u_prev; a.r_v = r_v; a.theta = theta; a.done = done; a.nlog = nlog;
+    a.x0 = x0; a.Rref = Rref; a.phi = phi; a.y = y; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
+    a.log_pos_err = log_pos_err; a.log_pos_err_norm = log_pos_err_norm; a.log_u_cmd = log_u_cmd;
+    a.log_timestep = log_timestep; a.log_x = log_x; a.log_theta = log_theta; a.log_r_v = log_r_v; a.log_f = log_f;
+    a.log_status = log_status; a.log_iters = log_iters;
+    HIPCHK(h, dartmpc_launch_rmpc_loop(&a, stream ? (hipStream_t)stream : h->stream), "loop-step kernel launch");
+    return DART_MPC_OK;
+}
+
+int dart_pmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                            int B, int k, int do_post, int do_pre, int log_rows, const double* prm,
+                            double* x, double* tilt, double* x0,
+                            const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                            double* log_X, double* log_U, double* log_quat, double* log_loss,
+                            int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_PMPC, plant, B, k, do_post ? 1 : 0, log_rows)) return rc;
+    if (any_null({prm, x, tilt, x0, u0, f, status, iters, log_X, log_U, log_quat, log_loss, log_status, log_iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    dartmpc::PmpcLoopArgs a;
+    a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+    a.plant = plant_args(h, plant);
+    a.prm = prm; a.x = x; a.tilt = tilt; a.x0 = x0; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
+    a.log_X = log_X; a.log_U = log_U; a.log_quat = log_quat; a.log_loss = log_loss; a.log_status = log_status;
+    a.log_iters = log_iters;
+    HIPCHK(h, dartmpc_launch_pmpc_loop(&a, stream ? (hipStream_t)stream : h->stream), "loop-step kernel launch");
+    return DART_MPC_OK;
+}
+
+int dart_rmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                          int B, int k0, int steps, int log_rows,
+                          const double* target, const double* prm, const double* mu,
+                          double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
+                          double* P, double* w, int32_t* done, int32_t* nlog,
+                          double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                          double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                          int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_RMPC, plant, B, k0, steps, log_rows)) return rc;
+    if (int rc = rmpc_loop_cfg_check(h, loop)) return rc;
+    if (any_null({target, prm, mu, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog, log_pos_err, log_pos_err_norm,
+                  log_u_cmd, log_timestep, log_x, log_theta, log_r_v, log_f, log_status, log_iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    LoopScratch L;
+    if (int rc = loop_scratch(h, L)) return rc;
+    void* s = stream ? stream : (void*)h->stream;
+    auto step = [&](int k, int post, int pre) {
+        return dart_rmpc_loop_step_dev(h, plant, loop, B, k, post, pre, log_rows, target, prm, mu, x, tilt, prev, u_prev,
+                                       r_v, theta, done, nlog, L.x0, L.Rref, L.phi, L.y, L.u0, L.f, L.status, L.iters,
+                                       log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v,
+                                       log_f, log_status, log_iters, s);
+    };
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        // warm start in place: every element of w's row is read (at the solve's start) and written (at its end)
+        // by the same wave, and an instance handed to the restoration kernel has not written its row
+        if (int rc = dart_rmpc_solve_batch_dev(h, B, L.x0, u_prev, theta, P, L.phi, L.y, loop->rls_lambda, L.Rref, prm, w,
+                                               L.u0, L.f, w, L.status, L.iters, s))
+            return rc;
+        if (int rc = step(k0 + j, 1, j + 1 < steps)) return rc;
+    }
+    return DART_MPC_OK;
+}
+
+int dart_pmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                          int B, int k0, int steps, int log_rows, const double* target, const double* prm,
+                          double* x, double* tilt,
+                          double* log_X, double* log_U, double* log_quat, double* log_loss,
+                          int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_PMPC, plant, B, k0, steps, log_rows)) return rc;
+    if (any_null({target, prm, x, tilt, log_X, log_U, log_quat, log_loss, log_status, log_iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    LoopScratch L;
+    if (int rc = loop_scratch(h, L)) return rc;
+    void* s = stream ? stream : (void*)h->stream;
+    auto step = [&](int k, int post, int pre) {
+        return dart_pmpc_loop_step_dev(h, plant, B, k, post, pre, log_rows, prm, x, tilt, L.x0, L.u0, L.f, L.status, L.iters,
+                                       log_X, log_U, log_quat, log_loss, log_status, log_iters, s);
+    };
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        if (int rc = dart_mpc_solve_batch_dev(h, B, L.x0, target, prm, nullptr, L.u0, L.f, nullptr, L.status, L.iters, s))
+            return rc;
+        if (int rc = step(k0 + j, 1, j + 1 < steps)) return rc;
+    }
+    return DART_MPC_OK;
+}
+
+int dart_rmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                      int B, int k0, int steps, int log_rows,
+                      const double* target, const double* prm, const double* mu,
+                      double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
+                      double* P, double* w, int32_t* done, int32_t* nlog,
+                      double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                      double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                      int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_RMPC, plant, B, k0, steps, log_rows)) return rc;
+    if (int rc = rmpc_loop_cfg_check(h, loop)) return rc;
+    if (any_null({target, prm, mu, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog, log_pos_err, log_pos_err_norm,
+                  log_u_cmd, log_timestep, log_x, log_theta, log_r_v, log_f, log_status, log_iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t), nw = (size_t)dart_rmpc_nw(h->cfg.N);
+    // episode rows: an instance writes rows nlog[b] .. nlog[b] + steps - 1 at most
+    int e0 = log_rows, e1 = 0;
+    for (int b = 0; b < B; ++b) {
+        if (nlog[b] < 0) return fail(h, DART_MPC_EINVAL, "negative nlog");
+        e0 = nlog[b] < e0 ? nlog[b] : e0;
+        e1 = nlog[b] > e1 ? nlog[b] : e1;
+    }
+    e1 = (long long)e1 + steps < log_rows ? e1 + steps : log_rows;
+    e0 = e0 < e1 ? e0 : e1;
+    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
+    RollStage S;
+    const int i_tg = S.add(target, 4 * nB * D, false), i_prm = S.add(prm, 10 * nB * D, false), i_mu = S.add(mu, nB * D, false);
+    const int i_x = S.add(x, 6 * nB * D, true), i_tilt = S.add(tilt, 2 * nB * D, true), i_prev = S.add(prev, 4 * nB * D, true);
+    const int i_up = S.add(u_prev, 2 * nB * D, true), i_rv = S.add(r_v, 4 * nB * D, true), i_th = S.add(theta, 14 * nB * D, true);
+    const int i_P = S.add(P, 98 * nB * D, true), i_w = S.add(w, nw * nB * D, true);
+    const int i_done = S.add(done, nB * I, true), i_nlog = S.add(nlog, nB * I, true);
+    const int l_pe = S.add_log(log_pos_err, R, 2 * nB * D, e0, e1, true), l_pn = S.add_log(log_pos_err_norm, R, nB * D, e0, e1, true);
+    const int l_uc = S.add_log(log_u_cmd, R, 2 * nB * D, e0, e1, true), l_ts = S.add_log(log_timestep, R, nB * D, e0, e1, true);
+    const int l_x = S.add_log(log_x, R, 4 * nB * D, r0, r1, false), l_th = S.add_log(log_theta, R, 14 * nB * D, r0, r1, false);
+    const int l_rv = S.add_log(log_r_v, R, 4 * nB * D, r0, r1, false), l_f = S.add_log(log_f, R, nB * D, r0, r1, false);
+    const int l_st = S.add_log(log_status, R, nB * I, r0, r1, false), l_it = S.add_log(log_iters, R, nB * I, r0, r1, false);
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    if (int rc = dart_rmpc_rollout_dev(
+            h, plant, loop, B, k0, steps, log_rows, S.dev<double>(h, i_tg), S.dev<double>(h, i_prm), S.dev<double>(h, i_mu),
+            S.dev<double>(h, i_x), S.dev<double>(h, i_tilt), S.dev<double>(h, i_prev), S.dev<double>(h, i_up),
+            S.dev<double>(h, i_rv), S.dev<double>(h, i_th), S.dev<double>(h, i_P), S.dev<double>(h, i_w),
+            S.dev<int32_t>(h, i_done), S.dev<int32_t>(h, i_nlog), S.dev<double>(h, l_pe), S.dev<double>(h, l_pn),
+            S.dev<double>(h, l_uc), S.dev<double>(h, l_ts), S.dev<double>(h, l_x), S.dev<double>(h, l_th),
+            S.dev<double>(h, l_rv), S.dev<double>(h, l_f), S.dev<int32_t>(h, l_st), S.dev<int32_t>(h, l_it), s))
+        return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+int dart_pmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant,
+                      int B, int k0, int steps, int log_rows, const double* target, const double* prm,
+                      double* x, double* tilt,
+                      double* log_X, double* log_U, double* log_quat, double* log_loss,
+                      int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_PMPC, plant, B, k0, steps, log_rows)) return rc;
+    if (any_null({target, prm, x, tilt, log_X, log_U, log_quat, log_loss, log_status, log_iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    if (int rc = settle_pending(h)) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t);
+    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
+    RollStage S;
+    const int i_tg = S.add(target, 6 * nB * D, false), i_prm = S.add(prm, 6 * nB * D, false);
+    const int i_x = S.add(x, 6 * nB * D, true), i_tilt = S.add(tilt, 2 * nB * D, true);
+    const int l_X = S.add_log(log_X, R, 6 * nB * D, r0, r1, false), l_U = S.add_log(log_U, R, 2 * nB * D, r0, r1, false);
+    const int l_Q = S.add_log(log_quat, R, 4 * nB * D, r0, r1, false), l_L = S.add_log(log_loss, R, nB * D, r0, r1, false);
+    const int l_st = S.add_log(log_status, R, nB * I, r0, r1, false), l_it = S.add_log(log_iters, R, nB * I, r0, r1, false);
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    if (int rc = dart_pmpc_rollout_dev(h, plant, B, k0, steps, log_rows, S.dev<double>(h, i_tg), S.dev<double>(h, i_prm),
+                                       S.dev<double>(h, i_x), S.dev<double>(h, i_tilt), S.dev<double>(h, l_X),
+                                       S.dev<double>(h, l_U), S.dev<double>(h, l_Q), S.dev<double>(h, l_L),
+                                       S.dev<int32_t>(h, l_st), S.dev<int32_t>(h, l_it), s))
+        return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
     return DART_MPC_OK;
 }

@@ -1,0 +1,82 @@
+// loop_step.h -- launch arguments of the closed-loop glue kernels (loop_step.hip): what the drivers do between
+// two solves (RMPC/dev_dual/rob_ctrl.py:331-416, PMPC/main_parallel_enhanced.py:290-419) and the tray plant of
+// dart_mpc/harness.py, so that a K-step rollout stays on one stream without the host.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace dartmpc {
+
+// harness.TrayPlant: first-order tilt lag, reference model + Coulomb friction, RK4 at dt
+struct PlantArgs {
+    double a_lag;       // 1 - exp(-dt / tau) (1 for tau <= 0)
+    double mu_c, v_c;   // Coulomb friction coefficient and its tanh velocity scale
+    double dt, g;
+};
+
+// One launch = post(k) and / or pre(next step) for B instances.  All arrays are device memory.
+struct RmpcLoopArgs {
+    int B, N;
+    int k;                      // step (log row) of the post half; timestep = k Ts
+    int do_post, do_pre;
+    int log_rows;
+    PlantArgs plant;
+    double Ts, dr_max, alpha_rg, step_fraction, pos_tol;
+    const double* target;       // [B][4]
+    const double* prm;          // [B][10] (v_eps = prm[9] scales the RLS features)
+    const double* mu;           // [B] viscous friction of the plant
+    // loop state, in/out
+    double* x;                  // [B][6]
+    double* tilt;               // [B][2]
+    double* prev;               // [B][4]
+    double* u_prev;             // [B][2]
+    double* r_v;                // [B][4]
+    const double* theta;        // [B][14] (updated by the solve's fused RLS; logged here)
+    int32_t* done;              // [B]
+    int32_t* nlog;              // [B] episode rows written so far
+    // the solve's per-step inputs (written by pre) and outputs (read by post)
+    double* x0;                 // [B][4]
+    double* Rref;               // [B][4(N+1)]
+    double* phi;                // [B][7]
+    double* y;                  // [B][2]
+    const double* u0;           // [B][2]
+    const double* f;            // [B]
+    const int32_t* status;      // [B]
+    const int32_t* iters;       // [B]
+    // logs [log_rows][B][...]: episode rows (index nlog[b], while !done[b]) and step rows (index k)
+    double* log_pos_err;        // [..][2]
+    double* log_pos_err_norm;   // [..]
+    double* log_u_cmd;          // [..][2]
+    double* log_timestep;       // [..]
+    double* log_x;              // [..][4]
+    double* log_theta;          // [..][14]
+    double* log_r_v;            // [..][4]
+    double* log_f;              // [..]
+    int32_t* log_status;        // [..]
+    int32_t* log_iters;         // [..]
+};
+
+struct PmpcLoopArgs {
+    int B;
+    int k, do_post, do_pre, log_rows;
+    PlantArgs plant;
+    const double* prm;          // [B][6] (mu = prm[0] is the plant's viscous friction)
+    double* x;                  // [B][6] in/out
+    double* tilt;               // [B][2] in/out
+    double* x0;                 // [B][6] the solve's input (written by pre)
+    const double* u0;           // [B][2]
+    const double* f;            // [B]
+    const int32_t* status;      // [B]
+    const int32_t* iters;       // [B]
+    double* log_X;              // [log_rows][B][6]
+    double* log_U;              // [..][2]
+    double* log_quat;           // [..][4]
+    double* log_loss;           // [..]
+    int32_t* log_status;        // [..]
+    int32_t* log_iters;         // [..]
+};
+
+}  // namespace dartmpc
+
+extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args, hipStream_t stream);

@@ -1,0 +1,180 @@
+// loop_step.hip -- the closed-loop glue between two solves, on the device.
+//
+// rmpc_loop_kernel: post(k) = the log rows, the episode end and the plant step of harness.run_rmpc; pre(k+1) =
+// the RLS features / targets, the reference governor and the staged reference of the next solve
+// (RMPC/dev_dual/rob_ctrl.py:335-351).  pmpc_loop_kernel: the same for harness.run_pmpc
+// (PMPC/main_parallel_enhanced.py:333-348: log, tilt -> quaternion, plant step, next state).
+//
+// One wave64 per instance, kLoopWaves instances per block; lane i owns horizon node i (the staged reference),
+// the per-instance scalars are computed by every lane and stored by one.  Plain fp64 in the operation order of
+// the numpy code (no contraction into fma), no LDS.  A lane only ever reads state that this launch does not
+// write, or keeps it in registers across the post and pre halves: nothing is read back from memory in a launch.
+#include "loop_step.h"
+
+#pragma clang fp contract(off)
+
+namespace dartmpc {
+
+constexpr int kLoopWave = 64;
+constexpr int kLoopWaves = 4;
+
+// harness.TrayPlant.step: x [6], tilt [2] in/out
+__host__ __device__ __forceinline__ void tray_plant_step(const PlantArgs& p, double mu, const double* u, double* x,
+                                                double* tilt) {
+    tilt[0] += p.a_lag * (u[0] - tilt[0]);
+    tilt[1] += p.a_lag * (u[1] - tilt[1]);
+    const double s0 = sin(tilt[0]), s1 = sin(tilt[1]);
+    const double fric = p.mu_c * fabs(p.g);
+    const double h = p.dt, h2 = h / 2, h6 = h / 6;
+    auto acc = [&](double s, double v) { return p.g * s - mu * v - fric * tanh(v / p.v_c); };
+    const double k1x = x[1], k1y = x[3];
+    const double a1x = acc(s0, k1x), a1y = acc(s1, k1y);
+    const double k2x = x[1] + h2 * a1x, k2y = x[3] + h2 * a1y;
+    const double a2x = acc(s0, k2x), a2y = acc(s1, k2y);
+    const double k3x = x[1] + h2 * a2x, k3y = x[3] + h2 * a2y;
+    const double a3x = acc(s0, k3x), a3y = acc(s1, k3y);
+    const double k4x = x[1] + h * a3x, k4y = x[3] + h * a3y;
+    const double a4x = acc(s0, k4x), a4y = acc(s1, k4y);
+    x[0] = x[0] + h6 * (k1x + 2 * k2x + 2 * k3x + k4x);
+    x[1] = x[1] + h6 * (a1x + 2 * a2x + 2 * a3x + a4x);
+    x[2] = x[2] + h6 * (k1y + 2 * k2y + 2 * k3y + k4y);
+    x[3] = x[3] + h6 * (a1y + 2 * a2y + 2 * a3y + a4y);
+    // (pz, vz: zero derivative)
+}
+
+__global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_loop_kernel(RmpcLoopArgs a) {
+    const int lane = threadIdx.x & (kLoopWave - 1);
+    const int b = blockIdx.x * kLoopWaves + (threadIdx.x >> 6);
+    if (b >= a.B) return;                    // wave-uniform
+    const size_t B = (size_t)a.B;
+    const double* tg = a.target + 4 * b;
+    const double t0 = tg[0], t2 = tg[2];
+    double x[6], tilt[2], prev[4], rv[4];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = a.x[6 * b + i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rv[i] = a.r_v[4 * b + i];
+
+    if (a.do_post) {
+        tilt[0] = a.tilt[2 * b]; tilt[1] = a.tilt[2 * b + 1];
+        const double u[2] = {a.u0[2 * b], a.u0[2 * b + 1]};
+        const size_t row = (size_t)a.k * B + b;
+        const double dx = x[0] - t0, dy = x[2] - t2;
+        const double en = sqrt(dx * dx + dy * dy);
+        if (lane < 14) a.log_theta[14 * row + lane] = a.theta[14 * b + lane];
+        if (lane == 0) {
+            const int nl = a.nlog[b];
+            if (!a.done[b]) {
+                if (nl >= 0 && nl < a.log_rows) {
+                    const size_t er = (size_t)nl * B + b;
+                    a.log_pos_err[2 * er] = t0 - x[0]; a.log_pos_err[2 * er + 1] = t2 - x[2];
+                    a.log_pos_err_norm[er] = en;
+                    a.log_u_cmd[2 * er] = u[0]; a.log_u_cmd[2 * er + 1] = u[1];
+                    a.log_timestep[er] = a.k * a.Ts;
+                }
+                a.nlog[b] = nl + 1;
+                if (en < a.pos_tol) a.done[b] = 1;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                a.log_x[4 * row + i] = x[i];
+                a.log_r_v[4 * row + i] = rv[i];
+                a.prev[4 * b + i] = x[i];
+            }
+            a.log_status[row] = a.status[b];
+            a.log_iters[row] = a.iters[b];
+            a.log_f[row] = a.f[b];
+            a.u_prev[2 * b] = u[0]; a.u_prev[2 * b + 1] = u[1];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) prev[i] = x[i];
+        tray_plant_step(a.plant, a.mu[b], u, x, tilt);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a.x[6 * b + i] = x[i];
+            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) prev[i] = a.prev[4 * b + i];
+    }
+
+    if (a.do_pre) {
+        const double veps = a.prm[10 * b + 9];
+        // reference governor (rob_ctrl.py:346-348) on the two position entries
+        rv[0] = rv[0] + a.alpha_rg * fmin(fmax(t0 - rv[0], -a.dr_max), a.dr_max);
+        rv[2] = rv[2] + a.alpha_rg * fmin(fmax(t2 - rv[2], -a.dr_max), a.dr_max);
+        if (lane <= a.N) {      // staged reference, node `lane` (np_mpc...:201-210)
+            const double wgt = 1.0 - pow(1.0 - a.step_fraction, (double)(lane + 1));
+            double* R = a.Rref + 4 * ((size_t)(a.N + 1) * b + lane);
+            R[0] = rv[0] + wgt * (t0 - rv[0]); R[1] = 0.0;
+            R[2] = rv[2] + wgt * (t2 - rv[2]); R[3] = 0.0;
+        }
+        if (lane == 0) {
+            a.r_v[4 * b] = rv[0]; a.r_v[4 * b + 2] = rv[2];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { a.x0[4 * b + i] = x[i]; a.phi[7 * b + i] = prev[i]; }
+            a.phi[7 * b + 4] = tanh(prev[1] / veps);
+            a.phi[7 * b + 5] = tanh(prev[3] / veps);
+            a.phi[7 * b + 6] = 1.0;
+            a.y[2 * b] = (x[1] - prev[1]) / a.Ts;
+            a.y[2 * b + 1] = (x[3] - prev[3]) / a.Ts;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_loop_kernel(PmpcLoopArgs a) {
+    const int lane = threadIdx.x & (kLoopWave - 1);
+    const int b = blockIdx.x * kLoopWaves + (threadIdx.x >> 6);
+    if (b >= a.B) return;                    // wave-uniform
+    double x[6], tilt[2];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = a.x[6 * b + i];
+
+    if (a.do_post) {
+        tilt[0] = a.tilt[2 * b]; tilt[1] = a.tilt[2 * b + 1];
+        const double u[2] = {a.u0[2 * b], a.u0[2 * b + 1]};
+        const size_t row = (size_t)a.k * a.B + b;
+        // pmpc.tilt_to_quat: Euler xyz [u1, -u0, 0] -> (w, x, y, z)
+        const double ax = u[1] / 2.0, ay = -u[0] / 2.0;
+        const double cx = cos(ax), cy = cos(ay), cz = 1.0, sx = sin(ax), sy = sin(ay), sz = 0.0;
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) a.log_X[6 * row + i] = x[i];
+            a.log_U[2 * row] = u[0]; a.log_U[2 * row + 1] = u[1];
+            a.log_quat[4 * row] = cx * cy * cz + sx * sy * sz;
+            a.log_quat[4 * row + 1] = sx * cy * cz - cx * sy * sz;
+            a.log_quat[4 * row + 2] = cx * sy * cz + sx * cy * sz;
+            a.log_quat[4 * row + 3] = cx * cy * sz - sx * sy * cz;
+            a.log_loss[row] = a.f[b];
+            a.log_status[row] = a.status[b];
+            a.log_iters[row] = a.iters[b];
+        }
+        tray_plant_step(a.plant, a.prm[6 * b], u, x, tilt);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a.x[6 * b + i] = x[i];
+            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
+        }
+    }
+    if (a.do_pre && lane < 6) a.x0[6 * b + lane] = x[lane];
+}
+
+}  // namespace dartmpc
+
+extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, hipStream_t stream) {
+    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
+    if (args->N < 1 || args->N > 63) return hipErrorInvalidValue;
+    const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
+    hipLaunchKernelGGL(dartmpc::rmpc_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0, stream,
+                       *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args, hipStream_t stream) {
+    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
+    const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
+    hipLaunchKernelGGL(dartmpc::pmpc_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0, stream,
+                       *args);
+    return hipGetLastError();
+}

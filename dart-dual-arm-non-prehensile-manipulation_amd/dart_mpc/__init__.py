@@ -12,10 +12,12 @@ Drop-in for the reference's MPC hot path:
                            Event process topology (rlmpc2.py:110-164, 229-533, 537-769, 986-1021)
   - ``ArmControl``, ``ArmSolver`` <- ARMCONTROL (PMPC/src/controller/arm.py), the per-arm impedance QP
   - ``harness``         <- the closed loops of main_parallel_enhanced.py / rob_ctrl.py without MuJoCo, and the
-                           reference's result formats (logger.py npz + metrics, rob_ctrl.py episode JSON)
+                           reference's result formats (logger.py npz + metrics, rob_ctrl.py episode JSON);
+                           ``harness.rollout_pmpc`` / ``rollout_rmpc`` run them resident on the device
   - ``Solver``, ``RmpcSolver``  the C ABI of include/dart_mpc.h (libdartmpc.so)
 """
 from ._lib import DartMPCError, LmpcSolver, RmpcSolver, Solver, build, lib, rls_update_batch, STATUS_NAMES  # noqa: F401
+from ._lib import plant_config, rmpc_loop_config  # noqa: F401
 from .pmpc import PMPC, tilt_to_quat  # noqa: F401
 from .worker import mpc_worker  # noqa: F401
 from .batch_server import mpc_batch_server  # noqa: F401
@@ -27,4 +29,4 @@ from .mjdata import BodyData  # noqa: F401
 from . import harness, workload  # noqa: F401
 
 __all__ = ["PMPC", "mpc_worker", "mpc_batch_server", "Solver", "RmpcSolver", "LmpcSolver", "RLMPC", "LmpcPolicy", "init_policy_weights", "policy_solve_batch", "RLMPCAsync", "lmpc_solver_worker", "lmpc_policy_worker", "ArmControl", "ArmSolver", "AdaptiveNPMPCSmooth", "RLS", "RMPCStep", "DartMPCError",
-           "build", "lib", "rls_update_batch", "tilt_to_quat", "workload", "harness", "BodyData"]
+           "build", "lib", "rls_update_batch", "plant_config", "rmpc_loop_config", "tilt_to_quat", "workload", "harness", "BodyData"]

@@ -40,7 +40,10 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_arm_config_default", "dart_arm_snapshot_len", "dart_arm_param_len", "dart_arm_solve_batch",
            "dart_arm_solve_batch_dev", "dart_set_device", "dart_mpc_serve_start", "dart_mpc_serve_stop",
            "dart_mpc_serve_running", "dart_mpc_bind", "dart_mpc_solve_bound", "dart_mpc_build_id",
-           "dart_mpc_build_flavor")
+           "dart_mpc_build_flavor",
+           "dart_plant_config_default", "dart_rmpc_loop_config_default", "dart_rmpc_loop_step_dev",
+           "dart_pmpc_loop_step_dev", "dart_rmpc_rollout_dev", "dart_pmpc_rollout_dev", "dart_rmpc_rollout",
+           "dart_pmpc_rollout")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -58,6 +61,34 @@ class Config(ctypes.Structure):
                 ("restoration", ctypes.c_int32), ("constr_mult_init_max", ctypes.c_double),
                 ("max_cpu_time", ctypes.c_double)]
 
+
+class PlantConfig(ctypes.Structure):
+    """Mirror of ``struct dart_plant_config`` (the tray plant of the closed-loop rollouts)."""
+    _fields_ = [("tau", ctypes.c_double), ("mu_c", ctypes.c_double), ("v_c", ctypes.c_double)]
+
+
+class RmpcLoopConfig(ctypes.Structure):
+    """Mirror of ``struct dart_rmpc_loop_config`` (governor, staged reference, RLS, episode tolerance)."""
+    _fields_ = [("dr_max", ctypes.c_double), ("alpha_rg", ctypes.c_double), ("step_fraction", ctypes.c_double),
+                ("rls_lambda", ctypes.c_double), ("pos_tol", ctypes.c_double)]
+
+
+# Arrays of the closed-loop rollouts in the argument order of include/dart_mpc.h: (name, row width, dtype);
+# width 0 = one scalar per instance, "nw" = the solver's w.  State arrays are [B, width], logs [rows, B, width].
+RMPC_LOOP_STATE = (("x", 6, np.float64), ("tilt", 2, np.float64), ("prev", 4, np.float64), ("u_prev", 2, np.float64),
+                   ("r_v", 4, np.float64), ("theta", 14, np.float64), ("P", 98, np.float64), ("w", "nw", np.float64),
+                   ("done", 0, np.int32), ("nlog", 0, np.int32))
+RMPC_LOOP_IO = (("x0", 4, np.float64), ("Rref", "nref", np.float64), ("phi", 7, np.float64), ("y", 2, np.float64),
+                ("u0", 2, np.float64), ("f", 0, np.float64), ("status", 0, np.int32), ("iters", 0, np.int32))
+RMPC_LOOP_LOGS = (("pos_err", 2, np.float64), ("pos_err_norm", 0, np.float64), ("u_cmd", 2, np.float64),
+                  ("timestep", 0, np.float64), ("x", 4, np.float64), ("theta", 14, np.float64), ("r_v", 4, np.float64),
+                  ("f", 0, np.float64), ("status", 0, np.int32), ("iters", 0, np.int32))
+PMPC_LOOP_STATE = (("x", 6, np.float64), ("tilt", 2, np.float64))
+PMPC_LOOP_IO = (("x0", 6, np.float64), ("u0", 2, np.float64), ("f", 0, np.float64), ("status", 0, np.int32),
+                ("iters", 0, np.int32))
+PMPC_LOOP_LOGS = (("X", 6, np.float64), ("U_cmd", 2, np.float64), ("quat_tray", 4, np.float64), ("loss", 0, np.float64),
+                  ("status", 0, np.int32), ("iters", 0, np.int32))
+LOG_INT_FILL = int(np.iinfo(np.int32).min)      # prefill of the int32 logs (the float logs are prefilled with NaN)
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -184,6 +215,21 @@ def lib():
     L.dart_arm_solve_batch_dev.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6
     L.dart_arm_solve_batch_dev.restype = ctypes.c_int
+    if hasattr(L, "dart_rmpc_rollout_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_plant_config_default.argtypes = [ctypes.POINTER(PlantConfig)]
+        L.dart_plant_config_default.restype = None
+        L.dart_rmpc_loop_config_default.argtypes = [ctypes.POINTER(RmpcLoopConfig)]
+        L.dart_rmpc_loop_config_default.restype = None
+        L.dart_rmpc_loop_step_dev.argtypes = [vp, vp, vp] + [ci] * 5 + [vp] * 30
+        L.dart_pmpc_loop_step_dev.argtypes = [vp, vp] + [ci] * 5 + [vp] * 15
+        for fn in (L.dart_rmpc_rollout_dev, L.dart_rmpc_rollout):
+            fn.argtypes = [vp, vp, vp] + [ci] * 4 + [vp] * 24
+        for fn in (L.dart_pmpc_rollout_dev, L.dart_pmpc_rollout):
+            fn.argtypes = [vp, vp] + [ci] * 4 + [vp] * 11
+        for fn in (L.dart_rmpc_loop_step_dev, L.dart_pmpc_loop_step_dev, L.dart_rmpc_rollout_dev,
+                   L.dart_pmpc_rollout_dev, L.dart_rmpc_rollout, L.dart_pmpc_rollout):
+            fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):         # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
         L.dart_mpc_bind.restype = ctypes.c_int
@@ -235,6 +281,57 @@ def default_config(**over) -> Config:
 
 def _ptr(a):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def _set_fields(c, over):
+    names = [f[0] for f in c._fields_]
+    for k, v in over.items():
+        if k not in names:
+            raise DartMPCError(f"{type(c).__name__} has no field {k!r} (fields: {names})")
+        setattr(c, k, float(v))
+    return c
+
+
+def plant_config(**over) -> PlantConfig:
+    """``dart_plant_config`` with the library's defaults (harness.TrayPlant's), fields overridden by keyword."""
+    c = PlantConfig()
+    lib().dart_plant_config_default(ctypes.byref(c))
+    return _set_fields(c, over)
+
+
+def rmpc_loop_config(**over) -> RmpcLoopConfig:
+    """``dart_rmpc_loop_config`` with the library's defaults (harness.run_rmpc's), fields overridden by keyword."""
+    c = RmpcLoopConfig()
+    lib().dart_rmpc_loop_config_default(ctypes.byref(c))
+    return _set_fields(c, over)
+
+
+def _loop_shape(B, width, **sizes):
+    width = sizes[width] if isinstance(width, str) else width
+    return (B, width) if width else (B,)
+
+
+def loop_logs(spec, rows, B):
+    """Host log arrays of a rollout, [rows, B, width] each: NaN (float) / LOG_INT_FILL (int32) prefilled."""
+    return {name: np.full((rows,) + _loop_shape(B, width), np.nan if dt is np.float64 else LOG_INT_FILL, dt)
+            for name, width, dt in spec}
+
+
+def _dev_ptrs(spec, arrays):
+    """Device pointers (ints) of ``arrays`` (a mapping name -> int) in the order of ``spec``."""
+    return [ctypes.c_void_p(int(arrays[name])) for name, _, _ in spec]
+
+
+def _host_ptrs(spec, arrays, lead, **sizes):
+    """Pointers of the numpy arrays of ``arrays`` in the order of ``spec``, shapes and dtypes checked."""
+    out = []
+    for name, width, dt in spec:
+        a = arrays[name]
+        shape = tuple(lead[:-1]) + _loop_shape(lead[-1], width, **sizes)
+        if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+            raise DartMPCError(f"rollout array {name!r} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+        out.append(_ptr(a))
+    return out
 
 
 # Handles still open at interpreter exit are destroyed by an atexit hook, before the HIP runtime's own teardown:
@@ -371,6 +468,41 @@ class Solver:
         if rc != 0:
             self._err(rc, "dart_mpc_solve_batch_dev")
 
+    # -- device-resident closed loop (dart_pmpc_loop_step_dev / dart_pmpc_rollout_dev / dart_pmpc_rollout) ----
+    def loop_step_dev(self, B, k, do_post, do_pre, log_rows, prm, state, io, logs, plant=None, stream=0):
+        """One loop-step launch: post(k) and / or the next step's pre.  ``state`` / ``io`` / ``logs`` map the names
+        of PMPC_LOOP_STATE / PMPC_LOOP_IO / PMPC_LOOP_LOGS to device pointers (ints).  Asynchronous."""
+        plant = plant or plant_config()
+        rc = lib().dart_pmpc_loop_step_dev(self._h, ctypes.byref(plant), int(B), int(k), int(do_post), int(do_pre),
+                                           int(log_rows), prm, *_dev_ptrs(PMPC_LOOP_STATE, state),
+                                           *_dev_ptrs(PMPC_LOOP_IO, io), *_dev_ptrs(PMPC_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_pmpc_loop_step_dev")
+
+    def rollout_dev(self, B, k0, steps, log_rows, target, prm, state, logs, plant=None, stream=0):
+        """``steps`` closed-loop steps from step ``k0`` on the device, no host synchronisation in between
+        (device pointers as in ``loop_step_dev``; asynchronous on ``stream``)."""
+        plant = plant or plant_config()
+        rc = lib().dart_pmpc_rollout_dev(self._h, ctypes.byref(plant), int(B), int(k0), int(steps), int(log_rows),
+                                         target, prm, *_dev_ptrs(PMPC_LOOP_STATE, state),
+                                         *_dev_ptrs(PMPC_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_pmpc_rollout_dev")
+
+    def rollout(self, k0, steps, target, prm, state, logs, plant=None):
+        """Host arrays (blocking): ``state`` (PMPC_LOOP_STATE) is advanced and ``logs`` (``loop_logs``) rows
+        k0 .. k0+steps-1 are filled in place."""
+        x = state["x"]
+        B, rows = x.shape[0], logs["X"].shape[0]
+        c = lambda a: np.ascontiguousarray(a, np.float64).reshape(B, 6)
+        target, prm = c(target), c(prm)
+        plant = plant or plant_config()
+        rc = lib().dart_pmpc_rollout(self._h, ctypes.byref(plant), B, int(k0), int(steps), rows, _ptr(target), _ptr(prm),
+                                     *_host_ptrs(PMPC_LOOP_STATE, state, (B,)),
+                                     *_host_ptrs(PMPC_LOOP_LOGS, logs, (rows, B)), None)
+        if rc != 0:
+            self._err(rc, "dart_pmpc_rollout")
+
     def sync(self):
         rc = lib().dart_mpc_sync(self._h)
         if rc != 0:
@@ -499,6 +631,56 @@ class RmpcSolver(Solver):
                                              w_out or None, status, iters, stream or None)
         if rc != 0:
             self._err(rc, "dart_rmpc_solve_batch_dev")
+
+    # -- device-resident closed loop (dart_rmpc_loop_step_dev / dart_rmpc_rollout_dev / dart_rmpc_rollout) ----
+    def loop_step_dev(self, B, k, do_post, do_pre, log_rows, target, prm, mu, state, io, logs, plant=None, loop=None,
+                      stream=0):
+        """One loop-step launch: post(k) and / or the next step's pre.  ``state`` / ``io`` / ``logs`` map the names
+        of RMPC_LOOP_STATE (P and w are not needed) / RMPC_LOOP_IO / RMPC_LOOP_LOGS to device pointers (ints)."""
+        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
+        spec = tuple(e for e in RMPC_LOOP_STATE if e[0] not in ("P", "w"))
+        rc = lib().dart_rmpc_loop_step_dev(self._h, ctypes.byref(plant), ctypes.byref(loop), int(B), int(k), int(do_post),
+                                           int(do_pre), int(log_rows), target, prm, mu, *_dev_ptrs(spec, state),
+                                           *_dev_ptrs(RMPC_LOOP_IO, io), *_dev_ptrs(RMPC_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_rmpc_loop_step_dev")
+
+    def rollout_dev(self, B, k0, steps, log_rows, target, prm, mu, state, logs, plant=None, loop=None, stream=0):
+        """``steps`` closed-loop steps from step ``k0`` on the device, no host synchronisation in between: RLS
+        features, governor, staged reference, warm-started solve with the fused RLS update, logs, plant step
+        (device pointers as in ``loop_step_dev``; asynchronous on ``stream``).  Calling again with ``k0`` advanced
+        continues the rollout."""
+        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
+        rc = lib().dart_rmpc_rollout_dev(self._h, ctypes.byref(plant), ctypes.byref(loop), int(B), int(k0), int(steps),
+                                         int(log_rows), target, prm, mu, *_dev_ptrs(RMPC_LOOP_STATE, state),
+                                         *_dev_ptrs(RMPC_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_rmpc_rollout_dev")
+
+    def rollout(self, k0, steps, target, prm, mu, state, logs, plant=None, loop=None):
+        """Host arrays (blocking): ``state`` (RMPC_LOOP_STATE, see ``loop_state``) is advanced and ``logs``
+        (``loop_logs``) are filled in place."""
+        B, rows = state["x"].shape[0], logs["x"].shape[0]
+        target = np.ascontiguousarray(target, np.float64).reshape(B, 4)
+        prm = np.ascontiguousarray(prm, np.float64).reshape(B, 10)
+        mu = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, np.float64), (B,)))
+        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
+        rc = lib().dart_rmpc_rollout(self._h, ctypes.byref(plant), ctypes.byref(loop), B, int(k0), int(steps), rows,
+                                     _ptr(target), _ptr(prm), _ptr(mu),
+                                     *_host_ptrs(RMPC_LOOP_STATE, state, (B,), nw=self.nw),
+                                     *_host_ptrs(RMPC_LOOP_LOGS, logs, (rows, B)), None)
+        if rc != 0:
+            self._err(rc, "dart_rmpc_rollout")
+
+    def loop_state(self, x0, P0=1e3):
+        """The state of a fresh rollout from the measured states ``x0`` [B, 4] (run_rmpc's initial values)."""
+        x0 = np.asarray(x0, np.float64).reshape(-1, 4)
+        B = x0.shape[0]
+        st = {name: np.zeros(_loop_shape(B, width, nw=self.nw), dt) for name, width, dt in RMPC_LOOP_STATE}
+        st["x"][:, :4] = x0
+        st["prev"][:] = x0
+        st["P"][:] = np.tile(np.eye(7) * float(P0), (2, 1, 1)).reshape(98)
+        return st
 
 
 LMPC_PRM_DEFAULT = np.array([200.0, 2.0, 200.0, 2.0, 0.0, 0.0, 0.0, 0.0,     # Q   LMPC/src/run.py:118

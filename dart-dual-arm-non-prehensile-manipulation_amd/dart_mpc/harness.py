@@ -225,3 +225,94 @@ def run_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=None, 
                     logs[b]["timestep"])
         episodes.append(eps)
     return episodes, ST[:k + 1], done
+
+
+# ---------------------------------------------------------------------------------------------
+# the same closed loops, resident on the device (dart_pmpc_rollout / dart_rmpc_rollout): per step one loop-step
+# kernel and the solve, on one stream, no host round trip; the logs come back with one download per call
+def rollout_pmpc(states0, targets, prm, steps: int, N: int = 20, Ts: float = 0.002, tol: float = 1e-8, device: int = 0,
+                 plant_kw: dict | None = None, return_logs: bool = False):
+    """``run_pmpc`` on the device: same arguments, same return values (AsyncLogger log dicts with metrics, statuses
+    [steps, B]).  ``solve_time`` is the rollout's wall time divided by the steps run.  ``return_logs``: also
+    return dict(iters [steps, B], solve_time)."""
+    from ._lib import PMPC_LOOP_STATE, PMPC_LOOP_LOGS, loop_logs, plant_config
+    states0 = np.asarray(states0, float).reshape(-1, 6)
+    B = states0.shape[0]
+    targets = np.asarray(targets, float).reshape(B, 6)
+    prm = np.asarray(prm, float).reshape(B, 6)
+    plant = plant_config(**{k: v for k, v in (plant_kw or {}).items()})
+    state = {"x": states0.copy(), "tilt": np.zeros((B, 2))}
+    assert set(state) == {n for n, _, _ in PMPC_LOOP_STATE}
+    lg = loop_logs(PMPC_LOOP_LOGS, steps, B)
+    solver = Solver(N=N, Ts=Ts, tol=tol, B_max=max(B, 1), device=device)
+    try:
+        t0 = time.perf_counter()
+        solver.rollout(0, steps, targets, prm, state, lg)
+        wall = time.perf_counter() - t0
+    finally:
+        solver.close()
+    t = np.arange(steps) * Ts
+    TS = np.full(steps, wall / max(steps, 1))
+    logs = []
+    for b in range(B):
+        d = {"t": t, "X": lg["X"][:, b], "X_target": np.tile(targets[b], (steps, 1)), "U_cmd": lg["U_cmd"][:, b],
+             "quat_tray": lg["quat_tray"][:, b], "loss": lg["loss"][:, b], "solve_time": TS.copy()}
+        for key, w in (("torques", 7), ("qpos", 7), ("qvel", 7), ("ee_pos", 3), ("ee_vel", 6)):
+            d["L_" + key] = np.zeros((steps, w))       # arms are not simulated here
+            d["R_" + key] = np.zeros((steps, w))
+        d.update(logger_metrics(d, Ts))
+        logs.append(d)
+    if return_logs:
+        return logs, lg["status"], {"iters": lg["iters"], "solve_time": wall / max(steps, 1)}
+    return logs, lg["status"]
+
+
+def rollout_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=None, device: int = 0,
+                 pos_tol: float = ERROR_THRESHOLD, plant_kw: dict | None = None, mu=0.1, dr_max: float = 0.01,
+                 alpha_rg: float = 0.5, lam: float = 0.995, P0: float = 1e3, check_every: int = 0,
+                 return_logs: bool = False):
+    """``run_rmpc`` on the device: same arguments, same return values (episodes per experiment in the rob_ctrl.py
+    JSON layout, statuses [steps run, B], done).  ``check_every`` > 0 runs the rollout in chunks of that many steps
+    and stops once every experiment's episode has closed (the state stays valid between calls); 0 runs all
+    ``steps`` in one call.  ``return_logs``: also return the per-step device logs (x, theta, r_v, f, status,
+    iters [steps run, B, ...]), the episode rows, the final loop state and ``solve_time``."""
+    from ._lib import RMPC_LOOP_LOGS, loop_logs, plant_config, rmpc_loop_config
+    x0 = np.asarray(x0, float).reshape(-1, 4)
+    B = x0.shape[0]
+    targets = np.asarray(targets, float).reshape(B, 4)
+    ctl = AdaptiveNPMPCSmooth(None, None, Ts=Ts, N=N, Qp=80.0, Qv=2.0, Ru=0.02, Rdu=1.0, u_bounds=(-0.6, 0.6),
+                              du_bounds=(-0.06, 0.06), vmax=0.2, v_eps=0.1)          # rob_ctrl.py:280-283
+    prm = np.tile(ctl.params(), (B, 1)) if prm is None else np.asarray(prm, float).reshape(B, 10)
+    plant = plant_config(**{k: v for k, v in (plant_kw or {}).items()})
+    loop = rmpc_loop_config(dr_max=dr_max, alpha_rg=alpha_rg, rls_lambda=lam, pos_tol=pos_tol)
+    lg = loop_logs(RMPC_LOOP_LOGS, steps, B)
+    solver = RmpcSolver(N=N, Ts=Ts, B_max=max(B, 1), device=device)
+    chunk = int(check_every) if check_every and check_every > 0 else max(steps, 1)
+    k = 0
+    try:
+        state = solver.loop_state(x0, P0)
+        t0 = time.perf_counter()
+        while k < steps:
+            n = min(chunk, steps - k)
+            solver.rollout(k, n, targets, prm, mu, state, lg, plant=plant, loop=loop)
+            k += n
+            if state["done"].all():
+                break
+        wall = time.perf_counter() - t0
+    finally:
+        solver.close()
+    done = state["done"].astype(bool)
+    episodes = []
+    for b in range(B):
+        n = int(state["nlog"][b])
+        eps = {}
+        add_episode(eps, "ep1", lg["pos_err"][:n, b].tolist(), lg["pos_err_norm"][:n, b].tolist(),
+                    list(lg["u_cmd"][:n, b]), [np.zeros(14) for _ in range(n)],      # arms are not simulated here
+                    lg["timestep"][:n, b].tolist())
+        episodes.append(eps)
+    if return_logs:
+        extra = {name: lg[name][:k] for name in ("x", "theta", "r_v", "f", "status", "iters")}
+        extra.update(state=state, solve_time=wall / max(k, 1),
+                     episode_rows={name: lg[name] for name in ("pos_err", "pos_err_norm", "u_cmd", "timestep")})
+        return episodes, lg["status"][:k], done, extra
+    return episodes, lg["status"][:k], done

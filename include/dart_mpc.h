@@ -372,6 +372,103 @@ int dart_arm_solve_batch_dev(const dart_arm_config *cfg, int B, int n, const dou
 int dart_arm_solve_batch(const dart_arm_config *cfg, int B, int n, const double *snap, const double *prm,
                          int prm_stride, double *qdd, double *tau, double *loss, int32_t *status, int32_t *iters);
 
+/* Device-resident closed-loop rollouts (added within ABI 8: new entries only, nothing existing changes).
+ * A K-step closed loop of B experiments on one stream with no host synchronisation between the steps: per step
+ * one loop-step kernel (csrc/loop_step.hip) and the unchanged solve.  They do what the drivers do around a
+ * solve -- RMPC/dev_dual/rob_ctrl.py:331-416 (RLS features and targets, reference governor, staged reference
+ * np_mpc...:201-210, episode log, stop at the position tolerance) and the PMPC worker loop
+ * PMPC/main_parallel_enhanced.py:290-419 (log, tilt -> quaternion :333-348) -- with the batched tray plant of
+ * dart_mpc/harness.py (first-order tilt lag, the reference model plus Coulomb friction, RK4 at Ts) in place of
+ * MuJoCo.  The launch sequence of a call is
+ *     pre(k0), [solve, post(k) + pre(k+1)] for k = k0 .. k0+steps-2, solve, post(k0+steps-1)
+ * The loop state is caller-owned device memory, in/out, so a rollout is continued by calling again with
+ * k0 advanced; two calls of K1 and K2 steps give bit for bit what one call of K1 + K2 steps gives.
+ *
+ * RMPC state: x [B][6] plant state [px vx py vy pz vz], tilt [B][2], prev [B][4] (the previous measured state),
+ *   u_prev [B][2], r_v [B][4] (governor), theta [B][14], P [B][2][7][7] (RLS), w [B][nw] (warm start: read and
+ *   rewritten in place by every solve), done [B], nlog [B] (int32: episode closed; episode rows logged).
+ *   A fresh rollout starts from x = [x0, 0, 0], prev = x0, P = P0 I and zeros elsewhere.
+ * RMPC logs, [log_rows][B][...]: episode rows at index nlog[b], written while !done[b] (rob_ctrl.py:64-76):
+ *   pos_err [2], pos_err_norm, u_cmd [2], timestep = k Ts; step rows at index k, always written: x [4] (the
+ *   solve's x0), theta [14] (after the step's RLS update), r_v [4], f, status, iters (int32).
+ * PMPC state: x [B][6], tilt [B][2]; logs at row k: X [6], U_cmd [2], quat_tray [4], loss, status, iters.
+ * Rows that a call does not write keep their contents.  target / prm as in the solve entries; mu [B] is the
+ * plant's viscous friction (PMPC: prm[0]); RMPC's feature scale v_eps is prm[9]. */
+typedef struct dart_plant_config {
+    double tau;     /* tilt lag time constant [s], 0.03; <= 0: the tilt follows the command at once */
+    double mu_c;    /* Coulomb friction coefficient the MPC model does not have, 0.02 */
+    double v_c;     /* its tanh velocity scale [m/s], 0.01 */
+} dart_plant_config;
+
+typedef struct dart_rmpc_loop_config {
+    double dr_max;          /* governor step clip, 0.01 (rob_ctrl.py:346-348) */
+    double alpha_rg;        /* governor gain, 0.5 */
+    double step_fraction;   /* staged reference, 0.2 (rob_ctrl.py:351) */
+    double rls_lambda;      /* RLS forgetting factor, 0.995 */
+    double pos_tol;         /* episode ends below this position error [m], 0.01 (rob_ctrl.py:323) */
+} dart_rmpc_loop_config;
+
+void dart_plant_config_default(dart_plant_config *cfg);
+void dart_rmpc_loop_config_default(dart_rmpc_loop_config *cfg);
+
+/* One loop-step launch (for callers that sequence their own loop): post(k) if do_post, then pre of the next
+ * step if do_pre.  The solve's per-step arrays are the caller's: pre writes x0 [B][4], Rref [B][4(N+1)],
+ * phi [B][7], y [B][2]; post reads u0 [B][2], f, status, iters [B].  Device pointers, asynchronous. */
+int dart_rmpc_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                            int B, int k, int do_post, int do_pre, int log_rows,
+                            const double *target, const double *prm, const double *mu,
+                            double *x, double *tilt, double *prev, double *u_prev, double *r_v, const double *theta,
+                            int32_t *done, int32_t *nlog,
+                            double *x0, double *Rref, double *phi, double *y,
+                            const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                            double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                            double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                            int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+int dart_pmpc_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                            int B, int k, int do_post, int do_pre, int log_rows, const double *prm,
+                            double *x, double *tilt, double *x0,
+                            const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                            double *log_X, double *log_U, double *log_quat, double *log_loss,
+                            int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+/* `steps` closed-loop steps k0 .. k0+steps-1 (k0 + steps <= log_rows); steps = 0 does nothing.  Device
+ * pointers, asynchronous on hip_stream (NULL = the handle's own).  The solve's per-step arrays live in the
+ * handle (B <= B_max).  The RMPC solves are warm-started from w and fuse the RLS update; the PMPC solves are
+ * cold-started, as in the reference. */
+int dart_rmpc_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                          int B, int k0, int steps, int log_rows,
+                          const double *target, const double *prm, const double *mu,
+                          double *x, double *tilt, double *prev, double *u_prev, double *r_v, double *theta,
+                          double *P, double *w, int32_t *done, int32_t *nlog,
+                          double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                          double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                          int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+int dart_pmpc_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                          int B, int k0, int steps, int log_rows, const double *target, const double *prm,
+                          double *x, double *tilt,
+                          double *log_X, double *log_U, double *log_quat, double *log_loss,
+                          int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+/* Host pointers: state and logs are staged through device memory; blocks until they are back.  Of the logs
+ * only the rows the call can write travel (the step rows k0 .. k0+steps-1, the episode rows from the smallest
+ * nlog on). */
+int dart_rmpc_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                      int B, int k0, int steps, int log_rows,
+                      const double *target, const double *prm, const double *mu,
+                      double *x, double *tilt, double *prev, double *u_prev, double *r_v, double *theta,
+                      double *P, double *w, int32_t *done, int32_t *nlog,
+                      double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                      double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                      int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+int dart_pmpc_rollout(dart_mpc_handle *h, const dart_plant_config *plant,
+                      int B, int k0, int steps, int log_rows, const double *target, const double *prm,
+                      double *x, double *tilt,
+                      double *log_X, double *log_U, double *log_quat, double *log_loss,
+                      int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
 int dart_mpc_sync(dart_mpc_handle *h);
 
 const char *dart_mpc_last_error(const dart_mpc_handle *h);

@@ -1,0 +1,488 @@
+"""Device-resident closed-loop rollouts (csrc/loop_step.hip, dart_*_loop_step_dev / dart_*_rollout*).
+
+Bars:
+  * one loop step against the numpy code it restates (harness.TrayPlant.step, rmpc.rls_features, the governor,
+    build_ref_traj, pmpc.tilt_to_quat): absolute 1e-13.  Every quantity is at most 1 in magnitude and fewer than
+    ~20 fp64 operations plus one transcendental from its inputs, i.e. a few ulp ~ 2e-15; the factor 50 covers libm
+    against device math.  The kernel keeps numpy's operation order (no fma contraction);
+  * rollout against the same launches issued one by one, and a rollout continued by a second call: bit for bit;
+  * per-step parity with the oracle chain: the bars of test_gpu_rmpc.py's closed-loop tests (theta rtol 1e-9,
+    r_v 1e-15, same status, |du0| <= 1e-6); PMPC |dU_cmd| <= 1e-6 as test_gpu_harness.py.
+"""
+import json
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib
+import rmpc_nlp
+
+pytestmark = pytest.mark.gpu
+
+TS = 0.002
+RMPC_PRM = np.array([80.0, 2.0, 0.02, 1.0, -0.6, 0.6, -0.06, 0.06, 0.2, 0.1])       # rob_ctrl.py:280-283
+
+
+@pytest.fixture(scope="module")
+def L():
+    from dart_mpc import _lib
+    return _lib
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch
+    return torch
+
+
+@pytest.fixture(scope="module")
+def rmpc_solvers(L):
+    """One handle per horizon (B_max 67), shared by the tests of this module."""
+    made = {}
+
+    def get(N):
+        if N not in made:
+            made[N] = L.RmpcSolver(N=N, Ts=TS, B_max=67)
+        return made[N]
+    yield get
+    for s in made.values():
+        s.close()
+
+
+@pytest.fixture(scope="module")
+def pmpc_solver(L):
+    s = L.Solver(N=20, Ts=TS, B_max=67)
+    yield s
+    s.close()
+
+
+def _to_dev(torch, arrays):
+    d = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in arrays.items()}
+    torch.cuda.synchronize()
+    return d
+
+
+def _ptrs(d):
+    return {k: v.data_ptr() for k, v in d.items()}
+
+
+def _host(d):
+    return {k: v.cpu().numpy() for k, v in d.items()}
+
+
+def _same(torch, a, b):
+    """Bit-for-bit equality (NaN prefill included)."""
+    if a.dtype == torch.float64:
+        return torch.equal(a.view(torch.int64), b.view(torch.int64))
+    return torch.equal(a, b)
+
+
+def _shape(B, width, **sizes):
+    width = sizes[width] if isinstance(width, str) else width
+    return (B, width) if width else (B,)
+
+
+def _nan_io(L, spec, B, **sizes):
+    return {n: (np.full(_shape(B, w, **sizes), np.nan) if dt is np.float64 else np.full(B, L.LOG_INT_FILL, np.int32))
+            for n, w, dt in spec}
+
+
+def _close(got, want, what):
+    """|got - want| <= 1e-13 with the NaN prefill in the same places (floats); equality (ints)."""
+    for k in want:
+        if want[k].dtype == np.float64:
+            np.testing.assert_allclose(got[k], want[k], rtol=0, atol=1e-13, equal_nan=True, err_msg=f"{what}: {k}")
+        else:
+            np.testing.assert_array_equal(got[k], want[k], err_msg=f"{what}: {k}")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Test 1: one loop-step launch against numpy
+def _rmpc_case(L, rng, B, N):
+    x = np.zeros((B, 6)); x[:, :4] = rng.uniform(-0.3, 0.3, (B, 4)); x[:, 4] = 0.43
+    state = dict(x=x, tilt=rng.uniform(-0.3, 0.3, (B, 2)), prev=x[:, :4] + rng.uniform(-1e-3, 1e-3, (B, 4)),
+                 u_prev=rng.uniform(-0.5, 0.5, (B, 2)), r_v=rng.uniform(-0.1, 0.1, (B, 4)),
+                 theta=rng.uniform(-1, 1, (B, 14)), done=(rng.uniform(size=B) < 0.3).astype(np.int32),
+                 nlog=rng.integers(0, 3, B).astype(np.int32))
+    target = np.zeros((B, 4)); target[:, [0, 2]] = rng.uniform(-0.1, 0.1, (B, 2))
+    near = np.arange(B) % 4 == 1            # within the tolerance: the episode closes at this step
+    target[near, 0] = x[near, 0] + 1e-3; target[near, 2] = x[near, 2] - 2e-3
+    io = _nan_io(L, L.RMPC_LOOP_IO, B, nref=4 * (N + 1))
+    io.update(u0=rng.uniform(-0.5, 0.5, (B, 2)), f=rng.uniform(0, 1, B), status=rng.integers(-2, 3, B).astype(np.int32),
+              iters=rng.integers(1, 60, B).astype(np.int32))
+    return state, target, np.tile(RMPC_PRM, (B, 1)), rng.uniform(0.05, 0.3, B), io
+
+
+def _rmpc_expected(L, harness, state, target, prm, mu, io, logs, N, k, do_post, do_pre):
+    from dart_mpc.rmpc import AdaptiveNPMPCSmooth, rls_features
+    s = {n: v.copy() for n, v in state.items()}
+    io = {n: v.copy() for n, v in io.items()}
+    lg = {n: v.copy() for n, v in logs.items()}
+    B = s["x"].shape[0]
+    c = L.rmpc_loop_config()
+    if do_post:
+        xk, u = s["x"][:, :4].copy(), io["u0"]
+        en = np.linalg.norm(xk[:, [0, 2]] - target[:, [0, 2]], axis=1)
+        for b in np.where(s["done"] == 0)[0]:
+            r = s["nlog"][b]
+            lg["pos_err"][r, b] = [target[b, 0] - xk[b, 0], target[b, 2] - xk[b, 2]]
+            lg["pos_err_norm"][r, b] = float(en[b])
+            lg["u_cmd"][r, b] = u[b]
+            lg["timestep"][r, b] = k * TS
+            s["nlog"][b] += 1
+            if en[b] < c.pos_tol:
+                s["done"][b] = 1
+        lg["x"][k], lg["theta"][k], lg["r_v"][k] = xk, s["theta"], s["r_v"]
+        lg["f"][k], lg["status"][k], lg["iters"][k] = io["f"], io["status"], io["iters"]
+        s["prev"], s["u_prev"] = xk, u.copy()
+        plant = harness.TrayPlant(s["x"], mu, dt=TS)
+        plant.tilt = s["tilt"].copy()
+        s["x"] = plant.step(u)
+        s["tilt"] = plant.tilt
+    if do_pre:
+        xk, prev = s["x"][:, :4].copy(), s["prev"]
+        io["y"] = (xk[:, [1, 3]] - prev[:, [1, 3]]) / TS
+        io["phi"] = np.stack([rls_features(p, prm[0, 9]) for p in prev])
+        err = np.stack([target[:, 0] - s["r_v"][:, 0], np.zeros(B), target[:, 2] - s["r_v"][:, 2], np.zeros(B)], axis=1)
+        s["r_v"] = s["r_v"] + c.alpha_rg * np.clip(err, -c.dr_max, c.dr_max) * np.array([1.0, 0.0, 1.0, 0.0])
+        io["Rref"] = np.stack([AdaptiveNPMPCSmooth.build_ref_traj(xk[b], s["r_v"][b], target[b], N, 4, step_fraction=0.2)
+                               for b in range(B)])
+        io["x0"] = xk
+    return s, io, lg
+
+
+@pytest.mark.parametrize("do_post,do_pre", [(0, 1), (1, 1), (1, 0)])
+@pytest.mark.parametrize("B", [1, 5, 67])
+@pytest.mark.parametrize("N", [1, 20, 31, 32, 63])
+def test_rmpc_loop_step_matches_numpy(L, torch, rmpc_solvers, N, B, do_post, do_pre):
+    from dart_mpc import harness
+    rng = np.random.default_rng(1000 * N + 10 * B + 2 * do_post + do_pre)
+    state, target, prm, mu, io = _rmpc_case(L, rng, B, N)
+    rows, k = 4, 3
+    logs = L.loop_logs(L.RMPC_LOOP_LOGS, rows, B)
+    want = _rmpc_expected(L, harness, state, target, prm, mu, io, logs, N, k, do_post, do_pre)
+    ds, dio, dl = _to_dev(torch, state), _to_dev(torch, io), _to_dev(torch, logs)
+    c = _to_dev(torch, dict(target=target, prm=prm, mu=mu))
+    s = rmpc_solvers(N)
+    s.loop_step_dev(B, k, do_post, do_pre, rows, c["target"].data_ptr(), c["prm"].data_ptr(), c["mu"].data_ptr(),
+                    _ptrs(ds), _ptrs(dio), _ptrs(dl))
+    s.sync()
+    for got, exp, what in zip((ds, dio, dl), want, ("state", "solve I/O", "logs")):
+        _close(_host(got), exp, what)
+    if do_post:        # closed episodes and rows past nlog keep the prefill
+        g = _host(dl)
+        closed = state["done"] == 1
+        assert np.isnan(g["pos_err_norm"][:, closed]).all()
+        for b in np.where(~closed)[0]:
+            assert np.isnan(np.delete(g["pos_err_norm"][:, b], state["nlog"][b])).all()
+        near = (np.arange(B) % 4 == 1) & ~closed
+        assert np.all(_host(ds)["done"][near] == 1)
+
+
+@pytest.mark.parametrize("do_post,do_pre", [(0, 1), (1, 1), (1, 0)])
+@pytest.mark.parametrize("B", [1, 5, 67])
+def test_pmpc_loop_step_matches_numpy(L, torch, pmpc_solver, B, do_post, do_pre):
+    from dart_mpc import harness
+    from dart_mpc.pmpc import tilt_to_quat
+    rng = np.random.default_rng(77 + 10 * B + 2 * do_post + do_pre)
+    x = rng.uniform(-0.3, 0.3, (B, 6)); x[:, 4] = 0.43
+    state = dict(x=x, tilt=rng.uniform(-0.3, 0.3, (B, 2)))
+    prm = np.tile([0.4, 100.0, 0.0, 0.1, -0.5, 0.5], (B, 1)); prm[:, 0] = rng.uniform(0.05, 0.6, B)
+    io = _nan_io(L, L.PMPC_LOOP_IO, B)
+    io.update(u0=rng.uniform(-0.5, 0.5, (B, 2)), f=rng.uniform(0, 1, B), status=rng.integers(-2, 1, B).astype(np.int32),
+              iters=rng.integers(1, 60, B).astype(np.int32))
+    rows, k = 3, 1
+    logs = L.loop_logs(L.PMPC_LOOP_LOGS, rows, B)
+    ws, wio, wl = ({n: v.copy() for n, v in d.items()} for d in (state, io, logs))
+    if do_post:
+        wl["X"][k], wl["U_cmd"][k], wl["loss"][k] = state["x"], io["u0"], io["f"]
+        wl["quat_tray"][k] = np.stack([tilt_to_quat(u) for u in io["u0"]])
+        wl["status"][k], wl["iters"][k] = io["status"], io["iters"]
+        plant = harness.TrayPlant(state["x"], prm[:, 0], dt=TS)
+        plant.tilt = state["tilt"].copy()
+        ws["x"] = plant.step(io["u0"])
+        ws["tilt"] = plant.tilt
+    if do_pre:
+        wio["x0"] = ws["x"].copy()
+    ds, dio, dl = _to_dev(torch, state), _to_dev(torch, io), _to_dev(torch, logs)
+    dp = _to_dev(torch, dict(prm=prm))
+    pmpc_solver.loop_step_dev(B, k, do_post, do_pre, rows, dp["prm"].data_ptr(), _ptrs(ds), _ptrs(dio), _ptrs(dl))
+    pmpc_solver.sync()
+    for got, exp, what in zip((ds, dio, dl), (ws, wio, wl), ("state", "solve I/O", "logs")):
+        _close(_host(got), exp, what)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Tests 2, 3: the rollout is its launches; a second call continues it
+def _rmpc_inputs(B, seed=5):
+    rng = np.random.default_rng(seed)
+    x0 = np.zeros((B, 4)); x0[:, [0, 2]] = rng.uniform(-0.05, 0.05, (B, 2)); x0[:, [1, 3]] = rng.uniform(-0.1, 0.1, (B, 2))
+    tg = np.zeros((B, 4)); tg[:, [0, 2]] = rng.uniform(-0.08, 0.08, (B, 2))
+    tg[0, [0, 2]] = x0[0, [0, 2]] + 2e-3        # one episode closes at its first step
+    return x0, tg, np.tile(RMPC_PRM, (B, 1)), rng.uniform(0.05, 0.3, B)
+
+
+def _rmpc_fresh(L, torch, s, x0, rows):
+    return _to_dev(torch, s.loop_state(x0)), _to_dev(torch, L.loop_logs(L.RMPC_LOOP_LOGS, rows, x0.shape[0]))
+
+
+def _rmpc_rollout(L, torch, s, x0, tg, prm, mu, rows, chunks):
+    B = x0.shape[0]
+    st, lg = _rmpc_fresh(L, torch, s, x0, rows)
+    c = _to_dev(torch, dict(target=tg, prm=prm, mu=mu))
+    k = 0
+    for n in chunks:
+        s.rollout_dev(B, k, n, rows, c["target"].data_ptr(), c["prm"].data_ptr(), c["mu"].data_ptr(), _ptrs(st), _ptrs(lg))
+        k += n
+    s.sync()
+    return st, lg
+
+
+def test_rmpc_rollout_equals_hand_sequenced_launches(L, torch, rmpc_solvers):
+    B, N, K = 5, 20, 12
+    s = rmpc_solvers(N)
+    x0, tg, prm, mu = _rmpc_inputs(B)
+    st, lg = _rmpc_rollout(L, torch, s, x0, tg, prm, mu, K, [K])
+    st2, lg2 = _rmpc_fresh(L, torch, s, x0, K)
+    io = _to_dev(torch, _nan_io(L, L.RMPC_LOOP_IO, B, nref=4 * (N + 1)))
+    c = _to_dev(torch, dict(target=tg, prm=prm, mu=mu))
+    cp = (c["target"].data_ptr(), c["prm"].data_ptr(), c["mu"].data_ptr())
+    p, q = _ptrs(st2), _ptrs(io)
+    s.loop_step_dev(B, 0, 0, 1, K, *cp, p, q, _ptrs(lg2))
+    for k in range(K):
+        s.solve_batch_dev(B, q["x0"], p["u_prev"], p["theta"], q["Rref"], cp[1], q["u0"], q["f"], q["status"], q["iters"],
+                          w_warm=p["w"], w_out=p["w"], rls_P=p["P"], rls_phi=q["phi"], rls_y=q["y"], rls_lambda=0.995)
+        s.loop_step_dev(B, k, 1, int(k + 1 < K), K, *cp, p, q, _ptrs(lg2))
+    s.sync()
+    for k in st:
+        assert _same(torch, st[k], st2[k]), k
+    for k in lg:
+        assert _same(torch, lg[k], lg2[k]), k
+    h = _host(lg)
+    assert not np.isnan(h["x"]).any() and np.all(h["status"] != L.LOG_INT_FILL)
+    n = _host(st)["nlog"]
+    assert n[0] == 1 and np.all(n[1:] == K)      # the closed episode logged one row, the others every step
+    assert np.isnan(h["u_cmd"][1:, 0]).all() and not np.isnan(h["u_cmd"][:, 1:]).any()
+
+
+def test_pmpc_rollout_equals_hand_sequenced_launches(L, torch, pmpc_solver):
+    from dart_mpc.workload import pmpc_batch
+    B, K = 5, 12
+    S, T, P = (a[:B] for a in pmpc_batch(1, seed0=2))
+    s = pmpc_solver
+    c = _to_dev(torch, dict(target=T, prm=P))
+
+    def fresh():
+        return (_to_dev(torch, dict(x=S.copy(), tilt=np.zeros((B, 2)))),
+                _to_dev(torch, L.loop_logs(L.PMPC_LOOP_LOGS, K, B)))
+    st, lg = fresh()
+    s.rollout_dev(B, 0, K, K, c["target"].data_ptr(), c["prm"].data_ptr(), _ptrs(st), _ptrs(lg))
+    s.sync()
+    st2, lg2 = fresh()
+    io = _to_dev(torch, _nan_io(L, L.PMPC_LOOP_IO, B))
+    p, q = _ptrs(st2), _ptrs(io)
+    s.loop_step_dev(B, 0, 0, 1, K, c["prm"].data_ptr(), p, q, _ptrs(lg2))
+    for k in range(K):
+        s.solve_batch_dev(B, q["x0"], c["target"].data_ptr(), c["prm"].data_ptr(), q["u0"], q["f"], q["status"], q["iters"])
+        s.loop_step_dev(B, k, 1, int(k + 1 < K), K, c["prm"].data_ptr(), p, q, _ptrs(lg2))
+    s.sync()
+    for k in st:
+        assert _same(torch, st[k], st2[k]), k
+    for k in lg:
+        assert _same(torch, lg[k], lg2[k]), k
+    assert not np.isnan(_host(lg)["U_cmd"]).any()
+
+
+@pytest.mark.parametrize("N", [20, 40])
+def test_rmpc_rollout_continues_bit_for_bit(L, torch, rmpc_solvers, N):
+    """7 steps then 5 (k0 = 7) equal 12 steps; N = 40 is the two-wave solve build."""
+    s = rmpc_solvers(N)
+    x0, tg, prm, mu = _rmpc_inputs(5, seed=6)
+    one = _rmpc_rollout(L, torch, s, x0, tg, prm, mu, 12, [12])
+    two = _rmpc_rollout(L, torch, s, x0, tg, prm, mu, 12, [7, 5])
+    for a, b in zip(one, two):
+        for k in a:
+            assert _same(torch, a[k], b[k]), k
+    assert not np.isnan(_host(one[1])["x"]).any()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Test 4: per-step parity with the oracle chain (scheme and bars of test_gpu_rmpc.py's closed-loop tests)
+def test_rmpc_rollout_matches_oracle_chain_per_step():
+    from dart_mpc import harness
+    B, N, K = 3, 20, 25
+    x0 = np.array([[0.0, 0.0, 0.0, 0.0], [0.01, 0.05, -0.02, 0.0], [0.0, 0.225, 0.0, -0.21]])     # the last: above vmax
+    tg = np.array([[0.08, 0.0, -0.05, 0.0], [-0.06, 0.0, 0.07, 0.0], [0.08, 0.0, -0.05, 0.0]])
+    # the plant of those tests (a_x = g sin u_x - v - 0.2 tanh(v / 0.1)); pos_tol 0: no episode closes, every step
+    # logs its u_cmd
+    eps, st, done, X = harness.rollout_rmpc(x0, tg, K, N=N, mu=1.0, pos_tol=0.0, return_logs=True,
+                                            plant_kw=dict(tau=0.0, mu_c=0.2 / 9.81, v_c=0.1))
+    assert st.shape == (K, B) and not done.any()
+    U = np.stack([np.asarray(e["ep1"]["u_cmd"]) for e in eps], axis=1)           # [K, B, 2]
+    assert U.shape == (K, B, 2)
+    seen = set()
+    for b in range(B):
+        rls = [rmpc_nlp.RLS(7), rmpc_nlp.RLS(7)]
+        r_v, w0, up, xprev = np.zeros(4), np.zeros(4 * (N + 1) + 2 * N), np.zeros(2), x0[b]
+        for k in range(K):
+            x = X["x"][k, b]
+            y = rmpc_nlp.rls_targets(x, xprev, TS)
+            f = rmpc_nlp.rls_features(xprev, 0.1)
+            rls[0].update(f, y[0]); rls[1].update(f, y[1])
+            th = np.concatenate([rls[0].get(), rls[1].get()])
+            assert np.allclose(X["theta"][k, b], th, rtol=1e-9, atol=1e-9 * max(1.0, np.abs(th).max())), (b, k)
+            r_v = rmpc_nlp.governor_step(r_v, tg[b])
+            assert np.allclose(X["r_v"][k, b], r_v, rtol=0, atol=1e-15), (b, k)
+            R = rmpc_nlp.build_ref_traj(x, X["r_v"][k, b], tg[b], N)
+            o = oracle_lib.rmpc_solve_batch(x[None], up[None], X["theta"][k, b][None], R[None], RMPC_PRM[None], N=N,
+                                            tol=1e-8, w_init=w0[None], max_iter=200)
+            w0 = o["w"][0]
+            seen.add(int(o["status"][0]))
+            assert int(st[k, b]) == int(o["status"][0]), (b, k, st[k, b], o["status"][0])
+            assert np.max(np.abs(U[k, b] - o["u0"][0])) <= 1e-6, (b, k, U[k, b], o["u0"][0], o["status"][0])
+            xprev, up = x, U[k, b]
+    assert seen == {0, 2}, seen
+    assert set(np.unique(st)) == {0, 2}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Test 5: PMPC rollout through the harness
+def test_pmpc_rollout_matches_oracle_and_npz(tmp_path):
+    from dart_mpc import harness
+    from dart_mpc.workload import pmpc_batch
+    S, T, P = pmpc_batch(1, seed0=0)
+    steps = 200
+    logs, st = harness.rollout_pmpc(S, T, P, steps)
+    assert st.shape == (steps, S.shape[0]) and np.all(st == 0)
+    np.testing.assert_array_equal(np.stack([lg["X"][0] for lg in logs]), S)
+    for k in (0, 100, steps - 1):
+        X = np.stack([lg["X"][k] for lg in logs])
+        U = np.stack([lg["U_cmd"][k] for lg in logs])
+        ref = oracle_lib.solve_batch(X, T, P, N=20, Ts=0.002, tol=1e-8)
+        assert np.max(np.abs(U - ref["u0"])) <= 1e-6, k
+    lg = logs[0]
+    assert lg["solve_time"].shape == (steps,) and lg["solve_time"][0] > 0
+    path = harness.save_npz(lg, {k: lg[k] for k in ("steady_state_error", "convergence_time", "control_effort")},
+                            tmp_path, "pmpc_rollout", "cube", 1.0, 0.05)
+    assert set(harness.NPZ_KEYS) <= set(np.load(path).files)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Test 6: episodes, chunked stop, the host loop
+# largest differences between the device rollout and harness.run_rmpc over the common episode rows, measured on
+# one MI355X (see the docstring below); the test asserts ten times these
+MEASURED_DU_CMD = 1.111e-14
+MEASURED_DPOS_ERR = 1.874e-16
+
+
+def test_rmpc_rollout_episodes_and_host_loop(tmp_path):
+    """B = 4 experiments of test_rmpc_closed_loop_first_step_and_episode_json plus one whose target is within
+    1 cm of its start, 300 steps.  Measured against harness.run_rmpc on one MI355X over the common episode rows
+    (4 x 300 + 1): max |du_cmd| = 1.111e-14, max |dpos_err| = 1.874e-16, episode lengths equal ([300] * 4 + [1]:
+    none of the four reaches 1 cm within 300 steps, so the chunked run goes to the end; the early stop is checked
+    on two experiments that start within the tolerance).  The test asserts ten times the measured values (the
+    margin: numpy against device transcendentals fed through the closed loop), far below the 1e-6 closed-loop
+    bar."""
+    from dart_mpc import harness
+    rng = np.random.default_rng(3)
+    B = 4
+    x0 = np.zeros((B + 1, 4))
+    tg = np.zeros((B + 1, 4)); tg[:B, 0] = rng.uniform(-0.08, 0.08, B); tg[:B, 2] = rng.uniform(-0.08, 0.08, B)
+    tg[B, 0], tg[B, 2] = 0.004, -0.003
+    steps = 300
+    full = harness.rollout_rmpc(x0, tg, steps)
+    part = harness.rollout_rmpc(x0, tg, steps, check_every=50)
+    n_full = [len(e["ep1"]["timestep"]) for e in full[0]]
+    assert full[1].shape == (steps, B + 1)
+    assert n_full[B] == 1 and full[2][B] and part[2][B]            # one row, then done
+    ran = part[1].shape[0]
+    assert ran % 50 == 0 and 0 < ran <= steps
+    if full[2].all():                                              # stops at the first check after the last episode end
+        assert ran == 50 * math.ceil(max(n_full) / 50)
+    else:
+        assert ran == steps
+    np.testing.assert_array_equal(part[1], full[1][:ran])
+    for b in range(B + 1):      # the chunked run stops only when every episode has closed: its logs are complete
+        for key in ("pos_err", "pos_err_norm", "u_cmd", "timestep"):
+            np.testing.assert_array_equal(np.asarray(full[0][b]["ep1"][key]), np.asarray(part[0][b]["ep1"][key]),
+                                          err_msg=f"{b} {key}")
+    # early stop: both episodes close at step 0, the run ends at the first check
+    near = np.zeros((2, 4)); near[:, 0] = [0.003, -0.002]
+    _, st2, done2 = harness.rollout_rmpc(np.zeros((2, 4)), near, 20, check_every=5)
+    assert done2.all() and st2.shape == (5, 2)
+    harness.save_episodes_json(tmp_path / "ep.json", full[0][0])
+    d = json.loads((tmp_path / "ep.json").read_text())["data"]["ep1"]
+    assert len(d["pos_err"]) == len(d["u_cmd"]) == len(d["timestep"]) == len(d["pos_err_norm"]) == n_full[0]
+    assert np.array_equal(np.asarray(d["u_cmd"]), np.asarray(full[0][0]["ep1"]["u_cmd"]))
+    # the host loop on the same inputs
+    host = harness.run_rmpc(x0, tg, steps)
+    du = dp = 0.0
+    for b in range(B + 1):
+        h, g = host[0][b]["ep1"], full[0][b]["ep1"]
+        n = len(g["timestep"])
+        assert len(h["timestep"]) == n, (b, len(h["timestep"]), n)        # equal episode lengths
+        du = max(du, float(np.max(np.abs(np.asarray(h["u_cmd"])[:n] - np.asarray(g["u_cmd"])[:n]))))
+        dp = max(dp, float(np.max(np.abs(np.asarray(h["pos_err"])[:n] - np.asarray(g["pos_err"])[:n]))))
+    print(f"rollout_rmpc vs run_rmpc: max|du_cmd| = {du:.3e}, max|dpos_err| = {dp:.3e}, steps run (host) = "
+          f"{host[1].shape[0]}, episode lengths = {n_full}, done = {full[2].tolist()}")
+    assert 10 * MEASURED_DU_CMD <= 1e-6 and 10 * MEASURED_DPOS_ERR <= 1e-6
+    assert du <= 10 * MEASURED_DU_CMD and dp <= 10 * MEASURED_DPOS_ERR
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Test 7: errors
+def test_rollout_errors_launch_nothing(L, torch, rmpc_solvers, pmpc_solver):
+    s = rmpc_solvers(20)
+    B, K = 3, 4
+    x0, tg, prm, mu = _rmpc_inputs(B)
+    st, lg = _rmpc_fresh(L, torch, s, x0, K)
+    c = _to_dev(torch, dict(target=tg, prm=prm, mu=mu))
+    cp = (c["target"].data_ptr(), c["prm"].data_ptr(), c["mu"].data_ptr())
+    before = ({k: v.clone() for k, v in st.items()}, {k: v.clone() for k, v in lg.items()})
+    with pytest.raises(L.DartMPCError, match="B_max"):
+        s.rollout_dev(68, 0, K, K, *cp, _ptrs(st), _ptrs(lg))
+    with pytest.raises(L.DartMPCError, match="log_rows"):
+        s.rollout_dev(B, 2, K - 1, K, *cp, _ptrs(st), _ptrs(lg))
+    with pytest.raises(L.DartMPCError, match="negative"):
+        s.rollout_dev(B, 0, -1, K, *cp, _ptrs(st), _ptrs(lg))
+    with pytest.raises(L.DartMPCError, match="null"):
+        s.rollout_dev(B, 0, K, K, cp[0], 0, cp[2], _ptrs(st), _ptrs(lg))
+    with pytest.raises(L.DartMPCError, match="not an RMPC handle"):       # a PMPC handle given to the RMPC entry
+        L.RmpcSolver.rollout_dev(pmpc_solver, B, 0, K, K, *cp, _ptrs(st), _ptrs(lg))
+    with pytest.raises(L.DartMPCError, match="not a PMPC handle"):
+        L.Solver.rollout_dev(s, B, 0, K, K, cp[0], cp[1], _ptrs(st), _ptrs({**lg, **{n: lg["x"] for n, _, _ in
+                                                                                   L.PMPC_LOOP_LOGS}}))
+    s.rollout_dev(B, 0, 0, K, *cp, _ptrs(st), _ptrs(lg))        # steps = 0: OK, touches nothing
+    s.sync()
+    torch.cuda.synchronize()
+    for a, b in zip((st, lg), before):
+        for k in a:
+            assert _same(torch, a[k], b[k]), k
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Test 8: a process that exits with the solver open (the atexit path of dart_mpc/_lib.py)
+_CHILD = """
+import numpy as np
+from dart_mpc import _lib
+s = _lib.RmpcSolver(N=20, B_max=4)
+x0 = np.zeros((2, 4)); tg = np.zeros((2, 4)); tg[:, 0] = 0.05
+st = s.loop_state(x0); lg = _lib.loop_logs(_lib.RMPC_LOOP_LOGS, 5, 2)
+s.rollout(0, 5, tg, np.tile(%r, (2, 1)), 0.1, st, lg)
+assert not np.isnan(lg["x"]).any() and (st["nlog"] == 5).all()
+print("rolled", int(lg["iters"].sum()))
+"""
+
+
+def test_child_exits_cleanly_with_an_open_solver():
+    from dart_mpc import _lib
+    pkg_root = os.path.dirname(_lib.PKG_DIR)
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([pkg_root, os.environ.get("PYTHONPATH", "")]))
+    r = subprocess.run([sys.executable, "-c", _CHILD % (RMPC_PRM.tolist(),)], env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    assert "rolled" in r.stdout
