@@ -200,10 +200,220 @@ __device__ __forceinline__ void mat4_scan_level(double* T) {
 // scan, the least-square iteration, second-order corrections, failures): C2 +2.1 % (A/B); the one-row
 // build (N <= 15) measured 1 % slower with them and goes without
 #define PM_EXPECT(x, v) (ONEROW ? (bool)(x) : (bool)__builtin_expect((long)(bool)(x), (v)))
-template <int NAX, bool QSCAN, bool ONEROW, bool SHORT2, bool RED>
+
+// The per-lane stage constants of the Riccati factorisation (pmpc_solve derives them at its start).
+struct PmStage {
+    double f11, a12k, a22k, ai12k, ai22k, a22i, uonf, A11k, A12k, A22k;
+};
+
+// One attempt of the Riccati factorisation at the inertia perturbation delta: from the stage quantities of the
+// current point (be, E, Rt0) the value function P, the gains W, 1 / Quu (iQs) of every node; returns ok (every
+// Quu > 0 and finite), use_scan tells which recursion ran.  One function for the iteration loop of pmpc_solve
+// (every attempt of the one-wave builds; the retries and the sequential fallback of the overlapped build) and
+// for the factor wave of the overlapped build (attempt 0, delta = 0), so both run the same arithmetic.
+template <int NAX, bool QSCAN, bool ONEROW, bool SHORT2>
+__device__ __forceinline__ bool pmpc_riccati(const int lane, const int N, const bool uon, const bool lsm,
+                                             const double delta, const double qp2, const double qv2,
+                                             const PmStage& c, const double (&be1)[NAX], const double (&be2)[NAX],
+                                             const double (&E11)[NAX], const double (&E12)[NAX],
+                                             const double (&E22)[NAX], const double (&Rt0)[NAX], double (&P11)[NAX],
+                                             double (&P12)[NAX], double (&P22)[NAX], double (&W1)[NAX],
+                                             double (&W2)[NAX], double (&iQs)[NAX], bool& use_scan) {
+    constexpr bool one_row = ONEROW;
+    constexpr bool short2 = SHORT2 && !ONEROW;
+    const double f11 = c.f11, a12k = c.a12k, a22k = c.a22k, ai12k = c.ai12k, ai22k = c.ai22k, a22i = c.a22i;
+    const double uonf = c.uonf, A11k = c.A11k, A12k = c.A12k, A22k = c.A22k;
+    (void)lane; (void)ai12k; (void)ai22k; (void)a22i; (void)uonf;
+    const double X11d = lsm ? 1.0 : qp2 + delta, X22d = lsm ? 1.0 : qv2 + delta;
+    double Quu[NAX], Rt[NAX];
+#pragma unroll
+    for (int j = 0; j < NAX; ++j) {      // terminal value function in every lane
+        P11[j] = X11d; P12[j] = 0.0; P22[j] = X22d;
+        Rt[j] = (lsm ? 1.0 : Rt0[j]) + delta;
+    }
+    // Quadratic part as a scan: with P = Y U^-1 the stage map P_k = X + A^T (P_{k+1}^-1 + G_k)^-1 A
+    // (G_k = B_k B_k^T / R_k) is linear on [U; Y]: [U; Y]_k = S_k [U; Y]_{k+1},
+    // S_k = [[A^-1, A^-1 G], [X A^-1, X A^-1 G + A^T]], so [U; Y]_k = S_k ... S_{N-1} [I; X]
+    // is a suffix product (5 DPP levels).  Exact in the reals; in fp64 it matches the
+    // sequential sweep to ~1e-15 while every stage is mildly stiff (B_k B_k^T X / R_k <= 2
+    // per axis, checked here); otherwise, and for NAX == 2, the sequential sweep runs.
+    use_scan = false;
+    if constexpr (NAX == 1 && QSCAN) {
+        const double ratio = fmax(E11[0] * X11d, E22[0] * X22d);
+        use_scan = !wany(uon && !(Rt[0] > 0.0 && ratio <= 2.0 * Rt[0]));
+    }
+    if (PM_EXPECT(use_scan, 1)) {
+        const double iR = uon ? frcp(Rt[0]) : 0.0;
+        const double G11 = be1[0] * be1[0] * iR, G12 = be1[0] * be2[0] * iR, G22 = be2[0] * be2[0] * iR;
+        const double g11 = G11 + ai12k * G12, g12 = G12 + ai12k * G22, g21 = ai22k * G12, g22 = ai22k * G22;
+        // idle / terminal lanes: A^-1 = I, G = 0 (iR = 0), X = 0, A^T = I give T = I without a select
+        const double X11k = X11d * uonf, X22k = X22d * uonf;
+        double T[16] = {1.0, ai12k, g11, g12,
+                        0.0, ai22k, g21, g22,
+                        X11k, X11k * ai12k, fma(X11k, g11, 1.0), X11k * g12,
+                        0.0, X22k * ai22k, fma(X22k, g21, a12k), fma(X22k, g22, a22i)};
+        mat4_scan_level<0x101, true>(T);
+        mat4_scan_level<0x102>(T);
+        mat4_scan_level<0x104>(T);
+        if constexpr (!short2 && !one_row) mat4_scan_level<0x108>(T);
+        // [U; Y] = T [I; X] of the row-local suffix
+        double W[8] = {fma(T[2], X11d, T[0]), fma(T[3], X22d, T[1]), fma(T[6], X11d, T[4]),
+                       fma(T[7], X22d, T[5]), fma(T[10], X11d, T[8]), fma(T[11], X22d, T[9]),
+                       fma(T[14], X11d, T[12]), fma(T[15], X22d, T[13])};
+        if constexpr (short2 || one_row) {
+            // after 3 levels lane k holds S_k ... S_{min(k+7, row end)}: lanes 16-23 (48-55)
+            // already reach the terminal (N <= 23), lanes 8-15 the row end (and the terminal
+            // when N <= 15).  Lanes 8-15 compose with the 4 x 2 of lane 16 (ds_swizzle; not
+            // for N <= 15), then lanes 0-7 with that of lane k + 8 (DPP).  Lanes past the
+            // terminal hold [I; X], so a suffix that is already complete stays unchanged.
+            double F[8];
+            if constexpr (short2) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) F[e] = half_bcast_c<16>(W[e]);
+            if ((lane & 16) == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj)
+                        W[2 * i + jj] = fma(T[4 * i], F[jj], fma(T[4 * i + 1], F[2 + jj],
+                                            fma(T[4 * i + 2], F[4 + jj], T[4 * i + 3] * F[6 + jj])));
+            }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) F[e] = dpp_fill<0x108, 0xf, 0>(W[e]);
+            if ((lane & 24) == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj)
+                        W[2 * i + jj] = fma(T[4 * i], F[jj], fma(T[4 * i + 1], F[2 + jj],
+                                            fma(T[4 * i + 2], F[4 + jj], T[4 * i + 3] * F[6 + jj])));
+            }
+        } else if constexpr (!one_row && kWaves == 1) {
+            // rows 0 and 2 of each half: [U; Y]_k = T_k(row) [U; Y]_16, the 4 x 2 of lane 16 (48)
+            // fetched by ds_swizzle (bitmask mode, or_mask 16: no address, no LDS access)
+            double F[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) F[e] = half_bcast_c<16>(W[e]);
+            if ((lane & 16) == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj)
+                        W[2 * i + jj] = fma(T[4 * i], F[jj], fma(T[4 * i + 1], F[2 + jj],
+                                            fma(T[4 * i + 2], F[4 + jj], T[4 * i + 3] * F[6 + jj])));
+            }
+        }
+        double pnx[3] = {0.0, 0.0, 0.0};      // two waves: P_32 (wave 1's node 32) in wave 0
+        if constexpr (kWaves == 2) {
+            // two waves (N >= 32, rows as above): wave 1's suffixes reach the terminal; wave 0's continue
+            // from the value function of node 32, [U; Y]_k = T_k(..31) [I; P_32] (exact in the reals, as the
+            // scan itself)
+            auto rows = [&]() {
+                double F[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) F[e] = half_bcast_c<16>(W[e]);
+                if ((lane & 16) == 0) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int jj = 0; jj < 2; ++jj)
+                            W[2 * i + jj] = fma(T[4 * i], F[jj], fma(T[4 * i + 1], F[2 + jj],
+                                                fma(T[4 * i + 2], F[4 + jj], T[4 * i + 3] * F[6 + jj])));
+                }
+            };
+            double v[3] = {0.0, 0.0, 0.0}, pn[3];
+            if (wave_idx() == 1) {
+                rows();
+                const double idet = frcp(fma(W[0], W[3], -W[1] * W[2]));
+                v[0] = fma(W[4], W[3], -W[5] * W[2]) * idet;
+                v[1] = 0.5 * (fma(W[5], W[0], -W[4] * W[1]) * idet + fma(W[6], W[3], -W[7] * W[2]) * idet);
+                v[2] = fma(W[7], W[0], -W[6] * W[1]) * idet;
+            }
+            pm_pass<0>(1, 0, v, pn);
+            pnx[0] = pn[0]; pnx[1] = pn[1]; pnx[2] = pn[2];
+            if (wave_idx() == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    W[2 * i] = fma(T[4 * i + 3], pn[1], fma(T[4 * i + 2], pn[0], T[4 * i]));
+                    W[2 * i + 1] = fma(T[4 * i + 3], pn[2], fma(T[4 * i + 2], pn[1], T[4 * i + 1]));
+                }
+                rows();
+            }
+        }
+        // P = Y U^-1 (symmetrised)
+        const double U11 = W[0], U12 = W[1], U21 = W[2], U22 = W[3];
+        const double Y11 = W[4], Y12 = W[5], Y21 = W[6], Y22 = W[7];
+        const double idet = frcp(fma(U11, U22, -U12 * U21));
+        const double q11 = fma(Y11, U22, -Y12 * U21) * idet, q12 = fma(Y12, U11, -Y11 * U12) * idet;
+        const double q21 = fma(Y21, U22, -Y22 * U21) * idet, q22 = fma(Y22, U11, -Y21 * U12) * idet;
+        P11[0] = q11; P12[0] = 0.5 * (q12 + q21); P22[0] = q22;
+        // the stage quantities of node k from P_{k+1}
+        double n11, n12, n22;
+        if constexpr (kWaves == 1) {
+            n11 = from_next(P11[0]); n12 = from_next(P12[0]); n22 = from_next(P22[0]);
+        } else {
+            // two waves: node 32's value function is already in wave 0 (pnx), no exchange
+            n11 = dpp<kWaveShl1>(P11[0]); n12 = dpp<kWaveShl1>(P12[0]); n22 = dpp<kWaveShl1>(P22[0]);
+            if (wave_idx() == 0 && (lane & 31) == 31) { n11 = pnx[0]; n12 = pnx[1]; n22 = pnx[2]; }
+        }
+        const double e1 = be1[0], e2 = be2[0];
+        const double Q = fma(E11[0], n11, fma(E12[0], n12, fma(E22[0], n22, Rt[0])));
+        const double PB1 = fma(n11, e1, n12 * e2), PB2 = fma(n12, e1, n22 * e2);
+        const double U1 = PB1, U2 = fma(PB1, a12k, PB2 * a22k);
+        const double iQ = frcp(Q);
+        W1[0] = iQ * U1; W2[0] = iQ * U2;
+        Quu[0] = Q; iQs[0] = iQ;
+    } else
+    // backward sweep: every lane maps its neighbour's value function through its own
+    // stage; after step j lane N-1-j is final.  Terminal/idle lanes have Phi = 0, B = 0.
+    for (int step = 0; step < N; ++step) {
+        double n11[NAX], n12[NAX], n22[NAX];
+#pragma unroll
+        for (int j = 0; j < NAX; ++j) {
+            n11[j] = from_next(P11[j]); n12[j] = from_next(P12[j]); n22[j] = from_next(P22[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < NAX; ++j) {
+            const double e1 = be1[j], e2 = be2[j];
+            const double Q = fma(E11[j], n11[j], fma(E12[j], n12[j], fma(E22[j], n22[j], Rt[j])));
+            const double PB1 = fma(n11[j], e1, n12[j] * e2), PB2 = fma(n12[j], e1, n22[j] * e2);
+            const double U1 = PB1, U2 = fma(PB1, a12k, PB2 * a22k);
+            const double X12 = fma(n11[j], a12k, n12[j] * a22k);
+            const double X22 = fma(A11k, n11[j], fma(A12k, n12[j], fma(A22k, n22[j], X22d)));
+            const double iQ = frcp(Q);
+            const double w1 = iQ * U1, w2 = iQ * U2;
+            P11[j] = fma(-w1, U1, fma(f11, n11[j], X11d));
+            P12[j] = fma(-w1, U2, X12);
+            P22[j] = fma(-w2, U2, X22);
+            W1[j] = w1; W2[j] = w2;
+            Quu[j] = Q; iQs[j] = iQ;
+        }
+    }
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < NAX; ++j) bad = bad || !(Quu[j] > 0.0) || !isfinite(Quu[j]);
+    return !wany(bad);
+}
+
+// The overlapped build (OVL; NAX == 1, QSCAN, one wave per instance, launched with two waves): LDS hand-over
+// between the solver wave (wave 0) and the factor wave (wave 1).  [field][lane]: every access is one
+// conflict-free 8-byte access per lane.  pt: th, snc, lp, lv, zl, zu of the current point (wave 0 writes
+// before barrier A, wave 1 reads after it); fc: P11, P12, P22, W1, W2, iQs (wave 1 writes before barrier B,
+// wave 0 reads after it); flag: [0] stop, [1] use_scan, [2] ok.  Each buffer has one writer, and its next write
+// comes after a barrier that the reader crosses only with its reads complete, so single buffers are enough.
+struct PmOvlShared {
+    double pt[6][kWave];
+    double fc[6][kWave];
+    int flag[4];       // ([3]: the stamps build's factor-wave timer)
+};
+__shared__ PmOvlShared g_pm_ovl;       // only the overlapped instantiations name it (6 KB beside PrShared when fused)
+
+template <int NAX, bool QSCAN, bool ONEROW, bool SHORT2, bool RED, bool OVL = false>
 __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
+    static_assert(!OVL || (NAX == 1 && QSCAN && !ONEROW && !RED && kWaves == 1), "the overlapped build: scan builds of N = 16..31");
     STAMP_DECL
-    const int lane = kWaves == 1 ? (int)threadIdx.x : lane_id();
+    const int lane = (kWaves == 1 && !OVL) ? (int)threadIdx.x : lane_id();
     const int k = NAX == 1 ? node_base() + (lane & 31) : lane;      // shooting node of this lane
     const int ax0 = NAX == 1 ? (lane >> 5) : 0;               // axis of slot 0 (NAX == 1)
     const int N = a.N;
@@ -272,6 +482,57 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
     const double sc = gmax > 100.0 ? 100.0 / gmax : 1.0;     // nlp_scaling_max_gradient = 100
     const double qp2 = sc * 2 * Qp, qv2 = sc * 2 * Qv, r2 = sc * 2 * R;
     const double scQp = sc * Qp, scQv = sc * Qv, scR = sc * R;
+    const PmStage stg = {f11, a12k, a22k, ai12k, ai22k, a22i, uonf, A11k, A12k, A22k};
+    // stage quantities of the quadratic (Riccati) pass at a point: B_k = Gamma cos(theta_k) (0 on idle lanes), its
+    // products, and the Hessian of the Lagrangian in theta, 2R + lam_{k+1}^T Gamma sin(theta) + Sigma
+    auto quad_stage = [&](double csj, double snj, double lpnj, double lvnj, double zlj, double islj, double zuj,
+                          double isuj, double& e1, double& e2, double& e11, double& e12, double& e22, double& rt0) {
+        e1 = b1 * csj; e2 = b2 * csj;
+        e11 = e1 * e1; e12 = 2.0 * e1 * e2; e22 = e2 * e2;
+        rt0 = uon ? fma(snj, fma(b1, lpnj, b2 * lvnj), r2 + zlj * islj + zuj * isuj) : 1.0;
+    };
+    if constexpr (OVL) {
+        // The factor wave.  It has derived the lane constants above from the same inputs with the same code as the
+        // solver wave (the gradient scaling's wave reduction included).  Every round: wait for a point (barrier A),
+        // factor it at delta = 0 (attempt 0 of the iteration's Riccati block), publish the result (barrier B).  It
+        // tests the stop word after every barrier and leaves the kernel when it is set (pmpc_solve's exit funnel).
+        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0) {
+            for (;;) {
+                __syncthreads();                                            // barrier A, or the stop barrier
+                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return false;
+#ifdef DART_STAMPS
+                const unsigned long long tf0 = __builtin_amdgcn_s_memtime();
+#endif
+                const double th1 = g_pm_ovl.pt[0][lane], sn1 = g_pm_ovl.pt[1][lane];
+                const double lp1 = g_pm_ovl.pt[2][lane], lv1 = g_pm_ovl.pt[3][lane];
+                const double zl1 = g_pm_ovl.pt[4][lane], zu1 = g_pm_ovl.pt[5][lane];
+                const double c_ = tilt_cos_econ(poly, th1);
+                const double cs1 = uon ? c_ : 0.0;
+                const double ln = from_next(lp1), vn = from_next(lv1);
+                const double lpn1 = uon ? ln : 0.0, lvn1 = uon ? vn : 0.0;
+                const double sl = th1 - lo, su = hi - th1;
+                const double isl1 = uon ? frcp(sl) : 0.0, isu1 = uon ? frcp(su) : 0.0;
+                double be1[NAX], be2[NAX], E11[NAX], E12[NAX], E22[NAX], Rt0[NAX];
+                quad_stage(cs1, sn1, lpn1, lvn1, zl1, isl1, zu1, isu1, be1[0], be2[0], E11[0], E12[0], E22[0], Rt0[0]);
+                double W1[NAX], W2[NAX], P11[NAX], P12[NAX], P22[NAX], iQs[NAX];
+                bool us = false;
+                const bool okf = pmpc_riccati<NAX, QSCAN, ONEROW, SHORT2>(lane, N, uon, false, 0.0, qp2, qv2, stg, be1,
+                                                                         be2, E11, E12, E22, Rt0, P11, P12, P22, W1,
+                                                                         W2, iQs, us);
+                g_pm_ovl.fc[0][lane] = P11[0]; g_pm_ovl.fc[1][lane] = P12[0]; g_pm_ovl.fc[2][lane] = P22[0];
+                g_pm_ovl.fc[3][lane] = W1[0]; g_pm_ovl.fc[4][lane] = W2[0]; g_pm_ovl.fc[5][lane] = iQs[0];
+                if (lane == 0) { g_pm_ovl.flag[1] = us ? 1 : 0; g_pm_ovl.flag[2] = okf ? 1 : 0; }
+#ifdef DART_STAMPS
+                // the factor wave's own time from barrier A to its arrival at barrier B, summed (slot 13 of wave 0)
+                t_acc_[13] += __builtin_amdgcn_s_memtime() - tf0;
+                if (lane == 0) g_pm_ovl.flag[3] = (int)t_acc_[13];
+#endif
+                __syncthreads();                                            // barrier B, or the stop barrier
+                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return false;
+            }
+        }
+        if (lane == 0) g_pm_ovl.flag[0] = 0;      // the solver wave, before its first barrier
+    }
 
     const double tol = a.tol, mu_min = tol / 10;
     const double n_eq = 6.0 * (N + 1), n_b = 4.0 * N;       // IPOPT counts on the full NLP
@@ -342,6 +603,21 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
     int in_soft = 0, soft_count = 0;
     STAMP(0);
 
+    // OVL: the current point to the factor wave, then barrier A.  Called as early as the point is known: for the
+    // start point at the first Newton iteration, then in the accepted update as soon as theta, lambda and z of
+    // the new point exist, so that the rest of the update, the evaluation, the error reductions and the mu update
+    // all run while the factor wave works.  The scheduling barriers keep the compiler from moving that work (plain
+    // register arithmetic, which __syncthreads() does not order) ahead of barrier A.
+    bool published = false;
+    auto publish = [&]() {
+        __builtin_amdgcn_sched_barrier(0);
+        g_pm_ovl.pt[0][lane] = th[0]; g_pm_ovl.pt[1][lane] = snc[0];
+        g_pm_ovl.pt[2][lane] = lp[0]; g_pm_ovl.pt[3][lane] = lv[0];
+        g_pm_ovl.pt[4][lane] = zl[0]; g_pm_ovl.pt[5][lane] = zu[0];
+        __syncthreads();                                                    // barrier A
+        __builtin_amdgcn_sched_barrier(0);
+        published = true;
+    };
 #ifdef DART_STAMPS
     const unsigned long long t_loop0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -356,6 +632,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
 #ifdef DART_STAMPS
         if (it == 1) t_acc_[12] = __builtin_amdgcn_s_memtime() - t_loop0;      // the first iteration (cold code)
 #endif
+        if constexpr (OVL) {
+            // the start point (every later point is published by the update that accepted it); the least-square
+            // iteration keeps its factorisation (unit weights) in this wave and crosses no barrier
+            if (PM_EXPECT(!lsm && !published, 0)) publish();
+        }
         // -------- point quantities and optimality error (IPOPT eq. 5) ------------
         double sn[NAX], cs[NAX], isl[NAX], isu[NAX], lpn[NAX], lvn[NAX];
         double dinf = 0.0, pinf = 0.0, c0 = 0.0, cmin = 1e300, suml = 0.0, sumz = 0.0;
@@ -414,10 +695,8 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         double be1[NAX], be2[NAX], E11[NAX], E12[NAX], E22[NAX], Rt0[NAX], rt[NAX], q1[NAX], q2[NAX];
 #pragma unroll
         for (int j = 0; j < NAX; ++j) {
-            be1[j] = b1 * cs[j]; be2[j] = b2 * cs[j];           // B_k = Gamma cos(theta_k); 0 on idle lanes
-            E11[j] = be1[j] * be1[j]; E12[j] = 2.0 * be1[j] * be2[j]; E22[j] = be2[j] * be2[j];
-            // Hessian of the Lagrangian in theta: 2R + lam_{k+1}^T Gamma sin(theta) + Sigma
-            Rt0[j] = uon ? fma(sn[j], fma(b1, lpn[j], b2 * lvn[j]), r2 + zl[j] * isl[j] + zu[j] * isu[j]) : 1.0;
+            quad_stage(cs[j], sn[j], lpn[j], lvn[j], zl[j], isl[j], zu[j], isu[j], be1[j], be2[j], E11[j], E12[j],
+                       E22[j], Rt0[j]);
             // the barrier gradient in theta (least-square estimate: r_u = grad f - z_L + z_U)
             rt[j] = uon ? (lsm ? r2 * th[j] - zl[j] + zu[j] : fma(r2, th[j], mu * (isu[j] - isl[j]))) : 0.0;
             q1[j] = qp2 * (p[j] - rp[j]); q2[j] = qv2 * (v[j] - rv[j]);
@@ -426,181 +705,35 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         double delta = 0.0;
         bool ok = false;
         int attempt = 0;
+        if constexpr (OVL) {
+            // attempt 0 comes from the factor wave.  Where it did not take the scan or found a Quu <= 0, the loop
+            // below runs in this wave from attempt 0 on, as in the one-wave build (the sequential sweep, the
+            // inertia retries): cold paths, without the factor wave and so without barriers.
+            if (!lsm) {
+                __builtin_amdgcn_sched_barrier(0);      // everything above is done before this wave waits
+                SPAN_BEGIN(t_b);
+                __syncthreads();                                            // barrier B
+                SPAN_END(14, t_b);                      // (stamps build, slot 14: the wait alone)
+                // (the six values are read with the flags, not after the branch on them: one LDS round trip)
+                const int usf = g_pm_ovl.flag[1], okff = g_pm_ovl.flag[2];
+                P11[0] = g_pm_ovl.fc[0][lane]; P12[0] = g_pm_ovl.fc[1][lane]; P22[0] = g_pm_ovl.fc[2][lane];
+                W1[0] = g_pm_ovl.fc[3][lane]; W2[0] = g_pm_ovl.fc[4][lane]; iQs[0] = g_pm_ovl.fc[5][lane];
+                const bool us = __builtin_amdgcn_readfirstlane(usf) != 0;
+                const bool okf = __builtin_amdgcn_readfirstlane(okff) != 0;
+                if (PM_EXPECT(us && okf, 1)) {
+                    STAMP_ADD(11, 1);
+                    ok = true; attempt = 1;
+                }
+            }
+        }
         for (; attempt < 60 && !ok; ++attempt) {
             if (PM_EXPECT(attempt > 0, 0))
                 delta = (attempt == 1) ? (delta_last == 0.0 ? 1e-4 : fmax(1e-20, delta_last * (1.0 / 3.0)))   // IPOPT perturb_dec_fact 1/3
                                        : delta * (delta_last == 0.0 ? 100.0 : 8.0);
-            const double X11d = lsm ? 1.0 : qp2 + delta, X22d = lsm ? 1.0 : qv2 + delta;
-            double Quu[NAX], Rt[NAX];
-#pragma unroll
-            for (int j = 0; j < NAX; ++j) {      // terminal value function in every lane
-                P11[j] = X11d; P12[j] = 0.0; P22[j] = X22d;
-                Rt[j] = (lsm ? 1.0 : Rt0[j]) + delta;
-            }
-            // Quadratic part as a scan: with P = Y U^-1 the stage map P_k = X + A^T (P_{k+1}^-1 + G_k)^-1 A
-            // (G_k = B_k B_k^T / R_k) is linear on [U; Y]: [U; Y]_k = S_k [U; Y]_{k+1},
-            // S_k = [[A^-1, A^-1 G], [X A^-1, X A^-1 G + A^T]], so [U; Y]_k = S_k ... S_{N-1} [I; X]
-            // is a suffix product (5 DPP levels).  Exact in the reals; in fp64 it matches the
-            // sequential sweep to ~1e-15 while every stage is mildly stiff (B_k B_k^T X / R_k <= 2
-            // per axis, checked here); otherwise, and for NAX == 2, the sequential sweep runs.
             bool use_scan = false;
-            if constexpr (NAX == 1 && QSCAN) {
-                const double ratio = fmax(E11[0] * X11d, E22[0] * X22d);
-                use_scan = !wany(uon && !(Rt[0] > 0.0 && ratio <= 2.0 * Rt[0]));
-            }
+            ok = pmpc_riccati<NAX, QSCAN, ONEROW, SHORT2>(lane, N, uon, lsm, delta, qp2, qv2, stg, be1, be2, E11, E12,
+                                                          E22, Rt0, P11, P12, P22, W1, W2, iQs, use_scan);
             STAMP_ADD(11, use_scan ? 1 : 0);
-            if (PM_EXPECT(use_scan, 1)) {
-                const double iR = uon ? frcp(Rt[0]) : 0.0;
-                const double G11 = be1[0] * be1[0] * iR, G12 = be1[0] * be2[0] * iR, G22 = be2[0] * be2[0] * iR;
-                const double g11 = G11 + ai12k * G12, g12 = G12 + ai12k * G22, g21 = ai22k * G12, g22 = ai22k * G22;
-                // idle / terminal lanes: A^-1 = I, G = 0 (iR = 0), X = 0, A^T = I give T = I without a select
-                const double X11k = X11d * uonf, X22k = X22d * uonf;
-                double T[16] = {1.0, ai12k, g11, g12,
-                                0.0, ai22k, g21, g22,
-                                X11k, X11k * ai12k, fma(X11k, g11, 1.0), X11k * g12,
-                                0.0, X22k * ai22k, fma(X22k, g21, a12k), fma(X22k, g22, a22i)};
-                mat4_scan_level<0x101, true>(T);
-                mat4_scan_level<0x102>(T);
-                mat4_scan_level<0x104>(T);
-                if constexpr (!short2 && !one_row) mat4_scan_level<0x108>(T);
-                // [U; Y] = T [I; X] of the row-local suffix
-                double W[8] = {fma(T[2], X11d, T[0]), fma(T[3], X22d, T[1]), fma(T[6], X11d, T[4]),
-                               fma(T[7], X22d, T[5]), fma(T[10], X11d, T[8]), fma(T[11], X22d, T[9]),
-                               fma(T[14], X11d, T[12]), fma(T[15], X22d, T[13])};
-                if constexpr (short2 || one_row) {
-                    // after 3 levels lane k holds S_k ... S_{min(k+7, row end)}: lanes 16-23 (48-55)
-                    // already reach the terminal (N <= 23), lanes 8-15 the row end (and the terminal
-                    // when N <= 15).  Lanes 8-15 compose with the 4 x 2 of lane 16 (ds_swizzle; not
-                    // for N <= 15), then lanes 0-7 with that of lane k + 8 (DPP).  Lanes past the
-                    // terminal hold [I; X], so a suffix that is already complete stays unchanged.
-                    double F[8];
-                    if constexpr (short2) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) F[e] = half_bcast_c<16>(W[e]);
-                    if ((lane & 16) == 0) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-#pragma unroll
-                            for (int jj = 0; jj < 2; ++jj)
-                                W[2 * i + jj] = fma(T[4 * i], F[jj], fma(T[4 * i + 1], F[2 + jj],
-                                                    fma(T[4 * i + 2], F[4 + jj], T[4 * i + 3] * F[6 + jj])));
-                    }
-                    }
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) F[e] = dpp_fill<0x108, 0xf, 0>(W[e]);
-                    if ((lane & 24) == 0) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-#pragma unroll
-                            for (int jj = 0; jj < 2; ++jj)
-                                W[2 * i + jj] = fma(T[4 * i], F[jj], fma(T[4 * i + 1], F[2 + jj],
-                                                    fma(T[4 * i + 2], F[4 + jj], T[4 * i + 3] * F[6 + jj])));
-                    }
-                } else if constexpr (!one_row && kWaves == 1) {
-                    // rows 0 and 2 of each half: [U; Y]_k = T_k(row) [U; Y]_16, the 4 x 2 of lane 16 (48)
-                    // fetched by ds_swizzle (bitmask mode, or_mask 16: no address, no LDS access)
-                    double F[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) F[e] = half_bcast_c<16>(W[e]);
-                    if ((lane & 16) == 0) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-#pragma unroll
-                            for (int jj = 0; jj < 2; ++jj)
-                                W[2 * i + jj] = fma(T[4 * i], F[jj], fma(T[4 * i + 1], F[2 + jj],
-                                                    fma(T[4 * i + 2], F[4 + jj], T[4 * i + 3] * F[6 + jj])));
-                    }
-                }
-                double pnx[3] = {0.0, 0.0, 0.0};      // two waves: P_32 (wave 1's node 32) in wave 0
-                if constexpr (kWaves == 2) {
-                    // two waves (N >= 32, rows as above): wave 1's suffixes reach the terminal; wave 0's continue
-                    // from the value function of node 32, [U; Y]_k = T_k(..31) [I; P_32] (exact in the reals, as the
-                    // scan itself)
-                    auto rows = [&]() {
-                        double F[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) F[e] = half_bcast_c<16>(W[e]);
-                        if ((lane & 16) == 0) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                                for (int jj = 0; jj < 2; ++jj)
-                                    W[2 * i + jj] = fma(T[4 * i], F[jj], fma(T[4 * i + 1], F[2 + jj],
-                                                        fma(T[4 * i + 2], F[4 + jj], T[4 * i + 3] * F[6 + jj])));
-                        }
-                    };
-                    double v[3] = {0.0, 0.0, 0.0}, pn[3];
-                    if (wave_idx() == 1) {
-                        rows();
-                        const double idet = frcp(fma(W[0], W[3], -W[1] * W[2]));
-                        v[0] = fma(W[4], W[3], -W[5] * W[2]) * idet;
-                        v[1] = 0.5 * (fma(W[5], W[0], -W[4] * W[1]) * idet + fma(W[6], W[3], -W[7] * W[2]) * idet);
-                        v[2] = fma(W[7], W[0], -W[6] * W[1]) * idet;
-                    }
-                    pm_pass<0>(1, 0, v, pn);
-                    pnx[0] = pn[0]; pnx[1] = pn[1]; pnx[2] = pn[2];
-                    if (wave_idx() == 0) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            W[2 * i] = fma(T[4 * i + 3], pn[1], fma(T[4 * i + 2], pn[0], T[4 * i]));
-                            W[2 * i + 1] = fma(T[4 * i + 3], pn[2], fma(T[4 * i + 2], pn[1], T[4 * i + 1]));
-                        }
-                        rows();
-                    }
-                }
-                // P = Y U^-1 (symmetrised)
-                const double U11 = W[0], U12 = W[1], U21 = W[2], U22 = W[3];
-                const double Y11 = W[4], Y12 = W[5], Y21 = W[6], Y22 = W[7];
-                const double idet = frcp(fma(U11, U22, -U12 * U21));
-                const double q11 = fma(Y11, U22, -Y12 * U21) * idet, q12 = fma(Y12, U11, -Y11 * U12) * idet;
-                const double q21 = fma(Y21, U22, -Y22 * U21) * idet, q22 = fma(Y22, U11, -Y21 * U12) * idet;
-                P11[0] = q11; P12[0] = 0.5 * (q12 + q21); P22[0] = q22;
-                // the stage quantities of node k from P_{k+1}
-                double n11, n12, n22;
-                if constexpr (kWaves == 1) {
-                    n11 = from_next(P11[0]); n12 = from_next(P12[0]); n22 = from_next(P22[0]);
-                } else {
-                    // two waves: node 32's value function is already in wave 0 (pnx), no exchange
-                    n11 = dpp<kWaveShl1>(P11[0]); n12 = dpp<kWaveShl1>(P12[0]); n22 = dpp<kWaveShl1>(P22[0]);
-                    if (wave_idx() == 0 && (lane & 31) == 31) { n11 = pnx[0]; n12 = pnx[1]; n22 = pnx[2]; }
-                }
-                const double e1 = be1[0], e2 = be2[0];
-                const double Q = fma(E11[0], n11, fma(E12[0], n12, fma(E22[0], n22, Rt[0])));
-                const double PB1 = fma(n11, e1, n12 * e2), PB2 = fma(n12, e1, n22 * e2);
-                const double U1 = PB1, U2 = fma(PB1, a12k, PB2 * a22k);
-                const double iQ = frcp(Q);
-                W1[0] = iQ * U1; W2[0] = iQ * U2;
-                Quu[0] = Q; iQs[0] = iQ;
-            } else
-            // backward sweep: every lane maps its neighbour's value function through its own
-            // stage; after step j lane N-1-j is final.  Terminal/idle lanes have Phi = 0, B = 0.
-            for (int step = 0; step < N; ++step) {
-                double n11[NAX], n12[NAX], n22[NAX];
-#pragma unroll
-                for (int j = 0; j < NAX; ++j) {
-                    n11[j] = from_next(P11[j]); n12[j] = from_next(P12[j]); n22[j] = from_next(P22[j]);
-                }
-#pragma unroll
-                for (int j = 0; j < NAX; ++j) {
-                    const double e1 = be1[j], e2 = be2[j];
-                    const double Q = fma(E11[j], n11[j], fma(E12[j], n12[j], fma(E22[j], n22[j], Rt[j])));
-                    const double PB1 = fma(n11[j], e1, n12[j] * e2), PB2 = fma(n12[j], e1, n22[j] * e2);
-                    const double U1 = PB1, U2 = fma(PB1, a12k, PB2 * a22k);
-                    const double X12 = fma(n11[j], a12k, n12[j] * a22k);
-                    const double X22 = fma(A11k, n11[j], fma(A12k, n12[j], fma(A22k, n22[j], X22d)));
-                    const double iQ = frcp(Q);
-                    const double w1 = iQ * U1, w2 = iQ * U2;
-                    P11[j] = fma(-w1, U1, fma(f11, n11[j], X11d));
-                    P12[j] = fma(-w1, U2, X12);
-                    P22[j] = fma(-w2, U2, X22);
-                    W1[j] = w1; W2[j] = w2;
-                    Quu[j] = Q; iQs[j] = iQ;
-                }
-            }
-            bool bad = false;
-#pragma unroll
-            for (int j = 0; j < NAX; ++j) bad = bad || !(Quu[j] > 0.0) || !isfinite(Quu[j]);
-            ok = !wany(bad);
         }
         STAMP_ADD(9, attempt);
         STAMP(3);
@@ -1125,11 +1258,10 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             ++nfilt;
         }
         // -------- accept the step ----------------------------------------------------
+        // (the quantities the factor wave needs come first: the overlapped build hands them over before the rest)
 #pragma unroll
         for (int j = 0; j < NAX; ++j) {
-            snc[j] = snt[j]; g1[j] = g1t[j]; g2[j] = g2t[j]; gz[j] = gzt[j];
-            p[j] = fma(alpha, dp[j], p[j]); v[j] = fma(alpha, dv[j], v[j]);
-            zz[j] = fma(alpha, dz[j], zz[j]);
+            snc[j] = snt[j];
             lp[j] = fma(alpha, dlp[j], lp[j]); lv[j] = fma(alpha, dlv[j], lv[j]);
             th[j] = fma(alpha, dth[j], th[j]);
             const double il = frcp(th[j] - lo), iu = frcp(hi - th[j]);
@@ -1137,8 +1269,35 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             const double zun = fmax(fmin(fma(az, dzu[j], zu[j]), 1e10 * mu * iu), 1e-10 * mu * iu);
             zl[j] = uon ? zln : 0.0; zu[j] = uon ? zun : 0.0;
         }
+        if constexpr (OVL) publish();
+#pragma unroll
+        for (int j = 0; j < NAX; ++j) {
+            g1[j] = g1t[j]; g2[j] = g2t[j]; gz[j] = gzt[j];
+            p[j] = fma(alpha, dp[j], p[j]); v[j] = fma(alpha, dv[j], v[j]);
+            zz[j] = fma(alpha, dz[j], zz[j]);
+        }
         theta = th_t;
         STAMP(7);
+    }
+    if constexpr (OVL) {
+        // The exit funnel of the overlapped build.  The iteration loop has no return, and every way out of it
+        // (status 0 between barriers A and B; status -3, the failed line search with its hand-over to the
+        // restoration phases or status -2, all after barrier B and before the update's barrier A; max_iter at the
+        // loop head, after the barrier A of a point that is then not used; a loop of no iterations) arrives here.
+        // Invariant: this wave crosses barriers A, B, A, B, ... only in publish() (the first Newton iteration's
+        // head, the accepted update) and at the head of the Riccati block (none in the least-square iteration, its
+        // `continue` included, in the retries or in the correction passes), then sets the stop word and crosses
+        // exactly one more barrier, here.  The
+        // factor wave crosses a barrier, tests the stop word and goes on to the next barrier, so it meets each of
+        // this wave's barriers in turn whatever their role, and leaves at the first test that finds the word set:
+        // after the stop barrier at the latest (or earlier, having seen the word before this wave arrived; a
+        // terminated wave takes no part in a barrier).  Both waves thus execute the same number of barriers up
+        // to the factor wave's end, and nothing below waits for it.
+        if (lane == 0) g_pm_ovl.flag[0] = 1;
+        __syncthreads();                                                    // the stop barrier
+#ifdef DART_STAMPS
+        t_acc_[13] = (unsigned)__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[3]);
+#endif
     }
 
     // -------- outputs ---------------------------------------------------------------
@@ -1241,15 +1400,20 @@ __device__ __noinline__ void pmpc_resto_tail(const int b, const uint32_t seq, co
 
 // FUSE: resto mode 3, the handed-over instance continues in pmpc_resto_tail (no second launch)
 template <int NAX, bool QSCAN, bool ONEROW = false, bool SHORT2 = false, bool RED = false, bool OCC2 = false,
-          bool FUSE = false>
-__global__ __launch_bounds__(kWave * kWaves) __attribute__((amdgpu_waves_per_eu(OCC2 ? 2 : ((QSCAN || NAX == 2) ? 1 : 2))))
+          bool FUSE = false, bool OVL = false>
+__global__ __launch_bounds__(kWave * kWaves * (OVL ? 2 : 1)) __attribute__((amdgpu_waves_per_eu(OCC2 ? 2 : ((QSCAN || NAX == 2) ? 1 : 2))))
 void pmpc_ipm_kernel(PmpcArgs a) {
     // small batches: the launcher deals 8 blocks per instance and only every 8th works, so all
     // instances land on one XCD (blocks go round-robin over the 8 XCDs) and share its L2 for the code
     if (blockIdx.x % a.pack) return;
     const int b = blockIdx.x / a.pack;
-    const bool handed = pmpc_solve<NAX, QSCAN, ONEROW, SHORT2, RED>(a, b);
+    // OVL: launched with two waves; wave 0 solves, wave 1 factors for it and returns false when told to stop
+    const bool handed = pmpc_solve<NAX, QSCAN, ONEROW, SHORT2, RED, OVL>(a, b);
     if constexpr (FUSE) {
+        // OVL: pmpc_resto_tail and pmpc_resto_solve are written for one wave and cross __syncthreads(), real
+        // barriers in a two-wave launch.  The solver wave enters here only past the stop barrier of pmpc_solve's
+        // exit funnel, after which the factor wave runs nothing but its way out of the kernel; a barrier waits only
+        // for the waves of the workgroup that have not terminated, so the tail's barriers concern this wave alone.
         if (PM_EXPECT(handed, 0)) pmpc_resto_tail(b, a.seq, 3u, kernarg_addr());
     }
 }
@@ -1459,7 +1623,24 @@ extern "C" hipError_t dartmpc_launch_pmpc(const dartmpc::PmpcArgs* args, hipStre
         dartmpc::resto_fuse_enabled())
         a.resto = 3;
     const bool fuse = a.resto == 3;
-    if (a.N <= 23 && occ2) {        // (N <= 15 too: the short-scan build at two waves beats the one-row build at one)
+    // The overlapped builds (two waves per instance: the second factors the Riccati scan of the point while the
+    // first evaluates it and updates mu) where a CU has SIMDs to spare: batches of at most 32 (one instance per
+    // CU of one XCD) on IPOPT's path at N = 16..31.  Larger batches, the resident server and the rollout
+    // kernels keep the one-wave builds.  DART_PMPC_OVERLAP=0: the one-wave builds here too (A/B).
+    const bool ovl = a.pack == 8 && !a.reduced && !occ2 && a.N >= 16 && a.N <= 31 && a.B <= qscan_max_b &&
+                     dartmpc::pmpc_overlap_enabled();
+    const dim3 block2(2 * dartmpc::kWave);
+    if (ovl && a.N <= 23) {
+        if (fuse)
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, true, true>), grid, block2, 0, stream, a);
+        else
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, false, true>), grid, block2, 0, stream, a);
+    } else if (ovl) {
+        if (fuse)
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, true, true>), grid, block2, 0, stream, a);
+        else
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, false, true>), grid, block2, 0, stream, a);
+    } else if (a.N <= 23 && occ2) {        // (N <= 15 too: the short-scan build at two waves beats the one-row build at one)
         hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
     } else if (a.N <= 15 && a.B <= qscan_max_b) {
         if (hipError_t e = dartmpc_launch_pmpc_seq(&a, grid.x, stream, 1)) return e;

@@ -34,6 +34,16 @@ inline bool resto_fuse_enabled() {
     }();
     return on;
 }
+// host: PMPC batches of at most 32 at N = 16..31 take the overlapped builds (a second wave factors the Riccati
+// scan while the solving wave evaluates the point, pmpc_ipm.hip) unless DART_PMPC_OVERLAP=0 (the one-wave
+// builds everywhere, for A/B)
+inline bool pmpc_overlap_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("DART_PMPC_OVERLAP");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
 // host, diagnostic: DART_FORCE_WG2=1 runs RMPC and LMPC on their two-wave builds at every N (A/B of the two-wave
 // machinery against the one-wave kernels on the same instances; tools/wg2_ab.py)
 inline bool force_wg2() {

@@ -39,4 +39,9 @@ print(f"  scan-path Riccati passes {int(st[11])}")
 it0 = int(st[0:9].sum() - st[0] - st[8])
 print(f"  first iteration {int(st[12])} cycles, mean iteration {it0 / max(1, out['iters'][0]):.0f} cycles")
 print(f"  riccati passes {int(st[9])}, line-search trials {int(st[10])}, iterations with a correction {int(st[15])}")
+if st[13]:
+    # the overlapped build (B <= 32, N = 16..31): the riccati span above is the solving wave's wait for the factor
+    # wave plus its LDS read; this is the factor wave's own time from barrier A to its arrival at barrier B
+    print(f"  factor wave: {int(st[13])} cycles between its barriers, per-iter {st[13] / max(1, out['iters'][0]):.0f}")
+    print(f"  solving wave: {int(st[14])} cycles waiting at barrier B, per-iter {st[14] / max(1, out['iters'][0]):.0f}")
 print("batch iters:", out["iters"].tolist())
