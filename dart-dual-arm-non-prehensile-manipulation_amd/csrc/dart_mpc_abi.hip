@@ -1266,9 +1266,13 @@ dartmpc::PlantArgs plant_args(const dart_mpc_handle* h, const dart_plant_config*
 // the checks every rollout / loop-step entry shares: the call writes the log rows k .. k + steps - 1
 int loop_check(dart_mpc_handle* h, int variant, const dart_plant_config* plant, int B, int k, int steps, int log_rows) {
     if (h->cfg.variant != variant)
-        return fail(h, DART_MPC_EINVAL, variant == DART_MPC_RMPC ? "handle is not an RMPC handle" : "handle is not a PMPC handle");
+        return fail(h, DART_MPC_EINVAL, variant == DART_MPC_RMPC   ? "handle is not an RMPC handle"
+                                        : variant == DART_MPC_LMPC ? "handle is not an LMPC handle"
+                                                                   : "handle is not a PMPC handle");
     if (!plant) return fail(h, DART_MPC_EINVAL, "null plant config");
-    if (!(plant->v_c > 0.0) || !(plant->mu_c >= 0.0)) return fail(h, DART_MPC_EINVAL, "plant config: v_c > 0, mu_c >= 0");
+    // (the LMPC plant does not use mu_c / v_c)
+    if (variant != DART_MPC_LMPC && (!(plant->v_c > 0.0) || !(plant->mu_c >= 0.0)))
+        return fail(h, DART_MPC_EINVAL, "plant config: v_c > 0, mu_c >= 0");
     if (B < 0 || k < 0 || steps < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
     if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
     if ((long long)k + steps > log_rows) return fail(h, DART_MPC_EINVAL, "k0 + steps exceeds log_rows");
@@ -1327,6 +1331,12 @@ struct RollStage {
     // a log: rows [r0, r1) of `rowbytes` each travel (up only where the call may leave entries of them untouched)
     int add_log(void* host, size_t rows, size_t rowbytes, size_t r0, size_t r1, bool up) {
         arr.push_back({host, rows * rowbytes, r0 * rowbytes, (r1 - r0) * rowbytes, up, true, total});
+        total += (rows * rowbytes + 255) & ~size_t(255);
+        return (int)arr.size() - 1;
+    }
+    // an input with one row per step (LMPC's noise): rows [r0, r1) go up, nothing comes down
+    int add_rows_in(const void* host, size_t rows, size_t rowbytes, size_t r0, size_t r1) {
+        arr.push_back({const_cast<void*>(host), rows * rowbytes, r0 * rowbytes, (r1 - r0) * rowbytes, true, false, total});
         total += (rows * rowbytes + 255) & ~size_t(255);
         return (int)arr.size() - 1;
     }
@@ -1564,6 +1574,192 @@ int dart_pmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant,
                                        S.dev<double>(h, i_x), S.dev<double>(h, i_tilt), S.dev<double>(h, l_X),
                                        S.dev<double>(h, l_U), S.dev<double>(h, l_Q), S.dev<double>(h, l_L),
                                        S.dev<int32_t>(h, l_st), S.dev<int32_t>(h, l_it), s))
+        return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// LMPC closed loop (lmpc_loop_kernel between the unchanged policy + solve launches)
+namespace {
+
+// the solve's per-step arrays of an LMPC rollout, the two warm-start buffers the solves alternate between, and
+// one zeroed noise row, in the handle (B_max instances)
+struct LmpcLoopScratch {
+    double *state, *u0, *f, *wbuf[2];
+    int32_t *status, *iters;
+    float* zero_noise;
+};
+
+int lmpc_loop_scratch(dart_mpc_handle* h, LmpcLoopScratch& L) {
+    const size_t Bm = (size_t)h->cfg.B_max, nw = (size_t)dart_lmpc_nw(h->cfg.N);
+    auto al = [](size_t n) { return (n + 255) & ~size_t(255); };
+    const size_t cnt[8] = {8 * 8, 8 * 2, 8, 8 * nw, 8 * nw, 4, 4, 4 * 34};
+    size_t off[9];
+    off[0] = 0;
+    for (int i = 0; i < 8; ++i) off[i + 1] = off[i] + al(cnt[i] * Bm);
+    if (!h->loop_buf) {
+        HIPCHK(h, hipMalloc((void**)&h->loop_buf, off[8]), "hipMalloc (rollout scratch)");
+        // (only the noise row needs a value: pre writes what the solve reads, the solve what post reads)
+        const hipError_t e = hipMemset(h->loop_buf + off[7], 0, off[8] - off[7]);
+        if (e != hipSuccess) {
+            (void)hipFree(h->loop_buf);
+            h->loop_buf = nullptr;
+            return fail(h, DART_MPC_EHIP, "hipMemset (rollout scratch)", e);
+        }
+    }
+    char* p = h->loop_buf;
+    L.state = (double*)(p + off[0]); L.u0 = (double*)(p + off[1]); L.f = (double*)(p + off[2]);
+    L.wbuf[0] = (double*)(p + off[3]); L.wbuf[1] = (double*)(p + off[4]);
+    L.status = (int32_t*)(p + off[5]); L.iters = (int32_t*)(p + off[6]); L.zero_noise = (float*)(p + off[7]);
+    return DART_MPC_OK;
+}
+
+// the argument checks the three LMPC rollout entries share (after loop_check)
+int lmpc_rollout_check(dart_mpc_handle* h, const dart_lmpc_policy_config* pcfg, int B, const float* weights,
+                       std::initializer_list<const void*> always, std::initializer_list<const void*> with_policy) {
+    if (any_null(always)) return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (weights) {
+        dartmpc::PolicyArgs chk;
+        if (policy_args(pcfg, B, weights, chk) != DART_MPC_OK) return fail(h, DART_MPC_EINVAL, "bad policy config");
+        if (any_null(with_policy)) return fail(h, DART_MPC_EINVAL, "null pointer (policy state)");
+    }
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                            int B, int k, int do_post, int do_pre, int log_rows,
+                            const double* target, const double* plant_pvec,
+                            double* x, double* tilt, double* u_prev, const double* model_params, double* state,
+                            const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                            double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                            int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_LMPC, plant, B, k, do_post ? 1 : 0, log_rows)) return rc;
+    if (any_null({target, plant_pvec, x, tilt, u_prev, model_params, state, u0, f, status, iters, log_X, log_U,
+                  log_pos_error, log_pvec, log_loss, log_status, log_iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    dartmpc::LmpcLoopArgs a;
+    a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+    a.a_lag = plant->tau > 0.0 ? 1.0 - std::exp(-h->cfg.Ts / plant->tau) : 1.0;
+    a.Ts = h->cfg.Ts;
+    a.target = target; a.plant_pvec = plant_pvec; a.x = x; a.tilt = tilt; a.u_prev = u_prev;
+    a.model_params = model_params; a.state = state; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
+    a.log_X = log_X; a.log_U = log_U; a.log_pos_error = log_pos_error; a.log_pvec = log_pvec; a.log_loss = log_loss;
+    a.log_status = log_status; a.log_iters = log_iters;
+    HIPCHK(h, dartmpc_launch_lmpc_loop(&a, stream ? (hipStream_t)stream : h->stream), "loop-step kernel launch");
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                          int B, int k0, int steps, int log_rows,
+                          const double* target, const double* prm, const double* plant_pvec, const double* current_k,
+                          const float* weights, const float* noise,
+                          double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                          int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                          double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                          int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_LMPC, plant, B, k0, steps, log_rows)) return rc;
+    if (int rc = lmpc_rollout_check(h, pcfg, B, weights,
+                                    {target, prm, plant_pvec, x, tilt, u_prev, w, model_params, log_X, log_U,
+                                     log_pos_error, log_pvec, log_loss, log_status, log_iters},
+                                    {current_k, obs_mean, obs_M2, obs_count, history, timestep}))
+        return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    LmpcLoopScratch L;
+    if (int rc = lmpc_loop_scratch(h, L)) return rc;
+    void* s = stream ? stream : (void*)h->stream;
+    auto step = [&](int k, int post, int pre) {
+        return dart_lmpc_loop_step_dev(h, plant, B, k, post, pre, log_rows, target, plant_pvec, x, tilt, u_prev,
+                                       model_params, L.state, L.u0, L.f, L.status, L.iters, log_X, log_U, log_pos_error,
+                                       log_pvec, log_loss, log_status, log_iters, s);
+    };
+    // Warm start: with the restoration phases on, an instance that <false> hands over has written the iterate of
+    // its failed iteration to w_out before lmpc_solve<true> (the tail, or the second launch) redoes the set-up from
+    // w_warm, so w_warm == w_out would change the scalings of the resumed solve.  The solves
+    // alternate between two handle-owned buffers instead: the first reads the caller's w, the last writes it.
+    // Without the restoration phases nothing is handed over and the row is rewritten in place.
+    const bool in_place = !h->cfg.restoration;
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        const double* w_in = (in_place || j == 0) ? w : L.wbuf[(j - 1) & 1];
+        double* w_out = (in_place || (j == steps - 1 && j > 0)) ? w : L.wbuf[j & 1];
+        int rc;
+        if (weights)
+            rc = dart_lmpc_policy_solve_batch_dev(h, pcfg, B, weights, L.state, u_prev, target, current_k, obs_mean, obs_M2,
+                                                  obs_count, history, timestep,
+                                                  noise ? noise + ((size_t)k0 + j) * B * 34 : L.zero_noise, model_params,
+                                                  nullptr, prm, w_in, L.u0, L.f, w_out, L.status, L.iters, s);
+        else
+            rc = dart_lmpc_solve_batch_dev(h, B, L.state, u_prev, model_params, target, prm, w_in, L.u0, L.f, w_out,
+                                           L.status, L.iters, s);
+        if (rc) return rc;
+        if (w_out != w && j == steps - 1)       // a one-step call: the iterate back into the caller's w
+            HIPCHK(h, hipMemcpyAsync(w, w_out, sizeof(double) * (size_t)dart_lmpc_nw(h->cfg.N) * B,
+                                     hipMemcpyDeviceToDevice, (hipStream_t)s), "copy w");
+        if ((rc = step(k0 + j, 1, j + 1 < steps))) return rc;
+    }
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                      int B, int k0, int steps, int log_rows,
+                      const double* target, const double* prm, const double* plant_pvec, const double* current_k,
+                      const float* weights, const float* noise,
+                      double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                      int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                      double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                      int32_t* log_status, int32_t* log_iters, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_LMPC, plant, B, k0, steps, log_rows)) return rc;
+    if (int rc = lmpc_rollout_check(h, pcfg, B, weights,
+                                    {target, prm, plant_pvec, x, tilt, u_prev, w, model_params, log_X, log_U,
+                                     log_pos_error, log_pvec, log_loss, log_status, log_iters},
+                                    {current_k, obs_mean, obs_M2, obs_count, history, timestep}))
+        return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t), F = sizeof(float);
+    const size_t nw = (size_t)dart_lmpc_nw(h->cfg.N);
+    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
+    RollStage S;
+    const int i_tg = S.add(target, 8 * nB * D, false), i_prm = S.add(prm, dartmpc::LM_NPRM * nB * D, false);
+    const int i_pp = S.add(plant_pvec, 34 * nB * D, false);
+    const int i_x = S.add(x, 8 * nB * D, true), i_tilt = S.add(tilt, 2 * nB * D, true), i_up = S.add(u_prev, 2 * nB * D, true);
+    const int i_w = S.add(w, nw * nB * D, true), i_mp = S.add(model_params, 34 * nB * D, true);
+    int i_ck = -1, i_wt = -1, i_nz = -1, i_om = -1, i_o2 = -1, i_oc = -1, i_hi = -1, i_ts = -1;
+    if (weights) {
+        i_ck = S.add(current_k, 34 * nB * D, false);
+        i_wt = S.add(weights, (size_t)DART_LMPC_POLICY_NWEIGHTS * F, false);
+        if (noise) i_nz = S.add_rows_in(noise, R, 34 * nB * F, r0, r1);
+        i_om = S.add(obs_mean, 52 * nB * D, true); i_o2 = S.add(obs_M2, 52 * nB * D, true);
+        i_oc = S.add(obs_count, nB * I, true); i_hi = S.add(history, 520 * nB * F, true);
+        i_ts = S.add(timestep, nB * I, true);
+    }
+    const int l_X = S.add_log(log_X, R, 8 * nB * D, r0, r1, false), l_U = S.add_log(log_U, R, 2 * nB * D, r0, r1, false);
+    const int l_pe = S.add_log(log_pos_error, R, nB * D, r0, r1, false), l_pv = S.add_log(log_pvec, R, 34 * nB * D, r0, r1, false);
+    const int l_L = S.add_log(log_loss, R, nB * D, r0, r1, false);
+    const int l_st = S.add_log(log_status, R, nB * I, r0, r1, false), l_it = S.add_log(log_iters, R, nB * I, r0, r1, false);
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    auto dd = [&](int i) { return i < 0 ? nullptr : S.dev<double>(h, i); };
+    auto di = [&](int i) { return i < 0 ? nullptr : S.dev<int32_t>(h, i); };
+    auto df = [&](int i) { return i < 0 ? nullptr : S.dev<float>(h, i); };
+    if (int rc = dart_lmpc_rollout_dev(h, plant, pcfg, B, k0, steps, log_rows, dd(i_tg), dd(i_prm), dd(i_pp), dd(i_ck),
+                                       df(i_wt), df(i_nz), dd(i_x), dd(i_tilt), dd(i_up), dd(i_w), dd(i_om), dd(i_o2),
+                                       di(i_oc), df(i_hi), di(i_ts), dd(i_mp), dd(l_X), dd(l_U), dd(l_pe), dd(l_pv),
+                                       dd(l_L), di(l_st), di(l_it), s))
         return rc;
     if (int rc = S.download(h, s)) return rc;
     HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");

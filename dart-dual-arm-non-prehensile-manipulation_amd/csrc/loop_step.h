@@ -76,7 +76,37 @@ struct PmpcLoopArgs {
     int32_t* log_iters;         // [..]
 };
 
+// harness.LmpcPlant: the same tilt lag, then one RK4 step at Ts of the LMPC model itself (safe_dynamics,
+// LMPC/src/controller/rlmpc2.py:260-429) with the lagged tilt as input and the instance's true parameters
+// plant_pvec.  mu_c / v_c of dart_plant_config are not used: the model's Stribeck terms are its Coulomb friction.
+// The driver's u_cmd *= -1 and the quaternion (LMPC/src/run.py:257-261) are MuJoCo tray conventions and are not
+// applied, as in the other two plants.
+struct LmpcLoopArgs {
+    int B;
+    int k, do_post, do_pre, log_rows;
+    double a_lag, Ts;
+    const double* target;       // [B][8]
+    const double* plant_pvec;   // [B][34] the plant's parameter vector (index map of rlmpc2.py:301-334)
+    double* x;                  // [B][8] in/out
+    double* tilt;               // [B][2] in/out
+    double* u_prev;             // [B][2] out (post): the next solve's u_prev and the policy's control
+    const double* model_params; // [B][34] the parameter row the solve used (logged by post)
+    double* state;              // [B][8] the solve's input (written by pre)
+    const double* u0;           // [B][2]
+    const double* f;            // [B]
+    const int32_t* status;      // [B]
+    const int32_t* iters;       // [B]
+    double* log_X;              // [log_rows][B][8] the state the solve saw
+    double* log_U;              // [..][2]
+    double* log_pos_error;      // [..] |x_next[[0, 2]] - target[[0, 2]]| after the plant step (run.py:274)
+    double* log_pvec;           // [..][34]
+    double* log_loss;           // [..]
+    int32_t* log_status;        // [..]
+    int32_t* log_iters;         // [..]
+};
+
 }  // namespace dartmpc
 
+extern "C" hipError_t dartmpc_launch_lmpc_loop(const dartmpc::LmpcLoopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args, hipStream_t stream);

@@ -3,12 +3,15 @@
 // rmpc_loop_kernel: post(k) = the log rows, the episode end and the plant step of harness.run_rmpc; pre(k+1) =
 // the RLS features / targets, the reference governor and the staged reference of the next solve
 // (RMPC/dev_dual/rob_ctrl.py:335-351).  pmpc_loop_kernel: the same for harness.run_pmpc
-// (PMPC/main_parallel_enhanced.py:333-348: log, tilt -> quaternion, plant step, next state).
+// (PMPC/main_parallel_enhanced.py:333-348: log, tilt -> quaternion, plant step, next state).  lmpc_loop_kernel:
+// the same for harness.run_lmpc (LMPC/src/run.py:256-286: log, plant step of the LMPC model, next state); its
+// lane mapping is described at the kernel.
 //
-// One wave64 per instance, kLoopWaves instances per block; lane i owns horizon node i (the staged reference),
-// the per-instance scalars are computed by every lane and stored by one.  Plain fp64 in the operation order of
-// the numpy code (no contraction into fma), no LDS.  A lane only ever reads state that this launch does not
-// write, or keeps it in registers across the post and pre halves: nothing is read back from memory in a launch.
+// RMPC / PMPC: one wave64 per instance, kLoopWaves instances per block; lane i owns horizon node i (the staged
+// reference), the per-instance scalars are computed by every lane and stored by one.  All three: plain fp64 in the
+// operation order of the numpy code (no contraction into fma), no LDS.  A lane only ever reads state that this
+// launch does not write, or keeps it in registers across the post and pre halves: nothing is read back from memory
+// in a launch.
 #include "loop_step.h"
 
 #pragma clang fp contract(off)
@@ -160,6 +163,122 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_loop_kernel(PmpcLo
     if (a.do_pre && lane < 6) a.x0[6 * b + lane] = x[lane];
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// LMPC (harness.run_lmpc): post(k) = the log row, u_prev, the tilt lag and one RK4 step of the LMPC model
+// (safe_dynamics, rlmpc2.py:260-429) with the plant's own parameter vector; pre(k+1) = the solve's state.
+//
+// kLmGroup = 8 lanes per instance, 8 instances per wave64 (there is no per-node reference to own).  An RK4 stage
+// has six independent Stribeck terms (tanh + exp each) and two sines: lane r of a group evaluates term r (lanes
+// 6, 7 repeat terms 0, 1) and the sine of th_x (even r) or th_y (odd r), the same instructions on every lane, and
+// the group exchanges the eight values by shuffles; the cheap combination is computed by every lane.  The serial
+// chain of a step is 4 x (one Stribeck + one sine) in place of 4 x (six + two).  Every term is computed by exactly
+// one expression in numpy's order (harness.LmpcPlant), so the result does not depend on the lane mapping.
+constexpr int kLmGroup = 8;
+constexpr int kLmLoopThreads = 256;
+constexpr double kLmG = 9.81;      // rlmpc2.py:354
+
+// squash_param (:296-298)
+__device__ __forceinline__ double lm_squash(double p) { return fabs(p) + 1e-6; }
+
+struct LmPlantPrm {
+    double m_x, m_y, c_x, c_y, k_x, k_y, I_x, I_y, r_x, r_y, c_rot_x, c_rot_y, h_com_x, h_com_y;
+    double Fs, Fc, Bv, vs, eps;     // the Stribeck term of this lane
+};
+
+// safe_dynamics at x with sin(tilt) = (sa, sb): xdot [8].  r = lane in the group.
+__device__ __forceinline__ void lm_plant_dyn(const LmPlantPrm& P, int r, const double* x, double sa, double sb,
+                                             double* d) {
+    const double px = x[0], vx = x[1], py = x[2], vy = x[3], th_x = x[4], om_x = x[5], th_y = x[6], om_y = x[7];
+    const double v_slip_x = vx - P.r_x * om_y;                          // :387-391
+    const double v_slip_y = vy - (-P.r_y * om_x);
+    const int t = r < 6 ? r : r - 6;
+    const double v = t == 0 ? vx : t == 1 ? vy : t == 2 ? v_slip_x : t == 3 ? v_slip_y : t == 4 ? om_x : om_y;
+    const double e = exp(-fabs(v) / (P.vs + 1e-12));                    // :372-376
+    const double F = tanh(v / P.eps) * (P.Fc + (P.Fs - P.Fc) * e) + P.Bv * v;
+    const double s = sin((r & 1) ? th_y : th_x);
+    const double Ff_x = __shfl(F, 0, kLmGroup), Ff_y = __shfl(F, 1, kLmGroup);
+    const double F_roll_x = __shfl(F, 2, kLmGroup), F_roll_y = __shfl(F, 3, kLmGroup);
+    const double T_noslip_x = __shfl(F, 4, kLmGroup), T_noslip_y = __shfl(F, 5, kLmGroup);
+    const double s_thx = __shfl(s, 0, kLmGroup), s_thy = __shfl(s, 1, kLmGroup);
+    const double Gx = P.m_x * (kLmG * sa), Gy = P.m_y * (kLmG * sb);   // :353-357
+    const double tau_slip_x = -P.r_y * F_roll_y, tau_slip_y = -P.r_x * F_roll_x;      // :402-403
+    const double T_damp_x = P.c_rot_x * om_x, T_damp_y = P.c_rot_y * om_y;            // :410-411
+    const double tau_topple_x = -P.m_y * kLmG * P.h_com_x * s_thx;      // :414-415
+    const double tau_topple_y = -P.m_x * kLmG * P.h_com_y * s_thy;
+    const double tau_x = tau_slip_x - T_noslip_x - T_damp_x + tau_topple_x;           // :418-419
+    const double tau_y = tau_slip_y - T_noslip_y - T_damp_y + tau_topple_y;
+    const double rhs_x = Gx - P.c_x * vx - P.k_x * px - Ff_x - F_roll_x;              // :427
+    const double rhs_y = Gy - P.c_y * vy - P.k_y * py - Ff_y - F_roll_y;
+    d[0] = vx; d[1] = rhs_x / P.m_x; d[2] = vy; d[3] = rhs_y / P.m_y;                 // :429
+    d[4] = om_x; d[5] = tau_x / (P.I_x + 1e-12); d[6] = om_y; d[7] = tau_y / (P.I_y + 1e-12);   // :422-423
+}
+
+__global__ __launch_bounds__(kLmLoopThreads) void lmpc_loop_kernel(LmpcLoopArgs a) {
+    const int r = threadIdx.x & (kLmGroup - 1);
+    const int b = (blockIdx.x * kLmLoopThreads + threadIdx.x) / kLmGroup;
+    if (b >= a.B) return;                    // uniform over the group (the shuffles stay inside it)
+    double x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = a.x[8 * b + i];
+
+    if (a.do_post) {
+        double tilt[2] = {a.tilt[2 * b], a.tilt[2 * b + 1]};
+        const double u[2] = {a.u0[2 * b], a.u0[2 * b + 1]};
+        const size_t row = (size_t)a.k * a.B + b;
+        for (int i = r; i < 34; i += kLmGroup) a.log_pvec[34 * row + i] = a.model_params[34 * b + i];
+        if (r == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a.log_X[8 * row + i] = x[i];
+            a.log_U[2 * row] = u[0]; a.log_U[2 * row + 1] = u[1];
+            a.log_loss[row] = a.f[b];
+            a.log_status[row] = a.status[b];
+            a.log_iters[row] = a.iters[b];
+            a.u_prev[2 * b] = u[0]; a.u_prev[2 * b + 1] = u[1];
+        }
+        // harness.LmpcPlant.step
+        tilt[0] += a.a_lag * (u[0] - tilt[0]);
+        tilt[1] += a.a_lag * (u[1] - tilt[1]);
+        const double* pv = a.plant_pvec + 34 * b;
+        LmPlantPrm P;
+        P.m_x = lm_squash(pv[0]); P.m_y = lm_squash(pv[1]); P.c_x = lm_squash(pv[2]); P.c_y = lm_squash(pv[3]);
+        P.k_x = lm_squash(pv[4]); P.k_y = lm_squash(pv[5]); P.I_x = lm_squash(pv[16]); P.I_y = lm_squash(pv[17]);
+        P.r_x = lm_squash(pv[18]); P.r_y = lm_squash(pv[19]); P.c_rot_x = lm_squash(pv[20]); P.c_rot_y = lm_squash(pv[21]);
+        P.h_com_x = lm_squash(pv[32]); P.h_com_y = lm_squash(pv[33]);
+        {       // Stribeck rows [F_s, F_c, B, v_s, eps] (:301-334): x 6.., y 11.., rot x 22.., rot y 27..
+            const int t = r < 6 ? r : r - 6;
+            const int o = t == 0 || t == 2 ? 6 : t == 1 || t == 3 ? 11 : t == 4 ? 22 : 27;
+            P.Fs = pv[o]; P.Fc = pv[o + 1]; P.Bv = pv[o + 2]; P.vs = lm_squash(pv[o + 3]); P.eps = lm_squash(pv[o + 4]);
+        }
+        const double st = sin((r & 1) ? tilt[1] : tilt[0]);
+        const double sa = __shfl(st, 0, kLmGroup), sb = __shfl(st, 1, kLmGroup);
+        const double h = a.Ts;
+        double k1[8], k2[8], k3[8], k4[8], y[8];
+        lm_plant_dyn(P, r, x, sa, sb, k1);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[i] = x[i] + 0.5 * h * k1[i];
+        lm_plant_dyn(P, r, y, sa, sb, k2);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[i] = x[i] + 0.5 * h * k2[i];
+        lm_plant_dyn(P, r, y, sa, sb, k3);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[i] = x[i] + h * k3[i];
+        lm_plant_dyn(P, r, y, sa, sb, k4);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = x[i] + h * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) / 6;
+        if (r == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a.x[8 * b + i] = x[i];
+            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
+            const double dx = x[0] - a.target[8 * b], dy = x[2] - a.target[8 * b + 2];
+            a.log_pos_error[row] = sqrt(dx * dx + dy * dy);
+        }
+    }
+    if (a.do_pre && r == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a.state[8 * b + i] = x[i];
+    }
+}
+
 }  // namespace dartmpc
 
 extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, hipStream_t stream) {
@@ -176,5 +295,13 @@ extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args
     const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
     hipLaunchKernelGGL(dartmpc::pmpc_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0, stream,
                        *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_loop(const dartmpc::LmpcLoopArgs* args, hipStream_t stream) {
+    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
+    const int per = dartmpc::kLmLoopThreads / dartmpc::kLmGroup;
+    const int blocks = (args->B + per - 1) / per;
+    hipLaunchKernelGGL(dartmpc::lmpc_loop_kernel, dim3(blocks), dim3(dartmpc::kLmLoopThreads), 0, stream, *args);
     return hipGetLastError();
 }

@@ -13,7 +13,8 @@ Drop-in for the reference's MPC hot path:
   - ``ArmControl``, ``ArmSolver`` <- ARMCONTROL (PMPC/src/controller/arm.py), the per-arm impedance QP
   - ``harness``         <- the closed loops of main_parallel_enhanced.py / rob_ctrl.py without MuJoCo, and the
                            reference's result formats (logger.py npz + metrics, rob_ctrl.py episode JSON);
-                           ``harness.rollout_pmpc`` / ``rollout_rmpc`` run them resident on the device
+                           ``harness.rollout_pmpc`` / ``rollout_rmpc`` run them resident on the device;
+                           ``harness.run_lmpc`` / ``rollout_lmpc`` <- LMPC/src/run.py:256-286 with ``LmpcPlant``
   - ``Solver``, ``RmpcSolver``  the C ABI of include/dart_mpc.h (libdartmpc.so)
 """
 from ._lib import DartMPCError, LmpcSolver, RmpcSolver, Solver, build, lib, rls_update_batch, STATUS_NAMES  # noqa: F401

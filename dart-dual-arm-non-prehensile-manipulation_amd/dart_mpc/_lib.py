@@ -43,7 +43,7 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_mpc_build_flavor",
            "dart_plant_config_default", "dart_rmpc_loop_config_default", "dart_rmpc_loop_step_dev",
            "dart_pmpc_loop_step_dev", "dart_rmpc_rollout_dev", "dart_pmpc_rollout_dev", "dart_rmpc_rollout",
-           "dart_pmpc_rollout")
+           "dart_pmpc_rollout", "dart_lmpc_loop_step_dev", "dart_lmpc_rollout_dev", "dart_lmpc_rollout")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -88,6 +88,13 @@ PMPC_LOOP_IO = (("x0", 6, np.float64), ("u0", 2, np.float64), ("f", 0, np.float6
                 ("iters", 0, np.int32))
 PMPC_LOOP_LOGS = (("X", 6, np.float64), ("U_cmd", 2, np.float64), ("quat_tray", 4, np.float64), ("loss", 0, np.float64),
                   ("status", 0, np.int32), ("iters", 0, np.int32))
+LMPC_LOOP_STATE = (("x", 8, np.float64), ("tilt", 2, np.float64), ("u_prev", 2, np.float64), ("w", "nw", np.float64),
+                   ("obs_mean", 52, np.float64), ("obs_M2", 52, np.float64), ("obs_count", 0, np.int32),
+                   ("history", 520, np.float32), ("timestep", 0, np.int32), ("model_params", 34, np.float64))
+LMPC_LOOP_IO = (("state", 8, np.float64), ("u0", 2, np.float64), ("f", 0, np.float64), ("status", 0, np.int32),
+                ("iters", 0, np.int32))
+LMPC_LOOP_LOGS = (("X", 8, np.float64), ("U_cmd", 2, np.float64), ("pos_error", 0, np.float64), ("pvec", 34, np.float64),
+                  ("loss", 0, np.float64), ("status", 0, np.int32), ("iters", 0, np.int32))
 LOG_INT_FILL = int(np.iinfo(np.int32).min)      # prefill of the int32 logs (the float logs are prefilled with NaN)
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -230,7 +237,14 @@ def lib():
         for fn in (L.dart_rmpc_loop_step_dev, L.dart_pmpc_loop_step_dev, L.dart_rmpc_rollout_dev,
                    L.dart_pmpc_rollout_dev, L.dart_rmpc_rollout, L.dart_pmpc_rollout):
             fn.restype = ctypes.c_int
-    if hasattr(L, "dart_mpc_bind"):         # (absent only in older in-tree builds used for A/B timing)
+    if hasattr(L, "dart_lmpc_rollout_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_lmpc_loop_step_dev.argtypes = [vp, vp] + [ci] * 5 + [vp] * 19
+        L.dart_lmpc_loop_step_dev.restype = ctypes.c_int
+        for fn in (L.dart_lmpc_rollout_dev, L.dart_lmpc_rollout):
+            fn.argtypes = [vp, vp, vp] + [ci] * 4 + [vp] * 24
+            fn.restype = ctypes.c_int
+    if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
         L.dart_mpc_bind.restype = ctypes.c_int
         L.dart_mpc_solve_bound.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
@@ -745,6 +759,75 @@ class LmpcSolver(Solver):
             status, iters, stream or None)
         if rc != 0:
             self._err(rc, "dart_lmpc_policy_solve_batch_dev")
+
+    # -- device-resident closed loop (dart_lmpc_loop_step_dev / dart_lmpc_rollout_dev / dart_lmpc_rollout) ----
+    def loop_step_dev(self, B, k, do_post, do_pre, log_rows, target, plant_pvec, state, io, logs, plant=None, stream=0):
+        """One loop-step launch: post(k) and / or the next step's pre.  ``state`` / ``io`` / ``logs`` map the names
+        of LMPC_LOOP_STATE (x, tilt, u_prev and model_params are needed) / LMPC_LOOP_IO / LMPC_LOOP_LOGS to device
+        pointers (ints).  Asynchronous."""
+        plant = plant or plant_config()
+        rc = lib().dart_lmpc_loop_step_dev(
+            self._h, ctypes.byref(plant), int(B), int(k), int(do_post), int(do_pre), int(log_rows), target, plant_pvec,
+            *[ctypes.c_void_p(int(state[n])) for n in ("x", "tilt", "u_prev", "model_params")],
+            *_dev_ptrs(LMPC_LOOP_IO, io), *_dev_ptrs(LMPC_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_loop_step_dev")
+
+    def rollout_dev(self, B, k0, steps, log_rows, target, prm, plant_pvec, state, logs, pcfg=None, weights=0,
+                    current_k=0, noise=0, plant=None, stream=0):
+        """``steps`` closed-loop steps from step ``k0`` on the device, no host synchronisation in between: policy
+        step and warm-started solve (one launch for B <= 32, N <= 31), log, plant step (device pointers as in
+        ``loop_step_dev``; asynchronous on ``stream``).  ``weights`` = 0 runs the loop without a policy (every solve
+        uses ``state["model_params"]`` as its pvec); ``noise`` = 0 means zero noise.  Calling again with ``k0``
+        advanced continues the rollout."""
+        plant = plant or plant_config()
+        rc = lib().dart_lmpc_rollout_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg) if pcfg is not None else None,
+                                         int(B), int(k0), int(steps), int(log_rows), target, prm, plant_pvec,
+                                         current_k or None, weights or None, noise or None,
+                                         *_dev_ptrs(LMPC_LOOP_STATE, state), *_dev_ptrs(LMPC_LOOP_LOGS, logs),
+                                         stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_rollout_dev")
+
+    def rollout(self, k0, steps, target, plant_pvec, state, logs, policy=None, prm=None, noise=None, plant=None):
+        """Host arrays (blocking): ``state`` (LMPC_LOOP_STATE, see ``loop_state``) is advanced and ``logs``
+        (``loop_logs``) rows k0 .. k0+steps-1 are filled in place.  ``policy`` (a ``dart_mpc.lmpc.LmpcPolicy``) gives
+        the weights, the config and ``current_k``; None runs without a policy.  ``noise`` [rows, B, 34] fp32 holds
+        step k's draws in row k (None: zero noise)."""
+        B, rows = state["x"].shape[0], logs["X"].shape[0]
+        c = lambda a, n: np.ascontiguousarray(a, np.float64).reshape(B, n)
+        target, plant_pvec = c(target, 8), c(plant_pvec, 34)
+        prm = c(np.tile(LMPC_PRM_DEFAULT, (B, 1)) if prm is None else prm, 22)
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, np.float32)
+            if noise.shape != (rows, B, 34):
+                raise DartMPCError(f"rollout noise must have shape {(rows, B, 34)}")
+        pcfg = ck = wt = None
+        if policy is not None:
+            pcfg, wt = ctypes.byref(policy.cfg), np.ascontiguousarray(policy.weights, np.float32)
+            ck = c(policy.current_k, 34)
+        plant = plant or plant_config()
+        rc = lib().dart_lmpc_rollout(self._h, ctypes.byref(plant), pcfg, B, int(k0), int(steps), rows, _ptr(target),
+                                     _ptr(prm), _ptr(plant_pvec), _ptr(ck), _ptr(wt), _ptr(noise),
+                                     *_host_ptrs(LMPC_LOOP_STATE, state, (B,), nw=self.nw),
+                                     *_host_ptrs(LMPC_LOOP_LOGS, logs, (rows, B)), None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_rollout")
+
+    def loop_state(self, x0, policy=None, model_params=None):
+        """The state of a fresh rollout from the states ``x0`` [B, 8]: ``model_params`` starts at the policy's (its
+        ``current_k`` for a fresh policy), or at the given fixed parameter vectors without one; zeros elsewhere."""
+        x0 = np.asarray(x0, np.float64).reshape(-1, 8)
+        B = x0.shape[0]
+        st = {name: np.zeros(_loop_shape(B, width, nw=self.nw), dt) for name, width, dt in LMPC_LOOP_STATE}
+        st["x"][:] = x0
+        if policy is not None:
+            for name in ("obs_mean", "obs_M2", "obs_count", "timestep", "model_params"):
+                st[name][:] = getattr(policy, name)
+            st["history"][:] = np.asarray(policy.history, np.float32).reshape(B, 520)
+        if model_params is not None:
+            st["model_params"][:] = np.asarray(model_params, np.float64).reshape(B, 34)
+        return st
 
 
 def rls_update_batch(theta, P, phi, y, lam=0.995):

@@ -316,3 +316,183 @@ def rollout_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=No
                      episode_rows={name: lg[name] for name in ("pos_err", "pos_err_norm", "u_cmd", "timestep")})
         return episodes, lg["status"][:k], done, extra
     return episodes, lg["status"][:k], done
+
+
+# ---------------------------------------------------------------------------------------------
+# LMPC: LMPC/src/run.py:256-286 without MuJoCo
+LMPC_G = 9.81                  # rlmpc2.py:354
+
+
+class LmpcPlant:
+    """B objects on B tilting trays that obey the LMPC model itself (safe_dynamics, rlmpc2.py:260-429: translation
+    with Stribeck friction and rolling, rotation with slip torque, rotational Stribeck friction, damping and
+    toppling), each with its own true parameter vector ``pvec`` [B, 34] (index map :301-334; squash_param
+    |p| + 1e-6), integrated with RK4 at ``dt`` (:431-436, tilt held within a step).
+
+    state x = [px, vx, py, vy, th_x, om_x, th_y, om_y]; tilt = [a, b] follows the command through TrayPlant's
+    first-order lag.  The model's Stribeck terms are its Coulomb friction, so TrayPlant's ``mu_c`` / ``v_c`` have
+    no counterpart.  The driver's ``u_cmd *= -1`` and quaternion (run.py:257-261) are MuJoCo tray conventions and
+    are not applied, as in TrayPlant."""
+
+    def __init__(self, x0, pvec, tau=0.03, dt=0.002):
+        self.x = np.array(x0, dtype=float).reshape(-1, 8).copy()
+        B = self.x.shape[0]
+        self.pvec = np.array(pvec, dtype=float).reshape(B, 34).copy()
+        self.tilt = np.zeros((B, 2))
+        self.a_lag = 1.0 - np.exp(-dt / tau) if tau > 0 else 1.0
+        self.dt = float(dt)
+
+    @staticmethod
+    def _stribeck(v, F_s, F_c, Bv, v_s, eps):
+        e = np.exp(-np.abs(v) / (v_s + 1e-12))                              # :372-376
+        return np.tanh(v / eps) * (F_c + (F_s - F_c) * e) + Bv * v
+
+    def _f(self, x, sa, sb):
+        p = self.pvec
+        sq = lambda i: np.abs(p[:, i]) + 1e-6                               # :296-298
+        m_x, m_y, c_x, c_y, k_x, k_y = (sq(i) for i in range(6))
+        sx = (p[:, 6], p[:, 7], p[:, 8], sq(9), sq(10))
+        sy = (p[:, 11], p[:, 12], p[:, 13], sq(14), sq(15))
+        I_x, I_y, r_x, r_y, c_rot_x, c_rot_y = (sq(i) for i in range(16, 22))
+        srx = (p[:, 22], p[:, 23], p[:, 24], sq(25), sq(26))
+        sry = (p[:, 27], p[:, 28], p[:, 29], sq(30), sq(31))
+        h_com_x, h_com_y = sq(32), sq(33)
+        px, vx, py, vy, th_x, om_x, th_y, om_y = (x[:, i] for i in range(8))
+        g = LMPC_G
+        Gx = m_x * (g * sa)                                                 # :353-357
+        Gy = m_y * (g * sb)
+        Ff_x = self._stribeck(vx, *sx)                                      # :379-380
+        Ff_y = self._stribeck(vy, *sy)
+        v_slip_x = vx - r_x * om_y                                          # :387-391
+        v_slip_y = vy - (-r_y * om_x)
+        F_roll_x = self._stribeck(v_slip_x, *sx)                            # :395-396
+        F_roll_y = self._stribeck(v_slip_y, *sy)
+        tau_slip_x = -r_y * F_roll_y                                        # :402-403
+        tau_slip_y = -r_x * F_roll_x
+        T_noslip_x = self._stribeck(om_x, *srx)
+        T_noslip_y = self._stribeck(om_y, *sry)
+        T_damp_x = c_rot_x * om_x                                           # :410-411
+        T_damp_y = c_rot_y * om_y
+        tau_topple_x = -m_y * g * h_com_x * np.sin(th_x)                    # :414-415
+        tau_topple_y = -m_x * g * h_com_y * np.sin(th_y)
+        tau_x = tau_slip_x - T_noslip_x - T_damp_x + tau_topple_x           # :418-419
+        tau_y = tau_slip_y - T_noslip_y - T_damp_y + tau_topple_y
+        al_x = tau_x / (I_x + 1e-12)                                        # :422-423
+        al_y = tau_y / (I_y + 1e-12)
+        rhs_x = Gx - c_x * vx - k_x * px - Ff_x - F_roll_x                  # :427
+        rhs_y = Gy - c_y * vy - k_y * py - Ff_y - F_roll_y
+        return np.stack([vx, rhs_x / m_x, vy, rhs_y / m_y, om_x, al_x, om_y, al_y], axis=1)       # :429
+
+    def step(self, u_cmd):
+        self.tilt += self.a_lag * (np.asarray(u_cmd, float).reshape(-1, 2) - self.tilt)
+        s = np.sin(self.tilt)
+        sa, sb = s[:, 0], s[:, 1]
+        h, x = self.dt, self.x
+        k1 = self._f(x, sa, sb)
+        k2 = self._f(x + 0.5 * h * k1, sa, sb)
+        k3 = self._f(x + 0.5 * h * k2, sa, sb)
+        k4 = self._f(x + h * k3, sa, sb)
+        self.x = x + h * (k1 + 2 * k2 + 2 * k3 + k4) / 6
+        return self.x
+
+
+def lmpc_noise(noise_seed, steps: int, B: int):
+    """The policy's standard-normal draws of a run, [steps, B, 34] fp32 (row k: step k); ``None`` = zero noise."""
+    if noise_seed is None:
+        return np.zeros((steps, B, 34), np.float32)
+    return np.random.default_rng(noise_seed).standard_normal((steps, B, 34)).astype(np.float32)
+
+
+def _lmpc_setup(x0, targets, plant_pvec, prm, policy_seed, model_params):
+    from .lmpc import LmpcPolicy
+    from ._lib import LMPC_PRM_DEFAULT
+    x0 = np.asarray(x0, float).reshape(-1, 8)
+    B = x0.shape[0]
+    targets = np.asarray(targets, float).reshape(B, 8)
+    plant_pvec = np.asarray(plant_pvec, float).reshape(B, 34)
+    prm = np.tile(LMPC_PRM_DEFAULT, (B, 1)) if prm is None else np.asarray(prm, float).reshape(B, 22)
+    policy = None if policy_seed is None else LmpcPolicy(B, seed=policy_seed)
+    if policy is None:
+        model_params = (plant_pvec if model_params is None else np.asarray(model_params, float).reshape(B, 34)).copy()
+    return x0, B, targets, plant_pvec, prm, policy, model_params
+
+
+def _lmpc_result(B, steps, Ts, targets, lg, final_x, state, wall, return_logs):
+    after = np.concatenate([lg["X"][1:], final_x[None]], axis=0) if steps else lg["X"]     # run.py:286: after the step
+    t = np.arange(steps) * Ts
+    logs = [{"pos_error": lg["pos_error"][:, b], "u_cmd": lg["U_cmd"][:, b], "timestep": t.copy(), "state": after[:, b],
+             "loss": lg["loss"][:, b]} for b in range(B)]
+    if return_logs:
+        return logs, lg["status"], {"iters": lg["iters"], "pvec": lg["pvec"], "X": lg["X"], "state": state,
+                                    "solve_time": wall / max(steps, 1)}
+    return logs, lg["status"]
+
+
+def run_lmpc(x0, targets, plant_pvec, steps: int, N: int = 30, policy_seed=0, noise_seed=None, Ts: float = 0.002,
+             prm=None, device: int = 0, plant_kw: dict | None = None, model_params=None, return_logs: bool = False):
+    """B LMPC experiments in lock step (LMPC/src/run.py:256-286 without MuJoCo): per step one fused policy step +
+    solve (``policy_solve_batch``), warm-started from the previous optimum (rlmpc2.py:494-524), then ``LmpcPlant``
+    with the true parameters ``plant_pvec`` [B, 34].  x0, targets [B, 8].  ``policy_seed`` seeds a fresh
+    ``LmpcPolicy``; None runs without a policy, every solve using ``model_params`` (default ``plant_pvec``).
+    ``noise_seed`` seeds the policy's draws (``lmpc_noise``; None: zero noise).
+
+    Returns per-experiment dicts with run.py's logged keys (pos_error, u_cmd, timestep, state -- the state after
+    the step, :286 -- plus loss) and the solver statuses [steps, B]; ``return_logs`` adds dict(iters, pvec
+    [steps, B, 34], X [steps, B, 8] the states the solves saw, state = the final loop state, solve_time)."""
+    from ._lib import LMPC_LOOP_LOGS, LmpcSolver, loop_logs
+    from .lmpc import policy_solve_batch
+    x0, B, targets, plant_pvec, prm, policy, model_params = _lmpc_setup(x0, targets, plant_pvec, prm, policy_seed,
+                                                                        model_params)
+    noise = lmpc_noise(noise_seed, steps, B)
+    lg = loop_logs(LMPC_LOOP_LOGS, steps, B)
+    plant = LmpcPlant(x0, plant_pvec, dt=Ts, **(plant_kw or {}))
+    solver = LmpcSolver(N=N, Ts=Ts, B_max=max(B, 1), device=device)
+    u_prev, w = np.zeros((B, 2)), np.zeros((B, solver.nw))
+    wall = 0.0
+    try:
+        for k in range(steps):
+            lg["X"][k] = plant.x
+            t0 = time.perf_counter()
+            if policy is not None:
+                out = policy_solve_batch(solver, policy, plant.x, u_prev, targets, prm, w_warm=w, want_w=True,
+                                         noise=noise[k])
+                lg["pvec"][k] = policy.model_params
+            else:
+                out = solver.solve_batch(plant.x, u_prev, model_params, targets, prm, w_warm=w, want_w=True)
+                lg["pvec"][k] = model_params
+            wall += time.perf_counter() - t0
+            w, u_prev = out["w"], out["u0"].copy()
+            lg["U_cmd"][k], lg["loss"][k], lg["status"][k], lg["iters"][k] = out["u0"], out["f"], out["status"], out["iters"]
+            xn = plant.step(out["u0"])
+            dx, dy = xn[:, 0] - targets[:, 0], xn[:, 2] - targets[:, 2]
+            lg["pos_error"][k] = np.sqrt(dx * dx + dy * dy)                 # run.py:274
+    finally:
+        solver.close()
+    state = {"x": plant.x.copy(), "tilt": plant.tilt.copy(), "u_prev": u_prev, "w": w,
+             "model_params": policy.model_params.copy() if policy is not None else model_params}
+    if policy is not None:
+        state.update(obs_mean=policy.obs_mean, obs_M2=policy.obs_M2, obs_count=policy.obs_count,
+                     history=policy.history.reshape(B, 520), timestep=policy.timestep)
+    return _lmpc_result(B, steps, Ts, targets, lg, plant.x, state, wall, return_logs)
+
+
+def rollout_lmpc(x0, targets, plant_pvec, steps: int, N: int = 30, policy_seed=0, noise_seed=None, Ts: float = 0.002,
+                 prm=None, device: int = 0, plant_kw: dict | None = None, model_params=None,
+                 return_logs: bool = False):
+    """``run_lmpc`` on the device (dart_lmpc_rollout): same arguments, same return values.  ``solve_time`` is the
+    rollout's wall time divided by the steps run."""
+    from ._lib import LMPC_LOOP_LOGS, LmpcSolver, loop_logs, plant_config
+    x0, B, targets, plant_pvec, prm, policy, model_params = _lmpc_setup(x0, targets, plant_pvec, prm, policy_seed,
+                                                                        model_params)
+    noise = lmpc_noise(noise_seed, steps, B) if (policy is not None and noise_seed is not None) else None
+    lg = loop_logs(LMPC_LOOP_LOGS, steps, B)
+    plant = plant_config(**{k: v for k, v in (plant_kw or {}).items()})
+    solver = LmpcSolver(N=N, Ts=Ts, B_max=max(B, 1), device=device)
+    try:
+        state = solver.loop_state(x0, policy=policy, model_params=model_params)
+        t0 = time.perf_counter()
+        solver.rollout(0, steps, targets, plant_pvec, state, lg, policy=policy, prm=prm, noise=noise, plant=plant)
+        wall = time.perf_counter() - t0
+    finally:
+        solver.close()
+    return _lmpc_result(B, steps, Ts, targets, lg, state["x"], state, wall, return_logs)

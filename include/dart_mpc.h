@@ -396,8 +396,8 @@ int dart_arm_solve_batch(const dart_arm_config *cfg, int B, int n, const double 
  * plant's viscous friction (PMPC: prm[0]); RMPC's feature scale v_eps is prm[9]. */
 typedef struct dart_plant_config {
     double tau;     /* tilt lag time constant [s], 0.03; <= 0: the tilt follows the command at once */
-    double mu_c;    /* Coulomb friction coefficient the MPC model does not have, 0.02 */
-    double v_c;     /* its tanh velocity scale [m/s], 0.01 */
+    double mu_c;    /* Coulomb friction coefficient the MPC model does not have, 0.02 (not used by the LMPC plant) */
+    double v_c;     /* its tanh velocity scale [m/s], 0.01 (not used by the LMPC plant) */
 } dart_plant_config;
 
 typedef struct dart_rmpc_loop_config {
@@ -467,6 +467,64 @@ int dart_pmpc_rollout(dart_mpc_handle *h, const dart_plant_config *plant,
                       int B, int k0, int steps, int log_rows, const double *target, const double *prm,
                       double *x, double *tilt,
                       double *log_X, double *log_U, double *log_quat, double *log_loss,
+                      int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+/* LMPC closed loop (handle of variant DART_MPC_LMPC; added within ABI 8).  What LMPC/src/run.py:256-286 does around
+ * ctlr.solve -- the policy step and the warm-started solve (rlmpc2.py:494-524), the log, the plant step, the next
+ * state -- with the plant of dart_mpc/harness.py (LmpcPlant) in place of MuJoCo: the first-order tilt lag of
+ * dart_plant_config.tau, then one RK4 step at Ts of the LMPC model itself (safe_dynamics, rlmpc2.py:260-429) with
+ * the lagged tilt as input and the instance's true parameters plant_pvec [B][34].  mu_c / v_c of dart_plant_config
+ * are not used here: the model's Stribeck terms are its Coulomb friction.  The driver's u_cmd *= -1 and the
+ * quaternion (run.py:257-261) are MuJoCo tray conventions and are not applied, as in the other two plants.  The
+ * launch sequence of a call is that of the RMPC rollout,
+ *     pre(k0), [solve launch(es), post(k) + pre(k+1)] for k = k0 .. k0+steps-2, solve launch(es), post(k0+steps-1)
+ * where the solve launches are exactly what dart_lmpc_policy_solve_batch_dev enqueues for that B and N.
+ *
+ * State (caller-owned, in/out): x [B][8], tilt [B][2], u_prev [B][2], w [B][nw] (warm start; the final iterate of
+ *   every call), and the policy state of dart_lmpc_policy_step: obs_mean, obs_M2 [B][52], obs_count [B],
+ *   history [B][10][52] (fp32), timestep [B], model_params [B][34].  A fresh rollout starts from x = x0,
+ *   model_params = current_k and zeros elsewhere.
+ * Inputs: target [B][8], prm [B][22], plant_pvec [B][34], current_k [B][34], weights (DART_LMPC_POLICY_NWEIGHTS
+ *   fp32), pcfg, noise [log_rows][B][34] fp32 (row k: the standard-normal draws of step k; NULL: zero noise).
+ *   weights == NULL runs the loop without a policy: every solve uses model_params as a fixed pvec through
+ *   dart_lmpc_solve_batch_dev; pcfg, current_k, noise and the other policy state arrays are then not read.
+ * Logs [log_rows][B][...], row k: X [8] (the state the solve saw), U_cmd [2], pos_error (the norm of
+ *   x_next[[0, 2]] - target[[0, 2]] after the plant step, run.py:274), pvec [34] (the parameter row the solve
+ *   used), loss, status, iters (int32).  Rows that a call does not write keep their contents.
+ * Two calls of K1 and K2 steps give bit for bit what one call of K1 + K2 steps gives. */
+
+/* One loop-step launch: post(k) if do_post, then the next step's pre if do_pre.  pre writes the solve's state
+ * [B][8]; post reads u0 [B][2], f, status, iters [B] and model_params, writes u_prev.  Device pointers, asynchronous. */
+int dart_lmpc_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                            int B, int k, int do_post, int do_pre, int log_rows,
+                            const double *target, const double *plant_pvec,
+                            double *x, double *tilt, double *u_prev, const double *model_params, double *state,
+                            const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                            double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
+                            int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+/* `steps` closed-loop steps k0 .. k0+steps-1 (k0 + steps <= log_rows); steps = 0 does nothing.  Device pointers,
+ * asynchronous on hip_stream (NULL = the handle's own).  The solve's per-step arrays, two warm-start buffers the
+ * solves alternate between (the first solve of a call reads w, the last writes it) and the zero noise row live in
+ * the handle (B <= B_max). */
+int dart_lmpc_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                          int B, int k0, int steps, int log_rows,
+                          const double *target, const double *prm, const double *plant_pvec, const double *current_k,
+                          const float *weights, const float *noise,
+                          double *x, double *tilt, double *u_prev, double *w, double *obs_mean, double *obs_M2,
+                          int32_t *obs_count, float *history, int32_t *timestep, double *model_params,
+                          double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
+                          int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+/* Host pointers: state, inputs and logs are staged through device memory; blocks until they are back.  Of the
+ * logs and of the noise only rows k0 .. k0+steps-1 travel. */
+int dart_lmpc_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                      int B, int k0, int steps, int log_rows,
+                      const double *target, const double *prm, const double *plant_pvec, const double *current_k,
+                      const float *weights, const float *noise,
+                      double *x, double *tilt, double *u_prev, double *w, double *obs_mean, double *obs_M2,
+                      int32_t *obs_count, float *history, int32_t *timestep, double *model_params,
+                      double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
                       int32_t *log_status, int32_t *log_iters, void *hip_stream);
 
 int dart_mpc_sync(dart_mpc_handle *h);

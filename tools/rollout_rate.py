@@ -1,10 +1,15 @@
-"""Closed-loop rate of the device-resident rollouts (harness.rollout_pmpc / rollout_rmpc) against the host loops
-of the same build (harness.run_pmpc / run_rmpc): B = 18 and B = 18 x 64 experiments, N = 20.  Each loop is run
-once untimed (library and code-object load), then timed as a whole call (handle creation included on both
-sides); the episode tolerance is 0 so that both RMPC loops run every step.  Reports steps/s, solves/s, and from
-the rollout's logs the mean iterations per solve and the share of solves with status != 0 over the chain (RMPC:
-warm-started; PMPC: cold-started, as in the reference).
-Usage: python tools/rollout_rate.py [out.json] [steps] [steps_large]
+"""Closed-loop rate of the device-resident rollouts (harness.rollout_pmpc / rollout_rmpc / rollout_lmpc) against the
+host loops of the same build (harness.run_pmpc / run_rmpc / run_lmpc): B = 18 and B = 18 x 64 experiments, N = 20
+(LMPC: N = 30, C5's horizon; workload.lmpc_batch's states and targets, its pvec as the plant's parameters, the
+policy on, restoration on).  Each loop is run once untimed (library and code-object load), then timed as a whole
+call (handle creation included on both sides); the episode tolerance is 0 so that both RMPC loops run every step.
+Reports steps/s, solves/s, and from the rollout's logs the mean iterations per solve and the share of solves with
+status != 0 over the chain (RMPC, LMPC: warm-started; PMPC: cold-started, as in the reference).  The LMPC rows
+(policy noise from seed 0) add the largest iteration count, the count of non-zero statuses and the tail: the share
+of steps on which some instance took more than 20 iterations.
+Usage: python tools/rollout_rate.py [out.json] [steps] [steps_large] [controllers]
+``controllers``: a comma-separated subset of PMPC,RMPC,LMPC (default: all); the rows of the others are kept from an
+existing out.json.
 """
 import json
 import os
@@ -16,11 +21,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dart-dual-arm-non-prehensile-manipulation_amd"))
 from dart_mpc import harness  # noqa: E402
-from dart_mpc.workload import pmpc_batch  # noqa: E402
+from dart_mpc.workload import lmpc_batch, pmpc_batch  # noqa: E402
 
 out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "rollout_rate.json")
 steps_small = int(sys.argv[2]) if len(sys.argv) > 2 else 300
 steps_large = int(sys.argv[3]) if len(sys.argv) > 3 else 100
+controllers = sys.argv[4].upper().split(",") if len(sys.argv) > 4 else ["PMPC", "RMPC", "LMPC"]
 
 
 def timed(fn, *a, **kw):
@@ -39,30 +45,56 @@ def rmpc_inputs(B):
     return np.zeros((B, 4)), tg
 
 
-results = []
-for seeds, steps in ((1, steps_small), (64, steps_large)):
-    B = 18 * seeds
+def pmpc_row(seeds, B, steps):
     S, T, P = pmpc_batch(seeds, seed0=0)
     harness.run_pmpc(S, T, P, 3); harness.rollout_pmpc(S, T, P, 3)
     (_, st_h), t_host = timed(harness.run_pmpc, S, T, P, steps)
     (_, st_d, X), t_dev = timed(harness.rollout_pmpc, S, T, P, steps, return_logs=True)
-    row = {"controller": "PMPC", "B": B, "N": 20, "steps": steps, "host_loop": rate(B, steps, t_host),
-           "rollout": dict(rate(B, steps, t_dev), loop_only_s=X["solve_time"] * steps,
-                           mean_iters=float(X["iters"].mean()), share_status_nonzero=float(np.mean(st_d != 0))),
-           "host_share_status_nonzero": float(np.mean(st_h != 0)), "speedup": t_host / t_dev}
-    results.append(row)
-    print(json.dumps(row), flush=True)
+    return {"controller": "PMPC", "B": B, "N": 20, "steps": steps, "host_loop": rate(B, steps, t_host),
+            "rollout": dict(rate(B, steps, t_dev), loop_only_s=X["solve_time"] * steps,
+                            mean_iters=float(X["iters"].mean()), share_status_nonzero=float(np.mean(st_d != 0))),
+            "host_share_status_nonzero": float(np.mean(st_h != 0)), "speedup": t_host / t_dev}
 
+
+def rmpc_row(seeds, B, steps):
     x0, tg = rmpc_inputs(B)
     harness.run_rmpc(x0, tg, 3, pos_tol=0.0); harness.rollout_rmpc(x0, tg, 3, pos_tol=0.0)
     (_, st_h, _), t_host = timed(harness.run_rmpc, x0, tg, steps, pos_tol=0.0)
     (_, st_d, _, X), t_dev = timed(harness.rollout_rmpc, x0, tg, steps, pos_tol=0.0, return_logs=True)
-    row = {"controller": "RMPC", "B": B, "N": 20, "steps": steps, "host_loop": rate(B, steps, t_host),
-           "rollout": dict(rate(B, steps, t_dev), loop_only_s=X["solve_time"] * steps,
-                           mean_iters=float(X["iters"].mean()), share_status_nonzero=float(np.mean(st_d != 0))),
-           "host_share_status_nonzero": float(np.mean(st_h != 0)), "speedup": t_host / t_dev}
-    results.append(row)
-    print(json.dumps(row), flush=True)
+    return {"controller": "RMPC", "B": B, "N": 20, "steps": steps, "host_loop": rate(B, steps, t_host),
+            "rollout": dict(rate(B, steps, t_dev), loop_only_s=X["solve_time"] * steps,
+                            mean_iters=float(X["iters"].mean()), share_status_nonzero=float(np.mean(st_d != 0))),
+            "host_share_status_nonzero": float(np.mean(st_h != 0)), "speedup": t_host / t_dev}
+
+
+def lmpc_row(seeds, B, steps):
+    D = lmpc_batch(seeds, seed0=0)
+    la = (D["state"], D["target"], D["pvec"])
+    lk = dict(N=30, policy_seed=0, noise_seed=0, return_logs=True)
+    harness.run_lmpc(*la, 3, **lk); harness.rollout_lmpc(*la, 3, **lk)
+    (_, st_h, Xh), t_host = timed(harness.run_lmpc, *la, steps, **lk)
+    (_, st_d, X), t_dev = timed(harness.rollout_lmpc, *la, steps, **lk)
+
+    def chain(st, it):
+        return {"mean_iters": float(it.mean()), "max_iters": int(it.max()), "n_status_nonzero": int(np.sum(st != 0)),
+                "share_status_nonzero": float(np.mean(st != 0)),
+                "tail_share_steps_over_20_iters": float(np.mean(it.max(axis=1) > 20))}
+    return {"controller": "LMPC", "B": B, "N": 30, "steps": steps,
+            "host_loop": dict(rate(B, steps, t_host), solves_only_s=Xh["solve_time"] * steps, **chain(st_h, Xh["iters"])),
+            "rollout": dict(rate(B, steps, t_dev), loop_only_s=X["solve_time"] * steps, **chain(st_d, X["iters"])),
+            "speedup": t_host / t_dev}
+
+
+ROWS = {"PMPC": pmpc_row, "RMPC": rmpc_row, "LMPC": lmpc_row}
+results = []
+if os.path.exists(out_path):        # the rows of the controllers that this run leaves out
+    with open(out_path) as f:
+        results = [r for r in json.load(f).get("results", []) if r.get("controller") not in controllers]
+for seeds, steps in ((1, steps_small), (64, steps_large)):
+    for name in controllers:
+        row = ROWS[name](seeds, 18 * seeds, steps)
+        results.append(row)
+        print(json.dumps(row), flush=True)
 
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as f:
