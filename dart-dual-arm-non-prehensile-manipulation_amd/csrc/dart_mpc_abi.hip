@@ -20,6 +20,7 @@
 #include "rmpc_ipm.h"
 #include "lmpc_ipm.h"
 #include "lmpc_policy.h"
+#include "lmpc_experience.h"
 #include "arm_qp.h"
 #include "loop_step.h"
 
@@ -214,6 +215,9 @@ struct dart_mpc_handle {
     char* loop_buf = nullptr;
     char* roll_buf = nullptr;
     size_t roll_cap = 0;
+    // experience collection (dart_lmpc_collect*): the policy's raw actions of one step, [B_max][34] fp32,
+    // allocated on first use
+    float* action_buf = nullptr;
 };
 
 namespace {
@@ -1168,6 +1172,7 @@ void dart_mpc_destroy(dart_mpc_handle* h) {
         if (e.buf) (void)hipFree(e.buf);       // (synchronises with the area's last use)
     if (h->loop_buf) (void)hipFree(h->loop_buf);
     if (h->roll_buf) (void)hipFree(h->roll_buf);
+    if (h->action_buf) (void)hipFree(h->action_buf);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1763,5 +1768,296 @@ int dart_lmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const 
         return rc;
     if (int rc = S.download(h, s)) return rc;
     HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// LMPC experience collection (lmpc_experience.hip after every post of the LMPC closed loop)
+void dart_lmpc_reward_config_default(dart_lmpc_reward_config* c) {
+    if (!c) return;
+    c->sigma_pos = 0.02; c->sigma_vel = 0.02;
+    c->w_pos = 40.0; c->w_vel = 0.1; c->w_change = 1e-3; c->w_d_ctrl = 5.0;
+    c->success_tol = 0.01; c->success_bonus = 20.0; c->oob_penalty = 20.0;
+    c->tray_limit[0] = 0.2; c->tray_limit[1] = 0.15;
+    c->max_per_dim_rms = 0.5; c->time_penalty_rate = 1e-4;
+    c->max_episode_steps = 20000; c->record_every = 8; c->done_sticky = 0; c->reserved = 0;
+}
+
+namespace {
+
+// the configuration half of the experience launch's arguments, checked (after loop_check)
+int experience_cfg(dart_mpc_handle* h, const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* r, int B,
+                   int rec_rows, int reset_rows, const float* weights, const float* critic,
+                   dartmpc::ExperienceArgs& a) {
+    if (!weights) return fail(h, DART_MPC_EINVAL, "experience collection needs a policy (null weights)");
+    if (!critic) return fail(h, DART_MPC_EINVAL, "null critic weights");
+    // (the experience kernel reads layer 1 of both nets with 16-byte loads)
+    if ((reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(critic)) & 15)
+        return fail(h, DART_MPC_EINVAL, "policy and critic weights must be 16-byte aligned");
+    dartmpc::PolicyArgs pa;
+    if (policy_args(pcfg, B, weights, pa) != DART_MPC_OK) return fail(h, DART_MPC_EINVAL, "bad policy config");
+    if (!r) return fail(h, DART_MPC_EINVAL, "null reward config");
+    if (r->record_every < 1 || !(r->sigma_pos > 0.0) || !(r->sigma_vel > 0.0))
+        return fail(h, DART_MPC_EINVAL, "reward config: record_every >= 1, sigma_pos > 0, sigma_vel > 0");
+    if (rec_rows < 0 || reset_rows < 0) return fail(h, DART_MPC_EINVAL, "negative rec_rows or reset_rows");
+    a.B = B; a.rec_rows = rec_rows; a.reset_rows = reset_rows;
+    a.w = pa.w;
+    a.c.V1 = critic; a.c.c1 = critic + 520 * 64; a.c.V2 = a.c.c1 + 64; a.c.c2 = a.c.V2 + 64 * 64;
+    a.c.V3 = a.c.c2 + 64; a.c.c3 = a.c.V3 + 64;
+    a.r.sigma_pos = r->sigma_pos; a.r.sigma_vel = r->sigma_vel; a.r.w_pos = r->w_pos; a.r.w_vel = r->w_vel;
+    a.r.w_change = r->w_change; a.r.w_d_ctrl = r->w_d_ctrl; a.r.success_tol = r->success_tol;
+    a.r.success_bonus = r->success_bonus; a.r.oob_penalty = r->oob_penalty;
+    a.r.tray_limit[0] = r->tray_limit[0]; a.r.tray_limit[1] = r->tray_limit[1];
+    a.r.max_per_dim_rms = r->max_per_dim_rms; a.r.time_penalty_rate = r->time_penalty_rate;
+    a.r.max_episode_steps = r->max_episode_steps; a.r.record_every = r->record_every; a.r.done_sticky = r->done_sticky;
+    a.max_delta = pcfg->max_delta; a.action_scale = pcfg->action_scale;
+    a.log_std_min = pcfg->log_std_min; a.log_std_max = pcfg->log_std_max;
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+#define DART_COLLECT_STATE_PARAMS                                                                                     \
+    double *prev_cmd, double *control_seen, int32_t *ep_step, double *ep_return, double *time_penalty,               \
+        int32_t *episodes, double *last_return, int32_t *last_steps, int32_t *nrec, int32_t *sticky,                 \
+        const double *reset_x, const double *reset_target, const double *reset_pvec
+#define DART_COLLECT_OUT_PARAMS                                                                                       \
+    double *log_reward, int32_t *log_done, float *log_value, float *log_logp, float *rec_obs, float *rec_action,     \
+        float *rec_logp, float *rec_value, double *rec_reward, float *rec_done
+// (after experience_cfg) the pointer half: null checks, then the fields of `a`
+#define DART_COLLECT_FILL(a)                                                                                          \
+    do {                                                                                                              \
+        if (any_null({prev_cmd, control_seen, ep_step, ep_return, time_penalty, episodes, last_return, last_steps,   \
+                      nrec, sticky, log_reward, log_done, log_value, log_logp}))                                      \
+            return fail(h, DART_MPC_EINVAL, "null pointer (collection state or logs)");                              \
+        if (rec_rows > 0 && any_null({rec_obs, rec_action, rec_logp, rec_value, rec_reward, rec_done}))              \
+            return fail(h, DART_MPC_EINVAL, "null pointer (records)");                                               \
+        if (reset_rows > 0 && any_null({reset_x, reset_target, reset_pvec}))                                         \
+            return fail(h, DART_MPC_EINVAL, "reset_rows > 0 with a null reset pool");                                \
+        (a).prev_cmd = prev_cmd; (a).control_seen = control_seen; (a).ep_step = ep_step; (a).ep_return = ep_return;  \
+        (a).time_penalty = time_penalty; (a).episodes = episodes; (a).last_return = last_return;                     \
+        (a).last_steps = last_steps; (a).nrec = nrec; (a).sticky = sticky;                                           \
+        (a).reset_x = reset_x; (a).reset_target = reset_target; (a).reset_pvec = reset_pvec;                         \
+        (a).log_reward = log_reward; (a).log_done = log_done; (a).log_value = log_value; (a).log_logp = log_logp;    \
+        (a).rec_obs = rec_obs; (a).rec_action = rec_action; (a).rec_logp = rec_logp; (a).rec_value = rec_value;      \
+        (a).rec_reward = rec_reward; (a).rec_done = rec_done;                                                        \
+    } while (0)
+
+int dart_lmpc_experience_step_dev(dart_mpc_handle* h, const dart_lmpc_policy_config* pcfg,
+                                  const dart_lmpc_reward_config* rcfg, int B, int k, int log_rows, int rec_rows,
+                                  int reset_rows, const float* weights, const float* critic, const float* history,
+                                  const float* action, const double* log_X, const int32_t* timestep,
+                                  const double* u_prev, double* target, double* plant_pvec, double* x, double* tilt,
+                                  double* state, DART_COLLECT_STATE_PARAMS, DART_COLLECT_OUT_PARAMS, float* mean_out,
+                                  void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, "handle is not an LMPC handle");
+    if (B < 0 || k < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
+    if (k >= log_rows) return fail(h, DART_MPC_EINVAL, "k exceeds log_rows");
+    dartmpc::ExperienceArgs a;
+    if (int rc = experience_cfg(h, pcfg, rcfg, B, rec_rows, reset_rows, weights, critic, a)) return rc;
+    if (any_null({history, action, log_X, timestep, u_prev, target, plant_pvec, x, tilt}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    DART_COLLECT_FILL(a);
+    if (B == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    a.k = k;
+    a.history = history; a.action = action; a.log_X = log_X; a.timestep = timestep; a.u_prev = u_prev;
+    a.target = target; a.plant_pvec = plant_pvec; a.x = x; a.tilt = tilt; a.state = state; a.mean_out = mean_out;
+    HIPCHK(h, dartmpc_launch_lmpc_experience(&a, stream ? (hipStream_t)stream : h->stream), "experience kernel launch");
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_collect_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                          const dart_lmpc_reward_config* rcfg, int B, int k0, int steps, int log_rows, int rec_rows,
+                          int reset_rows, double* target, const double* prm, double* plant_pvec,
+                          const double* current_k, const float* weights, const float* critic, const float* noise,
+                          double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                          int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                          DART_COLLECT_STATE_PARAMS, double* log_X, double* log_U, double* log_pos_error,
+                          double* log_pvec, double* log_loss, int32_t* log_status, int32_t* log_iters,
+                          DART_COLLECT_OUT_PARAMS, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_LMPC, plant, B, k0, steps, log_rows)) return rc;
+    dartmpc::ExperienceArgs ea;
+    if (int rc = experience_cfg(h, pcfg, rcfg, B, rec_rows, reset_rows, weights, critic, ea)) return rc;
+    if (int rc = lmpc_rollout_check(h, pcfg, B, weights,
+                                    {target, prm, plant_pvec, x, tilt, u_prev, w, model_params, log_X, log_U,
+                                     log_pos_error, log_pvec, log_loss, log_status, log_iters},
+                                    {current_k, obs_mean, obs_M2, obs_count, history, timestep}))
+        return rc;
+    DART_COLLECT_FILL(ea);
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    LmpcLoopScratch L;
+    if (int rc = lmpc_loop_scratch(h, L)) return rc;
+    if (!h->action_buf)
+        HIPCHK(h, hipMalloc((void**)&h->action_buf, sizeof(float) * 34 * (size_t)h->cfg.B_max), "hipMalloc (action buffer)");
+    void* s = stream ? stream : (void*)h->stream;
+    auto step = [&](int k, int post, int pre) {
+        return dart_lmpc_loop_step_dev(h, plant, B, k, post, pre, log_rows, target, plant_pvec, x, tilt, u_prev,
+                                       model_params, L.state, L.u0, L.f, L.status, L.iters, log_X, log_U, log_pos_error,
+                                       log_pvec, log_loss, log_status, log_iters, s);
+    };
+    ea.history = history; ea.action = h->action_buf; ea.log_X = log_X; ea.timestep = timestep; ea.u_prev = u_prev;
+    ea.target = target; ea.plant_pvec = plant_pvec; ea.x = x; ea.tilt = tilt; ea.mean_out = nullptr;
+    // the launch sequence and the warm-start ping-pong of dart_lmpc_rollout_dev, with the policy's action kept and
+    // one experience launch after every post; a reset at the last step of a call is picked up by the next call's pre
+    const bool in_place = !h->cfg.restoration;
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        const double* w_in = (in_place || j == 0) ? w : L.wbuf[(j - 1) & 1];
+        double* w_out = (in_place || (j == steps - 1 && j > 0)) ? w : L.wbuf[j & 1];
+        int rc = dart_lmpc_policy_solve_batch_dev(h, pcfg, B, weights, L.state, u_prev, target, current_k, obs_mean,
+                                                  obs_M2, obs_count, history, timestep,
+                                                  noise ? noise + ((size_t)k0 + j) * B * 34 : L.zero_noise, model_params,
+                                                  h->action_buf, prm, w_in, L.u0, L.f, w_out, L.status, L.iters, s);
+        if (rc) return rc;
+        if (w_out != w && j == steps - 1)       // a one-step call: the iterate back into the caller's w
+            HIPCHK(h, hipMemcpyAsync(w, w_out, sizeof(double) * (size_t)dart_lmpc_nw(h->cfg.N) * B,
+                                     hipMemcpyDeviceToDevice, (hipStream_t)s), "copy w");
+        const int pre = j + 1 < steps;
+        if ((rc = step(k0 + j, 1, pre))) return rc;
+        ea.k = k0 + j;
+        ea.state = pre ? L.state : nullptr;
+        HIPCHK(h, dartmpc_launch_lmpc_experience(&ea, (hipStream_t)s), "experience kernel launch");
+    }
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_collect(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                      const dart_lmpc_reward_config* rcfg, int B, int k0, int steps, int log_rows, int rec_rows,
+                      int reset_rows, double* target, const double* prm, double* plant_pvec, const double* current_k,
+                      const float* weights, const float* critic, const float* noise,
+                      double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                      int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                      DART_COLLECT_STATE_PARAMS, double* log_X, double* log_U, double* log_pos_error,
+                      double* log_pvec, double* log_loss, int32_t* log_status, int32_t* log_iters,
+                      DART_COLLECT_OUT_PARAMS, void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = loop_check(h, DART_MPC_LMPC, plant, B, k0, steps, log_rows)) return rc;
+    {
+        dartmpc::ExperienceArgs chk;
+        if (int rc = experience_cfg(h, pcfg, rcfg, B, rec_rows, reset_rows, weights, critic, chk)) return rc;
+        if (int rc = lmpc_rollout_check(h, pcfg, B, weights,
+                                        {target, prm, plant_pvec, x, tilt, u_prev, w, model_params, log_X, log_U,
+                                         log_pos_error, log_pvec, log_loss, log_status, log_iters},
+                                        {current_k, obs_mean, obs_M2, obs_count, history, timestep}))
+            return rc;
+        DART_COLLECT_FILL(chk);
+    }
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t), F = sizeof(float);
+    const size_t nw = (size_t)dart_lmpc_nw(h->cfg.N);
+    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
+    const size_t RR = (size_t)rec_rows, RS = (size_t)reset_rows;
+    RollStage S;
+    const int i_tg = S.add(target, 8 * nB * D, true), i_prm = S.add(prm, dartmpc::LM_NPRM * nB * D, false);
+    const int i_pp = S.add(plant_pvec, 34 * nB * D, true);
+    const int i_x = S.add(x, 8 * nB * D, true), i_tilt = S.add(tilt, 2 * nB * D, true), i_up = S.add(u_prev, 2 * nB * D, true);
+    const int i_w = S.add(w, nw * nB * D, true), i_mp = S.add(model_params, 34 * nB * D, true);
+    const int i_ck = S.add(current_k, 34 * nB * D, false);
+    const int i_wt = S.add(weights, (size_t)DART_LMPC_POLICY_NWEIGHTS * F, false);
+    const int i_cr = S.add(critic, (size_t)DART_LMPC_CRITIC_NWEIGHTS * F, false);
+    const int i_nz = noise ? S.add_rows_in(noise, R, 34 * nB * F, r0, r1) : -1;
+    const int i_om = S.add(obs_mean, 52 * nB * D, true), i_o2 = S.add(obs_M2, 52 * nB * D, true);
+    const int i_oc = S.add(obs_count, nB * I, true), i_hi = S.add(history, 520 * nB * F, true);
+    const int i_ts = S.add(timestep, nB * I, true);
+    const int c_pc = S.add(prev_cmd, 2 * nB * D, true), c_cs = S.add(control_seen, 2 * nB * D, true);
+    const int c_es = S.add(ep_step, nB * I, true), c_er = S.add(ep_return, nB * D, true);
+    const int c_tp = S.add(time_penalty, nB * D, true), c_ep = S.add(episodes, nB * I, true);
+    const int c_lr = S.add(last_return, nB * D, true), c_ls = S.add(last_steps, nB * I, true);
+    const int c_nr = S.add(nrec, nB * I, true), c_sk = S.add(sticky, nB * I, true);
+    int p_x = -1, p_t = -1, p_p = -1;
+    if (reset_rows > 0) {
+        p_x = S.add(reset_x, RS * 8 * nB * D, false); p_t = S.add(reset_target, RS * 8 * nB * D, false);
+        p_p = S.add(reset_pvec, RS * 34 * nB * D, false);
+    }
+    const int l_X = S.add_log(log_X, R, 8 * nB * D, r0, r1, false), l_U = S.add_log(log_U, R, 2 * nB * D, r0, r1, false);
+    const int l_pe = S.add_log(log_pos_error, R, nB * D, r0, r1, false), l_pv = S.add_log(log_pvec, R, 34 * nB * D, r0, r1, false);
+    const int l_L = S.add_log(log_loss, R, nB * D, r0, r1, false);
+    const int l_st = S.add_log(log_status, R, nB * I, r0, r1, false), l_it = S.add_log(log_iters, R, nB * I, r0, r1, false);
+    const int l_rw = S.add_log(log_reward, R, nB * D, r0, r1, false), l_dn = S.add_log(log_done, R, nB * I, r0, r1, false);
+    const int l_vl = S.add_log(log_value, R, nB * F, r0, r1, false), l_lp = S.add_log(log_logp, R, nB * F, r0, r1, false);
+    int r_ob = -1, r_ac = -1, r_lp = -1, r_vl = -1, r_rw = -1, r_dn = -1;
+    if (rec_rows > 0) {
+        // record rows: an instance writes rows nrec[b] .. nrec[b] + ceil(steps / record_every) - 1 at most; they
+        // travel both ways, since an instance that records less leaves its entries of them untouched
+        long long e0 = rec_rows, e1 = 0;
+        for (int b = 0; b < B; ++b) {
+            const long long n = nrec[b] < 0 ? 0 : nrec[b];
+            e0 = n < e0 ? n : e0;
+            e1 = n > e1 ? n : e1;
+        }
+        e1 += ((long long)steps + rcfg->record_every - 1) / rcfg->record_every;
+        e1 = e1 < rec_rows ? e1 : rec_rows;
+        e0 = e0 < e1 ? e0 : e1;
+        const size_t q0 = (size_t)e0, q1 = (size_t)e1;
+        r_ob = S.add_log(rec_obs, RR, 520 * nB * F, q0, q1, true); r_ac = S.add_log(rec_action, RR, 34 * nB * F, q0, q1, true);
+        r_lp = S.add_log(rec_logp, RR, nB * F, q0, q1, true); r_vl = S.add_log(rec_value, RR, nB * F, q0, q1, true);
+        r_rw = S.add_log(rec_reward, RR, nB * D, q0, q1, true); r_dn = S.add_log(rec_done, RR, nB * F, q0, q1, true);
+    }
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    auto dd = [&](int i) { return i < 0 ? nullptr : S.dev<double>(h, i); };
+    auto di = [&](int i) { return i < 0 ? nullptr : S.dev<int32_t>(h, i); };
+    auto df = [&](int i) { return i < 0 ? nullptr : S.dev<float>(h, i); };
+    if (int rc = dart_lmpc_collect_dev(
+            h, plant, pcfg, rcfg, B, k0, steps, log_rows, rec_rows, reset_rows, dd(i_tg), dd(i_prm), dd(i_pp), dd(i_ck),
+            df(i_wt), df(i_cr), df(i_nz), dd(i_x), dd(i_tilt), dd(i_up), dd(i_w), dd(i_om), dd(i_o2), di(i_oc), df(i_hi),
+            di(i_ts), dd(i_mp), dd(c_pc), dd(c_cs), di(c_es), dd(c_er), dd(c_tp), di(c_ep), dd(c_lr), di(c_ls), di(c_nr),
+            di(c_sk), dd(p_x), dd(p_t), dd(p_p), dd(l_X), dd(l_U), dd(l_pe), dd(l_pv), dd(l_L), di(l_st), di(l_it),
+            dd(l_rw), di(l_dn), df(l_vl), df(l_lp), df(r_ob), df(r_ac), df(r_lp), df(r_vl), dd(r_rw), df(r_dn), s))
+        return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+#undef DART_COLLECT_FILL
+#undef DART_COLLECT_OUT_PARAMS
+#undef DART_COLLECT_STATE_PARAMS
+
+int dart_lmpc_gae_dev(int B, int rec_rows, double gamma, double lam, const int32_t* nrec, const double* rec_reward,
+                      const float* rec_value, const float* rec_done, const float* last_value, double* adv, double* ret,
+                      void* stream) {
+    if (B < 0 || rec_rows < 0) return DART_MPC_EINVAL;
+    if (B == 0 || rec_rows == 0) return DART_MPC_OK;
+    if (!nrec || !rec_reward || !rec_value || !rec_done || !last_value || !adv || !ret) return DART_MPC_EINVAL;
+    dartmpc::GaeArgs a;
+    a.B = B; a.rec_rows = rec_rows; a.gamma = gamma; a.lam = lam; a.nrec = nrec; a.rec_reward = rec_reward;
+    a.rec_value = rec_value; a.rec_done = rec_done; a.last_value = last_value; a.adv = adv; a.ret = ret;
+    return dartmpc_launch_lmpc_gae(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_gae(int B, int rec_rows, double gamma, double lam, const int32_t* nrec, const double* rec_reward,
+                  const float* rec_value, const float* rec_done, const float* last_value, double* adv, double* ret) {
+    if (B < 0 || rec_rows < 0) return DART_MPC_EINVAL;
+    if (B == 0 || rec_rows == 0) return DART_MPC_OK;
+    if (!nrec || !rec_reward || !rec_value || !rec_done || !last_value || !adv || !ret) return DART_MPC_EINVAL;
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    const size_t n = (size_t)B * rec_rows;
+    if (S.reserve(sizeof(double) * 3 * n + sizeof(float) * (2 * n + B) + sizeof(int32_t) * B + 8 * 256, 0) != hipSuccess)
+        return DART_MPC_EHIP;
+    S.begin();
+    dartmpc::GaeArgs a;
+    a.B = B; a.rec_rows = rec_rows; a.gamma = gamma; a.lam = lam;
+    a.nrec = S.in(nrec, (size_t)B); a.rec_reward = S.in(rec_reward, n); a.rec_value = S.in(rec_value, n);
+    a.rec_done = S.in(rec_done, n); a.last_value = S.in(last_value, (size_t)B);
+    a.adv = S.inout(adv, n); a.ret = S.inout(ret, n);      // (rows >= nrec[b] keep the caller's contents)
+    hipError_t e = S.upload(D->stream);
+    if (e == hipSuccess) e = dartmpc_launch_lmpc_gae(&a, D->stream);
+    if (e == hipSuccess) e = S.download_inout(D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.finish_inout();
     return DART_MPC_OK;
 }

@@ -43,7 +43,9 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_mpc_build_flavor",
            "dart_plant_config_default", "dart_rmpc_loop_config_default", "dart_rmpc_loop_step_dev",
            "dart_pmpc_loop_step_dev", "dart_rmpc_rollout_dev", "dart_pmpc_rollout_dev", "dart_rmpc_rollout",
-           "dart_pmpc_rollout", "dart_lmpc_loop_step_dev", "dart_lmpc_rollout_dev", "dart_lmpc_rollout")
+           "dart_pmpc_rollout", "dart_lmpc_loop_step_dev", "dart_lmpc_rollout_dev", "dart_lmpc_rollout",
+           "dart_lmpc_reward_config_default", "dart_lmpc_experience_step_dev", "dart_lmpc_collect_dev",
+           "dart_lmpc_collect", "dart_lmpc_gae_dev", "dart_lmpc_gae")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -73,6 +75,16 @@ class RmpcLoopConfig(ctypes.Structure):
                 ("rls_lambda", ctypes.c_double), ("pos_tol", ctypes.c_double)]
 
 
+class RewardConfig(ctypes.Structure):
+    """Mirror of ``struct dart_lmpc_reward_config`` (reward, done and record settings of the experience collection)."""
+    _fields_ = [("sigma_pos", ctypes.c_double), ("sigma_vel", ctypes.c_double), ("w_pos", ctypes.c_double),
+                ("w_vel", ctypes.c_double), ("w_change", ctypes.c_double), ("w_d_ctrl", ctypes.c_double),
+                ("success_tol", ctypes.c_double), ("success_bonus", ctypes.c_double), ("oob_penalty", ctypes.c_double),
+                ("tray_limit", ctypes.c_double * 2), ("max_per_dim_rms", ctypes.c_double),
+                ("time_penalty_rate", ctypes.c_double), ("max_episode_steps", ctypes.c_int32),
+                ("record_every", ctypes.c_int32), ("done_sticky", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 # Arrays of the closed-loop rollouts in the argument order of include/dart_mpc.h: (name, row width, dtype);
 # width 0 = one scalar per instance, "nw" = the solver's w.  State arrays are [B, width], logs [rows, B, width].
 RMPC_LOOP_STATE = (("x", 6, np.float64), ("tilt", 2, np.float64), ("prev", 4, np.float64), ("u_prev", 2, np.float64),
@@ -95,6 +107,18 @@ LMPC_LOOP_IO = (("state", 8, np.float64), ("u0", 2, np.float64), ("f", 0, np.flo
                 ("iters", 0, np.int32))
 LMPC_LOOP_LOGS = (("X", 8, np.float64), ("U_cmd", 2, np.float64), ("pos_error", 0, np.float64), ("pvec", 34, np.float64),
                   ("loss", 0, np.float64), ("status", 0, np.int32), ("iters", 0, np.int32))
+# experience collection (dart_lmpc_collect): the collection state [B, width], the reset pool [reset_rows, B, width],
+# the per-step logs [rows, B] and the records [rec_rows, B, width]
+LMPC_COLLECT_STATE = (("prev_cmd", 2, np.float64), ("control_seen", 2, np.float64), ("ep_step", 0, np.int32),
+                      ("ep_return", 0, np.float64), ("time_penalty", 0, np.float64), ("episodes", 0, np.int32),
+                      ("last_return", 0, np.float64), ("last_steps", 0, np.int32), ("nrec", 0, np.int32),
+                      ("sticky", 0, np.int32))
+LMPC_COLLECT_POOL = (("reset_x", 8, np.float64), ("reset_target", 8, np.float64), ("reset_pvec", 34, np.float64))
+LMPC_COLLECT_LOGS = (("reward", 0, np.float64), ("done", 0, np.int32), ("value", 0, np.float32), ("logp", 0, np.float32))
+LMPC_COLLECT_REC = (("rec_obs", 520, np.float32), ("rec_action", 34, np.float32), ("rec_logp", 0, np.float32),
+                    ("rec_value", 0, np.float32), ("rec_reward", 0, np.float64), ("rec_done", 0, np.float32))
+DONE_OOB, DONE_MAX_STEPS = 1, 2                 # bits of the done log
+CRITIC_NWEIGHTS = 520 * 64 + 64 + 64 * 64 + 64 + 64 + 1
 LOG_INT_FILL = int(np.iinfo(np.int32).min)      # prefill of the int32 logs (the float logs are prefilled with NaN)
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -244,6 +268,19 @@ def lib():
         for fn in (L.dart_lmpc_rollout_dev, L.dart_lmpc_rollout):
             fn.argtypes = [vp, vp, vp] + [ci] * 4 + [vp] * 24
             fn.restype = ctypes.c_int
+    if hasattr(L, "dart_lmpc_collect_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+        L.dart_lmpc_reward_config_default.argtypes = [ctypes.POINTER(RewardConfig)]
+        L.dart_lmpc_reward_config_default.restype = None
+        L.dart_lmpc_experience_step_dev.argtypes = [vp, vp, vp] + [ci] * 5 + [vp] * 37
+        L.dart_lmpc_experience_step_dev.restype = ctypes.c_int
+        for fn in (L.dart_lmpc_collect_dev, L.dart_lmpc_collect):
+            fn.argtypes = [vp, vp, vp, vp] + [ci] * 6 + [vp] * 48
+            fn.restype = ctypes.c_int
+        L.dart_lmpc_gae_dev.argtypes = [ci, ci, cd, cd] + [vp] * 8
+        L.dart_lmpc_gae_dev.restype = ctypes.c_int
+        L.dart_lmpc_gae.argtypes = [ci, ci, cd, cd] + [vp] * 7
+        L.dart_lmpc_gae.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
         L.dart_mpc_bind.restype = ctypes.c_int
@@ -327,7 +364,7 @@ def _loop_shape(B, width, **sizes):
 
 def loop_logs(spec, rows, B):
     """Host log arrays of a rollout, [rows, B, width] each: NaN (float) / LOG_INT_FILL (int32) prefilled."""
-    return {name: np.full((rows,) + _loop_shape(B, width), np.nan if dt is np.float64 else LOG_INT_FILL, dt)
+    return {name: np.full((rows,) + _loop_shape(B, width), np.nan if np.issubdtype(dt, np.floating) else LOG_INT_FILL, dt)
             for name, width, dt in spec}
 
 
@@ -828,6 +865,127 @@ class LmpcSolver(Solver):
         if model_params is not None:
             st["model_params"][:] = np.asarray(model_params, np.float64).reshape(B, 34)
         return st
+
+    # -- experience collection (dart_lmpc_experience_step_dev / dart_lmpc_collect_dev / dart_lmpc_collect) ----
+    def experience_step_dev(self, B, k, log_rows, rec_rows, reset_rows, pcfg, rcfg, weights, critic, action, log_X,
+                            target, plant_pvec, state, cstate, logs, rec, pool=None, solve_state=0, mean_out=0, stream=0):
+        """One experience launch for step k (after post(k)).  ``state`` (history, timestep, u_prev, x, tilt),
+        ``cstate`` (LMPC_COLLECT_STATE), ``logs`` (LMPC_COLLECT_LOGS), ``rec`` (LMPC_COLLECT_REC) and ``pool``
+        (LMPC_COLLECT_POOL) map names to device pointers (ints).  Asynchronous."""
+        pool = pool or {}
+        p = lambda v: ctypes.c_void_p(int(v)) if v else None
+        rc = lib().dart_lmpc_experience_step_dev(
+            self._h, ctypes.byref(pcfg) if pcfg is not None else None, ctypes.byref(rcfg) if rcfg is not None else None,
+            int(B), int(k), int(log_rows), int(rec_rows), int(reset_rows), p(weights), p(critic), p(state["history"]),
+            p(action), p(log_X), p(state["timestep"]), p(state["u_prev"]), p(target), p(plant_pvec), p(state["x"]),
+            p(state["tilt"]), p(solve_state), *_dev_ptrs(LMPC_COLLECT_STATE, cstate),
+            *[p(pool.get(n, 0)) for n, _, _ in LMPC_COLLECT_POOL], *_dev_ptrs(LMPC_COLLECT_LOGS, logs),
+            *[p(rec.get(n, 0)) for n, _, _ in LMPC_COLLECT_REC], p(mean_out), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_experience_step_dev")
+
+    def collect_dev(self, B, k0, steps, log_rows, rec_rows, reset_rows, target, prm, plant_pvec, state, cstate, logs,
+                    clogs, rec, pcfg, rcfg, weights, critic, current_k, noise=0, pool=None, plant=None, stream=0):
+        """``rollout_dev`` with experience collection: device pointers (ints) as there, plus ``cstate``
+        (LMPC_COLLECT_STATE), ``clogs`` (LMPC_COLLECT_LOGS), ``rec`` (LMPC_COLLECT_REC) and ``pool``
+        (LMPC_COLLECT_POOL, with ``reset_rows`` > 0).  ``target`` and ``plant_pvec`` are rewritten by resets."""
+        plant = plant or plant_config()
+        pool = pool or {}
+        p = lambda v: ctypes.c_void_p(int(v)) if v else None
+        rc = lib().dart_lmpc_collect_dev(
+            self._h, ctypes.byref(plant), ctypes.byref(pcfg) if pcfg is not None else None,
+            ctypes.byref(rcfg) if rcfg is not None else None, int(B), int(k0), int(steps), int(log_rows), int(rec_rows),
+            int(reset_rows), p(target), p(prm), p(plant_pvec), p(current_k), p(weights), p(critic), p(noise),
+            *_dev_ptrs(LMPC_LOOP_STATE, state), *_dev_ptrs(LMPC_COLLECT_STATE, cstate),
+            *[p(pool.get(n, 0)) for n, _, _ in LMPC_COLLECT_POOL], *_dev_ptrs(LMPC_LOOP_LOGS, logs),
+            *_dev_ptrs(LMPC_COLLECT_LOGS, clogs), *[p(rec.get(n, 0)) for n, _, _ in LMPC_COLLECT_REC], stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_collect_dev")
+
+    def collect(self, k0, steps, target, plant_pvec, state, cstate, logs, clogs, rec, policy, rcfg=None, prm=None,
+                noise=None, pool=None, plant=None):
+        """Host arrays (blocking): ``rollout`` with experience collection.  ``target`` [B, 8] and ``plant_pvec``
+        [B, 34] (float64, C-contiguous) are updated in place by resets, ``cstate`` (``collect_state``) is advanced,
+        ``clogs`` (``loop_logs(LMPC_COLLECT_LOGS, rows, B)``) rows k0 .. k0+steps-1 and the records ``rec``
+        (``loop_logs(LMPC_COLLECT_REC, rec_rows, B)``) are filled in place.  ``policy`` (a ``dart_mpc.lmpc.LmpcPolicy``
+        with ``critic_weights``) is required; ``pool`` maps the names of LMPC_COLLECT_POOL to [reset_rows, B, width]
+        arrays (None: episode ends only reset the counters)."""
+        B, rows = state["x"].shape[0], logs["X"].shape[0]
+        rec_rows = rec["rec_reward"].shape[0]
+        reset_rows = 0 if not pool else pool["reset_x"].shape[0]
+        prm = np.ascontiguousarray(np.tile(LMPC_PRM_DEFAULT, (B, 1)) if prm is None else prm, np.float64).reshape(B, 22)
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, np.float32)
+            if noise.shape != (rows, B, 34):
+                raise DartMPCError(f"collect noise must have shape {(rows, B, 34)}")
+        tg, pp = _host_ptrs((("target", 8, np.float64), ("plant_pvec", 34, np.float64)),
+                            {"target": target, "plant_pvec": plant_pvec}, (B,))
+        pcfg = wt = cw = ck = None
+        if policy is not None:
+            pcfg, wt = ctypes.byref(policy.cfg), np.ascontiguousarray(policy.weights, np.float32)
+            cw = None if policy.critic_weights is None else np.ascontiguousarray(policy.critic_weights, np.float32)
+            ck = np.ascontiguousarray(policy.current_k, np.float64).reshape(B, 34)
+        rcfg = rcfg if rcfg is not None else reward_config()
+        plant = plant or plant_config()
+        pool_ptrs = (_host_ptrs(LMPC_COLLECT_POOL, pool, (reset_rows, B)) if reset_rows else [None] * 3)
+        rc = lib().dart_lmpc_collect(
+            self._h, ctypes.byref(plant), pcfg, ctypes.byref(rcfg), B, int(k0), int(steps), rows, rec_rows, reset_rows,
+            tg, _ptr(prm), pp, _ptr(ck), _ptr(wt), _ptr(cw), _ptr(noise),
+            *_host_ptrs(LMPC_LOOP_STATE, state, (B,), nw=self.nw), *_host_ptrs(LMPC_COLLECT_STATE, cstate, (B,)),
+            *pool_ptrs, *_host_ptrs(LMPC_LOOP_LOGS, logs, (rows, B)), *_host_ptrs(LMPC_COLLECT_LOGS, clogs, (rows, B)),
+            *_host_ptrs(LMPC_COLLECT_REC, rec, (rec_rows, B)), None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_collect")
+
+    @staticmethod
+    def collect_state(u_prev):
+        """The collection state of a fresh collection: ``prev_cmd`` and ``control_seen`` start at the initial
+        ``u_prev`` [B, 2] (rlmpc2.py:564), every counter at zero."""
+        u_prev = np.asarray(u_prev, np.float64).reshape(-1, 2)
+        B = u_prev.shape[0]
+        st = {name: np.zeros(_loop_shape(B, width), dt) for name, width, dt in LMPC_COLLECT_STATE}
+        st["prev_cmd"][:] = u_prev
+        st["control_seen"][:] = u_prev
+        return st
+
+
+def reward_config(**over) -> RewardConfig:
+    """``dart_lmpc_reward_config`` with the library's defaults (what LMPC/src/run.py effectively runs with), fields
+    overridden by keyword (``tray_limit``: a pair)."""
+    c = RewardConfig()
+    lib().dart_lmpc_reward_config_default(ctypes.byref(c))
+    names = [f[0] for f in c._fields_]
+    for k, v in over.items():
+        if k not in names:
+            raise DartMPCError(f"RewardConfig has no field {k!r} (fields: {names})")
+        if k == "tray_limit":
+            c.tray_limit[0], c.tray_limit[1] = float(v[0]), float(v[1])
+        elif k in ("max_episode_steps", "record_every", "done_sticky", "reserved"):
+            setattr(c, k, int(v))
+        else:
+            setattr(c, k, float(v))
+    return c
+
+
+def gae(nrec, rec_reward, rec_value, rec_done, last_value, gamma=0.99, lam=0.95, adv=None, ret=None):
+    """Generalised advantage estimation on the GPU (dart_lmpc_gae) over the records [rec_rows, B] of B instances,
+    instance b using its first ``nrec[b]`` rows and ``last_value[b]``.  Returns (adv, ret = adv + value), float64
+    [rec_rows, B]; rows >= nrec[b] keep the contents of ``adv`` / ``ret`` (NaN in fresh arrays)."""
+    rw = np.ascontiguousarray(rec_reward, np.float64)
+    rows, B = rw.shape
+    c = lambda a, dt, shape: np.ascontiguousarray(a, dt).reshape(shape)
+    nrec, lv = c(nrec, np.int32, (B,)), c(last_value, np.float32, (B,))
+    rv, rd = c(rec_value, np.float32, (rows, B)), c(rec_done, np.float32, (rows, B))
+    adv = np.full((rows, B), np.nan) if adv is None else adv
+    ret = np.full((rows, B), np.nan) if ret is None else ret
+    for a in (adv, ret):
+        if a.dtype != np.float64 or a.shape != (rows, B) or not a.flags.c_contiguous:
+            raise DartMPCError(f"gae adv / ret must be C-contiguous float64 arrays of shape {(rows, B)}")
+    rc = lib().dart_lmpc_gae(B, rows, float(gamma), float(lam), _ptr(nrec), _ptr(rw), _ptr(rv), _ptr(rd), _ptr(lv),
+                             _ptr(adv), _ptr(ret))
+    if rc != 0:
+        raise DartMPCError(f"dart_lmpc_gae failed ({rc})")
+    return adv, ret
 
 
 def rls_update_batch(theta, P, phi, y, lam=0.995):

@@ -496,3 +496,226 @@ def rollout_lmpc(x0, targets, plant_pvec, steps: int, N: int = 30, policy_seed=0
     finally:
         solver.close()
     return _lmpc_result(B, steps, Ts, targets, lg, state["x"], state, wall, return_logs)
+
+
+# ---------------------------------------------------------------------------------------------
+# LMPC experience collection: the training half of RLMPC._rl_worker (rlmpc2.py:537-938) up to the PPO update
+LOG_SQRT_2PI = np.float32(0.91893853320467274178)
+
+
+def _unpack_f32(w, shapes):
+    w = np.asarray(w, np.float32)
+    out, o = [], 0
+    for shape in shapes:
+        n = int(np.prod(shape))
+        out.append(w[o:o + n].reshape(shape)); o += n
+    return out
+
+
+def lmpc_actor_mean(weights, obs):
+    """Policy.mean_net (:39-46) on obs [B, 520] in fp32; returns (mean [B, 34], the unclamped log_std [34])."""
+    W1, b1, W2, b2, W3, b3, log_std = _unpack_f32(weights, ((520, 64), (64,), (64, 64), (64,), (64, 34), (34,), (34,)))
+    obs = np.asarray(obs, np.float32)
+    h1 = np.tanh(obs @ W1 + b1).astype(np.float32)
+    h2 = np.tanh(h1 @ W2 + b2).astype(np.float32)
+    return (h2 @ W3 + b3).astype(np.float32), log_std
+
+
+def lmpc_critic_value(critic, obs):
+    """Policy.value_net (:48-55) on obs [B, 520] in fp32: value [B]."""
+    V1, c1, V2, c2, V3, c3 = _unpack_f32(critic, ((520, 64), (64,), (64, 64), (64,), (64,), (1,)))
+    obs = np.asarray(obs, np.float32)
+    g1 = np.tanh(obs @ V1 + c1).astype(np.float32)
+    g2 = np.tanh(g1 @ V2 + c2).astype(np.float32)
+    return (g2 @ V3 + c3[0]).astype(np.float32)
+
+
+def lmpc_log_prob(mean, log_std, raw, log_std_min, log_std_max):
+    """Normal(mean, exp(clamp(log_std))).log_prob(raw).sum(-1) (:699) in fp32: [B]."""
+    lsd = np.clip(np.asarray(log_std, np.float32), np.float32(log_std_min), np.float32(log_std_max))
+    sd = np.exp(lsd).astype(np.float32)
+    z = (np.asarray(raw, np.float32) - np.asarray(mean, np.float32)).astype(np.float32)
+    lp = -(z * z) / (np.float32(2) * (sd * sd)) - lsd - LOG_SQRT_2PI
+    return lp.astype(np.float32).sum(axis=-1, dtype=np.float32)
+
+
+def lmpc_change_cost(raw, max_delta, action_scale, max_per_dim_rms):
+    """|delta_z| of :680-709 per instance, on fp32 values as the reference's tensors: delta_z = raw (max_delta
+    action_scale), damped by max_per_dim_rms / (rms + 1e-12) when rms = |delta_z| / sqrt(34) exceeds it."""
+    raw = np.asarray(raw, np.float32).reshape(-1, 34)
+    out = np.empty(raw.shape[0])
+    for b, r in enumerate(raw):
+        dz = r * np.float32(max_delta * action_scale)
+        rms = float(np.linalg.norm(dz)) / np.sqrt(34)
+        if rms > max_per_dim_rms:
+            dz = dz * np.float32(max_per_dim_rms / (rms + 1e-12))
+        out[b] = float(np.linalg.norm(dz))
+    return out
+
+
+def lmpc_reward_step(rcfg, cs, x, target, control, raw, max_delta=0.02, action_scale=1.0):
+    """Reward, done and the episode bookkeeping of one step for B controllers (:703-740, :771-773, :900-935), the
+    batched numpy statement of what lmpc_experience_kernel computes: fp64, except change_cost (fp32, :680-709).
+
+    ``x`` [B, 8] is the state the solve saw, ``control`` [B, 2] the u_prev policy step k observed, ``raw`` [B, 34]
+    the drawn action.  ``cs`` (``LmpcSolver.collect_state``) is advanced in place: prev_cmd, ep_step, ep_return,
+    time_penalty and, at an episode end, episodes, last_return, last_steps.  The in_contact penalty (:735) is left
+    out (LmpcPlant has no contact model).  Returns (reward [B] float64, done [B] int32: bit 1 out of bounds, bit 2
+    max_episode_steps)."""
+    x, target, control = (np.asarray(a, float) for a in (x, target, control))
+    pos_err = np.sqrt(np.abs(target[:, 0] - x[:, 0]) ** 2 + np.abs(target[:, 2] - x[:, 2]) ** 2)
+    vel_err = np.sqrt(x[:, 1] ** 2 + x[:, 3] ** 2)
+    e_p = np.exp(-(pos_err ** 2) / (2 * rcfg.sigma_pos ** 2))
+    e_v = np.exp(-(vel_err ** 2) / (2 * rcfg.sigma_vel ** 2))
+    prox = rcfg.w_pos * e_p + rcfg.w_vel * e_p * e_v
+    change = lmpc_change_cost(raw, max_delta, action_scale, rcfg.max_per_dim_rms)
+    rate = np.abs(control[:, 0] - cs["prev_cmd"][:, 0]) + np.abs(control[:, 1] - cs["prev_cmd"][:, 1])
+    cs["prev_cmd"][:] = control
+    reward = prox - rcfg.w_change * change - rcfg.w_d_ctrl * rate - cs["time_penalty"]
+    reward = np.where((pos_err < rcfg.success_tol) & (vel_err < rcfg.success_tol), reward + rcfg.success_bonus, reward)
+    cs["ep_step"] += 1
+    oob = (np.abs(x[:, 0]) > rcfg.tray_limit[0]) | (np.abs(x[:, 2]) > rcfg.tray_limit[1])
+    reward = np.where(oob, reward - rcfg.oob_penalty, reward)
+    done = (oob * 1 + (cs["ep_step"] >= rcfg.max_episode_steps) * 2).astype(np.int32)
+    cs["time_penalty"] += rcfg.time_penalty_rate
+    cs["ep_return"] += reward
+    end = done != 0
+    cs["last_return"][end] = cs["ep_return"][end]
+    cs["last_steps"][end] = cs["ep_step"][end]
+    cs["episodes"][end] += 1
+    cs["ep_return"][end] = 0.0
+    cs["ep_step"][end] = 0
+    cs["time_penalty"][end] = 0.0
+    return reward, done
+
+
+def gae_numpy(nrec, rec_reward, rec_value, rec_done, last_value, gamma=0.99, lam=0.95):
+    """compute_gae (:592-599) per instance over its first nrec[b] records [rec_rows, B], fp64: (adv, ret = adv +
+    value), NaN in the rows an instance has not recorded."""
+    rw = np.asarray(rec_reward, float)
+    rv, rd = np.asarray(rec_value, float), np.asarray(rec_done, float)
+    rows, B = rw.shape
+    adv, ret = np.full((rows, B), np.nan), np.full((rows, B), np.nan)
+    for b in range(B):
+        n = int(min(max(int(nrec[b]), 0), rows))
+        g, v_next = 0.0, float(last_value[b])
+        for s in reversed(range(n)):
+            delta = rw[s, b] + gamma * v_next * (1.0 - rd[s, b]) - rv[s, b]
+            g = delta + gamma * lam * (1.0 - rd[s, b]) * g
+            adv[s, b], ret[s, b] = g, g + rv[s, b]
+            v_next = rv[s, b]
+    return adv, ret
+
+
+def _collect_setup(B, steps, policy_seed, critic_seed, reset_pool, rec_rows, rcfg):
+    from ._lib import LMPC_COLLECT_LOGS, LMPC_COLLECT_REC, LmpcSolver, loop_logs, reward_config
+    from .lmpc import LmpcPolicy, init_critic_weights
+    policy = LmpcPolicy(B, seed=policy_seed, critic_weights=init_critic_weights(critic_seed))
+    rcfg = rcfg if rcfg is not None else reward_config()
+    if rec_rows is None:
+        rec_rows = steps // int(rcfg.record_every) + 1
+    pool = None
+    if reset_pool is not None:
+        pool = {k: np.ascontiguousarray(reset_pool[k], np.float64) for k in ("reset_x", "reset_target", "reset_pvec")}
+    cs = LmpcSolver.collect_state(np.zeros((B, 2)))
+    return policy, rcfg, pool, cs, loop_logs(LMPC_COLLECT_LOGS, steps, B), loop_logs(LMPC_COLLECT_REC, rec_rows, B)
+
+
+def _collect_result(res, cs, clogs, rec, targets, plant_pvec):
+    exp = dict(rec)
+    exp.update(clogs)
+    exp.update(cs)
+    exp.update(target=targets, plant_pvec=plant_pvec)
+    return res + (exp,)
+
+
+def run_lmpc_collect(x0, targets, plant_pvec, steps: int, N: int = 30, policy_seed=0, critic_seed=1, noise_seed=None,
+                     Ts: float = 0.002, prm=None, device: int = 0, plant_kw: dict | None = None, rcfg=None,
+                     reset_pool=None, rec_rows=None, policy=None, restoration: bool = True):
+    """``run_lmpc`` with experience collection on the host, the loop a user would otherwise write: per step the fused
+    policy step + solve, then in numpy the critic, the log-probability, ``lmpc_reward_step``, the record and the
+    reset into the next episode from ``reset_pool`` (dict reset_x / reset_target [R, B, 8], reset_pvec [R, B, 34];
+    None: episode ends only reset the counters).  ``rcfg`` is a ``reward_config()``; ``rec_rows`` defaults to what
+    ``steps`` can fill.  Returns ``run_lmpc``'s (logs, statuses, extra) plus a dict of the records (rec_*), the
+    per-step logs (reward, done, value, logp), the collection state and the final target / plant_pvec.
+    ``policy`` (an ``LmpcPolicy`` with ``critic_weights``) replaces the seeded one; ``restoration`` is the solver's."""
+    from ._lib import LMPC_LOOP_LOGS, LmpcSolver, loop_logs
+    from .lmpc import policy_solve_batch
+    x0, B, targets, plant_pvec, prm, _, _ = _lmpc_setup(x0, targets, plant_pvec, prm, None, None)
+    targets, plant_pvec = targets.copy(), plant_pvec.copy()
+    pol, rcfg, pool, cs, clogs, rec = _collect_setup(B, steps, policy_seed, critic_seed, reset_pool, rec_rows, rcfg)
+    policy = policy if policy is not None else pol
+    noise = lmpc_noise(noise_seed, steps, B)
+    lg = loop_logs(LMPC_LOOP_LOGS, steps, B)
+    plant = LmpcPlant(x0, plant_pvec, dt=Ts, **(plant_kw or {}))
+    solver = LmpcSolver(N=N, Ts=Ts, B_max=max(B, 1), device=device, restoration=restoration)
+    u_prev, w = np.zeros((B, 2)), np.zeros((B, solver.nw))
+    every, rows = int(rcfg.record_every), rec["rec_reward"].shape[0]
+    wall = 0.0
+    try:
+        for k in range(steps):
+            xk = plant.x.copy()
+            lg["X"][k] = xk
+            t0 = time.perf_counter()
+            out = policy_solve_batch(solver, policy, xk, u_prev, targets, prm, w_warm=w, want_w=True, noise=noise[k])
+            obs = policy.history.reshape(B, 520)
+            mean, log_std = lmpc_actor_mean(policy.weights, obs)
+            value = lmpc_critic_value(policy.critic_weights, obs)
+            logp = lmpc_log_prob(mean, log_std, out["action"], policy.cfg.log_std_min, policy.cfg.log_std_max)
+            reward, done = lmpc_reward_step(rcfg, cs, xk, targets, u_prev, out["action"], policy.cfg.max_delta,
+                                            policy.cfg.action_scale)
+            clogs["reward"][k], clogs["done"][k], clogs["value"][k], clogs["logp"][k] = reward, done, value, logp
+            cs["sticky"] |= done
+            for b in np.where((policy.timestep - 1) % every == 0)[0]:
+                n = int(cs["nrec"][b])
+                if n < rows:
+                    rec["rec_obs"][n, b], rec["rec_action"][n, b] = obs[b], out["action"][b]
+                    rec["rec_logp"][n, b], rec["rec_value"][n, b], rec["rec_reward"][n, b] = logp[b], value[b], reward[b]
+                    rec["rec_done"][n, b] = float((cs["sticky"][b] if rcfg.done_sticky else done[b]) != 0)
+                    cs["nrec"][b] = n + 1
+                cs["sticky"][b] = 0
+            wall += time.perf_counter() - t0
+            lg["pvec"][k] = policy.model_params
+            w, u_prev = out["w"], out["u0"].copy()
+            cs["control_seen"][:] = u_prev
+            lg["U_cmd"][k], lg["loss"][k], lg["status"][k], lg["iters"][k] = out["u0"], out["f"], out["status"], out["iters"]
+            xn = plant.step(out["u0"])
+            dx, dy = xn[:, 0] - targets[:, 0], xn[:, 2] - targets[:, 2]
+            lg["pos_error"][k] = np.sqrt(dx * dx + dy * dy)
+            if pool is not None:
+                for b in np.where(done != 0)[0]:
+                    e = (int(cs["episodes"][b]) - 1) % pool["reset_x"].shape[0]
+                    plant.x[b], plant.tilt[b] = pool["reset_x"][e, b], 0.0
+                    targets[b], plant.pvec[b] = pool["reset_target"][e, b], pool["reset_pvec"][e, b]
+    finally:
+        solver.close()
+    state = {"x": plant.x.copy(), "tilt": plant.tilt.copy(), "u_prev": u_prev, "w": w,
+             "model_params": policy.model_params.copy(), "obs_mean": policy.obs_mean, "obs_M2": policy.obs_M2,
+             "obs_count": policy.obs_count, "history": policy.history.reshape(B, 520), "timestep": policy.timestep}
+    res = _lmpc_result(B, steps, Ts, targets, lg, plant.x, state, wall, True)
+    return _collect_result(res, cs, clogs, rec, targets, plant.pvec.copy())
+
+
+def collect_lmpc(x0, targets, plant_pvec, steps: int, N: int = 30, policy_seed=0, critic_seed=1, noise_seed=None,
+                 Ts: float = 0.002, prm=None, device: int = 0, plant_kw: dict | None = None, rcfg=None,
+                 reset_pool=None, rec_rows=None, policy=None, restoration: bool = True):
+    """``run_lmpc_collect`` on the device (dart_lmpc_collect): same arguments, same return values."""
+    from ._lib import LMPC_LOOP_LOGS, LmpcSolver, loop_logs, plant_config
+    x0, B, targets, plant_pvec, prm, _, _ = _lmpc_setup(x0, targets, plant_pvec, prm, None, None)
+    targets, plant_pvec = np.ascontiguousarray(targets.copy()), np.ascontiguousarray(plant_pvec.copy())
+    pol, rcfg, pool, cs, clogs, rec = _collect_setup(B, steps, policy_seed, critic_seed, reset_pool, rec_rows, rcfg)
+    policy = policy if policy is not None else pol
+    noise = lmpc_noise(noise_seed, steps, B) if noise_seed is not None else None
+    lg = loop_logs(LMPC_LOOP_LOGS, steps, B)
+    plant = plant_config(**{k: v for k, v in (plant_kw or {}).items()})
+    solver = LmpcSolver(N=N, Ts=Ts, B_max=max(B, 1), device=device, restoration=restoration)
+    try:
+        state = solver.loop_state(x0, policy=policy)
+        t0 = time.perf_counter()
+        solver.collect(0, steps, targets, plant_pvec, state, cs, lg, clogs, rec, policy, rcfg=rcfg, prm=prm, noise=noise,
+                       pool=pool, plant=plant)
+        wall = time.perf_counter() - t0
+    finally:
+        solver.close()
+    res = _lmpc_result(B, steps, Ts, targets, lg, state["x"], state, wall, True)
+    return _collect_result(res, cs, clogs, rec, targets, plant_pvec)

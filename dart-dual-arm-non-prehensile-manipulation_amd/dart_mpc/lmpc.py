@@ -19,7 +19,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import DartMPCError, LMPC_PRM_DEFAULT, LmpcSolver, _ptr, lib
+from ._lib import CRITIC_NWEIGHTS, DartMPCError, LMPC_PRM_DEFAULT, LmpcSolver, _ptr, lib, reward_config  # noqa: F401
 
 HIST, PB, PH, PA = 10, 52, 64, 34
 NWEIGHTS = 520 * 64 + 64 + 64 * 64 + 64 + 64 * 34 + 34 + 34
@@ -65,15 +65,31 @@ def init_policy_weights(seed=0, std_init=0.1):
     return np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in parts]).astype(np.float32)
 
 
-class LmpcPolicy:
-    """B independent parameter policies; state arrays live on the host and are staged per call."""
+def init_critic_weights(seed=0):
+    """Packed fp32 weights (input-major: V1[520][64], c1[64], V2[64][64], c2[64], V3[64], c3[1]) of a freshly
+    initialised Policy.value_net (orthogonal, gain sqrt(2), zero bias, :48-69)."""
+    rng = np.random.default_rng(seed)
+    g = np.sqrt(2.0)
+    V1 = _orthogonal(rng, 64, 520, g).T
+    V2 = _orthogonal(rng, 64, 64, g).T
+    V3 = _orthogonal(rng, 1, 64, g).T
+    parts = [V1, np.zeros(64), V2, np.zeros(64), V3, np.zeros(1)]
+    return np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in parts]).astype(np.float32)
 
-    def __init__(self, B, weights=None, current_k=None, seed=0, **cfg):
+
+class LmpcPolicy:
+    """B independent parameter policies; state arrays live on the host and are staged per call.  ``critic_weights``
+    (optional, ``init_critic_weights``) is the value net the experience collection evaluates."""
+
+    def __init__(self, B, weights=None, current_k=None, seed=0, critic_weights=None, **cfg):
         self.B = int(B)
         self.cfg = policy_config(**cfg)
         self.weights = np.ascontiguousarray(init_policy_weights(seed) if weights is None else weights, np.float32)
         if self.weights.size != NWEIGHTS:
             raise ValueError(f"policy weights must have {NWEIGHTS} floats")
+        self.critic_weights = None if critic_weights is None else np.ascontiguousarray(critic_weights, np.float32)
+        if self.critic_weights is not None and self.critic_weights.size != CRITIC_NWEIGHTS:
+            raise ValueError(f"critic weights must have {CRITIC_NWEIGHTS} floats")
         if current_k is None:     # :566-568: mid-range with +-5 % jitter
             rng = np.random.default_rng(seed + 1)
             k_max = self.cfg.k_max

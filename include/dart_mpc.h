@@ -527,6 +527,127 @@ int dart_lmpc_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const 
                       double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
                       int32_t *log_status, int32_t *log_iters, void *hip_stream);
 
+/* LMPC experience collection (handle of variant DART_MPC_LMPC; added within ABI 8): the training half of
+ * RLMPC._rl_worker (rlmpc2.py:537-938) up to the PPO update, on the device.  dart_lmpc_collect is
+ * dart_lmpc_rollout with one experience launch after every post(k) (+ pre(k+1)) launch:
+ *     pre(k0), [solve launch(es), post(k) + pre(k+1), experience(k)] for k = k0 .. k0+steps-2,
+ *     solve launch(es), post(k0+steps-1), experience(k0+steps-1)
+ * The experience launch evaluates, for step k and on obs_k (history), raw_k (the policy's action, kept in a
+ * handle-owned buffer) and x_k (log_X row k):
+ *   - value_net(obs_k) (Policy :48-55, fp32) and the actor's mean recomputed in the policy kernel's own
+ *     accumulation order (bit for bit its mean); log-probability Normal(mean, std).log_prob(raw).sum() (:699);
+ *   - reward and done (:703-740): proximity w_pos e_p + w_vel e_p e_v, e = exp(-err^2 / (2 sigma^2)), minus
+ *     w_change |delta_z| (fp32, damped to max_per_dim_rms; the damping enters the reward only), minus w_d_ctrl
+ *     sum |control_k - prev_cmd|, minus the time penalty (+ time_penalty_rate per step), + success_bonus with both
+ *     errors below success_tol; |x_k[0]| > tray_limit[0] or |x_k[2]| > tray_limit[1]: - oob_penalty and done bit 1;
+ *     ++episode_step >= max_episode_steps: done bit 2.  The in_contact penalty (:735) has no counterpart in the
+ *     LMPC plant and is left out;
+ *   - the per-step logs reward (f64), done (int32), value, logp (fp32), row k;
+ *   - every record_every-th policy step (:742) a record obs [520], action [34], logp, value (fp32), reward (f64),
+ *     done (fp32 0 / 1) in row nrec[b]++ of the record arrays [rec_rows][B][..] while nrec[b] < rec_rows (a full
+ *     buffer drops further records).  Fields are stored under their own names: the reference's buf.add (:744)
+ *     swaps value and reward against RolloutBuffer.add (:93); that is not reproduced.  done_sticky = 1 stores the
+ *     OR of every done since the previous record (0 = the reference: this step's done only);
+ *   - at done: last_return, last_steps, episodes++, episode_return / episode_step / time_penalty zeroed, and with
+ *     reset_rows > 0 the reset x <- reset_x[e][b], tilt <- 0, target <- reset_target[e][b], plant_pvec <-
+ *     reset_pvec[e][b], e = (episodes - 1) % reset_rows (pool arrays [reset_rows][B][8 / 8 / 34]); the next
+ *     solve's input is overwritten with the same x.  u_prev, w, the policy's state and prev_cmd carry over, as the
+ *     reference's shared views do.  target and plant_pvec are therefore in/out here.
+ * Collection state (caller-owned, in/out): prev_cmd, control_seen [B][2] (both start at the initial u_prev),
+ * ep_step, ep_return, time_penalty, episodes, last_return, last_steps, nrec, sticky [B] (start at zero).
+ * Two calls of K1 and K2 steps give bit for bit what one call of K1 + K2 steps gives. */
+typedef struct dart_lmpc_reward_config {
+    double sigma_pos, sigma_vel;   /* 0.02 (:712) */
+    double w_pos, w_vel;           /* 40, 0.1 (rl_packet, rlmpc2.py:202-226) */
+    double w_change;               /* 1e-3 (:713) */
+    double w_d_ctrl;               /* 5 (:714) */
+    double success_tol;            /* 0.01 (:720) */
+    double success_bonus;          /* 20 (:721) */
+    double oob_penalty;            /* 20 (:728) */
+    double tray_limit[2];          /* {0.2, 0.15} (:726) */
+    double max_per_dim_rms;        /* 0.5 (:691) */
+    double time_penalty_rate;      /* 1e-4 (:772) */
+    int32_t max_episode_steps;     /* 20000 (rl_packet) */
+    int32_t record_every;          /* 8 (:742) */
+    int32_t done_sticky;           /* 0 */
+    int32_t reserved;
+} dart_lmpc_reward_config;
+
+/* value_net, fp32, input-major like the actor: V1[520][64], c1[64], V2[64][64], c2[64], V3[64], c3[1].  The
+ * experience and collect entries need both weight arrays 16-byte aligned on the device (EINVAL otherwise). */
+#define DART_LMPC_CRITIC_NWEIGHTS 37569
+
+void dart_lmpc_reward_config_default(dart_lmpc_reward_config *cfg);
+
+/* One experience launch for step k, for callers that sequence their own loop (after post(k) of
+ * dart_lmpc_loop_step_dev).  Device pointers, asynchronous.  action [B][34] is the action_out of step k's policy
+ * launch; state (the next solve's input) and mean_out [B][34] (the recomputed actor mean) are nullable; the reset
+ * pool is read only with reset_rows > 0. */
+int dart_lmpc_experience_step_dev(dart_mpc_handle *h, const dart_lmpc_policy_config *pcfg,
+                                  const dart_lmpc_reward_config *rcfg,
+                                  int B, int k, int log_rows, int rec_rows, int reset_rows,
+                                  const float *weights, const float *critic,
+                                  const float *history, const float *action, const double *log_X,
+                                  const int32_t *timestep, const double *u_prev,
+                                  double *target, double *plant_pvec, double *x, double *tilt, double *state,
+                                  double *prev_cmd, double *control_seen, int32_t *ep_step, double *ep_return,
+                                  double *time_penalty, int32_t *episodes, double *last_return, int32_t *last_steps,
+                                  int32_t *nrec, int32_t *sticky,
+                                  const double *reset_x, const double *reset_target, const double *reset_pvec,
+                                  double *log_reward, int32_t *log_done, float *log_value, float *log_logp,
+                                  float *rec_obs, float *rec_action, float *rec_logp, float *rec_value,
+                                  double *rec_reward, float *rec_done, float *mean_out, void *hip_stream);
+
+/* `steps` closed-loop steps with experience collection; arguments of dart_lmpc_rollout_dev plus the critic, the
+ * reward config, the collection state, the reset pool, the per-step logs and the records.  A policy is required
+ * (weights == NULL is DART_MPC_EINVAL).  Device pointers, asynchronous. */
+int dart_lmpc_collect_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                          const dart_lmpc_reward_config *rcfg,
+                          int B, int k0, int steps, int log_rows, int rec_rows, int reset_rows,
+                          double *target, const double *prm, double *plant_pvec, const double *current_k,
+                          const float *weights, const float *critic, const float *noise,
+                          double *x, double *tilt, double *u_prev, double *w, double *obs_mean, double *obs_M2,
+                          int32_t *obs_count, float *history, int32_t *timestep, double *model_params,
+                          double *prev_cmd, double *control_seen, int32_t *ep_step, double *ep_return,
+                          double *time_penalty, int32_t *episodes, double *last_return, int32_t *last_steps,
+                          int32_t *nrec, int32_t *sticky,
+                          const double *reset_x, const double *reset_target, const double *reset_pvec,
+                          double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
+                          int32_t *log_status, int32_t *log_iters,
+                          double *log_reward, int32_t *log_done, float *log_value, float *log_logp,
+                          float *rec_obs, float *rec_action, float *rec_logp, float *rec_value,
+                          double *rec_reward, float *rec_done, void *hip_stream);
+
+/* Host pointers, staged as dart_lmpc_rollout stages (of the logs and the noise only rows k0 .. k0+steps-1 travel,
+ * of the records the rows min nrec .. max nrec + ceil(steps / record_every) - 1, both ways); blocks. */
+int dart_lmpc_collect(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                      const dart_lmpc_reward_config *rcfg,
+                      int B, int k0, int steps, int log_rows, int rec_rows, int reset_rows,
+                      double *target, const double *prm, double *plant_pvec, const double *current_k,
+                      const float *weights, const float *critic, const float *noise,
+                      double *x, double *tilt, double *u_prev, double *w, double *obs_mean, double *obs_M2,
+                      int32_t *obs_count, float *history, int32_t *timestep, double *model_params,
+                      double *prev_cmd, double *control_seen, int32_t *ep_step, double *ep_return,
+                      double *time_penalty, int32_t *episodes, double *last_return, int32_t *last_steps,
+                      int32_t *nrec, int32_t *sticky,
+                      const double *reset_x, const double *reset_target, const double *reset_pvec,
+                      double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
+                      int32_t *log_status, int32_t *log_iters,
+                      double *log_reward, int32_t *log_done, float *log_value, float *log_logp,
+                      float *rec_obs, float *rec_action, float *rec_logp, float *rec_value,
+                      double *rec_reward, float *rec_done, void *hip_stream);
+
+/* Generalised advantage estimation (compute_gae, rlmpc2.py:592-599) per instance over its nrec[b] records
+ * (record arrays [rec_rows][B]), fp64, bootstrapped from last_value [B]: adv and ret = adv + value, [rec_rows][B];
+ * rows >= nrec[b] are left untouched.  Stateless (the HIP current device); normalising over the batch is a
+ * statistic of the whole buffer and is left to the caller. */
+int dart_lmpc_gae_dev(int B, int rec_rows, double gamma, double lam, const int32_t *nrec,
+                      const double *rec_reward, const float *rec_value, const float *rec_done,
+                      const float *last_value, double *adv, double *ret, void *hip_stream);
+int dart_lmpc_gae(int B, int rec_rows, double gamma, double lam, const int32_t *nrec,
+                  const double *rec_reward, const float *rec_value, const float *rec_done,
+                  const float *last_value, double *adv, double *ret);
+
 int dart_mpc_sync(dart_mpc_handle *h);
 
 const char *dart_mpc_last_error(const dart_mpc_handle *h);

@@ -1,0 +1,69 @@
+"""PPO on the LMPC parameter policy with the experience collected on the device: a usage example and a smoke
+record, not a test.  Per iteration: collect K closed-loop steps for B controllers (LmpcSolver.collect: policy step,
+solve, plant step, critic, reward, records and resets without the host), GAE on the device (_lib.gae), the
+clipped-surrogate update in torch (dart_mpc.ppo.ppo_update), then the new weights are packed into the next collect.
+The loop state, the collection state, the targets and the plants carry over from iteration to iteration.
+Prints the mean return of the episodes that ended, per iteration.
+Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps]
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "dart-dual-arm-non-prehensile-manipulation_amd"))
+import torch  # noqa: E402
+from dart_mpc import _lib, harness, ppo  # noqa: E402
+from dart_mpc.lmpc import LmpcPolicy  # noqa: E402
+from dart_mpc.workload import lmpc_batch  # noqa: E402
+
+iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+B = int(sys.argv[2]) if len(sys.argv) > 2 else 72
+K = int(sys.argv[3]) if len(sys.argv) > 3 else 256
+ep_steps = int(sys.argv[4]) if len(sys.argv) > 4 else 64
+GAMMA, LAM, N = 0.99, 0.95, 30
+
+seeds = -(-B // 18)
+D = lmpc_batch(seeds)
+target, pvec = np.ascontiguousarray(D["target"][:B]), np.ascontiguousarray(D["pvec"][:B])
+P = [lmpc_batch(seeds, seed0=100 + r) for r in range(4)]
+pool = {"reset_x": np.ascontiguousarray(np.stack([p["state"][:B] for p in P])),
+        "reset_target": np.ascontiguousarray(np.stack([p["target"][:B] for p in P])),
+        "reset_pvec": np.ascontiguousarray(np.stack([p["pvec"][:B] for p in P]))}
+rcfg = _lib.reward_config(max_episode_steps=ep_steps)
+rec_rows = K // int(rcfg.record_every) + 1
+
+torch.manual_seed(0)
+net = ppo.PolicyNet()
+opt = torch.optim.Adam(net.parameters(), lr=3e-4, weight_decay=1e-5)         # rlmpc2.py:561
+gen = torch.Generator().manual_seed(0)
+actor, critic = ppo.pack_weights(net)
+policy = LmpcPolicy(B, weights=actor, critic_weights=critic)
+solver = _lib.LmpcSolver(N=N, B_max=B)
+state = solver.loop_state(D["state"][:B], policy=policy)
+cs = solver.collect_state(np.zeros((B, 2)))
+try:
+    for it in range(iters):
+        policy.weights, policy.critic_weights = ppo.pack_weights(net)
+        lg, clg = _lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, B), _lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, B)
+        rec = _lib.loop_logs(_lib.LMPC_COLLECT_REC, rec_rows, B)
+        cs["nrec"][:] = 0
+        noise = harness.lmpc_noise(1000 + it, K, B)
+        ep0 = cs["episodes"].copy()
+        solver.collect(0, K, target, pvec, state, cs, lg, clg, rec, policy, rcfg=rcfg, noise=noise, pool=pool)
+        # bootstrap from the critic on the last observation (:776-779)
+        last_value = harness.lmpc_critic_value(policy.critic_weights, state["history"])
+        adv, ret = _lib.gae(cs["nrec"], rec["rec_reward"], rec["rec_value"], rec["rec_done"], last_value, GAMMA, LAM)
+        m = np.arange(rec_rows)[:, None] < cs["nrec"][None]
+        batch = dict(obs=rec["rec_obs"][m], action=rec["rec_action"][m], logp=rec["rec_logp"][m], adv=adv[m], ret=ret[m])
+        out = ppo.ppo_update(net, opt, batch, clip_eps=0.2, epochs=8, mini_batch_size=64, vf_coef=0.25, ent_coef=0.01,
+                             generator=gen)
+        ended = cs["episodes"] > ep0
+        mean_ret = float(cs["last_return"][ended].mean()) if ended.any() else float("nan")
+        print(f"iter {it}: samples {int(m.sum())}, episodes ended {int((cs['episodes'] - ep0).sum())}, "
+              f"mean last return {mean_ret:.2f}, mean step reward {float(clg['reward'].mean()):.3f}, "
+              f"status != 0: {float(np.mean(lg['status'] != 0)):.4f}, policy loss {out['policy_loss']:.4f}, "
+              f"value loss {out['value_loss']:.4f}, entropy {out['entropy']:.3f}", flush=True)
+finally:
+    solver.close()

@@ -7,9 +7,16 @@ Reports steps/s, solves/s, and from the rollout's logs the mean iterations per s
 status != 0 over the chain (RMPC, LMPC: warm-started; PMPC: cold-started, as in the reference).  The LMPC rows
 (policy noise from seed 0) add the largest iteration count, the count of non-zero statuses and the tail: the share
 of steps on which some instance took more than 20 iterations.
+The COLLECT rows (B = 18 x 300 steps and B = 1152 x 40 steps, N = 30, policy and noise on) time
+harness.collect_lmpc -- the LMPC rollout with one experience launch per step, episodes of 100 steps, resets from a
+pool of four rows -- against rollout_lmpc on the same inputs in the same run (the cost of the experience launch) and
+against run_lmpc_collect, the host loop a user would otherwise write.  They add the iteration and status statistics of
+the chain with resets, those of the solves that follow a reset, and how many of these were handed to the restoration
+phases: the count of status -2 among them in a second collection with the restoration phases off, where a hand-over
+ends the solve instead.
 Usage: python tools/rollout_rate.py [out.json] [steps] [steps_large] [controllers]
-``controllers``: a comma-separated subset of PMPC,RMPC,LMPC (default: all); the rows of the others are kept from an
-existing out.json.
+``controllers``: a comma-separated subset of PMPC,RMPC,LMPC,COLLECT (default: all); the rows of the others are kept
+from an existing out.json.
 """
 import json
 import os
@@ -26,7 +33,7 @@ from dart_mpc.workload import lmpc_batch, pmpc_batch  # noqa: E402
 out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "rollout_rate.json")
 steps_small = int(sys.argv[2]) if len(sys.argv) > 2 else 300
 steps_large = int(sys.argv[3]) if len(sys.argv) > 3 else 100
-controllers = sys.argv[4].upper().split(",") if len(sys.argv) > 4 else ["PMPC", "RMPC", "LMPC"]
+controllers = sys.argv[4].upper().split(",") if len(sys.argv) > 4 else ["PMPC", "RMPC", "LMPC", "COLLECT"]
 
 
 def timed(fn, *a, **kw):
@@ -85,7 +92,104 @@ def lmpc_row(seeds, B, steps):
             "speedup": t_host / t_dev}
 
 
-ROWS = {"PMPC": pmpc_row, "RMPC": rmpc_row, "LMPC": lmpc_row}
+def collect_row(seeds, B, steps):
+    from dart_mpc._lib import reward_config
+    steps = 40 if seeds > 1 else steps          # the large size runs 40 steps
+    D = lmpc_batch(seeds, seed0=0)
+    P = [lmpc_batch(seeds, seed0=100 + r) for r in range(4)]
+    pool = {"reset_x": np.stack([p["state"] for p in P]), "reset_target": np.stack([p["target"] for p in P]),
+            "reset_pvec": np.stack([p["pvec"] for p in P])}
+    la = (D["state"], D["target"], D["pvec"])
+    ep = 100 if seeds == 1 else 13              # three resets per instance at either size
+    ck = dict(N=30, policy_seed=0, critic_seed=1, noise_seed=0, reset_pool=pool, rcfg=reward_config(max_episode_steps=ep))
+    lk = dict(N=30, policy_seed=0, noise_seed=0, return_logs=True)
+    harness.run_lmpc_collect(*la, 3, **ck); harness.collect_lmpc(*la, 3, **ck); harness.rollout_lmpc(*la, 3, **lk)
+    (_, st_h, Xh, Eh), t_host = timed(harness.run_lmpc_collect, *la, steps, **ck)
+    # the two resident loops alternate, five rounds each: the windows are a few hundredths of a second
+    walls, loops = {"rollout": [], "collect": []}, {"rollout": [], "collect": []}
+    for _ in range(5):
+        (_, st_r, Xr), t = timed(harness.rollout_lmpc, *la, steps, **lk)
+        walls["rollout"].append(t); loops["rollout"].append(Xr["solve_time"] * steps)
+        (_, st_d, X, E), t = timed(harness.collect_lmpc, *la, steps, **ck)
+        walls["collect"].append(t); loops["collect"].append(X["solve_time"] * steps)
+    _, st_o, Xo, Eo = harness.collect_lmpc(*la, steps, restoration=False, **ck)
+
+    # the same two loops through the device entries (rollout_dev / collect_dev: no staging), alternating: the cost of
+    # the experience launches alone
+    import torch
+    from dart_mpc import _lib
+    from dart_mpc.lmpc import LmpcPolicy, init_critic_weights
+    pol = LmpcPolicy(B, seed=0, critic_weights=init_critic_weights(1))
+    s = _lib.LmpcSolver(N=30, B_max=B)
+    dev = lambda d: {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
+    ptr = lambda d: {k: v.data_ptr() for k, v in d.items()}
+    rec_rows = steps // 8 + 1
+    c = dev(dict(prm=np.tile(_lib.LMPC_PRM_DEFAULT, (B, 1)), current_k=pol.current_k, weights=pol.weights,
+                 critic=pol.critic_weights, noise=harness.lmpc_noise(0, steps, B)))
+    dpool = dev(pool)
+    dev_loops = {"rollout": [], "collect": []}
+
+    def dev_run(name):
+        st, lg = dev(s.loop_state(D["state"], policy=pol)), dev(_lib.loop_logs(_lib.LMPC_LOOP_LOGS, steps, B))
+        tp = dev(dict(target=D["target"], pvec=D["pvec"]))
+        cs = dev(s.collect_state(np.zeros((B, 2))))
+        clg, rec = dev(_lib.loop_logs(_lib.LMPC_COLLECT_LOGS, steps, B)), dev(_lib.loop_logs(_lib.LMPC_COLLECT_REC, rec_rows, B))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if name == "rollout":
+            s.rollout_dev(B, 0, steps, steps, tp["target"].data_ptr(), c["prm"].data_ptr(), tp["pvec"].data_ptr(), ptr(st),
+                          ptr(lg), pcfg=pol.cfg, weights=c["weights"].data_ptr(), current_k=c["current_k"].data_ptr(),
+                          noise=c["noise"].data_ptr())
+        else:
+            s.collect_dev(B, 0, steps, steps, rec_rows, 4, tp["target"].data_ptr(), c["prm"].data_ptr(),
+                          tp["pvec"].data_ptr(), ptr(st), ptr(cs), ptr(lg), ptr(clg), ptr(rec), pol.cfg, ck["rcfg"],
+                          c["weights"].data_ptr(), c["critic"].data_ptr(), c["current_k"].data_ptr(),
+                          noise=c["noise"].data_ptr(), pool=ptr(dpool))
+        s.sync()
+        return time.perf_counter() - t0
+    try:
+        dev_run("rollout"); dev_run("collect")
+        for _ in range(5):
+            for name in ("rollout", "collect"):
+                dev_loops[name].append(dev_run(name))
+    finally:
+        s.close()
+    dmed = {k: float(np.median(v)) for k, v in dev_loops.items()}
+
+    def resident(name):
+        return dict(rate(B, steps, float(np.median(walls[name]))), loop_only_s=float(np.median(loops[name])),
+                    loop_only_min_s=float(np.min(loops[name])), loop_only_max_s=float(np.max(loops[name])), rounds=5)
+
+    def chain(st, it):
+        return {"mean_iters": float(it.mean()), "max_iters": int(it.max()), "n_status_nonzero": int(np.sum(st != 0)),
+                "share_status_nonzero": float(np.mean(st != 0)),
+                "tail_share_steps_over_20_iters": float(np.mean(it.max(axis=1) > 20))}
+
+    def after_reset(st, it, done):
+        m = np.zeros(st.shape, bool); m[1:] = done[:-1] != 0
+        if not m.any():
+            return {"n": 0}
+        return {"n": int(m.sum()), "mean_iters": float(it[m].mean()), "max_iters": int(it[m].max()),
+                "n_status_nonzero": int(np.sum(st[m] != 0)), "n_status_minus2": int(np.sum(st[m] == -2))}
+    return {"controller": "COLLECT", "B": B, "N": 30, "steps": steps, "max_episode_steps": ep,
+            "episodes": int(E["episodes"].sum()), "records": int(E["nrec"].sum()),
+            "host_collect_loop": dict(rate(B, steps, t_host), **chain(st_h, Xh["iters"])),
+            "rollout_no_experience": resident("rollout"),
+            "collect": dict(resident("collect"), **chain(st_d, X["iters"])),
+            "collect_after_reset": after_reset(st_d, X["iters"], E["done"]),
+            "collect_restoration_off_after_reset": after_reset(st_o, Xo["iters"], Eo["done"]),
+            "handed_to_restoration_after_reset": after_reset(st_o, Xo["iters"], Eo["done"]).get("n_status_minus2", 0),
+            "collect_over_rollout_loop_only": float(np.median(loops["collect"]) / np.median(loops["rollout"])),
+            "experience_cost_us_per_step": float((np.median(loops["collect"]) - np.median(loops["rollout"])) / steps * 1e6),
+            "device_entries": {"rollout_dev_s": dmed["rollout"], "collect_dev_s": dmed["collect"],
+                               "rollout_dev_min_s": float(np.min(dev_loops["rollout"])),
+                               "collect_dev_min_s": float(np.min(dev_loops["collect"])), "rounds": 5,
+                               "collect_over_rollout": dmed["collect"] / dmed["rollout"],
+                               "experience_cost_us_per_step": (dmed["collect"] - dmed["rollout"]) / steps * 1e6},
+            "speedup_over_host_loop": t_host / float(np.median(walls["collect"]))}
+
+
+ROWS = {"PMPC": pmpc_row, "RMPC": rmpc_row, "LMPC": lmpc_row, "COLLECT": collect_row}
 results = []
 if os.path.exists(out_path):        # the rows of the controllers that this run leaves out
     with open(out_path) as f:
