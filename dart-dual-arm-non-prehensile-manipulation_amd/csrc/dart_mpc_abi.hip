@@ -21,6 +21,7 @@
 #include "lmpc_ipm.h"
 #include "lmpc_policy.h"
 #include "lmpc_experience.h"
+#include "lmpc_ppo.h"
 #include "arm_qp.h"
 #include "loop_step.h"
 
@@ -2055,6 +2056,260 @@ int dart_lmpc_gae(int B, int rec_rows, double gamma, double lam, const int32_t* 
     a.adv = S.inout(adv, n); a.ret = S.inout(ret, n);      // (rows >= nrec[b] keep the caller's contents)
     hipError_t e = S.upload(D->stream);
     if (e == hipSuccess) e = dartmpc_launch_lmpc_gae(&a, D->stream);
+    if (e == hipSuccess) e = S.download_inout(D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.finish_inout();
+    return DART_MPC_OK;
+}
+
+// ---- PPO update of the LMPC policy (lmpc_ppo.hip) ----------------------------------------------------------
+
+void dart_lmpc_ppo_config_default(dart_lmpc_ppo_config* c) {
+    if (!c) return;
+    c->clip_eps = 0.2; c->vf_coef = 0.25; c->ent_coef = 0.01; c->max_grad_norm = 0.5;
+    c->lr = 3e-4; c->beta1 = 0.9; c->beta2 = 0.999; c->adam_eps = 1e-8; c->weight_decay = 1e-5;
+    c->log_std_min = std::log(1e-2); c->log_std_max = std::log(2.0);
+    c->epochs = 8; c->mini_batch_size = 64;
+}
+
+size_t dart_lmpc_ppo_workspace_bytes(int n, int mini_batch_size) {
+    if (n < 1 || mini_batch_size < 1 || mini_batch_size > dartmpc::kPpoMaxBatch) return 0;
+    return dartmpc::ppo_workspace(n, mini_batch_size).bytes;
+}
+
+namespace {
+
+bool ppo_cfg_ok(const dart_lmpc_ppo_config* c) {
+    return c && c->mini_batch_size >= 1 && c->mini_batch_size <= dartmpc::kPpoMaxBatch && c->epochs >= 0 &&
+           c->clip_eps >= 0.0 && c->lr >= 0.0 && c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 &&
+           c->beta2 < 1.0 && c->adam_eps >= 0.0 && c->max_grad_norm >= 0.0 && c->log_std_min <= c->log_std_max;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// the launches of the PPO entries; ws is laid out for (n, mb) with M <= mb
+hipError_t ppo_launch_prepare(int n, long long total, const int32_t* sample, const double* adv, const double* ret,
+                              float* adv_out, float* ret_out, char* ws, int mb, hipStream_t s) {
+    const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
+    dartmpc::PpoPrepareArgs a;
+    a.n = n; a.rec_total = total; a.sample = sample; a.adv = adv; a.ret = ret;
+    a.adv_n = reinterpret_cast<float*>(ws + L.adv_n); a.ret_n = reinterpret_cast<float*>(ws + L.ret_n);
+    a.adv_out = adv_out; a.ret_out = ret_out;
+    return dartmpc_launch_ppo_prepare(&a, s);
+}
+
+hipError_t ppo_launch_grad(const dart_lmpc_ppo_config* c, int n, long long total, int M, const int32_t* sample,
+                           const int32_t* idx, const float* rec_obs, const float* rec_action, const float* rec_logp,
+                           const float* weights, const float* critic, char* ws, int mb, hipStream_t s) {
+    const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
+    dartmpc::PpoGradArgs a;
+    a.n = n; a.M = M; a.rec_total = total;
+    a.clip_lo = (float)(1.0 - c->clip_eps); a.clip_hi = (float)(1.0 + c->clip_eps);
+    a.vf_coef = (float)c->vf_coef; a.ent_coef = (float)c->ent_coef;
+    a.log_std_min = (float)c->log_std_min; a.log_std_max = (float)c->log_std_max;
+    a.sample = sample; a.idx = idx; a.rec_obs = rec_obs; a.rec_action = rec_action; a.rec_logp = rec_logp;
+    a.adv_n = reinterpret_cast<const float*>(ws + L.adv_n); a.ret_n = reinterpret_cast<const float*>(ws + L.ret_n);
+    a.actor = weights; a.critic = critic;
+    a.part = reinterpret_cast<float*>(ws + L.part); a.loss_part = reinterpret_cast<float*>(ws + L.loss_part);
+    return dartmpc_launch_ppo_grad(&a, s);
+}
+
+// from_tiles: sum the workspace's partials of a mini-batch of M; otherwise take the packed gradient `grad`
+hipError_t ppo_launch_apply(const dart_lmpc_ppo_config* c, int n, int M, bool from_tiles, const float* grad,
+                            const float* terms_in, bool do_step, float* grad_out, float* terms_out, float* weights,
+                            float* critic, float* adam, int32_t* adam_step, double* stats, float* step_log,
+                            int step_in_call, char* ws, int mb, hipStream_t s) {
+    const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
+    dartmpc::PpoApplyArgs a;
+    a.tiles = from_tiles ? (M + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile : 1;
+    a.M = M; a.do_step = do_step ? 1 : 0; a.step_in_call = step_in_call;
+    a.max_grad_norm = (float)c->max_grad_norm; a.lr = c->lr; a.beta1 = c->beta1;
+    a.beta2 = c->beta2; a.adam_eps = (float)c->adam_eps; a.weight_decay = (float)c->weight_decay;
+    a.ent_coef = (float)c->ent_coef; a.log_std_min = (float)c->log_std_min; a.log_std_max = (float)c->log_std_max;
+    a.part = from_tiles ? reinterpret_cast<const float*>(ws + L.part) : grad;
+    a.loss_part = from_tiles ? reinterpret_cast<const float*>(ws + L.loss_part) : nullptr;
+    a.terms_in = terms_in;
+    a.grad = grad_out ? grad_out : reinterpret_cast<float*>(ws + L.grad);
+    a.terms = terms_out ? terms_out : reinterpret_cast<float*>(ws + L.terms);
+    a.actor = weights; a.critic = critic; a.adam = adam; a.adam_step = adam_step;
+    a.step_log = step_log; a.stat_sum = reinterpret_cast<double*>(ws + L.stat_sum); a.stats = stats;
+    return dartmpc_launch_ppo_apply(&a, s);
+}
+
+}  // namespace
+
+int dart_lmpc_ppo_prepare_dev(int n, int rec_total, const int32_t* sample, const double* adv, const double* ret,
+                              float* adv_norm_out, float* ret_norm_out, void* workspace, void* stream) {
+    if (n < 1 || rec_total < 1 || !sample || !adv || !ret || !workspace) return DART_MPC_EINVAL;
+    return ppo_launch_prepare(n, rec_total, sample, adv, ret, adv_norm_out, ret_norm_out, (char*)workspace, 1,
+                              (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_ppo_grad_dev(const dart_lmpc_ppo_config* cfg, int n, int rec_total, int M, const int32_t* sample,
+                           const int32_t* idx, const float* rec_obs, const float* rec_action, const float* rec_logp,
+                           const float* weights, const float* critic, float* grad_out, float* terms_out,
+                           void* workspace, void* stream) {
+    if (!ppo_cfg_ok(cfg) || n < 1 || rec_total < 1 || M < 1 || M > dartmpc::kPpoMaxBatch) return DART_MPC_EINVAL;
+    if (!sample || !idx || !rec_obs || !rec_action || !rec_logp || !weights || !critic || !grad_out || !terms_out ||
+        !workspace) return DART_MPC_EINVAL;
+    if (!aligned16(weights) || !aligned16(critic)) return DART_MPC_EINVAL;
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = ppo_launch_grad(cfg, n, rec_total, M, sample, idx, rec_obs, rec_action, rec_logp, weights, critic,
+                                   ws, M, s);
+    if (e == hipSuccess)
+        e = ppo_launch_apply(cfg, n, M, true, nullptr, nullptr, false, grad_out, terms_out, const_cast<float*>(weights),
+                             const_cast<float*>(critic), nullptr, nullptr, nullptr, nullptr, 0, ws, M, s);
+    return e == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_ppo_apply_dev(const dart_lmpc_ppo_config* cfg, const float* grad, const float* terms, float* weights,
+                            float* critic, float* adam, int32_t* adam_step, double* stats, float* step_log,
+                            int step_in_call, void* workspace, void* stream) {
+    if (!ppo_cfg_ok(cfg) || !grad || !weights || !critic || !adam || !adam_step || !workspace || step_in_call < 0)
+        return DART_MPC_EINVAL;
+    if (!aligned16(weights) || !aligned16(critic)) return DART_MPC_EINVAL;
+    // (the blocks this launch uses lie at fixed offsets in front of the workspace: the layout of any n serves)
+    return ppo_launch_apply(cfg, 1, 1, false, grad, terms, true, nullptr, nullptr, weights, critic, adam, adam_step,
+                            stats, step_log, step_in_call, (char*)workspace, 1, (hipStream_t)stream) == hipSuccess
+               ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+namespace {
+
+int ppo_update_check(const dart_lmpc_ppo_config* cfg, int n, int rec_total, const void* sample, const void* perm,
+                     const void* rec_obs, const void* rec_action, const void* rec_logp, const void* adv,
+                     const void* ret, const void* weights, const void* critic, const void* adam,
+                     const void* adam_step, const void* stats) {
+    if (!ppo_cfg_ok(cfg) || n < 1 || rec_total < 1) return DART_MPC_EINVAL;
+    if (!sample || (!perm && cfg->epochs > 0) || !rec_obs || !rec_action || !rec_logp || !adv || !ret || !weights ||
+        !critic || !adam || !adam_step || !stats) return DART_MPC_EINVAL;
+    if (!aligned16(weights) || !aligned16(critic)) return DART_MPC_EINVAL;
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_ppo_update_dev(const dart_lmpc_ppo_config* cfg, int n, int rec_total, const int32_t* sample,
+                             const int32_t* perm, const float* rec_obs, const float* rec_action,
+                             const float* rec_logp, const double* adv, const double* ret, float* weights,
+                             float* critic, float* adam, int32_t* adam_step, double* stats, float* step_log,
+                             float* adv_norm_out, float* ret_norm_out, void* workspace, void* stream) {
+    if (int rc = ppo_update_check(cfg, n, rec_total, sample, perm, rec_obs, rec_action, rec_logp, adv, ret, weights,
+                                  critic, adam, adam_step, stats)) return rc;
+    if (!workspace) return DART_MPC_EINVAL;
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const int mb = cfg->mini_batch_size;
+    hipError_t e = ppo_launch_prepare(n, rec_total, sample, adv, ret, adv_norm_out, ret_norm_out, ws, mb, s);
+    int step = 0;
+    for (int ep = 0; ep < cfg->epochs && e == hipSuccess; ++ep) {
+        const int32_t* row = perm + (size_t)ep * n;
+        for (int start = 0; start < n && e == hipSuccess; start += mb, ++step) {
+            const int M = n - start < mb ? n - start : mb;
+            e = ppo_launch_grad(cfg, n, rec_total, M, sample, row + start, rec_obs, rec_action, rec_logp, weights,
+                                critic, ws, mb, s);
+            if (e == hipSuccess)
+                e = ppo_launch_apply(cfg, n, M, true, nullptr, nullptr, true, nullptr, nullptr, weights, critic, adam,
+                                     adam_step, stats, step_log, step, ws, mb, s);
+        }
+    }
+    return e == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_ppo_update(const dart_lmpc_ppo_config* cfg, int n, int rec_total, const int32_t* sample,
+                         const int32_t* perm, const float* rec_obs, const float* rec_action, const float* rec_logp,
+                         const double* adv, const double* ret, float* weights, float* critic, float* adam,
+                         int32_t* adam_step, double* stats, float* step_log, float* adv_norm_out,
+                         float* ret_norm_out) {
+    if (int rc = ppo_update_check(cfg, n, rec_total, sample, perm, rec_obs, rec_action, rec_logp, adv, ret, weights,
+                                  critic, adam, adam_step, stats)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (sample[i] < 0 || sample[i] >= rec_total) return DART_MPC_EINVAL;
+    const size_t np = (size_t)cfg->epochs * n;
+    for (size_t i = 0; i < np; ++i)
+        if (perm[i] < 0 || perm[i] >= n) return DART_MPC_EINVAL;
+    if (cfg->epochs == 0) { stats[0] = stats[1] = stats[2] = 0.0; }
+    // only the rows sample names travel: they are compacted on the way up (the device entry gathers through
+    // sample, so it is handed the identity) -- rows past an instance's record count are never read
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    const size_t N = (size_t)n, P = dartmpc::kPpoParams;
+    const size_t steps = (size_t)cfg->epochs * ((N + cfg->mini_batch_size - 1) / cfg->mini_batch_size);
+    const size_t ws_bytes = dartmpc::ppo_workspace(n, cfg->mini_batch_size).bytes;
+    const size_t staged = sizeof(int32_t) * (N + np + 1) + sizeof(float) * (N * (520 + 34 + 1) + 3 * P + 4 * steps + 2 * N) +
+                          sizeof(double) * (2 * N + 3) + 20 * 256;
+    if (S.reserve(staged + ws_bytes, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    auto gather = [&](auto* dst, const auto* src, size_t width) {
+        for (size_t i = 0; i < N; ++i) std::memcpy(dst + i * width, src + (size_t)sample[i] * width, sizeof(*dst) * width);
+    };
+    // (HostStage::in copies from a contiguous source: reserve the slots by hand for the gathered arrays)
+    auto slot = [&](size_t bytes) { char* p = S.hin + S.in_off; S.in_off += HostStage::al(bytes); return p; };
+    auto dev_of = [&](const void* h) { return S.din + ((const char*)h - S.hin); };
+    int32_t* h_id = (int32_t*)slot(sizeof(int32_t) * N);
+    for (int i = 0; i < n; ++i) h_id[i] = i;
+    float* h_obs = (float*)slot(sizeof(float) * N * 520); gather(h_obs, rec_obs, 520);
+    float* h_act = (float*)slot(sizeof(float) * N * 34); gather(h_act, rec_action, 34);
+    float* h_lp = (float*)slot(sizeof(float) * N); gather(h_lp, rec_logp, 1);
+    double* h_adv = (double*)slot(sizeof(double) * N); gather(h_adv, adv, 1);
+    double* h_ret = (double*)slot(sizeof(double) * N); gather(h_ret, ret, 1);
+    const int32_t* d_perm = S.in(perm, np);
+    float* d_w = S.inout(weights, (size_t)dartmpc::kPpoActorN);
+    float* d_c = S.inout(critic, (size_t)dartmpc::kPpoCriticN);
+    float* d_adam = S.inout(adam, 2 * P);
+    int32_t* d_step = S.inout(adam_step, (size_t)1);
+    double* d_stats = S.inout(stats, (size_t)3);
+    float* d_log = S.inout(step_log, 4 * steps);
+    float* d_an = S.inout(adv_norm_out, N);
+    float* d_rn = S.inout(ret_norm_out, N);
+    char* ws = S.din + S.in_off;
+    hipError_t e = S.upload(D->stream);
+    int rc = DART_MPC_OK;
+    if (e == hipSuccess)
+        rc = dart_lmpc_ppo_update_dev(cfg, n, n, (const int32_t*)dev_of(h_id), d_perm, (const float*)dev_of(h_obs),
+                                      (const float*)dev_of(h_act), (const float*)dev_of(h_lp),
+                                      (const double*)dev_of(h_adv), (const double*)dev_of(h_ret), d_w, d_c, d_adam,
+                                      d_step, d_stats, d_log, d_an, d_rn, ws, D->stream);
+    if (rc != DART_MPC_OK) {
+        (void)hipStreamSynchronize(D->stream);
+        return rc;
+    }
+    if (e == hipSuccess) e = S.download_inout(D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.finish_inout();
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_critic_value_dev(int n, const float* critic, const float* obs, float* value_out, void* stream) {
+    if (n < 0) return DART_MPC_EINVAL;
+    if (n == 0) return DART_MPC_OK;
+    if (!critic || !obs || !value_out) return DART_MPC_EINVAL;
+    dartmpc::CriticValueArgs a;
+    a.n = n; a.critic = critic; a.obs = obs; a.value = value_out;
+    return dartmpc_launch_critic_value(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_critic_value(int n, const float* critic, const float* obs, float* value_out) {
+    if (n < 0) return DART_MPC_EINVAL;
+    if (n == 0) return DART_MPC_OK;
+    if (!critic || !obs || !value_out) return DART_MPC_EINVAL;
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    const size_t N = (size_t)n;
+    if (S.reserve(sizeof(float) * (N * 520 + dartmpc::kPpoCriticN + N) + 4 * 256, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    dartmpc::CriticValueArgs a;
+    a.n = n; a.critic = S.in(critic, (size_t)dartmpc::kPpoCriticN); a.obs = S.in(obs, N * 520);
+    a.value = S.inout(value_out, N);
+    hipError_t e = S.upload(D->stream);
+    if (e == hipSuccess) e = dartmpc_launch_critic_value(&a, D->stream);
     if (e == hipSuccess) e = S.download_inout(D->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
     if (e != hipSuccess) return DART_MPC_EHIP;

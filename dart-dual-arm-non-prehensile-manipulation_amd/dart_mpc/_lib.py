@@ -45,7 +45,10 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_pmpc_loop_step_dev", "dart_rmpc_rollout_dev", "dart_pmpc_rollout_dev", "dart_rmpc_rollout",
            "dart_pmpc_rollout", "dart_lmpc_loop_step_dev", "dart_lmpc_rollout_dev", "dart_lmpc_rollout",
            "dart_lmpc_reward_config_default", "dart_lmpc_experience_step_dev", "dart_lmpc_collect_dev",
-           "dart_lmpc_collect", "dart_lmpc_gae_dev", "dart_lmpc_gae")
+           "dart_lmpc_collect", "dart_lmpc_gae_dev", "dart_lmpc_gae",
+           "dart_lmpc_ppo_config_default", "dart_lmpc_ppo_workspace_bytes", "dart_lmpc_ppo_update_dev",
+           "dart_lmpc_ppo_update", "dart_lmpc_ppo_prepare_dev", "dart_lmpc_ppo_grad_dev", "dart_lmpc_ppo_apply_dev",
+           "dart_lmpc_critic_value_dev", "dart_lmpc_critic_value")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -85,6 +88,15 @@ class RewardConfig(ctypes.Structure):
                 ("record_every", ctypes.c_int32), ("done_sticky", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class PpoConfig(ctypes.Structure):
+    """Mirror of ``struct dart_lmpc_ppo_config`` (the hyper-parameters of the PPO update on the device)."""
+    _fields_ = [("clip_eps", ctypes.c_double), ("vf_coef", ctypes.c_double), ("ent_coef", ctypes.c_double),
+                ("max_grad_norm", ctypes.c_double), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("adam_eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("log_std_min", ctypes.c_double), ("log_std_max", ctypes.c_double), ("epochs", ctypes.c_int32),
+                ("mini_batch_size", ctypes.c_int32)]
+
+
 # Arrays of the closed-loop rollouts in the argument order of include/dart_mpc.h: (name, row width, dtype);
 # width 0 = one scalar per instance, "nw" = the solver's w.  State arrays are [B, width], logs [rows, B, width].
 RMPC_LOOP_STATE = (("x", 6, np.float64), ("tilt", 2, np.float64), ("prev", 4, np.float64), ("u_prev", 2, np.float64),
@@ -119,6 +131,8 @@ LMPC_COLLECT_REC = (("rec_obs", 520, np.float32), ("rec_action", 34, np.float32)
                     ("rec_value", 0, np.float32), ("rec_reward", 0, np.float64), ("rec_done", 0, np.float32))
 DONE_OOB, DONE_MAX_STEPS = 1, 2                 # bits of the done log
 CRITIC_NWEIGHTS = 520 * 64 + 64 + 64 * 64 + 64 + 64 + 1
+ACTOR_NWEIGHTS = 520 * 64 + 64 + 64 * 64 + 64 + 64 * 34 + 34 + 34
+PPO_NPARAMS = ACTOR_NWEIGHTS + CRITIC_NWEIGHTS  # 77317: the actor, then the critic, in the packed order
 LOG_INT_FILL = int(np.iinfo(np.int32).min)      # prefill of the int32 logs (the float logs are prefilled with NaN)
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -281,6 +295,23 @@ def lib():
         L.dart_lmpc_gae_dev.restype = ctypes.c_int
         L.dart_lmpc_gae.argtypes = [ci, ci, cd, cd] + [vp] * 7
         L.dart_lmpc_gae.restype = ctypes.c_int
+    if hasattr(L, "dart_lmpc_ppo_update_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_lmpc_ppo_config_default.argtypes = [ctypes.POINTER(PpoConfig)]
+        L.dart_lmpc_ppo_config_default.restype = None
+        L.dart_lmpc_ppo_workspace_bytes.argtypes = [ci, ci]
+        L.dart_lmpc_ppo_workspace_bytes.restype = ctypes.c_size_t
+        L.dart_lmpc_ppo_update_dev.argtypes = [vp, ci, ci] + [vp] * 17
+        L.dart_lmpc_ppo_update.argtypes = [vp, ci, ci] + [vp] * 15
+        L.dart_lmpc_ppo_prepare_dev.argtypes = [ci, ci] + [vp] * 7
+        L.dart_lmpc_ppo_grad_dev.argtypes = [vp, ci, ci, ci] + [vp] * 11
+        L.dart_lmpc_ppo_apply_dev.argtypes = [vp] * 9 + [ci, vp, vp]
+        L.dart_lmpc_critic_value_dev.argtypes = [ci, vp, vp, vp, vp]
+        L.dart_lmpc_critic_value.argtypes = [ci, vp, vp, vp]
+        for fn in (L.dart_lmpc_ppo_update_dev, L.dart_lmpc_ppo_update, L.dart_lmpc_ppo_prepare_dev,
+                   L.dart_lmpc_ppo_grad_dev, L.dart_lmpc_ppo_apply_dev, L.dart_lmpc_critic_value_dev,
+                   L.dart_lmpc_critic_value):
+            fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
         L.dart_mpc_bind.restype = ctypes.c_int
@@ -986,6 +1017,176 @@ def gae(nrec, rec_reward, rec_value, rec_done, last_value, gamma=0.99, lam=0.95,
     if rc != 0:
         raise DartMPCError(f"dart_lmpc_gae failed ({rc})")
     return adv, ret
+
+
+def ppo_config(**over) -> PpoConfig:
+    """``dart_lmpc_ppo_config`` with the library's defaults (the reference's, rlmpc2.py:202-226, 561), fields
+    overridden by keyword."""
+    c = PpoConfig()
+    lib().dart_lmpc_ppo_config_default(ctypes.byref(c))
+    names = [f[0] for f in c._fields_]
+    for k, v in over.items():
+        if k not in names:
+            raise DartMPCError(f"PpoConfig has no field {k!r} (fields: {names})")
+        setattr(c, k, int(v) if k in ("epochs", "mini_batch_size") else float(v))
+    return c
+
+
+def ppo_workspace_bytes(n, mini_batch_size):
+    """Bytes of the device workspace of the PPO entries for ``n`` samples and mini-batches of up to
+    ``mini_batch_size``."""
+    b = int(lib().dart_lmpc_ppo_workspace_bytes(int(n), int(mini_batch_size)))
+    if b == 0:
+        raise DartMPCError(f"no PPO workspace for n = {n}, mini_batch_size = {mini_batch_size} (n >= 1, 1 .. 1024)")
+    return b
+
+
+def _vp(v):
+    return ctypes.c_void_p(int(v)) if v else None
+
+
+def _rc(rc, what):
+    if rc != 0:
+        raise DartMPCError(f"{what} failed ({rc}: {'invalid argument' if rc == -1 else 'HIP error'})")
+
+
+def ppo_update_dev(cfg, n, rec_total, sample, perm, rec_obs, rec_action, rec_logp, adv, ret, weights, critic, adam,
+                   adam_step, stats, workspace, step_log=0, adv_norm_out=0, ret_norm_out=0, stream=0):
+    """dart_lmpc_ppo_update_dev: the whole update on device pointers (ints), asynchronous.  ``perm`` holds
+    ``cfg.epochs`` rows of n; weights, critic, adam and adam_step are updated in place."""
+    _rc(lib().dart_lmpc_ppo_update_dev(
+        ctypes.byref(cfg), int(n), int(rec_total), _vp(sample), _vp(perm), _vp(rec_obs), _vp(rec_action),
+        _vp(rec_logp), _vp(adv), _vp(ret), _vp(weights), _vp(critic), _vp(adam), _vp(adam_step), _vp(stats),
+        _vp(step_log), _vp(adv_norm_out), _vp(ret_norm_out), _vp(workspace), stream or None),
+        "dart_lmpc_ppo_update_dev")
+
+
+def ppo_prepare_dev(n, rec_total, sample, adv, ret, workspace, adv_norm_out=0, ret_norm_out=0, stream=0):
+    """dart_lmpc_ppo_prepare_dev: the normalised returns and advantages into the workspace (device pointers)."""
+    _rc(lib().dart_lmpc_ppo_prepare_dev(int(n), int(rec_total), _vp(sample), _vp(adv), _vp(ret), _vp(adv_norm_out),
+                                        _vp(ret_norm_out), _vp(workspace), stream or None),
+        "dart_lmpc_ppo_prepare_dev")
+
+
+def ppo_grad_dev(cfg, n, rec_total, M, sample, idx, rec_obs, rec_action, rec_logp, weights, critic, grad_out,
+                 terms_out, workspace, stream=0):
+    """dart_lmpc_ppo_grad_dev: the gradient of one mini-batch ``idx`` [M] (after ``ppo_prepare_dev`` on the same
+    workspace) into ``grad_out`` [77317] and ``terms_out`` [4] (device pointers)."""
+    _rc(lib().dart_lmpc_ppo_grad_dev(
+        ctypes.byref(cfg), int(n), int(rec_total), int(M), _vp(sample), _vp(idx), _vp(rec_obs), _vp(rec_action),
+        _vp(rec_logp), _vp(weights), _vp(critic), _vp(grad_out), _vp(terms_out), _vp(workspace), stream or None),
+        "dart_lmpc_ppo_grad_dev")
+
+
+def ppo_apply_dev(cfg, grad, weights, critic, adam, adam_step, workspace, terms=0, stats=0, step_log=0, step_in_call=0,
+                  stream=0):
+    """dart_lmpc_ppo_apply_dev: clip + Adam step of a packed gradient, in place (device pointers)."""
+    _rc(lib().dart_lmpc_ppo_apply_dev(
+        ctypes.byref(cfg), _vp(grad), _vp(terms), _vp(weights), _vp(critic), _vp(adam), _vp(adam_step), _vp(stats),
+        _vp(step_log), int(step_in_call), _vp(workspace), stream or None), "dart_lmpc_ppo_apply_dev")
+
+
+def _ppo_records(sample, rec_obs, rec_action, rec_logp, adv, ret):
+    c = lambda a, dt: np.ascontiguousarray(a, dt)
+    rec_logp = c(rec_logp, np.float32).reshape(-1)
+    total = rec_logp.size
+    return (c(sample, np.int32).reshape(-1), c(rec_obs, np.float32).reshape(total, 520),
+            c(rec_action, np.float32).reshape(total, 34), rec_logp, c(adv, np.float64).reshape(total),
+            c(ret, np.float64).reshape(total), total)
+
+
+def _inplace(a, dt, size, name):
+    if not isinstance(a, np.ndarray) or a.dtype != dt or a.size != size or not a.flags.c_contiguous:
+        raise DartMPCError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of {size} entries (updated in place)")
+    return a
+
+
+def ppo_update(cfg, sample, perm, rec_obs, rec_action, rec_logp, adv, ret, weights, critic, adam, adam_step):
+    """The whole PPO update on host arrays (dart_lmpc_ppo_update, blocking).  The record arrays [rec_total, ..],
+    ``adv`` and ``ret`` (float64 [rec_total]) are indexed through ``sample`` [n]; ``perm`` is [cfg.epochs, n].
+    ``weights`` [39748], ``critic`` [37569], ``adam`` [2, 77317] (float32) and ``adam_step`` [1] (int32) are updated
+    in place.  Returns dict(policy_loss, value_loss, entropy, step_log [steps, 4], adv_norm [n], ret_norm [n])."""
+    sample, ro, ra, rl, adv, ret, total = _ppo_records(sample, rec_obs, rec_action, rec_logp, adv, ret)
+    n = sample.size
+    perm = np.ascontiguousarray(perm, np.int32).reshape(-1)
+    if perm.size != int(cfg.epochs) * n:
+        raise DartMPCError(f"perm must hold cfg.epochs = {cfg.epochs} rows of n = {n} entries")
+    _inplace(weights, np.float32, ACTOR_NWEIGHTS, "weights"); _inplace(critic, np.float32, CRITIC_NWEIGHTS, "critic")
+    _inplace(adam, np.float32, 2 * PPO_NPARAMS, "adam"); _inplace(adam_step, np.int32, 1, "adam_step")
+    mb = max(int(cfg.mini_batch_size), 1)
+    steps = int(cfg.epochs) * (-(-n // mb))
+    stats, log = np.zeros(3), np.full((steps, 4), np.nan, np.float32)
+    an, rn = np.full(n, np.nan, np.float32), np.full(n, np.nan, np.float32)
+    _rc(lib().dart_lmpc_ppo_update(ctypes.byref(cfg), n, total, _ptr(sample), _ptr(perm), _ptr(ro), _ptr(ra), _ptr(rl),
+                                   _ptr(adv), _ptr(ret), _ptr(weights), _ptr(critic), _ptr(adam), _ptr(adam_step),
+                                   _ptr(stats), _ptr(log), _ptr(an), _ptr(rn)), "dart_lmpc_ppo_update")
+    return dict(policy_loss=float(stats[0]), value_loss=float(stats[1]), entropy=float(stats[2]), step_log=log,
+                adv_norm=an, ret_norm=rn)
+
+
+def _torch_dev(*arrays):
+    """Device copies (torch tensors: the package's device-memory plumbing) of numpy arrays."""
+    import torch
+    return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
+def ppo_grad(cfg, sample, idx, rec_obs, rec_action, rec_logp, adv, ret, weights, critic):
+    """The gradient of one mini-batch on host arrays (blocking): ``ppo_prepare_dev`` over the n samples, then
+    ``ppo_grad_dev`` on ``idx`` [M] (positions in ``sample``).  Returns (grad float32 [77317] in the packed order,
+    terms float32 [4]: policy loss, value loss, entropy, gradient norm)."""
+    import torch
+    sample, ro, ra, rl, adv, ret, total = _ppo_records(sample, rec_obs, rec_action, rec_logp, adv, ret)
+    idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+    n, M = sample.size, idx.size
+    d = _torch_dev(sample, idx, ro, ra, rl, adv, ret, np.ascontiguousarray(weights, np.float32),
+                   np.ascontiguousarray(critic, np.float32))
+    ws = torch.zeros(ppo_workspace_bytes(n, M), dtype=torch.uint8, device="cuda")
+    grad = torch.empty(PPO_NPARAMS, dtype=torch.float32, device="cuda")
+    terms = torch.empty(4, dtype=torch.float32, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    p = [t.data_ptr() for t in d]
+    ppo_prepare_dev(n, total, p[0], p[5], p[6], ws.data_ptr(), stream=s)
+    ppo_grad_dev(cfg, n, total, M, p[0], p[1], p[2], p[3], p[4], p[7], p[8], grad.data_ptr(), terms.data_ptr(),
+                 ws.data_ptr(), stream=s)
+    torch.cuda.synchronize()
+    return grad.cpu().numpy(), terms.cpu().numpy()
+
+
+def ppo_apply(cfg, grad, weights, critic, adam, adam_step, terms=None):
+    """One clip + Adam step of a packed gradient on host arrays (blocking); ``weights``, ``critic``, ``adam`` and
+    ``adam_step`` are updated in place.  Returns the logged row (policy loss, value loss, entropy as given in
+    ``terms``, gradient norm before the clip)."""
+    import torch
+    _inplace(weights, np.float32, ACTOR_NWEIGHTS, "weights"); _inplace(critic, np.float32, CRITIC_NWEIGHTS, "critic")
+    _inplace(adam, np.float32, 2 * PPO_NPARAMS, "adam"); _inplace(adam_step, np.int32, 1, "adam_step")
+    g = np.ascontiguousarray(grad, np.float32).reshape(PPO_NPARAMS)
+    t = np.zeros(3, np.float32) if terms is None else np.ascontiguousarray(terms, np.float32).reshape(-1)[:3].copy()
+    dg, dt, dw, dc, da, ds = _torch_dev(g, t, weights, critic, adam, adam_step)
+    ws = torch.zeros(ppo_workspace_bytes(1, 1), dtype=torch.uint8, device="cuda")
+    log = torch.empty(4, dtype=torch.float32, device="cuda")
+    ppo_apply_dev(cfg, dg.data_ptr(), dw.data_ptr(), dc.data_ptr(), da.data_ptr(), ds.data_ptr(), ws.data_ptr(),
+                  terms=dt.data_ptr(), step_log=log.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    weights[...] = dw.cpu().numpy().reshape(weights.shape); critic[...] = dc.cpu().numpy().reshape(critic.shape)
+    adam[...] = da.cpu().numpy().reshape(adam.shape); adam_step[...] = ds.cpu().numpy().reshape(adam_step.shape)
+    return log.cpu().numpy()
+
+
+def critic_value_dev(n, critic, obs, value_out, stream=0):
+    """dart_lmpc_critic_value_dev: value_net on obs [n, 520] into value_out [n] (device pointers)."""
+    _rc(lib().dart_lmpc_critic_value_dev(int(n), _vp(critic), _vp(obs), _vp(value_out), stream or None),
+        "dart_lmpc_critic_value_dev")
+
+
+def critic_value(critic, obs):
+    """value_net (Policy :48-55) on obs [n, 520] on the GPU (dart_lmpc_critic_value, blocking): float32 [n]."""
+    cw = np.ascontiguousarray(critic, np.float32).reshape(-1)
+    if cw.size != CRITIC_NWEIGHTS:
+        raise DartMPCError(f"critic weights have {cw.size} floats, not {CRITIC_NWEIGHTS}")
+    ob = np.ascontiguousarray(obs, np.float32).reshape(-1, 520)
+    out = np.empty(ob.shape[0], np.float32)
+    _rc(lib().dart_lmpc_critic_value(ob.shape[0], _ptr(cw), _ptr(ob), _ptr(out)), "dart_lmpc_critic_value")
+    return out
 
 
 def rls_update_batch(theta, P, phi, y, lam=0.995):

@@ -648,6 +648,97 @@ int dart_lmpc_gae(int B, int rec_rows, double gamma, double lam, const int32_t *
                   const double *rec_reward, const float *rec_value, const float *rec_done,
                   const float *last_value, double *adv, double *ret);
 
+/* PPO update of the LMPC policy on the device (added within ABI 8): the clipped-surrogate update of
+ * RLMPC._rl_worker (rlmpc2.py:783-819) on the records dart_lmpc_collect wrote and the advantages dart_lmpc_gae
+ * wrote, fp32 like the reference's torch nets.  Stateless (the HIP current device), plain launches in stream
+ * order, no atomics: two runs give the same bits.
+ *   prepare, once:  ret_n = (ret - mean) / (std + 1e-8) in fp64 with the population std (:783, numpy);
+ *                   adv_n = (adv - mean) / (std + 1e-8) in fp32 with the unbiased std (:788-790, torch; n = 1
+ *                   gives NaN as torch does);
+ *   per mini-batch of M samples (mini_batch_size, the last of an epoch shorter):
+ *     grad:   both nets forward and backward on rows gathered through perm -> sample -> record row; loss
+ *             -mean(min(ratio adv, clamp(ratio, 1 - clip_eps, 1 + clip_eps) adv)) + vf_coef mse(value, ret_n)
+ *             - ent_coef entropy (:812-815), means over M; exact gradients of it (torch.clamp(std, min=1e-6) and
+ *             the softplus branch of :802-805 cannot be reached, std >= 1e-2);
+ *     apply:  clip_grad_norm_ (coef = min(1, max_grad_norm / (norm + 1e-6)), :818), then torch.optim.Adam with L2
+ *             weight decay (:561) on weights, critic, adam and adam_step in place.
+ * Parameters, gradients and Adam's moments share one packed order: the actor [39748] as dart_lmpc_policy_* reads
+ * it, then the critic [37569]. */
+typedef struct dart_lmpc_ppo_config {
+    double clip_eps;               /* 0.2 (rl_packet, rlmpc2.py:202-226) */
+    double vf_coef;                /* 0.25 (:202-226) */
+    double ent_coef;               /* 0.01 (:202-226) */
+    double max_grad_norm;          /* 0.5 (:202-226, :818) */
+    double lr;                     /* 3e-4 (:561) */
+    double beta1, beta2;           /* 0.9, 0.999 (:561, torch.optim.Adam's defaults) */
+    double adam_eps;               /* 1e-8 (:561, Adam's default) */
+    double weight_decay;           /* 1e-5 (:561) */
+    double log_std_min;            /* log 1e-2 (Policy, :33-80) */
+    double log_std_max;            /* log 2 */
+    int32_t epochs;                /* 8 (:202-226) */
+    int32_t mini_batch_size;       /* 64 (:202-226); 1 .. 1024 */
+} dart_lmpc_ppo_config;
+
+#define DART_LMPC_PPO_NPARAMS 77317
+
+void dart_lmpc_ppo_config_default(dart_lmpc_ppo_config *cfg);
+
+/* Bytes of the caller-provided device workspace for n samples and mini-batches of up to mini_batch_size samples
+ * (0 for n < 1 or a mini_batch_size outside 1 .. 1024). */
+size_t dart_lmpc_ppo_workspace_bytes(int n, int mini_batch_size);
+
+/* The whole update: prepare, then for each of cfg->epochs rows of perm [epochs][n] the mini-batches
+ * perm[e][0:M], perm[e][M:2M], ... each as one gradient launch and one apply launch.  Device pointers,
+ * asynchronous.  sample [n] holds flat indices row * B + b into the record arrays (rec_rows_times_B entries of
+ * 520 / 34 / 1 floats); record rows that sample does not name are never read.  adv, ret: the fp64
+ * [rec_rows][B] arrays of dart_lmpc_gae_dev.  weights [39748], critic [37569] (16-byte aligned, EINVAL otherwise),
+ * adam [2][77317] (m then v) and adam_step [1] are updated in place.  stats [3] (fp64): the means over this call's
+ * steps of policy loss, value loss and entropy; step_log [steps][4] (fp32, nullable): policy loss, value loss,
+ * entropy and gradient norm before the clip, one row per step of this call; adv_norm_out, ret_norm_out [n]
+ * (fp32, nullable): the normalised inputs.  Calls of e1 and e2 epochs with the Adam state carried over and perm
+ * rows 0 .. e1-1, then e1 .. e1+e2-1, give bit for bit what one call of e1 + e2 epochs gives. */
+int dart_lmpc_ppo_update_dev(const dart_lmpc_ppo_config *cfg, int n, int rec_rows_times_B,
+                             const int32_t *sample, const int32_t *perm,
+                             const float *rec_obs, const float *rec_action, const float *rec_logp,
+                             const double *adv, const double *ret,
+                             float *weights, float *critic, float *adam, int32_t *adam_step,
+                             double *stats, float *step_log, float *adv_norm_out, float *ret_norm_out,
+                             void *workspace, void *hip_stream);
+
+/* The same on host pointers: stages, blocks.  Before any device work it returns DART_MPC_EINVAL for n < 1, a
+ * mini_batch_size outside 1 .. 1024, epochs < 0, a sample entry outside [0, rec_rows_times_B), a perm entry
+ * outside [0, n), weights or critic not 16-byte aligned, or a null pointer. */
+int dart_lmpc_ppo_update(const dart_lmpc_ppo_config *cfg, int n, int rec_rows_times_B,
+                         const int32_t *sample, const int32_t *perm,
+                         const float *rec_obs, const float *rec_action, const float *rec_logp,
+                         const double *adv, const double *ret,
+                         float *weights, float *critic, float *adam, int32_t *adam_step,
+                         double *stats, float *step_log, float *adv_norm_out, float *ret_norm_out);
+
+/* The launches of the update one by one, for callers that sequence their own loop (device pointers,
+ * asynchronous, one workspace of dart_lmpc_ppo_workspace_bytes(n, largest M) throughout).  prepare writes the
+ * normalised inputs into the workspace.  grad: one mini-batch idx [M] (positions in sample) -> the packed
+ * gradient grad_out [77317] and terms_out [4] = policy loss, value loss, entropy, gradient norm (the gradient
+ * launch, then the apply launch with its step switched off).  apply: a packed gradient grad [77317] into weights,
+ * critic, adam and adam_step; terms [3] (nullable: zeros) are the loss terms it logs in row step_in_call of
+ * step_log (nullable) and averages into stats (nullable) over step_in_call + 1 steps.  The full update gives bit
+ * for bit what prepare followed by grad and apply for every mini-batch gives. */
+int dart_lmpc_ppo_prepare_dev(int n, int rec_rows_times_B, const int32_t *sample, const double *adv,
+                              const double *ret, float *adv_norm_out, float *ret_norm_out, void *workspace,
+                              void *hip_stream);
+int dart_lmpc_ppo_grad_dev(const dart_lmpc_ppo_config *cfg, int n, int rec_rows_times_B, int M,
+                           const int32_t *sample, const int32_t *idx,
+                           const float *rec_obs, const float *rec_action, const float *rec_logp,
+                           const float *weights, const float *critic, float *grad_out, float *terms_out,
+                           void *workspace, void *hip_stream);
+int dart_lmpc_ppo_apply_dev(const dart_lmpc_ppo_config *cfg, const float *grad, const float *terms,
+                            float *weights, float *critic, float *adam, int32_t *adam_step,
+                            double *stats, float *step_log, int step_in_call, void *workspace, void *hip_stream);
+
+/* value_net (Policy :48-55, fp32) on obs [n][520]: value_out [n]; the bootstrap value of :776-779.  Stateless. */
+int dart_lmpc_critic_value_dev(int n, const float *critic, const float *obs, float *value_out, void *hip_stream);
+int dart_lmpc_critic_value(int n, const float *critic, const float *obs, float *value_out);
+
 int dart_mpc_sync(dart_mpc_handle *h);
 
 const char *dart_mpc_last_error(const dart_mpc_handle *h);

@@ -1,10 +1,13 @@
 """PPO on the LMPC parameter policy with the experience collected on the device: a usage example and a smoke
 record, not a test.  Per iteration: collect K closed-loop steps for B controllers (LmpcSolver.collect: policy step,
 solve, plant step, critic, reward, records and resets without the host), GAE on the device (_lib.gae), the
-clipped-surrogate update in torch (dart_mpc.ppo.ppo_update), then the new weights are packed into the next collect.
+clipped-surrogate update, then the new weights go into the next collect.  --update torch (the default, so that the
+recorded output stays comparable) runs dart_mpc.ppo.ppo_update and re-packs the weights; --update device runs
+dart_mpc.ppo.ppo_update_device (the HIP kernels of csrc/lmpc_ppo.hip) on the packed weights in place, with the
+bootstrap value from _lib.critic_value: the records, the GAE outputs and the weights never pass through torch.
 The loop state, the collection state, the targets and the plants carry over from iteration to iteration.
 Prints the mean return of the episodes that ended, per iteration.
-Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps]
+Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps] [--update device|torch]
 """
 import os
 import sys
@@ -18,10 +21,18 @@ from dart_mpc import _lib, harness, ppo  # noqa: E402
 from dart_mpc.lmpc import LmpcPolicy  # noqa: E402
 from dart_mpc.workload import lmpc_batch  # noqa: E402
 
-iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-B = int(sys.argv[2]) if len(sys.argv) > 2 else 72
-K = int(sys.argv[3]) if len(sys.argv) > 3 else 256
-ep_steps = int(sys.argv[4]) if len(sys.argv) > 4 else 64
+argv = list(sys.argv[1:])
+update = "torch"
+if "--update" in argv:
+    i = argv.index("--update")
+    update = argv[i + 1]
+    del argv[i:i + 2]
+if update not in ("device", "torch"):
+    sys.exit("--update takes device or torch")
+iters = int(argv[0]) if len(argv) > 0 else 5
+B = int(argv[1]) if len(argv) > 1 else 72
+K = int(argv[2]) if len(argv) > 2 else 256
+ep_steps = int(argv[3]) if len(argv) > 3 else 64
 GAMMA, LAM, N = 0.99, 0.95, 30
 
 seeds = -(-B // 18)
@@ -39,13 +50,15 @@ net = ppo.PolicyNet()
 opt = torch.optim.Adam(net.parameters(), lr=3e-4, weight_decay=1e-5)         # rlmpc2.py:561
 gen = torch.Generator().manual_seed(0)
 actor, critic = ppo.pack_weights(net)
+adam, adam_step = ppo.pack_adam(net, opt)                                   # (device update: a fresh Adam, zeros)
 policy = LmpcPolicy(B, weights=actor, critic_weights=critic)
 solver = _lib.LmpcSolver(N=N, B_max=B)
 state = solver.loop_state(D["state"][:B], policy=policy)
 cs = solver.collect_state(np.zeros((B, 2)))
 try:
     for it in range(iters):
-        policy.weights, policy.critic_weights = ppo.pack_weights(net)
+        if update == "torch":
+            policy.weights, policy.critic_weights = ppo.pack_weights(net)
         lg, clg = _lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, B), _lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, B)
         rec = _lib.loop_logs(_lib.LMPC_COLLECT_REC, rec_rows, B)
         cs["nrec"][:] = 0
@@ -53,12 +66,20 @@ try:
         ep0 = cs["episodes"].copy()
         solver.collect(0, K, target, pvec, state, cs, lg, clg, rec, policy, rcfg=rcfg, noise=noise, pool=pool)
         # bootstrap from the critic on the last observation (:776-779)
-        last_value = harness.lmpc_critic_value(policy.critic_weights, state["history"])
+        last_value = (_lib.critic_value(policy.critic_weights, state["history"]) if update == "device"
+                      else harness.lmpc_critic_value(policy.critic_weights, state["history"]))
         adv, ret = _lib.gae(cs["nrec"], rec["rec_reward"], rec["rec_value"], rec["rec_done"], last_value, GAMMA, LAM)
         m = np.arange(rec_rows)[:, None] < cs["nrec"][None]
-        batch = dict(obs=rec["rec_obs"][m], action=rec["rec_action"][m], logp=rec["rec_logp"][m], adv=adv[m], ret=ret[m])
-        out = ppo.ppo_update(net, opt, batch, clip_eps=0.2, epochs=8, mini_batch_size=64, vf_coef=0.25, ent_coef=0.01,
-                             generator=gen)
+        if update == "device":
+            sample = np.flatnonzero(m.reshape(-1)).astype(np.int32)          # row-major: the order rec[m] gives
+            out = ppo.ppo_update_device(policy.weights, policy.critic_weights, adam, adam_step, rec, sample, adv, ret,
+                                        ppo.make_perms(sample.size, 8, gen), clip_eps=0.2, mini_batch_size=64,
+                                        vf_coef=0.25, ent_coef=0.01)
+        else:
+            batch = dict(obs=rec["rec_obs"][m], action=rec["rec_action"][m], logp=rec["rec_logp"][m], adv=adv[m],
+                         ret=ret[m])
+            out = ppo.ppo_update(net, opt, batch, clip_eps=0.2, epochs=8, mini_batch_size=64, vf_coef=0.25,
+                                 ent_coef=0.01, generator=gen)
         ended = cs["episodes"] > ep0
         mean_ret = float(cs["last_return"][ended].mean()) if ended.any() else float("nan")
         print(f"iter {it}: samples {int(m.sum())}, episodes ended {int((cs['episodes'] - ep0).sum())}, "
