@@ -22,6 +22,7 @@
 #include "lmpc_policy.h"
 #include "lmpc_experience.h"
 #include "lmpc_ppo.h"
+#include "lmpc_train.h"
 #include "arm_qp.h"
 #include "loop_step.h"
 
@@ -2314,5 +2315,334 @@ int dart_lmpc_critic_value(int n, const float* critic, const float* obs, float* 
     if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
     if (e != hipSuccess) return DART_MPC_EHIP;
     S.finish_inout();
+    return DART_MPC_OK;
+}
+
+// ---- whole PPO training iterations on the device (lmpc_train.hip) ---------------------------------------------
+
+int dart_lmpc_philox_dev(int n, const uint32_t* in, uint32_t* out, void* stream) {
+    if (n < 0) return DART_MPC_EINVAL;
+    if (n == 0) return DART_MPC_OK;
+    if (!in || !out) return DART_MPC_EINVAL;
+    dartmpc::PhiloxArgs a;
+    a.n = n; a.in = in; a.out = out;
+    return dartmpc_launch_philox(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+namespace {
+
+hipError_t launch_noise(uint64_t seed, int iteration, int steps, int B, float* out, hipStream_t s) {
+    dartmpc::NoiseArgs a;
+    a.n = (long long)steps * B * 34;
+    a.key0 = (uint32_t)(seed & 0xffffffffu); a.key1 = (uint32_t)(seed >> 32); a.iteration = (uint32_t)iteration;
+    a.out = out;
+    return dartmpc_launch_lmpc_noise(&a, s);
+}
+
+hipError_t launch_perms(uint64_t seed, int iteration, int epochs, int n, int32_t* perm, uint32_t* key_out,
+                        hipStream_t s) {
+    dartmpc::PermArgs a;
+    a.n = n; a.epochs = epochs;
+    a.key0 = (uint32_t)(seed & 0xffffffffu); a.key1 = (uint32_t)(seed >> 32); a.iteration = (uint32_t)iteration;
+    a.perm = perm; a.key_out = key_out;
+    return dartmpc_launch_lmpc_perms(&a, s);
+}
+
+// (the Philox block index is 32 bits wide: 4 * 2^32 elements at the most)
+bool noise_shape_ok(int iteration, int steps, int B) {
+    return iteration >= 0 && steps >= 0 && B >= 0 && (long long)steps * B * 34 <= (1LL << 34);
+}
+
+int mean_update_args(const dart_lmpc_policy_config* cfg, int B, const float* weights, dartmpc::MeanUpdateArgs& a) {
+    dartmpc::PolicyArgs pa;
+    if (policy_args(cfg, B, weights, pa) != DART_MPC_OK) return DART_MPC_EINVAL;
+    a.B = B; a.w = pa.w;
+    a.max_delta = pa.max_delta; a.k_max = pa.k_max; a.min_k = pa.min_k; a.k_ceiling_margin = pa.k_ceiling_margin;
+    a.action_scale = pa.action_scale; a.smooth_alpha = pa.smooth_alpha;
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_noise_dev(uint64_t seed, int iteration, int steps, int B, float* noise_out, void* stream) {
+    if (!noise_shape_ok(iteration, steps, B)) return DART_MPC_EINVAL;
+    if (steps == 0 || B == 0) return DART_MPC_OK;
+    if (!noise_out) return DART_MPC_EINVAL;
+    return launch_noise(seed, iteration, steps, B, noise_out, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK
+                                                                                                  : DART_MPC_EHIP;
+}
+
+int dart_lmpc_noise(uint64_t seed, int iteration, int steps, int B, float* noise_out) {
+    if (!noise_shape_ok(iteration, steps, B)) return DART_MPC_EINVAL;
+    if (steps == 0 || B == 0) return DART_MPC_OK;
+    if (!noise_out) return DART_MPC_EINVAL;
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    const size_t n = (size_t)steps * B * 34;
+    if (S.reserve(0, sizeof(float) * n + 256) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    float* d = S.out<float>(n);
+    hipError_t e = launch_noise(seed, iteration, steps, B, d, D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.take(noise_out, d, n);
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_perms_dev(uint64_t seed, int iteration, int epochs, int n, int32_t* perm_out, uint32_t* key_out,
+                        void* stream) {
+    if (iteration < 0 || epochs < 0 || n < 0) return DART_MPC_EINVAL;
+    if (epochs == 0 || n == 0) return DART_MPC_OK;
+    if (!perm_out) return DART_MPC_EINVAL;
+    return launch_perms(seed, iteration, epochs, n, perm_out, key_out, (hipStream_t)stream) == hipSuccess
+               ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_perms(uint64_t seed, int iteration, int epochs, int n, int32_t* perm_out, uint32_t* key_out) {
+    if (iteration < 0 || epochs < 0 || n < 0) return DART_MPC_EINVAL;
+    if (epochs == 0 || n == 0) return DART_MPC_OK;
+    if (!perm_out) return DART_MPC_EINVAL;
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    const size_t m = (size_t)epochs * n;
+    if (S.reserve(0, 2 * (sizeof(int32_t) * m + 256)) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    int32_t* d = S.out<int32_t>(m);
+    uint32_t* dk = key_out ? S.out<uint32_t>(m) : nullptr;
+    hipError_t e = launch_perms(seed, iteration, epochs, n, d, dk, D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.take(perm_out, d, m);
+    S.take(key_out, dk, m);
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_mean_param_update_dev(const dart_lmpc_policy_config* cfg, int B, const float* weights,
+                                    const float* history, double* model_params, double* current_k, float* mean_out,
+                                    void* stream) {
+    dartmpc::MeanUpdateArgs a;
+    if (mean_update_args(cfg, B, weights, a) != DART_MPC_OK) return DART_MPC_EINVAL;
+    if (B == 0) return DART_MPC_OK;
+    if (!history || !model_params || !current_k) return DART_MPC_EINVAL;
+    a.history = history; a.model_params = model_params; a.current_k = current_k; a.mean_out = mean_out;
+    return dartmpc_launch_lmpc_mean_update(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_mean_param_update(const dart_lmpc_policy_config* cfg, int B, const float* weights, const float* history,
+                                double* model_params, double* current_k, float* mean_out) {
+    dartmpc::MeanUpdateArgs a;
+    if (mean_update_args(cfg, B, weights, a) != DART_MPC_OK) return DART_MPC_EINVAL;
+    if (B == 0) return DART_MPC_OK;
+    if (!history || !model_params || !current_k) return DART_MPC_EINVAL;
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    const size_t nB = (size_t)B;
+    if (S.reserve(sizeof(float) * ((size_t)DART_LMPC_POLICY_NWEIGHTS + 520 * nB) + sizeof(double) * 68 * nB + 8 * 256,
+                  sizeof(float) * 34 * nB + 256) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    const float* d_w = S.in(weights, (size_t)DART_LMPC_POLICY_NWEIGHTS);
+    if (mean_update_args(cfg, B, d_w, a) != DART_MPC_OK) return DART_MPC_EINVAL;
+    a.history = S.in(history, 520 * nB);
+    a.model_params = S.inout(model_params, 34 * nB);
+    a.current_k = S.inout(current_k, 34 * nB);
+    a.mean_out = mean_out ? S.out<float>(34 * nB) : nullptr;
+    hipError_t e = S.upload(D->stream);
+    if (e == hipSuccess) e = dartmpc_launch_lmpc_mean_update(&a, D->stream);
+    if (e == hipSuccess) e = S.download_inout(D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.finish_inout();
+    S.take(mean_out, a.mean_out, 34 * nB);
+    return DART_MPC_OK;
+}
+
+void dart_lmpc_train_config_default(dart_lmpc_train_config* c) {
+    if (!c) return;
+    c->seed = 0; c->iterations = 1; c->it0 = 0; c->steps = 256; c->mean_update = 1; c->track_best = 1;
+    c->reserved = 0; c->gamma = 0.99; c->lam = 0.95;
+}
+
+size_t dart_lmpc_train_workspace_bytes(int B, int K, int record_every, int epochs, int mini_batch_size) {
+    if (B < 1 || record_every < 1 || K < record_every || K % record_every != 0 || epochs < 0 || mini_batch_size < 1 ||
+        mini_batch_size > dartmpc::kPpoMaxBatch) return 0;
+    if ((long long)(K / record_every) * B > 0x7fffffffLL) return 0;
+    return dartmpc::train_workspace(B, K, record_every, epochs, mini_batch_size).bytes;
+}
+
+namespace {
+
+// the checks of the training entries that need neither the device nor the arrays' contents
+int train_check(dart_mpc_handle* h, const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                const dart_lmpc_train_config* cfg, int B, const dart_lmpc_train_buffers* p, bool need_ws) {
+    if (!cfg || !p || !rcfg) return fail(h, DART_MPC_EINVAL, "null training config, reward config or buffers");
+    if (!ppo_cfg_ok(ppo)) return fail(h, DART_MPC_EINVAL, "bad PPO config");
+    if (cfg->iterations < 0 || cfg->it0 < 0 || (long long)cfg->it0 + cfg->iterations > 0x7fffffffLL)
+        return fail(h, DART_MPC_EINVAL, "training config: iterations >= 0, it0 >= 0");
+    if (B < 1) return fail(h, DART_MPC_EINVAL, "training needs B >= 1");
+    if (rcfg->record_every < 1 || cfg->steps < rcfg->record_every || cfg->steps % rcfg->record_every != 0)
+        return fail(h, DART_MPC_EINVAL, "training config: steps must be a positive multiple of record_every");
+    if ((long long)(cfg->steps / rcfg->record_every) * B > 0x7fffffffLL)
+        return fail(h, DART_MPC_EINVAL, "too many samples");
+    if (any_null({p->current_k, p->weights, p->critic, p->adam, p->adam_step, p->train_log, p->best_return,
+                  p->best_weights, p->best_iter}) || (need_ws && !p->workspace))
+        return fail(h, DART_MPC_EINVAL, "null pointer (training arrays)");
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                        const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                        const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                        void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = train_check(h, rcfg, ppo, cfg, B, p, true)) return rc;
+    const int K = cfg->steps, R = K / rcfg->record_every, n = R * B, mb = ppo->mini_batch_size;
+    void* s = stream ? stream : (void*)h->stream;
+    auto collect = [&](int steps, const float* noise) {
+        return dart_lmpc_collect_dev(
+            h, plant, pcfg, rcfg, B, 0, steps, K, R, reset_rows, p->target, p->prm, p->plant_pvec, p->current_k,
+            p->weights, p->critic, noise, p->x, p->tilt, p->u_prev, p->w, p->obs_mean, p->obs_M2, p->obs_count,
+            p->history, p->timestep, p->model_params, p->prev_cmd, p->control_seen, p->ep_step, p->ep_return,
+            p->time_penalty, p->episodes, p->last_return, p->last_steps, p->nrec, p->sticky, p->reset_x,
+            p->reset_target, p->reset_pvec, p->log_X, p->log_U, p->log_pos_error, p->log_pvec, p->log_loss,
+            p->log_status, p->log_iters, p->log_reward, p->log_done, p->log_value, p->log_logp, p->rec_obs,
+            p->rec_action, p->rec_logp, p->rec_value, p->rec_reward, p->rec_done, s);
+    };
+    // every check of the collection (configs, null pointers, B <= B_max) before any device work: zero steps
+    if (int rc = collect(0, nullptr)) return rc;
+    if (cfg->iterations == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const dartmpc::TrainWorkspace L = dartmpc::train_workspace(B, K, rcfg->record_every, ppo->epochs, mb);
+    char* ws = (char*)p->workspace;
+    float* noise = (float*)(ws + L.noise);
+    float* last_value = (float*)(ws + L.last_value);
+    double* adv = (double*)(ws + L.adv);
+    double* ret = (double*)(ws + L.ret);
+    int32_t* sample = (int32_t*)(ws + L.sample);
+    int32_t* perm = (int32_t*)(ws + L.perm);
+    double* stats = (double*)(ws + L.stats);
+    int32_t* ep0 = (int32_t*)(ws + L.ep0);
+    hipStream_t hs = (hipStream_t)s;
+    {
+        dartmpc::IotaArgs ia;
+        ia.n = n; ia.out = sample;
+        HIPCHK(h, dartmpc_launch_iota(&ia, hs), "sample list launch");
+    }
+    for (int j = 0; j < cfg->iterations; ++j) {
+        const int it = cfg->it0 + j;
+        HIPCHK(h, hipMemsetAsync(p->nrec, 0, sizeof(int32_t) * (size_t)B, hs), "clear nrec");
+        HIPCHK(h, hipMemcpyAsync(ep0, p->episodes, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, hs),
+               "copy episodes");
+        // (with epochs = 0 the update leaves its statistics untouched)
+        if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(double) * 3, hs), "clear stats");
+        HIPCHK(h, launch_noise(cfg->seed, it, K, B, noise, hs), "noise launch");
+        if (int rc = collect(K, noise)) return rc;
+        if (dart_lmpc_critic_value_dev(B, p->critic, p->history, last_value, s) != DART_MPC_OK)
+            return fail(h, DART_MPC_EHIP, "critic value launch");
+        if (dart_lmpc_gae_dev(B, R, cfg->gamma, cfg->lam, p->nrec, p->rec_reward, p->rec_value, p->rec_done,
+                              last_value, adv, ret, s) != DART_MPC_OK)
+            return fail(h, DART_MPC_EHIP, "GAE launch");
+        HIPCHK(h, launch_perms(cfg->seed, it, ppo->epochs, n, perm, nullptr, hs), "permutation launch");
+        if (int rc = dart_lmpc_ppo_update_dev(ppo, n, n, sample, perm, p->rec_obs, p->rec_action, p->rec_logp, adv,
+                                              ret, p->weights, p->critic, p->adam, p->adam_step, stats, nullptr,
+                                              nullptr, nullptr, ws + L.ppo, s))
+            return fail(h, rc, "PPO update");
+        if (cfg->mean_update)
+            if (dart_lmpc_mean_param_update_dev(pcfg, B, p->weights, p->history, p->model_params, p->current_k,
+                                                nullptr, s) != DART_MPC_OK)
+                return fail(h, DART_MPC_EHIP, "mean parameter update launch");
+        dartmpc::TrainLogArgs la;
+        la.B = B; la.K = K; la.R = R; la.n = n; la.iteration = it; la.track_best = cfg->track_best ? 1 : 0;
+        la.ep0 = ep0; la.episodes = p->episodes; la.last_return = p->last_return; la.nrec = p->nrec;
+        la.log_reward = p->log_reward; la.log_status = p->log_status; la.stats = stats;
+        la.actor = p->weights; la.critic = p->critic;
+        la.row = p->train_log + (size_t)dartmpc::kTrainLogCols * j;
+        la.best_return = p->best_return; la.best_weights = p->best_weights; la.best_iter = p->best_iter;
+        HIPCHK(h, dartmpc_launch_lmpc_train_log(&la, hs), "training log launch");
+    }
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_train(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                    const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                    const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                    void* stream) {
+    if (!h) return DART_MPC_EINVAL;
+    std::unique_lock<std::recursive_mutex> lock_(h->mu);
+    if (int rc = train_check(h, rcfg, ppo, cfg, B, p, false)) return rc;
+    if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, "handle is not an LMPC handle");
+    if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
+    if (reset_rows < 0) return fail(h, DART_MPC_EINVAL, "negative reset_rows");
+    if (any_null({p->target, p->prm, p->plant_pvec, p->x, p->tilt, p->u_prev, p->w, p->obs_mean, p->obs_M2,
+                  p->obs_count, p->history, p->timestep, p->model_params, p->prev_cmd, p->control_seen, p->ep_step,
+                  p->ep_return, p->time_penalty, p->episodes, p->last_return, p->last_steps, p->nrec, p->sticky,
+                  p->log_X, p->log_U, p->log_pos_error, p->log_pvec, p->log_loss, p->log_status, p->log_iters,
+                  p->log_reward, p->log_done, p->log_value, p->log_logp, p->rec_obs, p->rec_action, p->rec_logp,
+                  p->rec_value, p->rec_reward, p->rec_done}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (reset_rows > 0 && any_null({p->reset_x, p->reset_target, p->reset_pvec}))
+        return fail(h, DART_MPC_EINVAL, "reset_rows > 0 with a null reset pool");
+    // instances that do not share timestep are the only way to nrec[b] != R
+    for (int b = 1; b < B; ++b)
+        if (p->timestep[b] != p->timestep[0]) return fail(h, DART_MPC_EINVAL, "instances differ in timestep");
+    if (cfg->iterations == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t), F = sizeof(float);
+    const size_t nw = (size_t)dart_lmpc_nw(h->cfg.N), P = dartmpc::kPpoParams;
+    const size_t K = (size_t)cfg->steps, R = K / (size_t)rcfg->record_every, RS = (size_t)reset_rows;
+    RollStage S;
+    dart_lmpc_train_buffers d = *p;
+    std::vector<std::pair<void**, int>> bind;       // device pointer of field <- arena block
+    auto both = [&](auto*& field, size_t bytes) { bind.push_back({(void**)&field, S.add(field, bytes, true)}); };
+    auto up = [&](auto*& field, size_t bytes) { bind.push_back({(void**)&field, S.add(field, bytes, false)}); };
+    auto down = [&](auto*& field, size_t rows, size_t rowbytes) {
+        bind.push_back({(void**)&field, S.add_log((void*)field, rows, rowbytes, 0, rows, false)});
+    };
+    both(d.target, 8 * nB * D); up(d.prm, dartmpc::LM_NPRM * nB * D); both(d.plant_pvec, 34 * nB * D);
+    both(d.current_k, 34 * nB * D);
+    both(d.weights, (size_t)DART_LMPC_POLICY_NWEIGHTS * F); both(d.critic, (size_t)DART_LMPC_CRITIC_NWEIGHTS * F);
+    both(d.x, 8 * nB * D); both(d.tilt, 2 * nB * D); both(d.u_prev, 2 * nB * D); both(d.w, nw * nB * D);
+    both(d.obs_mean, 52 * nB * D); both(d.obs_M2, 52 * nB * D); both(d.obs_count, nB * I);
+    both(d.history, 520 * nB * F); both(d.timestep, nB * I); both(d.model_params, 34 * nB * D);
+    both(d.prev_cmd, 2 * nB * D); both(d.control_seen, 2 * nB * D); both(d.ep_step, nB * I); both(d.ep_return, nB * D);
+    both(d.time_penalty, nB * D); both(d.episodes, nB * I); both(d.last_return, nB * D); both(d.last_steps, nB * I);
+    both(d.nrec, nB * I); both(d.sticky, nB * I);
+    if (reset_rows > 0) {
+        up(d.reset_x, RS * 8 * nB * D); up(d.reset_target, RS * 8 * nB * D); up(d.reset_pvec, RS * 34 * nB * D);
+    } else {
+        d.reset_x = d.reset_target = d.reset_pvec = nullptr;
+    }
+    down(d.log_X, K, 8 * nB * D); down(d.log_U, K, 2 * nB * D); down(d.log_pos_error, K, nB * D);
+    down(d.log_pvec, K, 34 * nB * D); down(d.log_loss, K, nB * D); down(d.log_status, K, nB * I);
+    down(d.log_iters, K, nB * I); down(d.log_reward, K, nB * D); down(d.log_done, K, nB * I);
+    down(d.log_value, K, nB * F); down(d.log_logp, K, nB * F);
+    down(d.rec_obs, R, 520 * nB * F); down(d.rec_action, R, 34 * nB * F); down(d.rec_logp, R, nB * F);
+    down(d.rec_value, R, nB * F); down(d.rec_reward, R, nB * D); down(d.rec_done, R, nB * F);
+    both(d.adam, 2 * P * F); both(d.adam_step, I);
+    down(d.train_log, (size_t)cfg->iterations, dartmpc::kTrainLogCols * D);
+    both(d.best_return, D); both(d.best_weights, P * F); both(d.best_iter, I);
+    // the workspace: a block of the arena that does not travel
+    const size_t ws_bytes = dartmpc::train_workspace(B, (int)K, rcfg->record_every, ppo->epochs,
+                                                     ppo->mini_batch_size).bytes;
+    const int i_ws = S.add_log(nullptr, 1, ws_bytes, 0, 0, false);
+    if (int rc = S.reserve(h)) return rc;
+    for (auto& b : bind) *b.first = S.dev<char>(h, b.second);
+    d.workspace = S.dev<char>(h, i_ws);
+    if (int rc = S.upload(h, s)) return rc;
+    if (int rc = dart_lmpc_train_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, &d, s)) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
     return DART_MPC_OK;
 }

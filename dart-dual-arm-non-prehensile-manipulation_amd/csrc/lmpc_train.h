@@ -1,0 +1,127 @@
+// lmpc_train.h -- launch arguments of the kernels that close the LMPC training loop on the device
+// (lmpc_train.hip): the exploration noise and the mini-batch permutations from one counter-based generator, the
+// mean-based parameter write after an update (LMPC/src/controller/rlmpc2.py:876-896), and the iteration's log row
+// with the best-policy snapshot (:918-922).  With them dart_lmpc_train_dev enqueues whole PPO iterations -- noise,
+// dart_lmpc_collect_dev, critic value, GAE, permutations, dart_lmpc_ppo_update_dev, parameter write, log row -- on
+// one stream without host work in between.
+//
+// Plain launches in stream order: no cooperative launch, no grid barrier, no atomics; every sum has a fixed order.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "lmpc_policy.h"
+#include "lmpc_ppo.h"
+
+namespace dartmpc {
+
+// Philox4x32-10 (Salmon et al., SC'11) with the standard constants.  key = (seed & 0xffffffff, seed >> 32); the
+// counter is (c, iteration, stream, epoch): block c yields the four words of elements 4c .. 4c+3.
+constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
+constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
+constexpr uint32_t kStreamNoise = 0, kStreamPerm = 1;
+
+struct Philox4 { uint32_t w[4]; };
+
+__host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                 uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * c0, p1 = (uint64_t)kPhiloxM1 * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += kPhiloxW0; k1 += kPhiloxW1;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+
+struct PhiloxArgs {             // out[i] = philox(in[i][0:4], key in[i][4:6]), for the known-answer tests
+    int n;
+    const uint32_t* in;         // [n][6]
+    uint32_t* out;              // [n][4]
+};
+
+// standard-normal draws [n] (n = steps * B * 34): element e takes word e % 4 of block e / 4; words 0, 1 and 2, 3
+// each give one Box-Muller pair from u = ((r >> 9) + 0.5) 2^-23
+struct NoiseArgs {
+    long long n;
+    uint32_t key0, key1, iteration;
+    float* out;
+};
+
+// perm[e][rank of (key_i, i)] = i, key_i = word i % 4 of block i / 4 with stream 1 and epoch e in the counter;
+// grid (ceil(n / 256), epochs)
+struct PermArgs {
+    int n, epochs;
+    uint32_t key0, key1, iteration;
+    int32_t* perm;              // [epochs][n]
+    uint32_t* key_out;          // [epochs][n] the raw keys, nullable
+};
+
+struct IotaArgs {
+    int n;
+    int32_t* out;               // [n] 0 .. n-1
+};
+
+// the actor's mean on history (no Welford update, no shift, zero noise, timestep untouched), then the logit-space
+// update, the EMA and the soft clip of policy_step_wave, unconditionally; current_k <- model_params
+struct MeanUpdateArgs {
+    int B;
+    PolicyWeights w;
+    const float* history;       // [B][520]
+    double* model_params;       // [B][34] in/out
+    double* current_k;          // [B][34] out
+    float* mean_out;            // [B][34] nullable
+    double max_delta, k_max, min_k, k_ceiling_margin, action_scale, smooth_alpha;
+};
+
+constexpr int kTrainLogCols = 12;
+
+// one row of train_log and the best-policy snapshot; one workgroup
+struct TrainLogArgs {
+    int B, K, R, n, iteration, track_best;
+    const int32_t* ep0;         // [B] episodes before the collection
+    const int32_t* episodes;    // [B]
+    const double* last_return;  // [B]
+    const int32_t* nrec;        // [B]
+    const double* log_reward;   // [K][B]
+    const int32_t* log_status;  // [K][B]
+    const double* stats;        // [3] of the update
+    const float* actor;         // [39748]
+    const float* critic;        // [37569]
+    double* row;                // [12]
+    double* best_return;        // [1] in/out
+    float* best_weights;        // [77317]
+    int32_t* best_iter;         // [1]
+};
+
+// Workspace of dart_lmpc_train_dev (bytes from the base, every block 256-byte aligned)
+struct TrainWorkspace {
+    size_t noise, last_value, adv, ret, sample, perm, stats, ep0, ppo, bytes;
+};
+inline TrainWorkspace train_workspace(int B, int K, int record_every, int epochs, int mb) {
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t R = (size_t)(K / record_every), n = R * (size_t)B;
+    TrainWorkspace w;
+    size_t o = 0;
+    w.noise = o; o += al(sizeof(float) * (size_t)K * B * 34);
+    w.last_value = o; o += al(sizeof(float) * (size_t)B);
+    w.adv = o; o += al(sizeof(double) * n);
+    w.ret = o; o += al(sizeof(double) * n);
+    w.sample = o; o += al(sizeof(int32_t) * n);
+    w.perm = o; o += al(sizeof(int32_t) * n * (size_t)(epochs > 0 ? epochs : 1));
+    w.stats = o; o += al(sizeof(double) * 3);
+    w.ep0 = o; o += al(sizeof(int32_t) * (size_t)B);
+    w.ppo = o; o += ppo_workspace((int)n, mb).bytes;
+    w.bytes = o;
+    return w;
+}
+
+}  // namespace dartmpc
+
+extern "C" hipError_t dartmpc_launch_philox(const dartmpc::PhiloxArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_noise(const dartmpc::NoiseArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_perms(const dartmpc::PermArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_iota(const dartmpc::IotaArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_mean_update(const dartmpc::MeanUpdateArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_train_log(const dartmpc::TrainLogArgs* args, hipStream_t stream);

@@ -48,7 +48,10 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_lmpc_collect", "dart_lmpc_gae_dev", "dart_lmpc_gae",
            "dart_lmpc_ppo_config_default", "dart_lmpc_ppo_workspace_bytes", "dart_lmpc_ppo_update_dev",
            "dart_lmpc_ppo_update", "dart_lmpc_ppo_prepare_dev", "dart_lmpc_ppo_grad_dev", "dart_lmpc_ppo_apply_dev",
-           "dart_lmpc_critic_value_dev", "dart_lmpc_critic_value")
+           "dart_lmpc_critic_value_dev", "dart_lmpc_critic_value",
+           "dart_lmpc_philox_dev", "dart_lmpc_noise_dev", "dart_lmpc_noise", "dart_lmpc_perms_dev", "dart_lmpc_perms",
+           "dart_lmpc_mean_param_update_dev", "dart_lmpc_mean_param_update", "dart_lmpc_train_config_default",
+           "dart_lmpc_train_workspace_bytes", "dart_lmpc_train_dev", "dart_lmpc_train")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -95,6 +98,13 @@ class PpoConfig(ctypes.Structure):
                 ("beta2", ctypes.c_double), ("adam_eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
                 ("log_std_min", ctypes.c_double), ("log_std_max", ctypes.c_double), ("epochs", ctypes.c_int32),
                 ("mini_batch_size", ctypes.c_int32)]
+
+
+class TrainConfig(ctypes.Structure):
+    """Mirror of ``struct dart_lmpc_train_config`` (seed, iteration range and GAE settings of the training entry)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("iterations", ctypes.c_int32), ("it0", ctypes.c_int32),
+                ("steps", ctypes.c_int32), ("mean_update", ctypes.c_int32), ("track_best", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("gamma", ctypes.c_double), ("lam", ctypes.c_double)]
 
 
 # Arrays of the closed-loop rollouts in the argument order of include/dart_mpc.h: (name, row width, dtype);
@@ -311,6 +321,25 @@ def lib():
         for fn in (L.dart_lmpc_ppo_update_dev, L.dart_lmpc_ppo_update, L.dart_lmpc_ppo_prepare_dev,
                    L.dart_lmpc_ppo_grad_dev, L.dart_lmpc_ppo_apply_dev, L.dart_lmpc_critic_value_dev,
                    L.dart_lmpc_critic_value):
+            fn.restype = ctypes.c_int
+    if hasattr(L, "dart_lmpc_train_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
+        L.dart_lmpc_philox_dev.argtypes = [ci, vp, vp, vp]
+        L.dart_lmpc_noise_dev.argtypes = [u64, ci, ci, ci, vp, vp]
+        L.dart_lmpc_noise.argtypes = [u64, ci, ci, ci, vp]
+        L.dart_lmpc_perms_dev.argtypes = [u64, ci, ci, ci, vp, vp, vp]
+        L.dart_lmpc_perms.argtypes = [u64, ci, ci, ci, vp, vp]
+        L.dart_lmpc_mean_param_update_dev.argtypes = [vp, ci] + [vp] * 6
+        L.dart_lmpc_mean_param_update.argtypes = [vp, ci] + [vp] * 5
+        L.dart_lmpc_train_config_default.argtypes = [ctypes.POINTER(TrainConfig)]
+        L.dart_lmpc_train_config_default.restype = None
+        L.dart_lmpc_train_workspace_bytes.argtypes = [ci] * 5
+        L.dart_lmpc_train_workspace_bytes.restype = ctypes.c_size_t
+        for fn in (L.dart_lmpc_train_dev, L.dart_lmpc_train):
+            fn.argtypes = [vp] * 6 + [ci, ci, vp, vp]
+        for fn in (L.dart_lmpc_philox_dev, L.dart_lmpc_noise_dev, L.dart_lmpc_noise, L.dart_lmpc_perms_dev,
+                   L.dart_lmpc_perms, L.dart_lmpc_mean_param_update_dev, L.dart_lmpc_mean_param_update,
+                   L.dart_lmpc_train_dev, L.dart_lmpc_train):
             fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
@@ -968,6 +997,63 @@ class LmpcSolver(Solver):
         if rc != 0:
             self._err(rc, "dart_lmpc_collect")
 
+    # -- whole PPO iterations on the device (dart_lmpc_train_dev / dart_lmpc_train) ----
+    def train_dev(self, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state, cstate, logs, clogs,
+                  rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool=None, plant=None, stream=0):
+        """``tcfg.iterations`` complete PPO iterations enqueued on one stream, no host work in between
+        (dart_lmpc_train_dev).  Device pointers (ints) as in ``collect_dev``; ``weights``, ``critic`` and
+        ``current_k`` are updated in place; ``train`` maps the names of LMPC_TRAIN_ARRAYS (adam, adam_step,
+        train_log [iterations, 12], best_return, best_weights, best_iter, workspace of ``train_workspace_bytes``) to
+        device pointers.  The logs have ``tcfg.steps`` rows and the records steps / record_every."""
+        plant = plant or plant_config()
+        buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
+                             + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
+                             + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
+                             + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
+                             + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
+        rc = lib().dart_lmpc_train_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
+                                       ctypes.byref(ppo_cfg), ctypes.byref(tcfg), int(B), int(reset_rows), buf,
+                                       stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_train_dev")
+
+    def train(self, target, plant_pvec, state, cstate, logs, clogs, rec, policy, adam, adam_step, train_log,
+              best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None, pool=None, plant=None):
+        """Host arrays (blocking, dart_lmpc_train): state, weights, Adam's state and the reset pool are staged in
+        once, ``tcfg.iterations`` iterations run on the device, the results are staged out once.  Updated in place:
+        ``target``, ``plant_pvec``, ``state``, ``cstate``, ``policy.weights`` / ``critic_weights`` / ``current_k``,
+        ``adam`` [2, 77317], ``adam_step`` [1], ``best_return`` [1] (float64, start at -inf), ``best_weights``
+        [77317], ``best_iter`` [1]; ``logs`` / ``clogs`` ([steps, B, ..]) and ``rec`` ([steps / record_every, B, ..])
+        receive the last iteration's values, ``train_log`` [iterations, 12] one row per iteration."""
+        B, K = state["x"].shape[0], int(tcfg.steps)
+        rcfg = rcfg if rcfg is not None else reward_config()
+        R = K // max(int(rcfg.record_every), 1)
+        reset_rows = 0 if not pool else pool["reset_x"].shape[0]
+        prm = np.ascontiguousarray(np.tile(LMPC_PRM_DEFAULT, (B, 1)) if prm is None else prm, np.float64).reshape(B, 22)
+        plant = plant or plant_config()
+        if policy.critic_weights is None:
+            raise DartMPCError("training needs a policy with critic_weights")
+        policy.current_k = _inplace(policy.current_k, np.float64, 34 * B, "policy.current_k")
+        head = [("target", 8, np.float64), ("plant_pvec", 34, np.float64)]
+        tg, pp = _host_ptrs(head, {"target": target, "plant_pvec": plant_pvec}, (B,))
+        tail = [_inplace(adam, np.float32, 2 * PPO_NPARAMS, "adam"), _inplace(adam_step, np.int32, 1, "adam_step"),
+                _inplace(train_log, np.float64, TRAIN_LOG_COLS * int(tcfg.iterations), "train_log"),
+                _inplace(best_return, np.float64, 1, "best_return"),
+                _inplace(best_weights, np.float32, PPO_NPARAMS, "best_weights"),
+                _inplace(best_iter, np.int32, 1, "best_iter")]
+        ptrs = ([tg, _ptr(prm), pp, _ptr(policy.current_k),
+                 _ptr(_inplace(policy.weights, np.float32, ACTOR_NWEIGHTS, "policy.weights")),
+                 _ptr(_inplace(policy.critic_weights, np.float32, CRITIC_NWEIGHTS, "policy.critic_weights"))]
+                + _host_ptrs(LMPC_LOOP_STATE, state, (B,), nw=self.nw) + _host_ptrs(LMPC_COLLECT_STATE, cstate, (B,))
+                + (_host_ptrs(LMPC_COLLECT_POOL, pool, (reset_rows, B)) if reset_rows else [None] * 3)
+                + _host_ptrs(LMPC_LOOP_LOGS, logs, (K, B)) + _host_ptrs(LMPC_COLLECT_LOGS, clogs, (K, B))
+                + _host_ptrs(LMPC_COLLECT_REC, rec, (R, B)) + [_ptr(a) for a in tail] + [None])
+        buf = _train_buffers([0 if q is None else q.value for q in ptrs])
+        rc = lib().dart_lmpc_train(self._h, ctypes.byref(plant), ctypes.byref(policy.cfg), ctypes.byref(rcfg),
+                                   ctypes.byref(ppo_cfg), ctypes.byref(tcfg), B, reset_rows, buf, None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_train")
+
     @staticmethod
     def collect_state(u_prev):
         """The collection state of a fresh collection: ``prev_cmd`` and ``control_seen`` start at the initial
@@ -1170,6 +1256,102 @@ def ppo_apply(cfg, grad, weights, critic, adam, adam_step, terms=None):
     weights[...] = dw.cpu().numpy().reshape(weights.shape); critic[...] = dc.cpu().numpy().reshape(critic.shape)
     adam[...] = da.cpu().numpy().reshape(adam.shape); adam_step[...] = ds.cpu().numpy().reshape(adam_step.shape)
     return log.cpu().numpy()
+
+
+# the training arrays of dart_lmpc_train_buffers behind those of dart_lmpc_collect_dev, in the struct's order
+LMPC_TRAIN_ARRAYS = ("adam", "adam_step", "train_log", "best_return", "best_weights", "best_iter", "workspace")
+TRAIN_LOG_COLS = 12
+TRAIN_LOG_FIELDS = ("n", "episodes_ended", "mean_return", "max_return", "mean_step_reward", "status_nonzero",
+                    "policy_loss", "value_loss", "entropy", "nrec_mismatch", "best_return", "snapshot")
+_TRAIN_NPTR = 6 + len(LMPC_LOOP_STATE) + len(LMPC_COLLECT_STATE) + len(LMPC_COLLECT_POOL) + len(LMPC_LOOP_LOGS) \
+    + len(LMPC_COLLECT_LOGS) + len(LMPC_COLLECT_REC) + len(LMPC_TRAIN_ARRAYS)
+
+
+def _train_buffers(values):
+    """``struct dart_lmpc_train_buffers`` (pointers only, so an array of pointers has its layout) from addresses
+    (ints, 0 / None: NULL) in the struct's order."""
+    if len(values) != _TRAIN_NPTR:
+        raise DartMPCError(f"dart_lmpc_train_buffers has {_TRAIN_NPTR} pointers, got {len(values)}")
+    return (ctypes.c_void_p * _TRAIN_NPTR)(*[int(v) if v else None for v in values])
+
+
+def train_config(**over) -> TrainConfig:
+    """``dart_lmpc_train_config`` with the library's defaults, fields overridden by keyword."""
+    c = TrainConfig()
+    lib().dart_lmpc_train_config_default(ctypes.byref(c))
+    names = [f[0] for f in c._fields_]
+    for k, v in over.items():
+        if k not in names:
+            raise DartMPCError(f"TrainConfig has no field {k!r} (fields: {names})")
+        setattr(c, k, float(v) if k in ("gamma", "lam") else int(v))
+    return c
+
+
+def train_workspace_bytes(B, K, record_every, epochs, mini_batch_size):
+    """Bytes of the device workspace of ``LmpcSolver.train_dev``."""
+    b = int(lib().dart_lmpc_train_workspace_bytes(int(B), int(K), int(record_every), int(epochs), int(mini_batch_size)))
+    if b == 0:
+        raise DartMPCError(f"no training workspace for B = {B}, K = {K}, record_every = {record_every}, epochs = "
+                           f"{epochs}, mini_batch_size = {mini_batch_size} (K a positive multiple of record_every)")
+    return b
+
+
+def philox_dev(n, inputs, out, stream=0):
+    """dart_lmpc_philox_dev: Philox4x32-10 on ``inputs`` [n, 6] uint32 (counter[4], key[2]) into ``out`` [n, 4]
+    (device pointers)."""
+    _rc(lib().dart_lmpc_philox_dev(int(n), _vp(inputs), _vp(out), stream or None), "dart_lmpc_philox_dev")
+
+
+def noise_dev(seed, iteration, steps, B, noise_out, stream=0):
+    """dart_lmpc_noise_dev: the standard-normal draws [steps, B, 34] (fp32) of (seed, iteration) (device pointer)."""
+    _rc(lib().dart_lmpc_noise_dev(int(seed), int(iteration), int(steps), int(B), _vp(noise_out), stream or None),
+        "dart_lmpc_noise_dev")
+
+
+def noise(seed, iteration, steps, B):
+    """The exploration noise of (seed, iteration) from the device generator (dart_lmpc_noise, blocking): float32
+    [steps, B, 34], the array ``LmpcSolver.collect`` takes."""
+    out = np.empty((int(steps), int(B), 34), np.float32)
+    _rc(lib().dart_lmpc_noise(int(seed), int(iteration), int(steps), int(B), _ptr(out)), "dart_lmpc_noise")
+    return out
+
+
+def perms_dev(seed, iteration, epochs, n, perm_out, key_out=0, stream=0):
+    """dart_lmpc_perms_dev: the mini-batch permutations [epochs, n] (int32) of (seed, iteration); ``key_out``
+    [epochs, n] (uint32, optional) receives the raw keys (device pointers)."""
+    _rc(lib().dart_lmpc_perms_dev(int(seed), int(iteration), int(epochs), int(n), _vp(perm_out), _vp(key_out),
+                                  stream or None), "dart_lmpc_perms_dev")
+
+
+def perms(seed, iteration, epochs, n, want_keys=False):
+    """The permutations of (seed, iteration) from the device generator (dart_lmpc_perms, blocking): int32
+    [epochs, n], and with ``want_keys`` the uint32 keys they sort."""
+    out = np.empty((int(epochs), int(n)), np.int32)
+    keys = np.empty((int(epochs), int(n)), np.uint32) if want_keys else None
+    _rc(lib().dart_lmpc_perms(int(seed), int(iteration), int(epochs), int(n), _ptr(out), _ptr(keys)), "dart_lmpc_perms")
+    return (out, keys) if want_keys else out
+
+
+def mean_param_update_dev(pcfg, B, weights, history, model_params, current_k, mean_out=0, stream=0):
+    """dart_lmpc_mean_param_update_dev: the mean-based parameter write of rlmpc2.py:876-896 (device pointers)."""
+    _rc(lib().dart_lmpc_mean_param_update_dev(ctypes.byref(pcfg), int(B), _vp(weights), _vp(history), _vp(model_params),
+                                              _vp(current_k), _vp(mean_out), stream or None),
+        "dart_lmpc_mean_param_update_dev")
+
+
+def mean_param_update(pcfg, weights, history, model_params, current_k):
+    """The mean-based parameter write on host arrays (dart_lmpc_mean_param_update, blocking): ``model_params`` and
+    ``current_k`` [B, 34] (float64) are updated in place; returns the actor's mean, float32 [B, 34]."""
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w.size != ACTOR_NWEIGHTS:
+        raise DartMPCError(f"policy weights have {w.size} floats, not {ACTOR_NWEIGHTS}")
+    hist = np.ascontiguousarray(history, np.float32).reshape(-1, 520)
+    B = hist.shape[0]
+    _inplace(model_params, np.float64, 34 * B, "model_params"); _inplace(current_k, np.float64, 34 * B, "current_k")
+    mean = np.empty((B, 34), np.float32)
+    _rc(lib().dart_lmpc_mean_param_update(ctypes.byref(pcfg), B, _ptr(w), _ptr(hist), _ptr(model_params),
+                                          _ptr(current_k), _ptr(mean)), "dart_lmpc_mean_param_update")
+    return mean
 
 
 def critic_value_dev(n, critic, obs, value_out, stream=0):

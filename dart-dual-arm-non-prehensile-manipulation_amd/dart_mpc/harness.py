@@ -589,6 +589,77 @@ def lmpc_reward_step(rcfg, cs, x, target, control, raw, max_delta=0.02, action_s
     return reward, done
 
 
+def lmpc_mean_param_update(weights, history, model_params, pcfg=None):
+    """The mean-based parameter write after an update (:876-896) for B controllers, the batched numpy statement of
+    what lmpc_mean_update_kernel computes: the actor's mean on the current ``history`` [B, 520] (fp32; nothing of the
+    policy's state changes), k <- k_max sigmoid(logit(clamp(k / k_max, min_k / k_max, 1 - 1e-6)) + mean max_delta
+    action_scale) on fp32 tensors (:888-893), then the EMA and the tanh soft clip of write_params_to_shm (:606-616)
+    in fp64.  ``pcfg``: a ``dart_mpc.lmpc.PolicyConfig`` (default: the library's).  Returns (mean float32 [B, 34],
+    the new model_params float64 [B, 34], which the worker also takes as its current_k, :896)."""
+    if pcfg is None:
+        from .lmpc import policy_config
+        pcfg = policy_config()
+    mean, _ = lmpc_actor_mean(weights, np.asarray(history, np.float32).reshape(-1, 520))
+    prev = np.asarray(model_params, np.float64).reshape(-1, 34)
+    f32 = np.float32
+    kmax = f32(pcfg.k_max)
+    frac = np.clip(prev.astype(f32) / kmax, f32(pcfg.min_k / pcfg.k_max), f32(1.0) - f32(1e-6)).astype(f32)
+    z_prev = np.log(frac / (f32(1.0) - frac)).astype(f32)
+    z_new = (z_prev + mean * f32(pcfg.max_delta) * f32(pcfg.action_scale)).astype(f32)
+    k_new = (kmax * (f32(1.0) / (f32(1.0) + np.exp(-z_new).astype(f32)))).astype(f32)
+    smoothed = pcfg.smooth_alpha * k_new.astype(np.float64) + (1.0 - pcfg.smooth_alpha) * prev
+    lo, hi = pcfg.min_k, pcfg.k_max - pcfg.k_ceiling_margin
+    center, scale = 0.5 * (hi + lo), 0.5 * (hi - lo) - 1e-3
+    return mean, center + scale * np.tanh((smoothed - center) / scale)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 with the standard constants on broadcastable counter words (c0, c1, c2, c3) and key words
+    (k0, k1): uint32 [..., 4].  The numpy statement of the generator of csrc/lmpc_train.hip."""
+    u64, m = np.uint64, np.uint64(0xffffffff)
+    c = [np.asarray(x, u64) & m for x in counter]
+    k0, k1 = (np.asarray(x, u64) & m for x in key)
+    for _ in range(10):
+        p0, p1 = u64(0xD2511F53) * c[0], u64(0xCD9E8D57) * c[2]
+        c = [(p1 >> u64(32)) ^ c[1] ^ k0, p1 & m, (p0 >> u64(32)) ^ c[3] ^ k1, p0 & m]
+        k0, k1 = (k0 + u64(0x9E3779B9)) & m, (k1 + u64(0xBB67AE85)) & m
+    return np.stack([x.astype(np.uint32) for x in np.broadcast_arrays(*c)], axis=-1)
+
+
+def lmpc_train_words(seed, iteration, stream, epoch, n):
+    """The n 32-bit words of (seed, iteration, stream, epoch): element e is word e % 4 of block e / 4, key
+    (seed & 0xffffffff, seed >> 32), counter (block, iteration, stream, epoch); stream 0 = noise, 1 = permutations."""
+    seed = int(seed)
+    blocks = np.arange((int(n) + 3) // 4, dtype=np.uint64)
+    return philox4x32_10((blocks, int(iteration), int(stream), int(epoch)),
+                         (seed & 0xffffffff, (seed >> 32) & 0xffffffff)).reshape(-1)[:int(n)]
+
+
+def lmpc_train_noise(seed, iteration, steps, B, dtype=np.float64):
+    """The exploration noise of dart_lmpc_noise restated in numpy, [steps, B, 34] in ``dtype`` arithmetic: u =
+    ((word >> 9) + 0.5) 2^-23, words 0, 1 and 2, 3 of a block give one Box-Muller pair sqrt(-2 ln u0) (cos, sin)(2 pi
+    u1) each; a tail uses the leading words of its block."""
+    n = int(steps) * int(B) * 34
+    w = lmpc_train_words(seed, iteration, 0, 0, 4 * ((n + 3) // 4))
+    f = np.dtype(dtype).type
+    u = ((w >> np.uint32(9)).astype(dtype) + f(0.5)) * f(2.0 ** -23)
+    u0, u1 = u[0::2], u[1::2]
+    rad, ang = np.sqrt(f(-2.0) * np.log(u0)), f(2.0 * np.pi) * u1
+    z = np.stack([rad * np.cos(ang), rad * np.sin(ang)], axis=-1).astype(dtype)
+    return z.reshape(-1)[:n].reshape(int(steps), int(B), 34)
+
+
+def lmpc_train_perms(seed, iteration, epochs, n):
+    """The mini-batch permutations of dart_lmpc_perms restated in numpy: (perm int32 [epochs, n], keys uint32
+    [epochs, n]); a permutation is the argsort of (key, index)."""
+    keys = np.stack([lmpc_train_words(seed, iteration, 1, e, n) for e in range(int(epochs))]) if int(epochs) > 0 \
+        else np.zeros((0, int(n)), np.uint32)
+    idx = np.arange(int(n))
+    perm = np.stack([np.lexsort((idx, k)) for k in keys]).astype(np.int32) if int(epochs) > 0 \
+        else np.zeros((0, int(n)), np.int32)
+    return perm, keys
+
+
 def gae_numpy(nrec, rec_reward, rec_value, rec_done, last_value, gamma=0.99, lam=0.95):
     """compute_gae (:592-599) per instance over its first nrec[b] records [rec_rows, B], fp64: (adv, ret = adv +
     value), NaN in the rows an instance has not recorded."""

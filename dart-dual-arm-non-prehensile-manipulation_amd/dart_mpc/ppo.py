@@ -6,7 +6,11 @@ update as HIP kernels (csrc/lmpc_ppo.hip, ``_lib.ppo_update``) on the packed wei
 torch path is the reference the device path is tested against; ``make_perms`` gives both the same mini-batches.
 Experience comes from ``dart_lmpc_collect`` (harness.collect_lmpc) and ``_lib.gae``; ``pack_weights`` /
 ``load_weights`` and ``pack_adam`` / ``load_adam`` move the weights and Adam's state between the torch objects and
-the packed input-major arrays the kernels read.  The reference's ``.pth`` checkpoints are not loaded.
+the packed input-major arrays the kernels read.  ``train_device`` runs whole iterations -- noise, collection,
+GAE, permutations, update, the mean-based parameter write, log row and best-policy snapshot -- through
+``LmpcSolver.train`` (csrc/lmpc_train.hip) without the host in between.  ``save_checkpoint`` / ``load_checkpoint``
+keep a training state in one ``.npz`` of plain arrays (no pickle); its fields stand in for the reference's
+``best_agent.pth`` / ``latest_agent.pth``, which are not loaded.
 """
 from __future__ import annotations
 
@@ -183,3 +187,100 @@ def ppo_update(net, optimizer, batch, clip_eps=0.2, epochs=8, mini_batch_size=64
             count += 1
     stats /= max(count, 1)
     return dict(policy_loss=stats[0], value_loss=stats[1], entropy=stats[2])
+
+
+def train_device(solver, policy, target, plant_pvec, state, cstate, adam, adam_step, best, steps, iterations=1, it0=0,
+                 seed=0, rcfg=None, pool=None, prm=None, gamma=0.99, lam=0.95, mean_update=True, track_best=True,
+                 epochs=8, mini_batch_size=64, out=None, **hyper):
+    """``iterations`` complete PPO iterations of ``steps`` closed-loop steps on the device (``LmpcSolver.train``): the
+    exploration noise and the mini-batch permutations come from the device generator of (``seed``, iteration index
+    ``it0`` ..), nothing passes through the host between the steps of an iteration or between iterations.  Updated
+    in place: ``target``, ``plant_pvec``, ``state`` (``solver.loop_state``), ``cstate`` (``solver.collect_state``),
+    ``policy.weights`` / ``critic_weights`` / ``current_k``, ``adam`` [2, 77317], ``adam_step`` [1] and ``best`` =
+    dict(best_return float64 [1] starting at -inf, best_weights float32 [77317], best_iter int32 [1]).  ``hyper``
+    overrides fields of ``_lib.ppo_config``.  ``out`` (a dict, optional) receives the last iteration's ``logs``,
+    ``clogs`` and ``rec``.  Returns one dict per iteration with the keys of ``_lib.TRAIN_LOG_FIELDS``."""
+    from . import _lib
+    rcfg = rcfg if rcfg is not None else _lib.reward_config()
+    B, K = state["x"].shape[0], int(steps)
+    cfg = _lib.ppo_config(**dict(hyper, epochs=epochs, mini_batch_size=mini_batch_size))
+    tcfg = _lib.train_config(seed=seed, iterations=iterations, it0=it0, steps=K, gamma=gamma, lam=lam,
+                             mean_update=int(bool(mean_update)), track_best=int(bool(track_best)))
+    R = K // max(int(rcfg.record_every), 1)
+    logs, clogs = _lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, B), _lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, B)
+    rec = _lib.loop_logs(_lib.LMPC_COLLECT_REC, R, B)
+    train_log = np.full((int(iterations), _lib.TRAIN_LOG_COLS), np.nan)
+    solver.train(target, plant_pvec, state, cstate, logs, clogs, rec, policy, adam, adam_step, train_log,
+                 best["best_return"], best["best_weights"], best["best_iter"], cfg, tcfg, rcfg=rcfg, prm=prm, pool=pool)
+    if out is not None:
+        out.update(logs=logs, clogs=clogs, rec=rec, train_log=train_log)
+    return [dict(zip(_lib.TRAIN_LOG_FIELDS, (float(v) for v in row))) for row in train_log]
+
+
+def new_best():
+    """The best-policy state of a fresh training: best_return -inf, no weights, best_iter -1."""
+    return dict(best_return=np.array([-np.inf]), best_weights=np.zeros(77317, np.float32),
+                best_iter=np.array([-1], np.int32))
+
+
+# name -> (dtype, trailing shape; None: any) of a checkpoint's arrays
+CHECKPOINT_FIELDS = {
+    "actor": (np.float32, (39748,)), "critic": (np.float32, (37569,)), "adam": (np.float32, (2, 77317)),
+    "adam_step": (np.int32, (1,)), "best_weights": (np.float32, (77317,)), "best_return": (np.float64, (1,)),
+    "best_iter": (np.int32, (1,)), "iteration": (np.int64, (1,)), "obs_mean": (np.float64, (None, 52)),
+    "obs_M2": (np.float64, (None, 52)), "obs_count": (np.int32, (None,)), "history": (np.float32, (None, 520)),
+    "current_k": (np.float64, (None, 34)), "model_params": (np.float64, (None, 34)),
+}
+
+
+def save_checkpoint(path, actor, critic, adam, adam_step, best, iteration, obs_mean, obs_M2, obs_count, history,
+                    current_k, model_params):
+    """One ``.npz`` of plain arrays (``CHECKPOINT_FIELDS``; readable with ``allow_pickle=False``): the packed actor
+    and critic, Adam's state, the best-policy snapshot (``best`` as ``train_device`` takes it), the number of
+    iterations done and the policy's Welford state, history, ``current_k`` and ``model_params`` for B controllers.
+    Returns the path written (numpy appends ``.npz`` to a path without it)."""
+    from ._lib import DartMPCError
+    B = np.asarray(obs_count).reshape(-1).size
+    given = dict(actor=actor, critic=critic, adam=adam, adam_step=adam_step, best_weights=best["best_weights"],
+                 best_return=best["best_return"], best_iter=best["best_iter"], iteration=[int(iteration)],
+                 obs_mean=obs_mean, obs_M2=obs_M2, obs_count=obs_count, history=history, current_k=current_k,
+                 model_params=model_params)
+    arrays = {}
+    for name, (dt, shape) in CHECKPOINT_FIELDS.items():
+        want = tuple(B if d is None else d for d in shape)
+        a = np.asarray(given[name])
+        if a.size != int(np.prod(want)):
+            raise DartMPCError(f"checkpoint field {name!r} must have shape {want}, got {a.shape}")
+        arrays[name] = np.ascontiguousarray(a, dt).reshape(want)
+    path = str(path)
+    path = path if path.endswith(".npz") else path + ".npz"
+    with open(path, "wb") as fh:
+        np.savez(fh, **arrays)
+    return path
+
+
+def load_checkpoint(path):
+    """The arrays ``save_checkpoint`` wrote, as a dict name -> array (``allow_pickle=False``: a file that holds
+    pickled objects is refused).  A missing field, a wrong dtype or a wrong shape raises ``DartMPCError``."""
+    from ._lib import DartMPCError
+    try:
+        with np.load(str(path), allow_pickle=False) as z:
+            got = {name: z[name] for name in z.files}
+    except (ValueError, OSError, KeyError) as e:
+        raise DartMPCError(f"{path}: not a readable checkpoint ({e})") from e
+    out = {}
+    B = None
+    for name, (dt, shape) in CHECKPOINT_FIELDS.items():
+        if name not in got:
+            raise DartMPCError(f"{path}: checkpoint field {name!r} is missing")
+        a = got[name]
+        if a.dtype != np.dtype(dt) or a.ndim != len(shape):
+            raise DartMPCError(f"{path}: checkpoint field {name!r} must be {np.dtype(dt).name} with {len(shape)} axes")
+        for have, want in zip(a.shape, shape):
+            if want is None:
+                B = have if B is None else B
+                want = B
+            if have != want:
+                raise DartMPCError(f"{path}: checkpoint field {name!r} has shape {a.shape}")
+        out[name] = np.ascontiguousarray(a)
+    return out

@@ -739,6 +739,115 @@ int dart_lmpc_ppo_apply_dev(const dart_lmpc_ppo_config *cfg, const float *grad, 
 int dart_lmpc_critic_value_dev(int n, const float *critic, const float *obs, float *value_out, void *hip_stream);
 int dart_lmpc_critic_value(int n, const float *critic, const float *obs, float *value_out);
 
+/* Whole PPO training iterations of the LMPC policy on the device (added within ABI 8; csrc/lmpc_train.hip): the
+ * loop of RLMPC._rl_worker (rlmpc2.py:537-938) without the host between its steps.
+ *
+ * Random numbers.  One counter-based generator, Philox4x32-10 with the standard constants (multipliers 0xD2511F53,
+ * 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85), key (seed & 0xffffffff, seed >> 32), counter
+ * (c, iteration, stream, epoch); block c yields the four 32-bit words of elements 4c .. 4c+3.
+ *   noise (stream 0, epoch 0): noise_out [steps][B][34] fp32 in the layout dart_lmpc_collect_dev reads; flat element
+ *     e takes word e % 4 of block e / 4; a word r becomes u = ((r >> 9) + 0.5) 2^-23 (exact in fp32, never 0 or 1);
+ *     words 0, 1 give one Box-Muller pair sqrt(-2 ln u0) (cos, sin)(2 pi u1), words 2, 3 the second; a tail of 1 to 3
+ *     elements uses the leading words of its block.
+ *   permutations (stream 1): perm_out [epochs][n] int32; the key of position i in epoch e is word i % 4 of block
+ *     i / 4 with the epoch in the counter, and the permutation is the argsort of (key, i), ties broken on the index
+ *     (np.lexsort((arange(n), key))).  key_out [epochs][n] (nullable) receives the raw keys.
+ * dart_lmpc_philox_dev evaluates the generator on n given inputs in [n][6] = counter[4], key[2] into out [n][4]
+ * (the known answers of the Philox paper's reference implementation can be checked through it).
+ * The _dev entries take device pointers and are asynchronous on hip_stream; the host twins stage and block.
+ * Stateless (the HIP current device).  EINVAL: a negative size, a null pointer with a positive size. */
+int dart_lmpc_philox_dev(int n, const uint32_t *in, uint32_t *out, void *hip_stream);
+int dart_lmpc_noise_dev(uint64_t seed, int iteration, int steps, int B, float *noise_out, void *hip_stream);
+int dart_lmpc_noise(uint64_t seed, int iteration, int steps, int B, float *noise_out);
+int dart_lmpc_perms_dev(uint64_t seed, int iteration, int epochs, int n, int32_t *perm_out, uint32_t *key_out,
+                        void *hip_stream);
+int dart_lmpc_perms(uint64_t seed, int iteration, int epochs, int n, int32_t *perm_out, uint32_t *key_out);
+
+/* The mean-based parameter write after an update (rlmpc2.py:876-896) for B controllers: the actor on the current
+ * history [B][520] -- no Welford update, no history shift, zero noise (the action is the mean, in the policy
+ * kernel's accumulation order: its mean bit for bit), timestep untouched -- then the logit-space update (fp32), the
+ * EMA and the tanh soft clip (fp64) of the policy step, applied unconditionally into model_params [B][34], and
+ * current_k [B][34] <- model_params (:896).  mean_out [B][34] (fp32, nullable) receives the mean. */
+int dart_lmpc_mean_param_update_dev(const dart_lmpc_policy_config *cfg, int B, const float *weights,
+                                    const float *history, double *model_params, double *current_k,
+                                    float *mean_out, void *hip_stream);
+int dart_lmpc_mean_param_update(const dart_lmpc_policy_config *cfg, int B, const float *weights,
+                                const float *history, double *model_params, double *current_k, float *mean_out);
+
+typedef struct dart_lmpc_train_config {
+    uint64_t seed;                 /* 0: of the noise and the permutations */
+    int32_t iterations;            /* 1 */
+    int32_t it0;                   /* 0: index of the first iteration (calls chain: it0 = iterations done so far) */
+    int32_t steps;                 /* 256: closed-loop steps K per iteration; a multiple of record_every */
+    int32_t mean_update;           /* 1: the parameter write of :876-896 after every update */
+    int32_t track_best;            /* 1: the best-policy snapshot */
+    int32_t reserved;
+    double gamma;                  /* 0.99 */
+    double lam;                    /* 0.95 */
+} dart_lmpc_train_config;
+
+#define DART_LMPC_TRAIN_LOG_COLS 12
+
+/* The arrays of dart_lmpc_train(_dev): those of dart_lmpc_collect_dev in its order (weights, critic and current_k
+ * are in/out here), Adam's state of dart_lmpc_ppo_update_dev, and the training outputs.  The logs have `steps`
+ * rows and the records R = steps / record_every rows; after the call both hold the last iteration's values. */
+typedef struct dart_lmpc_train_buffers {
+    double *target; const double *prm; double *plant_pvec; double *current_k; float *weights; float *critic;
+    double *x, *tilt, *u_prev, *w, *obs_mean, *obs_M2; int32_t *obs_count; float *history; int32_t *timestep;
+    double *model_params;
+    double *prev_cmd, *control_seen; int32_t *ep_step; double *ep_return, *time_penalty; int32_t *episodes;
+    double *last_return; int32_t *last_steps, *nrec, *sticky;
+    const double *reset_x, *reset_target, *reset_pvec;
+    double *log_X, *log_U, *log_pos_error, *log_pvec, *log_loss; int32_t *log_status, *log_iters;
+    double *log_reward; int32_t *log_done; float *log_value, *log_logp;
+    float *rec_obs, *rec_action, *rec_logp, *rec_value; double *rec_reward; float *rec_done;
+    float *adam;                   /* [2][77317] */
+    int32_t *adam_step;            /* [1] */
+    double *train_log;             /* [iterations][12], written */
+    double *best_return;           /* [1] in/out, starts at -inf */
+    float *best_weights;           /* [77317] actor then critic, written at a snapshot */
+    int32_t *best_iter;            /* [1] written at a snapshot */
+    void *workspace;               /* dart_lmpc_train_workspace_bytes; device memory (NULL for the host entry) */
+} dart_lmpc_train_buffers;
+
+void dart_lmpc_train_config_default(dart_lmpc_train_config *cfg);
+
+/* Bytes of the workspace (noise, bootstrap values, advantages, returns, sample list, permutations, the update's
+ * statistics and its workspace); 0 for a bad shape (B < 1, record_every < 1, K < record_every, K not a multiple of
+ * record_every, epochs < 0, mini_batch_size outside 1 .. 1024). */
+size_t dart_lmpc_train_workspace_bytes(int B, int K, int record_every, int epochs, int mini_batch_size);
+
+/* Enqueues cfg->iterations complete PPO iterations on one stream (NULL: the handle's), plain launches in stream
+ * order, no host work, no host random numbers and no staging between them.  For it = it0 .. it0+iterations-1:
+ *   1. nrec <- 0; the noise of (seed, it) into the workspace;
+ *   2. dart_lmpc_collect_dev with k0 = 0, steps = log_rows = K and the weights as they are now;
+ *   3. dart_lmpc_critic_value_dev on history: the bootstrap value (:776-779);
+ *   4. dart_lmpc_gae_dev (gamma, lam);
+ *   5. the sample list 0 .. n-1, n = R B with R = K / record_every records per instance (K % record_every != 0 is
+ *      DART_MPC_EINVAL: n must be known on the host);
+ *   6. the permutations of (seed, it), then dart_lmpc_ppo_update_dev on weights, critic, adam, adam_step in place;
+ *   7. with mean_update: dart_lmpc_mean_param_update_dev (current_k is in/out);
+ *   8. row it - it0 of train_log, fp64, fixed-order sums: n; episodes ended in this iteration; mean and maximum of
+ *      last_return over the instances whose episodes advanced (NaN if none); mean step reward over K x B; share of
+ *      solves with status != 0; policy loss, value loss, entropy (the update's means); the number of instances with
+ *      nrec[b] != R; best_return after this iteration; 1 if a snapshot was taken.  With track_best, a maximum above
+ *      best_return replaces it, copies actor and critic (after this iteration's update) into best_weights and stores
+ *      it in best_iter.  (The reference compares every episode's return at its end, :918-922; this entry compares
+ *      once per iteration.)
+ * Two calls of i1 and i2 iterations (it0 = 0, then i1) give bit for bit what one call of i1 + i2 gives. */
+int dart_lmpc_train_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                        const dart_lmpc_reward_config *rcfg, const dart_lmpc_ppo_config *ppo,
+                        const dart_lmpc_train_config *cfg, int B, int reset_rows,
+                        const dart_lmpc_train_buffers *buf, void *hip_stream);
+
+/* Host pointers: state, weights, Adam's state and the reset pool are staged in once, all iterations run, and the
+ * results are staged out once (of logs and records what the last iteration wrote); blocks.  Instances whose
+ * timestep differ are DART_MPC_EINVAL before any device work (they are the only way to nrec[b] != R). */
+int dart_lmpc_train(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                    const dart_lmpc_reward_config *rcfg, const dart_lmpc_ppo_config *ppo,
+                    const dart_lmpc_train_config *cfg, int B, int reset_rows,
+                    const dart_lmpc_train_buffers *buf, void *hip_stream);
+
 int dart_mpc_sync(dart_mpc_handle *h);
 
 const char *dart_mpc_last_error(const dart_mpc_handle *h);

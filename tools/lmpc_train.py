@@ -5,9 +5,16 @@ clipped-surrogate update, then the new weights go into the next collect.  --upda
 recorded output stays comparable) runs dart_mpc.ppo.ppo_update and re-packs the weights; --update device runs
 dart_mpc.ppo.ppo_update_device (the HIP kernels of csrc/lmpc_ppo.hip) on the packed weights in place, with the
 bootstrap value from _lib.critic_value: the records, the GAE outputs and the weights never pass through torch.
+--update resident runs the iterations through dart_mpc.ppo.train_device (LmpcSolver.train, csrc/lmpc_train.hip): one
+call enqueues all of them -- the noise and the permutations come from the device generator, and the mean-based
+parameter write and the best-policy snapshot of the reference loop are part of every iteration -- and prints the
+same line per iteration from the log rows; with it --checkpoint PATH writes the training state (ppo.save_checkpoint,
+one .npz without pickle) at the end and --resume PATH continues from one (the loop state and the plants start
+afresh).
 The loop state, the collection state, the targets and the plants carry over from iteration to iteration.
 Prints the mean return of the episodes that ended, per iteration.
-Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps] [--update device|torch]
+Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps] [--update device|torch|resident]
+                                  [--checkpoint PATH] [--resume PATH] [--seed S]
 """
 import os
 import sys
@@ -27,8 +34,22 @@ if "--update" in argv:
     i = argv.index("--update")
     update = argv[i + 1]
     del argv[i:i + 2]
-if update not in ("device", "torch"):
-    sys.exit("--update takes device or torch")
+if update not in ("device", "torch", "resident"):
+    sys.exit("--update takes device, torch or resident")
+
+
+def _option(name):
+    if name not in argv:
+        return None
+    i = argv.index(name)
+    v = argv[i + 1]
+    del argv[i:i + 2]
+    return v
+
+
+ckpt_out, ckpt_in, seed = _option("--checkpoint"), _option("--resume"), int(_option("--seed") or 0)
+if (ckpt_out or ckpt_in) and update != "resident":
+    sys.exit("--checkpoint and --resume go with --update resident")
 iters = int(argv[0]) if len(argv) > 0 else 5
 B = int(argv[1]) if len(argv) > 1 else 72
 K = int(argv[2]) if len(argv) > 2 else 256
@@ -55,7 +76,45 @@ policy = LmpcPolicy(B, weights=actor, critic_weights=critic)
 solver = _lib.LmpcSolver(N=N, B_max=B)
 state = solver.loop_state(D["state"][:B], policy=policy)
 cs = solver.collect_state(np.zeros((B, 2)))
+
+
+def resident():
+    """All iterations in one call of the training entry; the line per iteration comes from its log rows."""
+    if K % int(rcfg.record_every):
+        sys.exit(f"--update resident needs K to be a multiple of record_every = {int(rcfg.record_every)}")
+    best, it0 = ppo.new_best(), 0
+    if ckpt_in:
+        c = ppo.load_checkpoint(ckpt_in)
+        if c["obs_count"].shape[0] != B:
+            sys.exit(f"{ckpt_in} holds {c['obs_count'].shape[0]} controllers, this run has {B}")
+        policy.weights[:], policy.critic_weights[:] = c["actor"], c["critic"]
+        adam[:], adam_step[:] = c["adam"], c["adam_step"]
+        best = {k: c[k].copy() for k in best}
+        it0 = int(c["iteration"][0])
+        policy.current_k[:] = c["current_k"]
+        for k in ("obs_mean", "obs_M2", "obs_count", "history", "model_params"):
+            state[k][:] = c[k]
+    rows = ppo.train_device(solver, policy, target, pvec, state, cs, adam, adam_step, best, K, iterations=iters,
+                            it0=it0, seed=seed, rcfg=rcfg, pool=pool, gamma=GAMMA, lam=LAM, epochs=8,
+                            mini_batch_size=64, clip_eps=0.2, vf_coef=0.25, ent_coef=0.01)
+    for j, r in enumerate(rows):
+        print(f"iter {it0 + j}: samples {int(r['n'])}, episodes ended {int(r['episodes_ended'])}, "
+              f"mean last return {r['mean_return']:.2f}, mean step reward {r['mean_step_reward']:.3f}, "
+              f"status != 0: {r['status_nonzero']:.4f}, policy loss {r['policy_loss']:.4f}, "
+              f"value loss {r['value_loss']:.4f}, entropy {r['entropy']:.3f}, best return {r['best_return']:.2f}"
+              f"{' (snapshot)' if r['snapshot'] else ''}", flush=True)
+    if ckpt_out:
+        path = ppo.save_checkpoint(ckpt_out, policy.weights, policy.critic_weights, adam, adam_step, best, it0 + iters,
+                                   state["obs_mean"], state["obs_M2"], state["obs_count"], state["history"],
+                                   policy.current_k, state["model_params"])
+        print(f"checkpoint: {path} (iteration {it0 + iters}, best return {float(best['best_return'][0]):.2f} "
+              f"at iteration {int(best['best_iter'][0])})", flush=True)
+
+
 try:
+    if update == "resident":
+        resident()
+        iters = 0
     for it in range(iters):
         if update == "torch":
             policy.weights, policy.critic_weights = ppo.pack_weights(net)

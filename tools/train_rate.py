@@ -1,0 +1,185 @@
+"""Time of one PPO training iteration of the LMPC policy: the device-resident iteration (LmpcSolver.train_dev /
+LmpcSolver.train, csrc/lmpc_train.hip) against the host-sequenced loop, the body of tools/lmpc_train.py --update
+device unchanged: numpy noise staged to the device, the blocking host entries collect, critic_value, gae and
+ppo_update, the sample list in numpy and the permutations from torch.randperm.
+Contenders: host_sequenced; resident_dev (train_dev with one iteration on device-resident arrays, then a
+synchronise); resident_host (LmpcSolver.train with one iteration: state, weights and Adam's state staged in, logs and
+records staged out); resident_host_x4 (one LmpcSolver.train call of four iterations, per iteration).
+Shapes: B = 72, K = 256 (tools/lmpc_train.py's, 2304 samples) and B = 18, K = 512 (1152 samples); episodes of 64
+steps, 8 epochs of mini-batches of 64, N = 30.
+Protocol of tools/rollout_rate.py: the contenders alternate in one process, one warm-up each, then five rounds each;
+a host clock around work that ends in a synchronise; medians with the min-to-max spread.  Every contender carries its
+own training state from round to round, so the rounds are consecutive iterations of a training run.
+Usage: python tools/train_rate.py [out.json] [rounds]
+       python tools/train_rate.py --once B K [iterations]   (resident iterations and nothing else: for a kernel trace)
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "dart-dual-arm-non-prehensile-manipulation_amd"))
+import torch  # noqa: E402
+from dart_mpc import _lib, harness, ppo  # noqa: E402
+from dart_mpc.lmpc import LmpcPolicy  # noqa: E402
+from dart_mpc.workload import lmpc_batch  # noqa: E402
+
+GAMMA, LAM, N, EP_STEPS, EPOCHS, MB = 0.99, 0.95, 30, 64, 8, 64
+HYPER = dict(clip_eps=0.2, vf_coef=0.25, ent_coef=0.01)
+SHAPES = ((72, 256), (18, 512))
+
+
+class Run:
+    """The training state of one contender: tools/lmpc_train.py's setup."""
+
+    def __init__(self, B, K):
+        self.B, self.K = B, K
+        seeds = -(-B // 18)
+        D = lmpc_batch(seeds)
+        self.target, self.pvec = np.ascontiguousarray(D["target"][:B]), np.ascontiguousarray(D["pvec"][:B])
+        P = [lmpc_batch(seeds, seed0=100 + r) for r in range(4)]
+        self.pool = {"reset_x": np.ascontiguousarray(np.stack([p["state"][:B] for p in P])),
+                     "reset_target": np.ascontiguousarray(np.stack([p["target"][:B] for p in P])),
+                     "reset_pvec": np.ascontiguousarray(np.stack([p["pvec"][:B] for p in P]))}
+        self.rcfg = _lib.reward_config(max_episode_steps=EP_STEPS)
+        self.every = int(self.rcfg.record_every)
+        torch.manual_seed(0)
+        net = ppo.PolicyNet()
+        self.gen = torch.Generator().manual_seed(0)
+        actor, critic = ppo.pack_weights(net)
+        self.adam, self.adam_step = np.zeros((2, _lib.PPO_NPARAMS), np.float32), np.zeros(1, np.int32)
+        self.policy = LmpcPolicy(B, weights=actor, critic_weights=critic)
+        self.solver = _lib.LmpcSolver(N=N, B_max=B)
+        self.state = self.solver.loop_state(D["state"][:B], policy=self.policy)
+        self.cs = self.solver.collect_state(np.zeros((B, 2)))
+        self.best = ppo.new_best()
+        self.it = 0
+        self.dev = None
+
+    def close(self):
+        self.solver.close()
+
+    # -- the parent's loop body (tools/lmpc_train.py --update device) ------------------------------------------------
+    def host_sequenced(self):
+        B, K, rcfg, policy, state, cs = self.B, self.K, self.rcfg, self.policy, self.state, self.cs
+        rec_rows = K // self.every + 1
+        lg, clg = _lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, B), _lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, B)
+        rec = _lib.loop_logs(_lib.LMPC_COLLECT_REC, rec_rows, B)
+        cs["nrec"][:] = 0
+        noise = harness.lmpc_noise(1000 + self.it, K, B)
+        self.solver.collect(0, K, self.target, self.pvec, state, cs, lg, clg, rec, policy, rcfg=rcfg, noise=noise,
+                            pool=self.pool)
+        last_value = _lib.critic_value(policy.critic_weights, state["history"])
+        adv, ret = _lib.gae(cs["nrec"], rec["rec_reward"], rec["rec_value"], rec["rec_done"], last_value, GAMMA, LAM)
+        m = np.arange(rec_rows)[:, None] < cs["nrec"][None]
+        sample = np.flatnonzero(m.reshape(-1)).astype(np.int32)
+        ppo.ppo_update_device(policy.weights, policy.critic_weights, self.adam, self.adam_step, rec, sample, adv, ret,
+                              ppo.make_perms(sample.size, EPOCHS, self.gen), mini_batch_size=MB, **HYPER)
+        self.it += 1
+
+    # -- the resident iteration through the host entry ----------------------------------------------------------------
+    def resident_host(self, iterations=1):
+        ppo.train_device(self.solver, self.policy, self.target, self.pvec, self.state, self.cs, self.adam,
+                         self.adam_step, self.best, self.K, iterations=iterations, it0=self.it, seed=0, rcfg=self.rcfg,
+                         pool=self.pool, gamma=GAMMA, lam=LAM, epochs=EPOCHS, mini_batch_size=MB, **HYPER)
+        self.it += iterations
+
+    # -- the resident iteration on device-resident arrays -------------------------------------------------------------
+    def to_device(self):
+        B, K = self.B, self.K
+        R = K // self.every
+        up = lambda d: {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
+        self.dev = dict(
+            c=up(dict(target=self.target, prm=np.tile(_lib.LMPC_PRM_DEFAULT, (B, 1)), pvec=self.pvec,
+                      current_k=self.policy.current_k, weights=self.policy.weights, critic=self.policy.critic_weights)),
+            st=up(self.state), cs=up(self.cs), pool=up(self.pool),
+            lg=up(_lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, B)), clg=up(_lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, B)),
+            rec=up(_lib.loop_logs(_lib.LMPC_COLLECT_REC, R, B)),
+            tr=up(dict(adam=self.adam, adam_step=self.adam_step, train_log=np.full((8, 12), np.nan),
+                       best_return=self.best["best_return"], best_weights=self.best["best_weights"],
+                       best_iter=self.best["best_iter"])))
+        self.dev["tr"]["workspace"] = torch.zeros(_lib.train_workspace_bytes(B, K, self.every, EPOCHS, MB),
+                                                  dtype=torch.uint8, device="cuda")
+        self.cfg = _lib.ppo_config(epochs=EPOCHS, mini_batch_size=MB, **HYPER)
+        torch.cuda.synchronize()
+
+    def resident_dev(self, iterations=1):
+        d = self.dev
+        p = lambda g: {k: v.data_ptr() for k, v in d[g].items()}
+        tcfg = _lib.train_config(seed=0, iterations=iterations, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
+        self.solver.train_dev(self.B, 4, d["c"]["target"].data_ptr(), d["c"]["prm"].data_ptr(), d["c"]["pvec"].data_ptr(),
+                              d["c"]["current_k"].data_ptr(), d["c"]["weights"].data_ptr(), d["c"]["critic"].data_ptr(),
+                              p("st"), p("cs"), p("lg"), p("clg"), p("rec"), p("tr"), self.policy.cfg, self.rcfg,
+                              self.cfg, tcfg, pool=p("pool"))
+        self.solver.sync()
+        self.it += iterations
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def measure(B, K, rounds):
+    runs = {name: Run(B, K) for name in ("host_sequenced", "resident_dev", "resident_host", "resident_host_x4")}
+    runs["resident_dev"].to_device()
+    calls = {"host_sequenced": (runs["host_sequenced"].host_sequenced, 1),
+             "resident_dev": (runs["resident_dev"].resident_dev, 1),
+             "resident_host": (runs["resident_host"].resident_host, 1),
+             "resident_host_x4": (lambda: runs["resident_host_x4"].resident_host(4), 4)}
+    times = {name: [] for name in calls}
+    try:
+        for r in range(rounds + 1):                 # round 0 is the warm-up
+            for name, (fn, per) in calls.items():
+                ms = timed(fn) / per
+                if r:
+                    times[name].append(ms)
+    finally:
+        for run in runs.values():
+            run.close()
+    out = {"B": B, "K": K, "samples": B * (K // 8), "rounds": rounds}
+    for name, t in times.items():
+        out[name] = {"median_ms": float(np.median(t)), "min_ms": float(min(t)), "max_ms": float(max(t)), "all_ms": t}
+    base = out["host_sequenced"]
+    for name in ("resident_dev", "resident_host", "resident_host_x4"):
+        o = out[name]
+        out[name]["speedup_vs_host_sequenced"] = {"median": base["median_ms"] / o["median_ms"],
+                                                  "low": base["min_ms"] / o["max_ms"],
+                                                  "high": base["max_ms"] / o["min_ms"]}
+    return out
+
+
+def main():
+    argv = sys.argv[1:]
+    if argv and argv[0] == "--once":
+        B, K = int(argv[1]), int(argv[2])
+        run = Run(B, K)
+        try:
+            run.to_device()
+            run.resident_dev(int(argv[3]) if len(argv) > 3 else 1)
+        finally:
+            run.close()
+        return
+    path = argv[0] if argv else os.path.join(ROOT, "profiles", "collect", "train_rate.json")
+    rounds = int(argv[1]) if len(argv) > 1 else 5
+    res = {"tool": "tools/train_rate.py", "device": torch.cuda.get_device_name(0), "N": N, "episode_steps": EP_STEPS,
+           "epochs": EPOCHS, "mini_batch_size": MB, "shapes": []}
+    for B, K in SHAPES:
+        r = measure(B, K, rounds)
+        res["shapes"].append(r)
+        print(f"B = {B}, K = {K}: " + ", ".join(
+            f"{n} {r[n]['median_ms']:.1f} ms ({r[n]['min_ms']:.1f}-{r[n]['max_ms']:.1f})"
+            for n in ("host_sequenced", "resident_dev", "resident_host", "resident_host_x4")), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps({n: res["shapes"][0][n]["speedup_vs_host_sequenced"] for n in
+                      ("resident_dev", "resident_host", "resident_host_x4")}))
+
+
+if __name__ == "__main__":
+    main()
