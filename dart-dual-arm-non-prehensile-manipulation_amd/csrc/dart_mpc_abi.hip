@@ -2339,11 +2339,13 @@ hipError_t launch_noise(uint64_t seed, int iteration, int steps, int B, float* o
     return dartmpc_launch_lmpc_noise(&a, s);
 }
 
+// limit = n: the permutations; limit = m < n: their first m entries (rows of m)
 hipError_t launch_perms(uint64_t seed, int iteration, int epochs, int n, int32_t* perm, uint32_t* key_out,
-                        hipStream_t s) {
+                        hipStream_t s, uint32_t rng_stream = dartmpc::kStreamPerm, int limit = -1) {
     dartmpc::PermArgs a;
-    a.n = n; a.epochs = epochs;
+    a.n = n; a.epochs = epochs; a.limit = limit < 0 ? n : limit;
     a.key0 = (uint32_t)(seed & 0xffffffffu); a.key1 = (uint32_t)(seed >> 32); a.iteration = (uint32_t)iteration;
+    a.stream = rng_stream;
     a.perm = perm; a.key_out = key_out;
     return dartmpc_launch_lmpc_perms(&a, s);
 }
@@ -2462,6 +2464,194 @@ int dart_lmpc_mean_param_update(const dart_lmpc_policy_config* cfg, int B, const
     return DART_MPC_OK;
 }
 
+// ---- the global-buffer update (rlmpc2.py:823-874): choice, record gather, GAE over one sequence ----------------
+
+int dart_lmpc_perms_stream_dev(uint64_t seed, int iteration, int rng_stream, int epochs, int n, int32_t* perm_out,
+                               uint32_t* key_out, void* stream) {
+    if (iteration < 0 || epochs < 0 || n < 0 || rng_stream < 0) return DART_MPC_EINVAL;
+    if (epochs == 0 || n == 0) return DART_MPC_OK;
+    if (!perm_out) return DART_MPC_EINVAL;
+    return launch_perms(seed, iteration, epochs, n, perm_out, key_out, (hipStream_t)stream, (uint32_t)rng_stream) ==
+                   hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_choice_dev(uint64_t seed, int iteration, int n, int m, int32_t* choice_out, void* stream) {
+    if (iteration < 0 || m < 1 || m > n || !choice_out) return DART_MPC_EINVAL;
+    return launch_perms(seed, iteration, 1, n, choice_out, nullptr, (hipStream_t)stream, dartmpc::kStreamChoice, m) ==
+                   hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_choice(uint64_t seed, int iteration, int n, int m, int32_t* choice_out) {
+    if (iteration < 0 || m < 1 || m > n || !choice_out) return DART_MPC_EINVAL;
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    if (S.reserve(0, sizeof(int32_t) * (size_t)m + 256) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    int32_t* d = S.out<int32_t>((size_t)m);
+    hipError_t e = launch_perms(seed, iteration, 1, n, d, nullptr, D->stream, dartmpc::kStreamChoice, m);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.take(choice_out, d, (size_t)m);
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_global_rows(int n, int32_t* m_out, int32_t* G_out) {
+    if (n < 1 || !m_out || !G_out) return DART_MPC_EINVAL;
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    *m_out = m; *G_out = G;
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_global_fill_after(int n, int fill, int iterations) {
+    if (n < 1 || iterations < 0 || fill < 0 || fill >= n) return DART_MPC_EINVAL;
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    if (fill % m != 0) return DART_MPC_EINVAL;
+    const long long period = G / m;
+    return (int)(((long long)(fill / m) + iterations) % period) * m;
+}
+
+size_t dart_lmpc_global_workspace_bytes(int n, int epochs, int mini_batch_size) {
+    if (n < 1 || epochs < 0 || mini_batch_size < 1 || mini_batch_size > dartmpc::kPpoMaxBatch) return 0;
+    if ((long long)n + n / 4 > 0x7fffffffLL) return 0;
+    return dartmpc::global_workspace(n, epochs, mini_batch_size).bytes;
+}
+
+namespace {
+
+int global_append_check(const dart_lmpc_global_buffer* g, int m, int n, int rec_total, const void* sample,
+                        const void* choice, const void* rec_obs, const void* rec_action, const void* rec_logp,
+                        const void* rec_value, const void* rec_reward, const void* rec_done) {
+    if (!g || m < 1 || n < 1 || rec_total < 1 || g->fill < 0 || (long long)g->fill + m > g->capacity)
+        return DART_MPC_EINVAL;
+    if (!sample || !choice || !rec_obs || !rec_action || !rec_logp || !rec_value || !rec_reward || !rec_done ||
+        !g->obs || !g->action || !g->logp || !g->value || !g->reward || !g->done) return DART_MPC_EINVAL;
+    return DART_MPC_OK;
+}
+
+hipError_t launch_global_append(const dart_lmpc_global_buffer* g, int fill, int m, int n, int rec_total,
+                                const int32_t* sample, const int32_t* choice, const float* rec_obs,
+                                const float* rec_action, const float* rec_logp, const float* rec_value,
+                                const double* rec_reward, const float* rec_done, hipStream_t s) {
+    dartmpc::GbufAppendArgs a;
+    a.m = m; a.n = n; a.fill = fill; a.rec_total = rec_total; a.sample = sample; a.choice = choice;
+    a.rec_obs = rec_obs; a.rec_action = rec_action; a.rec_logp = rec_logp; a.rec_value = rec_value;
+    a.rec_reward = rec_reward; a.rec_done = rec_done;
+    a.obs = g->obs; a.action = g->action; a.logp = g->logp; a.value = g->value; a.reward = g->reward; a.done = g->done;
+    return dartmpc_launch_lmpc_gbuf_append(&a, s);
+}
+
+hipError_t launch_gae_seq(int G, double gamma, double lam, const double* reward, const float* value,
+                          const float* done, const float* last_value, double* adv, double* ret, hipStream_t s) {
+    dartmpc::GaeSeqArgs a;
+    a.G = G; a.gamma = gamma; a.lam = lam; a.reward = reward; a.value = value; a.done = done;
+    a.last_value = last_value; a.adv = adv; a.ret = ret;
+    return dartmpc_launch_lmpc_gae_seq(&a, s);
+}
+
+}  // namespace
+
+int dart_lmpc_global_append_dev(const dart_lmpc_global_buffer* g, int m, int n, int rec_total, const int32_t* sample,
+                                const int32_t* choice, const float* rec_obs, const float* rec_action,
+                                const float* rec_logp, const float* rec_value, const double* rec_reward,
+                                const float* rec_done, void* stream) {
+    if (int rc = global_append_check(g, m, n, rec_total, sample, choice, rec_obs, rec_action, rec_logp, rec_value,
+                                     rec_reward, rec_done)) return rc;
+    if (!aligned16(rec_obs) || !aligned16(g->obs)) return DART_MPC_EINVAL;    // (the rows move in 16-byte pieces)
+    return launch_global_append(g, g->fill, m, n, rec_total, sample, choice, rec_obs, rec_action, rec_logp, rec_value,
+                                rec_reward, rec_done, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_global_append(const dart_lmpc_global_buffer* g, int m, int n, int rec_total, const int32_t* sample,
+                            const int32_t* choice, const float* rec_obs, const float* rec_action,
+                            const float* rec_logp, const float* rec_value, const double* rec_reward,
+                            const float* rec_done) {
+    if (int rc = global_append_check(g, m, n, rec_total, sample, choice, rec_obs, rec_action, rec_logp, rec_value,
+                                     rec_reward, rec_done)) return rc;
+    for (int j = 0; j < m; ++j)
+        if (choice[j] < 0 || choice[j] >= n) return DART_MPC_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (sample[i] < 0 || sample[i] >= rec_total) return DART_MPC_EINVAL;
+    // only the m drawn records travel: they are compacted on the way up (sample and choice become the identity)
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    const size_t M = (size_t)m, F = sizeof(float);
+    const size_t row = F * (520 + 34 + 3) + sizeof(double);
+    if (S.reserve(2 * (M * row + 8 * 256) + sizeof(int32_t) * M + 256, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    auto slot = [&](size_t bytes) { char* p = S.hin + S.in_off; S.in_off += HostStage::al(bytes); return p; };
+    auto dev_of = [&](const void* hp) { return S.din + ((const char*)hp - S.hin); };
+    auto gather = [&](auto* dst, const auto* src, size_t width) {
+        for (size_t j = 0; j < M; ++j)
+            std::memcpy(dst + j * width, src + (size_t)sample[choice[j]] * width, sizeof(*dst) * width);
+    };
+    int32_t* h_id = (int32_t*)slot(sizeof(int32_t) * M);
+    for (int j = 0; j < m; ++j) h_id[j] = j;
+    float* h_obs = (float*)slot(F * M * 520); gather(h_obs, rec_obs, 520);
+    float* h_act = (float*)slot(F * M * 34); gather(h_act, rec_action, 34);
+    float* h_lp = (float*)slot(F * M); gather(h_lp, rec_logp, 1);
+    float* h_vl = (float*)slot(F * M); gather(h_vl, rec_value, 1);
+    double* h_rw = (double*)slot(sizeof(double) * M); gather(h_rw, rec_reward, 1);
+    float* h_dn = (float*)slot(F * M); gather(h_dn, rec_done, 1);
+    const size_t f0 = (size_t)g->fill;
+    dart_lmpc_global_buffer d = *g;                 // rows fill .. fill + m - 1 alone, as rows 0 .. m - 1
+    d.obs = S.inout(g->obs + f0 * 520, M * 520); d.action = S.inout(g->action + f0 * 34, M * 34);
+    d.logp = S.inout(g->logp + f0, M); d.value = S.inout(g->value + f0, M);
+    d.reward = S.inout(g->reward + f0, M); d.done = S.inout(g->done + f0, M);
+    hipError_t e = S.upload(D->stream);
+    if (e == hipSuccess)
+        e = launch_global_append(&d, 0, m, m, m, (const int32_t*)dev_of(h_id), (const int32_t*)dev_of(h_id),
+                                 (const float*)dev_of(h_obs), (const float*)dev_of(h_act), (const float*)dev_of(h_lp),
+                                 (const float*)dev_of(h_vl), (const double*)dev_of(h_rw), (const float*)dev_of(h_dn),
+                                 D->stream);
+    if (e == hipSuccess) e = S.download_inout(D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.finish_inout();
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_gae_seq_dev(int G, double gamma, double lam, const double* reward, const float* value,
+                          const float* done, const float* last_value, double* adv, double* ret, void* stream) {
+    if (G < 0) return DART_MPC_EINVAL;
+    if (G == 0) return DART_MPC_OK;
+    if (!reward || !value || !done || !last_value || !adv || !ret) return DART_MPC_EINVAL;
+    return launch_gae_seq(G, gamma, lam, reward, value, done, last_value, adv, ret, (hipStream_t)stream) == hipSuccess
+               ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_gae_seq(int G, double gamma, double lam, const double* reward, const float* value, const float* done,
+                      const float* last_value, double* adv, double* ret) {
+    if (G < 0) return DART_MPC_EINVAL;
+    if (G == 0) return DART_MPC_OK;
+    if (!reward || !value || !done || !last_value || !adv || !ret) return DART_MPC_EINVAL;
+    DeviceStage* D = nullptr;
+    if (device_stage(&D) != hipSuccess) return DART_MPC_EHIP;
+    std::lock_guard<std::mutex> lock(D->mu);
+    HostStage& S = D->st;
+    const size_t n = (size_t)G;
+    if (S.reserve(sizeof(double) * 3 * n + sizeof(float) * (2 * n + 1) + 8 * 256, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    const double* d_rw = S.in(reward, n);
+    const float* d_vl = S.in(value, n);
+    const float* d_dn = S.in(done, n);
+    const float* d_lv = S.in(last_value, (size_t)1);
+    double* d_adv = S.inout(adv, n);
+    double* d_ret = S.inout(ret, n);
+    hipError_t e = S.upload(D->stream);
+    if (e == hipSuccess) e = launch_gae_seq(G, gamma, lam, d_rw, d_vl, d_dn, d_lv, d_adv, d_ret, D->stream);
+    if (e == hipSuccess) e = S.download_inout(D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.finish_inout();
+    return DART_MPC_OK;
+}
+
 void dart_lmpc_train_config_default(dart_lmpc_train_config* c) {
     if (!c) return;
     c->seed = 0; c->iterations = 1; c->it0 = 0; c->steps = 256; c->mean_update = 1; c->track_best = 1;
@@ -2495,16 +2685,32 @@ int train_check(dart_mpc_handle* h, const dart_lmpc_reward_config* rcfg, const d
     return DART_MPC_OK;
 }
 
-}  // namespace
+// the checks of the global buffer that need neither the device nor the arrays' contents (n = R B samples)
+int global_check(dart_mpc_handle* h, const dart_lmpc_global_buffer* g, int n, bool dev) {
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    if (g->fill < 0 || g->fill >= n || g->fill % m != 0)
+        return fail(h, DART_MPC_EINVAL, "global buffer: fill must be a multiple of m in [0, n)");
+    if (g->capacity < G) return fail(h, DART_MPC_EINVAL, "global buffer: capacity below G");
+    if (any_null({g->obs, g->action, g->logp, g->value, g->reward, g->done, g->global_log}) || (dev && !g->workspace))
+        return fail(h, DART_MPC_EINVAL, "null pointer (global buffer)");
+    if (dev && !aligned16(g->obs)) return fail(h, DART_MPC_EINVAL, "global buffer: obs is not 16-byte aligned");
+    return DART_MPC_OK;
+}
 
-int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
-                        const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
-                        const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
-                        void* stream) {
+// dart_lmpc_train_dev (g == nullptr) and dart_lmpc_train_global_dev
+int train_dev_impl(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                   const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                   const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                   const dart_lmpc_global_buffer* g, void* stream) {
     if (!h) return DART_MPC_EINVAL;
     std::unique_lock<std::recursive_mutex> lock_(h->mu);
     if (int rc = train_check(h, rcfg, ppo, cfg, B, p, true)) return rc;
     const int K = cfg->steps, R = K / rcfg->record_every, n = R * B, mb = ppo->mini_batch_size;
+    if (g) {
+        if (int rc = global_check(h, g, n, true)) return rc;
+        if (!aligned16(p->rec_obs)) return fail(h, DART_MPC_EINVAL, "rec_obs is not 16-byte aligned");
+    }
     void* s = stream ? stream : (void*)h->stream;
     auto collect = [&](int steps, const float* noise) {
         return dart_lmpc_collect_dev(
@@ -2531,6 +2737,19 @@ int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, cons
     double* stats = (double*)(ws + L.stats);
     int32_t* ep0 = (int32_t*)(ws + L.ep0);
     hipStream_t hs = (hipStream_t)s;
+    // the global update's sizes, workspace and running fill (the host knows every launch from n and g->fill)
+    int gm = 0, gG = 0, g_fill = g ? g->fill : 0;
+    dartmpc::global_rows(n, gm, gG);
+    const dartmpc::GlobalWorkspace GL = dartmpc::global_workspace(n, ppo->epochs, mb);
+    char* gws = g ? (char*)g->workspace : nullptr;
+    auto gp = [&](size_t off) { return gws ? gws + off : nullptr; };
+    int32_t* g_choice = (int32_t*)gp(GL.choice);
+    double* g_adv = (double*)gp(GL.adv);
+    double* g_ret = (double*)gp(GL.ret);
+    float* g_last = (float*)gp(GL.last_value);
+    int32_t* g_sample = (int32_t*)gp(GL.sample);
+    int32_t* g_perm = (int32_t*)gp(GL.perm);
+    double* g_stats = (double*)gp(GL.stats);
     {
         dartmpc::IotaArgs ia;
         ia.n = n; ia.out = sample;
@@ -2555,6 +2774,41 @@ int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, cons
                                               ret, p->weights, p->critic, p->adam, p->adam_step, stats, nullptr,
                                               nullptr, nullptr, ws + L.ppo, s))
             return fail(h, rc, "PPO update");
+        if (g) {
+            // 6a: m of this iteration's records, drawn without replacement, behind the rows held
+            HIPCHK(h, launch_perms(cfg->seed, it, 1, n, g_choice, nullptr, hs, dartmpc::kStreamChoice, gm),
+                   "choice launch");
+            HIPCHK(h, launch_global_append(g, g_fill, gm, n, n, sample, g_choice, p->rec_obs, p->rec_action,
+                                           p->rec_logp, p->rec_value, p->rec_reward, p->rec_done, hs),
+                   "global buffer append launch");
+            g_fill += gm;
+            const int ran = g_fill >= n ? 1 : 0;
+            const int logged_fill = g_fill;
+            if (ran) {
+                // 6b: the buffer holds G rows: one sequence for GAE, then a full update on the same optimizer
+                if (dart_lmpc_critic_value_dev(1, p->critic, g->obs + (size_t)(gG - 1) * 520, g_last, s) != DART_MPC_OK)
+                    return fail(h, DART_MPC_EHIP, "critic value launch (global buffer)");
+                HIPCHK(h, launch_gae_seq(gG, cfg->gamma, cfg->lam, g->reward, g->value, g->done, g_last, g_adv, g_ret,
+                                         hs), "sequence GAE launch");
+                {
+                    dartmpc::IotaArgs ia;
+                    ia.n = gG; ia.out = g_sample;
+                    HIPCHK(h, dartmpc_launch_iota(&ia, hs), "sample list launch (global buffer)");
+                }
+                if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(g_stats, 0, sizeof(double) * 3, hs), "clear stats");
+                HIPCHK(h, launch_perms(cfg->seed, it, ppo->epochs, gG, g_perm, nullptr, hs,
+                                       dartmpc::kStreamGlobalPerm), "permutation launch (global buffer)");
+                if (int rc = dart_lmpc_ppo_update_dev(ppo, gG, gG, g_sample, g_perm, g->obs, g->action, g->logp, g_adv,
+                                                      g_ret, p->weights, p->critic, p->adam, p->adam_step, g_stats,
+                                                      nullptr, nullptr, nullptr, gws + GL.ppo, s))
+                    return fail(h, rc, "PPO update (global buffer)");
+                g_fill = 0;
+            }
+            dartmpc::GlobalLogArgs ga;
+            ga.fill = logged_fill; ga.ran = ran; ga.G = gG; ga.stats = g_stats;
+            ga.row = g->global_log + (size_t)dartmpc::kGlobalLogCols * j;
+            HIPCHK(h, dartmpc_launch_lmpc_global_log(&ga, hs), "global log launch");
+        }
         if (cfg->mean_update)
             if (dart_lmpc_mean_param_update_dev(pcfg, B, p->weights, p->history, p->model_params, p->current_k,
                                                 nullptr, s) != DART_MPC_OK)
@@ -2571,13 +2825,16 @@ int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, cons
     return DART_MPC_OK;
 }
 
-int dart_lmpc_train(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+// dart_lmpc_train (g == nullptr) and dart_lmpc_train_global
+int train_host_impl(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                     const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
                     const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
-                    void* stream) {
+                    const dart_lmpc_global_buffer* g, void* stream) {
     if (!h) return DART_MPC_EINVAL;
     std::unique_lock<std::recursive_mutex> lock_(h->mu);
     if (int rc = train_check(h, rcfg, ppo, cfg, B, p, false)) return rc;
+    if (g)
+        if (int rc = global_check(h, g, cfg->steps / rcfg->record_every * B, false)) return rc;
     if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, "handle is not an LMPC handle");
     if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
     if (reset_rows < 0) return fail(h, DART_MPC_EINVAL, "negative reset_rows");
@@ -2634,15 +2891,77 @@ int dart_lmpc_train(dart_mpc_handle* h, const dart_plant_config* plant, const da
     const size_t ws_bytes = dartmpc::train_workspace(B, (int)K, rcfg->record_every, ppo->epochs,
                                                      ppo->mini_batch_size).bytes;
     const int i_ws = S.add_log(nullptr, 1, ws_bytes, 0, 0, false);
+    // the global buffer: blocks of the arena whose held rows travel by hand (those held at the start go up, those
+    // held at the end come down), its log, and its workspace
+    dart_lmpc_global_buffer gd;
+    int gi[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    size_t g_rowbytes[6] = {520 * F, 34 * F, F, F, D, F};
+    if (g) {
+        gd = *g;
+        const size_t cap = (size_t)g->capacity;
+        for (int q = 0; q < 6; ++q) gi[q] = S.add_log(nullptr, 1, cap * g_rowbytes[q], 0, 0, false);
+        gi[6] = S.add_log(g->global_log, (size_t)cfg->iterations, dartmpc::kGlobalLogCols * D, 0,
+                          (size_t)cfg->iterations, false);
+        gi[7] = S.add_log(nullptr, 1, dartmpc::global_workspace((int)(R * nB), ppo->epochs, ppo->mini_batch_size).bytes,
+                          0, 0, false);
+    }
     if (int rc = S.reserve(h)) return rc;
     for (auto& b : bind) *b.first = S.dev<char>(h, b.second);
     d.workspace = S.dev<char>(h, i_ws);
     if (int rc = S.upload(h, s)) return rc;
-    if (int rc = dart_lmpc_train_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, &d, s)) {
+    void* g_host[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (g) {
+        void* hp[6] = {g->obs, g->action, g->logp, g->value, g->reward, g->done};
+        for (int q = 0; q < 6; ++q) g_host[q] = hp[q];
+        gd.obs = S.dev<float>(h, gi[0]); gd.action = S.dev<float>(h, gi[1]); gd.logp = S.dev<float>(h, gi[2]);
+        gd.value = S.dev<float>(h, gi[3]); gd.reward = S.dev<double>(h, gi[4]); gd.done = S.dev<float>(h, gi[5]);
+        gd.global_log = S.dev<double>(h, gi[6]); gd.workspace = S.dev<char>(h, gi[7]);
+        for (int q = 0; q < 6 && g->fill > 0; ++q)
+            HIPCHK(h, hipMemcpyAsync(S.dev<char>(h, gi[q]), g_host[q], (size_t)g->fill * g_rowbytes[q],
+                                     hipMemcpyHostToDevice, s), "copy global buffer");
+    }
+    if (int rc = train_dev_impl(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, &d, g ? &gd : nullptr, s)) {
         (void)hipStreamSynchronize(s);
         return rc;
     }
     if (int rc = S.download(h, s)) return rc;
+    if (g) {
+        const int held = dart_lmpc_global_fill_after((int)(R * nB), g->fill, cfg->iterations);
+        for (int q = 0; q < 6 && held > 0; ++q)
+            HIPCHK(h, hipMemcpyAsync(g_host[q], S.dev<char>(h, gi[q]), (size_t)held * g_rowbytes[q],
+                                     hipMemcpyDeviceToHost, s), "copy global buffer back");
+    }
     HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
     return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                        const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                        const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                        void* stream) {
+    return train_dev_impl(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, nullptr, stream);
+}
+
+int dart_lmpc_train(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                    const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                    const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                    void* stream) {
+    return train_host_impl(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, nullptr, stream);
+}
+
+int dart_lmpc_train_global_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                               const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* rcfg,
+                               const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg, int B,
+                               int reset_rows, const dart_lmpc_train_buffers* p, const dart_lmpc_global_buffer* g,
+                               void* stream) {
+    return train_dev_impl(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, g, stream);
+}
+
+int dart_lmpc_train_global(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                           const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                           const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                           const dart_lmpc_global_buffer* g, void* stream) {
+    return train_host_impl(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, g, stream);
 }

@@ -3,7 +3,10 @@
 // mean-based parameter write after an update (LMPC/src/controller/rlmpc2.py:876-896), and the iteration's log row
 // with the best-policy snapshot (:918-922).  With them dart_lmpc_train_dev enqueues whole PPO iterations -- noise,
 // dart_lmpc_collect_dev, critic value, GAE, permutations, dart_lmpc_ppo_update_dev, parameter write, log row -- on
-// one stream without host work in between.
+// one stream without host work in between.  dart_lmpc_train_global_dev adds the loop's second update on the global
+// buffer (:823-874) between the update and the parameter write: a choice without replacement (the permutation
+// kernel on its own generator stream, cut to a prefix), the record gather into the persistent buffer, GAE over the
+// buffer as one sequence, and the update's launches once more on the buffer's rows.
 //
 // Plain launches in stream order: no cooperative launch, no grid barrier, no atomics; every sum has a fixed order.
 #pragma once
@@ -20,6 +23,8 @@ namespace dartmpc {
 constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
 constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 constexpr uint32_t kStreamNoise = 0, kStreamPerm = 1;
+// the global-buffer update (rlmpc2.py:823-874): its draw without replacement and its mini-batch permutations
+constexpr uint32_t kStreamChoice = 2, kStreamGlobalPerm = 3;
 
 struct Philox4 { uint32_t w[4]; };
 
@@ -49,11 +54,12 @@ struct NoiseArgs {
     float* out;
 };
 
-// perm[e][rank of (key_i, i)] = i, key_i = word i % 4 of block i / 4 with stream 1 and epoch e in the counter;
-// grid (ceil(n / 256), epochs)
+// perm[e][rank of (key_i, i)] = i, key_i = word i % 4 of block i / 4 with `stream` and epoch e in the counter;
+// grid (ceil(n / 256), epochs).  Only ranks below `limit` are written, in rows of `limit` entries: limit = n gives
+// the permutations, limit = m < n their first m entries (a choice of m out of n without replacement)
 struct PermArgs {
-    int n, epochs;
-    uint32_t key0, key1, iteration;
+    int n, epochs, limit;
+    uint32_t key0, key1, iteration, stream;
     int32_t* perm;              // [epochs][n]
     uint32_t* key_out;          // [epochs][n] the raw keys, nullable
 };
@@ -73,6 +79,42 @@ struct MeanUpdateArgs {
     double* current_k;          // [B][34] out
     float* mean_out;            // [B][34] nullable
     double max_delta, k_max, min_k, k_ceiling_margin, action_scale, smooth_alpha;
+};
+
+// rlmpc2.py:823-827: buffer row fill + j <- record sample[choice[j]] (flat index row * B + b), j < m, all six
+// fields bit for bit; one workgroup per record, the observation row in 16-byte moves (both obs bases 16-byte
+// aligned: 520 floats keep every row aligned).  A choice outside [0, n) or a record outside [0, rec_total) writes
+// nothing.
+struct GbufAppendArgs {
+    int m, n, fill;
+    long long rec_total;
+    const int32_t* sample;      // [n]
+    const int32_t* choice;      // [m]
+    const float* rec_obs; const float* rec_action; const float* rec_logp; const float* rec_value;
+    const double* rec_reward; const float* rec_done;
+    float* obs; float* action; float* logp; float* value; double* reward; float* done;     // [capacity][..]
+};
+
+// compute_gae (rlmpc2.py:592-599) over rows 0 .. G-1 as one chain, fp64, bootstrapped from last_value [1]: one
+// workgroup, a suffix scan of the affine maps gae -> delta_t + c_t gae over tiles of 1024 rows
+struct GaeSeqArgs {
+    int G;
+    double gamma, lam;
+    const double* reward;       // [G]
+    const float* value;         // [G]
+    const float* done;          // [G]
+    const float* last_value;    // [1]
+    double* adv;                // [G]
+    double* ret;                // [G] adv + value
+};
+
+constexpr int kGlobalLogCols = 6;
+
+// one row of global_log: fill after the append, 1 if the update ran, G, and the update's means (NaN without)
+struct GlobalLogArgs {
+    int fill, ran, G;
+    const double* stats;        // [3], read when ran
+    double* row;                // [6]
 };
 
 constexpr int kTrainLogCols = 12;
@@ -117,6 +159,36 @@ inline TrainWorkspace train_workspace(int B, int K, int record_every, int epochs
     return w;
 }
 
+// rows of the global buffer for n samples per iteration: m = max(1, n / 4) are drawn per iteration, and the buffer
+// is updated on when it holds G = ceil(n / m) m >= n rows
+inline void global_rows(int n, int& m, int& G) {
+    m = n / 4 > 1 ? n / 4 : 1;
+    G = (n + m - 1) / m * m;
+}
+
+// Workspace of the global update (bytes from the base, every block 256-byte aligned)
+struct GlobalWorkspace {
+    size_t choice, adv, ret, last_value, sample, perm, stats, ppo, bytes;
+};
+inline GlobalWorkspace global_workspace(int n, int epochs, int mb) {
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    int m, Gi;
+    global_rows(n, m, Gi);
+    const size_t G = (size_t)Gi;
+    GlobalWorkspace w;
+    size_t o = 0;
+    w.choice = o; o += al(sizeof(int32_t) * (size_t)m);
+    w.adv = o; o += al(sizeof(double) * G);
+    w.ret = o; o += al(sizeof(double) * G);
+    w.last_value = o; o += al(sizeof(float));
+    w.sample = o; o += al(sizeof(int32_t) * G);
+    w.perm = o; o += al(sizeof(int32_t) * G * (size_t)(epochs > 0 ? epochs : 1));
+    w.stats = o; o += al(sizeof(double) * 3);
+    w.ppo = o; o += ppo_workspace(Gi, mb).bytes;
+    w.bytes = o;
+    return w;
+}
+
 }  // namespace dartmpc
 
 extern "C" hipError_t dartmpc_launch_philox(const dartmpc::PhiloxArgs* args, hipStream_t stream);
@@ -125,3 +197,6 @@ extern "C" hipError_t dartmpc_launch_lmpc_perms(const dartmpc::PermArgs* args, h
 extern "C" hipError_t dartmpc_launch_iota(const dartmpc::IotaArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_lmpc_mean_update(const dartmpc::MeanUpdateArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_lmpc_train_log(const dartmpc::TrainLogArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_gbuf_append(const dartmpc::GbufAppendArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_gae_seq(const dartmpc::GaeSeqArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_global_log(const dartmpc::GlobalLogArgs* args, hipStream_t stream);

@@ -14,6 +14,11 @@
 //                          tanh soft clip (fp64) applied unconditionally, and current_k <- model_params (:896)
 // lmpc_train_log_kernel    one workgroup: the iteration's log row (fp64 sums in a fixed order: a strided partial per
 //                          thread, then a tree over LDS) and the best-policy snapshot
+// lmpc_gbuf_append_kernel  rlmpc2.py:823-827, one workgroup per drawn record: the record's six fields into the next
+//                          row of the global buffer, bit for bit, the observation in 16-byte moves
+// lmpc_gae_seq_kernel      compute_gae (:592-599) over the global buffer as one chain (:834): one workgroup, a suffix
+//                          scan of affine maps in tiles of 1024 rows (shuffles in the wave, LDS across the waves)
+// lmpc_global_log_kernel   one row of global_log
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -59,7 +64,7 @@ __global__ __launch_bounds__(kRngThreads) void lmpc_noise_kernel(NoiseArgs a) {
 }
 
 __device__ inline uint32_t perm_key(const PermArgs& a, int i, uint32_t epoch) {
-    const Philox4 r = philox4x32_10((uint32_t)(i >> 2), a.iteration, kStreamPerm, epoch, a.key0, a.key1);
+    const Philox4 r = philox4x32_10((uint32_t)(i >> 2), a.iteration, a.stream, epoch, a.key0, a.key1);
     return r.w[i & 3];
 }
 
@@ -84,7 +89,8 @@ __global__ __launch_bounds__(kRngThreads) void lmpc_perm_kernel(PermArgs a) {
         __syncthreads();
     }
     if (live) {
-        a.perm[(size_t)e * a.n + rank] = i;              // rank < n: at most n - 1 pairs lie below
+        // rank < n: at most n - 1 pairs lie below; limit = n for the permutations, m for a choice of m
+        if (rank < a.limit) a.perm[(size_t)e * a.limit + rank] = i;
         if (a.key_out) a.key_out[(size_t)e * a.n + i] = mine;
     }
 }
@@ -232,6 +238,100 @@ __global__ __launch_bounds__(kLogThreads) void lmpc_train_log_kernel(TrainLogArg
     }
 }
 
+constexpr int kAppendThreads = 128;
+constexpr int kObsVec = kObsN / 4;                  // 130 16-byte pieces of an observation row
+static_assert(kObsN % 4 == 0, "an observation row is a whole number of 16-byte pieces");
+
+__global__ __launch_bounds__(kAppendThreads) void lmpc_gbuf_append_kernel(GbufAppendArgs a) {
+    const int j = blockIdx.x, t = threadIdx.x;
+    if (j >= a.m) return;                           // block-uniform, as are the two below
+    const int c = a.choice[j];
+    if (c < 0 || c >= a.n) return;
+    const long long src = a.sample[c];
+    if (src < 0 || src >= a.rec_total) return;
+    const size_t s = (size_t)src, d = (size_t)a.fill + (size_t)j;
+    // moves of integer words: no float operation touches a payload
+    const uint4* so = reinterpret_cast<const uint4*>(a.rec_obs + s * kObsN);
+    uint4* dob = reinterpret_cast<uint4*>(a.obs + d * kObsN);
+    for (int e = t; e < kObsVec; e += kAppendThreads) dob[e] = so[e];
+    const uint32_t* sa = reinterpret_cast<const uint32_t*>(a.rec_action + s * PA);
+    uint32_t* da = reinterpret_cast<uint32_t*>(a.action + d * PA);
+    if (t < PA) da[t] = sa[t];
+    if (t == 64) reinterpret_cast<uint32_t*>(a.logp)[d] = reinterpret_cast<const uint32_t*>(a.rec_logp)[s];
+    if (t == 65) reinterpret_cast<uint32_t*>(a.value)[d] = reinterpret_cast<const uint32_t*>(a.rec_value)[s];
+    if (t == 66) reinterpret_cast<uint32_t*>(a.done)[d] = reinterpret_cast<const uint32_t*>(a.rec_done)[s];
+    if (t == 67) reinterpret_cast<uint64_t*>(a.reward)[d] = reinterpret_cast<const uint64_t*>(a.rec_reward)[s];
+}
+
+constexpr int kSeqThreads = 1024, kSeqWaves = kSeqThreads / 64;
+
+// One workgroup.  Row t is the affine map gae -> delta_t + c_t gae, c_t = gamma lam (1 - done_t); adv_t is the
+// composition of the maps of rows t .. G-1 applied to 0.  Tiles of 1024 rows from the last to the first: a
+// Hillis-Steele suffix scan in each wave64 (6 levels of shuffles), the 16 wave totals scanned the same way in wave 0
+// (4 levels), one composition with the later waves' suffix, and one with the carry, the advantage of the first row
+// of the tile behind (0 behind the last tile, where that composition is exact).  Rows past G are the identity map.
+__global__ __launch_bounds__(kSeqThreads) void lmpc_gae_seq_kernel(GaeSeqArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double wa[kSeqWaves], wc[kSeqWaves];
+    __shared__ double carry_sh;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int G = a.G;
+    const double kappa = a.gamma * a.lam;
+    double carry = 0.0;
+    for (int tile = (G - 1) / kSeqThreads; tile >= 0; --tile) {      // block-uniform trip count
+        const int i = tile * kSeqThreads + t;
+        const bool live = i < G;
+        double A = 0.0, C = 1.0, v = 0.0;
+        if (live) {
+            v = (double)a.value[i];
+            const double nd = 1.0 - (double)a.done[i];
+            const double v_next = i + 1 < G ? (double)a.value[i + 1] : (double)a.last_value[0];
+            A = a.reward[i] + a.gamma * v_next * nd - v;             // delta_t, in lmpc_gae_kernel's order
+            C = kappa * nd;
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const double a2 = __shfl_down(A, d), c2 = __shfl_down(C, d);
+            if (lane + d < 64) { A = A + C * a2; C = C * c2; }
+        }
+        if (lane == 0) { wa[w] = A; wc[w] = C; }
+        __syncthreads();
+        if (w == 0) {
+            double ta = lane < kSeqWaves ? wa[lane] : 0.0, tc = lane < kSeqWaves ? wc[lane] : 1.0;
+#pragma unroll
+            for (int d = 1; d < kSeqWaves; d <<= 1) {
+                const double a2 = __shfl_down(ta, d), c2 = __shfl_down(tc, d);
+                if (lane + d < kSeqWaves) { ta = ta + tc * a2; tc = tc * c2; }
+            }
+            // exclusive: wave l takes the composition of waves l + 1 .. 15
+            const double ea = __shfl_down(ta, 1), ec = __shfl_down(tc, 1);
+            if (lane < kSeqWaves) {
+                wa[lane] = lane + 1 < kSeqWaves ? ea : 0.0;
+                wc[lane] = lane + 1 < kSeqWaves ? ec : 1.0;
+            }
+        }
+        __syncthreads();
+        const double behind = wa[w] + wc[w] * carry;                 // the advantage of the next wave's first row
+        const double g = A + C * behind;
+        if (live) {
+            a.adv[i] = g;
+            a.ret[i] = g + v;
+        }
+        if (t == 0) carry_sh = g;
+        __syncthreads();                                             // (also: wa / wc are free for the next tile)
+        carry = carry_sh;
+    }
+}
+
+__global__ __launch_bounds__(64) void lmpc_global_log_kernel(GlobalLogArgs a) {
+    const int t = threadIdx.x;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    if (t == 0) a.row[0] = (double)a.fill;
+    if (t == 1) a.row[1] = (double)a.ran;
+    if (t == 2) a.row[2] = (double)a.G;
+    if (t >= 3 && t < kGlobalLogCols) a.row[t] = a.ran ? a.stats[t - 3] : nan;
+}
+
 inline int blocks_of(long long n, int per) { return (int)((n + per - 1) / per); }
 
 }  // namespace
@@ -273,5 +373,22 @@ extern "C" hipError_t dartmpc_launch_lmpc_mean_update(const MeanUpdateArgs* a, h
 
 extern "C" hipError_t dartmpc_launch_lmpc_train_log(const TrainLogArgs* a, hipStream_t s) {
     hipLaunchKernelGGL(lmpc_train_log_kernel, dim3(1), dim3(kLogThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_gbuf_append(const GbufAppendArgs* a, hipStream_t s) {
+    if (a->m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_gbuf_append_kernel, dim3(a->m), dim3(kAppendThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_gae_seq(const GaeSeqArgs* a, hipStream_t s) {
+    if (a->G <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_gae_seq_kernel, dim3(1), dim3(kSeqThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_global_log(const GlobalLogArgs* a, hipStream_t s) {
+    hipLaunchKernelGGL(lmpc_global_log_kernel, dim3(1), dim3(64), 0, s, *a);
     return hipGetLastError();
 }

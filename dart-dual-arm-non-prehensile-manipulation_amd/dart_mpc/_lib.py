@@ -51,7 +51,11 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_lmpc_critic_value_dev", "dart_lmpc_critic_value",
            "dart_lmpc_philox_dev", "dart_lmpc_noise_dev", "dart_lmpc_noise", "dart_lmpc_perms_dev", "dart_lmpc_perms",
            "dart_lmpc_mean_param_update_dev", "dart_lmpc_mean_param_update", "dart_lmpc_train_config_default",
-           "dart_lmpc_train_workspace_bytes", "dart_lmpc_train_dev", "dart_lmpc_train")
+           "dart_lmpc_train_workspace_bytes", "dart_lmpc_train_dev", "dart_lmpc_train",
+           "dart_lmpc_choice_dev", "dart_lmpc_choice", "dart_lmpc_perms_stream_dev", "dart_lmpc_global_rows",
+           "dart_lmpc_global_fill_after", "dart_lmpc_global_workspace_bytes", "dart_lmpc_global_append_dev",
+           "dart_lmpc_global_append", "dart_lmpc_gae_seq_dev", "dart_lmpc_gae_seq", "dart_lmpc_train_global_dev",
+           "dart_lmpc_train_global")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -105,6 +109,14 @@ class TrainConfig(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("iterations", ctypes.c_int32), ("it0", ctypes.c_int32),
                 ("steps", ctypes.c_int32), ("mean_update", ctypes.c_int32), ("track_best", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("gamma", ctypes.c_double), ("lam", ctypes.c_double)]
+
+
+class GlobalBuffer(ctypes.Structure):
+    """Mirror of ``struct dart_lmpc_global_buffer`` (the global buffer of the training loop's second update)."""
+    _fields_ = [("obs", ctypes.c_void_p), ("action", ctypes.c_void_p), ("logp", ctypes.c_void_p),
+                ("value", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("capacity", ctypes.c_int32), ("fill", ctypes.c_int32), ("global_log", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p)]
 
 
 # Arrays of the closed-loop rollouts in the argument order of include/dart_mpc.h: (name, row width, dtype);
@@ -340,6 +352,26 @@ def lib():
         for fn in (L.dart_lmpc_philox_dev, L.dart_lmpc_noise_dev, L.dart_lmpc_noise, L.dart_lmpc_perms_dev,
                    L.dart_lmpc_perms, L.dart_lmpc_mean_param_update_dev, L.dart_lmpc_mean_param_update,
                    L.dart_lmpc_train_dev, L.dart_lmpc_train):
+            fn.restype = ctypes.c_int
+    if hasattr(L, "dart_lmpc_train_global_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci, cd, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_uint64
+        L.dart_lmpc_choice_dev.argtypes = [u64, ci, ci, ci, vp, vp]
+        L.dart_lmpc_choice.argtypes = [u64, ci, ci, ci, vp]
+        L.dart_lmpc_perms_stream_dev.argtypes = [u64, ci, ci, ci, ci, vp, vp, vp]
+        L.dart_lmpc_global_rows.argtypes = [ci, vp, vp]
+        L.dart_lmpc_global_fill_after.argtypes = [ci, ci, ci]
+        L.dart_lmpc_global_workspace_bytes.argtypes = [ci, ci, ci]
+        L.dart_lmpc_global_workspace_bytes.restype = ctypes.c_size_t
+        L.dart_lmpc_global_append_dev.argtypes = [vp, ci, ci, ci] + [vp] * 9
+        L.dart_lmpc_global_append.argtypes = [vp, ci, ci, ci] + [vp] * 8
+        L.dart_lmpc_gae_seq_dev.argtypes = [ci, cd, cd] + [vp] * 7
+        L.dart_lmpc_gae_seq.argtypes = [ci, cd, cd] + [vp] * 6
+        for fn in (L.dart_lmpc_train_global_dev, L.dart_lmpc_train_global):
+            fn.argtypes = [vp] * 6 + [ci, ci, vp, vp, vp]
+        for fn in (L.dart_lmpc_choice_dev, L.dart_lmpc_choice, L.dart_lmpc_perms_stream_dev, L.dart_lmpc_global_rows,
+                   L.dart_lmpc_global_fill_after, L.dart_lmpc_global_append_dev, L.dart_lmpc_global_append,
+                   L.dart_lmpc_gae_seq_dev, L.dart_lmpc_gae_seq, L.dart_lmpc_train_global_dev,
+                   L.dart_lmpc_train_global):
             fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
@@ -1017,14 +1049,36 @@ class LmpcSolver(Solver):
         if rc != 0:
             self._err(rc, "dart_lmpc_train_dev")
 
+    def train_global_dev(self, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state, cstate, logs,
+                         clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, gbuf, pool=None, plant=None, stream=0):
+        """``train_dev`` with the global-buffer update (dart_lmpc_train_global_dev): ``gbuf`` is a ``global_buffer``
+        struct of device pointers (capacity >= G of ``global_rows``, ``fill`` the rows held now, ``global_log``
+        [iterations, 6], ``workspace`` of ``global_workspace_bytes``), or None for ``train_dev`` itself.  The next
+        call's fill is ``global_fill_after(n, gbuf.fill, tcfg.iterations)``."""
+        plant = plant or plant_config()
+        buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
+                             + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
+                             + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
+                             + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
+                             + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
+        rc = lib().dart_lmpc_train_global_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
+                                              ctypes.byref(ppo_cfg), ctypes.byref(tcfg), int(B), int(reset_rows), buf,
+                                              ctypes.byref(gbuf) if gbuf is not None else None, stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_train_global_dev")
+
     def train(self, target, plant_pvec, state, cstate, logs, clogs, rec, policy, adam, adam_step, train_log,
-              best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None, pool=None, plant=None):
+              best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None, pool=None, plant=None,
+              global_buffer=None, global_log=None):
         """Host arrays (blocking, dart_lmpc_train): state, weights, Adam's state and the reset pool are staged in
         once, ``tcfg.iterations`` iterations run on the device, the results are staged out once.  Updated in place:
         ``target``, ``plant_pvec``, ``state``, ``cstate``, ``policy.weights`` / ``critic_weights`` / ``current_k``,
         ``adam`` [2, 77317], ``adam_step`` [1], ``best_return`` [1] (float64, start at -inf), ``best_weights``
         [77317], ``best_iter`` [1]; ``logs`` / ``clogs`` ([steps, B, ..]) and ``rec`` ([steps / record_every, B, ..])
-        receive the last iteration's values, ``train_log`` [iterations, 12] one row per iteration."""
+        receive the last iteration's values, ``train_log`` [iterations, 12] one row per iteration.  With
+        ``global_buffer`` (a ``ppo.new_global_buffer`` dict) every iteration also runs the global-buffer update
+        (dart_lmpc_train_global): the dict's arrays and ``fill`` are updated in place and ``global_log``
+        [iterations, 6] (float64) receives one row per iteration."""
         B, K = state["x"].shape[0], int(tcfg.steps)
         rcfg = rcfg if rcfg is not None else reward_config()
         R = K // max(int(rcfg.record_every), 1)
@@ -1049,6 +1103,15 @@ class LmpcSolver(Solver):
                 + _host_ptrs(LMPC_LOOP_LOGS, logs, (K, B)) + _host_ptrs(LMPC_COLLECT_LOGS, clogs, (K, B))
                 + _host_ptrs(LMPC_COLLECT_REC, rec, (R, B)) + [_ptr(a) for a in tail] + [None])
         buf = _train_buffers([0 if q is None else q.value for q in ptrs])
+        if global_buffer is not None:
+            g = _host_global(global_buffer, int(tcfg.iterations), global_log)
+            rc = lib().dart_lmpc_train_global(self._h, ctypes.byref(plant), ctypes.byref(policy.cfg),
+                                              ctypes.byref(rcfg), ctypes.byref(ppo_cfg), ctypes.byref(tcfg), B,
+                                              reset_rows, buf, ctypes.byref(g), None)
+            if rc != 0:
+                self._err(rc, "dart_lmpc_train_global")
+            global_buffer["fill"] = global_fill_after(R * B, g.fill, int(tcfg.iterations))
+            return
         rc = lib().dart_lmpc_train(self._h, ctypes.byref(plant), ctypes.byref(policy.cfg), ctypes.byref(rcfg),
                                    ctypes.byref(ppo_cfg), ctypes.byref(tcfg), B, reset_rows, buf, None)
         if rc != 0:
@@ -1330,6 +1393,125 @@ def perms(seed, iteration, epochs, n, want_keys=False):
     keys = np.empty((int(epochs), int(n)), np.uint32) if want_keys else None
     _rc(lib().dart_lmpc_perms(int(seed), int(iteration), int(epochs), int(n), _ptr(out), _ptr(keys)), "dart_lmpc_perms")
     return (out, keys) if want_keys else out
+
+
+# ---- the global-buffer update (rlmpc2.py:823-874) ----
+GLOBAL_LOG_COLS = 6
+GLOBAL_LOG_FIELDS = ("global_fill", "global_update", "global_rows", "global_policy_loss", "global_value_loss",
+                     "global_entropy")
+# the buffer's arrays in the struct's order: (name, row width, dtype)
+LMPC_GLOBAL_ARRAYS = (("obs", 520, np.float32), ("action", 34, np.float32), ("logp", 0, np.float32),
+                      ("value", 0, np.float32), ("reward", 0, np.float64), ("done", 0, np.float32))
+
+
+def perms_stream_dev(seed, iteration, rng_stream, epochs, n, perm_out, key_out=0, stream=0):
+    """dart_lmpc_perms_stream_dev: ``perms_dev`` with the generator's stream index given (1: the local update's
+    permutations, 3: the global update's)."""
+    _rc(lib().dart_lmpc_perms_stream_dev(int(seed), int(iteration), int(rng_stream), int(epochs), int(n),
+                                         _vp(perm_out), _vp(key_out), stream or None), "dart_lmpc_perms_stream_dev")
+
+
+def choice_dev(seed, iteration, n, m, choice_out, stream=0):
+    """dart_lmpc_choice_dev: ``m`` of ``n`` without replacement (int32 [m]) for (seed, iteration): the first m
+    entries of the generator's permutation on stream 2 (device pointer)."""
+    _rc(lib().dart_lmpc_choice_dev(int(seed), int(iteration), int(n), int(m), _vp(choice_out), stream or None),
+        "dart_lmpc_choice_dev")
+
+
+def choice(seed, iteration, n, m):
+    """The choice of (seed, iteration) from the device generator (dart_lmpc_choice, blocking): int32 [m]."""
+    out = np.empty(max(int(m), 0), np.int32)
+    _rc(lib().dart_lmpc_choice(int(seed), int(iteration), int(n), int(m), _ptr(out)), "dart_lmpc_choice")
+    return out
+
+
+def global_rows(n):
+    """(m, G) of dart_lmpc_global_rows: m = max(1, n // 4) records are drawn per iteration, and the global buffer is
+    updated on when it holds G = ceil(n / m) m rows (its capacity)."""
+    m, G = ctypes.c_int32(), ctypes.c_int32()
+    _rc(lib().dart_lmpc_global_rows(int(n), ctypes.byref(m), ctypes.byref(G)), "dart_lmpc_global_rows")
+    return int(m.value), int(G.value)
+
+
+def global_fill_after(n, fill, iterations):
+    """The global buffer's fill after ``iterations`` more iterations (dart_lmpc_global_fill_after, host arithmetic)."""
+    f = int(lib().dart_lmpc_global_fill_after(int(n), int(fill), int(iterations)))
+    if f < 0:
+        raise DartMPCError(f"no global fill for n = {n}, fill = {fill}, iterations = {iterations} "
+                           f"(fill a multiple of m in [0, n))")
+    return f
+
+
+def global_workspace_bytes(n, epochs, mini_batch_size):
+    """Bytes of the device workspace of the global update (``LmpcSolver.train_global_dev``)."""
+    b = int(lib().dart_lmpc_global_workspace_bytes(int(n), int(epochs), int(mini_batch_size)))
+    if b == 0:
+        raise DartMPCError(f"no global workspace for n = {n}, epochs = {epochs}, mini_batch_size = {mini_batch_size}")
+    return b
+
+
+def global_buffer(arrays, capacity, fill, global_log=0, workspace=0) -> GlobalBuffer:
+    """``struct dart_lmpc_global_buffer`` from addresses (ints): ``arrays`` maps obs, action, logp, value, reward,
+    done to device (or host) pointers of ``capacity`` rows."""
+    g = GlobalBuffer()
+    for name, _, _ in LMPC_GLOBAL_ARRAYS:
+        setattr(g, name, int(arrays[name]) or None)
+    g.capacity, g.fill = int(capacity), int(fill)
+    g.global_log, g.workspace = int(global_log) or None, int(workspace) or None
+    return g
+
+
+def _host_global(buf, need_log_rows=None, global_log=None):
+    """GlobalBuffer over the host arrays of a ``ppo.new_global_buffer`` dict (checked: dtype, size, contiguity)."""
+    cap = int(np.asarray(buf["logp"]).size)
+    ptrs = {}
+    for name, width, dt in LMPC_GLOBAL_ARRAYS:
+        ptrs[name] = _inplace(buf[name], dt, cap * max(width, 1), "global_buffer[%r]" % name).ctypes.data
+    log = 0
+    if need_log_rows is not None:
+        log = _inplace(global_log, np.float64, GLOBAL_LOG_COLS * need_log_rows, "global_log").ctypes.data
+    return global_buffer(ptrs, cap, int(buf["fill"]), global_log=log)
+
+
+def global_append_dev(g, m, n, rec_total, sample, choice, rec, stream=0):
+    """dart_lmpc_global_append_dev: rows ``g.fill`` .. ``g.fill + m - 1`` of the buffer ``g`` (``global_buffer``)
+    <- records ``sample[choice[j]]``; ``rec`` maps the names of LMPC_COLLECT_REC to device pointers."""
+    _rc(lib().dart_lmpc_global_append_dev(ctypes.byref(g), int(m), int(n), int(rec_total), _vp(sample), _vp(choice),
+                                          *[_vp(rec[k]) for k, _, _ in LMPC_COLLECT_REC], stream or None),
+        "dart_lmpc_global_append_dev")
+
+
+def global_append(buf, sample, choice, rec):
+    """The record gather on host arrays (dart_lmpc_global_append, blocking): the rows ``buf['fill']`` .. of the
+    ``ppo.new_global_buffer`` dict ``buf`` receive records ``sample[choice[j]]`` of ``rec`` (the record arrays
+    [rec_rows, B, ..]); ``buf['fill']`` advances by ``len(choice)``."""
+    sample = np.ascontiguousarray(sample, np.int32).reshape(-1)
+    choice = np.ascontiguousarray(choice, np.int32).reshape(-1)
+    total = int(np.asarray(rec["rec_logp"]).size)
+    r = [np.ascontiguousarray(rec[k], dt).reshape(total, max(w, 1)) for k, w, dt in LMPC_COLLECT_REC]
+    g = _host_global(buf)
+    _rc(lib().dart_lmpc_global_append(ctypes.byref(g), choice.size, sample.size, total, _ptr(sample), _ptr(choice),
+                                      *[_ptr(a) for a in r]), "dart_lmpc_global_append")
+    buf["fill"] = int(buf["fill"]) + choice.size
+
+
+def gae_seq_dev(G, gamma, lam, reward, value, done, last_value, adv, ret, stream=0):
+    """dart_lmpc_gae_seq_dev: compute_gae over rows 0 .. G-1 as one chain (device pointers)."""
+    _rc(lib().dart_lmpc_gae_seq_dev(int(G), float(gamma), float(lam), _vp(reward), _vp(value), _vp(done),
+                                    _vp(last_value), _vp(adv), _vp(ret), stream or None), "dart_lmpc_gae_seq_dev")
+
+
+def gae_seq(reward, value, done, last_value, gamma=0.99, lam=0.95):
+    """compute_gae over one sequence on the GPU (dart_lmpc_gae_seq, blocking): (adv, ret = adv + value), float64
+    [G]."""
+    rw = np.ascontiguousarray(reward, np.float64).reshape(-1)
+    G = rw.size
+    vl, dn = (np.ascontiguousarray(a, np.float32).reshape(G) for a in (value, done))
+    lv = np.ascontiguousarray(last_value, np.float32).reshape(1)
+    adv, ret = np.full(G, np.nan), np.full(G, np.nan)
+    _rc(lib().dart_lmpc_gae_seq(G, float(gamma), float(lam), _ptr(rw), _ptr(vl), _ptr(dn), _ptr(lv), _ptr(adv),
+                                _ptr(ret)), "dart_lmpc_gae_seq")
+    return adv, ret
 
 
 def mean_param_update_dev(pcfg, B, weights, history, model_params, current_k, mean_out=0, stream=0):

@@ -660,6 +660,38 @@ def lmpc_train_perms(seed, iteration, epochs, n):
     return perm, keys
 
 
+def lmpc_train_choice(seed, iteration, n, m):
+    """dart_lmpc_choice restated in numpy: ``m`` of ``n`` without replacement, int32 [m] -- the first m entries of
+    the argsort of (key, index) over the n words of (seed, iteration, stream 2, epoch 0).  Stands in for the
+    reference's ``rng.choice(len(buf), max(1, len(buf) // 4), replace=False)`` (rlmpc2.py:823-827)."""
+    n, m = int(n), int(m)
+    if not 1 <= m <= n:
+        raise ValueError(f"a choice of m = {m} out of n = {n}")
+    keys = lmpc_train_words(seed, iteration, 2, 0, n)
+    return np.lexsort((np.arange(n), keys))[:m].astype(np.int32)
+
+
+def gae_sequence(reward, value, done, last_value, gamma=0.99, lam=0.95, magnitude=False):
+    """compute_gae (:592-599) over one sequence, the sequential recursion in fp64: (adv, ret = adv + value), [G].
+    With ``magnitude`` the same recursion on |delta_t| (the bootstrap value enters through delta_{G-1} alone): the
+    scale A_t = sum_k |c_t .. c_{t+k-1} delta_{t+k}| that the error of a reassociated evaluation is measured
+    against; returns (A, A + |value|)."""
+    rw = np.asarray(reward, np.float64).reshape(-1)
+    rv, rd = np.asarray(value, np.float64).reshape(-1), np.asarray(done, np.float64).reshape(-1)
+    G = rw.size
+    adv = np.zeros(G)
+    g, v_next = 0.0, float(np.asarray(last_value, np.float64).reshape(-1)[0])
+    for s in reversed(range(G)):
+        nd = 1.0 - rd[s]
+        delta = rw[s] + gamma * v_next * nd - rv[s]
+        if magnitude:
+            delta = abs(delta)
+        g = delta + gamma * lam * nd * g
+        adv[s] = g
+        v_next = rv[s]
+    return adv, adv + (np.abs(rv) if magnitude else rv)
+
+
 def gae_numpy(nrec, rec_reward, rec_value, rec_done, last_value, gamma=0.99, lam=0.95):
     """compute_gae (:592-599) per instance over its first nrec[b] records [rec_rows, B], fp64: (adv, ret = adv +
     value), NaN in the rows an instance has not recorded."""

@@ -8,9 +8,10 @@ Experience comes from ``dart_lmpc_collect`` (harness.collect_lmpc) and ``_lib.ga
 ``load_weights`` and ``pack_adam`` / ``load_adam`` move the weights and Adam's state between the torch objects and
 the packed input-major arrays the kernels read.  ``train_device`` runs whole iterations -- noise, collection,
 GAE, permutations, update, the mean-based parameter write, log row and best-policy snapshot -- through
-``LmpcSolver.train`` (csrc/lmpc_train.hip) without the host in between.  ``save_checkpoint`` / ``load_checkpoint``
-keep a training state in one ``.npz`` of plain arrays (no pickle); its fields stand in for the reference's
-``best_agent.pth`` / ``latest_agent.pth``, which are not loaded.
+``LmpcSolver.train`` (csrc/lmpc_train.hip) without the host in between; with ``global_buffer=new_global_buffer(n)``
+the iterations also contain the loop's second update on the global buffer (:823-874).  ``save_checkpoint`` /
+``load_checkpoint`` keep a training state, the global buffer included when given, in one ``.npz`` of plain arrays (no
+pickle); its fields stand in for the reference's ``best_agent.pth`` / ``latest_agent.pth``, which are not loaded.
 """
 from __future__ import annotations
 
@@ -191,7 +192,7 @@ def ppo_update(net, optimizer, batch, clip_eps=0.2, epochs=8, mini_batch_size=64
 
 def train_device(solver, policy, target, plant_pvec, state, cstate, adam, adam_step, best, steps, iterations=1, it0=0,
                  seed=0, rcfg=None, pool=None, prm=None, gamma=0.99, lam=0.95, mean_update=True, track_best=True,
-                 epochs=8, mini_batch_size=64, out=None, **hyper):
+                 epochs=8, mini_batch_size=64, out=None, global_buffer=None, **hyper):
     """``iterations`` complete PPO iterations of ``steps`` closed-loop steps on the device (``LmpcSolver.train``): the
     exploration noise and the mini-batch permutations come from the device generator of (``seed``, iteration index
     ``it0`` ..), nothing passes through the host between the steps of an iteration or between iterations.  Updated
@@ -199,7 +200,13 @@ def train_device(solver, policy, target, plant_pvec, state, cstate, adam, adam_s
     ``policy.weights`` / ``critic_weights`` / ``current_k``, ``adam`` [2, 77317], ``adam_step`` [1] and ``best`` =
     dict(best_return float64 [1] starting at -inf, best_weights float32 [77317], best_iter int32 [1]).  ``hyper``
     overrides fields of ``_lib.ppo_config``.  ``out`` (a dict, optional) receives the last iteration's ``logs``,
-    ``clogs`` and ``rec``.  Returns one dict per iteration with the keys of ``_lib.TRAIN_LOG_FIELDS``."""
+    ``clogs`` and ``rec``.  Returns one dict per iteration with the keys of ``_lib.TRAIN_LOG_FIELDS``.
+
+    With ``global_buffer`` (``new_global_buffer(n)``, n = B * steps / record_every) every iteration also runs the
+    reference's second update (rlmpc2.py:823-874): a quarter of its records is appended to the buffer, and a buffer
+    that holds n records is updated on and cleared, before the parameter write.  The dict is updated in place,
+    ``fill`` included, so it carries over to the next call; each returned row gains the keys of
+    ``_lib.GLOBAL_LOG_FIELDS``."""
     from . import _lib
     rcfg = rcfg if rcfg is not None else _lib.reward_config()
     B, K = state["x"].shape[0], int(steps)
@@ -210,11 +217,29 @@ def train_device(solver, policy, target, plant_pvec, state, cstate, adam, adam_s
     logs, clogs = _lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, B), _lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, B)
     rec = _lib.loop_logs(_lib.LMPC_COLLECT_REC, R, B)
     train_log = np.full((int(iterations), _lib.TRAIN_LOG_COLS), np.nan)
+    global_log = None if global_buffer is None else np.full((int(iterations), _lib.GLOBAL_LOG_COLS), np.nan)
     solver.train(target, plant_pvec, state, cstate, logs, clogs, rec, policy, adam, adam_step, train_log,
-                 best["best_return"], best["best_weights"], best["best_iter"], cfg, tcfg, rcfg=rcfg, prm=prm, pool=pool)
+                 best["best_return"], best["best_weights"], best["best_iter"], cfg, tcfg, rcfg=rcfg, prm=prm, pool=pool,
+                 global_buffer=global_buffer, global_log=global_log)
     if out is not None:
         out.update(logs=logs, clogs=clogs, rec=rec, train_log=train_log)
-    return [dict(zip(_lib.TRAIN_LOG_FIELDS, (float(v) for v in row))) for row in train_log]
+    rows = [dict(zip(_lib.TRAIN_LOG_FIELDS, (float(v) for v in row))) for row in train_log]
+    if global_buffer is not None:
+        if out is not None:
+            out.update(global_log=global_log)
+        for row, grow in zip(rows, global_log):
+            row.update(zip(_lib.GLOBAL_LOG_FIELDS, (float(v) for v in grow)))
+    return rows
+
+
+def new_global_buffer(n):
+    """The global buffer of a fresh training with ``n`` samples per iteration: zeroed arrays of capacity G
+    (``_lib.global_rows``) and ``fill`` = 0."""
+    from . import _lib
+    _, G = _lib.global_rows(n)
+    buf = {name: np.zeros((G, width) if width else (G,), dt) for name, width, dt in _lib.LMPC_GLOBAL_ARRAYS}
+    buf["fill"] = 0
+    return buf
 
 
 def new_best():
@@ -233,12 +258,22 @@ CHECKPOINT_FIELDS = {
 }
 
 
+# the optional arrays of the global buffer: name -> (dtype, trailing shape; None: the buffer's capacity)
+CHECKPOINT_GLOBAL_FIELDS = {
+    "g_obs": (np.float32, (None, 520)), "g_action": (np.float32, (None, 34)), "g_logp": (np.float32, (None,)),
+    "g_value": (np.float32, (None,)), "g_reward": (np.float64, (None,)), "g_done": (np.float32, (None,)),
+    "g_fill": (np.int64, (1,)),
+}
+
+
 def save_checkpoint(path, actor, critic, adam, adam_step, best, iteration, obs_mean, obs_M2, obs_count, history,
-                    current_k, model_params):
+                    current_k, model_params, global_buffer=None):
     """One ``.npz`` of plain arrays (``CHECKPOINT_FIELDS``; readable with ``allow_pickle=False``): the packed actor
     and critic, Adam's state, the best-policy snapshot (``best`` as ``train_device`` takes it), the number of
     iterations done and the policy's Welford state, history, ``current_k`` and ``model_params`` for B controllers.
-    Returns the path written (numpy appends ``.npz`` to a path without it)."""
+    With ``global_buffer`` (the dict of ``new_global_buffer``) the file also holds the plain arrays ``g_obs`` ..
+    ``g_done`` and ``g_fill`` (``CHECKPOINT_GLOBAL_FIELDS``), so that a training can resume in the middle of a fill
+    period.  Returns the path written (numpy appends ``.npz`` to a path without it)."""
     from ._lib import DartMPCError
     B = np.asarray(obs_count).reshape(-1).size
     given = dict(actor=actor, critic=critic, adam=adam, adam_step=adam_step, best_weights=best["best_weights"],
@@ -252,6 +287,16 @@ def save_checkpoint(path, actor, critic, adam, adam_step, best, iteration, obs_m
         if a.size != int(np.prod(want)):
             raise DartMPCError(f"checkpoint field {name!r} must have shape {want}, got {a.shape}")
         arrays[name] = np.ascontiguousarray(a, dt).reshape(want)
+    if global_buffer is not None:
+        cap = np.asarray(global_buffer["logp"]).size
+        for name, (dt, shape) in CHECKPOINT_GLOBAL_FIELDS.items():
+            want = tuple(cap if d is None else d for d in shape)
+            a = np.asarray(global_buffer[name[2:]])
+            if a.size != int(np.prod(want)):
+                raise DartMPCError(f"checkpoint field {name!r} must have shape {want}, got {a.shape}")
+            arrays[name] = np.ascontiguousarray(a, dt).reshape(want)
+        if not 0 <= int(arrays["g_fill"][0]) <= cap:
+            raise DartMPCError(f"checkpoint field 'g_fill' must lie in [0, {cap}]")
     path = str(path)
     path = path if path.endswith(".npz") else path + ".npz"
     with open(path, "wb") as fh:
@@ -261,7 +306,9 @@ def save_checkpoint(path, actor, critic, adam, adam_step, best, iteration, obs_m
 
 def load_checkpoint(path):
     """The arrays ``save_checkpoint`` wrote, as a dict name -> array (``allow_pickle=False``: a file that holds
-    pickled objects is refused).  A missing field, a wrong dtype or a wrong shape raises ``DartMPCError``."""
+    pickled objects is refused).  A missing field, a wrong dtype or a wrong shape raises ``DartMPCError``.  The
+    arrays of a global buffer (``CHECKPOINT_GLOBAL_FIELDS``) are returned when the file holds them -- all of them or
+    none; ``global_buffer_from_checkpoint`` turns them back into the dict ``train_device`` takes."""
     from ._lib import DartMPCError
     try:
         with np.load(str(path), allow_pickle=False) as z:
@@ -283,4 +330,28 @@ def load_checkpoint(path):
             if have != want:
                 raise DartMPCError(f"{path}: checkpoint field {name!r} has shape {a.shape}")
         out[name] = np.ascontiguousarray(a)
+    if any(name in got for name in CHECKPOINT_GLOBAL_FIELDS):
+        cap = None
+        for name, (dt, shape) in CHECKPOINT_GLOBAL_FIELDS.items():
+            if name not in got:
+                raise DartMPCError(f"{path}: checkpoint field {name!r} is missing")
+            a = got[name]
+            if a.dtype != np.dtype(dt) or a.ndim != len(shape):
+                raise DartMPCError(f"{path}: checkpoint field {name!r} must be {np.dtype(dt).name} with {len(shape)} axes")
+            for have, want in zip(a.shape, shape):
+                if want is None:
+                    cap = have if cap is None else cap
+                    want = cap
+                if have != want:
+                    raise DartMPCError(f"{path}: checkpoint field {name!r} has shape {a.shape}")
+            out[name] = np.ascontiguousarray(a)
     return out
+
+
+def global_buffer_from_checkpoint(ck):
+    """The ``new_global_buffer`` dict held in a loaded checkpoint (fresh arrays), or None when it has none."""
+    if "g_fill" not in ck:
+        return None
+    buf = {name[2:]: np.array(ck[name]) for name in CHECKPOINT_GLOBAL_FIELDS if name != "g_fill"}
+    buf["fill"] = int(ck["g_fill"][0])
+    return buf

@@ -740,7 +740,9 @@ int dart_lmpc_critic_value_dev(int n, const float *critic, const float *obs, flo
 int dart_lmpc_critic_value(int n, const float *critic, const float *obs, float *value_out);
 
 /* Whole PPO training iterations of the LMPC policy on the device (added within ABI 8; csrc/lmpc_train.hip): the
- * loop of RLMPC._rl_worker (rlmpc2.py:537-938) without the host between its steps.
+ * loop of RLMPC._rl_worker (rlmpc2.py:537-938) without the host between its steps.  dart_lmpc_train(_dev) runs the
+ * local update of every iteration (:783-819); dart_lmpc_train_global(_dev), further down, also runs the loop's second,
+ * global-buffer update (:823-874) inside the iteration, before the parameter write.
  *
  * Random numbers.  One counter-based generator, Philox4x32-10 with the standard constants (multipliers 0xD2511F53,
  * 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85), key (seed & 0xffffffff, seed >> 32), counter
@@ -847,6 +849,110 @@ int dart_lmpc_train(dart_mpc_handle *h, const dart_plant_config *plant, const da
                     const dart_lmpc_reward_config *rcfg, const dart_lmpc_ppo_config *ppo,
                     const dart_lmpc_train_config *cfg, int B, int reset_rows,
                     const dart_lmpc_train_buffers *buf, void *hip_stream);
+
+/* The global-buffer update of the training loop (rlmpc2.py:823-874; added within ABI 8: new entries only).  After
+ * its local update every iteration of RLMPC._rl_worker draws m = max(1, n / 4) of its n records without
+ * replacement (:823-827), appends them in the drawn order to a second buffer that survives across iterations
+ * (glob_buf, :581) and, once that buffer holds at least n records, runs compute_gae over it as ONE sequence
+ * bootstrapped from the critic on its last observation (:830-834), normalises and runs a second full PPO update on
+ * the same optimizer (:835-871), and clears the buffer (:874); only then comes the mean-based parameter write.
+ * The buffer is updated on when it holds G = ceil(n / m) m rows; G > n when n % 4 != 0 (n = 90: m = 22, G = 110).
+ *
+ * dart_lmpc_choice(_dev): choice_out [m] = the first m entries of the permutation of n elements that the generator
+ * of dart_lmpc_perms gives for (seed, iteration, stream 2, epoch 0): the argsort of (key, index), ties on the index.
+ * Nothing past choice_out[m - 1] is written.  EINVAL: iteration < 0, m < 1, m > n, a null pointer.
+ * dart_lmpc_perms_stream_dev: dart_lmpc_perms_dev with the generator's stream index given (1: the local update's
+ * permutations, what dart_lmpc_perms_dev draws; 3: the global update's). */
+int dart_lmpc_choice_dev(uint64_t seed, int iteration, int n, int m, int32_t *choice_out, void *hip_stream);
+int dart_lmpc_choice(uint64_t seed, int iteration, int n, int m, int32_t *choice_out);
+int dart_lmpc_perms_stream_dev(uint64_t seed, int iteration, int rng_stream, int epochs, int n, int32_t *perm_out,
+                               uint32_t *key_out, void *hip_stream);
+
+#define DART_LMPC_GLOBAL_LOG_COLS 6
+
+/* The global buffer: `capacity` rows of a record's six fields, device arrays for the _dev entries and host arrays
+ * for the host entries.  fill is the number of rows held when a call starts; the host knows it (calls never read
+ * it from the device) and advances it with dart_lmpc_global_fill_after. */
+typedef struct dart_lmpc_global_buffer {
+    float *obs;                    /* [capacity][520], 16-byte aligned (EINVAL otherwise) */
+    float *action;                 /* [capacity][34] */
+    float *logp;                   /* [capacity] */
+    float *value;                  /* [capacity] */
+    double *reward;                /* [capacity] */
+    float *done;                   /* [capacity] */
+    int32_t capacity;              /* >= G of dart_lmpc_global_rows */
+    int32_t fill;                  /* rows held when the call starts */
+    double *global_log;            /* [iterations][6], written by dart_lmpc_train_global(_dev) */
+    void *workspace;               /* dart_lmpc_global_workspace_bytes; device memory (NULL for the host entries) */
+} dart_lmpc_global_buffer;
+
+/* m = max(1, n / 4) and G = ceil(n / m) m for n samples per iteration.  EINVAL: n < 1 or a null pointer. */
+int dart_lmpc_global_rows(int n, int32_t *m_out, int32_t *G_out);
+/* The fill after `iterations` more iterations started at `fill` (each appends m rows; a fill that reaches n is
+ * updated on and becomes 0).  Pure host arithmetic, so calls chain.  Negative (DART_MPC_EINVAL) for n < 1,
+ * iterations < 0 or a fill that is negative, >= n or not a multiple of m. */
+int dart_lmpc_global_fill_after(int n, int fill, int iterations);
+/* Bytes of the global update's workspace (the choice [m], the sequence's advantages and returns [G], the
+ * bootstrap value, the sample list [G], the permutations [epochs][G], the update's statistics and
+ * dart_lmpc_ppo_workspace_bytes(G, mini_batch_size)); 0 for n < 1, epochs < 0 or a mini_batch_size outside
+ * 1 .. 1024. */
+size_t dart_lmpc_global_workspace_bytes(int n, int epochs, int mini_batch_size);
+
+/* Buffer row g->fill + j <- record sample[choice[j]] for j < m: sample [n] holds flat record indices row * B + b into
+ * the record arrays of rec_rows_times_B entries (as dart_lmpc_ppo_update_dev reads them), choice [m] positions in
+ * sample.  All six fields are copied bit for bit; nothing outside rows fill .. fill + m - 1 is written.  EINVAL
+ * before any device work: m < 1, n < 1, g->fill < 0, g->fill + m > g->capacity, a null pointer; the device entry
+ * also refuses rec_obs or g->obs not 16-byte aligned (the observation rows move in 16-byte pieces), the host entry a
+ * choice entry outside [0, n) and a sample entry outside [0, rec_rows_times_B) (on the device such an entry writes
+ * nothing).  global_log and workspace are not used. */
+int dart_lmpc_global_append_dev(const dart_lmpc_global_buffer *g, int m, int n, int rec_rows_times_B,
+                                const int32_t *sample, const int32_t *choice,
+                                const float *rec_obs, const float *rec_action, const float *rec_logp,
+                                const float *rec_value, const double *rec_reward, const float *rec_done,
+                                void *hip_stream);
+int dart_lmpc_global_append(const dart_lmpc_global_buffer *g, int m, int n, int rec_rows_times_B,
+                            const int32_t *sample, const int32_t *choice,
+                            const float *rec_obs, const float *rec_action, const float *rec_logp,
+                            const float *rec_value, const double *rec_reward, const float *rec_done);
+
+/* compute_gae (rlmpc2.py:592-599) over rows 0 .. G-1 as a single chain, fp64, bootstrapped from last_value [1]:
+ * adv [G] and ret = adv + value [G]; rows >= G are left untouched.  One workgroup evaluates the recurrence
+ * gae_t = delta_t + gamma lam (1 - done_t) gae_{t+1} as a suffix scan of affine maps, so the result is the sequential
+ * recursion's up to reassociation: |d adv_t| <= 32 * 2^-52 * A_t for G <= 4096, A the same recursion on |delta_t|
+ * (DESIGN.md section 6a has the count of roundings).  delta_t itself has the sequential recursion's bits. */
+int dart_lmpc_gae_seq_dev(int G, double gamma, double lam, const double *reward, const float *value,
+                          const float *done, const float *last_value, double *adv, double *ret, void *hip_stream);
+int dart_lmpc_gae_seq(int G, double gamma, double lam, const double *reward, const float *value,
+                      const float *done, const float *last_value, double *adv, double *ret);
+
+/* dart_lmpc_train(_dev) with the global-buffer update; with g == NULL they are dart_lmpc_train(_dev), bit for bit.
+ * With n = R B, (m, G) = dart_lmpc_global_rows(n) and the running fill starting at g->fill, every iteration `it`
+ * runs steps 1 - 6 of dart_lmpc_train_dev, then
+ *   6a. dart_lmpc_choice_dev(seed, it, n, m) and dart_lmpc_global_append_dev at the running fill (fill += m);
+ *   6b. if the fill has reached n (it then equals G): dart_lmpc_critic_value_dev on row G - 1's observation,
+ *       dart_lmpc_gae_seq_dev (gamma, lam), the sample list 0 .. G-1, dart_lmpc_perms_stream_dev with stream 3 over
+ *       G, and dart_lmpc_ppo_update_dev on the buffer's arrays (n = rec_rows_times_B = G) with the same weights,
+ *       critic, adam and adam_step in place -- Adam's step count runs on through both updates, as the reference's
+ *       single optimizer does; the fill returns to 0;
+ * then steps 7 and 8: the parameter write and the snapshot see the weights after both updates.  Row it - it0 of
+ * global_log: the fill after the append, 1 if the update ran, G, and that update's mean policy loss, value loss and
+ * entropy (NaN when it did not run).  The host computes the whole launch sequence from n and g->fill.
+ * EINVAL before any device work: a fill that is negative, >= n or not a multiple of m, capacity < G, a null
+ * pointer, obs or rec_obs not 16-byte aligned.  Calls chain: g->fill of the next call is
+ * dart_lmpc_global_fill_after(n, g->fill, iterations). */
+int dart_lmpc_train_global_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                               const dart_lmpc_policy_config *pcfg, const dart_lmpc_reward_config *rcfg,
+                               const dart_lmpc_ppo_config *ppo, const dart_lmpc_train_config *cfg, int B,
+                               int reset_rows, const dart_lmpc_train_buffers *buf,
+                               const dart_lmpc_global_buffer *g, void *hip_stream);
+/* Host pointers: as dart_lmpc_train, and the buffer's held rows (0 .. g->fill - 1) are staged in once and the rows
+ * held at the end (0 .. dart_lmpc_global_fill_after(...) - 1) are staged out; other rows of the host arrays are
+ * left untouched. */
+int dart_lmpc_train_global(dart_mpc_handle *h, const dart_plant_config *plant,
+                           const dart_lmpc_policy_config *pcfg, const dart_lmpc_reward_config *rcfg,
+                           const dart_lmpc_ppo_config *ppo, const dart_lmpc_train_config *cfg, int B,
+                           int reset_rows, const dart_lmpc_train_buffers *buf,
+                           const dart_lmpc_global_buffer *g, void *hip_stream);
 
 int dart_mpc_sync(dart_mpc_handle *h);
 

@@ -10,11 +10,14 @@ call enqueues all of them -- the noise and the permutations come from the device
 parameter write and the best-policy snapshot of the reference loop are part of every iteration -- and prints the
 same line per iteration from the log rows; with it --checkpoint PATH writes the training state (ppo.save_checkpoint,
 one .npz without pickle) at the end and --resume PATH continues from one (the loop state and the plants start
-afresh).
+afresh).  With --global-update (resident only) every iteration also runs the reference's second update on the
+global buffer (rlmpc2.py:823-874; ppo.new_global_buffer): a quarter of its records is appended to a buffer that
+survives across iterations and is updated on once it holds a full iteration's worth; the buffer is saved and resumed
+with the checkpoint, so a run can stop in the middle of a fill period.
 The loop state, the collection state, the targets and the plants carry over from iteration to iteration.
 Prints the mean return of the episodes that ended, per iteration.
 Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps] [--update device|torch|resident]
-                                  [--checkpoint PATH] [--resume PATH] [--seed S]
+                                  [--global-update] [--checkpoint PATH] [--resume PATH] [--seed S]
 """
 import os
 import sys
@@ -47,6 +50,11 @@ def _option(name):
     return v
 
 
+global_update = "--global-update" in argv
+if global_update:
+    argv.remove("--global-update")
+    if update != "resident":
+        sys.exit("--global-update goes with --update resident")
 ckpt_out, ckpt_in, seed = _option("--checkpoint"), _option("--resume"), int(_option("--seed") or 0)
 if (ckpt_out or ckpt_in) and update != "resident":
     sys.exit("--checkpoint and --resume go with --update resident")
@@ -83,6 +91,7 @@ def resident():
     if K % int(rcfg.record_every):
         sys.exit(f"--update resident needs K to be a multiple of record_every = {int(rcfg.record_every)}")
     best, it0 = ppo.new_best(), 0
+    gbuf = ppo.new_global_buffer(B * (K // int(rcfg.record_every))) if global_update else None
     if ckpt_in:
         c = ppo.load_checkpoint(ckpt_in)
         if c["obs_count"].shape[0] != B:
@@ -94,19 +103,29 @@ def resident():
         policy.current_k[:] = c["current_k"]
         for k in ("obs_mean", "obs_M2", "obs_count", "history", "model_params"):
             state[k][:] = c[k]
+        held = ppo.global_buffer_from_checkpoint(c)
+        if global_update and held is not None:
+            if held["logp"].shape != gbuf["logp"].shape:
+                sys.exit(f"{ckpt_in} holds a global buffer of {held['logp'].shape[0]} rows, this run needs "
+                         f"{gbuf['logp'].shape[0]}")
+            gbuf = held
     rows = ppo.train_device(solver, policy, target, pvec, state, cs, adam, adam_step, best, K, iterations=iters,
                             it0=it0, seed=seed, rcfg=rcfg, pool=pool, gamma=GAMMA, lam=LAM, epochs=8,
-                            mini_batch_size=64, clip_eps=0.2, vf_coef=0.25, ent_coef=0.01)
+                            mini_batch_size=64, clip_eps=0.2, vf_coef=0.25, ent_coef=0.01, global_buffer=gbuf)
     for j, r in enumerate(rows):
         print(f"iter {it0 + j}: samples {int(r['n'])}, episodes ended {int(r['episodes_ended'])}, "
               f"mean last return {r['mean_return']:.2f}, mean step reward {r['mean_step_reward']:.3f}, "
               f"status != 0: {r['status_nonzero']:.4f}, policy loss {r['policy_loss']:.4f}, "
               f"value loss {r['value_loss']:.4f}, entropy {r['entropy']:.3f}, best return {r['best_return']:.2f}"
               f"{' (snapshot)' if r['snapshot'] else ''}", flush=True)
+        if gbuf is not None:
+            tail = (f", update on {int(r['global_rows'])} rows: policy loss {r['global_policy_loss']:.4f}, value loss "
+                    f"{r['global_value_loss']:.4f}, entropy {r['global_entropy']:.3f}" if r["global_update"] else "")
+            print(f"        global buffer {int(r['global_fill'])} rows{tail}", flush=True)
     if ckpt_out:
         path = ppo.save_checkpoint(ckpt_out, policy.weights, policy.critic_weights, adam, adam_step, best, it0 + iters,
                                    state["obs_mean"], state["obs_M2"], state["obs_count"], state["history"],
-                                   policy.current_k, state["model_params"])
+                                   policy.current_k, state["model_params"], global_buffer=gbuf)
         print(f"checkpoint: {path} (iteration {it0 + iters}, best return {float(best['best_return'][0]):.2f} "
               f"at iteration {int(best['best_iter'][0])})", flush=True)
 

@@ -4,7 +4,11 @@ device unchanged: numpy noise staged to the device, the blocking host entries co
 ppo_update, the sample list in numpy and the permutations from torch.randperm.
 Contenders: host_sequenced; resident_dev (train_dev with one iteration on device-resident arrays, then a
 synchronise); resident_host (LmpcSolver.train with one iteration: state, weights and Adam's state staged in, logs and
-records staged out); resident_host_x4 (one LmpcSolver.train call of four iterations, per iteration).
+records staged out); resident_host_x4 (one LmpcSolver.train call of four iterations, per iteration);
+resident_dev_global (train_global_dev: the iteration with the global-buffer update of rlmpc2.py:823-874, one call of
+one full fill period of ceil(n / m) iterations -- one of them carries the second update -- per iteration).  A library
+that predates the global-buffer entries (an A/B build of the parent commit, DART_MPC_AB=1 DART_MPC_LIB=...) runs
+without that contender.
 Shapes: B = 72, K = 256 (tools/lmpc_train.py's, 2304 samples) and B = 18, K = 512 (1152 samples); episodes of 64
 steps, 8 epochs of mini-batches of 64, N = 30.
 Protocol of tools/rollout_rate.py: the contenders alternate in one process, one warm-up each, then five rounds each;
@@ -12,6 +16,8 @@ a host clock around work that ends in a synchronise; medians with the min-to-max
 own training state from round to round, so the rounds are consecutive iterations of a training run.
 Usage: python tools/train_rate.py [out.json] [rounds]
        python tools/train_rate.py --once B K [iterations]   (resident iterations and nothing else: for a kernel trace)
+       python tools/train_rate.py --micro B K [out.json]    (the global update's small launches on their own: a HIP
+                                                              event pair around one launch, 5 warm-ups, 30 repeats)
 """
 import json
 import os
@@ -30,6 +36,7 @@ from dart_mpc.workload import lmpc_batch  # noqa: E402
 GAMMA, LAM, N, EP_STEPS, EPOCHS, MB = 0.99, 0.95, 30, 64, 8, 64
 HYPER = dict(clip_eps=0.2, vf_coef=0.25, ent_coef=0.01)
 SHAPES = ((72, 256), (18, 512))
+HAVE_GLOBAL = hasattr(_lib.lib(), "dart_lmpc_train_global_dev")
 
 
 class Run:
@@ -104,7 +111,31 @@ class Run:
         self.dev["tr"]["workspace"] = torch.zeros(_lib.train_workspace_bytes(B, K, self.every, EPOCHS, MB),
                                                   dtype=torch.uint8, device="cuda")
         self.cfg = _lib.ppo_config(epochs=EPOCHS, mini_batch_size=MB, **HYPER)
+        n = B * R
+        self.period = -(-n // _lib.global_rows(n)[0]) if HAVE_GLOBAL else 1
+        if HAVE_GLOBAL:
+            G = _lib.global_rows(n)[1]
+            self.dev["gb"] = {f: torch.zeros((G, w) if w else (G,), dtype=getattr(torch, np.dtype(dt).name),
+                                             device="cuda") for f, w, dt in _lib.LMPC_GLOBAL_ARRAYS}
+            self.glog = torch.zeros(self.period, _lib.GLOBAL_LOG_COLS, dtype=torch.float64, device="cuda")
+            self.gws = torch.zeros(_lib.global_workspace_bytes(n, EPOCHS, MB), dtype=torch.uint8, device="cuda")
+            self.fill, self.G, self.n = 0, G, n
         torch.cuda.synchronize()
+
+    def resident_dev_global(self):
+        """One full fill period of the iteration with the global-buffer update, in one call."""
+        d = self.dev
+        p = lambda g: {k: v.data_ptr() for k, v in d[g].items()}
+        tcfg = _lib.train_config(seed=0, iterations=self.period, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
+        g = _lib.global_buffer(p("gb"), self.G, self.fill, global_log=self.glog.data_ptr(), workspace=self.gws.data_ptr())
+        self.solver.train_global_dev(self.B, 4, d["c"]["target"].data_ptr(), d["c"]["prm"].data_ptr(),
+                                     d["c"]["pvec"].data_ptr(), d["c"]["current_k"].data_ptr(),
+                                     d["c"]["weights"].data_ptr(), d["c"]["critic"].data_ptr(), p("st"), p("cs"), p("lg"),
+                                     p("clg"), p("rec"), p("tr"), self.policy.cfg, self.rcfg, self.cfg, tcfg, g,
+                                     pool=p("pool"))
+        self.solver.sync()
+        self.fill = _lib.global_fill_after(self.n, self.fill, self.period)
+        self.it += self.period
 
     def resident_dev(self, iterations=1):
         d = self.dev
@@ -127,10 +158,16 @@ def timed(fn):
 def measure(B, K, rounds):
     runs = {name: Run(B, K) for name in ("host_sequenced", "resident_dev", "resident_host", "resident_host_x4")}
     runs["resident_dev"].to_device()
+    if HAVE_GLOBAL:
+        runs["resident_dev_global"] = Run(B, K)
+        runs["resident_dev_global"].to_device()
     calls = {"host_sequenced": (runs["host_sequenced"].host_sequenced, 1),
              "resident_dev": (runs["resident_dev"].resident_dev, 1),
              "resident_host": (runs["resident_host"].resident_host, 1),
              "resident_host_x4": (lambda: runs["resident_host_x4"].resident_host(4), 4)}
+    if HAVE_GLOBAL:
+        g = runs["resident_dev_global"]
+        calls["resident_dev_global"] = (g.resident_dev_global, g.period)
     times = {name: [] for name in calls}
     try:
         for r in range(rounds + 1):                 # round 0 is the warm-up
@@ -145,6 +182,8 @@ def measure(B, K, rounds):
     for name, t in times.items():
         out[name] = {"median_ms": float(np.median(t)), "min_ms": float(min(t)), "max_ms": float(max(t)), "all_ms": t}
     base = out["host_sequenced"]
+    if HAVE_GLOBAL:
+        out["resident_dev_global"]["fill_period"] = runs["resident_dev_global"].period
     for name in ("resident_dev", "resident_host", "resident_host_x4"):
         o = out[name]
         out[name]["speedup_vs_host_sequenced"] = {"median": base["median_ms"] / o["median_ms"],
@@ -153,8 +192,59 @@ def measure(B, K, rounds):
     return out
 
 
+def micro(B, K):
+    """Event timing of the choice, the record gather, the sequence GAE and the stream-3 permutations at the shape's
+    n = B K / record_every (launch overhead included: one launch between the two events)."""
+    n = B * (K // int(_lib.reward_config().record_every))
+    m, G = _lib.global_rows(n)
+    rng = np.random.default_rng(0)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    f32 = lambda *shape: dev(rng.standard_normal(shape).astype(np.float32))
+    rec = dict(rec_obs=f32(n, 520), rec_action=f32(n, 34), rec_logp=f32(n), rec_value=f32(n),
+               rec_reward=dev(rng.standard_normal(n)), rec_done=dev((rng.random(n) < 0.1).astype(np.float32)))
+    gb = {f: torch.zeros((G, w) if w else (G,), dtype=getattr(torch, np.dtype(dt).name), device="cuda")
+          for f, w, dt in _lib.LMPC_GLOBAL_ARRAYS}
+    sample = dev(np.arange(n, dtype=np.int32))
+    choice = torch.zeros(m, dtype=torch.int32, device="cuda")
+    perm = torch.zeros(EPOCHS, G, dtype=torch.int32, device="cuda")
+    last = torch.zeros(1, dtype=torch.float32, device="cuda")
+    adv = torch.zeros(G, dtype=torch.float64, device="cuda")
+    ret = torch.zeros_like(adv)
+    p = lambda d: {k: v.data_ptr() for k, v in d.items()}
+    s = torch.cuda.current_stream().cuda_stream
+    g = _lib.global_buffer(p(gb), G, 0)
+    calls = {"choice": lambda: _lib.choice_dev(3, 1, n, m, choice.data_ptr(), stream=s),
+             "append": lambda: _lib.global_append_dev(g, m, n, n, sample.data_ptr(), choice.data_ptr(), p(rec), stream=s),
+             "gae_seq": lambda: _lib.gae_seq_dev(G, GAMMA, LAM, gb["reward"].data_ptr(), gb["value"].data_ptr(),
+                                                 gb["done"].data_ptr(), last.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                                                 stream=s),
+             "perms_stream_3": lambda: _lib.perms_stream_dev(3, 1, 3, EPOCHS, G, perm.data_ptr(), stream=s)}
+    out = {"B": B, "K": K, "n": n, "m": m, "G": G}
+    for name, fn in calls.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(30):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        out[name] = {"median_us": float(np.median(us)), "min_us": float(min(us)), "max_us": float(max(us))}
+        print(f"{name}: {out[name]['median_us']:.1f} us ({out[name]['min_us']:.1f}-{out[name]['max_us']:.1f})", flush=True)
+    return out
+
+
 def main():
     argv = sys.argv[1:]
+    if argv and argv[0] == "--micro":
+        res = micro(int(argv[1]), int(argv[2]))
+        if len(argv) > 3:
+            with open(argv[3], "w") as fh:
+                json.dump(res, fh, indent=1)
+        return
     if argv and argv[0] == "--once":
         B, K = int(argv[1]), int(argv[2])
         run = Run(B, K)
@@ -167,13 +257,14 @@ def main():
     path = argv[0] if argv else os.path.join(ROOT, "profiles", "collect", "train_rate.json")
     rounds = int(argv[1]) if len(argv) > 1 else 5
     res = {"tool": "tools/train_rate.py", "device": torch.cuda.get_device_name(0), "N": N, "episode_steps": EP_STEPS,
-           "epochs": EPOCHS, "mini_batch_size": MB, "shapes": []}
+           "epochs": EPOCHS, "mini_batch_size": MB, "library": _lib.LIB_NAME, "shapes": []}
     for B, K in SHAPES:
         r = measure(B, K, rounds)
         res["shapes"].append(r)
         print(f"B = {B}, K = {K}: " + ", ".join(
             f"{n} {r[n]['median_ms']:.1f} ms ({r[n]['min_ms']:.1f}-{r[n]['max_ms']:.1f})"
-            for n in ("host_sequenced", "resident_dev", "resident_host", "resident_host_x4")), flush=True)
+            for n in ("host_sequenced", "resident_dev", "resident_host", "resident_host_x4", "resident_dev_global")
+            if n in r), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as fh:
         json.dump(res, fh, indent=1)
