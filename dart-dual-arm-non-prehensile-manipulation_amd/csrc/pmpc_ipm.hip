@@ -399,8 +399,8 @@ __device__ __forceinline__ bool pmpc_riccati(const int lane, const int N, const 
 // The overlapped build (OVL; NAX == 1, QSCAN, one wave per instance, launched with two waves): LDS hand-over
 // between the solver wave (wave 0) and the factor wave (wave 1).  [field][lane]: every access is one
 // conflict-free 8-byte access per lane.  pt: th, snc, lp, lv, zl, zu of the current point (wave 0 writes
-// before barrier A, wave 1 reads after it); fc: P11, P12, P22, W1, W2, iQs (wave 1 writes before barrier B,
-// wave 0 reads after it); flag: [0] stop, [1] use_scan, [2] ok.  Each buffer has one writer, and its next write
+// before barrier A, wave 1 reads after it; wave 0 reads its own zl, zu back when the speculated point is taken);
+// fc: P11, P12, P22, W1, W2, iQs (wave 1 writes before barrier B, wave 0 reads after it); flag: [0] stop, [1] use_scan, [2] ok.  Each buffer has one writer, and its next write
 // comes after a barrier that the reader crosses only with its reads complete, so single buffers are enough.
 struct PmOvlShared {
     double pt[6][kWave];
@@ -497,7 +497,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         // factor it at delta = 0 (attempt 0 of the iteration's Riccati block), publish the result (barrier B).  It
         // tests the stop word after every barrier and leaves the kernel when it is set (pmpc_solve's exit funnel).
         if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0) {
-            for (;;) {
+            // Rounds: the start point, then per iteration the speculated first trial point and, where that trial is
+            // not the accepted step, the accepted point: at most 1 + 2 max_iter.  The bound only ends a wave that a
+            // protocol slip would otherwise leave at a barrier for ever (a terminated wave takes no part in one).
+            const long long max_rounds = 2ll * a.max_iter + 8;
+            for (long long round = 0; round < max_rounds; ++round) {
                 __syncthreads();                                            // barrier A, or the stop barrier
                 if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return false;
 #ifdef DART_STAMPS
@@ -530,6 +534,7 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 __syncthreads();                                            // barrier B, or the stop barrier
                 if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return false;
             }
+            return false;
         }
         if (lane == 0) g_pm_ovl.flag[0] = 0;      // the solver wave, before its first barrier
     }
@@ -603,11 +608,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
     int in_soft = 0, soft_count = 0;
     STAMP(0);
 
-    // OVL: the current point to the factor wave, then barrier A.  Called as early as the point is known: for the
-    // start point at the first Newton iteration, then in the accepted update as soon as theta, lambda and z of
-    // the new point exist, so that the rest of the update, the evaluation, the error reductions and the mu update
-    // all run while the factor wave works.  The scheduling barriers keep the compiler from moving that work (plain
-    // register arithmetic, which __syncthreads() does not order) ahead of barrier A.
+    // OVL: the current point to the factor wave, then barrier A.  Called for the start point at the first Newton
+    // iteration, and in the accepted update where the step taken is not the line search's first trial point (that
+    // point is handed over speculatively before the trial, below; the update then first crosses barrier B to drop
+    // the factors of the rejected point).  The scheduling barriers keep the compiler from moving the work that
+    // follows (plain register arithmetic, which __syncthreads() does not order) ahead of barrier A.
     bool published = false;
     auto publish = [&]() {
         __builtin_amdgcn_sched_barrier(0);
@@ -633,8 +638,9 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         if (it == 1) t_acc_[12] = __builtin_amdgcn_s_memtime() - t_loop0;      // the first iteration (cold code)
 #endif
         if constexpr (OVL) {
-            // the start point (every later point is published by the update that accepted it); the least-square
-            // iteration keeps its factorisation (unit weights) in this wave and crosses no barrier
+            // the start point (every later point is published by the line search of the iteration before, or by its
+            // update); the least-square iteration keeps its factorisation (unit weights) in this wave and crosses
+            // no barrier
             if (PM_EXPECT(!lsm && !published, 0)) publish();
         }
         // -------- point quantities and optimality error (IPOPT eq. 5) ------------
@@ -997,6 +1003,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         bool accepted = false, ftype = false, tiny = false;
         int ls = 0, soc = 0;        // soc: 0 Newton step, 1.. correction pass, -1 Newton step again after failed passes
         double snt[NAX], g1t[NAX], g2t[NAX], gzt[NAX];     // the trial's sines and defects (carried on acceptance)
+        // OVL: the sine of the first trial point, formed with the speculative hand-over below (sn_pre_on: the next
+        // trial takes it in place of its own tilt_sincos of the same angle, so the factor wave gets the trial's bits)
+        double sn_pre = 0.0;
+        bool sn_pre_on = false;
+        (void)sn_pre; (void)sn_pre_on;
         // trial point x + al d: defects, wave-summed theta and barrier objective
         auto trial = [&](double al) {
             double thl = 0.0, phl = 0.0, tt[NAX];
@@ -1029,9 +1040,13 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             for (int j = 0; j < NAX; ++j) {
                 const double pt = fma(al, dp[j], p[j]), vt = fma(al, dv[j], v[j]);
                 tt[j] = fma(al, dth[j], th[j]);
-                double s_, c_;
-                tilt_sincos(poly, tt[j], s_, c_);
-                snt[j] = uon ? s_ : 0.0;
+                if (OVL && PM_EXPECT(sn_pre_on, 1)) {
+                    snt[j] = sn_pre; sn_pre_on = false;
+                } else {
+                    double s_, c_;
+                    tilt_sincos(poly, tt[j], s_, c_);
+                    snt[j] = uon ? s_ : 0.0;
+                }
                 defects(pt, vt, snt[j], sp[j], sv[j], g1t[j], g2t[j]);
                 const double ep = pt - rp[j], ev = vt - rv[j];
                 thl += xon ? fabs(g1t[j]) + fabs(g2t[j]) : 0.0;
@@ -1113,6 +1128,27 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 amin *= gam_al;
                 tiny = tn_w < 2.2e-15f;
                 alpha = amax; amain = amax;
+                if constexpr (OVL) {
+                    // The speculative hand-over.  The first trial is the Newton step at alpha = amax, and where it
+                    // is accepted (most iterations) the accepted point is this trial point: theta, lambda and z by
+                    // the expressions of the accepted update below, operand for operand, and the trial's sine.  The
+                    // factor wave starts on it here (barrier A), so the trial, the acceptance test, the update, the
+                    // evaluation and the mu update all run in its shadow.  This branch runs once per Newton
+                    // iteration (soc == 0 is entered with ls == 0 only), always after this iteration's barrier B.
+                    const double thc = fma(alpha, dth[0], th[0]);
+                    double s_, c_;
+                    tilt_sincos(poly, thc, s_, c_);
+                    sn_pre = uon ? s_ : 0.0; sn_pre_on = true;
+                    const double il = frcp(thc - lo), iu = frcp(hi - thc);
+                    const double zln = fmax(fmin(fma(az, dzl[0], zl[0]), 1e10 * mu * il), 1e-10 * mu * il);   // kappa_sigma
+                    const double zun = fmax(fmin(fma(az, dzu[0], zu[0]), 1e10 * mu * iu), 1e-10 * mu * iu);
+                    __builtin_amdgcn_sched_barrier(0);
+                    g_pm_ovl.pt[0][lane] = thc; g_pm_ovl.pt[1][lane] = sn_pre;
+                    g_pm_ovl.pt[2][lane] = fma(alpha, dlp[0], lp[0]); g_pm_ovl.pt[3][lane] = fma(alpha, dlv[0], lv[0]);
+                    g_pm_ovl.pt[4][lane] = uon ? zln : 0.0; g_pm_ovl.pt[5][lane] = uon ? zun : 0.0;
+                    __syncthreads();                                        // barrier A
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             } else if (soc > 0) {
                 alpha = amax;                 // alpha_soc: fraction to the boundary of the corrected step
             }
@@ -1258,18 +1294,38 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             ++nfilt;
         }
         // -------- accept the step ----------------------------------------------------
-        // (the quantities the factor wave needs come first: the overlapped build hands them over before the rest)
+        // (the quantities the factor wave needs come first: a miss of the overlapped build hands them over before the rest)
+        // OVL, hit: the step taken is the first trial point, which the factor wave already has and may be reading,
+        // so nothing is written to pt and no barrier is crossed; z comes back from this wave's own pt entries (the
+        // clamp was evaluated for the hand-over).  Miss (a backtracked step, an accepted correction pass, the Newton
+        // step again after failed passes): barrier B first, the factors of the rejected trial point are dropped
+        // unread, then the accepted point goes over at barrier A as the start point did.
+        const bool hit = OVL && soc == 0 && ls == 0;
+        if constexpr (OVL) {
+            STAMP_ADD(15, hit ? (1ull << 16) : (1ull << 32));      // (stamps build: hits, misses beside the corrections)
+            if (PM_EXPECT(!hit, 0)) {
+                __builtin_amdgcn_sched_barrier(0);
+                __syncthreads();                                            // barrier B (discarded round)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
 #pragma unroll
         for (int j = 0; j < NAX; ++j) {
             snc[j] = snt[j];
             lp[j] = fma(alpha, dlp[j], lp[j]); lv[j] = fma(alpha, dlv[j], lv[j]);
             th[j] = fma(alpha, dth[j], th[j]);
-            const double il = frcp(th[j] - lo), iu = frcp(hi - th[j]);
-            const double zln = fmax(fmin(fma(az, dzl[j], zl[j]), 1e10 * mu * il), 1e-10 * mu * il);   // kappa_sigma
-            const double zun = fmax(fmin(fma(az, dzu[j], zu[j]), 1e10 * mu * iu), 1e-10 * mu * iu);
-            zl[j] = uon ? zln : 0.0; zu[j] = uon ? zun : 0.0;
+            if (OVL && PM_EXPECT(hit, 1)) {
+                zl[j] = g_pm_ovl.pt[4][lane]; zu[j] = g_pm_ovl.pt[5][lane];
+            } else {
+                const double il = frcp(th[j] - lo), iu = frcp(hi - th[j]);
+                const double zln = fmax(fmin(fma(az, dzl[j], zl[j]), 1e10 * mu * il), 1e-10 * mu * il);   // kappa_sigma
+                const double zun = fmax(fmin(fma(az, dzu[j], zu[j]), 1e10 * mu * iu), 1e-10 * mu * iu);
+                zl[j] = uon ? zln : 0.0; zu[j] = uon ? zun : 0.0;
+            }
         }
-        if constexpr (OVL) publish();
+        if constexpr (OVL) {
+            if (PM_EXPECT(!hit, 0)) publish();
+        }
 #pragma unroll
         for (int j = 0; j < NAX; ++j) {
             g1[j] = g1t[j]; g2[j] = g2t[j]; gz[j] = gzt[j];
@@ -1281,13 +1337,15 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
     }
     if constexpr (OVL) {
         // The exit funnel of the overlapped build.  The iteration loop has no return, and every way out of it
-        // (status 0 between barriers A and B; status -3, the failed line search with its hand-over to the
-        // restoration phases or status -2, all after barrier B and before the update's barrier A; max_iter at the
-        // loop head, after the barrier A of a point that is then not used; a loop of no iterations) arrives here.
+        // (status 0 between barriers A and B; status -3 after barrier B and before the line search's barrier A; the
+        // failed line search with its hand-over to the restoration phases or status -2, after the barrier A of a
+        // speculated point that is then not used; max_iter at the loop head, likewise after a barrier A; a loop
+        // of no iterations) arrives here.  DESIGN §5.R8 has the table.
         // Invariant: this wave crosses barriers A, B, A, B, ... only in publish() (the first Newton iteration's
-        // head, the accepted update) and at the head of the Riccati block (none in the least-square iteration, its
-        // `continue` included, in the retries or in the correction passes), then sets the stop word and crosses
-        // exactly one more barrier, here.  The
+        // head, the update of a missed speculation), at the speculative hand-over of the line search (A), at the
+        // head of the Riccati block (B) and in the update of a missed speculation (B) (none in the least-square
+        // iteration, its `continue` included, in the retries or in the correction passes), then sets the stop word
+        // and crosses exactly one more barrier, here.  The
         // factor wave crosses a barrier, tests the stop word and goes on to the next barrier, so it meets each of
         // this wave's barriers in turn whatever their role, and leaves at the first test that finds the word set:
         // after the stop barrier at the latest (or earlier, having seen the word before this wave arrived; a

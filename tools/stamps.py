@@ -38,8 +38,12 @@ for i, n in enumerate(PHASES):
 print(f"  scan-path Riccati passes {int(st[11])}")
 it0 = int(st[0:9].sum() - st[0] - st[8])
 print(f"  first iteration {int(st[12])} cycles, mean iteration {it0 / max(1, out['iters'][0]):.0f} cycles")
-print(f"  riccati passes {int(st[9])}, line-search trials {int(st[10])}, iterations with a correction {int(st[15])}")
+print(f"  riccati passes {int(st[9])}, line-search trials {int(st[10])}, iterations with a correction {int(st[15]) & 0xffff}")
 if st[13]:
+    # the overlapped build hands the first line-search trial point over before the trial: accepted updates that
+    # found it right (hits) and that had to drop its factors and hand the accepted point over (misses); slot 15
+    # holds both beside the corrections, 16 bits each
+    print(f"  speculative hand-over: {(int(st[15]) >> 16) & 0xffff} hits, {(int(st[15]) >> 32) & 0xffff} misses")
     # the overlapped build (B <= 32, N = 16..31): the riccati span above is the solving wave's wait for the factor
     # wave plus its LDS read; this is the factor wave's own time from barrier A to its arrival at barrier B
     print(f"  factor wave: {int(st[13])} cycles between its barriers, per-iter {st[13] / max(1, out['iters'][0]):.0f}")
