@@ -1,0 +1,748 @@
+// dart_mpc_rollout.hip -- the closed-loop entries of include/dart_mpc.h (host side): the loop-step and rollout entries
+// of the three controllers (loop_step.hip between the unchanged solves), LMPC experience step and collection
+// (lmpc_experience.hip after every post of the LMPC closed loop).
+#include "abi_internal.h"
+
+void dart_plant_config_default(dart_plant_config* c) {
+    if (!c) return;
+    c->tau = 0.03; c->mu_c = 0.02; c->v_c = 0.01;       // harness.TrayPlant
+}
+
+void dart_rmpc_loop_config_default(dart_rmpc_loop_config* c) {
+    if (!c) return;
+    c->dr_max = 0.01; c->alpha_rg = 0.5; c->step_fraction = 0.2; c->rls_lambda = 0.995; c->pos_tol = 0.01;
+}
+
+namespace {
+
+dartmpc::PlantArgs plant_args(const dart_mpc_handle* h, const dart_plant_config* p) {
+    dartmpc::PlantArgs a;
+    a.a_lag = p->tau > 0.0 ? 1.0 - std::exp(-h->cfg.Ts / p->tau) : 1.0;
+    a.mu_c = p->mu_c; a.v_c = p->v_c; a.dt = h->cfg.Ts; a.g = h->cfg.gravity;
+    return a;
+}
+
+// the checks every rollout / loop-step entry shares: the call writes the log rows k .. k + steps - 1
+int loop_check(dart_mpc_handle* h, int variant, const dart_plant_config* plant, int B, int k, int steps, int log_rows) {
+    if (h->cfg.variant != variant) return fail(h, DART_MPC_EINVAL, variant_text(variant));
+    if (!plant) return fail(h, DART_MPC_EINVAL, "null plant config");
+    // (the LMPC plant does not use mu_c / v_c)
+    if (variant != DART_MPC_LMPC && (!(plant->v_c > 0.0) || !(plant->mu_c >= 0.0)))
+        return fail(h, DART_MPC_EINVAL, "plant config: v_c > 0, mu_c >= 0");
+    if (B < 0 || k < 0 || steps < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
+    if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
+    if ((long long)k + steps > log_rows) return fail(h, DART_MPC_EINVAL, "k0 + steps exceeds log_rows");
+    return DART_MPC_OK;
+}
+
+// loop_check, RMPC's loop config, then the entry's pointers: what a PMPC / RMPC entry and its host twin both check
+int loop_entry_check(dart_mpc_handle* h, int variant, const dart_plant_config* plant, const dart_rmpc_loop_config* c,
+                     int B, int k, int steps, int log_rows, std::initializer_list<const void*> ptrs) {
+    if (int rc = loop_check(h, variant, plant, B, k, steps, log_rows)) return rc;
+    if (variant == DART_MPC_RMPC) {
+        if (!c) return fail(h, DART_MPC_EINVAL, "null loop config");
+        if (!(c->rls_lambda > 0.0) || !(c->dr_max >= 0.0) || !(c->step_fraction >= 0.0 && c->step_fraction <= 1.0))
+            return fail(h, DART_MPC_EINVAL, "loop config: rls_lambda > 0, dr_max >= 0, 0 <= step_fraction <= 1");
+    }
+    if (any_null(ptrs)) return fail(h, DART_MPC_EINVAL, "null pointer");
+    return DART_MPC_OK;
+}
+
+// The handle's rollout scratch (B_max instances): n blocks of cnt[i] bytes per instance, 256-byte aligned, allocated
+// on first use with the blocks from `zero_from` on cleared; ptr[i] receives block i
+int scratch_blocks(dart_mpc_handle* h, int n, const size_t* cnt, int zero_from, char** ptr) {
+    size_t off = 0;
+    size_t at[16];
+    for (int i = 0; i < n; ++i) {
+        at[i] = off;
+        off += align256(cnt[i] * (size_t)h->cfg.B_max);
+    }
+    if (!h->loop_buf) {
+        HIPCHK(h, hipMalloc((void**)&h->loop_buf, off), "hipMalloc (rollout scratch)");
+        const hipError_t e = zero_from < n ? hipMemset(h->loop_buf + at[zero_from], 0, off - at[zero_from]) : hipSuccess;
+        if (e != hipSuccess) {
+            (void)hipFree(h->loop_buf);
+            h->loop_buf = nullptr;
+            return fail(h, DART_MPC_EHIP, "hipMemset (rollout scratch)", e);
+        }
+    }
+    for (int i = 0; i < n; ++i) ptr[i] = h->loop_buf + at[i];
+    return DART_MPC_OK;
+}
+
+// the solve's per-step arrays of a PMPC / RMPC rollout
+struct LoopScratch {
+    double *x0, *Rref, *phi, *y, *u0, *f;
+    int32_t *status, *iters;
+};
+
+int loop_scratch(dart_mpc_handle* h, LoopScratch& L) {
+    const size_t N1 = (size_t)h->cfg.N + 1;
+    const bool rm = h->cfg.variant == DART_MPC_RMPC;
+    const size_t r = rm ? 1 : 0;         // (Rref, phi and y are RMPC's)
+    const size_t cnt[8] = {8 * (rm ? 4u : 6u), 8 * 4 * N1 * r, 8 * 7 * r, 8 * 2 * r, 8 * 2, 8, 4, 4};
+    char* p[8];
+    // (no initialisation: pre writes what the solve reads, the solve writes what post reads)
+    if (int rc = scratch_blocks(h, 8, cnt, 8, p)) return rc;
+    L.x0 = (double*)p[0]; L.Rref = (double*)p[1]; L.phi = (double*)p[2]; L.y = (double*)p[3];
+    L.u0 = (double*)p[4]; L.f = (double*)p[5]; L.status = (int32_t*)p[6]; L.iters = (int32_t*)p[7];
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_rmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                            int B, int k, int do_post, int do_pre, int log_rows,
+                            const double* target, const double* prm, const double* mu,
+                            double* x, double* tilt, double* prev, double* u_prev, double* r_v, const double* theta,
+                            int32_t* done, int32_t* nlog,
+                            double* x0, double* Rref, double* phi, double* y,
+                            const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                            double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                            double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                            int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = loop_entry_check(h, DART_MPC_RMPC, plant, loop, B, k, do_post ? 1 : 0, log_rows,
+                                  {target, prm, mu, x, tilt, prev, u_prev, r_v, theta, done, nlog, x0, Rref, phi, y, u0,
+                                   f, status, iters, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x,
+                                   log_theta, log_r_v, log_f, log_status, log_iters}))
+        return rc;
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    dartmpc::RmpcLoopArgs a;
+    a.B = B; a.N = h->cfg.N; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+    a.plant = plant_args(h, plant);
+    a.Ts = h->cfg.Ts; a.dr_max = loop->dr_max; a.alpha_rg = loop->alpha_rg; a.step_fraction = loop->step_fraction;
+    a.pos_tol = loop->pos_tol;
+    a.target = target; a.prm = prm; a.mu = mu;
+    a.x = x; a.tilt = tilt; a.prev = prev; a.u_prev = u_prev; a.r_v = r_v; a.theta = theta; a.done = done; a.nlog = nlog;
+    a.x0 = x0; a.Rref = Rref; a.phi = phi; a.y = y; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
+    a.log_pos_err = log_pos_err; a.log_pos_err_norm = log_pos_err_norm; a.log_u_cmd = log_u_cmd;
+    a.log_timestep = log_timestep; a.log_x = log_x; a.log_theta = log_theta; a.log_r_v = log_r_v; a.log_f = log_f;
+    a.log_status = log_status; a.log_iters = log_iters;
+    HIPCHK(h, dartmpc_launch_rmpc_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
+    return DART_MPC_OK;
+}
+
+int dart_pmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                            int B, int k, int do_post, int do_pre, int log_rows, const double* prm,
+                            double* x, double* tilt, double* x0,
+                            const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                            double* log_X, double* log_U, double* log_quat, double* log_loss,
+                            int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = loop_entry_check(h, DART_MPC_PMPC, plant, nullptr, B, k, do_post ? 1 : 0, log_rows,
+                                  {prm, x, tilt, x0, u0, f, status, iters, log_X, log_U, log_quat, log_loss, log_status,
+                                   log_iters}))
+        return rc;
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    dartmpc::PmpcLoopArgs a;
+    a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+    a.plant = plant_args(h, plant);
+    a.prm = prm; a.x = x; a.tilt = tilt; a.x0 = x0; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
+    a.log_X = log_X; a.log_U = log_U; a.log_quat = log_quat; a.log_loss = log_loss; a.log_status = log_status;
+    a.log_iters = log_iters;
+    HIPCHK(h, dartmpc_launch_pmpc_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
+    return DART_MPC_OK;
+}
+
+int dart_rmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                          int B, int k0, int steps, int log_rows,
+                          const double* target, const double* prm, const double* mu,
+                          double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
+                          double* P, double* w, int32_t* done, int32_t* nlog,
+                          double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                          double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                          int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = loop_entry_check(h, DART_MPC_RMPC, plant, loop, B, k0, steps, log_rows,
+                                  {target, prm, mu, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog, log_pos_err,
+                                   log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v, log_f,
+                                   log_status, log_iters}))
+        return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    LoopScratch L;
+    if (int rc = loop_scratch(h, L)) return rc;
+    void* s = stream_of(h, stream);
+    auto step = [&](int k, int post, int pre) {
+        return dart_rmpc_loop_step_dev(h, plant, loop, B, k, post, pre, log_rows, target, prm, mu, x, tilt, prev, u_prev,
+                                       r_v, theta, done, nlog, L.x0, L.Rref, L.phi, L.y, L.u0, L.f, L.status, L.iters,
+                                       log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v,
+                                       log_f, log_status, log_iters, s);
+    };
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        // warm start in place: every element of w's row is read (at the solve's start) and written (at its end)
+        // by the same wave, and an instance handed to the restoration kernel has not written its row
+        if (int rc = dart_rmpc_solve_batch_dev(h, B, L.x0, u_prev, theta, P, L.phi, L.y, loop->rls_lambda, L.Rref, prm, w,
+                                               L.u0, L.f, w, L.status, L.iters, s))
+            return rc;
+        if (int rc = step(k0 + j, 1, j + 1 < steps)) return rc;
+    }
+    return DART_MPC_OK;
+}
+
+int dart_pmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                          int B, int k0, int steps, int log_rows, const double* target, const double* prm,
+                          double* x, double* tilt,
+                          double* log_X, double* log_U, double* log_quat, double* log_loss,
+                          int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = loop_entry_check(h, DART_MPC_PMPC, plant, nullptr, B, k0, steps, log_rows,
+                                  {target, prm, x, tilt, log_X, log_U, log_quat, log_loss, log_status, log_iters}))
+        return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    LoopScratch L;
+    if (int rc = loop_scratch(h, L)) return rc;
+    void* s = stream_of(h, stream);
+    auto step = [&](int k, int post, int pre) {
+        return dart_pmpc_loop_step_dev(h, plant, B, k, post, pre, log_rows, prm, x, tilt, L.x0, L.u0, L.f, L.status, L.iters,
+                                       log_X, log_U, log_quat, log_loss, log_status, log_iters, s);
+    };
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        if (int rc = dart_mpc_solve_batch_dev(h, B, L.x0, target, prm, nullptr, L.u0, L.f, nullptr, L.status, L.iters, s))
+            return rc;
+        if (int rc = step(k0 + j, 1, j + 1 < steps)) return rc;
+    }
+    return DART_MPC_OK;
+}
+
+int dart_rmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                      int B, int k0, int steps, int log_rows,
+                      const double* target, const double* prm, const double* mu,
+                      double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
+                      double* P, double* w, int32_t* done, int32_t* nlog,
+                      double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                      double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                      int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = loop_entry_check(h, DART_MPC_RMPC, plant, loop, B, k0, steps, log_rows,
+                                  {target, prm, mu, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog, log_pos_err,
+                                   log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v, log_f,
+                                   log_status, log_iters}))
+        return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    hipStream_t s = stream_of(h, stream);
+    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t), nw = (size_t)dart_rmpc_nw(h->cfg.N);
+    // episode rows: an instance writes rows nlog[b] .. nlog[b] + steps - 1 at most
+    int e0 = log_rows, e1 = 0;
+    for (int b = 0; b < B; ++b) {
+        if (nlog[b] < 0) return fail(h, DART_MPC_EINVAL, "negative nlog");
+        e0 = nlog[b] < e0 ? nlog[b] : e0;
+        e1 = nlog[b] > e1 ? nlog[b] : e1;
+    }
+    e1 = (long long)e1 + steps < log_rows ? e1 + steps : log_rows;
+    e0 = e0 < e1 ? e0 : e1;
+    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
+    RollStage S;
+    const int i_tg = S.add(target, 4 * nB * D, false), i_prm = S.add(prm, 10 * nB * D, false), i_mu = S.add(mu, nB * D, false);
+    const int i_x = S.add(x, 6 * nB * D, true), i_tilt = S.add(tilt, 2 * nB * D, true), i_prev = S.add(prev, 4 * nB * D, true);
+    const int i_up = S.add(u_prev, 2 * nB * D, true), i_rv = S.add(r_v, 4 * nB * D, true), i_th = S.add(theta, 14 * nB * D, true);
+    const int i_P = S.add(P, 98 * nB * D, true), i_w = S.add(w, nw * nB * D, true);
+    const int i_done = S.add(done, nB * I, true), i_nlog = S.add(nlog, nB * I, true);
+    const int l_pe = S.add_log(log_pos_err, R, 2 * nB * D, e0, e1, true), l_pn = S.add_log(log_pos_err_norm, R, nB * D, e0, e1, true);
+    const int l_uc = S.add_log(log_u_cmd, R, 2 * nB * D, e0, e1, true), l_ts = S.add_log(log_timestep, R, nB * D, e0, e1, true);
+    const int l_x = S.add_log(log_x, R, 4 * nB * D, r0, r1, false), l_th = S.add_log(log_theta, R, 14 * nB * D, r0, r1, false);
+    const int l_rv = S.add_log(log_r_v, R, 4 * nB * D, r0, r1, false), l_f = S.add_log(log_f, R, nB * D, r0, r1, false);
+    const int l_st = S.add_log(log_status, R, nB * I, r0, r1, false), l_it = S.add_log(log_iters, R, nB * I, r0, r1, false);
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    auto dd = [&](int i) { return S.dev<double>(h, i); };
+    auto di = [&](int i) { return S.dev<int32_t>(h, i); };
+    if (int rc = dart_rmpc_rollout_dev(h, plant, loop, B, k0, steps, log_rows, dd(i_tg), dd(i_prm), dd(i_mu), dd(i_x),
+                                       dd(i_tilt), dd(i_prev), dd(i_up), dd(i_rv), dd(i_th), dd(i_P), dd(i_w), di(i_done),
+                                       di(i_nlog), dd(l_pe), dd(l_pn), dd(l_uc), dd(l_ts), dd(l_x), dd(l_th), dd(l_rv),
+                                       dd(l_f), di(l_st), di(l_it), s))
+        return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+int dart_pmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant,
+                      int B, int k0, int steps, int log_rows, const double* target, const double* prm,
+                      double* x, double* tilt,
+                      double* log_X, double* log_U, double* log_quat, double* log_loss,
+                      int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = loop_entry_check(h, DART_MPC_PMPC, plant, nullptr, B, k0, steps, log_rows,
+                                  {target, prm, x, tilt, log_X, log_U, log_quat, log_loss, log_status, log_iters}))
+        return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    if (int rc = settle_pending(h)) return rc;
+    hipStream_t s = stream_of(h, stream);
+    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t);
+    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
+    RollStage S;
+    const int i_tg = S.add(target, 6 * nB * D, false), i_prm = S.add(prm, 6 * nB * D, false);
+    const int i_x = S.add(x, 6 * nB * D, true), i_tilt = S.add(tilt, 2 * nB * D, true);
+    const int l_X = S.add_log(log_X, R, 6 * nB * D, r0, r1, false), l_U = S.add_log(log_U, R, 2 * nB * D, r0, r1, false);
+    const int l_Q = S.add_log(log_quat, R, 4 * nB * D, r0, r1, false), l_L = S.add_log(log_loss, R, nB * D, r0, r1, false);
+    const int l_st = S.add_log(log_status, R, nB * I, r0, r1, false), l_it = S.add_log(log_iters, R, nB * I, r0, r1, false);
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    if (int rc = dart_pmpc_rollout_dev(h, plant, B, k0, steps, log_rows, S.dev<double>(h, i_tg), S.dev<double>(h, i_prm),
+                                       S.dev<double>(h, i_x), S.dev<double>(h, i_tilt), S.dev<double>(h, l_X),
+                                       S.dev<double>(h, l_U), S.dev<double>(h, l_Q), S.dev<double>(h, l_L),
+                                       S.dev<int32_t>(h, l_st), S.dev<int32_t>(h, l_it), s))
+        return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// LMPC closed loop (lmpc_loop_kernel between the unchanged policy + solve launches), with or without experience
+// collection.  The entries build one dart_lmpc_train_buffers from their positional arguments; everything below
+// the entries takes that.
+
+// every array of the LMPC closed loop, once, in the order the host entries lay the arena out
+#define ARR(member, width, type, kind, group) {offsetof(dart_lmpc_train_buffers, member), width, sizeof(type), kind, group}
+static const LmpcArr kLmpcArr[] = {
+    ARR(target, kNx, double, kBothCollect, kLoop), ARR(prm, dartmpc::LM_NPRM, double, kUp, kLoop),
+    ARR(plant_pvec, kAct, double, kBothCollect, kLoop),
+    ARR(x, kNx, double, kBoth, kLoop), ARR(tilt, 2, double, kBoth, kLoop), ARR(u_prev, kNu, double, kBoth, kLoop),
+    ARR(w, -1, double, kBoth, kLoop), ARR(model_params, kAct, double, kBoth, kLoop),
+    ARR(current_k, kAct, double, kBothTrain, kPolicy), ARR(weights, DART_LMPC_POLICY_NWEIGHTS, float, kNet, kPolicy),
+    ARR(critic, DART_LMPC_CRITIC_NWEIGHTS, float, kNet, kCollect),
+    ARR(obs_mean, kObs, double, kBoth, kPolicy), ARR(obs_M2, kObs, double, kBoth, kPolicy),
+    ARR(obs_count, 1, int32_t, kBoth, kPolicy), ARR(history, kHist, float, kBoth, kPolicy),
+    ARR(timestep, 1, int32_t, kBoth, kPolicy),
+    ARR(prev_cmd, kNu, double, kBoth, kCollect), ARR(control_seen, kNu, double, kBoth, kCollect),
+    ARR(ep_step, 1, int32_t, kBoth, kCollect), ARR(ep_return, 1, double, kBoth, kCollect),
+    ARR(time_penalty, 1, double, kBoth, kCollect), ARR(episodes, 1, int32_t, kBoth, kCollect),
+    ARR(last_return, 1, double, kBoth, kCollect), ARR(last_steps, 1, int32_t, kBoth, kCollect),
+    ARR(nrec, 1, int32_t, kBoth, kCollect), ARR(sticky, 1, int32_t, kBoth, kCollect),
+    ARR(reset_x, kNx, double, kPool, kCollect), ARR(reset_target, kNx, double, kPool, kCollect),
+    ARR(reset_pvec, kAct, double, kPool, kCollect),
+    ARR(log_X, kNx, double, kLog, kLoop), ARR(log_U, kNu, double, kLog, kLoop), ARR(log_pos_error, 1, double, kLog, kLoop),
+    ARR(log_pvec, kAct, double, kLog, kLoop), ARR(log_loss, 1, double, kLog, kLoop),
+    ARR(log_status, 1, int32_t, kLog, kLoop), ARR(log_iters, 1, int32_t, kLog, kLoop),
+    ARR(log_reward, 1, double, kLog, kCollect), ARR(log_done, 1, int32_t, kLog, kCollect),
+    ARR(log_value, 1, float, kLog, kCollect), ARR(log_logp, 1, float, kLog, kCollect),
+    ARR(rec_obs, kHist, float, kRec, kCollect), ARR(rec_action, kAct, float, kRec, kCollect),
+    ARR(rec_logp, 1, float, kRec, kCollect), ARR(rec_value, 1, float, kRec, kCollect),
+    ARR(rec_reward, 1, double, kRec, kCollect), ARR(rec_done, 1, float, kRec, kCollect),
+    ARR(adam, 2 * dartmpc::kPpoParams, float, kCall, kTrain), ARR(adam_step, 1, int32_t, kCall, kTrain),
+    ARR(best_return, 1, double, kCall, kTrain), ARR(best_weights, dartmpc::kPpoParams, float, kCall, kTrain),
+    ARR(best_iter, 1, int32_t, kCall, kTrain),
+};
+#undef ARR
+static_assert(sizeof kLmpcArr / sizeof kLmpcArr[0] == kLmpcArrays, "kLmpcArrays counts the table's rows");
+
+namespace {
+
+// (every member of dart_lmpc_train_buffers is an object pointer)
+void*& member(dart_lmpc_train_buffers& d, const LmpcArr& a) {
+    return *reinterpret_cast<void**>(reinterpret_cast<char*>(&d) + a.member);
+}
+const void* member(const dart_lmpc_train_buffers& d, const LmpcArr& a) {
+    return *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(&d) + a.member);
+}
+
+}  // namespace
+
+bool lmpc_null(const dart_lmpc_train_buffers& p, int group, int kind) {
+    for (const LmpcArr& a : kLmpcArr) {
+        const bool apart = a.kind == kRec || a.kind == kPool;
+        if (a.group == group && a.kind != kNet && (kind == kAnyState ? !apart : a.kind == kind) && !member(p, a))
+            return true;
+    }
+    return false;
+}
+
+void lmpc_stage(RollStage& S, const dart_lmpc_train_buffers& host, const LmpcStagePlan& m, int idx[kLmpcArrays]) {
+    for (int i = 0; i < kLmpcArrays; ++i) {
+        const LmpcArr& a = kLmpcArr[i];
+        idx[i] = -1;
+        if ((a.group == kPolicy && !m.policy) || (a.group == kCollect && !m.collect) || (a.group == kTrain && !m.train))
+            continue;
+        const void* p = member(host, a);
+        const size_t call = (size_t)a.width * a.size;                                    // [width]
+        const size_t row = (a.width < 0 ? m.nw : (size_t)a.width) * a.size * m.B;       // [B][width]
+        switch (a.kind) {
+        case kUp: idx[i] = S.add(p, row, false); break;
+        case kBoth: idx[i] = S.add(p, row, true); break;
+        case kBothCollect: idx[i] = S.add(p, row, m.collect); break;
+        case kBothTrain: idx[i] = S.add(p, row, m.train); break;
+        case kNet: idx[i] = S.add(p, call, m.train); break;
+        case kCall: idx[i] = S.add(p, call, true); break;
+        case kLog: idx[i] = S.add_rows(p, m.log_rows, row, m.r0, m.r1, false, true); break;
+        // (collection: both ways, since an instance that records less leaves its entries of the rows untouched)
+        case kRec: if (m.rec_rows) idx[i] = S.add_rows(p, m.rec_rows, row, m.q0, m.q1, !m.train, true); break;
+        case kPool: if (m.reset_rows) idx[i] = S.add(p, m.reset_rows * row, false); break;
+        }
+    }
+}
+
+void lmpc_bind(const RollStage& S, const dart_mpc_handle* h, const int idx[kLmpcArrays], dart_lmpc_train_buffers& dev) {
+    for (int i = 0; i < kLmpcArrays; ++i) member(dev, kLmpcArr[i]) = S.dev<char>(h, idx[i]);
+}
+
+namespace {
+
+// the solve's per-step arrays of an LMPC rollout, the two warm-start buffers the solves alternate between, and
+// one zeroed noise row
+struct LmpcLoopScratch {
+    double *state, *u0, *f, *wbuf[2];
+    int32_t *status, *iters;
+    float* zero_noise;
+};
+
+int lmpc_loop_scratch(dart_mpc_handle* h, LmpcLoopScratch& L) {
+    const size_t nw = (size_t)dart_lmpc_nw(h->cfg.N);
+    const size_t cnt[8] = {8 * kNx, 8 * kNu, 8, 8 * nw, 8 * nw, 4, 4, 4 * kAct};
+    char* p[8];
+    // (only the noise row needs a value: pre writes what the solve reads, the solve what post reads)
+    if (int rc = scratch_blocks(h, 8, cnt, 7, p)) return rc;
+    L.state = (double*)p[0]; L.u0 = (double*)p[1]; L.f = (double*)p[2]; L.wbuf[0] = (double*)p[3];
+    L.wbuf[1] = (double*)p[4]; L.status = (int32_t*)p[5]; L.iters = (int32_t*)p[6]; L.zero_noise = (float*)p[7];
+    return DART_MPC_OK;
+}
+
+// the configuration half of the experience launch's arguments, checked (after loop_check)
+int experience_cfg(dart_mpc_handle* h, const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* r, int B,
+                   int rec_rows, int reset_rows, const float* weights, const float* critic,
+                   dartmpc::ExperienceArgs& a) {
+    if (!weights) return fail(h, DART_MPC_EINVAL, "experience collection needs a policy (null weights)");
+    if (!critic) return fail(h, DART_MPC_EINVAL, "null critic weights");
+    // (the experience kernel reads layer 1 of both nets with 16-byte loads)
+    if (!aligned16(weights) || !aligned16(critic))
+        return fail(h, DART_MPC_EINVAL, "policy and critic weights must be 16-byte aligned");
+    dartmpc::PolicyArgs pa;
+    if (policy_args(pcfg, B, weights, pa) != DART_MPC_OK) return fail(h, DART_MPC_EINVAL, "bad policy config");
+    if (!r) return fail(h, DART_MPC_EINVAL, "null reward config");
+    if (r->record_every < 1 || !(r->sigma_pos > 0.0) || !(r->sigma_vel > 0.0))
+        return fail(h, DART_MPC_EINVAL, "reward config: record_every >= 1, sigma_pos > 0, sigma_vel > 0");
+    if (rec_rows < 0 || reset_rows < 0) return fail(h, DART_MPC_EINVAL, "negative rec_rows or reset_rows");
+    a.B = B; a.rec_rows = rec_rows; a.reset_rows = reset_rows;
+    a.w = pa.w;
+    a.c = critic_weights(critic);
+    a.r.sigma_pos = r->sigma_pos; a.r.sigma_vel = r->sigma_vel; a.r.w_pos = r->w_pos; a.r.w_vel = r->w_vel;
+    a.r.w_change = r->w_change; a.r.w_d_ctrl = r->w_d_ctrl; a.r.success_tol = r->success_tol;
+    a.r.success_bonus = r->success_bonus; a.r.oob_penalty = r->oob_penalty;
+    a.r.tray_limit[0] = r->tray_limit[0]; a.r.tray_limit[1] = r->tray_limit[1];
+    a.r.max_per_dim_rms = r->max_per_dim_rms; a.r.time_penalty_rate = r->time_penalty_rate;
+    a.r.max_episode_steps = r->max_episode_steps; a.r.record_every = r->record_every; a.r.done_sticky = r->done_sticky;
+    a.max_delta = pcfg->max_delta; a.action_scale = pcfg->action_scale;
+    a.log_std_min = pcfg->log_std_min; a.log_std_max = pcfg->log_std_max;
+    return DART_MPC_OK;
+}
+
+// (after experience_cfg) the pointer half: the null checks of the collection's groups, then the fields of `a` that
+// the view holds (the caller sets k, action, state and mean_out)
+int experience_ptrs(dart_mpc_handle* h, int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p,
+                    dartmpc::ExperienceArgs& a) {
+    if (lmpc_null(p, kCollect)) return fail(h, DART_MPC_EINVAL, "null pointer (collection state or logs)");
+    if (rec_rows > 0 && lmpc_null(p, kCollect, kRec)) return fail(h, DART_MPC_EINVAL, "null pointer (records)");
+    if (reset_rows > 0 && lmpc_null(p, kCollect, kPool))
+        return fail(h, DART_MPC_EINVAL, "reset_rows > 0 with a null reset pool");
+    a.history = p.history; a.log_X = p.log_X; a.timestep = p.timestep; a.u_prev = p.u_prev;
+    a.target = p.target; a.plant_pvec = p.plant_pvec; a.x = p.x; a.tilt = p.tilt;
+    a.prev_cmd = p.prev_cmd; a.control_seen = p.control_seen; a.ep_step = p.ep_step; a.ep_return = p.ep_return;
+    a.time_penalty = p.time_penalty; a.episodes = p.episodes; a.last_return = p.last_return;
+    a.last_steps = p.last_steps; a.nrec = p.nrec; a.sticky = p.sticky;
+    a.reset_x = p.reset_x; a.reset_target = p.reset_target; a.reset_pvec = p.reset_pvec;
+    a.log_reward = p.log_reward; a.log_done = p.log_done; a.log_value = p.log_value; a.log_logp = p.log_logp;
+    a.rec_obs = p.rec_obs; a.rec_action = p.rec_action; a.rec_logp = p.rec_logp; a.rec_value = p.rec_value;
+    a.rec_reward = p.rec_reward; a.rec_done = p.rec_done;
+    return DART_MPC_OK;
+}
+
+// every argument check of the rollout (ea == nullptr) and collection entries, host and device forms alike; a
+// collection's experience arguments are left in *ea
+int lmpc_loop_check(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                    const dart_lmpc_reward_config* rcfg, int B, int k0, int steps, int log_rows, int rec_rows,
+                    int reset_rows, const dart_lmpc_train_buffers& p, dartmpc::ExperienceArgs* ea) {
+    if (int rc = loop_check(h, DART_MPC_LMPC, plant, B, k0, steps, log_rows)) return rc;
+    if (ea)
+        if (int rc = experience_cfg(h, pcfg, rcfg, B, rec_rows, reset_rows, p.weights, p.critic, *ea)) return rc;
+    if (lmpc_null(p, kLoop)) return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (p.weights) {
+        dartmpc::PolicyArgs chk;
+        if (policy_args(pcfg, B, p.weights, chk) != DART_MPC_OK) return fail(h, DART_MPC_EINVAL, "bad policy config");
+        if (lmpc_null(p, kPolicy)) return fail(h, DART_MPC_EINVAL, "null pointer (policy state)");
+    }
+    return ea ? experience_ptrs(h, rec_rows, reset_rows, p, *ea) : DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                            int B, int k, int do_post, int do_pre, int log_rows,
+                            const double* target, const double* plant_pvec,
+                            double* x, double* tilt, double* u_prev, const double* model_params, double* state,
+                            const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                            double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                            int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = loop_entry_check(h, DART_MPC_LMPC, plant, nullptr, B, k, do_post ? 1 : 0, log_rows,
+                                  {target, plant_pvec, x, tilt, u_prev, model_params, state, u0, f, status, iters, log_X,
+                                   log_U, log_pos_error, log_pvec, log_loss, log_status, log_iters}))
+        return rc;
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    dartmpc::LmpcLoopArgs a;
+    a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+    a.a_lag = plant->tau > 0.0 ? 1.0 - std::exp(-h->cfg.Ts / plant->tau) : 1.0;
+    a.Ts = h->cfg.Ts;
+    a.target = target; a.plant_pvec = plant_pvec; a.x = x; a.tilt = tilt; a.u_prev = u_prev;
+    a.model_params = model_params; a.state = state; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
+    a.log_X = log_X; a.log_U = log_U; a.log_pos_error = log_pos_error; a.log_pvec = log_pvec; a.log_loss = log_loss;
+    a.log_status = log_status; a.log_iters = log_iters;
+    HIPCHK(h, dartmpc_launch_lmpc_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
+    return DART_MPC_OK;
+}
+
+int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                     const dart_lmpc_reward_config* rcfg, bool collect, int B, int k0, int steps, int log_rows,
+                     int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise, void* stream) {
+    dartmpc::ExperienceArgs ea;
+    if (int rc = lmpc_loop_check(h, plant, pcfg, rcfg, B, k0, steps, log_rows, rec_rows, reset_rows, p,
+                                 collect ? &ea : nullptr))
+        return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    LmpcLoopScratch L;
+    if (int rc = lmpc_loop_scratch(h, L)) return rc;
+    if (collect && !h->action_buf)
+        HIPCHK(h, hipMalloc((void**)&h->action_buf, sizeof(float) * kAct * (size_t)h->cfg.B_max), "hipMalloc (action buffer)");
+    // a collection keeps the policy's action of the step for its experience launch
+    float* action = collect ? h->action_buf : nullptr;
+    ea.action = action; ea.mean_out = nullptr;
+    void* s = stream_of(h, stream);
+    auto step = [&](int k, int post, int pre) {
+        return dart_lmpc_loop_step_dev(h, plant, B, k, post, pre, log_rows, p.target, p.plant_pvec, p.x, p.tilt, p.u_prev,
+                                       p.model_params, L.state, L.u0, L.f, L.status, L.iters, p.log_X, p.log_U,
+                                       p.log_pos_error, p.log_pvec, p.log_loss, p.log_status, p.log_iters, s);
+    };
+    // Warm start: with the restoration phases on, an instance that <false> hands over has written the iterate of
+    // its failed iteration to w_out before lmpc_solve<true> (the tail, or the second launch) redoes the set-up from
+    // w_warm, so w_warm == w_out would change the scalings of the resumed solve.  The solves
+    // alternate between two handle-owned buffers instead: the first reads the caller's w, the last writes it.
+    // Without the restoration phases nothing is handed over and the row is rewritten in place.
+    const bool in_place = !h->cfg.restoration;
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        const double* w_in = (in_place || j == 0) ? p.w : L.wbuf[(j - 1) & 1];
+        double* w_out = (in_place || (j == steps - 1 && j > 0)) ? p.w : L.wbuf[j & 1];
+        int rc;
+        if (p.weights)       // (step k's draws are row k of the noise)
+            rc = dart_lmpc_policy_solve_batch_dev(h, pcfg, B, p.weights, L.state, p.u_prev, p.target, p.current_k,
+                                                  p.obs_mean, p.obs_M2, p.obs_count, p.history, p.timestep,
+                                                  noise ? noise + ((size_t)k0 + j) * B * kAct : L.zero_noise,
+                                                  p.model_params, action, p.prm, w_in, L.u0, L.f, w_out, L.status,
+                                                  L.iters, s);
+        else
+            rc = dart_lmpc_solve_batch_dev(h, B, L.state, p.u_prev, p.model_params, p.target, p.prm, w_in, L.u0, L.f,
+                                           w_out, L.status, L.iters, s);
+        if (rc) return rc;
+        if (w_out != p.w && j == steps - 1)       // a one-step call: the iterate back into the caller's w
+            HIPCHK(h, hipMemcpyAsync(p.w, w_out, sizeof(double) * (size_t)dart_lmpc_nw(h->cfg.N) * B,
+                                     hipMemcpyDeviceToDevice, (hipStream_t)s), "copy w");
+        const int pre = j + 1 < steps;
+        if ((rc = step(k0 + j, 1, pre))) return rc;
+        if (collect) {
+            // one experience launch after every post; a reset at the last step of a call is picked up by the next
+            // call's pre
+            ea.k = k0 + j;
+            ea.state = pre ? L.state : nullptr;
+            HIPCHK(h, dartmpc_launch_lmpc_experience(&ea, (hipStream_t)s), "experience kernel launch");
+        }
+    }
+    return DART_MPC_OK;
+}
+
+namespace {
+
+// the host form of the rollout and collection entries: the arrays of `p` staged into the handle's arena around
+// lmpc_closed_loop (the step rows [k0, k0 + steps) of the logs and of the noise travel)
+int lmpc_closed_loop_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                          const dart_lmpc_reward_config* rcfg, bool collect, int B, int k0, int steps, int log_rows,
+                          int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise,
+                          void* stream) {
+    dartmpc::ExperienceArgs chk;
+    if (int rc = lmpc_loop_check(h, plant, pcfg, rcfg, B, k0, steps, log_rows, rec_rows, reset_rows, p,
+                                 collect ? &chk : nullptr))
+        return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    hipStream_t s = stream_of(h, stream);
+    LmpcStagePlan m{};
+    m.policy = p.weights != nullptr; m.collect = collect;
+    m.B = (size_t)B; m.nw = (size_t)dart_lmpc_nw(h->cfg.N);
+    m.log_rows = (size_t)log_rows; m.r0 = (size_t)k0; m.r1 = (size_t)k0 + steps;
+    m.reset_rows = collect ? (size_t)reset_rows : 0;
+    if (collect && rec_rows > 0) {
+        // record rows: an instance writes rows nrec[b] .. nrec[b] + ceil(steps / record_every) - 1 at most
+        long long e0 = rec_rows, e1 = 0;
+        for (int b = 0; b < B; ++b) {
+            const long long n = p.nrec[b] < 0 ? 0 : p.nrec[b];
+            e0 = n < e0 ? n : e0;
+            e1 = n > e1 ? n : e1;
+        }
+        e1 += ((long long)steps + rcfg->record_every - 1) / rcfg->record_every;
+        e1 = e1 < rec_rows ? e1 : rec_rows;
+        e0 = e0 < e1 ? e0 : e1;
+        m.rec_rows = (size_t)rec_rows; m.q0 = (size_t)e0; m.q1 = (size_t)e1;
+    }
+    RollStage S;
+    int idx[kLmpcArrays];
+    lmpc_stage(S, p, m, idx);
+    const int i_nz = (m.policy && noise) ? S.add_rows(noise, m.log_rows, kAct * m.B * sizeof(float), m.r0, m.r1, true, false)
+                                         : -1;
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    dart_lmpc_train_buffers d{};
+    lmpc_bind(S, h, idx, d);
+    if (int rc = lmpc_closed_loop(h, plant, pcfg, rcfg, collect, B, k0, steps, log_rows, rec_rows, reset_rows, d,
+                                  S.dev<float>(h, i_nz), s))
+        return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+// (the entries never write through what they take const: the view's members are not const)
+template <class T> T* mut(const T* p) { return const_cast<T*>(p); }
+
+}  // namespace
+
+int dart_lmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                          int B, int k0, int steps, int log_rows,
+                          const double* target, const double* prm, const double* plant_pvec, const double* current_k,
+                          const float* weights, const float* noise,
+                          double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                          int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                          double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                          int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    // (the view's members in their order, up to model_params)
+    dart_lmpc_train_buffers p = {mut(target), prm, mut(plant_pvec), mut(current_k), mut(weights), nullptr, x, tilt, u_prev, w,
+                                 obs_mean, obs_M2, obs_count, history, timestep, model_params};
+    p.log_X = log_X; p.log_U = log_U; p.log_pos_error = log_pos_error; p.log_pvec = log_pvec; p.log_loss = log_loss;
+    p.log_status = log_status; p.log_iters = log_iters;
+    return lmpc_closed_loop(h, plant, pcfg, nullptr, false, B, k0, steps, log_rows, 0, 0, p, noise, stream);
+}
+
+int dart_lmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                      int B, int k0, int steps, int log_rows,
+                      const double* target, const double* prm, const double* plant_pvec, const double* current_k,
+                      const float* weights, const float* noise,
+                      double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                      int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                      double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                      int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    // (the view's members in their order, up to model_params)
+    dart_lmpc_train_buffers p = {mut(target), prm, mut(plant_pvec), mut(current_k), mut(weights), nullptr, x, tilt, u_prev, w,
+                                 obs_mean, obs_M2, obs_count, history, timestep, model_params};
+    p.log_X = log_X; p.log_U = log_U; p.log_pos_error = log_pos_error; p.log_pvec = log_pvec; p.log_loss = log_loss;
+    p.log_status = log_status; p.log_iters = log_iters;
+    return lmpc_closed_loop_host(h, plant, pcfg, nullptr, false, B, k0, steps, log_rows, 0, 0, p, noise, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// LMPC experience collection
+void dart_lmpc_reward_config_default(dart_lmpc_reward_config* c) {
+    if (!c) return;
+    c->sigma_pos = 0.02; c->sigma_vel = 0.02;
+    c->w_pos = 40.0; c->w_vel = 0.1; c->w_change = 1e-3; c->w_d_ctrl = 5.0;
+    c->success_tol = 0.01; c->success_bonus = 20.0; c->oob_penalty = 20.0;
+    c->tray_limit[0] = 0.2; c->tray_limit[1] = 0.15;
+    c->max_per_dim_rms = 0.5; c->time_penalty_rate = 1e-4;
+    c->max_episode_steps = 20000; c->record_every = 8; c->done_sticky = 0; c->reserved = 0;
+}
+
+int dart_lmpc_experience_step_dev(dart_mpc_handle* h, const dart_lmpc_policy_config* pcfg,
+                                  const dart_lmpc_reward_config* rcfg, int B, int k, int log_rows, int rec_rows,
+                                  int reset_rows, const float* weights, const float* critic, const float* history,
+                                  const float* action, const double* log_X, const int32_t* timestep,
+                                  const double* u_prev, double* target, double* plant_pvec, double* x, double* tilt,
+                                  double* state, double* prev_cmd, double* control_seen, int32_t* ep_step,
+                                  double* ep_return, double* time_penalty, int32_t* episodes, double* last_return,
+                                  int32_t* last_steps, int32_t* nrec, int32_t* sticky, const double* reset_x,
+                                  const double* reset_target, const double* reset_pvec, double* log_reward,
+                                  int32_t* log_done, float* log_value, float* log_logp, float* rec_obs,
+                                  float* rec_action, float* rec_logp, float* rec_value, double* rec_reward,
+                                  float* rec_done, float* mean_out, void* stream) {
+    DART_ENTER(h, DART_MPC_LMPC);
+    if (B < 0 || k < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
+    if (k >= log_rows) return fail(h, DART_MPC_EINVAL, "k exceeds log_rows");
+    dartmpc::ExperienceArgs a;
+    if (int rc = experience_cfg(h, pcfg, rcfg, B, rec_rows, reset_rows, weights, critic, a)) return rc;
+    if (any_null({history, action, log_X, timestep, u_prev, target, plant_pvec, x, tilt}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    dart_lmpc_train_buffers p{};
+    p.history = mut(history); p.log_X = mut(log_X); p.timestep = mut(timestep); p.u_prev = mut(u_prev);
+    p.target = target; p.plant_pvec = plant_pvec; p.x = x; p.tilt = tilt;
+    p.prev_cmd = prev_cmd; p.control_seen = control_seen; p.ep_step = ep_step; p.ep_return = ep_return;
+    p.time_penalty = time_penalty; p.episodes = episodes; p.last_return = last_return; p.last_steps = last_steps;
+    p.nrec = nrec; p.sticky = sticky; p.reset_x = reset_x; p.reset_target = reset_target; p.reset_pvec = reset_pvec;
+    p.log_reward = log_reward; p.log_done = log_done; p.log_value = log_value; p.log_logp = log_logp;
+    p.rec_obs = rec_obs; p.rec_action = rec_action; p.rec_logp = rec_logp; p.rec_value = rec_value;
+    p.rec_reward = rec_reward; p.rec_done = rec_done;
+    if (int rc = experience_ptrs(h, rec_rows, reset_rows, p, a)) return rc;
+    if (B == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    a.k = k; a.action = action; a.state = state; a.mean_out = mean_out;
+    HIPCHK(h, dartmpc_launch_lmpc_experience(&a, stream_of(h, stream)), "experience kernel launch");
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_collect_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                          const dart_lmpc_reward_config* rcfg, int B, int k0, int steps, int log_rows, int rec_rows,
+                          int reset_rows, double* target, const double* prm, double* plant_pvec,
+                          const double* current_k, const float* weights, const float* critic, const float* noise,
+                          double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                          int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                          double* prev_cmd, double* control_seen, int32_t* ep_step, double* ep_return,
+                          double* time_penalty, int32_t* episodes, double* last_return, int32_t* last_steps,
+                          int32_t* nrec, int32_t* sticky, const double* reset_x, const double* reset_target,
+                          const double* reset_pvec, double* log_X, double* log_U, double* log_pos_error,
+                          double* log_pvec, double* log_loss, int32_t* log_status, int32_t* log_iters,
+                          double* log_reward, int32_t* log_done, float* log_value, float* log_logp, float* rec_obs,
+                          float* rec_action, float* rec_logp, float* rec_value, double* rec_reward, float* rec_done,
+                          void* stream) {
+    DART_ENTER(h, -1);
+    // (the arguments are the view's members in their order, up to rec_done, but for the noise)
+    const dart_lmpc_train_buffers p = {
+        target, prm, plant_pvec, mut(current_k), mut(weights), mut(critic), x, tilt, u_prev, w, obs_mean, obs_M2, obs_count,
+        history, timestep, model_params, prev_cmd, control_seen, ep_step, ep_return, time_penalty, episodes, last_return,
+        last_steps, nrec, sticky, reset_x, reset_target, reset_pvec, log_X, log_U, log_pos_error, log_pvec, log_loss,
+        log_status, log_iters, log_reward, log_done, log_value, log_logp, rec_obs, rec_action, rec_logp, rec_value,
+        rec_reward, rec_done};
+    return lmpc_closed_loop(h, plant, pcfg, rcfg, true, B, k0, steps, log_rows, rec_rows, reset_rows, p, noise, stream);
+}
+
+int dart_lmpc_collect(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                      const dart_lmpc_reward_config* rcfg, int B, int k0, int steps, int log_rows, int rec_rows,
+                      int reset_rows, double* target, const double* prm, double* plant_pvec, const double* current_k,
+                      const float* weights, const float* critic, const float* noise,
+                      double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                      int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                      double* prev_cmd, double* control_seen, int32_t* ep_step, double* ep_return,
+                      double* time_penalty, int32_t* episodes, double* last_return, int32_t* last_steps,
+                      int32_t* nrec, int32_t* sticky, const double* reset_x, const double* reset_target,
+                      const double* reset_pvec, double* log_X, double* log_U, double* log_pos_error,
+                      double* log_pvec, double* log_loss, int32_t* log_status, int32_t* log_iters,
+                      double* log_reward, int32_t* log_done, float* log_value, float* log_logp, float* rec_obs,
+                      float* rec_action, float* rec_logp, float* rec_value, double* rec_reward, float* rec_done,
+                      void* stream) {
+    DART_ENTER(h, -1);
+    // (the arguments are the view's members in their order, up to rec_done, but for the noise)
+    const dart_lmpc_train_buffers p = {
+        target, prm, plant_pvec, mut(current_k), mut(weights), mut(critic), x, tilt, u_prev, w, obs_mean, obs_M2, obs_count,
+        history, timestep, model_params, prev_cmd, control_seen, ep_step, ep_return, time_penalty, episodes, last_return,
+        last_steps, nrec, sticky, reset_x, reset_target, reset_pvec, log_X, log_U, log_pos_error, log_pvec, log_loss,
+        log_status, log_iters, log_reward, log_done, log_value, log_logp, rec_obs, rec_action, rec_logp, rec_value,
+        rec_reward, rec_done};
+    return lmpc_closed_loop_host(h, plant, pcfg, rcfg, true, B, k0, steps, log_rows, rec_rows, reset_rows, p, noise,
+                                 stream);
+}

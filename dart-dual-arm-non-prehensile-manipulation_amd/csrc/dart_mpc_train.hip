@@ -1,0 +1,822 @@
+// dart_mpc_train.hip -- the training entries of include/dart_mpc.h (host side): GAE, the PPO update
+// (lmpc_ppo.hip), the generator entries, the global buffer and whole training iterations (lmpc_train.hip).
+#include "abi_internal.h"
+
+int dart_lmpc_gae_dev(int B, int rec_rows, double gamma, double lam, const int32_t* nrec, const double* rec_reward,
+                      const float* rec_value, const float* rec_done, const float* last_value, double* adv, double* ret,
+                      void* stream) {
+    if (B < 0 || rec_rows < 0) return DART_MPC_EINVAL;
+    if (B == 0 || rec_rows == 0) return DART_MPC_OK;
+    if (any_null({nrec, rec_reward, rec_value, rec_done, last_value, adv, ret})) return DART_MPC_EINVAL;
+    dartmpc::GaeArgs a;
+    a.B = B; a.rec_rows = rec_rows; a.gamma = gamma; a.lam = lam; a.nrec = nrec; a.rec_reward = rec_reward;
+    a.rec_value = rec_value; a.rec_done = rec_done; a.last_value = last_value; a.adv = adv; a.ret = ret;
+    return dartmpc_launch_lmpc_gae(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_gae(int B, int rec_rows, double gamma, double lam, const int32_t* nrec, const double* rec_reward,
+                  const float* rec_value, const float* rec_done, const float* last_value, double* adv, double* ret) {
+    if (B < 0 || rec_rows < 0) return DART_MPC_EINVAL;
+    if (B == 0 || rec_rows == 0) return DART_MPC_OK;
+    if (any_null({nrec, rec_reward, rec_value, rec_done, last_value, adv, ret})) return DART_MPC_EINVAL;
+    DART_DEVICE_STAGE(D, S);
+    const size_t n = (size_t)B * rec_rows;
+    if (S.reserve(sizeof(double) * 3 * n + sizeof(float) * (2 * n + B) + sizeof(int32_t) * B + 8 * 256, 0) != hipSuccess)
+        return DART_MPC_EHIP;
+    S.begin();
+    dartmpc::GaeArgs a;
+    a.B = B; a.rec_rows = rec_rows; a.gamma = gamma; a.lam = lam;
+    a.nrec = S.in(nrec, (size_t)B); a.rec_reward = S.in(rec_reward, n); a.rec_value = S.in(rec_value, n);
+    a.rec_done = S.in(rec_done, n); a.last_value = S.in(last_value, (size_t)B);
+    a.adv = S.inout(adv, n); a.ret = S.inout(ret, n);      // (rows >= nrec[b] keep the caller's contents)
+    if (!D->run([&](hipStream_t s) { return dartmpc_launch_lmpc_gae(&a, s); })) return DART_MPC_EHIP;
+    return DART_MPC_OK;
+}
+
+// ---- PPO update of the LMPC policy (lmpc_ppo.hip) ----------------------------------------------------------
+
+void dart_lmpc_ppo_config_default(dart_lmpc_ppo_config* c) {
+    if (!c) return;
+    c->clip_eps = 0.2; c->vf_coef = 0.25; c->ent_coef = 0.01; c->max_grad_norm = 0.5;
+    c->lr = 3e-4; c->beta1 = 0.9; c->beta2 = 0.999; c->adam_eps = 1e-8; c->weight_decay = 1e-5;
+    c->log_std_min = std::log(1e-2); c->log_std_max = std::log(2.0);
+    c->epochs = 8; c->mini_batch_size = 64;
+}
+
+size_t dart_lmpc_ppo_workspace_bytes(int n, int mini_batch_size) {
+    if (n < 1 || mini_batch_size < 1 || mini_batch_size > dartmpc::kPpoMaxBatch) return 0;
+    return dartmpc::ppo_workspace(n, mini_batch_size).bytes;
+}
+
+namespace {
+
+bool ppo_cfg_ok(const dart_lmpc_ppo_config* c) {
+    return c && c->mini_batch_size >= 1 && c->mini_batch_size <= dartmpc::kPpoMaxBatch && c->epochs >= 0 &&
+           c->clip_eps >= 0.0 && c->lr >= 0.0 && c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 &&
+           c->beta2 < 1.0 && c->adam_eps >= 0.0 && c->max_grad_norm >= 0.0 && c->log_std_min <= c->log_std_max;
+}
+
+// the launches of the PPO entries; ws is laid out for (n, mb) with M <= mb
+hipError_t ppo_launch_prepare(int n, long long total, const int32_t* sample, const double* adv, const double* ret,
+                              float* adv_out, float* ret_out, char* ws, int mb, hipStream_t s) {
+    const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
+    dartmpc::PpoPrepareArgs a;
+    a.n = n; a.rec_total = total; a.sample = sample; a.adv = adv; a.ret = ret;
+    a.adv_n = reinterpret_cast<float*>(ws + L.adv_n); a.ret_n = reinterpret_cast<float*>(ws + L.ret_n);
+    a.adv_out = adv_out; a.ret_out = ret_out;
+    return dartmpc_launch_ppo_prepare(&a, s);
+}
+
+hipError_t ppo_launch_grad(const dart_lmpc_ppo_config* c, int n, long long total, int M, const int32_t* sample,
+                           const int32_t* idx, const float* rec_obs, const float* rec_action, const float* rec_logp,
+                           const float* weights, const float* critic, char* ws, int mb, hipStream_t s) {
+    const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
+    dartmpc::PpoGradArgs a;
+    a.n = n; a.M = M; a.rec_total = total;
+    a.clip_lo = (float)(1.0 - c->clip_eps); a.clip_hi = (float)(1.0 + c->clip_eps);
+    a.vf_coef = (float)c->vf_coef; a.ent_coef = (float)c->ent_coef;
+    a.log_std_min = (float)c->log_std_min; a.log_std_max = (float)c->log_std_max;
+    a.sample = sample; a.idx = idx; a.rec_obs = rec_obs; a.rec_action = rec_action; a.rec_logp = rec_logp;
+    a.adv_n = reinterpret_cast<const float*>(ws + L.adv_n); a.ret_n = reinterpret_cast<const float*>(ws + L.ret_n);
+    a.actor = weights; a.critic = critic;
+    a.part = reinterpret_cast<float*>(ws + L.part); a.loss_part = reinterpret_cast<float*>(ws + L.loss_part);
+    return dartmpc_launch_ppo_grad(&a, s);
+}
+
+// from_tiles: sum the workspace's partials of a mini-batch of M; otherwise take the packed gradient `grad`
+hipError_t ppo_launch_apply(const dart_lmpc_ppo_config* c, int n, int M, bool from_tiles, const float* grad,
+                            const float* terms_in, bool do_step, float* grad_out, float* terms_out, float* weights,
+                            float* critic, float* adam, int32_t* adam_step, double* stats, float* step_log,
+                            int step_in_call, char* ws, int mb, hipStream_t s) {
+    const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
+    dartmpc::PpoApplyArgs a;
+    a.tiles = from_tiles ? (M + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile : 1;
+    a.M = M; a.do_step = do_step ? 1 : 0; a.step_in_call = step_in_call;
+    a.max_grad_norm = (float)c->max_grad_norm; a.lr = c->lr; a.beta1 = c->beta1;
+    a.beta2 = c->beta2; a.adam_eps = (float)c->adam_eps; a.weight_decay = (float)c->weight_decay;
+    a.ent_coef = (float)c->ent_coef; a.log_std_min = (float)c->log_std_min; a.log_std_max = (float)c->log_std_max;
+    a.part = from_tiles ? reinterpret_cast<const float*>(ws + L.part) : grad;
+    a.loss_part = from_tiles ? reinterpret_cast<const float*>(ws + L.loss_part) : nullptr;
+    a.terms_in = terms_in;
+    a.grad = grad_out ? grad_out : reinterpret_cast<float*>(ws + L.grad);
+    a.terms = terms_out ? terms_out : reinterpret_cast<float*>(ws + L.terms);
+    a.actor = weights; a.critic = critic; a.adam = adam; a.adam_step = adam_step;
+    a.step_log = step_log; a.stat_sum = reinterpret_cast<double*>(ws + L.stat_sum); a.stats = stats;
+    return dartmpc_launch_ppo_apply(&a, s);
+}
+
+}  // namespace
+
+int dart_lmpc_ppo_prepare_dev(int n, int rec_total, const int32_t* sample, const double* adv, const double* ret,
+                              float* adv_norm_out, float* ret_norm_out, void* workspace, void* stream) {
+    if (n < 1 || rec_total < 1 || !sample || !adv || !ret || !workspace) return DART_MPC_EINVAL;
+    return ppo_launch_prepare(n, rec_total, sample, adv, ret, adv_norm_out, ret_norm_out, (char*)workspace, 1,
+                              (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_ppo_grad_dev(const dart_lmpc_ppo_config* cfg, int n, int rec_total, int M, const int32_t* sample,
+                           const int32_t* idx, const float* rec_obs, const float* rec_action, const float* rec_logp,
+                           const float* weights, const float* critic, float* grad_out, float* terms_out,
+                           void* workspace, void* stream) {
+    if (!ppo_cfg_ok(cfg) || n < 1 || rec_total < 1 || M < 1 || M > dartmpc::kPpoMaxBatch) return DART_MPC_EINVAL;
+    if (!sample || !idx || !rec_obs || !rec_action || !rec_logp || !weights || !critic || !grad_out || !terms_out ||
+        !workspace) return DART_MPC_EINVAL;
+    if (!aligned16(weights) || !aligned16(critic)) return DART_MPC_EINVAL;
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = ppo_launch_grad(cfg, n, rec_total, M, sample, idx, rec_obs, rec_action, rec_logp, weights, critic,
+                                   ws, M, s);
+    if (e == hipSuccess)
+        e = ppo_launch_apply(cfg, n, M, true, nullptr, nullptr, false, grad_out, terms_out, const_cast<float*>(weights),
+                             const_cast<float*>(critic), nullptr, nullptr, nullptr, nullptr, 0, ws, M, s);
+    return e == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_ppo_apply_dev(const dart_lmpc_ppo_config* cfg, const float* grad, const float* terms, float* weights,
+                            float* critic, float* adam, int32_t* adam_step, double* stats, float* step_log,
+                            int step_in_call, void* workspace, void* stream) {
+    if (!ppo_cfg_ok(cfg) || !grad || !weights || !critic || !adam || !adam_step || !workspace || step_in_call < 0)
+        return DART_MPC_EINVAL;
+    if (!aligned16(weights) || !aligned16(critic)) return DART_MPC_EINVAL;
+    // (the blocks this launch uses lie at fixed offsets in front of the workspace: the layout of any n serves)
+    return ppo_launch_apply(cfg, 1, 1, false, grad, terms, true, nullptr, nullptr, weights, critic, adam, adam_step,
+                            stats, step_log, step_in_call, (char*)workspace, 1, (hipStream_t)stream) == hipSuccess
+               ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+namespace {
+
+int ppo_update_check(const dart_lmpc_ppo_config* cfg, int n, int rec_total, const void* sample, const void* perm,
+                     const void* rec_obs, const void* rec_action, const void* rec_logp, const void* adv,
+                     const void* ret, const void* weights, const void* critic, const void* adam,
+                     const void* adam_step, const void* stats) {
+    if (!ppo_cfg_ok(cfg) || n < 1 || rec_total < 1) return DART_MPC_EINVAL;
+    if (!sample || (!perm && cfg->epochs > 0) || !rec_obs || !rec_action || !rec_logp || !adv || !ret || !weights ||
+        !critic || !adam || !adam_step || !stats) return DART_MPC_EINVAL;
+    if (!aligned16(weights) || !aligned16(critic)) return DART_MPC_EINVAL;
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_ppo_update_dev(const dart_lmpc_ppo_config* cfg, int n, int rec_total, const int32_t* sample,
+                             const int32_t* perm, const float* rec_obs, const float* rec_action,
+                             const float* rec_logp, const double* adv, const double* ret, float* weights,
+                             float* critic, float* adam, int32_t* adam_step, double* stats, float* step_log,
+                             float* adv_norm_out, float* ret_norm_out, void* workspace, void* stream) {
+    if (int rc = ppo_update_check(cfg, n, rec_total, sample, perm, rec_obs, rec_action, rec_logp, adv, ret, weights,
+                                  critic, adam, adam_step, stats)) return rc;
+    if (!workspace) return DART_MPC_EINVAL;
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const int mb = cfg->mini_batch_size;
+    hipError_t e = ppo_launch_prepare(n, rec_total, sample, adv, ret, adv_norm_out, ret_norm_out, ws, mb, s);
+    int step = 0;
+    for (int ep = 0; ep < cfg->epochs && e == hipSuccess; ++ep) {
+        const int32_t* row = perm + (size_t)ep * n;
+        for (int start = 0; start < n && e == hipSuccess; start += mb, ++step) {
+            const int M = n - start < mb ? n - start : mb;
+            e = ppo_launch_grad(cfg, n, rec_total, M, sample, row + start, rec_obs, rec_action, rec_logp, weights,
+                                critic, ws, mb, s);
+            if (e == hipSuccess)
+                e = ppo_launch_apply(cfg, n, M, true, nullptr, nullptr, true, nullptr, nullptr, weights, critic, adam,
+                                     adam_step, stats, step_log, step, ws, mb, s);
+        }
+    }
+    return e == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_ppo_update(const dart_lmpc_ppo_config* cfg, int n, int rec_total, const int32_t* sample,
+                         const int32_t* perm, const float* rec_obs, const float* rec_action, const float* rec_logp,
+                         const double* adv, const double* ret, float* weights, float* critic, float* adam,
+                         int32_t* adam_step, double* stats, float* step_log, float* adv_norm_out,
+                         float* ret_norm_out) {
+    if (int rc = ppo_update_check(cfg, n, rec_total, sample, perm, rec_obs, rec_action, rec_logp, adv, ret, weights,
+                                  critic, adam, adam_step, stats)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (sample[i] < 0 || sample[i] >= rec_total) return DART_MPC_EINVAL;
+    const size_t np = (size_t)cfg->epochs * n;
+    for (size_t i = 0; i < np; ++i)
+        if (perm[i] < 0 || perm[i] >= n) return DART_MPC_EINVAL;
+    if (cfg->epochs == 0) { stats[0] = stats[1] = stats[2] = 0.0; }
+    // only the rows sample names travel: they are compacted on the way up (the device entry gathers through
+    // sample, so it is handed the identity) -- rows past an instance's record count are never read
+    DART_DEVICE_STAGE(D, S);
+    const size_t N = (size_t)n, P = dartmpc::kPpoParams;
+    const size_t steps = (size_t)cfg->epochs * ((N + cfg->mini_batch_size - 1) / cfg->mini_batch_size);
+    const size_t ws_bytes = dartmpc::ppo_workspace(n, cfg->mini_batch_size).bytes;
+    const size_t staged = sizeof(int32_t) * (N + np + 1) + sizeof(float) * (N * (kHist + kAct + 1) + 3 * P + 4 * steps + 2 * N) +
+                          sizeof(double) * (2 * N + 3) + 20 * 256;
+    if (S.reserve(staged + ws_bytes, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    auto at = [&](size_t i) { return sample[i]; };
+    auto iota = [n](int32_t* q) { for (int i = 0; i < n; ++i) q[i] = i; };
+    const int32_t* d_id = S.in_with<int32_t>(N, iota);
+    const float *d_obs = S.in_rows(rec_obs, N, kHist, at), *d_act = S.in_rows(rec_action, N, kAct, at);
+    const float* d_lp = S.in_rows(rec_logp, N, 1, at);
+    const double *d_adv = S.in_rows(adv, N, 1, at), *d_ret = S.in_rows(ret, N, 1, at);
+    const int32_t* d_perm = S.in(perm, np);
+    float* d_w = S.inout(weights, (size_t)dartmpc::kPpoActorN);
+    float* d_c = S.inout(critic, (size_t)dartmpc::kPpoCriticN);
+    float* d_adam = S.inout(adam, 2 * P);
+    int32_t* d_step = S.inout(adam_step, (size_t)1);
+    double* d_stats = S.inout(stats, (size_t)3);
+    float* d_log = S.inout(step_log, 4 * steps);
+    float* d_an = S.inout(adv_norm_out, N);
+    float* d_rn = S.inout(ret_norm_out, N);
+    char* ws = S.din + S.in_off;
+    hipError_t e = S.upload(D->stream);
+    int rc = DART_MPC_OK;
+    if (e == hipSuccess)
+        rc = dart_lmpc_ppo_update_dev(cfg, n, n, d_id, d_perm, d_obs, d_act, d_lp, d_adv, d_ret, d_w, d_c, d_adam, d_step,
+                                      d_stats, d_log, d_an, d_rn, ws, D->stream);
+    if (rc != DART_MPC_OK) {
+        (void)hipStreamSynchronize(D->stream);
+        return rc;
+    }
+    if (e == hipSuccess) e = S.download_inout(D->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) return DART_MPC_EHIP;
+    S.finish_inout();
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_critic_value_dev(int n, const float* critic, const float* obs, float* value_out, void* stream) {
+    if (n < 0) return DART_MPC_EINVAL;
+    if (n == 0) return DART_MPC_OK;
+    if (!critic || !obs || !value_out) return DART_MPC_EINVAL;
+    dartmpc::CriticValueArgs a;
+    a.n = n; a.critic = critic; a.obs = obs; a.value = value_out;
+    return dartmpc_launch_critic_value(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_critic_value(int n, const float* critic, const float* obs, float* value_out) {
+    if (n < 0) return DART_MPC_EINVAL;
+    if (n == 0) return DART_MPC_OK;
+    if (!critic || !obs || !value_out) return DART_MPC_EINVAL;
+    DART_DEVICE_STAGE(D, S);
+    const size_t N = (size_t)n;
+    if (S.reserve(sizeof(float) * (N * kHist + dartmpc::kPpoCriticN + N) + 4 * 256, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    dartmpc::CriticValueArgs a;
+    a.n = n; a.critic = S.in(critic, (size_t)dartmpc::kPpoCriticN); a.obs = S.in(obs, N * kHist);
+    a.value = S.inout(value_out, N);
+    if (!D->run([&](hipStream_t s) { return dartmpc_launch_critic_value(&a, s); })) return DART_MPC_EHIP;
+    return DART_MPC_OK;
+}
+
+// ---- whole PPO training iterations on the device (lmpc_train.hip) ---------------------------------------------
+
+int dart_lmpc_philox_dev(int n, const uint32_t* in, uint32_t* out, void* stream) {
+    if (n < 0) return DART_MPC_EINVAL;
+    if (n == 0) return DART_MPC_OK;
+    if (!in || !out) return DART_MPC_EINVAL;
+    dartmpc::PhiloxArgs a;
+    a.n = n; a.in = in; a.out = out;
+    return dartmpc_launch_philox(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+namespace {
+
+hipError_t launch_noise(uint64_t seed, int iteration, int steps, int B, float* out, hipStream_t s) {
+    dartmpc::NoiseArgs a;
+    a.n = (long long)steps * B * kAct;
+    a.key0 = (uint32_t)(seed & 0xffffffffu); a.key1 = (uint32_t)(seed >> 32); a.iteration = (uint32_t)iteration;
+    a.out = out;
+    return dartmpc_launch_lmpc_noise(&a, s);
+}
+
+// limit = n: the permutations; limit = m < n: their first m entries (rows of m)
+hipError_t launch_perms(uint64_t seed, int iteration, int epochs, int n, int32_t* perm, uint32_t* key_out,
+                        hipStream_t s, uint32_t rng_stream = dartmpc::kStreamPerm, int limit = -1) {
+    dartmpc::PermArgs a;
+    a.n = n; a.epochs = epochs; a.limit = limit < 0 ? n : limit;
+    a.key0 = (uint32_t)(seed & 0xffffffffu); a.key1 = (uint32_t)(seed >> 32); a.iteration = (uint32_t)iteration;
+    a.stream = rng_stream;
+    a.perm = perm; a.key_out = key_out;
+    return dartmpc_launch_lmpc_perms(&a, s);
+}
+
+// (the Philox block index is 32 bits wide: 4 * 2^32 elements at the most)
+bool noise_shape_ok(int iteration, int steps, int B) {
+    return iteration >= 0 && steps >= 0 && B >= 0 && (long long)steps * B * kAct <= (1LL << 34);
+}
+
+int mean_update_args(const dart_lmpc_policy_config* cfg, int B, const float* weights, dartmpc::MeanUpdateArgs& a) {
+    dartmpc::PolicyArgs pa;
+    if (policy_args(cfg, B, weights, pa) != DART_MPC_OK) return DART_MPC_EINVAL;
+    a.B = B; a.w = pa.w;
+    a.max_delta = pa.max_delta; a.k_max = pa.k_max; a.min_k = pa.min_k; a.k_ceiling_margin = pa.k_ceiling_margin;
+    a.action_scale = pa.action_scale; a.smooth_alpha = pa.smooth_alpha;
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_noise_dev(uint64_t seed, int iteration, int steps, int B, float* noise_out, void* stream) {
+    if (!noise_shape_ok(iteration, steps, B)) return DART_MPC_EINVAL;
+    if (steps == 0 || B == 0) return DART_MPC_OK;
+    if (!noise_out) return DART_MPC_EINVAL;
+    return launch_noise(seed, iteration, steps, B, noise_out, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK
+                                                                                                  : DART_MPC_EHIP;
+}
+
+int dart_lmpc_noise(uint64_t seed, int iteration, int steps, int B, float* noise_out) {
+    if (!noise_shape_ok(iteration, steps, B)) return DART_MPC_EINVAL;
+    if (steps == 0 || B == 0) return DART_MPC_OK;
+    if (!noise_out) return DART_MPC_EINVAL;
+    DART_DEVICE_STAGE(D, S);
+    const size_t n = (size_t)steps * B * kAct;
+    if (S.reserve(0, sizeof(float) * n + 256) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    float* d = S.out<float>(n);
+    if (!D->run([&](hipStream_t s) { return launch_noise(seed, iteration, steps, B, d, s); })) return DART_MPC_EHIP;
+    S.take(noise_out, d, n);
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_perms_dev(uint64_t seed, int iteration, int epochs, int n, int32_t* perm_out, uint32_t* key_out,
+                        void* stream) {
+    if (iteration < 0 || epochs < 0 || n < 0) return DART_MPC_EINVAL;
+    if (epochs == 0 || n == 0) return DART_MPC_OK;
+    if (!perm_out) return DART_MPC_EINVAL;
+    return launch_perms(seed, iteration, epochs, n, perm_out, key_out, (hipStream_t)stream) == hipSuccess
+               ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_perms(uint64_t seed, int iteration, int epochs, int n, int32_t* perm_out, uint32_t* key_out) {
+    if (iteration < 0 || epochs < 0 || n < 0) return DART_MPC_EINVAL;
+    if (epochs == 0 || n == 0) return DART_MPC_OK;
+    if (!perm_out) return DART_MPC_EINVAL;
+    DART_DEVICE_STAGE(D, S);
+    const size_t m = (size_t)epochs * n;
+    if (S.reserve(0, 2 * (sizeof(int32_t) * m + 256)) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    int32_t* d = S.out<int32_t>(m);
+    uint32_t* dk = key_out ? S.out<uint32_t>(m) : nullptr;
+    auto launch = [&](hipStream_t s) { return launch_perms(seed, iteration, epochs, n, d, dk, s); };
+    if (!D->run(launch)) return DART_MPC_EHIP;
+    S.take(perm_out, d, m);
+    S.take(key_out, dk, m);
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_mean_param_update_dev(const dart_lmpc_policy_config* cfg, int B, const float* weights,
+                                    const float* history, double* model_params, double* current_k, float* mean_out,
+                                    void* stream) {
+    dartmpc::MeanUpdateArgs a;
+    if (mean_update_args(cfg, B, weights, a) != DART_MPC_OK) return DART_MPC_EINVAL;
+    if (B == 0) return DART_MPC_OK;
+    if (!history || !model_params || !current_k) return DART_MPC_EINVAL;
+    a.history = history; a.model_params = model_params; a.current_k = current_k; a.mean_out = mean_out;
+    return dartmpc_launch_lmpc_mean_update(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_mean_param_update(const dart_lmpc_policy_config* cfg, int B, const float* weights, const float* history,
+                                double* model_params, double* current_k, float* mean_out) {
+    dartmpc::MeanUpdateArgs a;
+    if (mean_update_args(cfg, B, weights, a) != DART_MPC_OK) return DART_MPC_EINVAL;
+    if (B == 0) return DART_MPC_OK;
+    if (!history || !model_params || !current_k) return DART_MPC_EINVAL;
+    DART_DEVICE_STAGE(D, S);
+    const size_t nB = (size_t)B;
+    if (S.reserve(sizeof(float) * ((size_t)DART_LMPC_POLICY_NWEIGHTS + kHist * nB) + sizeof(double) * 68 * nB + 8 * 256,
+                  sizeof(float) * kAct * nB + 256) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    const float* d_w = S.in(weights, (size_t)DART_LMPC_POLICY_NWEIGHTS);
+    if (mean_update_args(cfg, B, d_w, a) != DART_MPC_OK) return DART_MPC_EINVAL;
+    a.history = S.in(history, kHist * nB);
+    a.model_params = S.inout(model_params, kAct * nB);
+    a.current_k = S.inout(current_k, kAct * nB);
+    a.mean_out = mean_out ? S.out<float>(kAct * nB) : nullptr;
+    if (!D->run([&](hipStream_t s) { return dartmpc_launch_lmpc_mean_update(&a, s); })) return DART_MPC_EHIP;
+    S.take(mean_out, a.mean_out, kAct * nB);
+    return DART_MPC_OK;
+}
+
+// ---- the global-buffer update (rlmpc2.py:823-874): choice, record gather, GAE over one sequence ----------------
+
+int dart_lmpc_perms_stream_dev(uint64_t seed, int iteration, int rng_stream, int epochs, int n, int32_t* perm_out,
+                               uint32_t* key_out, void* stream) {
+    if (iteration < 0 || epochs < 0 || n < 0 || rng_stream < 0) return DART_MPC_EINVAL;
+    if (epochs == 0 || n == 0) return DART_MPC_OK;
+    if (!perm_out) return DART_MPC_EINVAL;
+    return launch_perms(seed, iteration, epochs, n, perm_out, key_out, (hipStream_t)stream, (uint32_t)rng_stream) ==
+                   hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_choice_dev(uint64_t seed, int iteration, int n, int m, int32_t* choice_out, void* stream) {
+    if (iteration < 0 || m < 1 || m > n || !choice_out) return DART_MPC_EINVAL;
+    return launch_perms(seed, iteration, 1, n, choice_out, nullptr, (hipStream_t)stream, dartmpc::kStreamChoice, m) ==
+                   hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_choice(uint64_t seed, int iteration, int n, int m, int32_t* choice_out) {
+    if (iteration < 0 || m < 1 || m > n || !choice_out) return DART_MPC_EINVAL;
+    DART_DEVICE_STAGE(D, S);
+    if (S.reserve(0, sizeof(int32_t) * (size_t)m + 256) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    int32_t* d = S.out<int32_t>((size_t)m);
+    auto launch = [&](hipStream_t s) { return launch_perms(seed, iteration, 1, n, d, nullptr, s, dartmpc::kStreamChoice, m); };
+    if (!D->run(launch)) return DART_MPC_EHIP;
+    S.take(choice_out, d, (size_t)m);
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_global_rows(int n, int32_t* m_out, int32_t* G_out) {
+    if (n < 1 || !m_out || !G_out) return DART_MPC_EINVAL;
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    *m_out = m; *G_out = G;
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_global_fill_after(int n, int fill, int iterations) {
+    if (n < 1 || iterations < 0 || fill < 0 || fill >= n) return DART_MPC_EINVAL;
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    if (fill % m != 0) return DART_MPC_EINVAL;
+    const long long period = G / m;
+    return (int)(((long long)(fill / m) + iterations) % period) * m;
+}
+
+size_t dart_lmpc_global_workspace_bytes(int n, int epochs, int mini_batch_size) {
+    if (n < 1 || epochs < 0 || mini_batch_size < 1 || mini_batch_size > dartmpc::kPpoMaxBatch) return 0;
+    if ((long long)n + n / 4 > 0x7fffffffLL) return 0;
+    return dartmpc::global_workspace(n, epochs, mini_batch_size).bytes;
+}
+
+namespace {
+
+int global_append_check(const dart_lmpc_global_buffer* g, int m, int n, int rec_total, const void* sample,
+                        const void* choice, const void* rec_obs, const void* rec_action, const void* rec_logp,
+                        const void* rec_value, const void* rec_reward, const void* rec_done) {
+    if (!g || m < 1 || n < 1 || rec_total < 1 || g->fill < 0 || (long long)g->fill + m > g->capacity)
+        return DART_MPC_EINVAL;
+    if (!sample || !choice || !rec_obs || !rec_action || !rec_logp || !rec_value || !rec_reward || !rec_done ||
+        !g->obs || !g->action || !g->logp || !g->value || !g->reward || !g->done) return DART_MPC_EINVAL;
+    return DART_MPC_OK;
+}
+
+hipError_t launch_global_append(const dart_lmpc_global_buffer* g, int fill, int m, int n, int rec_total,
+                                const int32_t* sample, const int32_t* choice, const float* rec_obs,
+                                const float* rec_action, const float* rec_logp, const float* rec_value,
+                                const double* rec_reward, const float* rec_done, hipStream_t s) {
+    dartmpc::GbufAppendArgs a;
+    a.m = m; a.n = n; a.fill = fill; a.rec_total = rec_total; a.sample = sample; a.choice = choice;
+    a.rec_obs = rec_obs; a.rec_action = rec_action; a.rec_logp = rec_logp; a.rec_value = rec_value;
+    a.rec_reward = rec_reward; a.rec_done = rec_done;
+    a.obs = g->obs; a.action = g->action; a.logp = g->logp; a.value = g->value; a.reward = g->reward; a.done = g->done;
+    return dartmpc_launch_lmpc_gbuf_append(&a, s);
+}
+
+hipError_t launch_gae_seq(int G, double gamma, double lam, const double* reward, const float* value,
+                          const float* done, const float* last_value, double* adv, double* ret, hipStream_t s) {
+    dartmpc::GaeSeqArgs a;
+    a.G = G; a.gamma = gamma; a.lam = lam; a.reward = reward; a.value = value; a.done = done;
+    a.last_value = last_value; a.adv = adv; a.ret = ret;
+    return dartmpc_launch_lmpc_gae_seq(&a, s);
+}
+
+}  // namespace
+
+int dart_lmpc_global_append_dev(const dart_lmpc_global_buffer* g, int m, int n, int rec_total, const int32_t* sample,
+                                const int32_t* choice, const float* rec_obs, const float* rec_action,
+                                const float* rec_logp, const float* rec_value, const double* rec_reward,
+                                const float* rec_done, void* stream) {
+    if (int rc = global_append_check(g, m, n, rec_total, sample, choice, rec_obs, rec_action, rec_logp, rec_value,
+                                     rec_reward, rec_done)) return rc;
+    if (!aligned16(rec_obs) || !aligned16(g->obs)) return DART_MPC_EINVAL;    // (the rows move in 16-byte pieces)
+    return launch_global_append(g, g->fill, m, n, rec_total, sample, choice, rec_obs, rec_action, rec_logp, rec_value,
+                                rec_reward, rec_done, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_global_append(const dart_lmpc_global_buffer* g, int m, int n, int rec_total, const int32_t* sample,
+                            const int32_t* choice, const float* rec_obs, const float* rec_action,
+                            const float* rec_logp, const float* rec_value, const double* rec_reward,
+                            const float* rec_done) {
+    if (int rc = global_append_check(g, m, n, rec_total, sample, choice, rec_obs, rec_action, rec_logp, rec_value,
+                                     rec_reward, rec_done)) return rc;
+    for (int j = 0; j < m; ++j)
+        if (choice[j] < 0 || choice[j] >= n) return DART_MPC_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (sample[i] < 0 || sample[i] >= rec_total) return DART_MPC_EINVAL;
+    // only the m drawn records travel: they are compacted on the way up (sample and choice become the identity)
+    DART_DEVICE_STAGE(D, S);
+    const size_t M = (size_t)m, F = sizeof(float);
+    const size_t row = F * (kHist + kAct + 3) + sizeof(double);
+    if (S.reserve(2 * (M * row + 8 * 256) + sizeof(int32_t) * M + 256, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    auto at = [&](size_t j) { return sample[choice[j]]; };
+    auto iota = [m](int32_t* q) { for (int j = 0; j < m; ++j) q[j] = j; };
+    const int32_t* d_id = S.in_with<int32_t>(M, iota);
+    const float *d_obs = S.in_rows(rec_obs, M, kHist, at), *d_act = S.in_rows(rec_action, M, kAct, at);
+    const float *d_lp = S.in_rows(rec_logp, M, 1, at), *d_vl = S.in_rows(rec_value, M, 1, at);
+    const double* d_rw = S.in_rows(rec_reward, M, 1, at);
+    const float* d_dn = S.in_rows(rec_done, M, 1, at);
+    const size_t f0 = (size_t)g->fill;
+    dart_lmpc_global_buffer d = *g;                 // rows fill .. fill + m - 1 alone, as rows 0 .. m - 1
+    d.obs = S.inout(g->obs + f0 * kHist, M * kHist); d.action = S.inout(g->action + f0 * kAct, M * kAct);
+    d.logp = S.inout(g->logp + f0, M); d.value = S.inout(g->value + f0, M);
+    d.reward = S.inout(g->reward + f0, M); d.done = S.inout(g->done + f0, M);
+    auto launch = [&](hipStream_t s) {
+        return launch_global_append(&d, 0, m, m, m, d_id, d_id, d_obs, d_act, d_lp, d_vl, d_rw, d_dn, s);
+    };
+    if (!D->run(launch)) return DART_MPC_EHIP;
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_gae_seq_dev(int G, double gamma, double lam, const double* reward, const float* value,
+                          const float* done, const float* last_value, double* adv, double* ret, void* stream) {
+    if (G < 0) return DART_MPC_EINVAL;
+    if (G == 0) return DART_MPC_OK;
+    if (!reward || !value || !done || !last_value || !adv || !ret) return DART_MPC_EINVAL;
+    return launch_gae_seq(G, gamma, lam, reward, value, done, last_value, adv, ret, (hipStream_t)stream) == hipSuccess
+               ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_gae_seq(int G, double gamma, double lam, const double* reward, const float* value, const float* done,
+                      const float* last_value, double* adv, double* ret) {
+    if (G < 0) return DART_MPC_EINVAL;
+    if (G == 0) return DART_MPC_OK;
+    if (!reward || !value || !done || !last_value || !adv || !ret) return DART_MPC_EINVAL;
+    DART_DEVICE_STAGE(D, S);
+    const size_t n = (size_t)G;
+    if (S.reserve(sizeof(double) * 3 * n + sizeof(float) * (2 * n + 1) + 8 * 256, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    const double* d_rw = S.in(reward, n);
+    const float* d_vl = S.in(value, n);
+    const float* d_dn = S.in(done, n);
+    const float* d_lv = S.in(last_value, (size_t)1);
+    double* d_adv = S.inout(adv, n);
+    double* d_ret = S.inout(ret, n);
+    auto launch = [&](hipStream_t s) { return launch_gae_seq(G, gamma, lam, d_rw, d_vl, d_dn, d_lv, d_adv, d_ret, s); };
+    if (!D->run(launch)) return DART_MPC_EHIP;
+    return DART_MPC_OK;
+}
+
+void dart_lmpc_train_config_default(dart_lmpc_train_config* c) {
+    if (!c) return;
+    c->seed = 0; c->iterations = 1; c->it0 = 0; c->steps = 256; c->mean_update = 1; c->track_best = 1;
+    c->reserved = 0; c->gamma = 0.99; c->lam = 0.95;
+}
+
+size_t dart_lmpc_train_workspace_bytes(int B, int K, int record_every, int epochs, int mini_batch_size) {
+    if (B < 1 || record_every < 1 || K < record_every || K % record_every != 0 || epochs < 0 || mini_batch_size < 1 ||
+        mini_batch_size > dartmpc::kPpoMaxBatch) return 0;
+    if ((long long)(K / record_every) * B > 0x7fffffffLL) return 0;
+    return dartmpc::train_workspace(B, K, record_every, epochs, mini_batch_size).bytes;
+}
+
+namespace {
+
+// the checks of the training entries that need neither the device nor the arrays' contents
+int train_check(dart_mpc_handle* h, const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                const dart_lmpc_train_config* cfg, int B, const dart_lmpc_train_buffers* p, bool need_ws) {
+    if (!cfg || !p || !rcfg) return fail(h, DART_MPC_EINVAL, "null training config, reward config or buffers");
+    if (!ppo_cfg_ok(ppo)) return fail(h, DART_MPC_EINVAL, "bad PPO config");
+    if (cfg->iterations < 0 || cfg->it0 < 0 || (long long)cfg->it0 + cfg->iterations > 0x7fffffffLL)
+        return fail(h, DART_MPC_EINVAL, "training config: iterations >= 0, it0 >= 0");
+    if (B < 1) return fail(h, DART_MPC_EINVAL, "training needs B >= 1");
+    if (rcfg->record_every < 1 || cfg->steps < rcfg->record_every || cfg->steps % rcfg->record_every != 0)
+        return fail(h, DART_MPC_EINVAL, "training config: steps must be a positive multiple of record_every");
+    if ((long long)(cfg->steps / rcfg->record_every) * B > 0x7fffffffLL)
+        return fail(h, DART_MPC_EINVAL, "too many samples");
+    if (any_null({p->current_k, p->weights, p->critic, p->adam, p->adam_step, p->train_log, p->best_return,
+                  p->best_weights, p->best_iter}) || (need_ws && !p->workspace))
+        return fail(h, DART_MPC_EINVAL, "null pointer (training arrays)");
+    return DART_MPC_OK;
+}
+
+// the checks of the global buffer that need neither the device nor the arrays' contents (n = R B samples)
+int global_check(dart_mpc_handle* h, const dart_lmpc_global_buffer* g, int n, bool dev) {
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    if (g->fill < 0 || g->fill >= n || g->fill % m != 0)
+        return fail(h, DART_MPC_EINVAL, "global buffer: fill must be a multiple of m in [0, n)");
+    if (g->capacity < G) return fail(h, DART_MPC_EINVAL, "global buffer: capacity below G");
+    if (any_null({g->obs, g->action, g->logp, g->value, g->reward, g->done, g->global_log}) || (dev && !g->workspace))
+        return fail(h, DART_MPC_EINVAL, "null pointer (global buffer)");
+    if (dev && !aligned16(g->obs)) return fail(h, DART_MPC_EINVAL, "global buffer: obs is not 16-byte aligned");
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+// (g == nullptr: dart_lmpc_train_dev)
+int dart_lmpc_train_global_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                               const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* rcfg,
+                               const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg, int B,
+                               int reset_rows, const dart_lmpc_train_buffers* p, const dart_lmpc_global_buffer* g,
+                               void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = train_check(h, rcfg, ppo, cfg, B, p, true)) return rc;
+    const int K = cfg->steps, R = K / rcfg->record_every, n = R * B, mb = ppo->mini_batch_size;
+    if (g) {
+        if (int rc = global_check(h, g, n, true)) return rc;
+        if (!aligned16(p->rec_obs)) return fail(h, DART_MPC_EINVAL, "rec_obs is not 16-byte aligned");
+    }
+    void* s = stream_of(h, stream);
+    auto collect = [&](int steps, const float* noise) {
+        return lmpc_closed_loop(h, plant, pcfg, rcfg, true, B, 0, steps, K, R, reset_rows, *p, noise, s);
+    };
+    // every check of the collection (configs, null pointers, B <= B_max) before any device work: zero steps
+    if (int rc = collect(0, nullptr)) return rc;
+    if (cfg->iterations == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const dartmpc::TrainWorkspace L = dartmpc::train_workspace(B, K, rcfg->record_every, ppo->epochs, mb);
+    char* ws = (char*)p->workspace;
+    float* noise = (float*)(ws + L.noise);
+    float* last_value = (float*)(ws + L.last_value);
+    double* adv = (double*)(ws + L.adv);
+    double* ret = (double*)(ws + L.ret);
+    int32_t* sample = (int32_t*)(ws + L.sample);
+    int32_t* perm = (int32_t*)(ws + L.perm);
+    double* stats = (double*)(ws + L.stats);
+    int32_t* ep0 = (int32_t*)(ws + L.ep0);
+    hipStream_t hs = (hipStream_t)s;
+    // the global update's sizes, workspace and running fill (the host knows every launch from n and g->fill)
+    int gm = 0, gG = 0, g_fill = g ? g->fill : 0;
+    dartmpc::global_rows(n, gm, gG);
+    const dartmpc::GlobalWorkspace GL = dartmpc::global_workspace(n, ppo->epochs, mb);
+    char* gws = g ? (char*)g->workspace : nullptr;
+    auto gp = [&](size_t off) { return gws ? gws + off : nullptr; };
+    int32_t* g_choice = (int32_t*)gp(GL.choice);
+    double* g_adv = (double*)gp(GL.adv);
+    double* g_ret = (double*)gp(GL.ret);
+    float* g_last = (float*)gp(GL.last_value);
+    int32_t* g_sample = (int32_t*)gp(GL.sample);
+    int32_t* g_perm = (int32_t*)gp(GL.perm);
+    double* g_stats = (double*)gp(GL.stats);
+    {
+        dartmpc::IotaArgs ia;
+        ia.n = n; ia.out = sample;
+        HIPCHK(h, dartmpc_launch_iota(&ia, hs), "sample list launch");
+    }
+    for (int j = 0; j < cfg->iterations; ++j) {
+        const int it = cfg->it0 + j;
+        HIPCHK(h, hipMemsetAsync(p->nrec, 0, sizeof(int32_t) * (size_t)B, hs), "clear nrec");
+        HIPCHK(h, hipMemcpyAsync(ep0, p->episodes, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, hs),
+               "copy episodes");
+        // (with epochs = 0 the update leaves its statistics untouched)
+        if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(double) * 3, hs), "clear stats");
+        HIPCHK(h, launch_noise(cfg->seed, it, K, B, noise, hs), "noise launch");
+        if (int rc = collect(K, noise)) return rc;
+        if (dart_lmpc_critic_value_dev(B, p->critic, p->history, last_value, s) != DART_MPC_OK)
+            return fail(h, DART_MPC_EHIP, "critic value launch");
+        if (dart_lmpc_gae_dev(B, R, cfg->gamma, cfg->lam, p->nrec, p->rec_reward, p->rec_value, p->rec_done,
+                              last_value, adv, ret, s) != DART_MPC_OK)
+            return fail(h, DART_MPC_EHIP, "GAE launch");
+        HIPCHK(h, launch_perms(cfg->seed, it, ppo->epochs, n, perm, nullptr, hs), "permutation launch");
+        if (int rc = dart_lmpc_ppo_update_dev(ppo, n, n, sample, perm, p->rec_obs, p->rec_action, p->rec_logp, adv,
+                                              ret, p->weights, p->critic, p->adam, p->adam_step, stats, nullptr,
+                                              nullptr, nullptr, ws + L.ppo, s))
+            return fail(h, rc, "PPO update");
+        if (g) {
+            // 6a: m of this iteration's records, drawn without replacement, behind the rows held
+            HIPCHK(h, launch_perms(cfg->seed, it, 1, n, g_choice, nullptr, hs, dartmpc::kStreamChoice, gm),
+                   "choice launch");
+            HIPCHK(h, launch_global_append(g, g_fill, gm, n, n, sample, g_choice, p->rec_obs, p->rec_action,
+                                           p->rec_logp, p->rec_value, p->rec_reward, p->rec_done, hs),
+                   "global buffer append launch");
+            g_fill += gm;
+            const int ran = g_fill >= n ? 1 : 0;
+            const int logged_fill = g_fill;
+            if (ran) {
+                // 6b: the buffer holds G rows: one sequence for GAE, then a full update on the same optimizer
+                if (dart_lmpc_critic_value_dev(1, p->critic, g->obs + (size_t)(gG - 1) * kHist, g_last, s) != DART_MPC_OK)
+                    return fail(h, DART_MPC_EHIP, "critic value launch (global buffer)");
+                HIPCHK(h, launch_gae_seq(gG, cfg->gamma, cfg->lam, g->reward, g->value, g->done, g_last, g_adv, g_ret,
+                                         hs), "sequence GAE launch");
+                {
+                    dartmpc::IotaArgs ia;
+                    ia.n = gG; ia.out = g_sample;
+                    HIPCHK(h, dartmpc_launch_iota(&ia, hs), "sample list launch (global buffer)");
+                }
+                if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(g_stats, 0, sizeof(double) * 3, hs), "clear stats");
+                HIPCHK(h, launch_perms(cfg->seed, it, ppo->epochs, gG, g_perm, nullptr, hs,
+                                       dartmpc::kStreamGlobalPerm), "permutation launch (global buffer)");
+                if (int rc = dart_lmpc_ppo_update_dev(ppo, gG, gG, g_sample, g_perm, g->obs, g->action, g->logp, g_adv,
+                                                      g_ret, p->weights, p->critic, p->adam, p->adam_step, g_stats,
+                                                      nullptr, nullptr, nullptr, gws + GL.ppo, s))
+                    return fail(h, rc, "PPO update (global buffer)");
+                g_fill = 0;
+            }
+            dartmpc::GlobalLogArgs ga;
+            ga.fill = logged_fill; ga.ran = ran; ga.G = gG; ga.stats = g_stats;
+            ga.row = g->global_log + (size_t)dartmpc::kGlobalLogCols * j;
+            HIPCHK(h, dartmpc_launch_lmpc_global_log(&ga, hs), "global log launch");
+        }
+        if (cfg->mean_update)
+            if (dart_lmpc_mean_param_update_dev(pcfg, B, p->weights, p->history, p->model_params, p->current_k,
+                                                nullptr, s) != DART_MPC_OK)
+                return fail(h, DART_MPC_EHIP, "mean parameter update launch");
+        dartmpc::TrainLogArgs la;
+        la.B = B; la.K = K; la.R = R; la.n = n; la.iteration = it; la.track_best = cfg->track_best ? 1 : 0;
+        la.ep0 = ep0; la.episodes = p->episodes; la.last_return = p->last_return; la.nrec = p->nrec;
+        la.log_reward = p->log_reward; la.log_status = p->log_status; la.stats = stats;
+        la.actor = p->weights; la.critic = p->critic;
+        la.row = p->train_log + (size_t)dartmpc::kTrainLogCols * j;
+        la.best_return = p->best_return; la.best_weights = p->best_weights; la.best_iter = p->best_iter;
+        HIPCHK(h, dartmpc_launch_lmpc_train_log(&la, hs), "training log launch");
+    }
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                        const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                        const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                        void* stream) {
+    return dart_lmpc_train_global_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, nullptr, stream);
+}
+
+// (g == nullptr: dart_lmpc_train)
+int dart_lmpc_train_global(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                           const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                           const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                           const dart_lmpc_global_buffer* g, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = train_check(h, rcfg, ppo, cfg, B, p, false)) return rc;
+    if (g)
+        if (int rc = global_check(h, g, cfg->steps / rcfg->record_every * B, false)) return rc;
+    if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, "handle is not an LMPC handle");
+    if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
+    if (reset_rows < 0) return fail(h, DART_MPC_EINVAL, "negative reset_rows");
+    if (lmpc_null(*p, kLoop) || lmpc_null(*p, kPolicy) || lmpc_null(*p, kCollect) || lmpc_null(*p, kCollect, kRec))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (reset_rows > 0 && lmpc_null(*p, kCollect, kPool))
+        return fail(h, DART_MPC_EINVAL, "reset_rows > 0 with a null reset pool");
+    // instances that do not share timestep are the only way to nrec[b] != R
+    for (int b = 1; b < B; ++b)
+        if (p->timestep[b] != p->timestep[0]) return fail(h, DART_MPC_EINVAL, "instances differ in timestep");
+    if (cfg->iterations == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    hipStream_t s = stream_of(h, stream);
+    const size_t nB = (size_t)B, D = sizeof(double), F = sizeof(float);
+    const size_t K = (size_t)cfg->steps, R = K / (size_t)rcfg->record_every;
+    // every array of the closed loop and of the update whole: state both ways, logs and records down
+    LmpcStagePlan m{};
+    m.policy = m.collect = m.train = true;
+    m.B = nB; m.nw = (size_t)dart_lmpc_nw(h->cfg.N); m.log_rows = m.r1 = K; m.rec_rows = m.q1 = R;
+    m.reset_rows = (size_t)reset_rows;
+    RollStage S;
+    int idx[kLmpcArrays];
+    lmpc_stage(S, *p, m, idx);
+    const int i_log = S.add_log(p->train_log, (size_t)cfg->iterations, dartmpc::kTrainLogCols * D, 0,
+                                (size_t)cfg->iterations, false);
+    // the workspace: a block of the arena that does not travel
+    const size_t ws_bytes = dartmpc::train_workspace(B, (int)K, rcfg->record_every, ppo->epochs,
+                                                     ppo->mini_batch_size).bytes;
+    const int i_ws = S.add_log(nullptr, 1, ws_bytes, 0, 0, false);
+    // the global buffer: blocks of the arena whose held rows travel by hand (those held at the start go up, those
+    // held at the end come down), its log, and its workspace
+    dart_lmpc_global_buffer gd;
+    int gi[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    size_t g_rowbytes[6] = {kHist * F, kAct * F, F, F, D, F};
+    if (g) {
+        gd = *g;
+        const size_t cap = (size_t)g->capacity;
+        for (int q = 0; q < 6; ++q) gi[q] = S.add_log(nullptr, 1, cap * g_rowbytes[q], 0, 0, false);
+        gi[6] = S.add_log(g->global_log, (size_t)cfg->iterations, dartmpc::kGlobalLogCols * D, 0,
+                          (size_t)cfg->iterations, false);
+        gi[7] = S.add_log(nullptr, 1, dartmpc::global_workspace((int)(R * nB), ppo->epochs, ppo->mini_batch_size).bytes,
+                          0, 0, false);
+    }
+    if (int rc = S.reserve(h)) return rc;
+    dart_lmpc_train_buffers d{};
+    lmpc_bind(S, h, idx, d);
+    d.train_log = S.dev<double>(h, i_log);
+    d.workspace = S.dev<char>(h, i_ws);
+    if (int rc = S.upload(h, s)) return rc;
+    void* g_host[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (g) {
+        void* hp[6] = {g->obs, g->action, g->logp, g->value, g->reward, g->done};
+        for (int q = 0; q < 6; ++q) g_host[q] = hp[q];
+        gd.obs = S.dev<float>(h, gi[0]); gd.action = S.dev<float>(h, gi[1]); gd.logp = S.dev<float>(h, gi[2]);
+        gd.value = S.dev<float>(h, gi[3]); gd.reward = S.dev<double>(h, gi[4]); gd.done = S.dev<float>(h, gi[5]);
+        gd.global_log = S.dev<double>(h, gi[6]); gd.workspace = S.dev<char>(h, gi[7]);
+        for (int q = 0; q < 6 && g->fill > 0; ++q)
+            HIPCHK(h, hipMemcpyAsync(S.dev<char>(h, gi[q]), g_host[q], (size_t)g->fill * g_rowbytes[q],
+                                     hipMemcpyHostToDevice, s), "copy global buffer");
+    }
+    if (int rc = dart_lmpc_train_global_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, &d, g ? &gd : nullptr, s)) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    if (int rc = S.download(h, s)) return rc;
+    if (g) {
+        const int held = dart_lmpc_global_fill_after((int)(R * nB), g->fill, cfg->iterations);
+        for (int q = 0; q < 6 && held > 0; ++q)
+            HIPCHK(h, hipMemcpyAsync(g_host[q], S.dev<char>(h, gi[q]), (size_t)held * g_rowbytes[q],
+                                     hipMemcpyDeviceToHost, s), "copy global buffer back");
+    }
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+int dart_lmpc_train(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                    const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                    const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                    void* stream) {
+    return dart_lmpc_train_global(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, nullptr, stream);
+}
