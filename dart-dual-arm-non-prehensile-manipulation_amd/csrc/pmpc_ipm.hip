@@ -584,6 +584,10 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
     // sines and defects of the current point: computed here once, then carried over from the
     // accepted line-search trial (the update x + alpha d repeats the trial's arithmetic exactly)
     double g1[NAX], g2[NAX], gz[NAX], snc[NAX];
+    // OVL: the barrier logarithm log((theta - lo)(hi - theta)) of the current point is carried the same way (the
+    // line-search preparation needs it at the point the accepted trial evaluated it at; mu multiplies it outside)
+    double lgc[NAX];
+    (void)lgc;
     double th0 = 0.0;
     {
         const double w0 = vz_new(th);
@@ -592,6 +596,7 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             double s0, c0_;
             tilt_sincos(poly, th[j], s0, c0_);
             snc[j] = uon ? s0 : 0.0;
+            if constexpr (OVL) lgc[j] = log_fast((th[j] - lo) * (hi - th[j]));
             defects(p[j], v[j], snc[j], sp[j], sv[j], g1[j], g2[j]);
             gz[j] = RED ? 0.0 : zdefect(zz[j], w0, j);
             if (xon) th0 += fabs(g1[j]) + fabs(g2[j]) + fabs(gz[j]);
@@ -607,6 +612,18 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
     // IPOPT's soft restoration phase (round 5): in_soft while its steps are being taken, soft_count of them
     int in_soft = 0, soft_count = 0;
     STAMP(0);
+
+    // OVL: the z scan's multipliers after its levels row_shr 1, 2, 4 (and 8: the full scan), lane constants of the
+    // launch (Ts and the node index only), by the products the levels of direction() form
+    double zsm[4] = {0.0, 0.0, 0.0, 0.0};
+    (void)zsm;
+    if constexpr (OVL) {
+        double m = k == 0 ? 0.0 : zA[0], c = 0.0;
+        affine1_scan_level<0x111, 0xf>(m, c); zsm[0] = m;
+        affine1_scan_level<0x112, 0xf>(m, c); zsm[1] = m;
+        affine1_scan_level<0x114, 0xf>(m, c); zsm[2] = m;
+        if constexpr (!short2) { affine1_scan_level<0x118, 0xf>(m, c); zsm[3] = m; }
+    }
 
     // OVL: the current point to the factor wave, then barrier A.  Called for the start point at the first Newton
     // iteration, and in the accepted update where the step taken is not the line search's first trial point (that
@@ -961,11 +978,20 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             } else if constexpr (NAX == 1) {
                 const double src = from_prev(zC[0] * wd);
                 double m = k == 0 ? 0.0 : zA[0], c = k == 0 ? -gz[0] : src - gz[0];
+                if constexpr (OVL) {
+                    // the multipliers are lane constants of the launch (zsm, formed before the loop)
+                    affine1_scan_const<0x111, 0xf>(m, c);        // row_shr:1
+                    affine1_scan_const<0x112, 0xf>(zsm[0], c);   // row_shr:2
+                    affine1_scan_const<0x114, 0xf>(zsm[1], c);   // row_shr:4
+                    affine1_scan_const<0x118, 0xf>(zsm[2], c);   // row_shr:8
+                    m = short2 ? zsm[2] : zsm[3];
+                } else {
                 affine1_scan_level<0x111, 0xf>(m, c);   // row_shr:1
                 affine1_scan_level<0x112, 0xf>(m, c);   // row_shr:2
                 affine1_scan_level<0x114, 0xf>(m, c);   // row_shr:4
                 if constexpr (one_row || short2) affine1_scan_const<0x118, 0xf>(m, c);
                 else affine1_scan_level<0x118, 0xf>(m, c);   // row_shr:8
+                }
                 if constexpr (kWaves == 1) {
                     if constexpr (!one_row) affine1_scan_const<0x142, 0xa>(m, c);   // row_bcast:15 -> rows 1, 3
                 } else {       // two waves: as the state sweep
@@ -1003,6 +1029,8 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         bool accepted = false, ftype = false, tiny = false;
         int ls = 0, soc = 0;        // soc: 0 Newton step, 1.. correction pass, -1 Newton step again after failed passes
         double snt[NAX], g1t[NAX], g2t[NAX], gzt[NAX];     // the trial's sines and defects (carried on acceptance)
+        double lgt[NAX];                                   // OVL: and its barrier logarithm
+        (void)lgt;
         // OVL: the sine of the first trial point, formed with the speculative hand-over below (sn_pre_on: the next
         // trial takes it in place of its own tilt_sincos of the same angle, so the factor wave gets the trial's bits)
         double sn_pre = 0.0;
@@ -1051,7 +1079,12 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 const double ep = pt - rp[j], ev = vt - rv[j];
                 thl += xon ? fabs(g1t[j]) + fabs(g2t[j]) : 0.0;
                 phl += xon ? fma(scQp * ep, ep, scQv * ev * ev) : 0.0;
-                phl += uon ? fma(scR * tt[j], tt[j], -mu * log_fast((tt[j] - lo) * (hi - tt[j]))) : 0.0;
+                if constexpr (OVL) {
+                    lgt[j] = log_fast((tt[j] - lo) * (hi - tt[j]));
+                    phl += uon ? fma(scR * tt[j], tt[j], -mu * lgt[j]) : 0.0;
+                } else {
+                    phl += uon ? fma(scR * tt[j], tt[j], -mu * log_fast((tt[j] - lo) * (hi - tt[j]))) : 0.0;
+                }
             }
             if constexpr (RED) {
 #pragma unroll
@@ -1103,7 +1136,9 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                     const double sl = th[j] - lo, su = hi - th[j];
                     phil += xon ? fma(scQp * ep, ep, scQv * ev * ev) : 0.0;
                     gtdl += xon ? fma(qp2 * ep, dp[j], qv2 * ev * dv[j]) : 0.0;
-                    phil += uon ? fma(scR * th[j], th[j], -mu * log_fast(sl * su)) : 0.0;
+                    // (OVL: sl * su has the bits of the accepted trial's argument, so its logarithm is carried)
+                    if constexpr (OVL) phil += uon ? fma(scR * th[j], th[j], -mu * lgc[j]) : 0.0;
+                    else phil += uon ? fma(scR * th[j], th[j], -mu * log_fast(sl * su)) : 0.0;
                     gtdl += uon ? rt[j] * dth[j] : 0.0;
                 }
                 // IPOPT's tiny-step test (max |d|/(1+|x|) < 10 eps_mach accepts the full step unfiltered): its maximum
@@ -1329,6 +1364,7 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
 #pragma unroll
         for (int j = 0; j < NAX; ++j) {
             g1[j] = g1t[j]; g2[j] = g2t[j]; gz[j] = gzt[j];
+            if constexpr (OVL) lgc[j] = lgt[j];
             p[j] = fma(alpha, dp[j], p[j]); v[j] = fma(alpha, dv[j], v[j]);
             zz[j] = fma(alpha, dz[j], zz[j]);
         }
