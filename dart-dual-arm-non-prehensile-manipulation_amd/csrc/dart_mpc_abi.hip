@@ -26,7 +26,9 @@ int check_cfg(const dart_mpc_config* c) {
     if (!c) return 0;
     if (c->variant != DART_MPC_PMPC && c->variant != DART_MPC_RMPC && c->variant != DART_MPC_LMPC) return 0;
     if (c->N < 1 || c->N > 63) return 0;
-    if (!(c->Ts > 0.0) || !(c->tol > 0.0) || !(c->gravity == c->gravity) || c->max_iter < 1 || c->B_max < 1) return 0;
+    // (PMPC takes max_iter = 0, as IPOPT does: no Newton iteration, the start point comes back at status -1)
+    if (!(c->Ts > 0.0) || !(c->tol > 0.0) || !(c->gravity == c->gravity) || c->B_max < 1) return 0;
+    if (c->max_iter < (c->variant == DART_MPC_PMPC ? 0 : 1)) return 0;
     if (c->acceptable_iter < 0 || (c->acceptable_iter > 0 && !(c->acceptable_tol > 0.0))) return 0;
     if (c->max_soc < 0 || c->max_soc > 8) return 0;
     if (c->pmpc_path != 0 && c->pmpc_path != 1) return 0;

@@ -51,11 +51,11 @@ namespace dartmpc {
 // optimisation level that is fastest for it.
 #ifdef DART_STAMPS
 #ifndef PMPC_SEQ
-__device__ unsigned long long g_stamp[16];
-#define STAMP_FLUSH(b) STAMP_FLUSH_TO(g_stamp, b)
+__device__ unsigned long long g_stamp[32];
+#define STAMP_FLUSH(b) STAMP_FLUSH32_TO(g_stamp, b)
 #else
-__device__ unsigned long long g_stamp_seq[16];
-#define STAMP_FLUSH(b) STAMP_FLUSH_TO(g_stamp_seq, b)
+__device__ unsigned long long g_stamp_seq[32];
+#define STAMP_FLUSH(b) STAMP_FLUSH32_TO(g_stamp_seq, b)
 #endif
 #else
 #define STAMP_FLUSH(b) STAMP_FLUSH_TO(g_stamp, b)
@@ -200,6 +200,14 @@ __device__ __forceinline__ void mat4_scan_level(double* T) {
 // scan, the least-square iteration, second-order corrections, failures): C2 +2.1 % (A/B); the one-row
 // build (N <= 15) measured 1 % slower with them and goes without
 #define PM_EXPECT(x, v) (ONEROW ? (bool)(x) : (bool)__builtin_expect((long)(bool)(x), (v)))
+
+// a double that holds the same value in every lane, as a scalar (two v_readfirstlane)
+__device__ __forceinline__ double wave_uniform(double x) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b & 0xffffffffu));
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
 
 // The per-lane stage constants of the Riccati factorisation (pmpc_solve derives them at its start).
 struct PmStage {
@@ -396,18 +404,25 @@ __device__ __forceinline__ bool pmpc_riccati(const int lane, const int N, const 
     return !wany(bad);
 }
 
-// The overlapped build (OVL; NAX == 1, QSCAN, one wave per instance, launched with two waves): LDS hand-over
-// between the solver wave (wave 0) and the factor wave (wave 1).  [field][lane]: every access is one
-// conflict-free 8-byte access per lane.  pt: th, snc, lp, lv, zl, zu of the current point (wave 0 writes
-// before barrier A, wave 1 reads after it; wave 0 reads its own zl, zu back when the speculated point is taken);
-// fc: P11, P12, P22, W1, W2, iQs (wave 1 writes before barrier B, wave 0 reads after it); flag: [0] stop, [1] use_scan, [2] ok.  Each buffer has one writer, and its next write
-// comes after a barrier that the reader crosses only with its reads complete, so single buffers are enough.
+// The overlapped build (OVL; NAX == 1, QSCAN, one wave per instance, launched with three waves): LDS hand-over
+// between the solver wave (wave 0) and its two helper waves, the factor wave (wave 1) and the evaluation wave
+// (wave 2).  [field][lane]: every access is one conflict-free 8-byte access per lane.
+// pt: th, snc, lp, lv, zl, zu of the current point, then p, v, z and mu (the same value in every lane: one unmasked
+// write); wave 0 writes before barrier A, the helper waves read after it (the factor wave rows 0-5 only); wave 0
+// reads its own zl, zu back when the speculated point is taken.
+// fc: P11, P12, P22, W1, W2, iQs (wave 1 writes before barrier B, wave 0 reads after it).
+// mu_new and flag[4], flag[5]: the evaluation wave's results for the point (the updated mu, converged, mu
+// decreased), written before barrier B and read by wave 0 after it with the factors.
+// flag: [0] stop, [1] use_scan, [2] ok, [4] converged, [5] mu decreased ([3], [6]: the stamps build's helper-wave
+// timers).  Each buffer has one writer, and its next write comes after a barrier that the readers cross only with
+// their reads complete, so single buffers are enough.
 struct PmOvlShared {
-    double pt[6][kWave];
+    double pt[10][kWave];
     double fc[6][kWave];
-    int flag[4];       // ([3]: the stamps build's factor-wave timer)
+    double mu_new;
+    int flag[8];
 };
-__shared__ PmOvlShared g_pm_ovl;       // only the overlapped instantiations name it (6 KB beside PrShared when fused)
+__shared__ PmOvlShared g_pm_ovl;       // only the overlapped instantiations name it (8 KB beside PrShared when fused)
 
 template <int NAX, bool QSCAN, bool ONEROW, bool SHORT2, bool RED, bool OVL = false>
 __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
@@ -491,54 +506,6 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         e11 = e1 * e1; e12 = 2.0 * e1 * e2; e22 = e2 * e2;
         rt0 = uon ? fma(snj, fma(b1, lpnj, b2 * lvnj), r2 + zlj * islj + zuj * isuj) : 1.0;
     };
-    if constexpr (OVL) {
-        // The factor wave.  It has derived the lane constants above from the same inputs with the same code as the
-        // solver wave (the gradient scaling's wave reduction included).  Every round: wait for a point (barrier A),
-        // factor it at delta = 0 (attempt 0 of the iteration's Riccati block), publish the result (barrier B).  It
-        // tests the stop word after every barrier and leaves the kernel when it is set (pmpc_solve's exit funnel).
-        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0) {
-            // Rounds: the start point, then per iteration the speculated first trial point and, where that trial is
-            // not the accepted step, the accepted point: at most 1 + 2 max_iter.  The bound only ends a wave that a
-            // protocol slip would otherwise leave at a barrier for ever (a terminated wave takes no part in one).
-            const long long max_rounds = 2ll * a.max_iter + 8;
-            for (long long round = 0; round < max_rounds; ++round) {
-                __syncthreads();                                            // barrier A, or the stop barrier
-                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return false;
-#ifdef DART_STAMPS
-                const unsigned long long tf0 = __builtin_amdgcn_s_memtime();
-#endif
-                const double th1 = g_pm_ovl.pt[0][lane], sn1 = g_pm_ovl.pt[1][lane];
-                const double lp1 = g_pm_ovl.pt[2][lane], lv1 = g_pm_ovl.pt[3][lane];
-                const double zl1 = g_pm_ovl.pt[4][lane], zu1 = g_pm_ovl.pt[5][lane];
-                const double c_ = tilt_cos_econ(poly, th1);
-                const double cs1 = uon ? c_ : 0.0;
-                const double ln = from_next(lp1), vn = from_next(lv1);
-                const double lpn1 = uon ? ln : 0.0, lvn1 = uon ? vn : 0.0;
-                const double sl = th1 - lo, su = hi - th1;
-                const double isl1 = uon ? frcp(sl) : 0.0, isu1 = uon ? frcp(su) : 0.0;
-                double be1[NAX], be2[NAX], E11[NAX], E12[NAX], E22[NAX], Rt0[NAX];
-                quad_stage(cs1, sn1, lpn1, lvn1, zl1, isl1, zu1, isu1, be1[0], be2[0], E11[0], E12[0], E22[0], Rt0[0]);
-                double W1[NAX], W2[NAX], P11[NAX], P12[NAX], P22[NAX], iQs[NAX];
-                bool us = false;
-                const bool okf = pmpc_riccati<NAX, QSCAN, ONEROW, SHORT2>(lane, N, uon, false, 0.0, qp2, qv2, stg, be1,
-                                                                         be2, E11, E12, E22, Rt0, P11, P12, P22, W1,
-                                                                         W2, iQs, us);
-                g_pm_ovl.fc[0][lane] = P11[0]; g_pm_ovl.fc[1][lane] = P12[0]; g_pm_ovl.fc[2][lane] = P22[0];
-                g_pm_ovl.fc[3][lane] = W1[0]; g_pm_ovl.fc[4][lane] = W2[0]; g_pm_ovl.fc[5][lane] = iQs[0];
-                if (lane == 0) { g_pm_ovl.flag[1] = us ? 1 : 0; g_pm_ovl.flag[2] = okf ? 1 : 0; }
-#ifdef DART_STAMPS
-                // the factor wave's own time from barrier A to its arrival at barrier B, summed (slot 13 of wave 0)
-                t_acc_[13] += __builtin_amdgcn_s_memtime() - tf0;
-                if (lane == 0) g_pm_ovl.flag[3] = (int)t_acc_[13];
-#endif
-                __syncthreads();                                            // barrier B, or the stop barrier
-                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return false;
-            }
-            return false;
-        }
-        if (lane == 0) g_pm_ovl.flag[0] = 0;      // the solver wave, before its first barrier
-    }
-
     const double tol = a.tol, mu_min = tol / 10;
     const double n_eq = 6.0 * (N + 1), n_b = 4.0 * N;       // IPOPT counts on the full NLP
     const double inv_neb = 1.0 / (n_eq + n_b), inv_nb = 1.0 / n_b;
@@ -580,6 +547,140 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         for (int j = 0; j < NAX; ++j) sq[j] = uon ? t[j] * t[j] : 0.0;
         return -a.g * axes_sum(sq);
     };
+
+    // OVL, the evaluation wave's verdict on a point: its optimality error (IPOPT eq. 5), the convergence test and the
+    // monotone barrier update, statement for statement those of the iteration loop below (which the one-wave builds
+    // run, and whose text stays untouched so that they keep their instructions; the bit-for-bit tests of the
+    // overlapped builds against them hold the two together).  Of the lane values only those the error terms need:
+    // the cosine and the next node's multipliers, not the reciprocal slacks.  Returns converged; mu is updated in
+    // place and dec tells whether it decreased (BacktrackingLineSearch::Reset in the solving wave).
+    auto point_verdict = [&](const double (&p)[NAX], const double (&v)[NAX], const double (&th)[NAX],
+                             const double (&lp)[NAX], const double (&lv)[NAX], const double (&zl)[NAX],
+                             const double (&zu)[NAX], const double (&g1)[NAX], const double (&g2)[NAX],
+                             const double (&gz)[NAX], double& mu, bool& dec) -> bool {
+        double dinf = 0.0, pinf = 0.0, c0 = 0.0, cmin = 1e300, suml = 0.0, sumz = 0.0;
+#pragma unroll
+        for (int j = 0; j < NAX; ++j) {
+            const double c_ = tilt_cos_econ(poly, th[j]);
+            const double cs = uon ? c_ : 0.0;
+            const double ln = from_next(lp[j]), vn = from_next(lv[j]);       // unconditional: EXEC stays full
+            const double lpn = uon ? ln : 0.0, lvn = uon ? vn : 0.0;
+            const double sl = th[j] - lo, su = hi - th[j];
+            const double r1 = fma(qp2, p[j] - rp[j], lp[j] - lpn);
+            const double r2x = fma(qv2, v[j] - rv[j], lv[j] - fma(a12, lpn, a22 * lvn));
+            const double ru = fma(r2, th[j], -cs * fma(b1, lpn, b2 * lvn)) - zl[j] + zu[j];
+            dinf = fmax(dinf, xon ? fmax(fabs(r1), fabs(r2x)) : 0.0);
+            dinf = fmax(dinf, uon ? fabs(ru) : 0.0);
+            pinf = fmax(pinf, xon ? fmax(fmax(fabs(g1[j]), fabs(g2[j])), fabs(gz[j])) : 0.0);
+            suml += xon ? fabs(lp[j]) + fabs(lv[j]) : 0.0;
+            c0 = fmax(c0, uon ? fmax(zl[j] * sl, zu[j] * su) : 0.0);
+            cmin = fmin(cmin, uon ? fmin(zl[j] * sl, zu[j] * su) : 1e300);
+            sumz += zl[j] + zu[j];
+        }
+        float dinf_f = (float)dinf, pinf_f = (float)pinf, c0_f = (float)c0, cmin_f = (float)cmin;
+        float suml_f = (float)suml, sumz_f = (float)sumz;
+        wred_errors(dinf_f, pinf_f, c0_f, cmin_f, suml_f, sumz_f);
+        const double dinf_w = dinf_f, pinf_w = pinf_f, c0_w = c0_f;
+        const double cmin_w = cmin_f;
+        const float sz_w = sumz_f;
+        const double is_d = 100.0 * frcp(fmax(100.0, (double)(suml_f + sz_w) * inv_neb));
+        const double is_c = 100.0 * frcp(fmax(100.0, (double)sz_w * inv_nb));
+        dinf = dinf_w; pinf = pinf_w; c0 = c0_w;
+        dec = false;
+        if (fmax(dinf * is_d, fmax(pinf, c0 * is_c)) <= tol) return true;
+        for (;;) {
+            const double cmu = fmax(c0 - mu, mu - cmin_w);
+            if (fmax(dinf * is_d, fmax(pinf, cmu * is_c)) > 10.0 * mu || mu <= mu_min) break;
+            mu = fmax(mu_min, fmin(0.2 * mu, mu * sqrt(mu)));
+            dec = true;
+        }
+        return false;
+    };
+    (void)point_verdict;
+    if constexpr (OVL) {
+        // The helper waves.  Each has derived the lane constants above from the same inputs with the same code as the
+        // solver wave (the gradient scaling's wave reduction included).  Every round: wait for a point (barrier A),
+        // run the role's body on it, publish the result (barrier B).  One skeleton for both roles, so they cannot
+        // differ in how they meet the solver wave's barriers: a helper tests the stop word after every barrier and
+        // leaves the kernel when it is set (pmpc_solve's exit funnel).
+        // Rounds: the start point, then per iteration the speculated first trial point and, where that trial is not
+        // the accepted step, the accepted point: at most 1 + 2 max_iter.  The bound only ends a wave that a protocol
+        // slip would otherwise leave at a barrier for ever (a terminated wave takes no part in one).
+        auto helper_rounds = [&](auto&& body) {
+            const long long max_rounds = 2ll * a.max_iter + 8;
+            for (long long round = 0; round < max_rounds; ++round) {
+                __syncthreads();                                            // barrier A, or the stop barrier
+                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return;
+                body();
+                __syncthreads();                                            // barrier B, or the stop barrier
+                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return;
+            }
+        };
+        const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        if (wv == 1) {
+            // The factor wave: the point at delta = 0 (attempt 0 of the iteration's Riccati block).
+            helper_rounds([&]() {
+#ifdef DART_STAMPS
+                const unsigned long long tf0 = __builtin_amdgcn_s_memtime();
+#endif
+                const double th1 = g_pm_ovl.pt[0][lane], sn1 = g_pm_ovl.pt[1][lane];
+                const double lp1 = g_pm_ovl.pt[2][lane], lv1 = g_pm_ovl.pt[3][lane];
+                const double zl1 = g_pm_ovl.pt[4][lane], zu1 = g_pm_ovl.pt[5][lane];
+                const double c_ = tilt_cos_econ(poly, th1);
+                const double cs1 = uon ? c_ : 0.0;
+                const double ln = from_next(lp1), vn = from_next(lv1);
+                const double lpn1 = uon ? ln : 0.0, lvn1 = uon ? vn : 0.0;
+                const double sl = th1 - lo, su = hi - th1;
+                const double isl1 = uon ? frcp(sl) : 0.0, isu1 = uon ? frcp(su) : 0.0;
+                double be1[NAX], be2[NAX], E11[NAX], E12[NAX], E22[NAX], Rt0[NAX];
+                quad_stage(cs1, sn1, lpn1, lvn1, zl1, isl1, zu1, isu1, be1[0], be2[0], E11[0], E12[0], E22[0], Rt0[0]);
+                double W1[NAX], W2[NAX], P11[NAX], P12[NAX], P22[NAX], iQs[NAX];
+                bool us = false;
+                const bool okf = pmpc_riccati<NAX, QSCAN, ONEROW, SHORT2>(lane, N, uon, false, 0.0, qp2, qv2, stg, be1,
+                                                                         be2, E11, E12, E22, Rt0, P11, P12, P22, W1,
+                                                                         W2, iQs, us);
+                g_pm_ovl.fc[0][lane] = P11[0]; g_pm_ovl.fc[1][lane] = P12[0]; g_pm_ovl.fc[2][lane] = P22[0];
+                g_pm_ovl.fc[3][lane] = W1[0]; g_pm_ovl.fc[4][lane] = W2[0]; g_pm_ovl.fc[5][lane] = iQs[0];
+                if (lane == 0) { g_pm_ovl.flag[1] = us ? 1 : 0; g_pm_ovl.flag[2] = okf ? 1 : 0; }
+#ifdef DART_STAMPS
+                // the factor wave's own time from barrier A to its arrival at barrier B, summed (slot 13 of wave 0)
+                t_acc_[13] += __builtin_amdgcn_s_memtime() - tf0;
+                if (lane == 0) g_pm_ovl.flag[3] = (int)t_acc_[13];
+#endif
+            });
+            return false;
+        }
+        if (wv == 2) {
+            // The evaluation wave: the defects of the point by the expressions of the line-search trial that wave 0
+            // carries them from (and of the start point), then point_verdict.  It indexes memory by lane only,
+            // whatever the point holds.
+            helper_rounds([&]() {
+#ifdef DART_STAMPS
+                const unsigned long long te0 = __builtin_amdgcn_s_memtime();
+#endif
+                const double th1[NAX] = {g_pm_ovl.pt[0][lane]}, sn1 = g_pm_ovl.pt[1][lane];
+                const double lp1[NAX] = {g_pm_ovl.pt[2][lane]}, lv1[NAX] = {g_pm_ovl.pt[3][lane]};
+                const double zl1[NAX] = {g_pm_ovl.pt[4][lane]}, zu1[NAX] = {g_pm_ovl.pt[5][lane]};
+                const double p1[NAX] = {g_pm_ovl.pt[6][lane]}, v1[NAX] = {g_pm_ovl.pt[7][lane]};
+                const double zz1 = g_pm_ovl.pt[8][lane];
+                double mu1 = wave_uniform(g_pm_ovl.pt[9][lane]);
+                double g1e[NAX], g2e[NAX], gze[NAX];
+                const double w1 = vz_new(th1);
+                defects(p1[0], v1[0], sn1, sp[0], sv[0], g1e[0], g2e[0]);
+                gze[0] = zdefect(zz1, w1, 0);
+                bool dec = false;
+                const bool conv = point_verdict(p1, v1, th1, lp1, lv1, zl1, zu1, g1e, g2e, gze, mu1, dec);
+                if (lane == 0) { g_pm_ovl.mu_new = mu1; g_pm_ovl.flag[4] = conv ? 1 : 0; g_pm_ovl.flag[5] = dec ? 1 : 0; }
+#ifdef DART_STAMPS
+                // the evaluation wave's own time from barrier A to its arrival at barrier B, summed (slot 17 of wave 0)
+                t_acc_[17] += __builtin_amdgcn_s_memtime() - te0;
+                if (lane == 0) g_pm_ovl.flag[6] = (int)t_acc_[17];
+#endif
+            });
+            return false;
+        }
+        if (lane == 0) g_pm_ovl.flag[0] = 0;      // the solver wave, before its first barrier
+    }
 
     // sines and defects of the current point: computed here once, then carried over from the
     // accepted line-search trial (the update x + alpha d repeats the trial's arithmetic exactly)
@@ -625,10 +726,10 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         if constexpr (!short2) { affine1_scan_level<0x118, 0xf>(m, c); zsm[3] = m; }
     }
 
-    // OVL: the current point to the factor wave, then barrier A.  Called for the start point at the first Newton
+    // OVL: the current point and mu to the helper waves, then barrier A.  Called for the start point at the first Newton
     // iteration, and in the accepted update where the step taken is not the line search's first trial point (that
     // point is handed over speculatively before the trial, below; the update then first crosses barrier B to drop
-    // the factors of the rejected point).  The scheduling barriers keep the compiler from moving the work that
+    // the factors and the verdict of the rejected point).  The scheduling barriers keep the compiler from moving the work that
     // follows (plain register arithmetic, which __syncthreads() does not order) ahead of barrier A.
     bool published = false;
     auto publish = [&]() {
@@ -636,6 +737,8 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         g_pm_ovl.pt[0][lane] = th[0]; g_pm_ovl.pt[1][lane] = snc[0];
         g_pm_ovl.pt[2][lane] = lp[0]; g_pm_ovl.pt[3][lane] = lv[0];
         g_pm_ovl.pt[4][lane] = zl[0]; g_pm_ovl.pt[5][lane] = zu[0];
+        g_pm_ovl.pt[6][lane] = p[0]; g_pm_ovl.pt[7][lane] = v[0];
+        g_pm_ovl.pt[8][lane] = zz[0]; g_pm_ovl.pt[9][lane] = mu;
         __syncthreads();                                                    // barrier A
         __builtin_amdgcn_sched_barrier(0);
         published = true;
@@ -661,6 +764,9 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             if (PM_EXPECT(!lsm && !published, 0)) publish();
         }
         // -------- point quantities and optimality error (IPOPT eq. 5) ------------
+        // (OVL: this wave forms the lane values only.  The error terms, the convergence test and the mu update, the
+        // statements under `if constexpr (!OVL)`, are the evaluation wave's, which states them in point_verdict; the
+        // text here stays as it is, declarations and all, so that every other build keeps its instructions.)
         double sn[NAX], cs[NAX], isl[NAX], isu[NAX], lpn[NAX], lvn[NAX];
         double dinf = 0.0, pinf = 0.0, c0 = 0.0, cmin = 1e300, suml = 0.0, sumz = 0.0;
 #pragma unroll
@@ -680,9 +786,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             lpn[j] = uon ? ln : 0.0; lvn[j] = uon ? vn : 0.0;
             const double sl = th[j] - lo, su = hi - th[j];
             isl[j] = uon ? frcp(sl) : 0.0; isu[j] = uon ? frcp(su) : 0.0;
+            STAMP(16);      // (stamps build: the lane values end, the error terms begin)
             const double r1 = fma(qp2, p[j] - rp[j], lp[j] - lpn[j]);
             const double r2x = fma(qv2, v[j] - rv[j], lv[j] - fma(a12, lpn[j], a22 * lvn[j]));
             const double ru = fma(r2, th[j], -cs[j] * fma(b1, lpn[j], b2 * lvn[j])) - zl[j] + zu[j];
+            if constexpr (!OVL) {
             dinf = fmax(dinf, xon ? fmax(fabs(r1), fabs(r2x)) : 0.0);
             dinf = fmax(dinf, uon ? fabs(ru) : 0.0);
             pinf = fmax(pinf, xon ? fmax(fmax(fabs(g1[j]), fabs(g2[j])), fabs(gz[j])) : 0.0);
@@ -690,10 +798,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             c0 = fmax(c0, uon ? fmax(zl[j] * sl, zu[j] * su) : 0.0);
             cmin = fmin(cmin, uon ? fmin(zl[j] * sl, zu[j] * su) : 1e300);
             sumz += zl[j] + zu[j];
+            }
         }
         float dinf_f = (float)dinf, pinf_f = (float)pinf, c0_f = (float)c0, cmin_f = (float)cmin;
         float suml_f = (float)suml, sumz_f = (float)sumz;
-        wred_errors(dinf_f, pinf_f, c0_f, cmin_f, suml_f, sumz_f);
+        if constexpr (!OVL) wred_errors(dinf_f, pinf_f, c0_f, cmin_f, suml_f, sumz_f);
         const double dinf_w = dinf_f, pinf_w = pinf_f, c0_w = c0_f;
         const double cmin_w = cmin_f;
         // IPOPT's scalings s_d, s_c (>= 1) as reciprocals: one division each instead of one per test
@@ -702,16 +811,20 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         const double is_c = 100.0 * frcp(fmax(100.0, (double)sz_w * inv_nb));
         dinf = dinf_w; pinf = pinf_w; c0 = c0_w;
         STAMP(1);
+        if constexpr (!OVL) {
         if (!lsm && fmax(dinf * is_d, fmax(pinf, c0 * is_c)) <= tol) { status = 0; break; }
+        }
         // -------- monotone barrier update (Fiacco-McCormick, may fire repeatedly) --
         // max_i |z_i s_i - mu| = max(max z s - mu, mu - min z s): one reduction pair, scalar loop
+        if constexpr (!OVL) {
         for (; !lsm;) {
             const double cmu = fmax(c0 - mu, mu - cmin_w);
             if (fmax(dinf * is_d, fmax(pinf, cmu * is_c)) > 10.0 * mu || mu <= mu_min) break;
             mu = fmax(mu_min, fmin(0.2 * mu, mu * sqrt(mu)));
             nfilt = 0; in_soft = 0;       // BacktrackingLineSearch::Reset: the filter and the soft phase
         }
-        const double tau = fmax(0.99, 1.0 - mu);
+        }
+        double tau = fmax(0.99, 1.0 - mu);
         STAMP(2);
 
         // -------- Newton step: Riccati recursion + inertia correction ---------------
@@ -721,7 +834,8 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             quad_stage(cs[j], sn[j], lpn[j], lvn[j], zl[j], isl[j], zu[j], isu[j], be1[j], be2[j], E11[j], E12[j],
                        E22[j], Rt0[j]);
             // the barrier gradient in theta (least-square estimate: r_u = grad f - z_L + z_U)
-            rt[j] = uon ? (lsm ? r2 * th[j] - zl[j] + zu[j] : fma(r2, th[j], mu * (isu[j] - isl[j]))) : 0.0;
+            // (OVL: mu comes with the factors, so the Newton iterations form it after barrier B)
+            if (!OVL || lsm) rt[j] = uon ? (lsm ? r2 * th[j] - zl[j] + zu[j] : fma(r2, th[j], mu * (isu[j] - isl[j]))) : 0.0;
             q1[j] = qp2 * (p[j] - rp[j]); q2[j] = qv2 * (v[j] - rv[j]);
         }
         double W1[NAX], W2[NAX], P11[NAX], P12[NAX], P22[NAX], iQs[NAX];
@@ -731,7 +845,10 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         if constexpr (OVL) {
             // attempt 0 comes from the factor wave.  Where it did not take the scan or found a Quu <= 0, the loop
             // below runs in this wave from attempt 0 on, as in the one-wave build (the sequential sweep, the
-            // inertia retries): cold paths, without the factor wave and so without barriers.
+            // inertia retries): cold paths, without the helper waves and so without barriers.
+            // The evaluation wave's verdict on the point comes with the factors: converged (status 0 and out through
+            // the funnel, with nothing outstanding: both helper waves are on their way to barrier A), the updated mu,
+            // and whether it decreased (BacktrackingLineSearch::Reset, as in the one-wave mu update).
             if (!lsm) {
                 __builtin_amdgcn_sched_barrier(0);      // everything above is done before this wave waits
                 SPAN_BEGIN(t_b);
@@ -739,10 +856,17 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 SPAN_END(14, t_b);                      // (stamps build, slot 14: the wait alone)
                 // (the six values are read with the flags, not after the branch on them: one LDS round trip)
                 const int usf = g_pm_ovl.flag[1], okff = g_pm_ovl.flag[2];
+                const int cvf = g_pm_ovl.flag[4], mdf = g_pm_ovl.flag[5];
+                const double mun = g_pm_ovl.mu_new;
                 P11[0] = g_pm_ovl.fc[0][lane]; P12[0] = g_pm_ovl.fc[1][lane]; P22[0] = g_pm_ovl.fc[2][lane];
                 W1[0] = g_pm_ovl.fc[3][lane]; W2[0] = g_pm_ovl.fc[4][lane]; iQs[0] = g_pm_ovl.fc[5][lane];
                 const bool us = __builtin_amdgcn_readfirstlane(usf) != 0;
                 const bool okf = __builtin_amdgcn_readfirstlane(okff) != 0;
+                if (__builtin_amdgcn_readfirstlane(cvf)) { status = 0; break; }
+                mu = wave_uniform(mun);
+                if (__builtin_amdgcn_readfirstlane(mdf)) { nfilt = 0; in_soft = 0; }
+                tau = fmax(0.99, 1.0 - mu);
+                rt[0] = uon ? fma(r2, th[0], mu * (isu[0] - isl[0])) : 0.0;
                 if (PM_EXPECT(us && okf, 1)) {
                     STAMP_ADD(11, 1);
                     ok = true; attempt = 1;
@@ -1181,6 +1305,8 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                     g_pm_ovl.pt[0][lane] = thc; g_pm_ovl.pt[1][lane] = sn_pre;
                     g_pm_ovl.pt[2][lane] = fma(alpha, dlp[0], lp[0]); g_pm_ovl.pt[3][lane] = fma(alpha, dlv[0], lv[0]);
                     g_pm_ovl.pt[4][lane] = uon ? zln : 0.0; g_pm_ovl.pt[5][lane] = uon ? zun : 0.0;
+                    g_pm_ovl.pt[6][lane] = fma(alpha, dp[0], p[0]); g_pm_ovl.pt[7][lane] = fma(alpha, dv[0], v[0]);
+                    g_pm_ovl.pt[8][lane] = fma(alpha, dz[0], zz[0]); g_pm_ovl.pt[9][lane] = mu;
                     __syncthreads();                                        // barrier A
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1329,12 +1455,12 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             ++nfilt;
         }
         // -------- accept the step ----------------------------------------------------
-        // (the quantities the factor wave needs come first: a miss of the overlapped build hands them over before the rest)
-        // OVL, hit: the step taken is the first trial point, which the factor wave already has and may be reading,
+        // (the quantities the helper waves need come first: a miss of the overlapped build hands them over before the rest)
+        // OVL, hit: the step taken is the first trial point, which the helper waves already have and may be reading,
         // so nothing is written to pt and no barrier is crossed; z comes back from this wave's own pt entries (the
         // clamp was evaluated for the hand-over).  Miss (a backtracked step, an accepted correction pass, the Newton
-        // step again after failed passes): barrier B first, the factors of the rejected trial point are dropped
-        // unread, then the accepted point goes over at barrier A as the start point did.
+        // step again after failed passes): barrier B first, the factors and the verdict of the rejected trial point
+        // are dropped unread, then the accepted point goes over at barrier A as the start point did.
         const bool hit = OVL && soc == 0 && ls == 0;
         if constexpr (OVL) {
             STAMP_ADD(15, hit ? (1ull << 16) : (1ull << 32));      // (stamps build: hits, misses beside the corrections)
@@ -1359,38 +1485,44 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             }
         }
         if constexpr (OVL) {
+            // (the evaluation wave needs p, v and z of the accepted point as well: formed ahead of a miss's hand-over)
+            p[0] = fma(alpha, dp[0], p[0]); v[0] = fma(alpha, dv[0], v[0]);
+            zz[0] = fma(alpha, dz[0], zz[0]);
             if (PM_EXPECT(!hit, 0)) publish();
         }
 #pragma unroll
         for (int j = 0; j < NAX; ++j) {
             g1[j] = g1t[j]; g2[j] = g2t[j]; gz[j] = gzt[j];
             if constexpr (OVL) lgc[j] = lgt[j];
-            p[j] = fma(alpha, dp[j], p[j]); v[j] = fma(alpha, dv[j], v[j]);
-            zz[j] = fma(alpha, dz[j], zz[j]);
+            if constexpr (!OVL) {
+                p[j] = fma(alpha, dp[j], p[j]); v[j] = fma(alpha, dv[j], v[j]);
+                zz[j] = fma(alpha, dz[j], zz[j]);
+            }
         }
         theta = th_t;
         STAMP(7);
     }
     if constexpr (OVL) {
         // The exit funnel of the overlapped build.  The iteration loop has no return, and every way out of it
-        // (status 0 between barriers A and B; status -3 after barrier B and before the line search's barrier A; the
+        // (status 0 and status -3 after barrier B and before the line search's barrier A, nothing outstanding; the
         // failed line search with its hand-over to the restoration phases or status -2, after the barrier A of a
         // speculated point that is then not used; max_iter at the loop head, likewise after a barrier A; a loop
-        // of no iterations) arrives here.  DESIGN §5.R8 has the table.
+        // of no iterations) arrives here.  DESIGN §5.R10 has the table.
         // Invariant: this wave crosses barriers A, B, A, B, ... only in publish() (the first Newton iteration's
         // head, the update of a missed speculation), at the speculative hand-over of the line search (A), at the
         // head of the Riccati block (B) and in the update of a missed speculation (B) (none in the least-square
         // iteration, its `continue` included, in the retries or in the correction passes), then sets the stop word
-        // and crosses exactly one more barrier, here.  The
-        // factor wave crosses a barrier, tests the stop word and goes on to the next barrier, so it meets each of
-        // this wave's barriers in turn whatever their role, and leaves at the first test that finds the word set:
-        // after the stop barrier at the latest (or earlier, having seen the word before this wave arrived; a
-        // terminated wave takes no part in a barrier).  Both waves thus execute the same number of barriers up
-        // to the factor wave's end, and nothing below waits for it.
+        // and crosses exactly one more barrier, here.  Each helper wave (helper_rounds, one skeleton for both) crosses
+        // a barrier, tests the stop word and goes on to the next barrier, so it meets each of this wave's barriers in
+        // turn whatever their role, and leaves at the first test that finds the word set: after the stop barrier at
+        // the latest (or earlier, having seen the word before this wave arrived; a terminated wave takes no part in a
+        // barrier).  All waves thus execute the same number of barriers up to each helper's end, and nothing below
+        // waits for a helper.
         if (lane == 0) g_pm_ovl.flag[0] = 1;
         __syncthreads();                                                    // the stop barrier
 #ifdef DART_STAMPS
         t_acc_[13] = (unsigned)__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[3]);
+        t_acc_[17] = (unsigned)__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[6]);
 #endif
     }
 
@@ -1495,18 +1627,19 @@ __device__ __noinline__ void pmpc_resto_tail(const int b, const uint32_t seq, co
 // FUSE: resto mode 3, the handed-over instance continues in pmpc_resto_tail (no second launch)
 template <int NAX, bool QSCAN, bool ONEROW = false, bool SHORT2 = false, bool RED = false, bool OCC2 = false,
           bool FUSE = false, bool OVL = false>
-__global__ __launch_bounds__(kWave * kWaves * (OVL ? 2 : 1)) __attribute__((amdgpu_waves_per_eu(OCC2 ? 2 : ((QSCAN || NAX == 2) ? 1 : 2))))
+__global__ __launch_bounds__(kWave * kWaves * (OVL ? 3 : 1)) __attribute__((amdgpu_waves_per_eu(OCC2 ? 2 : ((QSCAN || NAX == 2) ? 1 : 2))))
 void pmpc_ipm_kernel(PmpcArgs a) {
     // small batches: the launcher deals 8 blocks per instance and only every 8th works, so all
     // instances land on one XCD (blocks go round-robin over the 8 XCDs) and share its L2 for the code
     if (blockIdx.x % a.pack) return;
     const int b = blockIdx.x / a.pack;
-    // OVL: launched with two waves; wave 0 solves, wave 1 factors for it and returns false when told to stop
+    // OVL: launched with three waves; wave 0 solves, wave 1 factors and wave 2 evaluates for it, and both return false
+    // when told to stop
     const bool handed = pmpc_solve<NAX, QSCAN, ONEROW, SHORT2, RED, OVL>(a, b);
     if constexpr (FUSE) {
         // OVL: pmpc_resto_tail and pmpc_resto_solve are written for one wave and cross __syncthreads(), real
-        // barriers in a two-wave launch.  The solver wave enters here only past the stop barrier of pmpc_solve's
-        // exit funnel, after which the factor wave runs nothing but its way out of the kernel; a barrier waits only
+        // barriers in a three-wave launch.  The solver wave enters here only past the stop barrier of pmpc_solve's
+        // exit funnel, after which the helper waves run nothing but their way out of the kernel; a barrier waits only
         // for the waves of the workgroup that have not terminated, so the tail's barriers concern this wave alone.
         if (PM_EXPECT(handed, 0)) pmpc_resto_tail(b, a.seq, 3u, kernarg_addr());
     }
@@ -1634,7 +1767,7 @@ extern "C" hipError_t dartmpc_launch_pmpc_serve_onerow(const dartmpc::PmpcArgs* 
 #ifdef DART_STAMPS
 // diagnostic build only: the stamps of the one-row (N <= 15) and sequential builds of this object
 extern "C" hipError_t dartmpc_read_stamps_seq(unsigned long long* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(dartmpc::g_stamp_seq), sizeof(unsigned long long) * 16, 0,
+    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(dartmpc::g_stamp_seq), sizeof(unsigned long long) * 32, 0,
                                hipMemcpyDeviceToHost);
 }
 #endif
@@ -1717,23 +1850,24 @@ extern "C" hipError_t dartmpc_launch_pmpc(const dartmpc::PmpcArgs* args, hipStre
         dartmpc::resto_fuse_enabled())
         a.resto = 3;
     const bool fuse = a.resto == 3;
-    // The overlapped builds (two waves per instance: the second factors the Riccati scan of the point while the
-    // first evaluates it and updates mu) where a CU has SIMDs to spare: batches of at most 32 (one instance per
+    // The overlapped builds (three waves per instance: the second factors the Riccati scan of the point and the third
+    // forms its error measures, tests convergence and updates mu while the first runs the line search's trial and
+    // the update) where a CU has SIMDs to spare: batches of at most 32 (one instance per
     // CU of one XCD) on IPOPT's path at N = 16..31.  Larger batches, the resident server and the rollout
     // kernels keep the one-wave builds.  DART_PMPC_OVERLAP=0: the one-wave builds here too (A/B).
     const bool ovl = a.pack == 8 && !a.reduced && !occ2 && a.N >= 16 && a.N <= 31 && a.B <= qscan_max_b &&
                      dartmpc::pmpc_overlap_enabled();
-    const dim3 block2(2 * dartmpc::kWave);
+    const dim3 block3(3 * dartmpc::kWave);
     if (ovl && a.N <= 23) {
         if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, true, true>), grid, block2, 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, true, true>), grid, block3, 0, stream, a);
         else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, false, true>), grid, block2, 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, false, true>), grid, block3, 0, stream, a);
     } else if (ovl) {
         if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, true, true>), grid, block2, 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, true, true>), grid, block3, 0, stream, a);
         else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, false, true>), grid, block2, 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, false, true>), grid, block3, 0, stream, a);
     } else if (a.N <= 23 && occ2) {        // (N <= 15 too: the short-scan build at two waves beats the one-row build at one)
         hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
     } else if (a.N <= 15 && a.B <= qscan_max_b) {
@@ -1775,7 +1909,7 @@ extern "C" hipError_t dartmpc_wave_selftest(double* d_out, hipStream_t stream) {
 #ifdef DART_STAMPS
 // diagnostic build only: per-phase s_memtime cycles of block 0 from the last launch
 extern "C" hipError_t dartmpc_read_stamps(unsigned long long* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(dartmpc::g_stamp), sizeof(unsigned long long) * 16, 0,
+    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(dartmpc::g_stamp), sizeof(unsigned long long) * 32, 0,
                                hipMemcpyDeviceToHost);
 }
 #endif

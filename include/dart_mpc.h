@@ -100,7 +100,7 @@ typedef struct dart_mpc_config {
     int32_t N;          /* horizon, 1 <= N <= 63 */
     double Ts;          /* sampling time [s] */
     double tol;         /* IPOPT-style scaled optimality tolerance */
-    int32_t max_iter;   /* interior-point iteration cap */
+    int32_t max_iter;   /* interior-point iteration cap (>= 1; PMPC also 0: the start point at status -1) */
     int32_t B_max;      /* largest batch the handle's device workspace serves */
     double gravity;     /* model.opt.gravity[2] (mpc_3d.py:23), default -9.81 */
     double acceptable_tol;   /* IPOPT acceptable_tol; used by LMPC (rlmpc2.py:487: 1e-3) */

@@ -23,20 +23,22 @@ B = int(os.environ.get("DART_STAMPS_B", "18"))
 # PMPC_SEQ object, which has its own stamp array
 read = L.dartmpc_read_stamps_seq if (N <= 15 or N > 31 or B > 1664) else L.dartmpc_read_stamps
 read.argtypes = [ctypes.c_void_p]
-PHASES = ["setup", "eval+errors", "mu update", "riccati", "direction", "ls prep", "ls trials", "update", "outputs"]
+# (phase, slot): the evaluation is split where the per-lane values the Newton step needs end and the error terms begin
+PHASES = [("setup", 0), ("eval lanes", 16), ("eval errors", 1), ("mu update", 2), ("riccati", 3), ("direction", 4),
+          ("ls prep", 5), ("ls trials", 6), ("update", 7), ("outputs", 8)]
 S, T, P = pmpc_batch(-(-B // 18))
 S, T, P = S[:B], T[:B], P[:B]
 s = _lib.Solver(N=N, B_max=B, path=os.environ.get("DART_PMPC_PATH", "ipopt"))
 for rep in range(3):
     out = s.solve_batch(S, T, P)
-st = np.zeros(16, dtype=np.uint64)
+st = np.zeros(32, dtype=np.uint64)
 read(ctypes.c_void_p(st.ctypes.data))
-tot = float(st[:9].sum())
+tot = float(sum(st[i] for _, i in PHASES))
 print(f"block0 iters={out['iters'][0]} total cycles={tot:.0f}")
-for i, n in enumerate(PHASES):
+for n, i in PHASES:
     print(f"  {n:12s} {int(st[i]):10d}  {100 * st[i] / tot:5.1f}%  per-iter {st[i] / max(1, out['iters'][0]):9.0f}")
 print(f"  scan-path Riccati passes {int(st[11])}")
-it0 = int(st[0:9].sum() - st[0] - st[8])
+it0 = int(tot - st[0] - st[8])
 print(f"  first iteration {int(st[12])} cycles, mean iteration {it0 / max(1, out['iters'][0]):.0f} cycles")
 print(f"  riccati passes {int(st[9])}, line-search trials {int(st[10])}, iterations with a correction {int(st[15]) & 0xffff}")
 if st[13]:
@@ -48,4 +50,7 @@ if st[13]:
     # wave plus its LDS read; this is the factor wave's own time from barrier A to its arrival at barrier B
     print(f"  factor wave: {int(st[13])} cycles between its barriers, per-iter {st[13] / max(1, out['iters'][0]):.0f}")
     print(f"  solving wave: {int(st[14])} cycles waiting at barrier B, per-iter {st[14] / max(1, out['iters'][0]):.0f}")
+if st[17]:
+    # the evaluation wave of the overlapped build: its own time from barrier A to its arrival at barrier B
+    print(f"  evaluation wave: {int(st[17])} cycles between its barriers, per-iter {st[17] / max(1, out['iters'][0]):.0f}")
 print("batch iters:", out["iters"].tolist())
