@@ -407,25 +407,38 @@ __device__ __forceinline__ bool pmpc_riccati(const int lane, const int N, const 
 // The overlapped build (OVL; NAX == 1, QSCAN, one wave per instance, launched with three waves): LDS hand-over
 // between the solver wave (wave 0) and its two helper waves, the factor wave (wave 1) and the evaluation wave
 // (wave 2).  [field][lane]: every access is one conflict-free 8-byte access per lane.
-// pt: th, snc, lp, lv, zl, zu of the current point, then p, v, z and mu (the same value in every lane: one unmasked
-// write); wave 0 writes before barrier A, the helper waves read after it (the factor wave rows 0-5 only); wave 0
-// reads its own zl, zu back when the speculated point is taken.
-// fc: P11, P12, P22, W1, W2, iQs (wave 1 writes before barrier B, wave 0 reads after it).
-// mu_new and flag[4], flag[5]: the evaluation wave's results for the point (the updated mu, converged, mu
-// decreased), written before barrier B and read by wave 0 after it with the factors.
-// flag: [0] stop, [1] use_scan, [2] ok, [4] converged, [5] mu decreased ([3], [6]: the stamps build's helper-wave
-// timers).  Each buffer has one writer, and its next write comes after a barrier that the readers cross only with
-// their reads complete, so single buffers are enough.
+// Ownership: wave 0 writes pt (the point; mu is the same value in every lane, one unmasked write) before barrier A,
+// the helper waves read it after it (the factor wave the rows up to kPtZu only), and wave 0 reads its own zl, zu
+// back when the speculated point is taken.  Wave 1 writes fc, kFlUseScan and kFlOk, wave 2 mu_new, kFlConverged and
+// kFlMuDec, all before barrier B; wave 0 reads them after it.  Wave 0 alone writes kFlStop.  Each buffer has one
+// writer, and its next write comes after a barrier that the readers cross only with their reads complete, so single
+// buffers are enough.
+enum PmPt { kPtTh, kPtSn, kPtLp, kPtLv, kPtZl, kPtZu, kPtP, kPtV, kPtZ, kPtMu, kPtRows };      // the point and mu
+enum PmFc { kFcP11, kFcP12, kFcP22, kFcW1, kFcW2, kFcIQs, kFcRows };                            // its factors
+// stop; the factor wave's use_scan and ok; the evaluation wave's converged and mu decreased (kFl*Time: the stamps
+// build's helper-wave timers)
+enum PmFlag { kFlStop, kFlUseScan, kFlOk, kFlFactorTime, kFlConverged, kFlMuDec, kFlEvalTime, kFlWords = 8 };
 struct PmOvlShared {
-    double pt[10][kWave];
-    double fc[6][kWave];
+    double pt[kPtRows][kWave];
+    double fc[kFcRows][kWave];
     double mu_new;
-    int flag[8];
+    int flag[kFlWords];
 };
 __shared__ PmOvlShared g_pm_ovl;       // only the overlapped instantiations name it (8 KB beside PrShared when fused)
 
-template <int NAX, bool QSCAN, bool ONEROW, bool SHORT2, bool RED, bool OVL = false>
+// IPOPT's kappa_sigma safeguard of a bound multiplier after its step: z within [1e-10, 1e10] mu / slack
+__device__ __forceinline__ double pm_clamp_mult(const double z, const double mu, const double islack) {
+    return fmax(fmin(z, 1e10 * mu * islack), 1e-10 * mu * islack);
+}
+
+// The build of the kernel as one mask (the template argument of pmpc_ipm_kernel, pmpc_serve_kernel and pmpc_solve);
+// the comment above PM_EXPECT says what each selects.  kOcc2 and kFuse concern the kernels only.
+enum : unsigned { kScan = 1u, kOneRow = 2u, kShort2 = 4u, kRed = 8u, kOcc2 = 16u, kFuse = 32u, kOvl = 64u };
+
+template <int NAX, unsigned F>
 __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
+    constexpr bool QSCAN = (F & kScan) != 0, ONEROW = (F & kOneRow) != 0, SHORT2 = (F & kShort2) != 0;
+    constexpr bool RED = (F & kRed) != 0, OVL = (F & kOvl) != 0;
     static_assert(!OVL || (NAX == 1 && QSCAN && !ONEROW && !RED && kWaves == 1), "the overlapped build: scan builds of N = 16..31");
     STAMP_DECL
     const int lane = (kWaves == 1 && !OVL) ? (int)threadIdx.x : lane_id();
@@ -610,10 +623,10 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             const long long max_rounds = 2ll * a.max_iter + 8;
             for (long long round = 0; round < max_rounds; ++round) {
                 __syncthreads();                                            // barrier A, or the stop barrier
-                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return;
+                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[kFlStop])) return;
                 body();
                 __syncthreads();                                            // barrier B, or the stop barrier
-                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[0])) return;
+                if (__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[kFlStop])) return;
             }
         };
         const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -623,9 +636,9 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
 #ifdef DART_STAMPS
                 const unsigned long long tf0 = __builtin_amdgcn_s_memtime();
 #endif
-                const double th1 = g_pm_ovl.pt[0][lane], sn1 = g_pm_ovl.pt[1][lane];
-                const double lp1 = g_pm_ovl.pt[2][lane], lv1 = g_pm_ovl.pt[3][lane];
-                const double zl1 = g_pm_ovl.pt[4][lane], zu1 = g_pm_ovl.pt[5][lane];
+                const double th1 = g_pm_ovl.pt[kPtTh][lane], sn1 = g_pm_ovl.pt[kPtSn][lane];
+                const double lp1 = g_pm_ovl.pt[kPtLp][lane], lv1 = g_pm_ovl.pt[kPtLv][lane];
+                const double zl1 = g_pm_ovl.pt[kPtZl][lane], zu1 = g_pm_ovl.pt[kPtZu][lane];
                 const double c_ = tilt_cos_econ(poly, th1);
                 const double cs1 = uon ? c_ : 0.0;
                 const double ln = from_next(lp1), vn = from_next(lv1);
@@ -639,13 +652,13 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 const bool okf = pmpc_riccati<NAX, QSCAN, ONEROW, SHORT2>(lane, N, uon, false, 0.0, qp2, qv2, stg, be1,
                                                                          be2, E11, E12, E22, Rt0, P11, P12, P22, W1,
                                                                          W2, iQs, us);
-                g_pm_ovl.fc[0][lane] = P11[0]; g_pm_ovl.fc[1][lane] = P12[0]; g_pm_ovl.fc[2][lane] = P22[0];
-                g_pm_ovl.fc[3][lane] = W1[0]; g_pm_ovl.fc[4][lane] = W2[0]; g_pm_ovl.fc[5][lane] = iQs[0];
-                if (lane == 0) { g_pm_ovl.flag[1] = us ? 1 : 0; g_pm_ovl.flag[2] = okf ? 1 : 0; }
+                g_pm_ovl.fc[kFcP11][lane] = P11[0]; g_pm_ovl.fc[kFcP12][lane] = P12[0]; g_pm_ovl.fc[kFcP22][lane] = P22[0];
+                g_pm_ovl.fc[kFcW1][lane] = W1[0]; g_pm_ovl.fc[kFcW2][lane] = W2[0]; g_pm_ovl.fc[kFcIQs][lane] = iQs[0];
+                if (lane == 0) { g_pm_ovl.flag[kFlUseScan] = us ? 1 : 0; g_pm_ovl.flag[kFlOk] = okf ? 1 : 0; }
 #ifdef DART_STAMPS
                 // the factor wave's own time from barrier A to its arrival at barrier B, summed (slot 13 of wave 0)
                 t_acc_[13] += __builtin_amdgcn_s_memtime() - tf0;
-                if (lane == 0) g_pm_ovl.flag[3] = (int)t_acc_[13];
+                if (lane == 0) g_pm_ovl.flag[kFlFactorTime] = (int)t_acc_[13];
 #endif
             });
             return false;
@@ -658,28 +671,28 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
 #ifdef DART_STAMPS
                 const unsigned long long te0 = __builtin_amdgcn_s_memtime();
 #endif
-                const double th1[NAX] = {g_pm_ovl.pt[0][lane]}, sn1 = g_pm_ovl.pt[1][lane];
-                const double lp1[NAX] = {g_pm_ovl.pt[2][lane]}, lv1[NAX] = {g_pm_ovl.pt[3][lane]};
-                const double zl1[NAX] = {g_pm_ovl.pt[4][lane]}, zu1[NAX] = {g_pm_ovl.pt[5][lane]};
-                const double p1[NAX] = {g_pm_ovl.pt[6][lane]}, v1[NAX] = {g_pm_ovl.pt[7][lane]};
-                const double zz1 = g_pm_ovl.pt[8][lane];
-                double mu1 = wave_uniform(g_pm_ovl.pt[9][lane]);
+                const double th1[NAX] = {g_pm_ovl.pt[kPtTh][lane]}, sn1 = g_pm_ovl.pt[kPtSn][lane];
+                const double lp1[NAX] = {g_pm_ovl.pt[kPtLp][lane]}, lv1[NAX] = {g_pm_ovl.pt[kPtLv][lane]};
+                const double zl1[NAX] = {g_pm_ovl.pt[kPtZl][lane]}, zu1[NAX] = {g_pm_ovl.pt[kPtZu][lane]};
+                const double p1[NAX] = {g_pm_ovl.pt[kPtP][lane]}, v1[NAX] = {g_pm_ovl.pt[kPtV][lane]};
+                const double zz1 = g_pm_ovl.pt[kPtZ][lane];
+                double mu1 = wave_uniform(g_pm_ovl.pt[kPtMu][lane]);
                 double g1e[NAX], g2e[NAX], gze[NAX];
                 const double w1 = vz_new(th1);
                 defects(p1[0], v1[0], sn1, sp[0], sv[0], g1e[0], g2e[0]);
                 gze[0] = zdefect(zz1, w1, 0);
                 bool dec = false;
                 const bool conv = point_verdict(p1, v1, th1, lp1, lv1, zl1, zu1, g1e, g2e, gze, mu1, dec);
-                if (lane == 0) { g_pm_ovl.mu_new = mu1; g_pm_ovl.flag[4] = conv ? 1 : 0; g_pm_ovl.flag[5] = dec ? 1 : 0; }
+                if (lane == 0) { g_pm_ovl.mu_new = mu1; g_pm_ovl.flag[kFlConverged] = conv ? 1 : 0; g_pm_ovl.flag[kFlMuDec] = dec ? 1 : 0; }
 #ifdef DART_STAMPS
                 // the evaluation wave's own time from barrier A to its arrival at barrier B, summed (slot 17 of wave 0)
                 t_acc_[17] += __builtin_amdgcn_s_memtime() - te0;
-                if (lane == 0) g_pm_ovl.flag[6] = (int)t_acc_[17];
+                if (lane == 0) g_pm_ovl.flag[kFlEvalTime] = (int)t_acc_[17];
 #endif
             });
             return false;
         }
-        if (lane == 0) g_pm_ovl.flag[0] = 0;      // the solver wave, before its first barrier
+        if (lane == 0) g_pm_ovl.flag[kFlStop] = 0;      // the solver wave, before its first barrier
     }
 
     // sines and defects of the current point: computed here once, then carried over from the
@@ -734,11 +747,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
     bool published = false;
     auto publish = [&]() {
         __builtin_amdgcn_sched_barrier(0);
-        g_pm_ovl.pt[0][lane] = th[0]; g_pm_ovl.pt[1][lane] = snc[0];
-        g_pm_ovl.pt[2][lane] = lp[0]; g_pm_ovl.pt[3][lane] = lv[0];
-        g_pm_ovl.pt[4][lane] = zl[0]; g_pm_ovl.pt[5][lane] = zu[0];
-        g_pm_ovl.pt[6][lane] = p[0]; g_pm_ovl.pt[7][lane] = v[0];
-        g_pm_ovl.pt[8][lane] = zz[0]; g_pm_ovl.pt[9][lane] = mu;
+        g_pm_ovl.pt[kPtTh][lane] = th[0]; g_pm_ovl.pt[kPtSn][lane] = snc[0];
+        g_pm_ovl.pt[kPtLp][lane] = lp[0]; g_pm_ovl.pt[kPtLv][lane] = lv[0];
+        g_pm_ovl.pt[kPtZl][lane] = zl[0]; g_pm_ovl.pt[kPtZu][lane] = zu[0];
+        g_pm_ovl.pt[kPtP][lane] = p[0]; g_pm_ovl.pt[kPtV][lane] = v[0];
+        g_pm_ovl.pt[kPtZ][lane] = zz[0]; g_pm_ovl.pt[kPtMu][lane] = mu;
         __syncthreads();                                                    // barrier A
         __builtin_amdgcn_sched_barrier(0);
         published = true;
@@ -855,11 +868,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 __syncthreads();                                            // barrier B
                 SPAN_END(14, t_b);                      // (stamps build, slot 14: the wait alone)
                 // (the six values are read with the flags, not after the branch on them: one LDS round trip)
-                const int usf = g_pm_ovl.flag[1], okff = g_pm_ovl.flag[2];
-                const int cvf = g_pm_ovl.flag[4], mdf = g_pm_ovl.flag[5];
+                const int usf = g_pm_ovl.flag[kFlUseScan], okff = g_pm_ovl.flag[kFlOk];
+                const int cvf = g_pm_ovl.flag[kFlConverged], mdf = g_pm_ovl.flag[kFlMuDec];
                 const double mun = g_pm_ovl.mu_new;
-                P11[0] = g_pm_ovl.fc[0][lane]; P12[0] = g_pm_ovl.fc[1][lane]; P22[0] = g_pm_ovl.fc[2][lane];
-                W1[0] = g_pm_ovl.fc[3][lane]; W2[0] = g_pm_ovl.fc[4][lane]; iQs[0] = g_pm_ovl.fc[5][lane];
+                P11[0] = g_pm_ovl.fc[kFcP11][lane]; P12[0] = g_pm_ovl.fc[kFcP12][lane]; P22[0] = g_pm_ovl.fc[kFcP22][lane];
+                W1[0] = g_pm_ovl.fc[kFcW1][lane]; W2[0] = g_pm_ovl.fc[kFcW2][lane]; iQs[0] = g_pm_ovl.fc[kFcIQs][lane];
                 const bool us = __builtin_amdgcn_readfirstlane(usf) != 0;
                 const bool okf = __builtin_amdgcn_readfirstlane(okff) != 0;
                 if (__builtin_amdgcn_readfirstlane(cvf)) { status = 0; break; }
@@ -1299,14 +1312,14 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                     tilt_sincos(poly, thc, s_, c_);
                     sn_pre = uon ? s_ : 0.0; sn_pre_on = true;
                     const double il = frcp(thc - lo), iu = frcp(hi - thc);
-                    const double zln = fmax(fmin(fma(az, dzl[0], zl[0]), 1e10 * mu * il), 1e-10 * mu * il);   // kappa_sigma
-                    const double zun = fmax(fmin(fma(az, dzu[0], zu[0]), 1e10 * mu * iu), 1e-10 * mu * iu);
+                    const double zln = pm_clamp_mult(fma(az, dzl[0], zl[0]), mu, il);
+                    const double zun = pm_clamp_mult(fma(az, dzu[0], zu[0]), mu, iu);
                     __builtin_amdgcn_sched_barrier(0);
-                    g_pm_ovl.pt[0][lane] = thc; g_pm_ovl.pt[1][lane] = sn_pre;
-                    g_pm_ovl.pt[2][lane] = fma(alpha, dlp[0], lp[0]); g_pm_ovl.pt[3][lane] = fma(alpha, dlv[0], lv[0]);
-                    g_pm_ovl.pt[4][lane] = uon ? zln : 0.0; g_pm_ovl.pt[5][lane] = uon ? zun : 0.0;
-                    g_pm_ovl.pt[6][lane] = fma(alpha, dp[0], p[0]); g_pm_ovl.pt[7][lane] = fma(alpha, dv[0], v[0]);
-                    g_pm_ovl.pt[8][lane] = fma(alpha, dz[0], zz[0]); g_pm_ovl.pt[9][lane] = mu;
+                    g_pm_ovl.pt[kPtTh][lane] = thc; g_pm_ovl.pt[kPtSn][lane] = sn_pre;
+                    g_pm_ovl.pt[kPtLp][lane] = fma(alpha, dlp[0], lp[0]); g_pm_ovl.pt[kPtLv][lane] = fma(alpha, dlv[0], lv[0]);
+                    g_pm_ovl.pt[kPtZl][lane] = uon ? zln : 0.0; g_pm_ovl.pt[kPtZu][lane] = uon ? zun : 0.0;
+                    g_pm_ovl.pt[kPtP][lane] = fma(alpha, dp[0], p[0]); g_pm_ovl.pt[kPtV][lane] = fma(alpha, dv[0], v[0]);
+                    g_pm_ovl.pt[kPtZ][lane] = fma(alpha, dz[0], zz[0]); g_pm_ovl.pt[kPtMu][lane] = mu;
                     __syncthreads();                                        // barrier A
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1476,11 +1489,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             lp[j] = fma(alpha, dlp[j], lp[j]); lv[j] = fma(alpha, dlv[j], lv[j]);
             th[j] = fma(alpha, dth[j], th[j]);
             if (OVL && PM_EXPECT(hit, 1)) {
-                zl[j] = g_pm_ovl.pt[4][lane]; zu[j] = g_pm_ovl.pt[5][lane];
+                zl[j] = g_pm_ovl.pt[kPtZl][lane]; zu[j] = g_pm_ovl.pt[kPtZu][lane];
             } else {
                 const double il = frcp(th[j] - lo), iu = frcp(hi - th[j]);
-                const double zln = fmax(fmin(fma(az, dzl[j], zl[j]), 1e10 * mu * il), 1e-10 * mu * il);   // kappa_sigma
-                const double zun = fmax(fmin(fma(az, dzu[j], zu[j]), 1e10 * mu * iu), 1e-10 * mu * iu);
+                const double zln = pm_clamp_mult(fma(az, dzl[j], zl[j]), mu, il);
+                const double zun = pm_clamp_mult(fma(az, dzu[j], zu[j]), mu, iu);
                 zl[j] = uon ? zln : 0.0; zu[j] = uon ? zun : 0.0;
             }
         }
@@ -1518,11 +1531,11 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         // the latest (or earlier, having seen the word before this wave arrived; a terminated wave takes no part in a
         // barrier).  All waves thus execute the same number of barriers up to each helper's end, and nothing below
         // waits for a helper.
-        if (lane == 0) g_pm_ovl.flag[0] = 1;
+        if (lane == 0) g_pm_ovl.flag[kFlStop] = 1;
         __syncthreads();                                                    // the stop barrier
 #ifdef DART_STAMPS
-        t_acc_[13] = (unsigned)__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[3]);
-        t_acc_[17] = (unsigned)__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[6]);
+        t_acc_[13] = (unsigned)__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[kFlFactorTime]);
+        t_acc_[17] = (unsigned)__builtin_amdgcn_readfirstlane(g_pm_ovl.flag[kFlEvalTime]);
 #endif
     }
 
@@ -1624,19 +1637,24 @@ __device__ __noinline__ void pmpc_resto_tail(const int b, const uint32_t seq, co
     pmpc_resto_solve(a, b);
 }
 
-// FUSE: resto mode 3, the handed-over instance continues in pmpc_resto_tail (no second launch)
-template <int NAX, bool QSCAN, bool ONEROW = false, bool SHORT2 = false, bool RED = false, bool OCC2 = false,
-          bool FUSE = false, bool OVL = false>
-__global__ __launch_bounds__(kWave * kWaves * (OVL ? 3 : 1)) __attribute__((amdgpu_waves_per_eu(OCC2 ? 2 : ((QSCAN || NAX == 2) ? 1 : 2))))
+// F: the build (kScan | kShort2 | ...).  kFuse: resto mode 3, the handed-over instance continues in pmpc_resto_tail
+// (no second launch); kOcc2: compiled for two waves per SIMD
+template <int NAX, unsigned F>
+__global__ __launch_bounds__(kWave * kWaves * ((F & kOvl) ? 3 : 1))
+__attribute__((amdgpu_waves_per_eu((F & kOcc2) ? 2 : (((F & kScan) || NAX == 2) ? 1 : 2))))
 void pmpc_ipm_kernel(PmpcArgs a) {
+    static_assert(F < 2 * kOvl && (!(F & (kOneRow | kShort2 | kOcc2 | kOvl)) || (F & kScan)),
+                  "one-row, short-scan, two-waves-per-SIMD and overlapped builds are scan builds");
+    static_assert(!(F & kFuse) || !(F & (kRed | kOcc2)), "the fused tail: IPOPT's path at one wave per SIMD");
+    constexpr bool ONEROW = (F & kOneRow) != 0;      // (PM_EXPECT)
     // small batches: the launcher deals 8 blocks per instance and only every 8th works, so all
     // instances land on one XCD (blocks go round-robin over the 8 XCDs) and share its L2 for the code
     if (blockIdx.x % a.pack) return;
     const int b = blockIdx.x / a.pack;
     // OVL: launched with three waves; wave 0 solves, wave 1 factors and wave 2 evaluates for it, and both return false
     // when told to stop
-    const bool handed = pmpc_solve<NAX, QSCAN, ONEROW, SHORT2, RED, OVL>(a, b);
-    if constexpr (FUSE) {
+    const bool handed = pmpc_solve<NAX, F & ~(kOcc2 | kFuse)>(a, b);
+    if constexpr ((F & kFuse) != 0) {
         // OVL: pmpc_resto_tail and pmpc_resto_solve are written for one wave and cross __syncthreads(), real
         // barriers in a three-wave launch.  The solver wave enters here only past the stop barrier of pmpc_solve's
         // exit funnel, after which the helper waves run nothing but their way out of the kernel; a barrier waits only
@@ -1654,9 +1672,11 @@ void pmpc_ipm_kernel(PmpcArgs a) {
 // so the grid always drains.
 // FUSE (B_serve <= 32, resto mode 3): a handed-over instance continues in pmpc_resto_tail, so the grid stays
 // resident through a restoration
-template <int NAX, bool ONEROW, bool SHORT2, bool FUSE = false>
+template <int NAX, unsigned F>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1)))
 void pmpc_serve_kernel(PmpcArgs a, PmpcServe sv) {
+    static_assert((F & kScan) && !(F & (kRed | kOcc2 | kOvl)), "the server: one-wave scan builds on IPOPT's path");
+    constexpr bool ONEROW = (F & kOneRow) != 0;      // (PM_EXPECT)
     if (blockIdx.x % a.pack) return;
     const int b = blockIdx.x / a.pack;
     uint32_t seen = a.seq;
@@ -1682,8 +1702,8 @@ void pmpc_serve_kernel(PmpcArgs a, PmpcServe sv) {
             r.B = (int)B; r.seq = sq;
             r.w_warm = (fl & 1u) ? a.w_warm : nullptr;
             r.w_out = (fl & 2u) ? a.w_out : nullptr;
-            const bool handed = pmpc_solve<NAX, true, ONEROW, SHORT2, false>(r, b);
-            if constexpr (FUSE) {
+            const bool handed = pmpc_solve<NAX, F & ~kFuse>(r, b);
+            if constexpr ((F & kFuse) != 0) {
                 if (PM_EXPECT(handed, 0)) pmpc_resto_tail(b, sq, fl, kernarg_addr());
             }
         }
@@ -1720,13 +1740,17 @@ __global__ __launch_bounds__(kWave) void wave_selftest_kernel(double* out) {
 
 }  // namespace dartmpc
 
+// the launchers name the builds by their flags
+using dartmpc::kScan; using dartmpc::kOneRow; using dartmpc::kShort2; using dartmpc::kRed; using dartmpc::kOcc2;
+using dartmpc::kFuse; using dartmpc::kOvl;
+
 #if DART_WG == 2
 // N = 32..63 on IPOPT's path (dartmpc_launch_pmpc forwards here): the scan build, one instance per two-wave
 // workgroup; grid = B x pack blocks as for the one-wave builds
 extern "C" hipError_t dartmpc_launch_pmpc_wg2(const void* args, unsigned grid, hipStream_t stream) {
     const dartmpc::PmpcArgs& a = *static_cast<const dartmpc::PmpcArgs*>(args);
     if (a.N < 32 || a.N > 63 || a.reduced || a.resto) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true>), dim3(grid), dim3(dartmpc::kWave * dartmpc::kWaves), 0,
+    hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan>), dim3(grid), dim3(dartmpc::kWave * dartmpc::kWaves), 0,
                        stream, a);
     return hipGetLastError();
 }
@@ -1735,17 +1759,18 @@ extern "C" hipError_t dartmpc_launch_pmpc_wg2(const void* args, unsigned grid, h
 // SIMD, used once B exceeds the scan limit or N > 31
 template <bool RED>
 static void launch_seq(const dartmpc::PmpcArgs* a, unsigned grid, hipStream_t stream, int onerow) {
+    constexpr unsigned red = RED ? kRed : 0u;
     if (onerow && !RED && a->resto == 3)
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, true, false, false, false, true>), dim3(grid),
+        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kOneRow | kFuse>), dim3(grid),
                            dim3(dartmpc::kWave), 0, stream, *a);
     else if (onerow)
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, true, false, RED>), dim3(grid), dim3(dartmpc::kWave), 0,
+        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kOneRow | red>), dim3(grid), dim3(dartmpc::kWave), 0,
                            stream, *a);
     else if (a->N <= 31)
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, false, false, false, RED>), dim3(grid), dim3(dartmpc::kWave), 0,
+        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, red>), dim3(grid), dim3(dartmpc::kWave), 0,
                            stream, *a);
     else
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<2, false, false, false, RED>), dim3(grid), dim3(dartmpc::kWave), 0,
+        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<2, red>), dim3(grid), dim3(dartmpc::kWave), 0,
                            stream, *a);
 }
 extern "C" hipError_t dartmpc_launch_pmpc_seq(const dartmpc::PmpcArgs* a, unsigned grid, hipStream_t stream,
@@ -1757,10 +1782,10 @@ extern "C" hipError_t dartmpc_launch_pmpc_seq(const dartmpc::PmpcArgs* a, unsign
 extern "C" hipError_t dartmpc_launch_pmpc_serve_onerow(const dartmpc::PmpcArgs* a, const dartmpc::PmpcServe* sv,
                                                       unsigned grid, hipStream_t stream) {
     if (a->resto == 3)
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, true, false, true>), dim3(grid), dim3(dartmpc::kWave), 0,
+        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kOneRow | kFuse>), dim3(grid), dim3(dartmpc::kWave), 0,
                            stream, *a, *sv);
     else
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, true, false>), dim3(grid), dim3(dartmpc::kWave), 0, stream,
+        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kOneRow>), dim3(grid), dim3(dartmpc::kWave), 0, stream,
                            *a, *sv);
     return hipGetLastError();
 }
@@ -1791,16 +1816,16 @@ extern "C" hipError_t dartmpc_launch_pmpc_serve(const dartmpc::PmpcArgs* args, c
     const unsigned grid = (unsigned)(a.B * a.pack);
     if (a.N <= 15) return dartmpc_launch_pmpc_serve_onerow(&a, sv, grid, stream);
     if (a.N <= 23 && a.resto == 3)
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, false, true, true>), dim3(grid), dim3(dartmpc::kWave), 0,
+        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kShort2 | kFuse>), dim3(grid), dim3(dartmpc::kWave), 0,
                            stream, a, *sv);
     else if (a.N <= 23)
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, false, true>), dim3(grid), dim3(dartmpc::kWave), 0, stream, a,
+        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kShort2>), dim3(grid), dim3(dartmpc::kWave), 0, stream, a,
                            *sv);
     else if (a.resto == 3)
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, false, false, true>), dim3(grid), dim3(dartmpc::kWave), 0,
+        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kFuse>), dim3(grid), dim3(dartmpc::kWave), 0,
                            stream, a, *sv);
     else
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, false, false>), dim3(grid), dim3(dartmpc::kWave), 0, stream, a,
+        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan>), dim3(grid), dim3(dartmpc::kWave), 0, stream, a,
                            *sv);
     return hipGetLastError();
 }
@@ -1860,34 +1885,34 @@ extern "C" hipError_t dartmpc_launch_pmpc(const dartmpc::PmpcArgs* args, hipStre
     const dim3 block3(3 * dartmpc::kWave);
     if (ovl && a.N <= 23) {
         if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, true, true>), grid, block3, 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kFuse | kOvl>), grid, block3, 0, stream, a);
         else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, false, true>), grid, block3, 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kOvl>), grid, block3, 0, stream, a);
     } else if (ovl) {
         if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, true, true>), grid, block3, 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kFuse | kOvl>), grid, block3, 0, stream, a);
         else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, false, true>), grid, block3, 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kOvl>), grid, block3, 0, stream, a);
     } else if (a.N <= 23 && occ2) {        // (N <= 15 too: the short-scan build at two waves beats the one-row build at one)
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
+        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kOcc2>), grid, dim3(dartmpc::kWave), 0, stream, a);
     } else if (a.N <= 15 && a.B <= qscan_max_b) {
         if (hipError_t e = dartmpc_launch_pmpc_seq(&a, grid.x, stream, 1)) return e;
     } else if (a.N <= 23 && a.B <= qscan_max_b) {
         if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, false, false, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kFuse>), grid, dim3(dartmpc::kWave), 0, stream, a);
         else if (a.reduced)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kRed>), grid, dim3(dartmpc::kWave), 0, stream, a);
         else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2>), grid, dim3(dartmpc::kWave), 0, stream, a);
     } else if (a.N <= 31 && a.B <= qscan_max_b) {
         if (occ2)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kOcc2>), grid, dim3(dartmpc::kWave), 0, stream, a);
         else if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, false, false, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kFuse>), grid, dim3(dartmpc::kWave), 0, stream, a);
         else if (a.reduced)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true, false, false, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kRed>), grid, dim3(dartmpc::kWave), 0, stream, a);
         else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, true>), grid, dim3(dartmpc::kWave), 0, stream, a);
+            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan>), grid, dim3(dartmpc::kWave), 0, stream, a);
     } else if (a.N > 31 && !a.reduced && !a.resto && long_wg2) {
         if (hipError_t e = dartmpc_launch_pmpc_wg2(&a, grid.x, stream)) return e;
     } else {

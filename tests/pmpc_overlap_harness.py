@@ -1,0 +1,80 @@
+"""What the four test files of the overlapped PMPC builds share (test_gpu_pmpc_overlap.py, _speculative.py,
+_scan_handover.py, _eval_wave.py): the inputs, the .npy convention of their child processes, the back-to-back
+launch loop and the body of their `runs` fixtures.
+
+DART_PMPC_OVERLAP is read once per process, so each of those files runs itself as a script in a fresh child process
+per setting, one after the other; the child writes <case>__<key>.npy files and the parent loads them.  Each file keeps
+its own cases, oracle preconditions and tests.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(ROOT, "dart-dual-arm-non-prehensile-manipulation_amd"), os.path.join(ROOT, "oracle")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+KEYS = ("u0", "f", "status", "iters", "w")
+
+
+def inputs():
+    """The first 32 instances of pmpc_batch(2)."""
+    from dart_mpc.workload import pmpc_batch
+    S, T, P = pmpc_batch(2)
+    return S[:32], T[:32], P[:32]
+
+
+def wide_inputs():
+    """The inputs of test_gpu_pmpc.py::test_wide_tilt_box_library_trig_path (tilt box [-1.2, 1.2], far targets)."""
+    from dart_mpc.workload import pmpc_batch
+    S, T, P = pmpc_batch(1)
+    P = P.copy(); P[:, 4] = -1.2; P[:, 5] = 1.2
+    T = T.copy(); T[:, 0] = np.where(S[:, 0] > 0, -0.6, 0.6); T[:, 2] = np.where(S[:, 2] > 0, -0.5, 0.5)
+    return S, T, P
+
+
+def save(outdir, case, out):
+    for k in KEYS:
+        np.save(os.path.join(outdir, f"{case}__{k}.npy"), out[k])
+
+
+def back_to_back(s, S, T, P, nw, launches):
+    """`launches` launches of solver s on one stream with no synchronisation between them, each into its own output
+    rows; the outputs as a dict of KEYS."""
+    import torch
+    dev = torch.device("cuda:0")
+    B = S.shape[0]
+    d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (S, T, P)]
+    U0 = torch.zeros((launches, B, 2), dtype=torch.float64, device=dev)
+    FV = torch.zeros((launches, B), dtype=torch.float64, device=dev)
+    WO = torch.zeros((launches, B, nw), dtype=torch.float64, device=dev)
+    ST = torch.full((launches, B), -99, dtype=torch.int32, device=dev)
+    IT = torch.zeros((launches, B), dtype=torch.int32, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    for i in range(launches):
+        s.solve_batch_dev(B, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), U0[i].data_ptr(), FV[i].data_ptr(),
+                          ST[i].data_ptr(), IT[i].data_ptr(), w_out=WO[i].data_ptr(), stream=stream.cuda_stream)
+    torch.cuda.synchronize()
+    return dict(u0=U0.cpu().numpy(), f=FV.cpu().numpy(), status=ST.cpu().numpy(), iters=IT.cpu().numpy(),
+                w=WO.cpu().numpy())
+
+
+def run_settings(tmp_path_factory, script, tag, args=()):
+    """{setting: {name: array}} of a fresh child per setting: "0" (one-wave builds) and "default" (overlap on).  The
+    child is `script` run with an output directory and `args`."""
+    res = {}
+    for setting in ("0", "default"):
+        outdir = str(tmp_path_factory.mktemp(f"{tag}_{setting}"))
+        env = dict(os.environ)
+        env.pop("DART_PMPC_OVERLAP", None)
+        if setting == "0":
+            env["DART_PMPC_OVERLAP"] = "0"
+        r = subprocess.run([sys.executable, os.path.abspath(script), outdir] + list(args), env=env,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (setting, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+        res[setting] = {f[:-4]: np.load(os.path.join(outdir, f)) for f in os.listdir(outdir) if f.endswith(".npy")}
+    return res

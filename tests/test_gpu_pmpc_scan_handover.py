@@ -16,19 +16,14 @@ after the other, and hands its arrays back as .npy files.  The preconditions are
 on the CPU.  What the oracle cannot show is whether the warm-started wide-box case really leaves the scan path in
 the factor wave (the oracle has no warm start); that case is compared all the same.
 """
-import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (os.path.join(ROOT, "dart-dual-arm-non-prehensile-manipulation_amd"), os.path.join(ROOT, "oracle")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import pmpc_overlap_harness as H
+from pmpc_overlap_harness import KEYS, inputs as _inputs, wide_inputs as _wide_inputs
 
-KEYS = ("u0", "f", "status", "iters", "w")
 # every N of the overlapped builds: which lanes are final after which level changes with N, and 23 / 24 is the
 # boundary between the SHORT2 and the full-scan instantiations
 NS = tuple(range(16, 32))
@@ -38,31 +33,13 @@ B2B = 5
 CASES = ([f"n{N}_r{r}" for N in NS for r in (0, 1)] + [f"soc4_n{N}" for N in NS_SOC] + ["wide", "wide_warm"])
 
 
-def _inputs():
-    """The first 32 instances of pmpc_batch(2)."""
-    from dart_mpc.workload import pmpc_batch
-    S, T, P = pmpc_batch(2)
-    return S[:32], T[:32], P[:32]
-
-
-def _wide_inputs():
-    """The inputs of test_gpu_pmpc_overlap.py::_wide_inputs (tilt box [-1.2, 1.2], far targets)."""
-    from dart_mpc.workload import pmpc_batch
-    S, T, P = pmpc_batch(1)
-    P = P.copy(); P[:, 4] = -1.2; P[:, 5] = 1.2
-    T = T.copy(); T[:, 0] = np.where(S[:, 0] > 0, -0.6, 0.6); T[:, 2] = np.where(S[:, 2] > 0, -0.5, 0.5)
-    return S, T, P
-
-
 def _child(outdir, bsoc):
     """Every case on the GPU with this process's DART_PMPC_OVERLAP; <case>__<key>.npy into outdir.  bsoc: the batch
     sizes of the correction-pass cases, one per N of NS_SOC (the parent takes them from the oracle)."""
-    import torch
     import dart_mpc
 
     def save(case, out):
-        for k in KEYS:
-            np.save(os.path.join(outdir, f"{case}__{k}.npy"), out[k])
+        H.save(outdir, case, out)
 
     S, T, P = _inputs()
     for N in NS:
@@ -82,26 +59,10 @@ def _child(outdir, bsoc):
     s.close()
     # back-to-back launches at N = 20, B = 18 on one stream, no synchronisation between them
     S18, T18, P18 = S[:18], T[:18], P[:18]
-    dev = torch.device("cuda:0")
-    d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (S18, T18, P18)]
     s = dart_mpc.Solver(N=20, Ts=0.002, tol=1e-8, B_max=18)
     ref = s.solve_batch(S18, T18, P18, want_w=True)
     save("b2b_ref", ref)
-    nw = ref["w"].shape[1]
-    U0 = torch.zeros((B2B, 18, 2), dtype=torch.float64, device=dev)
-    FV = torch.zeros((B2B, 18), dtype=torch.float64, device=dev)
-    WO = torch.zeros((B2B, 18, nw), dtype=torch.float64, device=dev)
-    ST = torch.full((B2B, 18), -99, dtype=torch.int32, device=dev)
-    IT = torch.zeros((B2B, 18), dtype=torch.int32, device=dev)
-    stream = torch.cuda.Stream(device=dev)
-    torch.cuda.synchronize()
-    for i in range(B2B):
-        s.solve_batch_dev(18, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), U0[i].data_ptr(),
-                          FV[i].data_ptr(), ST[i].data_ptr(), IT[i].data_ptr(), w_out=WO[i].data_ptr(),
-                          stream=stream.cuda_stream)
-    torch.cuda.synchronize()
-    save("b2b", dict(u0=U0.cpu().numpy(), f=FV.cpu().numpy(), status=ST.cpu().numpy(), iters=IT.cpu().numpy(),
-                     w=WO.cpu().numpy()))
+    save("b2b", H.back_to_back(s, S18, T18, P18, ref["w"].shape[1], B2B))
     s.close()
 
 
@@ -126,18 +87,7 @@ def _soc_prefix(oracle_soc, N):
 def runs(tmp_path_factory, oracle_soc):
     """{setting: {name: array}} of a fresh child per setting: "0" (one-wave builds) and "default" (overlap on)."""
     bsoc = [str(_soc_prefix(oracle_soc, N)) for N in NS_SOC]
-    res = {}
-    for setting in ("0", "default"):
-        outdir = str(tmp_path_factory.mktemp(f"scan_{setting}"))
-        env = dict(os.environ)
-        env.pop("DART_PMPC_OVERLAP", None)
-        if setting == "0":
-            env["DART_PMPC_OVERLAP"] = "0"
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), outdir] + bsoc, env=env, capture_output=True,
-                           text=True, timeout=300)
-        assert r.returncode == 0, (setting, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-        res[setting] = {f[:-4]: np.load(os.path.join(outdir, f)) for f in os.listdir(outdir) if f.endswith(".npy")}
-    return res
+    return H.run_settings(tmp_path_factory, __file__, "scan", bsoc)
 
 
 @pytest.mark.parametrize("N", NS)

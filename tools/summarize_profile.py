@@ -32,7 +32,7 @@ GRID = {"pmpc_ipm_kernel": 18 * 8 * 64, "rmpc_ipm_kernel": 18 * 8 * 64, "lmpc_ip
         "arm_qp_kernel": 36 * 64}
 # the template instances the headline launches use: round 5, B <= 32 runs the FUSE instantiations of PMPC and
 # LMPC (restoration in the solving wave); RMPC's <false> is followed by its queued <true> (~4 us when empty)
-STATS_NAME = {"pmpc_ipm_kernel": "pmpc_ipm_kernel<1, true, false, true, false, false, true>",
+STATS_NAME = {"pmpc_ipm_kernel": "pmpc_ipm_kernel<1, 37u>",      # kScan | kShort2 | kFuse (pmpc_ipm.hip)
               "rmpc_ipm_kernel": "rmpc_ipm_kernel<false>",
               "lmpc_ipm_kernel": "lmpc_ipm_kernel<false, true>"}
 

@@ -20,7 +20,8 @@ DST = os.path.join(ROOT, "profiles", TAG, "sq_summary.json")
 
 # label: (kernel-name prefix, grid size of the headline launch, working waves per launch)
 # (B <= 32 launches run the fused instantiations: <..., FUSE = true>, restoration in the solving wave)
-KERNELS = {"PMPC C2": ("void dartmpc::pmpc_ipm_kernel<1, true, false, true, false", 9216, 18),
+# (PMPC: the second template argument is the build's flag mask, pmpc_ipm.hip; the grid size picks the launch)
+KERNELS = {"PMPC C2": ("void dartmpc::pmpc_ipm_kernel<1, ", 9216, 18),
            "RMPC C3": ("void dartmpc::rmpc_ipm_kernel<false", 9216, 18),
            "LMPC C5": ("void dartmpc::lmpc_ipm_kernel<false", 9216, 18),
            "arm QP": ("void dartmpc::arm_qp_kernel<7>", 2304, 36)}
