@@ -746,3 +746,327 @@ int dart_lmpc_collect(dart_mpc_handle* h, const dart_plant_config* plant, const 
     return lmpc_closed_loop_host(h, plant, pcfg, rcfg, true, B, k0, steps, log_rows, rec_rows, reset_rows, p, noise,
                                  stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Cross-plant closed loops: the PMPC and RMPC loops on the LMPC plant (pmpc_lm_loop_kernel / rmpc_lm_loop_kernel
+// between the unchanged solves), with streaming metrics.  The entries build one CrossBuf from their positional
+// arguments; everything below the entries takes that.  One table, kCrossArr, describes each array once.
+namespace {
+
+struct CrossBuf {
+    const double *target, *prm, *plant_pvec, *pz_vz;
+    double *x, *tilt, *prev, *u_prev, *r_v, *theta, *P, *w;
+    int32_t *done, *nlog;
+    double* metrics;
+    double *log_pos_err, *log_pos_err_norm, *log_u_cmd, *log_timestep;     // RMPC's episode rows
+    double *log_x, *log_theta, *log_r_v, *log_f;                          // RMPC's step rows
+    double *log_X, *log_U, *log_quat, *log_loss;                          // PMPC's step rows
+    int32_t *log_status, *log_iters;
+    double* log_rot;
+};
+
+// the solve's per-step arrays of one loop-step launch
+struct CrossIo {
+    double *x0, *Rref, *phi, *y;
+    const double *u0, *f;
+    const int32_t *status, *iters;
+};
+
+enum CrossKind : uint8_t {
+    cUp,        // [B][width], up only
+    cBoth,      // [B][width], both ways
+    cEpisode,   // [log_rows][B][width], RMPC's episode rows: the rows the call can write travel both ways
+    cStep       // [log_rows][B][width], the call's step rows come down
+};
+constexpr uint8_t kPm = 1, kRm = 2;     // bits of the controllers
+struct CrossArr {
+    size_t member;        // offsetof(CrossBuf, ...)
+    int wp, wr;           // elements per instance under PMPC / RMPC; 0: not an array of that controller, -1: nw
+    uint8_t size, kind;
+    uint8_t solve_only;   // controllers whose loop-step launch does not take the array (only the solve reads it)
+};
+#define ARR(member, wp, wr, type, kind, solve_only) {offsetof(CrossBuf, member), wp, wr, sizeof(type), kind, solve_only}
+const CrossArr kCrossArr[] = {
+    ARR(target, 6, 4, double, cUp, 0), ARR(prm, 6, 10, double, cUp, kPm), ARR(plant_pvec, 34, 34, double, cUp, 0),
+    ARR(pz_vz, 2, 0, double, cUp, 0),
+    ARR(x, 8, 8, double, cBoth, 0), ARR(tilt, 2, 2, double, cBoth, 0), ARR(prev, 0, 4, double, cBoth, 0),
+    ARR(u_prev, 0, 2, double, cBoth, 0), ARR(r_v, 0, 4, double, cBoth, 0), ARR(theta, 0, 14, double, cBoth, 0),
+    ARR(P, 0, 98, double, cBoth, kRm), ARR(w, 0, -1, double, cBoth, kRm),
+    ARR(done, 0, 1, int32_t, cBoth, 0), ARR(nlog, 0, 1, int32_t, cBoth, 0), ARR(metrics, 8, 8, double, cBoth, 0),
+    ARR(log_pos_err, 0, 2, double, cEpisode, 0), ARR(log_pos_err_norm, 0, 1, double, cEpisode, 0),
+    ARR(log_u_cmd, 0, 2, double, cEpisode, 0), ARR(log_timestep, 0, 1, double, cEpisode, 0),
+    ARR(log_x, 0, 4, double, cStep, 0), ARR(log_theta, 0, 14, double, cStep, 0), ARR(log_r_v, 0, 4, double, cStep, 0),
+    ARR(log_f, 0, 1, double, cStep, 0),
+    ARR(log_X, 6, 0, double, cStep, 0), ARR(log_U, 2, 0, double, cStep, 0), ARR(log_quat, 4, 0, double, cStep, 0),
+    ARR(log_loss, 1, 0, double, cStep, 0),
+    ARR(log_status, 1, 1, int32_t, cStep, 0), ARR(log_iters, 1, 1, int32_t, cStep, 0), ARR(log_rot, 4, 4, double, cStep, 0),
+};
+#undef ARR
+constexpr int kCrossArrays = sizeof kCrossArr / sizeof kCrossArr[0];
+
+// (every member of CrossBuf is an object pointer)
+void*& member(CrossBuf& d, const CrossArr& a) { return *reinterpret_cast<void**>(reinterpret_cast<char*>(&d) + a.member); }
+const void* member(const CrossBuf& d, const CrossArr& a) {
+    return *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(&d) + a.member);
+}
+
+// Every argument check of the cross-plant entries, host and device forms alike (`step`: a loop-step entry, which
+// does not take the arrays that only the solve reads).  *logs: 1 with every log given, 0 in metrics-only mode
+// (every log null, log_rows not consulted).  mu_c / v_c of the plant config are not used, as in the LMPC loop.
+int cross_check(dart_mpc_handle* h, int variant, const dart_plant_config* plant, const dart_rmpc_loop_config* c, int B,
+                int k, int steps, int log_rows, const CrossBuf& p, bool step, int* logs) {
+    if (h->cfg.variant != variant) return fail(h, DART_MPC_EINVAL, variant_text(variant));
+    if (!plant) return fail(h, DART_MPC_EINVAL, "null plant config");
+    const bool rm = variant == DART_MPC_RMPC;
+    if (rm) {
+        if (!c) return fail(h, DART_MPC_EINVAL, "null loop config");
+        if (!(c->rls_lambda > 0.0) || !(c->dr_max >= 0.0) || !(c->step_fraction >= 0.0 && c->step_fraction <= 1.0))
+            return fail(h, DART_MPC_EINVAL, "loop config: rls_lambda > 0, dr_max >= 0, 0 <= step_fraction <= 1");
+    }
+    if (B < 0 || k < 0 || steps < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
+    if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
+    int given = 0, absent = 0;
+    for (const CrossArr& a : kCrossArr) {
+        if (!(rm ? a.wr : a.wp) || (step && (a.solve_only & (rm ? kRm : kPm)))) continue;
+        const bool log = a.kind == cEpisode || a.kind == cStep;
+        if (!log && !member(p, a)) return fail(h, DART_MPC_EINVAL, "null pointer");
+        if (log) ++(member(p, a) ? given : absent);
+    }
+    if (given && absent) return fail(h, DART_MPC_EINVAL, "null and non-null log pointers (metrics-only mode: every log null)");
+    if (given && (long long)k + steps > log_rows) return fail(h, DART_MPC_EINVAL, "k0 + steps exceeds log_rows");
+    *logs = given ? 1 : 0;
+    return DART_MPC_OK;
+}
+
+// one loop-step launch (the checks made)
+int cross_loop_step(dart_mpc_handle* h, bool rm, const dart_plant_config* plant, const dart_rmpc_loop_config* loop, int B,
+                    int k, int do_post, int do_pre, int log_rows, int logs, const CrossBuf& p, const CrossIo& io,
+                    void* stream) {
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const double a_lag = plant->tau > 0.0 ? 1.0 - std::exp(-h->cfg.Ts / plant->tau) : 1.0;
+    if (rm) {
+        dartmpc::RmpcLmLoopArgs a;
+        a.B = B; a.N = h->cfg.N; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+        a.logs = logs; a.a_lag = a_lag;
+        a.Ts = h->cfg.Ts; a.dr_max = loop->dr_max; a.alpha_rg = loop->alpha_rg; a.step_fraction = loop->step_fraction;
+        a.pos_tol = loop->pos_tol;
+        a.target = p.target; a.prm = p.prm; a.plant_pvec = p.plant_pvec;
+        a.x = p.x; a.tilt = p.tilt; a.prev = p.prev; a.u_prev = p.u_prev; a.r_v = p.r_v; a.theta = p.theta;
+        a.done = p.done; a.nlog = p.nlog; a.metrics = p.metrics;
+        a.x0 = io.x0; a.Rref = io.Rref; a.phi = io.phi; a.y = io.y; a.u0 = io.u0; a.f = io.f; a.status = io.status;
+        a.iters = io.iters;
+        a.log_pos_err = p.log_pos_err; a.log_pos_err_norm = p.log_pos_err_norm; a.log_u_cmd = p.log_u_cmd;
+        a.log_timestep = p.log_timestep; a.log_x = p.log_x; a.log_theta = p.log_theta; a.log_r_v = p.log_r_v;
+        a.log_f = p.log_f; a.log_status = p.log_status; a.log_iters = p.log_iters; a.log_rot = p.log_rot;
+        HIPCHK(h, dartmpc_launch_rmpc_lm_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
+    } else {
+        dartmpc::PmpcLmLoopArgs a;
+        a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows; a.logs = logs;
+        a.a_lag = a_lag; a.Ts = h->cfg.Ts;
+        a.target = p.target; a.plant_pvec = p.plant_pvec; a.pz_vz = p.pz_vz; a.x = p.x; a.tilt = p.tilt;
+        a.metrics = p.metrics; a.x0 = io.x0; a.u0 = io.u0; a.f = io.f; a.status = io.status; a.iters = io.iters;
+        a.log_X = p.log_X; a.log_U = p.log_U; a.log_quat = p.log_quat; a.log_loss = p.log_loss;
+        a.log_status = p.log_status; a.log_iters = p.log_iters; a.log_rot = p.log_rot;
+        HIPCHK(h, dartmpc_launch_pmpc_lm_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
+    }
+    return DART_MPC_OK;
+}
+
+// the closed loop on device pointers, the handle's lock held: every check, then the launches of the tray-plant
+// rollouts (RMPC warm-started in place with the fused RLS, PMPC cold-started)
+int cross_closed_loop(dart_mpc_handle* h, int variant, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                      int B, int k0, int steps, int log_rows, const CrossBuf& p, void* stream) {
+    int logs = 0;
+    if (int rc = cross_check(h, variant, plant, loop, B, k0, steps, log_rows, p, false, &logs)) return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const bool rm = variant == DART_MPC_RMPC;
+    LoopScratch L;
+    if (int rc = loop_scratch(h, L)) return rc;
+    const CrossIo io = {L.x0, L.Rref, L.phi, L.y, L.u0, L.f, L.status, L.iters};
+    void* s = stream_of(h, stream);
+    auto step = [&](int k, int post, int pre) {
+        return cross_loop_step(h, rm, plant, loop, B, k, post, pre, log_rows, logs, p, io, s);
+    };
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        const int rc = rm ? dart_rmpc_solve_batch_dev(h, B, L.x0, p.u_prev, p.theta, p.P, L.phi, L.y, loop->rls_lambda, L.Rref,
+                                                      p.prm, p.w, L.u0, L.f, p.w, L.status, L.iters, s)
+                          : dart_mpc_solve_batch_dev(h, B, L.x0, p.target, p.prm, nullptr, L.u0, L.f, nullptr, L.status,
+                                                     L.iters, s);
+        if (rc) return rc;
+        if (int rc2 = step(k0 + j, 1, j + 1 < steps)) return rc2;
+    }
+    return DART_MPC_OK;
+}
+
+// the host form: the arrays of `p` staged into the handle's arena around cross_closed_loop; in metrics-only mode
+// no log is laid out or moved
+int cross_closed_loop_host(dart_mpc_handle* h, int variant, const dart_plant_config* plant,
+                           const dart_rmpc_loop_config* loop, int B, int k0, int steps, int log_rows, const CrossBuf& p,
+                           void* stream) {
+    int logs = 0;
+    if (int rc = cross_check(h, variant, plant, loop, B, k0, steps, log_rows, p, false, &logs)) return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const bool rm = variant == DART_MPC_RMPC;
+    if (!rm)
+        if (int rc = settle_pending(h)) return rc;
+    hipStream_t s = stream_of(h, stream);
+    const size_t nB = (size_t)B, nw = rm ? (size_t)dart_rmpc_nw(h->cfg.N) : 0;
+    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
+    // episode rows: an instance writes rows nlog[b] .. nlog[b] + steps - 1 at most
+    int e0 = log_rows, e1 = 0;
+    if (rm && logs) {
+        for (int b = 0; b < B; ++b) {
+            if (p.nlog[b] < 0) return fail(h, DART_MPC_EINVAL, "negative nlog");
+            e0 = p.nlog[b] < e0 ? p.nlog[b] : e0;
+            e1 = p.nlog[b] > e1 ? p.nlog[b] : e1;
+        }
+        e1 = (long long)e1 + steps < log_rows ? e1 + steps : log_rows;
+        e0 = e0 < e1 ? e0 : e1;
+    }
+    RollStage S;
+    int idx[kCrossArrays];
+    for (int i = 0; i < kCrossArrays; ++i) {
+        const CrossArr& a = kCrossArr[i];
+        const int width = rm ? a.wr : a.wp;
+        idx[i] = -1;
+        if (!width) continue;
+        const size_t row = (width < 0 ? nw : (size_t)width) * a.size * nB;
+        switch (a.kind) {
+        case cUp: idx[i] = S.add(member(p, a), row, false); break;
+        case cBoth: idx[i] = S.add(member(p, a), row, true); break;
+        case cEpisode: if (logs) idx[i] = S.add_log(const_cast<void*>(member(p, a)), R, row, e0, e1, true); break;
+        case cStep: if (logs) idx[i] = S.add_log(const_cast<void*>(member(p, a)), R, row, r0, r1, false); break;
+        }
+    }
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    CrossBuf d{};
+    for (int i = 0; i < kCrossArrays; ++i) member(d, kCrossArr[i]) = S.dev<char>(h, idx[i]);
+    if (int rc = cross_closed_loop(h, variant, plant, loop, B, k0, steps, log_rows, d, s)) return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+CrossBuf pmpc_cross_buf(const double* target, const double* prm, const double* plant_pvec, const double* pz_vz, double* x,
+                        double* tilt, double* metrics, double* log_X, double* log_U, double* log_quat, double* log_loss,
+                        int32_t* log_status, int32_t* log_iters, double* log_rot) {
+    CrossBuf p{};
+    p.target = target; p.prm = prm; p.plant_pvec = plant_pvec; p.pz_vz = pz_vz; p.x = x; p.tilt = tilt;
+    p.metrics = metrics; p.log_X = log_X; p.log_U = log_U; p.log_quat = log_quat; p.log_loss = log_loss;
+    p.log_status = log_status; p.log_iters = log_iters; p.log_rot = log_rot;
+    return p;
+}
+
+CrossBuf rmpc_cross_buf(const double* target, const double* prm, const double* plant_pvec, double* x, double* tilt,
+                        double* prev, double* u_prev, double* r_v, double* theta, double* P, double* w, int32_t* done,
+                        int32_t* nlog, double* metrics, double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd,
+                        double* log_timestep, double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                        int32_t* log_status, int32_t* log_iters, double* log_rot) {
+    CrossBuf p{};
+    p.target = target; p.prm = prm; p.plant_pvec = plant_pvec; p.x = x; p.tilt = tilt; p.prev = prev; p.u_prev = u_prev;
+    p.r_v = r_v; p.theta = theta; p.P = P; p.w = w; p.done = done; p.nlog = nlog; p.metrics = metrics;
+    p.log_pos_err = log_pos_err; p.log_pos_err_norm = log_pos_err_norm; p.log_u_cmd = log_u_cmd;
+    p.log_timestep = log_timestep; p.log_x = log_x; p.log_theta = log_theta; p.log_r_v = log_r_v; p.log_f = log_f;
+    p.log_status = log_status; p.log_iters = log_iters; p.log_rot = log_rot;
+    return p;
+}
+
+}  // namespace
+
+int dart_pmpc_lm_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                               int B, int k, int do_post, int do_pre, int log_rows,
+                               const double* target, const double* plant_pvec, const double* pz_vz,
+                               double* x, double* tilt, double* metrics, double* x0,
+                               const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                               double* log_X, double* log_U, double* log_quat, double* log_loss,
+                               int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    const CrossBuf p = pmpc_cross_buf(target, nullptr, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat,
+                                      log_loss, log_status, log_iters, log_rot);
+    int logs = 0;
+    if (int rc = cross_check(h, DART_MPC_PMPC, plant, nullptr, B, k, do_post ? 1 : 0, log_rows, p, true, &logs)) return rc;
+    if (any_null({x0, u0, f, status, iters})) return fail(h, DART_MPC_EINVAL, "null pointer");
+    const CrossIo io = {x0, nullptr, nullptr, nullptr, u0, f, status, iters};
+    return cross_loop_step(h, false, plant, nullptr, B, k, do_post, do_pre, log_rows, logs, p, io, stream);
+}
+
+int dart_rmpc_lm_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                               int B, int k, int do_post, int do_pre, int log_rows,
+                               const double* target, const double* prm, const double* plant_pvec,
+                               double* x, double* tilt, double* prev, double* u_prev, double* r_v, const double* theta,
+                               int32_t* done, int32_t* nlog, double* metrics,
+                               double* x0, double* Rref, double* phi, double* y,
+                               const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                               double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                               double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                               int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    const CrossBuf p = rmpc_cross_buf(target, prm, plant_pvec, x, tilt, prev, u_prev, r_v, mut(theta), nullptr, nullptr, done,
+                                      nlog, metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x,
+                                      log_theta, log_r_v, log_f, log_status, log_iters, log_rot);
+    int logs = 0;
+    if (int rc = cross_check(h, DART_MPC_RMPC, plant, loop, B, k, do_post ? 1 : 0, log_rows, p, true, &logs)) return rc;
+    if (any_null({x0, Rref, phi, y, u0, f, status, iters})) return fail(h, DART_MPC_EINVAL, "null pointer");
+    const CrossIo io = {x0, Rref, phi, y, u0, f, status, iters};
+    return cross_loop_step(h, true, plant, loop, B, k, do_post, do_pre, log_rows, logs, p, io, stream);
+}
+
+int dart_pmpc_lm_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                             int B, int k0, int steps, int log_rows,
+                             const double* target, const double* prm, const double* plant_pvec, const double* pz_vz,
+                             double* x, double* tilt, double* metrics,
+                             double* log_X, double* log_U, double* log_quat, double* log_loss,
+                             int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return cross_closed_loop(h, DART_MPC_PMPC, plant, nullptr, B, k0, steps, log_rows,
+                             pmpc_cross_buf(target, prm, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat, log_loss,
+                                            log_status, log_iters, log_rot), stream);
+}
+
+int dart_pmpc_lm_rollout(dart_mpc_handle* h, const dart_plant_config* plant,
+                         int B, int k0, int steps, int log_rows,
+                         const double* target, const double* prm, const double* plant_pvec, const double* pz_vz,
+                         double* x, double* tilt, double* metrics,
+                         double* log_X, double* log_U, double* log_quat, double* log_loss,
+                         int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return cross_closed_loop_host(h, DART_MPC_PMPC, plant, nullptr, B, k0, steps, log_rows,
+                                  pmpc_cross_buf(target, prm, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat,
+                                                 log_loss, log_status, log_iters, log_rot), stream);
+}
+
+int dart_rmpc_lm_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                             int B, int k0, int steps, int log_rows,
+                             const double* target, const double* prm, const double* plant_pvec,
+                             double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
+                             double* P, double* w, int32_t* done, int32_t* nlog, double* metrics,
+                             double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                             double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                             int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return cross_closed_loop(h, DART_MPC_RMPC, plant, loop, B, k0, steps, log_rows,
+                             rmpc_cross_buf(target, prm, plant_pvec, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog,
+                                            metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x,
+                                            log_theta, log_r_v, log_f, log_status, log_iters, log_rot), stream);
+}
+
+int dart_rmpc_lm_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                         int B, int k0, int steps, int log_rows,
+                         const double* target, const double* prm, const double* plant_pvec,
+                         double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
+                         double* P, double* w, int32_t* done, int32_t* nlog, double* metrics,
+                         double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                         double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                         int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return cross_closed_loop_host(h, DART_MPC_RMPC, plant, loop, B, k0, steps, log_rows,
+                                  rmpc_cross_buf(target, prm, plant_pvec, x, tilt, prev, u_prev, r_v, theta, P, w, done,
+                                                 nlog, metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep,
+                                                 log_x, log_theta, log_r_v, log_f, log_status, log_iters, log_rot),
+                                  stream);
+}

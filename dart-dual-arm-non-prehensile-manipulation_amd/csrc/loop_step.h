@@ -105,8 +105,85 @@ struct LmpcLoopArgs {
     int32_t* log_iters;         // [..]
 };
 
+// Cross-plant loops: the PMPC / RMPC closed loops of pmpc_loop_kernel / rmpc_loop_kernel on harness.LmpcPlant, with
+// streaming metrics.  The plant state is LmpcPlant's x [B][8] = [px vx py vy th_x om_x th_y om_y], stepped by the
+// LMPC model with plant_pvec.  tilt [B][2] is the lagged PMPC / RMPC command (a = g sin(theta), g = -9.81,
+// mpc_3d.py:91-92); the LMPC model has G = m g sin(a) with g = +9.81 (rlmpc2.py:353-357), so its input is
+// sin(-tilt) (run.py:257 flips the command for the same reason): the next state is bit for bit what
+// lmpc_loop_kernel computes for (x, -tilt, -u, pvec).
+//
+// metrics [B][8], in/out, updated by every post with e_k = |X_k[[0, 2]] - target[[0, 2]]| of the state that solve k
+// saw: 0 e of the last step, 1 first k with e_k < 0.01 (-1 while there is none), 2 sum |u_k| Ts, 3 max e_k,
+// 4 steps with status != 0, 5 sum of iters, 6 max of |th_x|, |th_y| over the states the solves saw, 7 steps
+// accumulated.  A fresh run starts from zeros with slot 1 = -1.
+//
+// logs == 0 (every log pointer null): no log row is written and log_rows is not consulted.
+struct PmpcLmLoopArgs {
+    int B;
+    int k, do_post, do_pre, log_rows, logs;
+    double a_lag, Ts;
+    const double* target;       // [B][6]
+    const double* plant_pvec;   // [B][34]
+    const double* pz_vz;        // [B][2] the solve's x0[4..5] (no plant moves them)
+    double* x;                  // [B][8] in/out
+    double* tilt;               // [B][2] in/out
+    double* metrics;            // [B][8] in/out
+    double* x0;                 // [B][6] the solve's input (written by pre): [x[0..3], pz_vz]
+    const double* u0;           // [B][2]
+    const double* f;            // [B]
+    const int32_t* status;      // [B]
+    const int32_t* iters;       // [B]
+    double* log_X;              // [log_rows][B][6] = [x[0..3], pz_vz]
+    double* log_U;              // [..][2]
+    double* log_quat;           // [..][4]
+    double* log_loss;           // [..]
+    int32_t* log_status;        // [..]
+    int32_t* log_iters;         // [..]
+    double* log_rot;            // [..][4] = x[4..7]
+};
+
+struct RmpcLmLoopArgs {
+    int B, N;
+    int k, do_post, do_pre, log_rows, logs;
+    double a_lag;
+    double Ts, dr_max, alpha_rg, step_fraction, pos_tol;
+    const double* target;       // [B][4]
+    const double* prm;          // [B][10]
+    const double* plant_pvec;   // [B][34]
+    double* x;                  // [B][8] in/out
+    double* tilt;               // [B][2]
+    double* prev;               // [B][4]
+    double* u_prev;             // [B][2]
+    double* r_v;                // [B][4]
+    const double* theta;        // [B][14]
+    int32_t* done;              // [B]
+    int32_t* nlog;              // [B] (advances in metrics-only mode too)
+    double* metrics;            // [B][8] in/out
+    double* x0;                 // [B][4]
+    double* Rref;               // [B][4(N+1)]
+    double* phi;                // [B][7]
+    double* y;                  // [B][2]
+    const double* u0;           // [B][2]
+    const double* f;            // [B]
+    const int32_t* status;      // [B]
+    const int32_t* iters;       // [B]
+    double* log_pos_err;        // as RmpcLoopArgs
+    double* log_pos_err_norm;
+    double* log_u_cmd;
+    double* log_timestep;
+    double* log_x;              // [..][4] = x[0..3]
+    double* log_theta;
+    double* log_r_v;
+    double* log_f;
+    int32_t* log_status;
+    int32_t* log_iters;
+    double* log_rot;            // [..][4] = x[4..7]
+};
+
 }  // namespace dartmpc
 
 extern "C" hipError_t dartmpc_launch_lmpc_loop(const dartmpc::LmpcLoopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_pmpc_lm_loop(const dartmpc::PmpcLmLoopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_rmpc_lm_loop(const dartmpc::RmpcLmLoopArgs* args, hipStream_t stream);

@@ -5,7 +5,8 @@
 // (RMPC/dev_dual/rob_ctrl.py:335-351).  pmpc_loop_kernel: the same for harness.run_pmpc
 // (PMPC/main_parallel_enhanced.py:333-348: log, tilt -> quaternion, plant step, next state).  lmpc_loop_kernel:
 // the same for harness.run_lmpc (LMPC/src/run.py:256-286: log, plant step of the LMPC model, next state); its
-// lane mapping is described at the kernel.
+// lane mapping is described at the kernel.  pmpc_lm_loop_kernel / rmpc_lm_loop_kernel: the PMPC / RMPC glue on the
+// LMPC plant, with streaming metrics (harness.run_pmpc / run_rmpc with plant_pvec), at the end of the file.
 //
 // RMPC / PMPC: one wave64 per instance, kLoopWaves instances per block; lane i owns horizon node i (the staged
 // reference), the per-instance scalars are computed by every lane and stored by one.  All three: plain fp64 in the
@@ -279,7 +280,226 @@ __global__ __launch_bounds__(kLmLoopThreads) void lmpc_loop_kernel(LmpcLoopArgs 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Cross-plant loops (harness.run_pmpc / run_rmpc with plant_pvec): pmpc_loop_kernel / rmpc_loop_kernel on the LMPC
+// plant, with streaming metrics (loop_step.h).  One wave64 per instance as there: lane i owns node i of RMPC's
+// staged reference, and every aligned group of kLmGroup lanes runs the plant step the way lmpc_loop_kernel's
+// group does (lane r = lane & 7 evaluates Stribeck term r; the shuffles stay inside the group), so all 64 lanes
+// hold the same next state.  The plant step is lmpc_loop_kernel's text again, not shared with it, so that kernel
+// keeps its instructions.
+constexpr double kMetricTol = 0.01;     // logger.py:162
+
+// harness.LmpcPlant.step with the command -u: tilt is the lagged PMPC / RMPC command, the model's input sin(-tilt)
+__device__ __forceinline__ void lm_cross_plant_step(const double* pv, int r, double a_lag, double h, const double* u,
+                                                    double* x, double* tilt) {
+    tilt[0] += a_lag * (u[0] - tilt[0]);
+    tilt[1] += a_lag * (u[1] - tilt[1]);
+    LmPlantPrm P;
+    P.m_x = lm_squash(pv[0]); P.m_y = lm_squash(pv[1]); P.c_x = lm_squash(pv[2]); P.c_y = lm_squash(pv[3]);
+    P.k_x = lm_squash(pv[4]); P.k_y = lm_squash(pv[5]); P.I_x = lm_squash(pv[16]); P.I_y = lm_squash(pv[17]);
+    P.r_x = lm_squash(pv[18]); P.r_y = lm_squash(pv[19]); P.c_rot_x = lm_squash(pv[20]); P.c_rot_y = lm_squash(pv[21]);
+    P.h_com_x = lm_squash(pv[32]); P.h_com_y = lm_squash(pv[33]);
+    {
+        const int t = r < 6 ? r : r - 6;
+        const int o = t == 0 || t == 2 ? 6 : t == 1 || t == 3 ? 11 : t == 4 ? 22 : 27;
+        P.Fs = pv[o]; P.Fc = pv[o + 1]; P.Bv = pv[o + 2]; P.vs = lm_squash(pv[o + 3]); P.eps = lm_squash(pv[o + 4]);
+    }
+    const double st = sin((r & 1) ? -tilt[1] : -tilt[0]);
+    const double sa = __shfl(st, 0, kLmGroup), sb = __shfl(st, 1, kLmGroup);
+    double k1[8], k2[8], k3[8], k4[8], y[8];
+    lm_plant_dyn(P, r, x, sa, sb, k1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y[i] = x[i] + 0.5 * h * k1[i];
+    lm_plant_dyn(P, r, y, sa, sb, k2);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y[i] = x[i] + 0.5 * h * k2[i];
+    lm_plant_dyn(P, r, y, sa, sb, k3);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y[i] = x[i] + h * k3[i];
+    lm_plant_dyn(P, r, y, sa, sb, k4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = x[i] + h * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) / 6;
+}
+
+// harness.rollout_metrics, one step: m [8] in/out (one lane per instance)
+__device__ __forceinline__ void loop_metrics_step(double* m, int k, double Ts, double e, const double* u, int status,
+                                                  int iters, double th_x, double th_y) {
+    const double first = m[1], eff = m[2], emax = m[3], bad = m[4], its = m[5], rot = m[6], n = m[7];
+    const double un = sqrt(u[0] * u[0] + u[1] * u[1]);
+    const double th = fabs(th_x) > fabs(th_y) ? fabs(th_x) : fabs(th_y);
+    m[0] = e;
+    m[1] = (first < 0.0 && e < kMetricTol) ? (double)k : first;
+    m[2] = eff + un * Ts;
+    m[3] = e > emax ? e : emax;
+    m[4] = status != 0 ? bad + 1.0 : bad;
+    m[5] = its + (double)iters;
+    m[6] = th > rot ? th : rot;
+    m[7] = n + 1.0;
+}
+
+__global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_lm_loop_kernel(RmpcLmLoopArgs a) {
+    const int lane = threadIdx.x & (kLoopWave - 1);
+    const int b = blockIdx.x * kLoopWaves + (threadIdx.x >> 6);
+    if (b >= a.B) return;                    // wave-uniform
+    const size_t B = (size_t)a.B;
+    const double* tg = a.target + 4 * b;
+    const double t0 = tg[0], t2 = tg[2];
+    double x[8], tilt[2], prev[4], rv[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = a.x[8 * b + i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rv[i] = a.r_v[4 * b + i];
+
+    if (a.do_post) {
+        tilt[0] = a.tilt[2 * b]; tilt[1] = a.tilt[2 * b + 1];
+        const double u[2] = {a.u0[2 * b], a.u0[2 * b + 1]};
+        const size_t row = (size_t)a.k * B + b;
+        const double dx = x[0] - t0, dy = x[2] - t2;
+        const double en = sqrt(dx * dx + dy * dy);
+        if (a.logs && lane < 14) a.log_theta[14 * row + lane] = a.theta[14 * b + lane];
+        if (lane == 0) {
+            const int nl = a.nlog[b];
+            if (!a.done[b]) {
+                if (a.logs && nl >= 0 && nl < a.log_rows) {
+                    const size_t er = (size_t)nl * B + b;
+                    a.log_pos_err[2 * er] = t0 - x[0]; a.log_pos_err[2 * er + 1] = t2 - x[2];
+                    a.log_pos_err_norm[er] = en;
+                    a.log_u_cmd[2 * er] = u[0]; a.log_u_cmd[2 * er + 1] = u[1];
+                    a.log_timestep[er] = a.k * a.Ts;
+                }
+                a.nlog[b] = nl + 1;
+                if (en < a.pos_tol) a.done[b] = 1;
+            }
+            const int status = a.status[b], iters = a.iters[b];
+            if (a.logs) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    a.log_x[4 * row + i] = x[i];
+                    a.log_r_v[4 * row + i] = rv[i];
+                    a.log_rot[4 * row + i] = x[4 + i];
+                }
+                a.log_status[row] = status;
+                a.log_iters[row] = iters;
+                a.log_f[row] = a.f[b];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a.prev[4 * b + i] = x[i];
+            a.u_prev[2 * b] = u[0]; a.u_prev[2 * b + 1] = u[1];
+            double m[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) m[i] = a.metrics[8 * b + i];
+            loop_metrics_step(m, a.k, a.Ts, en, u, status, iters, x[4], x[6]);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a.metrics[8 * b + i] = m[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) prev[i] = x[i];
+        lm_cross_plant_step(a.plant_pvec + 34 * b, lane & (kLmGroup - 1), a.a_lag, a.Ts, u, x, tilt);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a.x[8 * b + i] = x[i];
+            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) prev[i] = a.prev[4 * b + i];
+    }
+
+    if (a.do_pre) {
+        const double veps = a.prm[10 * b + 9];
+        // reference governor (rob_ctrl.py:346-348) on the two position entries
+        rv[0] = rv[0] + a.alpha_rg * fmin(fmax(t0 - rv[0], -a.dr_max), a.dr_max);
+        rv[2] = rv[2] + a.alpha_rg * fmin(fmax(t2 - rv[2], -a.dr_max), a.dr_max);
+        if (lane <= a.N) {      // staged reference, node `lane` (np_mpc...:201-210)
+            const double wgt = 1.0 - pow(1.0 - a.step_fraction, (double)(lane + 1));
+            double* R = a.Rref + 4 * ((size_t)(a.N + 1) * b + lane);
+            R[0] = rv[0] + wgt * (t0 - rv[0]); R[1] = 0.0;
+            R[2] = rv[2] + wgt * (t2 - rv[2]); R[3] = 0.0;
+        }
+        if (lane == 0) {
+            a.r_v[4 * b] = rv[0]; a.r_v[4 * b + 2] = rv[2];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { a.x0[4 * b + i] = x[i]; a.phi[7 * b + i] = prev[i]; }
+            a.phi[7 * b + 4] = tanh(prev[1] / veps);
+            a.phi[7 * b + 5] = tanh(prev[3] / veps);
+            a.phi[7 * b + 6] = 1.0;
+            a.y[2 * b] = (x[1] - prev[1]) / a.Ts;
+            a.y[2 * b + 1] = (x[3] - prev[3]) / a.Ts;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_lm_loop_kernel(PmpcLmLoopArgs a) {
+    const int lane = threadIdx.x & (kLoopWave - 1);
+    const int b = blockIdx.x * kLoopWaves + (threadIdx.x >> 6);
+    if (b >= a.B) return;                    // wave-uniform
+    double x[8], tilt[2];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = a.x[8 * b + i];
+    const double pz = a.pz_vz[2 * b], vz = a.pz_vz[2 * b + 1];
+
+    if (a.do_post) {
+        tilt[0] = a.tilt[2 * b]; tilt[1] = a.tilt[2 * b + 1];
+        const double u[2] = {a.u0[2 * b], a.u0[2 * b + 1]};
+        const size_t row = (size_t)a.k * a.B + b;
+        // pmpc.tilt_to_quat: Euler xyz [u1, -u0, 0] -> (w, x, y, z)
+        const double ax = u[1] / 2.0, ay = -u[0] / 2.0;
+        const double cx = cos(ax), cy = cos(ay), cz = 1.0, sx = sin(ax), sy = sin(ay), sz = 0.0;
+        if (lane == 0) {
+            const int status = a.status[b], iters = a.iters[b];
+            if (a.logs) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { a.log_X[6 * row + i] = x[i]; a.log_rot[4 * row + i] = x[4 + i]; }
+                a.log_X[6 * row + 4] = pz; a.log_X[6 * row + 5] = vz;
+                a.log_U[2 * row] = u[0]; a.log_U[2 * row + 1] = u[1];
+                a.log_quat[4 * row] = cx * cy * cz + sx * sy * sz;
+                a.log_quat[4 * row + 1] = sx * cy * cz - cx * sy * sz;
+                a.log_quat[4 * row + 2] = cx * sy * cz + sx * cy * sz;
+                a.log_quat[4 * row + 3] = cx * cy * sz - sx * sy * cz;
+                a.log_loss[row] = a.f[b];
+                a.log_status[row] = status;
+                a.log_iters[row] = iters;
+            }
+            const double dx = x[0] - a.target[6 * b], dy = x[2] - a.target[6 * b + 2];
+            double m[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) m[i] = a.metrics[8 * b + i];
+            loop_metrics_step(m, a.k, a.Ts, sqrt(dx * dx + dy * dy), u, status, iters, x[4], x[6]);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a.metrics[8 * b + i] = m[i];
+        }
+        lm_cross_plant_step(a.plant_pvec + 34 * b, lane & (kLmGroup - 1), a.a_lag, a.Ts, u, x, tilt);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a.x[8 * b + i] = x[i];
+            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
+        }
+    }
+    if (a.do_pre && lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a.x0[6 * b + i] = x[i];
+        a.x0[6 * b + 4] = pz; a.x0[6 * b + 5] = vz;
+    }
+}
+
 }  // namespace dartmpc
+
+extern "C" hipError_t dartmpc_launch_rmpc_lm_loop(const dartmpc::RmpcLmLoopArgs* args, hipStream_t stream) {
+    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
+    if (args->N < 1 || args->N > 63) return hipErrorInvalidValue;
+    const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
+    hipLaunchKernelGGL(dartmpc::rmpc_lm_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0,
+                       stream, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_pmpc_lm_loop(const dartmpc::PmpcLmLoopArgs* args, hipStream_t stream) {
+    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
+    const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
+    hipLaunchKernelGGL(dartmpc::pmpc_lm_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0,
+                       stream, *args);
+    return hipGetLastError();
+}
 
 extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, hipStream_t stream) {
     if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;

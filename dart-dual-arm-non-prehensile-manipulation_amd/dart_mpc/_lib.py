@@ -55,7 +55,9 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_lmpc_choice_dev", "dart_lmpc_choice", "dart_lmpc_perms_stream_dev", "dart_lmpc_global_rows",
            "dart_lmpc_global_fill_after", "dart_lmpc_global_workspace_bytes", "dart_lmpc_global_append_dev",
            "dart_lmpc_global_append", "dart_lmpc_gae_seq_dev", "dart_lmpc_gae_seq", "dart_lmpc_train_global_dev",
-           "dart_lmpc_train_global")
+           "dart_lmpc_train_global",
+           "dart_pmpc_lm_loop_step_dev", "dart_pmpc_lm_rollout_dev", "dart_pmpc_lm_rollout",
+           "dart_rmpc_lm_loop_step_dev", "dart_rmpc_lm_rollout_dev", "dart_rmpc_lm_rollout")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -141,6 +143,14 @@ LMPC_LOOP_IO = (("state", 8, np.float64), ("u0", 2, np.float64), ("f", 0, np.flo
                 ("iters", 0, np.int32))
 LMPC_LOOP_LOGS = (("X", 8, np.float64), ("U_cmd", 2, np.float64), ("pos_error", 0, np.float64), ("pvec", 34, np.float64),
                   ("loss", 0, np.float64), ("status", 0, np.int32), ("iters", 0, np.int32))
+# cross-plant loops (dart_pmpc_lm_* / dart_rmpc_lm_*): PMPC / RMPC on the LMPC plant, x [B, 8], with streaming metrics
+# [B, 8] (METRIC_SLOTS) and the rotation log; the solve's per-step arrays are PMPC_LOOP_IO / RMPC_LOOP_IO
+PMPC_LM_LOOP_STATE = (("x", 8, np.float64), ("tilt", 2, np.float64), ("metrics", 8, np.float64))
+PMPC_LM_LOOP_LOGS = PMPC_LOOP_LOGS + (("rot", 4, np.float64),)
+RMPC_LM_LOOP_STATE = (("x", 8, np.float64),) + RMPC_LOOP_STATE[1:] + (("metrics", 8, np.float64),)
+RMPC_LM_LOOP_LOGS = RMPC_LOOP_LOGS + (("rot", 4, np.float64),)
+METRIC_SLOTS = ("steady_state_error", "convergence_step", "control_effort", "max_error", "status_nonzero", "iters",
+                "max_rotation", "steps")
 # experience collection (dart_lmpc_collect): the collection state [B, width], the reset pool [reset_rows, B, width],
 # the per-step logs [rows, B] and the records [rec_rows, B, width]
 LMPC_COLLECT_STATE = (("prev_cmd", 2, np.float64), ("control_seen", 2, np.float64), ("ep_step", 0, np.int32),
@@ -304,6 +314,17 @@ def lib():
         for fn in (L.dart_lmpc_rollout_dev, L.dart_lmpc_rollout):
             fn.argtypes = [vp, vp, vp] + [ci] * 4 + [vp] * 24
             fn.restype = ctypes.c_int
+    if hasattr(L, "dart_pmpc_lm_rollout_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_pmpc_lm_loop_step_dev.argtypes = [vp, vp] + [ci] * 5 + [vp] * 19
+        L.dart_rmpc_lm_loop_step_dev.argtypes = [vp, vp, vp] + [ci] * 5 + [vp] * 32
+        for fn in (L.dart_pmpc_lm_rollout_dev, L.dart_pmpc_lm_rollout):
+            fn.argtypes = [vp, vp] + [ci] * 4 + [vp] * 15
+        for fn in (L.dart_rmpc_lm_rollout_dev, L.dart_rmpc_lm_rollout):
+            fn.argtypes = [vp, vp, vp] + [ci] * 4 + [vp] * 26
+        for fn in (L.dart_pmpc_lm_loop_step_dev, L.dart_rmpc_lm_loop_step_dev, L.dart_pmpc_lm_rollout_dev,
+                   L.dart_pmpc_lm_rollout, L.dart_rmpc_lm_rollout_dev, L.dart_rmpc_lm_rollout):
+            fn.restype = ctypes.c_int
     if hasattr(L, "dart_lmpc_collect_dev"):  # (absent only in older in-tree builds used for A/B timing)
         vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
         L.dart_lmpc_reward_config_default.argtypes = [ctypes.POINTER(RewardConfig)]
@@ -460,13 +481,25 @@ def loop_logs(spec, rows, B):
             for name, width, dt in spec}
 
 
+def loop_metrics(B):
+    """The metrics of a fresh cross-plant run, [B, 8] (METRIC_SLOTS): zeros, slot 1 (the convergence step) -1."""
+    m = np.zeros((B, 8))
+    m[:, 1] = -1.0
+    return m
+
+
 def _dev_ptrs(spec, arrays):
-    """Device pointers (ints) of ``arrays`` (a mapping name -> int) in the order of ``spec``."""
+    """Device pointers (ints) of ``arrays`` (a mapping name -> int) in the order of ``spec``; ``arrays`` None: null
+    pointers (the metrics-only mode of the cross-plant entries)."""
+    if arrays is None:
+        return [None] * len(spec)
     return [ctypes.c_void_p(int(arrays[name])) for name, _, _ in spec]
 
 
 def _host_ptrs(spec, arrays, lead, **sizes):
     """Pointers of the numpy arrays of ``arrays`` in the order of ``spec``, shapes and dtypes checked."""
+    if arrays is None:          # (the metrics-only mode of the cross-plant entries)
+        return [None] * len(spec)
     out = []
     for name, width, dt in spec:
         a = arrays[name]
@@ -646,6 +679,44 @@ class Solver:
         if rc != 0:
             self._err(rc, "dart_pmpc_rollout")
 
+    # -- the same loop on the LMPC plant (dart_pmpc_lm_loop_step_dev / dart_pmpc_lm_rollout_dev / dart_pmpc_lm_rollout) ----
+    def loop_step_lm_dev(self, B, k, do_post, do_pre, log_rows, target, plant_pvec, pz_vz, state, io, logs, plant=None,
+                         stream=0):
+        """``loop_step_dev`` on the LMPC plant: ``state`` maps PMPC_LM_LOOP_STATE, ``logs`` PMPC_LM_LOOP_LOGS (None:
+        metrics-only) to device pointers."""
+        plant = plant or plant_config()
+        rc = lib().dart_pmpc_lm_loop_step_dev(self._h, ctypes.byref(plant), int(B), int(k), int(do_post), int(do_pre),
+                                              int(log_rows), target, plant_pvec, pz_vz,
+                                              *_dev_ptrs(PMPC_LM_LOOP_STATE, state), *_dev_ptrs(PMPC_LOOP_IO, io),
+                                              *_dev_ptrs(PMPC_LM_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_pmpc_lm_loop_step_dev")
+
+    def rollout_lm_dev(self, B, k0, steps, log_rows, target, prm, plant_pvec, pz_vz, state, logs, plant=None, stream=0):
+        """``rollout_dev`` on the LMPC plant with the true parameters ``plant_pvec`` [B, 34]: ``state`` maps
+        PMPC_LM_LOOP_STATE (x [B, 8], tilt, metrics [B, 8], see ``loop_metrics``), ``logs`` PMPC_LM_LOOP_LOGS to device
+        pointers; ``logs`` None is the metrics-only mode (no log row is written)."""
+        plant = plant or plant_config()
+        rc = lib().dart_pmpc_lm_rollout_dev(self._h, ctypes.byref(plant), int(B), int(k0), int(steps), int(log_rows),
+                                            target, prm, plant_pvec, pz_vz, *_dev_ptrs(PMPC_LM_LOOP_STATE, state),
+                                            *_dev_ptrs(PMPC_LM_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_pmpc_lm_rollout_dev")
+
+    def rollout_lm(self, k0, steps, target, prm, plant_pvec, pz_vz, state, logs, plant=None):
+        """Host arrays (blocking): ``state`` (PMPC_LM_LOOP_STATE) is advanced and ``logs`` (``loop_logs`` of
+        PMPC_LM_LOOP_LOGS) rows k0 .. k0+steps-1 are filled in place; ``logs`` None moves no log."""
+        B = state["x"].shape[0]
+        rows = logs["X"].shape[0] if logs is not None else 0
+        c = lambda a, n: np.ascontiguousarray(a, np.float64).reshape(B, n)
+        target, prm, plant_pvec, pz_vz = c(target, 6), c(prm, 6), c(plant_pvec, 34), c(pz_vz, 2)
+        plant = plant or plant_config()
+        rc = lib().dart_pmpc_lm_rollout(self._h, ctypes.byref(plant), B, int(k0), int(steps), rows, _ptr(target), _ptr(prm),
+                                        _ptr(plant_pvec), _ptr(pz_vz), *_host_ptrs(PMPC_LM_LOOP_STATE, state, (B,)),
+                                        *_host_ptrs(PMPC_LM_LOOP_LOGS, logs, (rows, B)), None)
+        if rc != 0:
+            self._err(rc, "dart_pmpc_lm_rollout")
+
     def sync(self):
         rc = lib().dart_mpc_sync(self._h)
         if rc != 0:
@@ -814,6 +885,61 @@ class RmpcSolver(Solver):
                                      *_host_ptrs(RMPC_LOOP_LOGS, logs, (rows, B)), None)
         if rc != 0:
             self._err(rc, "dart_rmpc_rollout")
+
+    # -- the same loop on the LMPC plant (dart_rmpc_lm_loop_step_dev / dart_rmpc_lm_rollout_dev / dart_rmpc_lm_rollout) ----
+    def loop_step_lm_dev(self, B, k, do_post, do_pre, log_rows, target, prm, plant_pvec, state, io, logs, plant=None,
+                         loop=None, stream=0):
+        """``loop_step_dev`` on the LMPC plant: ``state`` maps RMPC_LM_LOOP_STATE (P and w are not needed), ``logs``
+        RMPC_LM_LOOP_LOGS (None: metrics-only) to device pointers."""
+        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
+        spec = tuple(e for e in RMPC_LM_LOOP_STATE if e[0] not in ("P", "w"))
+        rc = lib().dart_rmpc_lm_loop_step_dev(self._h, ctypes.byref(plant), ctypes.byref(loop), int(B), int(k), int(do_post),
+                                              int(do_pre), int(log_rows), target, prm, plant_pvec, *_dev_ptrs(spec, state),
+                                              *_dev_ptrs(RMPC_LOOP_IO, io), *_dev_ptrs(RMPC_LM_LOOP_LOGS, logs),
+                                              stream or None)
+        if rc != 0:
+            self._err(rc, "dart_rmpc_lm_loop_step_dev")
+
+    def rollout_lm_dev(self, B, k0, steps, log_rows, target, prm, plant_pvec, state, logs, plant=None, loop=None, stream=0):
+        """``rollout_dev`` on the LMPC plant with the true parameters ``plant_pvec`` [B, 34]: ``state`` maps
+        RMPC_LM_LOOP_STATE (x [B, 8], ..., metrics [B, 8]), ``logs`` RMPC_LM_LOOP_LOGS to device pointers; ``logs`` None
+        is the metrics-only mode (done / nlog still advance)."""
+        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
+        rc = lib().dart_rmpc_lm_rollout_dev(self._h, ctypes.byref(plant), ctypes.byref(loop), int(B), int(k0), int(steps),
+                                            int(log_rows), target, prm, plant_pvec, *_dev_ptrs(RMPC_LM_LOOP_STATE, state),
+                                            *_dev_ptrs(RMPC_LM_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_rmpc_lm_rollout_dev")
+
+    def rollout_lm(self, k0, steps, target, prm, plant_pvec, state, logs, plant=None, loop=None):
+        """Host arrays (blocking): ``state`` (RMPC_LM_LOOP_STATE, see ``loop_state_lm``) is advanced and ``logs``
+        (``loop_logs`` of RMPC_LM_LOOP_LOGS) are filled in place; ``logs`` None moves no log."""
+        B = state["x"].shape[0]
+        rows = logs["x"].shape[0] if logs is not None else 0
+        target = np.ascontiguousarray(target, np.float64).reshape(B, 4)
+        prm = np.ascontiguousarray(prm, np.float64).reshape(B, 10)
+        plant_pvec = np.ascontiguousarray(plant_pvec, np.float64).reshape(B, 34)
+        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
+        rc = lib().dart_rmpc_lm_rollout(self._h, ctypes.byref(plant), ctypes.byref(loop), B, int(k0), int(steps), rows,
+                                        _ptr(target), _ptr(prm), _ptr(plant_pvec),
+                                        *_host_ptrs(RMPC_LM_LOOP_STATE, state, (B,), nw=self.nw),
+                                        *_host_ptrs(RMPC_LM_LOOP_LOGS, logs, (rows, B)), None)
+        if rc != 0:
+            self._err(rc, "dart_rmpc_lm_rollout")
+
+    def loop_state_lm(self, x0, x_rot0=None, P0=1e3):
+        """The state of a fresh cross-plant rollout from the measured states ``x0`` [B, 4] and the rotation states
+        ``x_rot0`` [B, 4] (default zeros)."""
+        x0 = np.asarray(x0, np.float64).reshape(-1, 4)
+        B = x0.shape[0]
+        st = {name: np.zeros(_loop_shape(B, width, nw=self.nw), dt) for name, width, dt in RMPC_LM_LOOP_STATE}
+        st["x"][:, :4] = x0
+        if x_rot0 is not None:
+            st["x"][:, 4:] = np.asarray(x_rot0, np.float64).reshape(B, 4)
+        st["prev"][:] = x0
+        st["P"][:] = np.tile(np.eye(7) * float(P0), (2, 1, 1)).reshape(98)
+        st["metrics"][:] = loop_metrics(B)
+        return st
 
     def loop_state(self, x0, P0=1e3):
         """The state of a fresh rollout from the measured states ``x0`` [B, 4] (run_rmpc's initial values)."""

@@ -84,6 +84,47 @@ def logger_metrics(logs: dict, dt: float) -> dict:
     return {"steady_state_error": sse, "convergence_time": conv, "control_effort": effort}
 
 
+def rollout_metrics(X, target, U, status, iters, rot, Ts, metrics=None, k0=0):
+    """The eight streaming accumulators of the cross-plant loops (csrc/loop_step.hip loop_metrics_step, _lib.METRIC_SLOTS)
+    restated in numpy as a plain sequential loop over the steps: X [K, B, >= 3] the states the solves saw, target
+    [B, >= 3], U [K, B, 2], status / iters [K, B], rot [K, B, 4] = [th_x, om_x, th_y, om_y] (one experiment: the same
+    without the B axis).  With e_k = |X_k[[0, 2]] - target[[0, 2]]|: 0 e of the last step, 1 first k with e_k <
+    ERROR_THRESHOLD (-1 while none), 2 sum |u_k| Ts, 3 max e_k, 4 steps with status != 0, 5 sum of iters, 6 max of
+    |th_x|, |th_y|, 7 steps.  Slots 0 .. 2 are ``logger_metrics`` (convergence_time = Ts * slot 1, or t[-1] when slot 1
+    is -1).  ``metrics`` [B, 8] / ``k0`` continue an earlier run.  Returns [B, 8] ([8] for one experiment)."""
+    X, U = np.asarray(X, float), np.asarray(U, float)
+    one = X.ndim == 2
+    if one:
+        X, U, target = X[:, None], U[:, None], np.asarray(target, float)[None]
+        status, iters, rot = np.asarray(status)[:, None], np.asarray(iters)[:, None], np.asarray(rot, float)[:, None]
+    target, status, iters, rot = np.asarray(target, float), np.asarray(status), np.asarray(iters), np.asarray(rot, float)
+    K, B = X.shape[:2]
+    if metrics is None:
+        M = np.zeros((B, 8)); M[:, 1] = -1.0
+    else:
+        M = np.array(metrics, float).reshape(B, 8)
+    for k in range(K):
+        for b in range(B):
+            m = M[b]
+            dx, dy = X[k, b, 0] - target[b, 0], X[k, b, 2] - target[b, 2]
+            e = np.sqrt(dx * dx + dy * dy)
+            un = np.sqrt(U[k, b, 0] * U[k, b, 0] + U[k, b, 1] * U[k, b, 1])
+            th = max(abs(rot[k, b, 0]), abs(rot[k, b, 2]))
+            m[0] = e
+            if m[1] < 0.0 and e < ERROR_THRESHOLD:
+                m[1] = float(k0 + k)
+            m[2] = m[2] + un * Ts
+            if e > m[3]:
+                m[3] = e
+            if status[k, b] != 0:
+                m[4] = m[4] + 1.0
+            m[5] = m[5] + float(iters[k, b])
+            if th > m[6]:
+                m[6] = th
+            m[7] = m[7] + 1.0
+    return M[0] if one else M
+
+
 def save_npz(logs: dict, metrics: dict, log_dir, experiment_name: str, object_name: str, mass, friction) -> str:
     """np.savez(logs + metrics) at ``{log_dir}/{object}/mass={m}_friction={f}/{name}_{timestamp}.npz``
     (logger.py:186-196)."""
@@ -125,34 +166,59 @@ def save_episodes_json(path, episodes: dict, pretty: bool = True) -> None:
 
 # ---------------------------------------------------------------------------------------------
 # closed loops
+def _cross_plant(x4, x_rot0, plant_pvec, Ts, plant_kw):
+    """``LmpcPlant`` of the cross-plant loops from the translation states [B, 4] and ``x_rot0`` [B, 4] (default zeros);
+    of ``plant_kw`` only ``tau`` applies (the LMPC model's Stribeck terms are its Coulomb friction)."""
+    x4 = np.asarray(x4, float).reshape(-1, 4)
+    B = x4.shape[0]
+    x8 = np.zeros((B, 8)); x8[:, :4] = x4
+    if x_rot0 is not None:
+        x8[:, 4:] = np.asarray(x_rot0, float).reshape(B, 4)
+    kw = {k: v for k, v in (plant_kw or {}).items() if k == "tau"}
+    return LmpcPlant(x8, np.asarray(plant_pvec, float).reshape(B, 34), dt=Ts, **kw)
+
+
 def run_pmpc(states0, targets, prm, steps: int, N: int = 20, Ts: float = 0.002, tol: float = 1e-8, device: int = 0,
-             plant_kw: dict | None = None):
+             plant_kw: dict | None = None, plant_pvec=None, x_rot0=None):
     """B PMPC experiments in lock step (main_parallel_enhanced.py:290-419 without MuJoCo): per step the
     state of every object, one batched cold-started solve, tilt -> quaternion (:333-348), plant step.
 
     states0, targets [B, 6]; prm [B, 6] = [mu, Qp, Qv, R, u_lo, u_hi] (the solver's parameter rows).
     Returns a list of per-experiment log dicts in the AsyncLogger schema, metrics included, and the
-    per-step solver statuses [steps, B]."""
+    per-step solver statuses [steps, B].
+
+    ``plant_pvec`` [B, 34]: the plant is ``LmpcPlant`` with these true parameters, started from states0[:, :4] and
+    ``x_rot0`` [B, 4] (default zeros) and stepped with ``-u0`` (the LMPC model's gravity has the other sign,
+    rlmpc2.py:353-357 against mpc_3d.py:91-92); the solves see [x[:4], states0[:, 4:6]].  The dicts then also hold
+    ``rot`` [steps, 4] and ``metrics`` [8] (``rollout_metrics``)."""
     states0 = np.asarray(states0, float).reshape(-1, 6)
     B = states0.shape[0]
     targets = np.asarray(targets, float).reshape(B, 6)
     prm = np.asarray(prm, float).reshape(B, 6)
+    cross = plant_pvec is not None
     solver = Solver(N=N, Ts=Ts, tol=tol, B_max=max(B, 1), device=device)
-    plant = TrayPlant(states0, prm[:, 0], dt=Ts, **(plant_kw or {}))
+    plant = _cross_plant(states0[:, :4], x_rot0, plant_pvec, Ts, plant_kw) if cross \
+        else TrayPlant(states0, prm[:, 0], dt=Ts, **(plant_kw or {}))
     X = np.zeros((steps, B, 6)); U = np.zeros((steps, B, 2)); Q = np.zeros((steps, B, 4))
     L = np.zeros((steps, B)); ST = np.zeros((steps, B), np.int32); TS = np.zeros(steps)
+    IT = np.zeros((steps, B), np.int32); ROT = np.zeros((steps, B, 4))
     try:
         for k in range(steps):
-            X[k] = plant.x
+            if cross:
+                X[k] = np.concatenate([plant.x[:, :4], states0[:, 4:6]], axis=1)
+                ROT[k] = plant.x[:, 4:]
+            else:
+                X[k] = plant.x
             t0 = time.perf_counter()
-            out = solver.solve_batch(plant.x, targets, prm)
+            out = solver.solve_batch(X[k], targets, prm)
             TS[k] = time.perf_counter() - t0
-            U[k], L[k], ST[k] = out["u0"], out["f"], out["status"]
+            U[k], L[k], ST[k], IT[k] = out["u0"], out["f"], out["status"], out["iters"]
             Q[k] = np.stack([tilt_to_quat(u) for u in out["u0"]])
-            plant.step(out["u0"])
+            plant.step(-out["u0"] if cross else out["u0"])
     finally:
         solver.close()
     t = np.arange(steps) * Ts
+    M = rollout_metrics(X, targets, U, ST, IT, ROT, Ts) if cross else None
     logs = []
     for b in range(B):
         lg = {"t": t, "X": X[:, b], "X_target": np.tile(targets[b], (steps, 1)), "U_cmd": U[:, b],
@@ -161,18 +227,24 @@ def run_pmpc(states0, targets, prm, steps: int, N: int = 20, Ts: float = 0.002, 
             lg["L_" + key] = np.zeros((steps, w))       # arms are not simulated here
             lg["R_" + key] = np.zeros((steps, w))
         lg.update(logger_metrics(lg, Ts))
+        if cross:
+            lg.update(rot=ROT[:, b], metrics=M[b])
         logs.append(lg)
     return logs, ST
 
 
 def run_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=None, device: int = 0,
              pos_tol: float = ERROR_THRESHOLD, plant_kw: dict | None = None, mu=0.1, dr_max: float = 0.01,
-             alpha_rg: float = 0.5, lam: float = 0.995, P0: float = 1e3):
+             alpha_rg: float = 0.5, lam: float = 0.995, P0: float = 1e3, plant_pvec=None, x_rot0=None):
     """B RMPC experiments in lock step (rob_ctrl.py:320-420 without MuJoCo): RLS on the measured
     accelerations fused into the solve launch, reference governor, staged reference, warm-started
     solve; an experiment's episode closes when its error first drops below ``pos_tol`` (the
     reference then stops).  Returns (episodes per experiment in the rob_ctrl.py JSON layout,
-    statuses [steps, B])."""
+    statuses [steps, B]).
+
+    ``plant_pvec`` [B, 34]: the plant is ``LmpcPlant`` with these true parameters (``mu`` is then not used), started
+    from x0 and ``x_rot0`` [B, 4] (default zeros) and stepped with ``-u`` (see ``run_pmpc``).  Each experiment's dict
+    then also holds ``rot`` [steps run, 4] and ``metrics`` [8] (``rollout_metrics`` over the steps run)."""
     x0 = np.asarray(x0, float).reshape(-1, 4)
     B = x0.shape[0]
     targets = np.asarray(targets, float).reshape(B, 4)
@@ -181,7 +253,10 @@ def run_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=None, 
     prm = np.tile(ctl.params(), (B, 1)) if prm is None else np.asarray(prm, float).reshape(B, 10)
     solver = RmpcSolver(N=N, Ts=Ts, B_max=max(B, 1), device=device)
     full = np.zeros((B, 6)); full[:, :4] = x0
-    plant = TrayPlant(full, mu, dt=Ts, **(plant_kw or {}))
+    cross = plant_pvec is not None
+    plant = _cross_plant(x0, x_rot0, plant_pvec, Ts, plant_kw) if cross else TrayPlant(full, mu, dt=Ts, **(plant_kw or {}))
+    XS = np.zeros((steps, B, 4)); US = np.zeros((steps, B, 2)); IT = np.zeros((steps, B), np.int32)
+    ROT = np.zeros((steps, B, 4))
     theta = np.zeros((B, 14)); P = np.tile(np.eye(7) * P0, (B, 2, 1, 1))
     r_v = np.zeros((B, 4)); u_prev = np.zeros((B, 2)); w = np.zeros((B, ctl.w0.shape[0]))
     prev = x0.copy()
@@ -201,6 +276,8 @@ def run_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=None, 
             theta, P, w = out["theta"], out["rls_P"], out["w"]
             u = out["u0"]
             ST[k] = out["status"]
+            if cross:
+                XS[k], US[k], IT[k], ROT[k] = xk, u, out["iters"], plant.x[:, 4:]
             en = np.linalg.norm(xk[:, [0, 2]] - targets[:, [0, 2]], axis=1)
             for b in np.where(~done)[0]:
                 lg = logs[b]
@@ -213,16 +290,20 @@ def run_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=None, 
                     done[b] = True
             prev = xk
             u_prev = u.copy()
-            plant.step(u)
+            plant.step(-u if cross else u)
             if done.all():
                 break
     finally:
         solver.close()
+    n = k + 1
+    M = rollout_metrics(XS[:n], targets, US[:n], ST[:n], IT[:n], ROT[:n], Ts) if cross else None
     episodes = []
     for b in range(B):
         eps = {}
         add_episode(eps, "ep1", logs[b]["pos_err"], logs[b]["pos_err_norm"], logs[b]["u_cmd"], logs[b]["torque"],
                     logs[b]["timestep"])
+        if cross:
+            eps.update(rot=ROT[:n, b], metrics=M[b])
         episodes.append(eps)
     return episodes, ST[:k + 1], done
 
@@ -231,26 +312,42 @@ def run_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=None, 
 # the same closed loops, resident on the device (dart_pmpc_rollout / dart_rmpc_rollout): per step one loop-step
 # kernel and the solve, on one stream, no host round trip; the logs come back with one download per call
 def rollout_pmpc(states0, targets, prm, steps: int, N: int = 20, Ts: float = 0.002, tol: float = 1e-8, device: int = 0,
-                 plant_kw: dict | None = None, return_logs: bool = False):
+                 plant_kw: dict | None = None, plant_pvec=None, x_rot0=None, return_logs: bool = False,
+                 metrics_only: bool = False):
     """``run_pmpc`` on the device: same arguments, same return values (AsyncLogger log dicts with metrics, statuses
     [steps, B]).  ``solve_time`` is the rollout's wall time divided by the steps run.  ``return_logs``: also
-    return dict(iters [steps, B], solve_time)."""
-    from ._lib import PMPC_LOOP_STATE, PMPC_LOOP_LOGS, loop_logs, plant_config
+    return dict(iters [steps, B], solve_time).  With ``plant_pvec`` the loop runs on the LMPC plant
+    (dart_pmpc_lm_rollout); ``metrics_only`` (with ``plant_pvec``) writes and moves no log and returns only the
+    metrics [B, 8] (_lib.METRIC_SLOTS)."""
+    from ._lib import PMPC_LOOP_STATE, PMPC_LOOP_LOGS, PMPC_LM_LOOP_LOGS, loop_logs, loop_metrics, plant_config
     states0 = np.asarray(states0, float).reshape(-1, 6)
     B = states0.shape[0]
     targets = np.asarray(targets, float).reshape(B, 6)
     prm = np.asarray(prm, float).reshape(B, 6)
+    cross = plant_pvec is not None
+    if metrics_only and not cross:
+        raise ValueError("metrics_only needs plant_pvec (the tray-plant rollout has no streaming metrics)")
     plant = plant_config(**{k: v for k, v in (plant_kw or {}).items()})
-    state = {"x": states0.copy(), "tilt": np.zeros((B, 2))}
-    assert set(state) == {n for n, _, _ in PMPC_LOOP_STATE}
-    lg = loop_logs(PMPC_LOOP_LOGS, steps, B)
+    if cross:
+        state = {"x": _cross_plant(states0[:, :4], x_rot0, plant_pvec, Ts, None).x, "tilt": np.zeros((B, 2)),
+                 "metrics": loop_metrics(B)}
+        lg = None if metrics_only else loop_logs(PMPC_LM_LOOP_LOGS, steps, B)
+    else:
+        state = {"x": states0.copy(), "tilt": np.zeros((B, 2))}
+        assert set(state) == {n for n, _, _ in PMPC_LOOP_STATE}
+        lg = loop_logs(PMPC_LOOP_LOGS, steps, B)
     solver = Solver(N=N, Ts=Ts, tol=tol, B_max=max(B, 1), device=device)
     try:
         t0 = time.perf_counter()
-        solver.rollout(0, steps, targets, prm, state, lg)
+        if cross:
+            solver.rollout_lm(0, steps, targets, prm, plant_pvec, states0[:, 4:6], state, lg, plant=plant)
+        else:
+            solver.rollout(0, steps, targets, prm, state, lg, plant=plant)
         wall = time.perf_counter() - t0
     finally:
         solver.close()
+    if metrics_only:
+        return state["metrics"]
     t = np.arange(steps) * Ts
     TS = np.full(steps, wall / max(steps, 1))
     logs = []
@@ -261,6 +358,8 @@ def rollout_pmpc(states0, targets, prm, steps: int, N: int = 20, Ts: float = 0.0
             d["L_" + key] = np.zeros((steps, w))       # arms are not simulated here
             d["R_" + key] = np.zeros((steps, w))
         d.update(logger_metrics(d, Ts))
+        if cross:
+            d.update(rot=lg["rot"][:, b], metrics=state["metrics"][b])
         logs.append(d)
     if return_logs:
         return logs, lg["status"], {"iters": lg["iters"], "solve_time": wall / max(steps, 1)}
@@ -269,14 +368,16 @@ def rollout_pmpc(states0, targets, prm, steps: int, N: int = 20, Ts: float = 0.0
 
 def rollout_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=None, device: int = 0,
                  pos_tol: float = ERROR_THRESHOLD, plant_kw: dict | None = None, mu=0.1, dr_max: float = 0.01,
-                 alpha_rg: float = 0.5, lam: float = 0.995, P0: float = 1e3, check_every: int = 0,
-                 return_logs: bool = False):
+                 alpha_rg: float = 0.5, lam: float = 0.995, P0: float = 1e3, plant_pvec=None, x_rot0=None,
+                 check_every: int = 0, return_logs: bool = False, metrics_only: bool = False):
     """``run_rmpc`` on the device: same arguments, same return values (episodes per experiment in the rob_ctrl.py
     JSON layout, statuses [steps run, B], done).  ``check_every`` > 0 runs the rollout in chunks of that many steps
     and stops once every experiment's episode has closed (the state stays valid between calls); 0 runs all
     ``steps`` in one call.  ``return_logs``: also return the per-step device logs (x, theta, r_v, f, status,
-    iters [steps run, B, ...]), the episode rows, the final loop state and ``solve_time``."""
-    from ._lib import RMPC_LOOP_LOGS, loop_logs, plant_config, rmpc_loop_config
+    iters [steps run, B, ...]), the episode rows, the final loop state and ``solve_time``.  With ``plant_pvec`` the
+    loop runs on the LMPC plant (dart_rmpc_lm_rollout; ``mu`` is then not used); ``metrics_only`` (with ``plant_pvec``)
+    writes and moves no log and returns only the metrics [B, 8] (_lib.METRIC_SLOTS)."""
+    from ._lib import RMPC_LOOP_LOGS, RMPC_LM_LOOP_LOGS, loop_logs, plant_config, rmpc_loop_config
     x0 = np.asarray(x0, float).reshape(-1, 4)
     B = x0.shape[0]
     targets = np.asarray(targets, float).reshape(B, 4)
@@ -285,22 +386,30 @@ def rollout_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=No
     prm = np.tile(ctl.params(), (B, 1)) if prm is None else np.asarray(prm, float).reshape(B, 10)
     plant = plant_config(**{k: v for k, v in (plant_kw or {}).items()})
     loop = rmpc_loop_config(dr_max=dr_max, alpha_rg=alpha_rg, rls_lambda=lam, pos_tol=pos_tol)
-    lg = loop_logs(RMPC_LOOP_LOGS, steps, B)
+    cross = plant_pvec is not None
+    if metrics_only and not cross:
+        raise ValueError("metrics_only needs plant_pvec (the tray-plant rollout has no streaming metrics)")
+    lg = None if metrics_only else loop_logs(RMPC_LM_LOOP_LOGS if cross else RMPC_LOOP_LOGS, steps, B)
     solver = RmpcSolver(N=N, Ts=Ts, B_max=max(B, 1), device=device)
     chunk = int(check_every) if check_every and check_every > 0 else max(steps, 1)
     k = 0
     try:
-        state = solver.loop_state(x0, P0)
+        state = solver.loop_state_lm(x0, x_rot0, P0) if cross else solver.loop_state(x0, P0)
         t0 = time.perf_counter()
         while k < steps:
             n = min(chunk, steps - k)
-            solver.rollout(k, n, targets, prm, mu, state, lg, plant=plant, loop=loop)
+            if cross:
+                solver.rollout_lm(k, n, targets, prm, plant_pvec, state, lg, plant=plant, loop=loop)
+            else:
+                solver.rollout(k, n, targets, prm, mu, state, lg, plant=plant, loop=loop)
             k += n
             if state["done"].all():
                 break
         wall = time.perf_counter() - t0
     finally:
         solver.close()
+    if metrics_only:
+        return state["metrics"]
     done = state["done"].astype(bool)
     episodes = []
     for b in range(B):
@@ -309,6 +418,8 @@ def rollout_rmpc(x0, targets, steps: int, N: int = 20, Ts: float = 0.002, prm=No
         add_episode(eps, "ep1", lg["pos_err"][:n, b].tolist(), lg["pos_err_norm"][:n, b].tolist(),
                     list(lg["u_cmd"][:n, b]), [np.zeros(14) for _ in range(n)],      # arms are not simulated here
                     lg["timestep"][:n, b].tolist())
+        if cross:
+            eps.update(rot=lg["rot"][:k, b], metrics=state["metrics"][b])
         episodes.append(eps)
     if return_logs:
         extra = {name: lg[name][:k] for name in ("x", "theta", "r_v", "f", "status", "iters")}
@@ -496,6 +607,38 @@ def rollout_lmpc(x0, targets, plant_pvec, steps: int, N: int = 30, policy_seed=0
     finally:
         solver.close()
     return _lmpc_result(B, steps, Ts, targets, lg, state["x"], state, wall, return_logs)
+
+
+def compare_controllers(x0, target_xy, plant_pvec, steps: int, N: int = 20, lmpc_N: int = 30, Ts: float = 0.002,
+                        pmpc_prm=None, pz_vz=(0.4, 0.0), lmpc_policy_seed=None, device: int = 0,
+                        plant_kw: dict | None = None):
+    """PMPC, RMPC and LMPC on the same objects: B experiments from the states ``x0`` [B, 8] (LmpcPlant's layout) to the
+    targets ``target_xy`` [B, 2] on ``LmpcPlant`` with the true parameters ``plant_pvec`` [B, 34], ``steps`` steps each.
+    PMPC and RMPC run through the cross-plant rollouts in metrics-only mode; LMPC runs through ``rollout_lmpc``
+    (``lmpc_policy_seed`` None: every solve uses ``plant_pvec`` as its model) and ``rollout_metrics`` of its logs.
+    ``pmpc_prm`` [B, 6]: PMPC's parameter rows, default [c_x / m_x of the plant, 600, 5, 0.1, -0.6, 0.6] (the cube's
+    weights, main_parallel_enhanced.py:171-179).  Returns {"PMPC", "RMPC", "LMPC"}: metrics [B, 8] each
+    (_lib.METRIC_SLOTS)."""
+    x0 = np.asarray(x0, float).reshape(-1, 8)
+    B = x0.shape[0]
+    txy = np.asarray(target_xy, float).reshape(B, 2)
+    plant_pvec = np.asarray(plant_pvec, float).reshape(B, 34)
+    zz = np.broadcast_to(np.asarray(pz_vz, float), (B, 2))
+    if pmpc_prm is None:
+        pmpc_prm = np.tile([0.0, 600.0, 5.0, 0.1, -0.6, 0.6], (B, 1))
+        pmpc_prm[:, 0] = (np.abs(plant_pvec[:, 2]) + 1e-6) / (np.abs(plant_pvec[:, 0]) + 1e-6)
+    s6 = np.concatenate([x0[:, :4], zz], axis=1)
+    t6 = np.stack([txy[:, 0], np.zeros(B), txy[:, 1], np.zeros(B), zz[:, 0], np.zeros(B)], axis=1)
+    t4, t8 = t6[:, :4], np.concatenate([t6[:, :4], np.zeros((B, 4))], axis=1)
+    out = {"PMPC": rollout_pmpc(s6, t6, pmpc_prm, steps, N=N, Ts=Ts, device=device, plant_kw=plant_kw,
+                                plant_pvec=plant_pvec, x_rot0=x0[:, 4:], metrics_only=True),
+           "RMPC": rollout_rmpc(x0[:, :4], t4, steps, N=N, Ts=Ts, device=device, plant_kw=plant_kw, pos_tol=0.0,
+                                plant_pvec=plant_pvec, x_rot0=x0[:, 4:], metrics_only=True)}
+    logs, st, X = rollout_lmpc(x0, t8, plant_pvec, steps, N=lmpc_N, policy_seed=lmpc_policy_seed, Ts=Ts, device=device,
+                               plant_kw={k: v for k, v in (plant_kw or {}).items() if k == "tau"}, return_logs=True)
+    U = np.stack([lg["u_cmd"] for lg in logs], axis=1)
+    out["LMPC"] = rollout_metrics(X["X"], t8, U, st, X["iters"], X["X"][:, :, 4:], Ts)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

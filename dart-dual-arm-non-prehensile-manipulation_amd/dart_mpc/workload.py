@@ -183,6 +183,19 @@ def lmpc_batch(n_seeds: int = 1, seed0: int = 0):
     return out
 
 
+def point_mass_pvec(mu, m=1.0):
+    """LMPC plant parameters [B, 34] (index map of rlmpc2.py:301-334) that reduce ``harness.LmpcPlant`` to
+    ``harness.TrayPlant`` without Coulomb friction: masses pvec[0:2] = m, viscous damping pvec[2:4] = mu m (the
+    acceleration is g sin(a) - mu v), inertias pvec[16:18] = 1, zeros elsewhere (no spring, no Stribeck or rolling
+    terms, no toppling arm; squash_param leaves 1e-6 of each).  ``mu`` and ``m`` broadcast to [B]."""
+    mu, m = np.broadcast_arrays(np.atleast_1d(np.asarray(mu, float)), np.asarray(m, float))
+    pvec = np.zeros((mu.shape[0], 34))
+    pvec[:, 0] = pvec[:, 1] = m
+    pvec[:, 2] = pvec[:, 3] = mu * m
+    pvec[:, 16:18] = 1.0
+    return pvec
+
+
 # ---------------------------------------------------------------------------------------------
 # Per-arm impedance QP (SURVEY §8f rank 1; PMPC/src/controller/arm.py:266-457).  MuJoCo is not in
 # this image, so the shared-memory snapshot that compute_dynamics (arm.py:111-199) publishes is

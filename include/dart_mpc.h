@@ -469,6 +469,84 @@ int dart_pmpc_rollout(dart_mpc_handle *h, const dart_plant_config *plant,
                       double *log_X, double *log_U, double *log_quat, double *log_loss,
                       int32_t *log_status, int32_t *log_iters, void *hip_stream);
 
+/* Cross-plant closed loops (added within ABI 8): the PMPC and RMPC loops above on the plant of the LMPC loop below
+ * (dart_mpc/harness.py LmpcPlant: the tilt lag of dart_plant_config.tau, then one RK4 step at Ts of the LMPC model
+ * with the instance's true parameters plant_pvec [B][34]; mu_c / v_c are not used), so that the three controllers
+ * can be compared on the same objects.  Same launch sequence, same handle-owned per-step arrays and the same
+ * warm / cold starts as dart_rmpc_rollout_dev / dart_pmpc_rollout_dev; two calls of K1 and K2 steps give bit for bit
+ * what one call of K1 + K2 steps gives, metrics included.
+ *
+ * State: x [B][8] = [px vx py vy th_x om_x th_y om_y] (LmpcPlant's layout) replaces x [B][6]; mu is gone.  tilt
+ *   [B][2] keeps its meaning, the lagged command: tilt += a_lag (u - tilt).  The PMPC / RMPC command convention is
+ *   a = g sin(theta) with g = -9.81 (mpc_3d.py:91-92) and the LMPC model has G = m g sin(a) with g = +9.81
+ *   (rlmpc2.py:353-357), so the model's input is sin(-tilt): the next x is bit for bit what dart_lmpc_loop_step_dev
+ *   computes for (x, -tilt, -u0, plant_pvec).  PMPC's solve sees x0 = [x[0..3], pz_vz]: pz_vz [B][2] is a constant
+ *   input (the tray plant never moves pz, vz either).  RMPC's solve sees x[0..3] and prev as before.
+ * metrics [B][8] (fp64, in/out; a fresh run starts from zeros with slot 1 = -1), updated by every post with
+ *   e_k = |X_k[[0, 2]] - target[[0, 2]]| of the state that solve k saw:
+ *     0 e of the last step                      4 steps with status != 0
+ *     1 first k with e_k < 0.01, -1 while none  5 sum of iters
+ *     2 sum of |u_k| Ts                         6 max of |th_x|, |th_y| over the states the solves saw
+ *     3 max e_k                                 7 steps accumulated
+ *   Slots 0 .. 2 are AsyncLogger's steady-state error, convergence step and control effort (logger.py:158-183).
+ * Logs: the rows of the tray-plant entries (the state rows take x[0..3]; PMPC's log_X = [x[0..3], pz_vz]) plus
+ *   log_rot [log_rows][B][4] = x[4..7].  Metrics-only mode: every log pointer NULL -- no log row is written,
+ *   log_rows is not consulted, the host entries move no log; RMPC's done / nlog still advance.  Some log pointers
+ *   NULL and others not is DART_MPC_EINVAL. */
+int dart_pmpc_lm_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                               int B, int k, int do_post, int do_pre, int log_rows,
+                               const double *target, const double *plant_pvec, const double *pz_vz,
+                               double *x, double *tilt, double *metrics, double *x0,
+                               const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                               double *log_X, double *log_U, double *log_quat, double *log_loss,
+                               int32_t *log_status, int32_t *log_iters, double *log_rot, void *hip_stream);
+
+int dart_rmpc_lm_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                               int B, int k, int do_post, int do_pre, int log_rows,
+                               const double *target, const double *prm, const double *plant_pvec,
+                               double *x, double *tilt, double *prev, double *u_prev, double *r_v, const double *theta,
+                               int32_t *done, int32_t *nlog, double *metrics,
+                               double *x0, double *Rref, double *phi, double *y,
+                               const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                               double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                               double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                               int32_t *log_status, int32_t *log_iters, double *log_rot, void *hip_stream);
+
+/* Device pointers, asynchronous on hip_stream (NULL = the handle's own). */
+int dart_pmpc_lm_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                             int B, int k0, int steps, int log_rows,
+                             const double *target, const double *prm, const double *plant_pvec, const double *pz_vz,
+                             double *x, double *tilt, double *metrics,
+                             double *log_X, double *log_U, double *log_quat, double *log_loss,
+                             int32_t *log_status, int32_t *log_iters, double *log_rot, void *hip_stream);
+
+int dart_rmpc_lm_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                             int B, int k0, int steps, int log_rows,
+                             const double *target, const double *prm, const double *plant_pvec,
+                             double *x, double *tilt, double *prev, double *u_prev, double *r_v, double *theta,
+                             double *P, double *w, int32_t *done, int32_t *nlog, double *metrics,
+                             double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                             double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                             int32_t *log_status, int32_t *log_iters, double *log_rot, void *hip_stream);
+
+/* Host pointers: staged through device memory; blocks until state, metrics and (unless metrics-only) the rows of the
+ * logs that the call can write are back. */
+int dart_pmpc_lm_rollout(dart_mpc_handle *h, const dart_plant_config *plant,
+                         int B, int k0, int steps, int log_rows,
+                         const double *target, const double *prm, const double *plant_pvec, const double *pz_vz,
+                         double *x, double *tilt, double *metrics,
+                         double *log_X, double *log_U, double *log_quat, double *log_loss,
+                         int32_t *log_status, int32_t *log_iters, double *log_rot, void *hip_stream);
+
+int dart_rmpc_lm_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                         int B, int k0, int steps, int log_rows,
+                         const double *target, const double *prm, const double *plant_pvec,
+                         double *x, double *tilt, double *prev, double *u_prev, double *r_v, double *theta,
+                         double *P, double *w, int32_t *done, int32_t *nlog, double *metrics,
+                         double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                         double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                         int32_t *log_status, int32_t *log_iters, double *log_rot, void *hip_stream);
+
 /* LMPC closed loop (handle of variant DART_MPC_LMPC; added within ABI 8).  What LMPC/src/run.py:256-286 does around
  * ctlr.solve -- the policy step and the warm-started solve (rlmpc2.py:494-524), the log, the plant step, the next
  * state -- with the plant of dart_mpc/harness.py (LmpcPlant) in place of MuJoCo: the first-order tilt lag of

@@ -14,6 +14,9 @@ same object with the same instruction text (a rename), failing that to the most 
 as such.  Where functions are both renamed and changed, --renames takes the pairs from the report of the change
 that only renamed them.  Exit status 1 if anything differs.
 
+--object KEY=TARGET (repeatable) compares other objects of the Makefile instead, e.g. --object loop=build/loop_step.o
+for the closed-loop glue kernels of loop_step.hip.
+
 --resources prints, for the same pairs, the compiler's own figures from the assembly's summary comments (VGPRs, AGPRs,
 scratch and LDS bytes, the occupancy compiled for), old -> new.
 """
@@ -200,7 +203,12 @@ def main():
     ap.add_argument("--renames", metavar="REPORT", help="an earlier report of this tool: its `NEW  (was OLD)` pairs "
                     "name the renamed functions (a names-only change's report, for a later change that alters them)")
     ap.add_argument("--resources", action="store_true", help="print the register / scratch / LDS table instead")
+    ap.add_argument("--object", action="append", metavar="KEY=TARGET", help="compare these objects of csrc/Makefile "
+                    "(KEY.s from the compile line of TARGET) instead of the three built from pmpc_ipm.hip")
     a = ap.parse_args()
+    if a.object:
+        OBJECTS.clear()
+        OBJECTS.update(dict(o.split("=", 1) for o in a.object))
     if a.renames:
         for line in open(a.renames):
             m = re.search(r"((?:void |bool )?\S+::\S.*?)  \(was (.*)\)$", line.rstrip())
@@ -213,9 +221,11 @@ def main():
         if a.resources:
             resource_table(old_dir, new_dir, sys.stdout)
             return 0
-        print("# device assembly of the three objects built from pmpc_ipm.hip (main, -DPMPC_SEQ, -DDART_WG=2), function by "
+        what = ("the three objects built from pmpc_ipm.hip (main, -DPMPC_SEQ, -DDART_WG=2)" if not a.object
+                else ", ".join(OBJECTS.values()))
+        print("# device assembly of %s, function by "
               "function,\n# old against new: instruction text with comments, labels and directives removed\n"
-              "# object, instructions in the old build, result, function")
+              "# object, instructions in the old build, result, function" % what)
         return 1 if compare(old_dir, new_dir, sys.stdout) else 0
 
 

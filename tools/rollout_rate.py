@@ -14,9 +14,17 @@ against run_lmpc_collect, the host loop a user would otherwise write.  They add 
 the chain with resets, those of the solves that follow a reset, and how many of these were handed to the restoration
 phases: the count of status -2 among them in a second collection with the restoration phases off, where a hand-over
 ends the solve instead.
+The CROSS rows (N = 20, not part of the default set) time the cross-plant rollouts -- the PMPC and RMPC loops on the
+LMPC plant with streaming metrics, dart_pmpc_lm_rollout_dev / dart_rmpc_lm_rollout_dev -- against the tray-plant
+rollouts of the same B, N and steps through the device entries (no staging), in the same process, alternating, five
+rounds each after one untimed round.  Two plants: workload.point_mass_pvec of each experiment's friction against the
+tray plant with mu_c = 0 (the same physics: what differs is the glue kernel), and workload.lmpc_batch's pvec (objects
+that neither controller models; the trajectories and with them the iteration counts differ).  The large size adds the
+host entries (harness.rollout_pmpc / rollout_rmpc with plant_pvec, point-mass plant) in metrics-only mode against
+logging mode at 500 steps: wall time and the bytes staged each way.
 Usage: python tools/rollout_rate.py [out.json] [steps] [steps_large] [controllers]
-``controllers``: a comma-separated subset of PMPC,RMPC,LMPC,COLLECT (default: all); the rows of the others are kept
-from an existing out.json.
+``controllers``: a comma-separated subset of PMPC,RMPC,LMPC,COLLECT,CROSS (default: all but CROSS); the rows of the
+others are kept from an existing out.json.
 """
 import json
 import os
@@ -189,7 +197,104 @@ def collect_row(seeds, B, steps):
             "speedup_over_host_loop": t_host / float(np.median(walls["collect"]))}
 
 
-ROWS = {"PMPC": pmpc_row, "RMPC": rmpc_row, "LMPC": lmpc_row, "COLLECT": collect_row}
+def cross_row(seeds, B, steps):
+    import torch
+    from dart_mpc import _lib
+    from dart_mpc.workload import RMPC_PRM, point_mass_pvec
+    S, T, P = pmpc_batch(seeds, seed0=0)
+    x0, tg = rmpc_inputs(B)
+    mu_r = 0.1                                                      # run_rmpc's default plant friction
+    # two plants: the point mass of each experiment (the tray plant without Coulomb friction: like for like, the
+    # difference is the glue kernel's) and workload.lmpc_batch's pvec (objects with springs, Stribeck friction,
+    # rolling and toppling, which neither controller models: other trajectories, other iteration counts)
+    hard = lmpc_batch(seeds, seed0=0)["pvec"]
+    dev = lambda d: {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
+    ptr = lambda d: {k: v.data_ptr() for k, v in d.items()}
+    c = dev(dict(T=T, P=P, pz_vz=S[:, 4:6], tg=tg, rprm=np.tile(RMPC_PRM, (B, 1)), mu=np.full(B, mu_r),
+                 pmpc_pm=point_mass_pvec(P[:, 0]), rmpc_pm=point_mass_pvec(np.full(B, mu_r)), hard=hard))
+    x8 = np.zeros((B, 8)); x8[:, :4] = S[:, :4]
+    ps, rs = _lib.Solver(N=20, B_max=B), _lib.RmpcSolver(N=20, B_max=B)
+    loop = _lib.rmpc_loop_config(pos_tol=0.0)
+    no_coulomb = _lib.plant_config(mu_c=0.0)
+    last = {}
+
+    def run(name):
+        ctl, plant = name.split("_", 1)
+        if name == "pmpc_tray":
+            st, lg = dev(dict(x=S.copy(), tilt=np.zeros((B, 2)))), dev(_lib.loop_logs(_lib.PMPC_LOOP_LOGS, steps, B))
+            go = lambda: ps.rollout_dev(B, 0, steps, steps, c["T"].data_ptr(), c["P"].data_ptr(), ptr(st), ptr(lg),
+                                        plant=no_coulomb)
+        elif ctl == "pmpc":
+            st = dev(dict(x=x8, tilt=np.zeros((B, 2)), metrics=_lib.loop_metrics(B)))
+            lg = dev(_lib.loop_logs(_lib.PMPC_LM_LOOP_LOGS, steps, B))
+            pv = c["pmpc_pm" if plant == "lm_point_mass" else "hard"]
+            go = lambda: ps.rollout_lm_dev(B, 0, steps, steps, c["T"].data_ptr(), c["P"].data_ptr(), pv.data_ptr(),
+                                           c["pz_vz"].data_ptr(), ptr(st), ptr(lg))
+        elif name == "rmpc_tray":
+            st, lg = dev(rs.loop_state(x0)), dev(_lib.loop_logs(_lib.RMPC_LOOP_LOGS, steps, B))
+            go = lambda: rs.rollout_dev(B, 0, steps, steps, c["tg"].data_ptr(), c["rprm"].data_ptr(), c["mu"].data_ptr(),
+                                        ptr(st), ptr(lg), plant=no_coulomb, loop=loop)
+        else:
+            st, lg = dev(rs.loop_state_lm(x0)), dev(_lib.loop_logs(_lib.RMPC_LM_LOOP_LOGS, steps, B))
+            pv = c["rmpc_pm" if plant == "lm_point_mass" else "hard"]
+            go = lambda: rs.rollout_lm_dev(B, 0, steps, steps, c["tg"].data_ptr(), c["rprm"].data_ptr(), pv.data_ptr(),
+                                           ptr(st), ptr(lg), loop=loop)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        go()
+        (ps if ctl == "pmpc" else rs).sync()
+        wall = time.perf_counter() - t0
+        it = lg["iters"].double()
+        last[name] = {"mean_iters": float(it.mean()), "mean_of_max_iters_per_step": float(it.max(dim=1).values.mean()),
+                      "share_status_nonzero": float((lg["status"] != 0).double().mean())}
+        return wall
+    names = ("pmpc_tray", "pmpc_lm_point_mass", "pmpc_lm_objects", "rmpc_tray", "rmpc_lm_point_mass", "rmpc_lm_objects")
+    walls = {n: [] for n in names}
+    try:
+        for n in names:
+            run(n)
+        for _ in range(5):
+            for n in names:
+                walls[n].append(run(n))
+        nw = rs.nw
+    finally:
+        ps.close(); rs.close()
+    row = {"controller": "CROSS", "B": B, "N": 20, "steps": steps, "rounds": 5, "tray_plant_mu_c": 0.0}
+    for n in names:
+        w = walls[n]
+        row[n] = dict(rate(B, steps, float(np.median(w))), min_s=float(np.min(w)), max_s=float(np.max(w)), **last[n])
+    for n in names:
+        if "_lm_" in n:
+            row[n]["steps_per_s_over_tray"] = row[n]["steps_per_s"] / row[n.split("_")[0] + "_tray"]["steps_per_s"]
+    if seeds > 1:       # the host entries on the point-mass plant: metrics-only against logging mode
+        K = 500
+        width = lambda spec, **sz: sum((sz[w] if isinstance(w, str) else max(w, 1)) * np.dtype(dt).itemsize for _, w, dt in spec)
+        host = {}
+        for name, fn, a, kw, state, logs, inputs, sz in (
+                ("pmpc", harness.rollout_pmpc, (S, T, P), dict(plant_pvec=point_mass_pvec(P[:, 0])),
+                 _lib.PMPC_LM_LOOP_STATE, _lib.PMPC_LM_LOOP_LOGS, 8 * (6 + 6 + 34 + 2), {}),
+                ("rmpc", harness.rollout_rmpc, (x0, tg), dict(plant_pvec=point_mass_pvec(np.full(B, mu_r)), pos_tol=0.0),
+                 _lib.RMPC_LM_LOOP_STATE, _lib.RMPC_LM_LOOP_LOGS, 8 * (4 + 10 + 34), dict(nw=nw))):
+            fn(*a, 3, **kw); fn(*a, 3, metrics_only=True, **kw)
+            t = {"logging": [], "metrics_only": []}
+            for _ in range(3):
+                t["logging"].append(timed(fn, *a, K, **kw)[1])
+                t["metrics_only"].append(timed(fn, *a, K, metrics_only=True, **kw)[1])
+            sb, lb = width(state, **sz) * B, width(logs) * B * K
+            # (RMPC's four episode logs also travel up: an instance whose episode has closed leaves its rows untouched)
+            ep_up = width([e for e in logs if e[0] in ("pos_err", "pos_err_norm", "u_cmd", "timestep")]) * B * K \
+                if name == "rmpc" else 0
+            host[name] = {"steps": K, "rounds": 3,
+                          "logging": {"wall_s": float(np.median(t["logging"])), "wall_min_s": float(np.min(t["logging"])),
+                                      "bytes_up": inputs * B + sb + ep_up, "bytes_down": sb + lb},
+                          "metrics_only": {"wall_s": float(np.median(t["metrics_only"])),
+                                           "wall_min_s": float(np.min(t["metrics_only"])), "bytes_up": inputs * B + sb,
+                                           "bytes_down": sb}}
+        row["host_entries"] = host
+    return row
+
+
+ROWS = {"PMPC": pmpc_row, "RMPC": rmpc_row, "LMPC": lmpc_row, "COLLECT": collect_row, "CROSS": cross_row}
 results = []
 if os.path.exists(out_path):        # the rows of the controllers that this run leaves out
     with open(out_path) as f:
