@@ -297,6 +297,14 @@ inline dartmpc::CriticWeights critic_weights(const float* c) {
 // dart_mpc_abi.hip
 int policy_args(const dart_lmpc_policy_config* c, int B, const float* w, dartmpc::PolicyArgs& a);
 int settle_pending(dart_mpc_handle* h);
+// dart_lmpc_policy_solve_batch_dev with the learner block size of a population: instance b steps with the weights of
+// learner b / learner_B, `weights` being [learners][39748]; 0: one policy for all (the public entry)
+int lmpc_policy_solve_dev(dart_mpc_handle* h, const dart_lmpc_policy_config* pcfg, int B, int learner_B,
+                          const float* weights, const double* state, const double* u_prev, const double* target,
+                          const double* current_k, double* obs_mean, double* obs_M2, int32_t* obs_count, float* history,
+                          int32_t* timestep, const float* noise, double* model_params, float* action_out,
+                          const double* prm, const double* w_warm, double* u0, double* f, double* w_out,
+                          int32_t* status, int32_t* iters, void* stream);
 
 // Device arena of the host rollout / collection / training entries: arrays laid out 256-byte aligned in the handle's
 // roll_buf, copied up / down in part
@@ -379,6 +387,8 @@ struct LmpcStagePlan {
     size_t B, nw, log_rows, r0, r1;               // the step logs' rows and those that travel
     size_t rec_rows, q0, q1;                      // the records' (collect: both ways; train: down only)
     size_t reset_rows;
+    size_t learners;                              // a population's host entry: B = learners * B each, the nets and the
+                                                  // training arrays stacked per learner; 0: one learner
 };
 
 // true if a pointer of `group` (kind kAnyState: its state and log arrays; kRec / kPool: those) is null
@@ -389,9 +399,12 @@ void lmpc_stage(RollStage& S, const dart_lmpc_train_buffers& host, const LmpcSta
 void lmpc_bind(const RollStage& S, const dart_mpc_handle* h, const int idx[kLmpcArrays], dart_lmpc_train_buffers& dev);
 
 // The closed loop of dart_lmpc_rollout_dev (collect false: no experience launches, weights may be null, rcfg unused)
-// and of dart_lmpc_collect_dev on device pointers, the handle's lock held: every check, then the launches
+// and of dart_lmpc_collect_dev on device pointers, the handle's lock held: every check, then the launches.
+// learner_B > 0 (a population's collection): instance b acts and is valued with the nets of learner b / learner_B
+// (weights [learners][39748], critic [learners][kPopCriticStride]); 0: one policy for all
 int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                      const dart_lmpc_reward_config* rcfg, bool collect, int B, int k0, int steps, int log_rows,
-                     int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise, void* stream);
+                     int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise, void* stream,
+                     int learner_B = 0);
 
 #pragma GCC visibility pop

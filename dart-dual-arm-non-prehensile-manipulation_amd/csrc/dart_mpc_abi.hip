@@ -657,7 +657,7 @@ int policy_args(const dart_lmpc_policy_config* c, int B, const float* w, dartmpc
     if (!c || B < 0 || !w || c->update_every < 1 || !(c->k_max > c->min_k) || !(c->min_k > 0.0)) return DART_MPC_EINVAL;
     a.B = B;
     a.w = policy_weights(w);
-    a.update_every = c->update_every;
+    a.update_every = c->update_every; a.learner_B = 0;
     a.max_delta = c->max_delta; a.k_max = c->k_max; a.min_k = c->min_k; a.k_ceiling_margin = c->k_ceiling_margin;
     a.action_scale = c->action_scale; a.smooth_alpha = c->smooth_alpha;
     a.log_std_min = c->log_std_min; a.log_std_max = c->log_std_max;
@@ -729,7 +729,19 @@ int dart_lmpc_policy_solve_batch_dev(dart_mpc_handle* h, const dart_lmpc_policy_
                                      double* model_params, float* action_out, const double* prm, const double* w_warm,
                                      double* u0, double* f, double* w_out, int32_t* status, int32_t* iters,
                                      void* stream) {
+    return lmpc_policy_solve_dev(h, pcfg, B, 0, weights, state, u_prev, target, current_k, obs_mean, obs_M2, obs_count,
+                                 history, timestep, noise, model_params, action_out, prm, w_warm, u0, f, w_out, status,
+                                 iters, stream);
+}
+
+int lmpc_policy_solve_dev(dart_mpc_handle* h, const dart_lmpc_policy_config* pcfg, int B, int learner_B,
+                          const float* weights, const double* state, const double* u_prev, const double* target,
+                          const double* current_k, double* obs_mean, double* obs_M2, int32_t* obs_count, float* history,
+                          int32_t* timestep, const float* noise, double* model_params, float* action_out,
+                          const double* prm, const double* w_warm, double* u0, double* f, double* w_out,
+                          int32_t* status, int32_t* iters, void* stream) {
     DART_ENTER(h, DART_MPC_LMPC);
+    if (learner_B < 0) return fail(h, DART_MPC_EINVAL, "negative learner block size");
     dartmpc::LmpcArgs a;
     if (int rc = policy_solve_check(h, pcfg, B, B, weights, a.pol,
                                     {state, u_prev, target, current_k, obs_mean, obs_M2, obs_count, history, timestep,
@@ -740,6 +752,7 @@ int dart_lmpc_policy_solve_batch_dev(dart_mpc_handle* h, const dart_lmpc_policy_
     a.pol.state = state; a.pol.target = target; a.pol.control = u_prev; a.pol.current_k = current_k;
     a.pol.obs_mean = obs_mean; a.pol.obs_M2 = obs_M2; a.pol.obs_count = obs_count; a.pol.history = history;
     a.pol.timestep = timestep; a.pol.noise = noise; a.pol.model_params = model_params; a.pol.action_out = action_out;
+    a.pol.learner_B = learner_B;
     a.fuse_policy = 1;
     if (int rc = lmpc_cfg_args(h, B, stream_of(h, stream), a)) return rc;
     a.state = state; a.u_prev = u_prev; a.pvec = nullptr; a.target = target; a.prm = prm; a.w_warm = w_warm;

@@ -364,7 +364,10 @@ void lmpc_stage(RollStage& S, const dart_lmpc_train_buffers& host, const LmpcSta
         if ((a.group == kPolicy && !m.policy) || (a.group == kCollect && !m.collect) || (a.group == kTrain && !m.train))
             continue;
         const void* p = member(host, a);
-        const size_t call = (size_t)a.width * a.size;                                    // [width]
+        // [width]; a population's: [learners][width], the critics kPopCriticStride apart
+        const bool is_critic = a.member == offsetof(dart_lmpc_train_buffers, critic);
+        const size_t call = m.learners ? m.learners * (is_critic ? dartmpc::kPopCriticStride : (size_t)a.width) * a.size
+                                       : (size_t)a.width * a.size;
         const size_t row = (a.width < 0 ? m.nw : (size_t)a.width) * a.size * m.B;       // [B][width]
         switch (a.kind) {
         case kUp: idx[i] = S.add(p, row, false); break;
@@ -421,7 +424,7 @@ int experience_cfg(dart_mpc_handle* h, const dart_lmpc_policy_config* pcfg, cons
     if (r->record_every < 1 || !(r->sigma_pos > 0.0) || !(r->sigma_vel > 0.0))
         return fail(h, DART_MPC_EINVAL, "reward config: record_every >= 1, sigma_pos > 0, sigma_vel > 0");
     if (rec_rows < 0 || reset_rows < 0) return fail(h, DART_MPC_EINVAL, "negative rec_rows or reset_rows");
-    a.B = B; a.rec_rows = rec_rows; a.reset_rows = reset_rows;
+    a.B = B; a.rec_rows = rec_rows; a.reset_rows = reset_rows; a.learner_B = 0;
     a.w = pa.w;
     a.c = critic_weights(critic);
     a.r.sigma_pos = r->sigma_pos; a.r.sigma_vel = r->sigma_vel; a.r.w_pos = r->w_pos; a.r.w_vel = r->w_vel;
@@ -502,11 +505,14 @@ int dart_lmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
 
 int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                      const dart_lmpc_reward_config* rcfg, bool collect, int B, int k0, int steps, int log_rows,
-                     int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise, void* stream) {
+                     int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise, void* stream,
+                     int learner_B) {
     dartmpc::ExperienceArgs ea;
     if (int rc = lmpc_loop_check(h, plant, pcfg, rcfg, B, k0, steps, log_rows, rec_rows, reset_rows, p,
                                  collect ? &ea : nullptr))
         return rc;
+    if (learner_B < 0) return fail(h, DART_MPC_EINVAL, "negative learner block size");
+    ea.learner_B = learner_B;
     if (B == 0 || steps == 0) return DART_MPC_OK;
     HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
     LmpcLoopScratch L;
@@ -534,11 +540,10 @@ int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const d
         double* w_out = (in_place || (j == steps - 1 && j > 0)) ? p.w : L.wbuf[j & 1];
         int rc;
         if (p.weights)       // (step k's draws are row k of the noise)
-            rc = dart_lmpc_policy_solve_batch_dev(h, pcfg, B, p.weights, L.state, p.u_prev, p.target, p.current_k,
-                                                  p.obs_mean, p.obs_M2, p.obs_count, p.history, p.timestep,
-                                                  noise ? noise + ((size_t)k0 + j) * B * kAct : L.zero_noise,
-                                                  p.model_params, action, p.prm, w_in, L.u0, L.f, w_out, L.status,
-                                                  L.iters, s);
+            rc = lmpc_policy_solve_dev(h, pcfg, B, learner_B, p.weights, L.state, p.u_prev, p.target, p.current_k,
+                                       p.obs_mean, p.obs_M2, p.obs_count, p.history, p.timestep,
+                                       noise ? noise + ((size_t)k0 + j) * B * kAct : L.zero_noise, p.model_params,
+                                       action, p.prm, w_in, L.u0, L.f, w_out, L.status, L.iters, s);
         else
             rc = dart_lmpc_solve_batch_dev(h, B, L.state, p.u_prev, p.model_params, p.target, p.prm, w_in, L.u0, L.f,
                                            w_out, L.status, L.iters, s);

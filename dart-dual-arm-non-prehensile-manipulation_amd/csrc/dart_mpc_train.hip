@@ -56,20 +56,32 @@ bool ppo_cfg_ok(const dart_lmpc_ppo_config* c) {
            c->beta2 < 1.0 && c->adam_eps >= 0.0 && c->max_grad_norm >= 0.0 && c->log_std_min <= c->log_std_max;
 }
 
+// A population's form of the three launches below: P learners, whose workspaces lie ws_stride bytes and whose rows of
+// the permutations idx_stride entries apart (lmpc_ppo.h); P = 0: the single launch
+struct PpoPop {
+    int P = 0;
+    size_t ws_stride = 0, idx_stride = 0;
+};
+
 // the launches of the PPO entries; ws is laid out for (n, mb) with M <= mb
 hipError_t ppo_launch_prepare(int n, long long total, const int32_t* sample, const double* adv, const double* ret,
-                              float* adv_out, float* ret_out, char* ws, int mb, hipStream_t s) {
+                              float* adv_out, float* ret_out, char* ws, int mb, hipStream_t s, PpoPop pop = {}) {
     const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
     dartmpc::PpoPrepareArgs a;
     a.n = n; a.rec_total = total; a.sample = sample; a.adv = adv; a.ret = ret;
     a.adv_n = reinterpret_cast<float*>(ws + L.adv_n); a.ret_n = reinterpret_cast<float*>(ws + L.ret_n);
     a.adv_out = adv_out; a.ret_out = ret_out;
+    if (pop.P > 0) {
+        const dartmpc::PpoPreparePopArgs q{a, pop.P, pop.ws_stride};
+        return dartmpc_launch_ppo_prepare_pop(&q, s);
+    }
     return dartmpc_launch_ppo_prepare(&a, s);
 }
 
 hipError_t ppo_launch_grad(const dart_lmpc_ppo_config* c, int n, long long total, int M, const int32_t* sample,
                            const int32_t* idx, const float* rec_obs, const float* rec_action, const float* rec_logp,
-                           const float* weights, const float* critic, char* ws, int mb, hipStream_t s) {
+                           const float* weights, const float* critic, char* ws, int mb, hipStream_t s,
+                           PpoPop pop = {}) {
     const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
     dartmpc::PpoGradArgs a;
     a.n = n; a.M = M; a.rec_total = total;
@@ -80,6 +92,10 @@ hipError_t ppo_launch_grad(const dart_lmpc_ppo_config* c, int n, long long total
     a.adv_n = reinterpret_cast<const float*>(ws + L.adv_n); a.ret_n = reinterpret_cast<const float*>(ws + L.ret_n);
     a.actor = weights; a.critic = critic;
     a.part = reinterpret_cast<float*>(ws + L.part); a.loss_part = reinterpret_cast<float*>(ws + L.loss_part);
+    if (pop.P > 0) {
+        const dartmpc::PpoGradPopArgs q{a, pop.P, pop.ws_stride, pop.idx_stride};
+        return dartmpc_launch_ppo_grad_pop(&q, s);
+    }
     return dartmpc_launch_ppo_grad(&a, s);
 }
 
@@ -87,7 +103,7 @@ hipError_t ppo_launch_grad(const dart_lmpc_ppo_config* c, int n, long long total
 hipError_t ppo_launch_apply(const dart_lmpc_ppo_config* c, int n, int M, bool from_tiles, const float* grad,
                             const float* terms_in, bool do_step, float* grad_out, float* terms_out, float* weights,
                             float* critic, float* adam, int32_t* adam_step, double* stats, float* step_log,
-                            int step_in_call, char* ws, int mb, hipStream_t s) {
+                            int step_in_call, char* ws, int mb, hipStream_t s, PpoPop pop = {}) {
     const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
     dartmpc::PpoApplyArgs a;
     a.tiles = from_tiles ? (M + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile : 1;
@@ -102,6 +118,10 @@ hipError_t ppo_launch_apply(const dart_lmpc_ppo_config* c, int n, int M, bool fr
     a.terms = terms_out ? terms_out : reinterpret_cast<float*>(ws + L.terms);
     a.actor = weights; a.critic = critic; a.adam = adam; a.adam_step = adam_step;
     a.step_log = step_log; a.stat_sum = reinterpret_cast<double*>(ws + L.stat_sum); a.stats = stats;
+    if (pop.P > 0) {
+        const dartmpc::PpoApplyPopArgs q{a, pop.P, pop.ws_stride};
+        return dartmpc_launch_ppo_apply_pop(&q, s);
+    }
     return dartmpc_launch_ppo_apply(&a, s);
 }
 
@@ -305,7 +325,7 @@ bool noise_shape_ok(int iteration, int steps, int B) {
 int mean_update_args(const dart_lmpc_policy_config* cfg, int B, const float* weights, dartmpc::MeanUpdateArgs& a) {
     dartmpc::PolicyArgs pa;
     if (policy_args(cfg, B, weights, pa) != DART_MPC_OK) return DART_MPC_EINVAL;
-    a.B = B; a.w = pa.w;
+    a.B = B; a.learner_B = 0; a.w = pa.w;
     a.max_delta = pa.max_delta; a.k_max = pa.k_max; a.min_k = pa.min_k; a.k_ceiling_margin = pa.k_ceiling_margin;
     a.action_scale = pa.action_scale; a.smooth_alpha = pa.smooth_alpha;
     return DART_MPC_OK;
@@ -730,16 +750,34 @@ int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, cons
     return dart_lmpc_train_global_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, nullptr, stream);
 }
 
-// (g == nullptr: dart_lmpc_train)
-int dart_lmpc_train_global(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
-                           const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
-                           const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
-                           const dart_lmpc_global_buffer* g, void* stream) {
+namespace {
+
+// the checks of a population's shape: P learners of B instances each, R records per instance
+int pop_check(dart_mpc_handle* h, const dart_lmpc_reward_config* rcfg, const dart_lmpc_train_config* cfg, int P,
+              const uint64_t* seeds, int B) {
+    if (P < 1 || P > DART_LMPC_POP_MAX) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+    if (!seeds) return fail(h, DART_MPC_EINVAL, "population: null seeds");
+    if ((long long)P * B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "population: P * B larger than B_max");
+    if ((long long)(cfg->steps / rcfg->record_every) * P * B > 0x7fffffffLL)
+        return fail(h, DART_MPC_EINVAL, "too many samples");
+    return DART_MPC_OK;
+}
+
+// The host form of the training entries.  P = 0: dart_lmpc_train_global (g == nullptr: dart_lmpc_train); P >= 1:
+// dart_lmpc_train_pop on P * B instances, the nets and the training arrays stacked per learner (g == nullptr)
+int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+               const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg,
+               int P, const uint64_t* seeds, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+               const dart_lmpc_global_buffer* g, void* stream) {
     DART_ENTER(h, -1);
     if (int rc = train_check(h, rcfg, ppo, cfg, B, p, false)) return rc;
     if (g)
         if (int rc = global_check(h, g, cfg->steps / rcfg->record_every * B, false)) return rc;
     if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, "handle is not an LMPC handle");
+    if (P > 0)
+        if (int rc = pop_check(h, rcfg, cfg, P, seeds, B)) return rc;
+    const int learner_B = B;
+    B *= P > 0 ? P : 1;                            // every instance from here on
     if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
     if (reset_rows < 0) return fail(h, DART_MPC_EINVAL, "negative reset_rows");
     if (lmpc_null(*p, kLoop) || lmpc_null(*p, kPolicy) || lmpc_null(*p, kCollect) || lmpc_null(*p, kCollect, kRec))
@@ -758,15 +796,16 @@ int dart_lmpc_train_global(dart_mpc_handle* h, const dart_plant_config* plant, c
     LmpcStagePlan m{};
     m.policy = m.collect = m.train = true;
     m.B = nB; m.nw = (size_t)dart_lmpc_nw(h->cfg.N); m.log_rows = m.r1 = K; m.rec_rows = m.q1 = R;
-    m.reset_rows = (size_t)reset_rows;
+    m.reset_rows = (size_t)reset_rows; m.learners = (size_t)P;
     RollStage S;
     int idx[kLmpcArrays];
     lmpc_stage(S, *p, m, idx);
-    const int i_log = S.add_log(p->train_log, (size_t)cfg->iterations, dartmpc::kTrainLogCols * D, 0,
-                                (size_t)cfg->iterations, false);
+    const size_t log_rows = (size_t)cfg->iterations * (size_t)(P > 0 ? P : 1);
+    const int i_log = S.add_log(p->train_log, log_rows, dartmpc::kTrainLogCols * D, 0, log_rows, false);
     // the workspace: a block of the arena that does not travel
-    const size_t ws_bytes = dartmpc::train_workspace(B, (int)K, rcfg->record_every, ppo->epochs,
-                                                     ppo->mini_batch_size).bytes;
+    const size_t ws_bytes =
+        P > 0 ? dartmpc::train_pop_workspace(P, learner_B, (int)K, rcfg->record_every, ppo->epochs, ppo->mini_batch_size).bytes
+              : dartmpc::train_workspace(B, (int)K, rcfg->record_every, ppo->epochs, ppo->mini_batch_size).bytes;
     const int i_ws = S.add_log(nullptr, 1, ws_bytes, 0, 0, false);
     // the global buffer: blocks of the arena whose held rows travel by hand (those held at the start go up, those
     // held at the end come down), its log, and its workspace
@@ -799,7 +838,9 @@ int dart_lmpc_train_global(dart_mpc_handle* h, const dart_plant_config* plant, c
             HIPCHK(h, hipMemcpyAsync(S.dev<char>(h, gi[q]), g_host[q], (size_t)g->fill * g_rowbytes[q],
                                      hipMemcpyHostToDevice, s), "copy global buffer");
     }
-    if (int rc = dart_lmpc_train_global_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, &d, g ? &gd : nullptr, s)) {
+    if (int rc = P > 0 ? dart_lmpc_train_pop_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, learner_B, reset_rows, &d, s)
+                       : dart_lmpc_train_global_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, &d,
+                                                    g ? &gd : nullptr, s)) {
         (void)hipStreamSynchronize(s);
         return rc;
     }
@@ -812,6 +853,147 @@ int dart_lmpc_train_global(dart_mpc_handle* h, const dart_plant_config* plant, c
     }
     HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
     return DART_MPC_OK;
+}
+
+}  // namespace
+
+// ---- a population of P learners in the launches of one (lmpc_train.h, lmpc_ppo.h) --------------------------------
+
+static_assert(DART_LMPC_POP_MAX == dartmpc::kPopMax && DART_LMPC_POP_CRITIC_STRIDE == dartmpc::kPopCriticStride,
+              "the header's population constants are the kernels'");
+
+size_t dart_lmpc_train_pop_workspace_bytes(int P, int B, int K, int record_every, int epochs, int mini_batch_size) {
+    if (P < 1 || P > DART_LMPC_POP_MAX) return 0;
+    if (dart_lmpc_train_workspace_bytes(B, K, record_every, epochs, mini_batch_size) == 0) return 0;
+    if ((long long)(K / record_every) * P * B > 0x7fffffffLL) return 0;
+    return dartmpc::train_pop_workspace(P, B, K, record_every, epochs, mini_batch_size).bytes;
+}
+
+// dart_lmpc_train_dev's launch sequence, each step issued once for all P learners
+int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                            const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                            const dart_lmpc_train_config* cfg, int P, const uint64_t* seeds, int B, int reset_rows,
+                            const dart_lmpc_train_buffers* p, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = train_check(h, rcfg, ppo, cfg, B, p, true)) return rc;
+    if (int rc = pop_check(h, rcfg, cfg, P, seeds, B)) return rc;
+    if (!aligned16(p->weights) || !aligned16(p->critic))
+        return fail(h, DART_MPC_EINVAL, "policy and critic weights must be 16-byte aligned");
+    const int NI = P * B;                           // instances, learner-major
+    const int K = cfg->steps, R = K / rcfg->record_every, n = R * B, mb = ppo->mini_batch_size;
+    const long long rec_total = (long long)R * NI;
+    void* s = stream_of(h, stream);
+    auto collect = [&](int steps, const float* noise) {
+        return lmpc_closed_loop(h, plant, pcfg, rcfg, true, NI, 0, steps, K, R, reset_rows, *p, noise, s, B);
+    };
+    // every check of the collection (configs, null pointers, the handle's variant) before any device work: zero steps
+    if (int rc = collect(0, nullptr)) return rc;
+    dartmpc::MeanUpdateArgs ma;
+    if (mean_update_args(pcfg, NI, p->weights, ma) != DART_MPC_OK) return fail(h, DART_MPC_EINVAL, "bad policy config");
+    if (cfg->iterations == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const dartmpc::TrainPopWorkspace L = dartmpc::train_pop_workspace(P, B, K, rcfg->record_every, ppo->epochs, mb);
+    char* ws = (char*)p->workspace;
+    float* noise = (float*)(ws + L.noise);
+    float* last_value = (float*)(ws + L.last_value);
+    double* adv = (double*)(ws + L.adv);
+    double* ret = (double*)(ws + L.ret);
+    int32_t* sample = (int32_t*)(ws + L.sample);
+    int32_t* perm = (int32_t*)(ws + L.perm);
+    double* stats = (double*)(ws + L.stats);
+    int32_t* ep0 = (int32_t*)(ws + L.ep0);
+    hipStream_t hs = (hipStream_t)s;
+    // the learners' keys travel in the launch arguments: nothing is read from seeds after this loop
+    dartmpc::PopKeys keys{};
+    for (int l = 0; l < P; ++l) {
+        keys.k[l][0] = (uint32_t)(seeds[l] & 0xffffffffu);
+        keys.k[l][1] = (uint32_t)(seeds[l] >> 32);
+    }
+    PpoPop pop;
+    pop.P = P; pop.ws_stride = L.ppo_stride; pop.idx_stride = (size_t)ppo->epochs * n;
+    {
+        dartmpc::PopSampleArgs sa;
+        sa.P = P; sa.B = B; sa.R = R; sa.out = sample;
+        HIPCHK(h, dartmpc_launch_lmpc_pop_sample(&sa, hs), "sample list launch");
+    }
+    for (int j = 0; j < cfg->iterations; ++j) {
+        const int it = cfg->it0 + j;
+        HIPCHK(h, hipMemsetAsync(p->nrec, 0, sizeof(int32_t) * (size_t)NI, hs), "clear nrec");
+        HIPCHK(h, hipMemcpyAsync(ep0, p->episodes, sizeof(int32_t) * (size_t)NI, hipMemcpyDeviceToDevice, hs),
+               "copy episodes");
+        if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(double) * 3 * (size_t)P, hs), "clear stats");
+        {
+            dartmpc::NoisePopArgs na;
+            na.n = (long long)K * B * kAct; na.B = B; na.P = P; na.iteration = (uint32_t)it; na.keys = keys;
+            na.out = noise;
+            HIPCHK(h, dartmpc_launch_lmpc_noise_pop(&na, hs), "noise launch");
+        }
+        if (int rc = collect(K, noise)) return rc;
+        {
+            dartmpc::CriticValuePopArgs va;
+            va.a.n = B; va.a.critic = p->critic; va.a.obs = p->history; va.a.value = last_value; va.P = P;
+            HIPCHK(h, dartmpc_launch_critic_value_pop(&va, hs), "critic value launch");
+        }
+        if (dart_lmpc_gae_dev(NI, R, cfg->gamma, cfg->lam, p->nrec, p->rec_reward, p->rec_value, p->rec_done,
+                              last_value, adv, ret, s) != DART_MPC_OK)
+            return fail(h, DART_MPC_EHIP, "GAE launch");
+        {
+            dartmpc::PermPopArgs pa;
+            pa.a.n = n; pa.a.epochs = ppo->epochs; pa.a.limit = n; pa.a.key0 = pa.a.key1 = 0;
+            pa.a.iteration = (uint32_t)it; pa.a.stream = dartmpc::kStreamPerm; pa.a.perm = perm; pa.a.key_out = nullptr;
+            pa.P = P; pa.keys = keys;
+            HIPCHK(h, dartmpc_launch_lmpc_perms_pop(&pa, hs), "permutation launch");
+        }
+        // dart_lmpc_ppo_update_dev's launches, every learner in each
+        HIPCHK(h, ppo_launch_prepare(n, rec_total, sample, adv, ret, nullptr, nullptr, ws + L.ppo, mb, hs, pop),
+               "PPO prepare launch");
+        int step = 0;
+        for (int ep = 0; ep < ppo->epochs; ++ep) {
+            const int32_t* row = perm + (size_t)ep * n;
+            for (int start = 0; start < n; start += mb, ++step) {
+                const int M = n - start < mb ? n - start : mb;
+                HIPCHK(h, ppo_launch_grad(ppo, n, rec_total, M, sample, row + start, p->rec_obs, p->rec_action,
+                                          p->rec_logp, p->weights, p->critic, ws + L.ppo, mb, hs, pop),
+                       "PPO gradient launch");
+                HIPCHK(h, ppo_launch_apply(ppo, n, M, true, nullptr, nullptr, true, nullptr, nullptr, p->weights,
+                                           p->critic, p->adam, p->adam_step, stats, nullptr, step, ws + L.ppo, mb, hs,
+                                           pop), "PPO apply launch");
+            }
+        }
+        if (cfg->mean_update) {
+            ma.learner_B = B;
+            ma.history = p->history; ma.model_params = p->model_params; ma.current_k = p->current_k;
+            ma.mean_out = nullptr;
+            HIPCHK(h, dartmpc_launch_lmpc_mean_update(&ma, hs), "mean parameter update launch");
+        }
+        dartmpc::TrainLogPopArgs la;
+        la.a.B = B; la.a.K = K; la.a.R = R; la.a.n = n; la.a.iteration = it; la.a.track_best = cfg->track_best ? 1 : 0;
+        la.a.ep0 = ep0; la.a.episodes = p->episodes; la.a.last_return = p->last_return; la.a.nrec = p->nrec;
+        la.a.log_reward = p->log_reward; la.a.log_status = p->log_status; la.a.stats = stats;
+        la.a.actor = p->weights; la.a.critic = p->critic;
+        la.a.row = p->train_log + (size_t)dartmpc::kTrainLogCols * j;
+        la.a.best_return = p->best_return; la.a.best_weights = p->best_weights; la.a.best_iter = p->best_iter;
+        la.P = P; la.row_stride = (long long)dartmpc::kTrainLogCols * cfg->iterations;
+        HIPCHK(h, dartmpc_launch_lmpc_train_log_pop(&la, hs), "training log launch");
+    }
+    return DART_MPC_OK;
+}
+
+// (g == nullptr: dart_lmpc_train)
+int dart_lmpc_train_global(dart_mpc_handle* h,const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                           const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                           const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                           const dart_lmpc_global_buffer* g, void* stream) {
+    return train_host(h, plant, pcfg, rcfg, ppo, cfg, 0, nullptr, B, reset_rows, p, g, stream);
+}
+
+int dart_lmpc_train_pop(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                        const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                        const dart_lmpc_train_config* cfg, int P, const uint64_t* seeds, int B, int reset_rows,
+                        const dart_lmpc_train_buffers* p, void* stream) {
+    DART_ENTER(h, -1);
+    if (P < 1) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+    return train_host(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, B, reset_rows, p, nullptr, stream);
 }
 
 int dart_lmpc_train(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,

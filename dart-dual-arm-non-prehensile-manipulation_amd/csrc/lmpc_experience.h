@@ -43,6 +43,8 @@ constexpr int kDoneMaxSteps = 2;    // max_episode_steps reached (:738-740)
 struct ExperienceArgs {
     int B, k;
     int rec_rows, reset_rows;
+    int learner_B;              // population: instance b reads the nets of learner b / learner_B (the actors kPolicyN
+                                // and the critics kPopCriticStride floats apart); 0: one pair of nets for all
     PolicyWeights w;            // the actor (recomputed: mean) and log_std
     CriticWeights c;
     RewardArgs r;

@@ -36,14 +36,22 @@ struct alignas(16) ExperienceLds {
     float part[2][4][PH];       // layer 1: the four chains of either net before they are combined
 };
 
+// POP: a population's launch (dart_lmpc_train_pop_dev), instance b reads the nets of learner b / learner_B; its own
+// instantiation, so that the single-policy kernel keeps its instructions
+template <bool POP>
 __global__ __launch_bounds__(kWave) void lmpc_experience_kernel(ExperienceArgs a) {
     __shared__ ExperienceLds L;
     const int l = threadIdx.x;
     const int b = blockIdx.x;
     if (b >= a.B) return;                    // block-uniform
     const size_t B = (size_t)a.B;
-    const PolicyWeights& W = a.w;
-    const CriticWeights& C = a.c;
+    PolicyWeights W = a.w;
+    CriticWeights C = a.c;
+    if constexpr (POP) {
+        W = learner_weights(a.w, b, a.learner_B);
+        const size_t o = (size_t)(b / a.learner_B) * kPopCriticStride;
+        C.V1 += o; C.c1 += o; C.V2 += o; C.c2 += o; C.V3 += o; C.c3 += o;
+    }
     const RewardArgs& R = a.r;
 
     // ---- everything this launch both reads and writes, read first (lane-uniform) ----------------------------
@@ -274,7 +282,10 @@ __global__ __launch_bounds__(kGaeThreads) void lmpc_gae_kernel(GaeArgs a) {
 
 extern "C" hipError_t dartmpc_launch_lmpc_experience(const dartmpc::ExperienceArgs* args, hipStream_t stream) {
     if (args->B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(dartmpc::lmpc_experience_kernel, dim3(args->B), dim3(dartmpc::kWave), 0, stream, *args);
+    if (args->learner_B > 0)
+        hipLaunchKernelGGL(dartmpc::lmpc_experience_kernel<true>, dim3(args->B), dim3(dartmpc::kWave), 0, stream, *args);
+    else
+        hipLaunchKernelGGL(dartmpc::lmpc_experience_kernel<false>, dim3(args->B), dim3(dartmpc::kWave), 0, stream, *args);
     return hipGetLastError();
 }
 

@@ -467,7 +467,8 @@ __device__ __forceinline__ double sub_direction(const LmSub& m, const double (*s
 }
 
 // The solve of instance b by the calling wave; returns true when <false> handed the instance over.
-template <bool RESTO>
+// POP: the policy prologue of a population's launch (policy_step_wave<true>)
+template <bool RESTO, bool POP = false>
 __device__ __forceinline__ bool lmpc_solve(const LmpcArgs& a, const int b) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LmShared& SH = *reinterpret_cast<LmShared*>(smem);
@@ -493,7 +494,7 @@ __device__ __forceinline__ bool lmpc_solve(const LmpcArgs& a, const int b) {
     const double* pvec = a.fuse_policy ? (RESTO ? a.pol.model_params + LM_NPV * b : nullptr) : a.pvec + LM_NPV * b;
     if (!RESTO && a.fuse_policy) {
         PolicyLds& PL = *reinterpret_cast<PolicyLds*>(smem + kLmPolicyLdsOff);
-        policy_step_wave(a.pol, b, PL);
+        policy_step_wave<POP>(a.pol, b, PL);
         pvec = PL.pv;
     }
     // IPOPT max_cpu_time (rlmpc2.py:485): the solve's clock starts here; the resumed kernel continues it from
@@ -2073,7 +2074,9 @@ __device__ __noinline__ void lmpc_resto_tail(const int b, const unsigned long lo
 // loop); launched right after it for batches above 32, only flagged instances run: they redo the setup,
 // reload the parked state and continue from the failed iteration.  FUSE (batches of at most 32): the flagged
 // instances continue in lmpc_resto_tail in the same launch.
-template <bool RESTO, bool FUSE = false>
+// POP (fused policy launches of a population, dart_lmpc_train_pop_dev): instance b steps with the weights of
+// learner b / pol.learner_B; instantiations of their own, so that the single-policy kernels keep their instructions.
+template <bool RESTO, bool FUSE = false, bool POP = false>
 __global__ __launch_bounds__(kWave * kWaves) void lmpc_ipm_kernel(LmpcArgs a) {
     // small batches packed onto one XCD (launcher; blocks go round robin over the 8 XCDs)
     if (blockIdx.x % a.pack != (unsigned)(a.xcd % a.pack)) return;
@@ -2081,7 +2084,7 @@ __global__ __launch_bounds__(kWave * kWaves) void lmpc_ipm_kernel(LmpcArgs a) {
     if constexpr (RESTO) {
         if (a.status[b] != kLmNeedResto) return;     // wave-uniform: the instance was solved by <false>
     }
-    const bool handed = lmpc_solve<RESTO>(a, b);
+    const bool handed = lmpc_solve<RESTO, POP>(a, b);
     if constexpr (FUSE) {
         if (__builtin_expect(handed, 0)) lmpc_resto_tail(b, kernarg_addr());
     }
@@ -2174,6 +2177,12 @@ extern "C" hipError_t dartmpc_launch_lmpc(const dartmpc::LmpcArgs* args, hipStre
             if (e == hipSuccess)
                 e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<false, true>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<false, false, true>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<false, true, true>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
             attr_set[dev] = true;
         }
@@ -2182,13 +2191,23 @@ extern "C" hipError_t dartmpc_launch_lmpc(const dartmpc::LmpcArgs* args, hipStre
     a.pack = (a.B <= 32) ? 8 : 1;            // one XCD (and its L2) for the code of a small batch
     // the policy prologue's LDS only when the launch runs it (the opt-in above covers the maximum)
     const size_t lds_launch = a.fuse_policy ? dartmpc::kLmPolicyLdsOff + sizeof(dartmpc::PolicyLds) : sizeof(dartmpc::LmShared);
+    const bool pop = a.fuse_policy && a.pol.learner_B > 0;      // a population's policies in the prologue
     if (a.resto && a.pack == 8 && dartmpc::resto_fuse_enabled()) {   // restoration in the solving wave: one launch
         const size_t lds_r = dartmpc::kLmRestoOff + sizeof(dartmpc::LmResto);
-        hipLaunchKernelGGL((dartmpc::lmpc_ipm_kernel<false, true>), dim3(a.B * a.pack), dim3(dartmpc::kWave),
-                           lds_launch > lds_r ? lds_launch : lds_r, stream, a);
+        const size_t lds_f = lds_launch > lds_r ? lds_launch : lds_r;
+        if (pop)
+            hipLaunchKernelGGL((dartmpc::lmpc_ipm_kernel<false, true, true>), dim3(a.B * a.pack), dim3(dartmpc::kWave),
+                               lds_f, stream, a);
+        else
+            hipLaunchKernelGGL((dartmpc::lmpc_ipm_kernel<false, true>), dim3(a.B * a.pack), dim3(dartmpc::kWave), lds_f,
+                               stream, a);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(dartmpc::lmpc_ipm_kernel<false>, dim3(a.B * a.pack), dim3(dartmpc::kWave), lds_launch, stream, a);
+    if (pop)
+        hipLaunchKernelGGL((dartmpc::lmpc_ipm_kernel<false, false, true>), dim3(a.B * a.pack), dim3(dartmpc::kWave),
+                           lds_launch, stream, a);
+    else
+        hipLaunchKernelGGL(dartmpc::lmpc_ipm_kernel<false>, dim3(a.B * a.pack), dim3(dartmpc::kWave), lds_launch, stream, a);
     // IPOPT's restoration phases for the instances the first launch handed off (the others return at once)
     if (a.resto)
         hipLaunchKernelGGL(dartmpc::lmpc_ipm_kernel<true>, dim3(a.B * a.pack), dim3(dartmpc::kWave),

@@ -38,12 +38,29 @@ struct PolicyArgs {
     double* model_params;      // [B][34]  views["model_params"], in/out
     float* action_out;         // [B][34]  raw action, nullable
     int update_every;
+    int learner_B;             // population training: instance b reads the weights of learner b / learner_B, kPolicyN
+                               // floats apart from w; 0: one policy for all
     double max_delta, k_max, min_k, k_ceiling_margin, action_scale, smooth_alpha, log_std_min, log_std_max;
 };
 
 constexpr int PB = 52;              // base observation length
 constexpr int PH = 64;              // hidden units
 constexpr int PA = 34;              // action / parameter dimension
+constexpr int kPolicyN = PolicyArgs::kHist * PB * PH + PH + PH * PH + PH + PH * PA + 2 * PA;      // 39748 packed weights
+// a population of learners (dart_lmpc_train_pop_dev): at most kPopMax, their actors kPolicyN floats apart and their
+// critics (37569 weights) kPopCriticStride, the next multiple of four, so that every critic is 16-byte aligned
+constexpr int kCriticN = PolicyArgs::kHist * PB * PH + PH + PH * PH + PH + PH + 1;
+constexpr int kPopCriticStride = (kCriticN + 3) & ~3;             // 37572
+constexpr int kPopMax = 32;
+
+// the weights of instance b's learner (wave-uniform: b is)
+__device__ __forceinline__ PolicyWeights learner_weights(PolicyWeights W, int b, int learner_B) {
+    if (learner_B > 0) {
+        const size_t o = (size_t)(b / learner_B) * kPolicyN;
+        W.W1 += o; W.b1 += o; W.W2 += o; W.b2 += o; W.W3 += o; W.b3 += o; W.log_std += o;
+    }
+    return W;
+}
 
 // LDS of one policy step
 struct PolicyLds {
@@ -62,10 +79,14 @@ struct PolicyLds {
 //   action_scale) in fp32 (:742-756), then the EMA and the tanh soft clip of
 //   write_params_to_shm (:606-616) in fp64.
 // On return L.pv holds views["model_params"] as the solver reads it next (:506); ends with a barrier.
+// POP: a population's launch, controller b steps with the weights of learner b / learner_B.  A template argument and
+// not a run-time branch: the fused launch with the run-time form measured 0.13 % above the parent's, outside the
+// 0.03 % spread of its repetitions, so the single-policy kernels keep their instructions.
+template <bool POP = false>
 __device__ __forceinline__ void policy_step_wave(const PolicyArgs& a, int b, PolicyLds& L) {
     const int l = threadIdx.x;
     const int HL = PolicyArgs::kHist;
-    const PolicyWeights& W = a.w;
+    const PolicyWeights W = POP ? learner_weights(a.w, b, a.learner_B) : a.w;
 
     // ---- base vector, Welford update, normalisation (lanes 0..51) -------------------------
     const int64_t cnt = (int64_t)a.obs_count[b] + 1;

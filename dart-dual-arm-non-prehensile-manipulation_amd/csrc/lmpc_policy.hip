@@ -12,15 +12,19 @@
 
 namespace dartmpc {
 
+template <bool POP>
 __global__ __launch_bounds__(kWave) void lmpc_policy_kernel(PolicyArgs a) {
     __shared__ PolicyLds L;
-    policy_step_wave(a, blockIdx.x, L);
+    policy_step_wave<POP>(a, blockIdx.x, L);
 }
 
 }  // namespace dartmpc
 
 extern "C" hipError_t dartmpc_launch_policy(const dartmpc::PolicyArgs* args, hipStream_t stream) {
     if (args->B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(dartmpc::lmpc_policy_kernel, dim3(args->B), dim3(dartmpc::kWave), 0, stream, *args);
+    if (args->learner_B > 0)
+        hipLaunchKernelGGL(dartmpc::lmpc_policy_kernel<true>, dim3(args->B), dim3(dartmpc::kWave), 0, stream, *args);
+    else
+        hipLaunchKernelGGL(dartmpc::lmpc_policy_kernel<false>, dim3(args->B), dim3(dartmpc::kWave), 0, stream, *args);
     return hipGetLastError();
 }

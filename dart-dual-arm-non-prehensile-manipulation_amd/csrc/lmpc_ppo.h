@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lmpc_policy.h"
+
 namespace dartmpc {
 
 constexpr int kPpoObs = 520, kPpoHid = 64, kPpoAct = 34;
@@ -24,6 +26,7 @@ constexpr int kPpoParams = kPpoActorN + kPpoCriticN;              // 39748 + 375
 constexpr int kPpoTile = 16;                                      // samples per workgroup of the gradient kernel
 constexpr int kPpoMaxBatch = 1024;                                // mini-batch limit (64 tiles)
 constexpr int kPpoPartStride = (kPpoParams + 3) & ~3;             // one tile's partial gradient, 16-byte multiple
+static_assert(kPpoActorN == kPolicyN && kPpoCriticN == kCriticN, "one pair of nets");
 
 // Workspace layout (bytes from the base, every block 256-byte aligned) for n samples and mini-batches of up to mb.
 // The blocks of fixed size come first and the tile partials last, so that every offset but `bytes` depends on n
@@ -108,8 +111,38 @@ struct CriticValueArgs {
     float* value;               // [n]
 };
 
+// ---- a population of P learners in one launch (dart_lmpc_train_pop_dev) ------------------------------------------
+// `a` holds learner 0's arguments.  Learner l works on them moved by l strides: its sample list [P][n], its slice of
+// the permutations (idx_stride entries apart), its workspace (ws_stride bytes apart, a ppo_workspace each), its
+// actor ([P][39748]), critic ([P][kPopCriticStride]), Adam state ([P][2][77317], adam_step [P]) and running means
+// (stats [P][3]).  adv, ret and the record arrays are shared: the sample lists address them.  Every learner has the
+// same n, so the same M in every step.
+struct PpoPreparePopArgs {      // one workgroup per learner
+    PpoPrepareArgs a;           // adv_out, ret_out: null
+    int P;
+    size_t ws_stride;
+};
+struct PpoGradPopArgs {         // grid (tiles, 2, P)
+    PpoGradArgs a;
+    int P;
+    size_t ws_stride, idx_stride;
+};
+struct PpoApplyPopArgs {        // one workgroup per learner
+    PpoApplyArgs a;             // terms_in, step_log: null
+    int P;
+    size_t ws_stride;
+};
+struct CriticValuePopArgs {     // grid (tiles of a.n, P): learner l's critic on rows l a.n .. (l + 1) a.n - 1
+    CriticValueArgs a;
+    int P;
+};
+
 }  // namespace dartmpc
 
+extern "C" hipError_t dartmpc_launch_ppo_prepare_pop(const dartmpc::PpoPreparePopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_ppo_grad_pop(const dartmpc::PpoGradPopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_ppo_apply_pop(const dartmpc::PpoApplyPopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_critic_value_pop(const dartmpc::CriticValuePopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_ppo_prepare(const dartmpc::PpoPrepareArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_ppo_grad(const dartmpc::PpoGradArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_ppo_apply(const dartmpc::PpoApplyArgs* args, hipStream_t stream);

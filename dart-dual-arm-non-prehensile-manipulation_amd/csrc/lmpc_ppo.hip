@@ -6,6 +6,9 @@
 // ppo_apply_kernel     once per mini-batch, one workgroup: sums the partials in tile order, takes the L2 norm with
 //                      a fixed tree, clips as clip_grad_norm_ does and applies torch.optim.Adam in place
 // critic_value_kernel  value_net on [n][520] observations (the bootstrap value of :776-779)
+// *_pop_kernel         the four above for a population of P learners in one launch (dart_lmpc_train_pop_dev): the
+//                      learner is a grid coordinate, the body is the single kernel's on arguments moved to that
+//                      learner's sample list, permutation rows, nets, Adam state and workspace (lmpc_ppo.h)
 //
 // Everything is fp32 as the reference's torch nets are, except the statistics of the normalisation, the sum of
 // squares of the gradient norm, and the running sums of the actor's forward layers and of its log-probability
@@ -147,7 +150,9 @@ __device__ inline void backward(PpoLds& L, const float* __restrict__ w, float* _
     weight_grad<kPpoHid>(kPpoObs, L.Xt, L.D1t, gp + oW1, gp + ob1);
 }
 
-__global__ __launch_bounds__(kGradThreads) void ppo_grad_kernel(PpoGradArgs a) {
+// The bodies of the kernels take their arguments by reference: the single launches pass their own, a population's
+// launches (the *_pop_kernel forms below) a copy moved to the block's learner.
+__device__ __forceinline__ void ppo_grad_body(const PpoGradArgs& a) {
     __shared__ PpoLds L;
     const int t = threadIdx.x, tile = blockIdx.x;
     const bool is_critic = blockIdx.y == 1;
@@ -269,7 +274,25 @@ __device__ inline double block_sum(double v, double* red) {
     return red[0];
 }
 
-__global__ __launch_bounds__(kOneWg) void ppo_prepare_kernel(PpoPrepareArgs a) {
+__global__ __launch_bounds__(kGradThreads) void ppo_grad_kernel(PpoGradArgs a) { ppo_grad_body(a); }
+
+// p + bytes
+template <class T> __device__ __forceinline__ T* moved(T* p, size_t bytes) {
+    return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes) : p;
+}
+
+// grid (tiles, 2, P): learner z on its sample list, its slice of the permutations, its nets and its workspace
+__global__ __launch_bounds__(kGradThreads) void ppo_grad_pop_kernel(PpoGradPopArgs p) {
+    PpoGradArgs a = p.a;
+    const size_t l = blockIdx.z, ws = l * p.ws_stride;
+    a.sample += l * (size_t)a.n; a.idx += l * p.idx_stride;
+    a.adv_n = moved(a.adv_n, ws); a.ret_n = moved(a.ret_n, ws);
+    a.actor += l * kPpoActorN; a.critic += l * kPopCriticStride;
+    a.part = moved(a.part, ws); a.loss_part = moved(a.loss_part, ws);
+    ppo_grad_body(a);
+}
+
+__device__ __forceinline__ void ppo_prepare_body(const PpoPrepareArgs& a) {
     __shared__ double red[kOneWg];
     const int t = threadIdx.x;
     auto at = [&](const double* v, int i) {
@@ -302,7 +325,18 @@ __global__ __launch_bounds__(kOneWg) void ppo_prepare_kernel(PpoPrepareArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kOneWg) void ppo_apply_kernel(PpoApplyArgs a) {
+__global__ __launch_bounds__(kOneWg) void ppo_prepare_kernel(PpoPrepareArgs a) { ppo_prepare_body(a); }
+
+// one workgroup per learner: the statistics over its n samples, in the single kernel's order
+__global__ __launch_bounds__(kOneWg) void ppo_prepare_pop_kernel(PpoPreparePopArgs p) {
+    PpoPrepareArgs a = p.a;
+    const size_t l = blockIdx.x, ws = l * p.ws_stride;
+    a.sample += l * (size_t)a.n;
+    a.adv_n = moved(a.adv_n, ws); a.ret_n = moved(a.ret_n, ws);
+    ppo_prepare_body(a);
+}
+
+__device__ __forceinline__ void ppo_apply_body(const PpoApplyArgs& a) {
     __shared__ double red[kOneWg];
     __shared__ float sh[4];
     const int t = threadIdx.x;
@@ -388,7 +422,21 @@ __global__ __launch_bounds__(kOneWg) void ppo_apply_kernel(PpoApplyArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kGradThreads) void critic_value_kernel(CriticValueArgs a) {
+__global__ __launch_bounds__(kOneWg) void ppo_apply_kernel(PpoApplyArgs a) { ppo_apply_body(a); }
+
+// one workgroup per learner: its partials, its nets, its Adam state, its running means
+__global__ __launch_bounds__(kOneWg) void ppo_apply_pop_kernel(PpoApplyPopArgs p) {
+    PpoApplyArgs a = p.a;
+    const size_t l = blockIdx.x, ws = l * p.ws_stride;
+    a.part = moved(a.part, ws); a.loss_part = moved(a.loss_part, ws);
+    a.grad = moved(a.grad, ws); a.terms = moved(a.terms, ws); a.stat_sum = moved(a.stat_sum, ws);
+    a.actor += l * kPpoActorN; a.critic += l * kPopCriticStride;
+    a.adam += l * 2 * (size_t)kPpoParams; a.adam_step += l;
+    if (a.stats) a.stats += 3 * l;
+    ppo_apply_body(a);
+}
+
+__device__ __forceinline__ void critic_value_body(const CriticValueArgs& a) {
     __shared__ PpoLds L;
     const int t = threadIdx.x, first = blockIdx.x * kPpoTile;
     if (first >= a.n) return;                               // block-uniform
@@ -398,6 +446,17 @@ __global__ __launch_bounds__(kGradThreads) void critic_value_kernel(CriticValueA
     __syncthreads();
     forward<1, float>(L, a.critic);
     if (t < kPpoTile && first + t < a.n) a.value[first + t] = L.Ot[0][t];
+}
+
+__global__ __launch_bounds__(kGradThreads) void critic_value_kernel(CriticValueArgs a) { critic_value_body(a); }
+
+// grid (tiles of a.n, P): learner y's critic on its a.n observations (a sample's value does not depend on its tile)
+__global__ __launch_bounds__(kGradThreads) void critic_value_pop_kernel(CriticValuePopArgs p) {
+    CriticValueArgs a = p.a;
+    const size_t l = blockIdx.y;
+    a.critic += l * kPopCriticStride;
+    a.obs += l * (size_t)a.n * kPpoObs; a.value += l * (size_t)a.n;
+    critic_value_body(a);
 }
 
 }  // namespace
@@ -427,5 +486,35 @@ extern "C" hipError_t dartmpc_launch_critic_value(const dartmpc::CriticValueArgs
     if (args->n <= 0) return hipSuccess;
     const int blocks = (args->n + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile;
     hipLaunchKernelGGL(dartmpc::critic_value_kernel, dim3(blocks), dim3(dartmpc::kGradThreads), 0, stream, *args);
+    return hipGetLastError();
+}
+
+// ---- a population's launches: every learner in one grid ---------------------------------------------------------
+
+extern "C" hipError_t dartmpc_launch_ppo_prepare_pop(const dartmpc::PpoPreparePopArgs* args, hipStream_t stream) {
+    if (args->a.n <= 0 || args->P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(dartmpc::ppo_prepare_pop_kernel, dim3(args->P), dim3(dartmpc::kOneWg), 0, stream, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_ppo_grad_pop(const dartmpc::PpoGradPopArgs* args, hipStream_t stream) {
+    if (args->a.M <= 0 || args->P <= 0) return hipSuccess;
+    const int tiles = (args->a.M + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile;
+    hipLaunchKernelGGL(dartmpc::ppo_grad_pop_kernel, dim3(tiles, 2, args->P), dim3(dartmpc::kGradThreads), 0, stream,
+                       *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_ppo_apply_pop(const dartmpc::PpoApplyPopArgs* args, hipStream_t stream) {
+    if (args->a.tiles <= 0 || args->P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(dartmpc::ppo_apply_pop_kernel, dim3(args->P), dim3(dartmpc::kOneWg), 0, stream, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_critic_value_pop(const dartmpc::CriticValuePopArgs* args, hipStream_t stream) {
+    if (args->a.n <= 0 || args->P <= 0) return hipSuccess;
+    const int blocks = (args->a.n + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile;
+    hipLaunchKernelGGL(dartmpc::critic_value_pop_kernel, dim3(blocks, args->P), dim3(dartmpc::kGradThreads), 0, stream,
+                       *args);
     return hipGetLastError();
 }

@@ -69,10 +69,39 @@ struct IotaArgs {
     int32_t* out;               // [n] 0 .. n-1
 };
 
+// ---- a population of P learners (dart_lmpc_train_pop_dev): instance i = l B + b, learner-major -------------------
+// the generator keys of the learners travel in the launch arguments
+struct PopKeys { uint32_t k[kPopMax][2]; };
+
+// learner l's draws are those of NoiseArgs for its key: element (k, b, j), flat (k B + b) 34 + j of its generator
+// (n = steps * B * 34 of them), is stored at out[k][l B + b][j]; grid (blocks, P)
+struct NoisePopArgs {
+    long long n;
+    int B, P;
+    uint32_t iteration;
+    PopKeys keys;
+    float* out;                 // [steps][P B][34]
+};
+
+// PermArgs per learner (limit = n, no key_out): perm [P][epochs][n]; grid (ceil(n / 256), epochs, P)
+struct PermPopArgs {
+    PermArgs a;                 // key0, key1 unused
+    int P;
+    PopKeys keys;
+};
+
+// the sample lists [P][n], n = R B: sample_l[r B + b] = r (P B) + l B + b, the flat index of record r of instance
+// l B + b in the stacked record arrays
+struct PopSampleArgs {
+    int P, B, R;
+    int32_t* out;
+};
+
 // the actor's mean on history (no Welford update, no shift, zero noise, timestep untouched), then the logit-space
 // update, the EMA and the soft clip of policy_step_wave, unconditionally; current_k <- model_params
 struct MeanUpdateArgs {
     int B;
+    int learner_B;              // population: instance b reads the actor of learner b / learner_B; 0: one for all
     PolicyWeights w;
     const float* history;       // [B][520]
     double* model_params;       // [B][34] in/out
@@ -137,6 +166,40 @@ struct TrainLogArgs {
     int32_t* best_iter;         // [1]
 };
 
+// one workgroup per learner: TrainLogArgs (learner 0's, B instances each) moved to learner l; log_reward and
+// log_status are the stacked logs [K][P B], of which learner l visits its entries in the single run's flat order
+// i = k B + b, read at [k][l B + b]; train_log is [P][iterations][12] (row_stride = iterations * 12), stats [P][3]
+struct TrainLogPopArgs {
+    TrainLogArgs a;
+    int P;
+    long long row_stride;
+};
+
+// Workspace of dart_lmpc_train_pop_dev (bytes from the base, every block 256-byte aligned): the single run's blocks
+// with P B instances (noise, last_value, adv, ret, ep0), the per-learner sample lists, permutations and statistics,
+// and P workspaces of the update, ppo_stride bytes apart
+struct TrainPopWorkspace {
+    size_t noise, last_value, adv, ret, sample, perm, stats, ep0, ppo, ppo_stride, bytes;
+};
+inline TrainPopWorkspace train_pop_workspace(int P, int B, int K, int record_every, int epochs, int mb) {
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t PB_ = (size_t)P * B, R = (size_t)(K / record_every), n = R * (size_t)B;
+    TrainPopWorkspace w;
+    size_t o = 0;
+    w.noise = o; o += al(sizeof(float) * (size_t)K * PB_ * 34);
+    w.last_value = o; o += al(sizeof(float) * PB_);
+    w.adv = o; o += al(sizeof(double) * R * PB_);
+    w.ret = o; o += al(sizeof(double) * R * PB_);
+    w.sample = o; o += al(sizeof(int32_t) * n * P);
+    w.perm = o; o += al(sizeof(int32_t) * n * P * (size_t)(epochs > 0 ? epochs : 1));
+    w.stats = o; o += al(sizeof(double) * 3 * P);
+    w.ep0 = o; o += al(sizeof(int32_t) * PB_);
+    w.ppo_stride = ppo_workspace((int)n, mb).bytes;
+    w.ppo = o; o += w.ppo_stride * P;
+    w.bytes = o;
+    return w;
+}
+
 // Workspace of dart_lmpc_train_dev (bytes from the base, every block 256-byte aligned)
 struct TrainWorkspace {
     size_t noise, last_value, adv, ret, sample, perm, stats, ep0, ppo, bytes;
@@ -195,6 +258,10 @@ extern "C" hipError_t dartmpc_launch_philox(const dartmpc::PhiloxArgs* args, hip
 extern "C" hipError_t dartmpc_launch_lmpc_noise(const dartmpc::NoiseArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_lmpc_perms(const dartmpc::PermArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_iota(const dartmpc::IotaArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_noise_pop(const dartmpc::NoisePopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_perms_pop(const dartmpc::PermPopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_pop_sample(const dartmpc::PopSampleArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_train_log_pop(const dartmpc::TrainLogPopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_lmpc_mean_update(const dartmpc::MeanUpdateArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_lmpc_train_log(const dartmpc::TrainLogArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_lmpc_gbuf_append(const dartmpc::GbufAppendArgs* args, hipStream_t stream);

@@ -19,6 +19,13 @@
 // lmpc_gae_seq_kernel      compute_gae (:592-599) over the global buffer as one chain (:834): one workgroup, a suffix
 //                          scan of affine maps in tiles of 1024 rows (shuffles in the wave, LDS across the waves)
 // lmpc_global_log_kernel   one row of global_log
+//
+// A population of P learners (dart_lmpc_train_pop_dev; instance i = l B + b) runs in the launches of one:
+// lmpc_noise_pop_kernel / lmpc_perm_pop_kernel take the learner from the grid and its generator key from the launch
+// arguments, lmpc_pop_sample_kernel writes the per-learner sample lists, lmpc_mean_update_kernel<true> reads the actor
+// of learner b / learner_B, and lmpc_train_log_pop_kernel is one workgroup per learner that visits its entries of the
+// stacked logs in the single run's flat order, so that every fp64 sum has the single run's order.  The kernels of
+// one learner are untouched instantiations: the bodies are shared, the arguments moved to the learner.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,11 +52,9 @@ __device__ inline float unit_open(uint32_t r) {     // in (0, 1), exact in fp32
     return ((float)(r >> 9) + 0.5f) * 1.1920928955078125e-7f;
 }
 
-__global__ __launch_bounds__(kRngThreads) void lmpc_noise_kernel(NoiseArgs a) {
-    const long long c = (long long)blockIdx.x * kRngThreads + threadIdx.x;
-    if (4 * c >= a.n) return;
-    const Philox4 r = philox4x32_10((uint32_t)c, a.iteration, kStreamNoise, 0u, a.key0, a.key1);
-    float z[4];
+// the four draws of Philox block c of (key, iteration)
+__device__ __forceinline__ void noise_block(uint32_t c, uint32_t iteration, uint32_t key0, uint32_t key1, float z[4]) {
+    const Philox4 r = philox4x32_10(c, iteration, kStreamNoise, 0u, key0, key1);
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         const float rad = sqrtf(-2.0f * logf(unit_open(r.w[2 * p])));
@@ -58,9 +63,34 @@ __global__ __launch_bounds__(kRngThreads) void lmpc_noise_kernel(NoiseArgs a) {
         z[2 * p] = rad * cs;
         z[2 * p + 1] = rad * sn;
     }
+}
+
+__global__ __launch_bounds__(kRngThreads) void lmpc_noise_kernel(NoiseArgs a) {
+    const long long c = (long long)blockIdx.x * kRngThreads + threadIdx.x;
+    if (4 * c >= a.n) return;
+    float z[4];
+    noise_block((uint32_t)c, a.iteration, a.key0, a.key1, z);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         if (4 * c + j < a.n) a.out[4 * c + j] = z[j];
+}
+
+// grid (blocks, P): learner y's generator; a block's four elements may lie in two instance rows (34 = 4 * 8 + 2)
+__global__ __launch_bounds__(kRngThreads) void lmpc_noise_pop_kernel(NoisePopArgs a) {
+    const long long c = (long long)blockIdx.x * kRngThreads + threadIdx.x;
+    if (4 * c >= a.n) return;
+    const int l = blockIdx.y;
+    float z[4];
+    noise_block((uint32_t)c, a.iteration, a.keys.k[l][0], a.keys.k[l][1], z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long e = 4 * c + j;
+        if (e < a.n) {
+            const long long row = e / PA, k = row / a.B;         // row = k B + b
+            const int col = (int)(e - row * PA), b = (int)(row - k * a.B);
+            a.out[((k * a.P + l) * a.B + b) * PA + col] = z[j];
+        }
+    }
 }
 
 __device__ inline uint32_t perm_key(const PermArgs& a, int i, uint32_t epoch) {
@@ -68,7 +98,7 @@ __device__ inline uint32_t perm_key(const PermArgs& a, int i, uint32_t epoch) {
     return r.w[i & 3];
 }
 
-__global__ __launch_bounds__(kRngThreads) void lmpc_perm_kernel(PermArgs a) {
+__device__ __forceinline__ void perm_body(const PermArgs& a) {
     __shared__ uint32_t tile[kRngThreads];
     const int t = threadIdx.x;
     const int i = blockIdx.x * kRngThreads + t;
@@ -95,6 +125,27 @@ __global__ __launch_bounds__(kRngThreads) void lmpc_perm_kernel(PermArgs a) {
     }
 }
 
+__global__ __launch_bounds__(kRngThreads) void lmpc_perm_kernel(PermArgs a) { perm_body(a); }
+
+// grid (ceil(n / 256), epochs, P): learner z's key, its rows of perm [P][epochs][limit]
+__global__ __launch_bounds__(kRngThreads) void lmpc_perm_pop_kernel(PermPopArgs p) {
+    PermArgs a = p.a;
+    const int l = blockIdx.z;
+    a.key0 = p.keys.k[l][0]; a.key1 = p.keys.k[l][1];
+    a.perm += (size_t)l * a.epochs * a.limit;
+    a.key_out = nullptr;
+    perm_body(a);
+}
+
+// grid (ceil(R B / 256), P)
+__global__ __launch_bounds__(kRngThreads) void lmpc_pop_sample_kernel(PopSampleArgs a) {
+    const int i = blockIdx.x * kRngThreads + threadIdx.x, l = blockIdx.y;
+    const int n = a.R * a.B;
+    if (i >= n) return;
+    const int r = i / a.B, b = i - r * a.B;
+    a.out[(size_t)l * n + i] = (r * a.P + l) * a.B + b;
+}
+
 __global__ __launch_bounds__(kRngThreads) void iota_kernel(IotaArgs a) {
     const int i = blockIdx.x * kRngThreads + threadIdx.x;
     if (i < a.n) a.out[i] = i;
@@ -105,12 +156,15 @@ struct MeanLds {
     float h1[PH], h2[PH];
 };
 
+// POP: instance b reads the actor of learner b / learner_B (its own instantiation: the single-policy kernel keeps
+// its instructions)
+template <bool POP>
 __global__ __launch_bounds__(64) void lmpc_mean_update_kernel(MeanUpdateArgs a) {
     __shared__ MeanLds L;
     const int l = threadIdx.x;
     const int b = blockIdx.x;
     if (b >= a.B) return;                    // block-uniform
-    const PolicyWeights& W = a.w;
+    const PolicyWeights W = POP ? learner_weights(a.w, b, a.learner_B) : a.w;
     const float* hist = a.history + (size_t)kObsN * b;
     for (int e = l; e < kObsN; e += 64) L.obs[e] = hist[e];
     __syncthreads();
@@ -188,7 +242,8 @@ __device__ inline double block_max(double v, double* sh) {
     return sh[0];
 }
 
-__global__ __launch_bounds__(kLogThreads) void lmpc_train_log_kernel(TrainLogArgs a) {
+// ld > 0 (a population): the logs are [K][ld] and this learner's B instances start at column `first`
+__device__ __forceinline__ void train_log_body(const TrainLogArgs& a, const int ld, const int first) {
     __shared__ double sh[kLogThreads];
     __shared__ int take;
     const int t = threadIdx.x;
@@ -205,8 +260,13 @@ __global__ __launch_bounds__(kLogThreads) void lmpc_train_log_kernel(TrainLogArg
     double rew = 0.0, bad = 0.0;
     const long long KB = (long long)a.K * a.B;
     for (long long i = t; i < KB; i += kLogThreads) {
-        rew += a.log_reward[i];
-        bad += a.log_status[i] != 0 ? 1.0 : 0.0;
+        long long at = i;
+        if (ld > 0) {
+            const long long k = i / a.B;
+            at = k * ld + first + (i - k * a.B);
+        }
+        rew += a.log_reward[at];
+        bad += a.log_status[at] != 0 ? 1.0 : 0.0;
     }
     ended = block_sum(ended, sh); nadv = block_sum(nadv, sh); rsum = block_sum(rsum, sh);
     mism = block_sum(mism, sh); rew = block_sum(rew, sh); bad = block_sum(bad, sh);
@@ -236,6 +296,19 @@ __global__ __launch_bounds__(kLogThreads) void lmpc_train_log_kernel(TrainLogArg
         for (int i = t; i < kPpoActorN; i += kLogThreads) a.best_weights[i] = a.actor[i];
         for (int i = t; i < kPpoCriticN; i += kLogThreads) a.best_weights[kPpoActorN + i] = a.critic[i];
     }
+}
+
+__global__ __launch_bounds__(kLogThreads) void lmpc_train_log_kernel(TrainLogArgs a) { train_log_body(a, 0, 0); }
+
+__global__ __launch_bounds__(kLogThreads) void lmpc_train_log_pop_kernel(TrainLogPopArgs p) {
+    TrainLogArgs a = p.a;
+    const size_t l = blockIdx.x, i0 = l * (size_t)a.B;
+    a.ep0 += i0; a.episodes += i0; a.last_return += i0; a.nrec += i0;
+    a.stats += 3 * l;
+    a.actor += l * kPpoActorN; a.critic += l * kPopCriticStride;
+    a.row += l * p.row_stride;
+    a.best_return += l; a.best_weights += l * (size_t)kPpoParams; a.best_iter += l;
+    train_log_body(a, p.P * a.B, (int)i0);
 }
 
 constexpr int kAppendThreads = 128;
@@ -367,7 +440,35 @@ extern "C" hipError_t dartmpc_launch_iota(const IotaArgs* a, hipStream_t s) {
 
 extern "C" hipError_t dartmpc_launch_lmpc_mean_update(const MeanUpdateArgs* a, hipStream_t s) {
     if (a->B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(lmpc_mean_update_kernel, dim3(a->B), dim3(64), 0, s, *a);
+    if (a->learner_B > 0) hipLaunchKernelGGL(lmpc_mean_update_kernel<true>, dim3(a->B), dim3(64), 0, s, *a);
+    else hipLaunchKernelGGL(lmpc_mean_update_kernel<false>, dim3(a->B), dim3(64), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_noise_pop(const NoisePopArgs* a, hipStream_t s) {
+    if (a->n <= 0 || a->P <= 0) return hipSuccess;
+    const long long nblk = (a->n + 3) / 4;
+    hipLaunchKernelGGL(lmpc_noise_pop_kernel, dim3(blocks_of(nblk, kRngThreads), a->P), dim3(kRngThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_perms_pop(const PermPopArgs* a, hipStream_t s) {
+    if (a->a.n <= 0 || a->a.epochs <= 0 || a->P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_perm_pop_kernel, dim3(blocks_of(a->a.n, kRngThreads), a->a.epochs, a->P), dim3(kRngThreads),
+                       0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_pop_sample(const PopSampleArgs* a, hipStream_t s) {
+    if (a->P <= 0 || a->B <= 0 || a->R <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_pop_sample_kernel, dim3(blocks_of((long long)a->R * a->B, kRngThreads), a->P),
+                       dim3(kRngThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_train_log_pop(const TrainLogPopArgs* a, hipStream_t s) {
+    if (a->P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_train_log_pop_kernel, dim3(a->P), dim3(kLogThreads), 0, s, *a);
     return hipGetLastError();
 }
 

@@ -56,6 +56,7 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_lmpc_global_fill_after", "dart_lmpc_global_workspace_bytes", "dart_lmpc_global_append_dev",
            "dart_lmpc_global_append", "dart_lmpc_gae_seq_dev", "dart_lmpc_gae_seq", "dart_lmpc_train_global_dev",
            "dart_lmpc_train_global",
+           "dart_lmpc_train_pop_workspace_bytes", "dart_lmpc_train_pop_dev", "dart_lmpc_train_pop",
            "dart_pmpc_lm_loop_step_dev", "dart_pmpc_lm_rollout_dev", "dart_pmpc_lm_rollout",
            "dart_rmpc_lm_loop_step_dev", "dart_rmpc_lm_rollout_dev", "dart_rmpc_lm_rollout")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
@@ -393,6 +394,13 @@ def lib():
                    L.dart_lmpc_global_fill_after, L.dart_lmpc_global_append_dev, L.dart_lmpc_global_append,
                    L.dart_lmpc_gae_seq_dev, L.dart_lmpc_gae_seq, L.dart_lmpc_train_global_dev,
                    L.dart_lmpc_train_global):
+            fn.restype = ctypes.c_int
+    if hasattr(L, "dart_lmpc_train_pop_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_lmpc_train_pop_workspace_bytes.argtypes = [ci] * 6
+        L.dart_lmpc_train_pop_workspace_bytes.restype = ctypes.c_size_t
+        for fn in (L.dart_lmpc_train_pop_dev, L.dart_lmpc_train_pop):
+            fn.argtypes = [vp] * 6 + [ci, vp, ci, ci, vp, vp]
             fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
@@ -1193,6 +1201,74 @@ class LmpcSolver(Solver):
         if rc != 0:
             self._err(rc, "dart_lmpc_train_global_dev")
 
+    # -- a population of learners in one device-resident iteration (dart_lmpc_train_pop_dev / dart_lmpc_train_pop) ----
+    def train_pop_dev(self, P, seeds, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state, cstate,
+                      logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool=None, plant=None, stream=0):
+        """``train_dev`` for ``P`` independent learners of ``B`` instances each in the same launches
+        (dart_lmpc_train_pop_dev).  Device pointers as in ``train_dev`` with the instances stacked learner-major
+        (instance l B + b: every per-instance array has P B in place of B) and, per learner, ``weights`` [P, 39748],
+        ``critic`` [P, POP_CRITIC_STRIDE], adam [P, 2, 77317], adam_step [P], train_log [P, iterations, 12],
+        best_return [P], best_weights [P, 77317], best_iter [P]; the workspace has ``train_pop_workspace_bytes``.
+        ``seeds`` are P integers (``tcfg.seed`` is ignored); learner l is bit for bit ``train_dev`` on its arrays with
+        seed ``seeds[l]``."""
+        plant = plant or plant_config()
+        seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(-1)
+        if seeds is not None and seeds.size != int(P):
+            raise DartMPCError(f"train_pop_dev needs {P} seeds, got {seeds.size}")
+        buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
+                             + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
+                             + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
+                             + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
+                             + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
+        rc = lib().dart_lmpc_train_pop_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
+                                           ctypes.byref(ppo_cfg), ctypes.byref(tcfg), int(P), _ptr(seeds), int(B),
+                                           int(reset_rows), buf, stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_train_pop_dev")
+
+    def train_pop(self, P, seeds, target, plant_pvec, state, cstate, logs, clogs, rec, pcfg, weights, critic, current_k,
+                  adam, adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None,
+                  pool=None, plant=None):
+        """Host arrays (blocking, dart_lmpc_train_pop): ``train`` for ``P`` learners, all arrays stacked as
+        ``train_pop_dev`` takes them (``ppo.population_stack`` builds them, ``ppo.train_population`` wraps this) and
+        updated in place: ``weights`` [P, 39748], ``critic`` [P, POP_CRITIC_STRIDE], ``current_k`` [P B, 34], ``adam``
+        [P, 2, 77317], ``adam_step`` [P], ``train_log`` [P, iterations, 12], ``best_return`` [P], ``best_weights``
+        [P, 77317], ``best_iter`` [P]; ``state`` / ``cstate`` hold P B instances."""
+        P, K = int(P), int(tcfg.steps)
+        NI = state["x"].shape[0]
+        B = NI // max(P, 1)
+        if P >= 1 and B * P != NI:
+            raise DartMPCError(f"train_pop: {NI} instances are not {P} learners of equal size")
+        rcfg = rcfg if rcfg is not None else reward_config()
+        R = K // max(int(rcfg.record_every), 1)
+        reset_rows = 0 if not pool else pool["reset_x"].shape[0]
+        prm = np.ascontiguousarray(np.tile(LMPC_PRM_DEFAULT, (NI, 1)) if prm is None else prm, np.float64).reshape(NI, 22)
+        plant = plant or plant_config()
+        seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(-1)
+        if seeds is not None and seeds.size != P:
+            raise DartMPCError(f"train_pop needs {P} seeds, got {seeds.size}")
+        nl = max(P, 1)
+        head = [("target", 8, np.float64), ("plant_pvec", 34, np.float64)]
+        tg, pp = _host_ptrs(head, {"target": target, "plant_pvec": plant_pvec}, (NI,))
+        tail = [_inplace(adam, np.float32, nl * 2 * PPO_NPARAMS, "adam"), _inplace(adam_step, np.int32, nl, "adam_step"),
+                _inplace(train_log, np.float64, nl * TRAIN_LOG_COLS * int(tcfg.iterations), "train_log"),
+                _inplace(best_return, np.float64, nl, "best_return"),
+                _inplace(best_weights, np.float32, nl * PPO_NPARAMS, "best_weights"),
+                _inplace(best_iter, np.int32, nl, "best_iter")]
+        ptrs = ([tg, _ptr(prm), pp, _ptr(_inplace(current_k, np.float64, 34 * NI, "current_k")),
+                 _ptr(_inplace(weights, np.float32, nl * ACTOR_NWEIGHTS, "weights")),
+                 _ptr(_inplace(critic, np.float32, nl * POP_CRITIC_STRIDE, "critic"))]
+                + _host_ptrs(LMPC_LOOP_STATE, state, (NI,), nw=self.nw) + _host_ptrs(LMPC_COLLECT_STATE, cstate, (NI,))
+                + (_host_ptrs(LMPC_COLLECT_POOL, pool, (reset_rows, NI)) if reset_rows else [None] * 3)
+                + _host_ptrs(LMPC_LOOP_LOGS, logs, (K, NI)) + _host_ptrs(LMPC_COLLECT_LOGS, clogs, (K, NI))
+                + _host_ptrs(LMPC_COLLECT_REC, rec, (R, NI)) + [_ptr(a) for a in tail] + [None])
+        buf = _train_buffers([0 if q is None else q.value for q in ptrs])
+        rc = lib().dart_lmpc_train_pop(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
+                                       ctypes.byref(ppo_cfg), ctypes.byref(tcfg), P, _ptr(seeds), B, reset_rows, buf,
+                                       None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_train_pop")
+
     def train(self, target, plant_pvec, state, cstate, logs, clogs, rec, policy, adam, adam_step, train_log,
               best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None, pool=None, plant=None,
               global_buffer=None, global_log=None):
@@ -1483,6 +1559,16 @@ def train_workspace_bytes(B, K, record_every, epochs, mini_batch_size):
         raise DartMPCError(f"no training workspace for B = {B}, K = {K}, record_every = {record_every}, epochs = "
                            f"{epochs}, mini_batch_size = {mini_batch_size} (K a positive multiple of record_every)")
     return b
+
+
+POP_MAX = 32                    # DART_LMPC_POP_MAX: learners per population
+POP_CRITIC_STRIDE = 37572       # DART_LMPC_POP_CRITIC_STRIDE: floats between the critics of a population (16-byte rows)
+
+
+def train_pop_workspace_bytes(P, B, K, record_every, epochs, mini_batch_size):
+    """Bytes of the device workspace of ``LmpcSolver.train_pop_dev``; 0 for a bad shape."""
+    return int(lib().dart_lmpc_train_pop_workspace_bytes(int(P), int(B), int(K), int(record_every), int(epochs),
+                                                         int(mini_batch_size)))
 
 
 def philox_dev(n, inputs, out, stream=0):

@@ -232,6 +232,140 @@ def train_device(solver, policy, target, plant_pvec, state, cstate, adam, adam_s
     return rows
 
 
+def new_population_best(P):
+    """``new_best`` for ``P`` learners, stacked: best_return [P], best_weights [P, 77317], best_iter [P]."""
+    return dict(best_return=np.full(int(P), -np.inf), best_weights=np.zeros((int(P), 77317), np.float32),
+                best_iter=np.full(int(P), -1, np.int32))
+
+
+def stack_critics(critics):
+    """Packed critics (37569 weights each) as ``train_pop`` takes them: float32 [P, POP_CRITIC_STRIDE], every row
+    16-byte aligned; the three pad floats of a row are never read or written by the library."""
+    from . import _lib
+    out = np.zeros((len(critics), _lib.POP_CRITIC_STRIDE), np.float32)
+    for l, c in enumerate(critics):
+        out[l, :_lib.CRITIC_NWEIGHTS] = np.asarray(c, np.float32).reshape(-1)
+    return out
+
+
+def population_stack(members):
+    """The stacked arrays of a population from its members' (the inverse of ``population_member``).  A member is a
+    dict of what ``train_device`` takes for one learner of B instances: ``target`` [B, 8], ``plant_pvec`` [B, 34],
+    ``state`` and ``cstate`` (dicts of [B, ..] arrays), ``adam`` [2, 77317], ``adam_step`` [1], ``best``
+    (``new_best``), and optionally ``pool`` (dict of [rows, B, ..] arrays), ``current_k`` [B, 34], ``weights`` [39748]
+    and ``critic`` [37569].  Returns the same keys with the instances stacked learner-major (instance l B + b), ``adam``
+    [P, 2, 77317], ``adam_step`` [P], ``best`` as ``new_population_best``, ``weights`` [P, 39748] and ``critic``
+    [P, POP_CRITIC_STRIDE] (``stack_critics``)."""
+    cat = lambda arrs, axis=0: np.ascontiguousarray(np.concatenate([np.asarray(a) for a in arrs], axis=axis))
+    m0 = members[0]
+    out = dict(target=cat([m["target"] for m in members]), plant_pvec=cat([m["plant_pvec"] for m in members]),
+               state={k: cat([m["state"][k] for m in members]) for k in m0["state"]},
+               cstate={k: cat([m["cstate"][k] for m in members]) for k in m0["cstate"]},
+               adam=np.ascontiguousarray(np.stack([np.asarray(m["adam"]).reshape(2, -1) for m in members])),
+               adam_step=cat([np.asarray(m["adam_step"]).reshape(1) for m in members]),
+               best={k: (np.ascontiguousarray(np.stack([np.asarray(m["best"][k]).reshape(-1) for m in members]))
+                         if k == "best_weights" else cat([np.asarray(m["best"][k]).reshape(1) for m in members]))
+                     for k in ("best_return", "best_weights", "best_iter")})
+    if m0.get("pool"):
+        out["pool"] = {k: cat([m["pool"][k] for m in members], axis=1) for k in m0["pool"]}
+    if "current_k" in m0:
+        out["current_k"] = cat([np.asarray(m["current_k"]).reshape(-1, 34) for m in members])
+    if "weights" in m0:
+        out["weights"] = np.ascontiguousarray(np.stack([np.asarray(m["weights"], np.float32).reshape(-1)
+                                                        for m in members]))
+    if "critic" in m0:
+        out["critic"] = stack_critics([m["critic"] for m in members])
+    return out
+
+
+def population_member(l, P, pop):
+    """Learner ``l`` of the ``P`` in ``pop`` (a dict as ``population_stack`` returns it; keys it lacks are left out),
+    in the shapes ``train_device`` and ``save_checkpoint`` take: views of its slice of every stacked array -- writing
+    through them writes the population -- except ``pool``, whose slice is not contiguous and is copied (it is only
+    read).  ``critic`` is the 37569 weights of its row, without the pad."""
+    from . import _lib
+    l, P = int(l), int(P)
+    if not 0 <= l < P:
+        raise _lib.DartMPCError(f"population_member: learner {l} of {P}")
+    NI = np.asarray(pop["target"]).shape[0]
+    if NI % P:
+        raise _lib.DartMPCError(f"population_member: {NI} instances are not {P} learners of equal size")
+    B = NI // P
+    sl = slice(l * B, (l + 1) * B)
+    out = dict(target=pop["target"][sl], plant_pvec=pop["plant_pvec"][sl],
+               state={k: v[sl] for k, v in pop["state"].items()}, cstate={k: v[sl] for k, v in pop["cstate"].items()},
+               adam=pop["adam"][l], adam_step=pop["adam_step"][l:l + 1],
+               best={k: (pop["best"][k][l] if k == "best_weights" else pop["best"][k][l:l + 1])
+                     for k in ("best_return", "best_weights", "best_iter")})
+    if pop.get("pool"):
+        out["pool"] = {k: np.ascontiguousarray(v[:, sl]) for k, v in pop["pool"].items()}
+    if "current_k" in pop:
+        out["current_k"] = pop["current_k"][sl]
+    if "weights" in pop:
+        out["weights"] = pop["weights"][l]
+    if "critic" in pop:
+        out["critic"] = pop["critic"][l, :_lib.CRITIC_NWEIGHTS]
+    return out
+
+
+def population_samples(P, B, R):
+    """The sample lists of a population, int32 [P, R B]: entry r B + b of learner l is r (P B) + l B + b, the flat
+    index of record r of instance l B + b in the stacked record arrays [R, P B]."""
+    l, r, b = np.arange(P)[:, None, None], np.arange(R)[None, :, None], np.arange(B)[None, None, :]
+    return (r * (P * B) + l * B + b).reshape(P, R * B).astype(np.int32)
+
+
+def population_noise(seeds, iteration, steps, B):
+    """The numpy statement of a population's stacked noise, float32 [steps, P B, 34]: learner l's block
+    [:, l B:(l + 1) B] is ``harness.lmpc_train_noise(seeds[l], iteration, steps, B)``, the single run's draws."""
+    from . import harness
+    return np.ascontiguousarray(np.concatenate(
+        [harness.lmpc_train_noise(int(sd), iteration, steps, B, np.float32) for sd in seeds], axis=1))
+
+
+def train_population(solver, policies, target, plant_pvec, state, cstate, adam, adam_step, best, steps, seeds,
+                     iterations=1, it0=0, rcfg=None, pool=None, prm=None, gamma=0.99, lam=0.95, mean_update=True,
+                     track_best=True, epochs=8, mini_batch_size=64, out=None, **hyper):
+    """``train_device`` for a population: ``policies`` is a list of P ``LmpcPolicy(B, ...)`` that share one config,
+    the other arrays are stacked learner-major as ``population_stack`` lays them out (``target`` [P B, 8], ``state``
+    / ``cstate`` of P B instances, ``adam`` [P, 2, 77317], ``adam_step`` [P], ``best`` = ``new_population_best(P)``,
+    ``pool`` [rows, P B, ..]), ``seeds`` are P integers.  All learners run in the same launches
+    (``LmpcSolver.train_pop``); learner l is bit for bit ``train_device`` on ``population_member(l, ...)`` with
+    ``seed=seeds[l]``.  Updated in place: the stacked arrays, and every policy's ``weights``, ``critic_weights`` and
+    ``current_k``.  There is no global-buffer update for a population.  Returns one list of ``TRAIN_LOG_FIELDS``
+    dicts (one per iteration) per learner."""
+    from . import _lib
+    P = len(policies)
+    rcfg = rcfg if rcfg is not None else _lib.reward_config()
+    NI, K = state["x"].shape[0], int(steps)
+    if P < 1 or NI % P:
+        raise _lib.DartMPCError(f"train_population: {NI} instances are not {P} learners of equal size")
+    B = NI // P
+    if any(p.critic_weights is None for p in policies):
+        raise _lib.DartMPCError("training needs policies with critic_weights")
+    cfg = _lib.ppo_config(**dict(hyper, epochs=epochs, mini_batch_size=mini_batch_size))
+    tcfg = _lib.train_config(seed=0, iterations=iterations, it0=it0, steps=K, gamma=gamma, lam=lam,
+                             mean_update=int(bool(mean_update)), track_best=int(bool(track_best)))
+    R = K // max(int(rcfg.record_every), 1)
+    weights = np.ascontiguousarray(np.stack([np.asarray(p.weights, np.float32).reshape(-1) for p in policies]))
+    critic = stack_critics([p.critic_weights for p in policies])
+    current_k = np.ascontiguousarray(np.concatenate([np.asarray(p.current_k, np.float64).reshape(B, 34)
+                                                     for p in policies]))
+    logs, clogs = _lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, NI), _lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, NI)
+    rec = _lib.loop_logs(_lib.LMPC_COLLECT_REC, R, NI)
+    train_log = np.full((P, int(iterations), _lib.TRAIN_LOG_COLS), np.nan)
+    solver.train_pop(P, seeds, target, plant_pvec, state, cstate, logs, clogs, rec, policies[0].cfg, weights, critic,
+                     current_k, adam, adam_step, train_log, best["best_return"], best["best_weights"],
+                     best["best_iter"], cfg, tcfg, rcfg=rcfg, prm=prm, pool=pool)
+    for l, p in enumerate(policies):
+        p.weights[...] = weights[l].reshape(p.weights.shape)
+        p.critic_weights[...] = critic[l, :_lib.CRITIC_NWEIGHTS].reshape(p.critic_weights.shape)
+        p.current_k[...] = current_k[l * B:(l + 1) * B].reshape(p.current_k.shape)
+    if out is not None:
+        out.update(logs=logs, clogs=clogs, rec=rec, train_log=train_log, weights=weights, critic=critic)
+    return [[dict(zip(_lib.TRAIN_LOG_FIELDS, (float(v) for v in row))) for row in train_log[l]] for l in range(P)]
+
+
 def new_global_buffer(n):
     """The global buffer of a fresh training with ``n`` samples per iteration: zeroed arrays of capacity G
     (``_lib.global_rows``) and ``fill`` = 0."""

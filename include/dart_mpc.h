@@ -1041,6 +1041,48 @@ void dart_mpc_destroy(dart_mpc_handle *h);
 /* Number of fp64 entries of w for horizon N: 6(N+1) + 2N. */
 int dart_mpc_nw(int N);
 
+/* A population of P independent learners trained in the launches of one (added within ABI 8: new entries only).
+ * Every learner has its own actor, critic, Adam state, seed, controllers, reset pool, log and best-policy snapshot;
+ * learner l is, bit for bit, the run dart_lmpc_train(_dev) gives for its arrays and cfg->seed = seeds[l] alone.  The
+ * shared configs (plant, policy, reward, PPO; gamma, lam, steps, mean_update, track_best) apply to every learner.
+ *
+ * Layout, with dart_lmpc_train_buffers unchanged: the P B controllers are stacked learner-major, instance
+ * i = l B + b, and every per-instance array keeps its meaning with P B in place of B (state and collection state
+ * [P B][..], logs [K][P B][..], records [R][P B][..], reset pool [reset_rows][P B][..]).  Per learner: weights
+ * [P][39748]; critic [P][DART_LMPC_POP_CRITIC_STRIDE] (37569 weights and three pad floats that are never read or
+ * written, so that every critic is 16-byte aligned); adam [P][2][77317]; adam_step [P]; train_log
+ * [P][iterations][12]; best_return [P]; best_weights [P][77317]; best_iter [P].
+ *
+ * seeds [P] (host memory, read before the entry returns; cfg->seed is ignored): learner l's noise and permutations
+ * are those of dart_lmpc_noise_dev / dart_lmpc_perms_dev for (seeds[l], it); element (k, b, j) of its noise is
+ * stored at [k][l B + b][j] of the stacked noise.  Its sample list is r B + b -> r (P B) + l B + b.
+ *
+ * The launch sequence per iteration is dart_lmpc_train_dev's, each step issued once for the whole population (the
+ * update: prepare once, then gradient + apply per mini-batch index with every learner in each launch).  Calls chain
+ * through it0 as the single entry's do.  There is no population form of the global-buffer update
+ * (dart_lmpc_train_global), of dart_lmpc_rollout or of dart_lmpc_collect. */
+#define DART_LMPC_POP_MAX 32
+#define DART_LMPC_POP_CRITIC_STRIDE 37572
+
+/* Bytes of the workspace; 0 for a bad shape (P outside 1 .. DART_LMPC_POP_MAX, or what
+ * dart_lmpc_train_workspace_bytes refuses). */
+size_t dart_lmpc_train_pop_workspace_bytes(int P, int B, int K, int record_every, int epochs, int mini_batch_size);
+
+/* Device pointers; h needs B_max >= P B.  DART_MPC_EINVAL before any device work: P < 1, P > DART_LMPC_POP_MAX,
+ * P B > B_max, null seeds or a null required pointer, weights or critic not 16-byte aligned, steps not a multiple of
+ * record_every, a handle of the wrong variant. */
+int dart_lmpc_train_pop_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                            const dart_lmpc_reward_config *rcfg, const dart_lmpc_ppo_config *ppo,
+                            const dart_lmpc_train_config *cfg, int P, const uint64_t *seeds, int B, int reset_rows,
+                            const dart_lmpc_train_buffers *buf, void *hip_stream);
+
+/* Host pointers: staged in once, all iterations, staged out once; blocks.  Instances (all P B) whose timestep
+ * differ are DART_MPC_EINVAL before any device work. */
+int dart_lmpc_train_pop(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                        const dart_lmpc_reward_config *rcfg, const dart_lmpc_ppo_config *ppo,
+                        const dart_lmpc_train_config *cfg, int P, const uint64_t *seeds, int B, int reset_rows,
+                        const dart_lmpc_train_buffers *buf, void *hip_stream);
+
 /* ABI version (DART_MPC_ABI_VERSION) of the loaded library. */
 int dart_mpc_abi_version(void);
 

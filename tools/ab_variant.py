@@ -35,6 +35,26 @@ elif kind == "lmpc":
     PR = f64(np.tile(LMPC_PRM_DEFAULT, (B, 1)))
     s = dart_mpc.LmpcSolver(N=30, B_max=B, device=0)
     call = lambda i, o: s.solve_batch_dev(B, *[x[i % nb].data_ptr() for x in X], PR.data_ptr(), *o, stream=sp)
+elif kind == "lmpc_fused":
+    # C5's launch: the policy step as the solve's prologue (dart_lmpc_policy_solve_batch_dev), B = 18, N = 30.  The
+    # policy's state (Welford sums, history, timestep, model_params) advances from launch to launch, the same way in
+    # every build, so the outputs compare bit for bit.
+    from dart_mpc._lib import LMPC_PRM_DEFAULT
+    from dart_mpc.lmpc import LmpcPolicy
+    D = [W.lmpc_batch(1, seed0=7000 + i) for i in range(nb)]
+    X = [f64(np.stack([d[k] for d in D])) for k in ("state", "u_prev", "target")]
+    PR = f64(np.tile(LMPC_PRM_DEFAULT, (B, 1)))
+    pol = LmpcPolicy(B, seed=3)
+    s = dart_mpc.LmpcSolver(N=30, B_max=B, device=0)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    PW, CK, MP = up(pol.weights), up(pol.current_k), up(pol.model_params)
+    OM, O2, OC = up(pol.obs_mean), up(pol.obs_M2), up(pol.obs_count)
+    HI, TS = up(pol.history), up(pol.timestep)
+    NZ = up(np.random.default_rng(1).standard_normal((nb, B, 34)).astype(np.float32))
+    call = lambda i, o: s.policy_solve_batch_dev(
+        pol.cfg, B, PW.data_ptr(), X[0][i % nb].data_ptr(), X[1][i % nb].data_ptr(), X[2][i % nb].data_ptr(),
+        CK.data_ptr(), OM.data_ptr(), O2.data_ptr(), OC.data_ptr(), HI.data_ptr(), TS.data_ptr(),
+        NZ[i % nb].data_ptr(), MP.data_ptr(), PR.data_ptr(), *o, stream=sp)
 elif kind == "arm":
     # the bench's arm QP line: 36 arm snapshots per launch (18 configs x 2 arms), n = 7, reference parameters
     from dart_mpc.arm import pack_params, pack_snapshot

@@ -14,10 +14,15 @@ afresh).  With --global-update (resident only) every iteration also runs the ref
 global buffer (rlmpc2.py:823-874; ppo.new_global_buffer): a quarter of its records is appended to a buffer that
 survives across iterations and is updated on once it holds a full iteration's worth; the buffer is saved and resumed
 with the checkpoint, so a run can stop in the middle of a fill period.
+With --population P (resident only) P independent learners -- their own instances, reset pools, initial nets and
+seeds (--seeds a,b,...; default 0 .. P-1) -- train in the launches of one (dart_mpc.ppo.train_population,
+LmpcSolver.train_pop); a line per learner and iteration, and --checkpoint PATH writes one checkpoint per member
+(PATH.member<l>.npz, each of which --resume continues alone).
 The loop state, the collection state, the targets and the plants carry over from iteration to iteration.
 Prints the mean return of the episodes that ended, per iteration.
 Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps] [--update device|torch|resident]
                                   [--global-update] [--checkpoint PATH] [--resume PATH] [--seed S]
+                                  [--population P [--seeds a,b,...]]
 """
 import os
 import sys
@@ -56,6 +61,9 @@ if global_update:
     if update != "resident":
         sys.exit("--global-update goes with --update resident")
 ckpt_out, ckpt_in, seed = _option("--checkpoint"), _option("--resume"), int(_option("--seed") or 0)
+population, pop_seeds = int(_option("--population") or 0), _option("--seeds")
+if population and (update != "resident" or global_update or ckpt_in):
+    sys.exit("--population goes with --update resident, without --global-update and --resume")
 if (ckpt_out or ckpt_in) and update != "resident":
     sys.exit("--checkpoint and --resume go with --update resident")
 iters = int(argv[0]) if len(argv) > 0 else 5
@@ -64,6 +72,66 @@ K = int(argv[2]) if len(argv) > 2 else 256
 ep_steps = int(argv[3]) if len(argv) > 3 else 64
 GAMMA, LAM, N = 0.99, 0.95, 30
 
+
+
+def train_population():
+    """P learners in one call of the population entry; member l is the single run of this script on its own data."""
+    if K % int(rcfg.record_every):
+        sys.exit(f"--population needs K to be a multiple of record_every = {int(rcfg.record_every)}")
+    P_ = population
+    sd = [int(v) for v in pop_seeds.split(",")] if pop_seeds else list(range(P_))
+    if len(sd) != P_:
+        sys.exit(f"--seeds needs {P_} values")
+    solver = _lib.LmpcSolver(N=N, B_max=P_ * B)
+    try:
+        members, policies = [], []
+        ns = -(-B // 18)
+        for l in range(P_):
+            D = lmpc_batch(ns, seed0=1000 * l)
+            Q = [lmpc_batch(ns, seed0=100 + r + 1000 * l) for r in range(4)]
+            torch.manual_seed(l)
+            actor, critic = ppo.pack_weights(ppo.PolicyNet())
+            pol = LmpcPolicy(B, weights=actor, critic_weights=critic, seed=l)
+            policies.append(pol)
+            members.append(dict(target=D["target"][:B], plant_pvec=D["pvec"][:B],
+                                state=solver.loop_state(D["state"][:B], policy=pol),
+                                cstate=solver.collect_state(np.zeros((B, 2))),
+                                adam=np.zeros((2, _lib.PPO_NPARAMS), np.float32), adam_step=np.zeros(1, np.int32),
+                                best=ppo.new_best(),
+                                pool={"reset_x": np.stack([q["state"][:B] for q in Q]),
+                                      "reset_target": np.stack([q["target"][:B] for q in Q]),
+                                      "reset_pvec": np.stack([q["pvec"][:B] for q in Q])}))
+        H = ppo.population_stack(members)
+        rows = ppo.train_population(solver, policies, H["target"], H["plant_pvec"], H["state"], H["cstate"], H["adam"],
+                                    H["adam_step"], H["best"], K, sd, iterations=iters, rcfg=rcfg, pool=H["pool"],
+                                    gamma=GAMMA, lam=LAM, epochs=8, mini_batch_size=64, clip_eps=0.2, vf_coef=0.25,
+                                    ent_coef=0.01)
+        for j in range(iters):
+            for l in range(P_):
+                r = rows[l][j]
+                print(f"iter {j} learner {l} (seed {sd[l]}): samples {int(r['n'])}, episodes ended "
+                      f"{int(r['episodes_ended'])}, mean last return {r['mean_return']:.2f}, mean step reward "
+                      f"{r['mean_step_reward']:.3f}, policy loss {r['policy_loss']:.4f}, value loss "
+                      f"{r['value_loss']:.4f}, entropy {r['entropy']:.3f}, best return {r['best_return']:.2f}"
+                      f"{' (snapshot)' if r['snapshot'] else ''}", flush=True)
+        if ckpt_out:
+            for l in range(P_):
+                m = ppo.population_member(l, P_, H)
+                st = m["state"]
+                path = ppo.save_checkpoint(f"{ckpt_out}.member{l}", policies[l].weights, policies[l].critic_weights,
+                                           m["adam"], m["adam_step"], m["best"], iters, st["obs_mean"], st["obs_M2"],
+                                           st["obs_count"], st["history"], policies[l].current_k, st["model_params"])
+                print(f"checkpoint: {path} (learner {l}, best return {float(m['best']['best_return'][0]):.2f})",
+                      flush=True)
+    finally:
+        solver.close()
+
+
+rcfg = _lib.reward_config(max_episode_steps=ep_steps)
+if population:
+    train_population()
+    sys.exit(0)
+
 seeds = -(-B // 18)
 D = lmpc_batch(seeds)
 target, pvec = np.ascontiguousarray(D["target"][:B]), np.ascontiguousarray(D["pvec"][:B])
@@ -71,7 +139,6 @@ P = [lmpc_batch(seeds, seed0=100 + r) for r in range(4)]
 pool = {"reset_x": np.ascontiguousarray(np.stack([p["state"][:B] for p in P])),
         "reset_target": np.ascontiguousarray(np.stack([p["target"][:B] for p in P])),
         "reset_pvec": np.ascontiguousarray(np.stack([p["pvec"][:B] for p in P]))}
-rcfg = _lib.reward_config(max_episode_steps=ep_steps)
 rec_rows = K // int(rcfg.record_every) + 1
 
 torch.manual_seed(0)

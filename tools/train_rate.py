@@ -14,7 +14,16 @@ steps, 8 epochs of mini-batches of 64, N = 30.
 Protocol of tools/rollout_rate.py: the contenders alternate in one process, one warm-up each, then five rounds each;
 a host clock around work that ends in a synchronise; medians with the min-to-max spread.  Every contender carries its
 own training state from round to round, so the rounds are consecutive iterations of a training run.
+Population contenders (--population): B = 72, K = 256, P in {1, 2, 3, 4, 8} learners.  `population` is one
+train_pop_dev iteration of all P learners (csrc: the *_pop_kernel launches); `sequential` is P back-to-back train_dev
+iterations on P separate training states, each ending in its synchronise -- the way a user gets a population without
+the entry; `streams` enqueues the P train_dev iterations on the P solvers' own streams and synchronises once.  Same
+protocol; times are per population.
 Usage: python tools/train_rate.py [out.json] [rounds]
+       python tools/train_rate.py --population [out.json] [rounds]
+       python tools/train_rate.py --once-pop P B K [iterations]   (population iterations and nothing else)
+       python tools/train_rate.py --ab B K out.npz [iterations]   (resident_dev alone, one time per iteration, and its
+                                                                    results for a bit-for-bit check of two builds)
        python tools/train_rate.py --once B K [iterations]   (resident iterations and nothing else: for a kernel trace)
        python tools/train_rate.py --micro B K [out.json]    (the global update's small launches on their own: a HIP
                                                               event pair around one launch, 5 warm-ups, 30 repeats)
@@ -42,18 +51,19 @@ HAVE_GLOBAL = hasattr(_lib.lib(), "dart_lmpc_train_global_dev")
 class Run:
     """The training state of one contender: tools/lmpc_train.py's setup."""
 
-    def __init__(self, B, K):
+    def __init__(self, B, K, member=0):
+        """``member`` > 0: another learner of a population (its own instances, pool rows and initial nets)."""
         self.B, self.K = B, K
         seeds = -(-B // 18)
-        D = lmpc_batch(seeds)
+        D = lmpc_batch(seeds, seed0=1000 * member)
         self.target, self.pvec = np.ascontiguousarray(D["target"][:B]), np.ascontiguousarray(D["pvec"][:B])
-        P = [lmpc_batch(seeds, seed0=100 + r) for r in range(4)]
+        P = [lmpc_batch(seeds, seed0=100 + r + 1000 * member) for r in range(4)]
         self.pool = {"reset_x": np.ascontiguousarray(np.stack([p["state"][:B] for p in P])),
                      "reset_target": np.ascontiguousarray(np.stack([p["target"][:B] for p in P])),
                      "reset_pvec": np.ascontiguousarray(np.stack([p["pvec"][:B] for p in P]))}
         self.rcfg = _lib.reward_config(max_episode_steps=EP_STEPS)
         self.every = int(self.rcfg.record_every)
-        torch.manual_seed(0)
+        torch.manual_seed(member)
         net = ppo.PolicyNet()
         self.gen = torch.Generator().manual_seed(0)
         actor, critic = ppo.pack_weights(net)
@@ -137,16 +147,106 @@ class Run:
         self.fill = _lib.global_fill_after(self.n, self.fill, self.period)
         self.it += self.period
 
-    def resident_dev(self, iterations=1):
+    def resident_dev(self, iterations=1, sync=True, seed=0):
         d = self.dev
         p = lambda g: {k: v.data_ptr() for k, v in d[g].items()}
-        tcfg = _lib.train_config(seed=0, iterations=iterations, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
+        tcfg = _lib.train_config(seed=seed, iterations=iterations, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
         self.solver.train_dev(self.B, 4, d["c"]["target"].data_ptr(), d["c"]["prm"].data_ptr(), d["c"]["pvec"].data_ptr(),
                               d["c"]["current_k"].data_ptr(), d["c"]["weights"].data_ptr(), d["c"]["critic"].data_ptr(),
                               p("st"), p("cs"), p("lg"), p("clg"), p("rec"), p("tr"), self.policy.cfg, self.rcfg,
                               self.cfg, tcfg, pool=p("pool"))
+        if sync:
+            self.solver.sync()
+        self.it += iterations
+
+
+class PopRun:
+    """P learners of B instances on one solver, device-resident: the members are Run(B, K, member=l), stacked."""
+
+    def __init__(self, P, B, K):
+        self.P, self.B, self.K = P, B, K
+        members = [Run(B, K, member=l) for l in range(P)]
+        for m in members:
+            m.close()
+        m0 = members[0]
+        self.rcfg, self.every, self.pcfg = m0.rcfg, m0.every, m0.policy.cfg
+        H = ppo.population_stack([dict(target=m.target, plant_pvec=m.pvec, state=m.state, cstate=m.cs, adam=m.adam,
+                                       adam_step=m.adam_step, best=m.best, pool=m.pool, current_k=m.policy.current_k,
+                                       weights=m.policy.weights, critic=m.policy.critic_weights) for m in members])
+        NI, R = P * B, K // self.every
+        self.solver = _lib.LmpcSolver(N=N, B_max=NI)
+        up = lambda d: {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
+        self.dev = dict(
+            c=up(dict(target=H["target"], prm=np.tile(_lib.LMPC_PRM_DEFAULT, (NI, 1)), pvec=H["plant_pvec"],
+                      current_k=H["current_k"], weights=H["weights"], critic=H["critic"])),
+            st=up(H["state"]), cs=up(H["cstate"]), pool=up(H["pool"]),
+            lg=up(_lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, NI)), clg=up(_lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, NI)),
+            rec=up(_lib.loop_logs(_lib.LMPC_COLLECT_REC, R, NI)),
+            tr=up(dict(adam=H["adam"], adam_step=H["adam_step"], train_log=np.full((P, 8, 12), np.nan),
+                       best_return=H["best"]["best_return"], best_weights=H["best"]["best_weights"],
+                       best_iter=H["best"]["best_iter"])))
+        self.dev["tr"]["workspace"] = torch.zeros(_lib.train_pop_workspace_bytes(P, B, K, self.every, EPOCHS, MB),
+                                                  dtype=torch.uint8, device="cuda")
+        self.cfg = _lib.ppo_config(epochs=EPOCHS, mini_batch_size=MB, **HYPER)
+        self.it = 0
+        torch.cuda.synchronize()
+
+    def close(self):
+        self.solver.close()
+
+    def population(self, iterations=1):
+        d = self.dev
+        p = lambda g: {k: v.data_ptr() for k, v in d[g].items()}
+        tcfg = _lib.train_config(iterations=iterations, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
+        self.solver.train_pop_dev(self.P, list(range(self.P)), self.B, 4, d["c"]["target"].data_ptr(),
+                                  d["c"]["prm"].data_ptr(), d["c"]["pvec"].data_ptr(), d["c"]["current_k"].data_ptr(),
+                                  d["c"]["weights"].data_ptr(), d["c"]["critic"].data_ptr(), p("st"), p("cs"), p("lg"),
+                                  p("clg"), p("rec"), p("tr"), self.pcfg, self.rcfg, self.cfg, tcfg, pool=p("pool"))
         self.solver.sync()
         self.it += iterations
+
+
+def measure_population(P, B, K, rounds):
+    pop = PopRun(P, B, K)
+    seq = [Run(B, K, member=l) for l in range(P)]
+    par = [Run(B, K, member=l) for l in range(P)]
+    for r in seq + par:
+        r.to_device()
+
+    def sequential():
+        for l, r in enumerate(seq):
+            r.resident_dev(seed=l)
+
+    def streams():
+        for l, r in enumerate(par):
+            r.resident_dev(sync=False, seed=l)
+        for r in par:
+            r.solver.sync()
+
+    calls = {"population": pop.population, "sequential": sequential, "streams": streams}
+    times = {name: [] for name in calls}
+    try:
+        for r in range(rounds + 1):                 # round 0 is the warm-up
+            for name, fn in calls.items():
+                ms = timed(fn)
+                if r:
+                    times[name].append(ms)
+        # the learners are the same runs in all three: learner l's actor after the rounds, bit for bit
+        w = pop.dev["c"]["weights"].cpu().numpy()
+        same = all(np.array_equal(w[l].view(np.int32), m.dev["c"]["weights"].cpu().numpy().view(np.int32))
+                   for group in (seq, par) for l, m in enumerate(group))
+    finally:
+        for run in [pop] + seq + par:
+            run.close()
+    out = {"P": P, "B": B, "K": K, "instances": P * B, "samples_per_learner": B * (K // 8), "rounds": rounds,
+           "learners_bit_identical_across_contenders": bool(same)}
+    for name, t in times.items():
+        out[name] = {"median_ms": float(np.median(t)), "min_ms": float(min(t)), "max_ms": float(max(t)), "all_ms": t}
+    for name in ("sequential", "streams"):
+        o, q = out[name], out["population"]
+        out["population"]["speedup_vs_" + name] = {"median": o["median_ms"] / q["median_ms"],
+                                                   "low": o["min_ms"] / q["max_ms"], "high": o["max_ms"] / q["min_ms"]}
+    return out
 
 
 def timed(fn):
@@ -244,6 +344,46 @@ def main():
         if len(argv) > 3:
             with open(argv[3], "w") as fh:
                 json.dump(res, fh, indent=1)
+        return
+    if argv and argv[0] == "--population":
+        path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "population", "train_rate.json")
+        rounds = int(argv[2]) if len(argv) > 2 else 5
+        res = {"tool": "tools/train_rate.py --population", "device": torch.cuda.get_device_name(0), "N": N,
+               "episode_steps": EP_STEPS, "epochs": EPOCHS, "mini_batch_size": MB, "library": _lib.LIB_NAME,
+               "populations": []}
+        for P in (1, 2, 3, 4, 8):
+            r = measure_population(P, 72, 256, rounds)
+            res["populations"].append(r)
+            print(f"P = {P}: " + ", ".join(f"{n} {r[n]['median_ms']:.1f} ms ({r[n]['min_ms']:.1f}-{r[n]['max_ms']:.1f})"
+                                           for n in ("population", "sequential", "streams"))
+                  + f", bit-identical learners: {r['learners_bit_identical_across_contenders']}", flush=True)
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as fh:
+                json.dump(res, fh, indent=1)
+        return
+    if argv and argv[0] == "--once-pop":
+        run = PopRun(int(argv[1]), int(argv[2]), int(argv[3]))
+        try:
+            run.population(int(argv[4]) if len(argv) > 4 else 1)
+        finally:
+            run.close()
+        return
+    if argv and argv[0] == "--ab":
+        B, K, iters = int(argv[1]), int(argv[2]), int(argv[4]) if len(argv) > 4 else 5
+        run = Run(B, K)
+        try:
+            run.to_device()
+            run.resident_dev()                      # warm-up
+            t = [timed(run.resident_dev) for _ in range(iters)]
+            d = run.dev
+            np.savez(argv[3], weights=d["c"]["weights"].cpu().numpy(), critic=d["c"]["critic"].cpu().numpy(),
+                     current_k=d["c"]["current_k"].cpu().numpy(), adam=d["tr"]["adam"].cpu().numpy(),
+                     reward=d["clg"]["reward"].cpu().numpy(), x=d["st"]["x"].cpu().numpy(),
+                     best_return=d["tr"]["best_return"].cpu().numpy())
+        finally:
+            run.close()
+        print(f"{_lib.LIB_NAME} resident_dev B = {B}, K = {K}: median {np.median(t):.2f} ms "
+              f"({min(t):.2f}-{max(t):.2f}) over {iters} iterations", flush=True)
         return
     if argv and argv[0] == "--once":
         B, K = int(argv[1]), int(argv[2])
