@@ -498,7 +498,87 @@ hipError_t launch_gae_seq(int G, double gamma, double lam, const double* reward,
     return dartmpc_launch_lmpc_gae_seq(&a, s);
 }
 
+// ---- a population's forms: every learner in one launch (lmpc_train.h) ----
+
+bool pop_shape_ok(int P, const uint64_t* seeds) { return P >= 1 && P <= DART_LMPC_POP_MAX && seeds; }
+
+// the learners' generator keys travel in the launch arguments
+dartmpc::PopKeys pop_keys(int P, const uint64_t* seeds) {
+    dartmpc::PopKeys keys{};
+    for (int l = 0; l < P; ++l) {
+        keys.k[l][0] = (uint32_t)(seeds[l] & 0xffffffffu);
+        keys.k[l][1] = (uint32_t)(seeds[l] >> 32);
+    }
+    return keys;
+}
+
+// launch_perms per learner: perm [P][epochs][limit]
+hipError_t launch_perms_pop(int P, const dartmpc::PopKeys& keys, int iteration, int epochs, int n, int32_t* perm,
+                            hipStream_t s, uint32_t rng_stream, int limit) {
+    dartmpc::PermPopArgs pa;
+    pa.a.n = n; pa.a.epochs = epochs; pa.a.limit = limit; pa.a.key0 = pa.a.key1 = 0;
+    pa.a.iteration = (uint32_t)iteration; pa.a.stream = rng_stream; pa.a.perm = perm; pa.a.key_out = nullptr;
+    pa.P = P; pa.keys = keys;
+    return dartmpc_launch_lmpc_perms_pop(&pa, s);
+}
+
+// g: P buffers stacked g->capacity rows apart; sample [P][n], choice [P][m]
+hipError_t launch_global_append_pop(const dart_lmpc_global_buffer* g, int P, int fill, int m, int n,
+                                    long long rec_total, const int32_t* sample, const int32_t* choice,
+                                    const float* rec_obs, const float* rec_action, const float* rec_logp,
+                                    const float* rec_value, const double* rec_reward, const float* rec_done,
+                                    hipStream_t s) {
+    dartmpc::GbufAppendPopArgs q;
+    dartmpc::GbufAppendArgs& a = q.a;
+    a.m = m; a.n = n; a.fill = fill; a.rec_total = rec_total; a.sample = sample; a.choice = choice;
+    a.rec_obs = rec_obs; a.rec_action = rec_action; a.rec_logp = rec_logp; a.rec_value = rec_value;
+    a.rec_reward = rec_reward; a.rec_done = rec_done;
+    a.obs = g->obs; a.action = g->action; a.logp = g->logp; a.value = g->value; a.reward = g->reward; a.done = g->done;
+    q.P = P; q.capacity = g->capacity;
+    return dartmpc_launch_lmpc_gbuf_append_pop(&q, s);
+}
+
+hipError_t launch_gae_seq_pop(int P, int capacity, int G, double gamma, double lam, const double* reward,
+                              const float* value, const float* done, const float* last_value, double* adv,
+                              double* ret, hipStream_t s) {
+    dartmpc::GaeSeqPopArgs q;
+    q.a.G = G; q.a.gamma = gamma; q.a.lam = lam; q.a.reward = reward; q.a.value = value; q.a.done = done;
+    q.a.last_value = last_value; q.a.adv = adv; q.a.ret = ret;
+    q.P = P; q.capacity = capacity;
+    return dartmpc_launch_lmpc_gae_seq_pop(&q, s);
+}
+
 }  // namespace
+
+int dart_lmpc_choice_pop_dev(int P, const uint64_t* seeds, int iteration, int n, int m, int32_t* choice_out,
+                             void* stream) {
+    if (!pop_shape_ok(P, seeds) || iteration < 0 || m < 1 || m > n || !choice_out) return DART_MPC_EINVAL;
+    return launch_perms_pop(P, pop_keys(P, seeds), iteration, 1, n, choice_out, (hipStream_t)stream,
+                            dartmpc::kStreamChoice, m) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_global_append_pop_dev(const dart_lmpc_global_buffer* g, int P, int m, int n, int rec_total,
+                                    const int32_t* sample, const int32_t* choice, const float* rec_obs,
+                                    const float* rec_action, const float* rec_logp, const float* rec_value,
+                                    const double* rec_reward, const float* rec_done, void* stream) {
+    if (P < 1 || P > DART_LMPC_POP_MAX) return DART_MPC_EINVAL;
+    if (int rc = global_append_check(g, m, n, rec_total, sample, choice, rec_obs, rec_action, rec_logp, rec_value,
+                                     rec_reward, rec_done)) return rc;
+    if (!aligned16(rec_obs) || !aligned16(g->obs)) return DART_MPC_EINVAL;
+    return launch_global_append_pop(g, P, g->fill, m, n, rec_total, sample, choice, rec_obs, rec_action, rec_logp,
+                                    rec_value, rec_reward, rec_done, (hipStream_t)stream) == hipSuccess
+               ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_gae_seq_pop_dev(int P, int capacity, int G, double gamma, double lam, const double* reward,
+                              const float* value, const float* done, const float* last_value, double* adv,
+                              double* ret, void* stream) {
+    if (P < 1 || P > DART_LMPC_POP_MAX || G < 0 || capacity < G) return DART_MPC_EINVAL;
+    if (G == 0) return DART_MPC_OK;
+    if (!reward || !value || !done || !last_value || !adv || !ret) return DART_MPC_EINVAL;
+    return launch_gae_seq_pop(P, capacity, G, gamma, lam, reward, value, done, last_value, adv, ret,
+                              (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
 
 int dart_lmpc_global_append_dev(const dart_lmpc_global_buffer* g, int m, int n, int rec_total, const int32_t* sample,
                                 const int32_t* choice, const float* rec_obs, const float* rec_action,
@@ -764,7 +844,8 @@ int pop_check(dart_mpc_handle* h, const dart_lmpc_reward_config* rcfg, const dar
 }
 
 // The host form of the training entries.  P = 0: dart_lmpc_train_global (g == nullptr: dart_lmpc_train); P >= 1:
-// dart_lmpc_train_pop on P * B instances, the nets and the training arrays stacked per learner (g == nullptr)
+// dart_lmpc_train_pop_global on P * B instances, the nets and the training arrays stacked per learner, and g (when
+// given) P buffers stacked g->capacity rows apart
 int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg,
                int P, const uint64_t* seeds, int B, int reset_rows, const dart_lmpc_train_buffers* p,
@@ -812,13 +893,17 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
     dart_lmpc_global_buffer gd;
     int gi[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     size_t g_rowbytes[6] = {kHist * F, kAct * F, F, F, D, F};
+    const size_t g_bufs = P > 0 ? (size_t)P : 1;     // buffers, g->capacity rows apart
+    const int g_n = (int)R * learner_B;
     if (g) {
         gd = *g;
         const size_t cap = (size_t)g->capacity;
-        for (int q = 0; q < 6; ++q) gi[q] = S.add_log(nullptr, 1, cap * g_rowbytes[q], 0, 0, false);
-        gi[6] = S.add_log(g->global_log, (size_t)cfg->iterations, dartmpc::kGlobalLogCols * D, 0,
-                          (size_t)cfg->iterations, false);
-        gi[7] = S.add_log(nullptr, 1, dartmpc::global_workspace((int)(R * nB), ppo->epochs, ppo->mini_batch_size).bytes,
+        if (g_bufs * cap > 0x7fffffffULL) return fail(h, DART_MPC_EINVAL, "too many buffer rows");
+        for (int q = 0; q < 6; ++q) gi[q] = S.add_log(nullptr, 1, g_bufs * cap * g_rowbytes[q], 0, 0, false);
+        gi[6] = S.add_log(g->global_log, log_rows, dartmpc::kGlobalLogCols * D, 0, log_rows, false);
+        gi[7] = S.add_log(nullptr, 1,
+                          P > 0 ? dartmpc::global_pop_workspace(P, g_n, g->capacity, ppo->epochs, ppo->mini_batch_size).bytes
+                                : dartmpc::global_workspace(g_n, ppo->epochs, ppo->mini_batch_size).bytes,
                           0, 0, false);
     }
     if (int rc = S.reserve(h)) return rc;
@@ -834,11 +919,16 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
         gd.obs = S.dev<float>(h, gi[0]); gd.action = S.dev<float>(h, gi[1]); gd.logp = S.dev<float>(h, gi[2]);
         gd.value = S.dev<float>(h, gi[3]); gd.reward = S.dev<double>(h, gi[4]); gd.done = S.dev<float>(h, gi[5]);
         gd.global_log = S.dev<double>(h, gi[6]); gd.workspace = S.dev<char>(h, gi[7]);
-        for (int q = 0; q < 6 && g->fill > 0; ++q)
-            HIPCHK(h, hipMemcpyAsync(S.dev<char>(h, gi[q]), g_host[q], (size_t)g->fill * g_rowbytes[q],
-                                     hipMemcpyHostToDevice, s), "copy global buffer");
+        for (size_t l = 0; l < g_bufs; ++l)
+            for (int q = 0; q < 6 && g->fill > 0; ++q) {
+                const size_t off = l * (size_t)g->capacity * g_rowbytes[q];
+                HIPCHK(h, hipMemcpyAsync(S.dev<char>(h, gi[q]) + off, (const char*)g_host[q] + off,
+                                         (size_t)g->fill * g_rowbytes[q], hipMemcpyHostToDevice, s),
+                       "copy global buffer");
+            }
     }
-    if (int rc = P > 0 ? dart_lmpc_train_pop_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, learner_B, reset_rows, &d, s)
+    if (int rc = P > 0 ? dart_lmpc_train_pop_global_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, learner_B, reset_rows,
+                                                        &d, g ? &gd : nullptr, s)
                        : dart_lmpc_train_global_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, &d,
                                                     g ? &gd : nullptr, s)) {
         (void)hipStreamSynchronize(s);
@@ -846,10 +936,14 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
     }
     if (int rc = S.download(h, s)) return rc;
     if (g) {
-        const int held = dart_lmpc_global_fill_after((int)(R * nB), g->fill, cfg->iterations);
-        for (int q = 0; q < 6 && held > 0; ++q)
-            HIPCHK(h, hipMemcpyAsync(g_host[q], S.dev<char>(h, gi[q]), (size_t)held * g_rowbytes[q],
-                                     hipMemcpyDeviceToHost, s), "copy global buffer back");
+        const int held = dart_lmpc_global_fill_after(g_n, g->fill, cfg->iterations);
+        for (size_t l = 0; l < g_bufs; ++l)
+            for (int q = 0; q < 6 && held > 0; ++q) {
+                const size_t off = l * (size_t)g->capacity * g_rowbytes[q];
+                HIPCHK(h, hipMemcpyAsync((char*)g_host[q] + off, S.dev<char>(h, gi[q]) + off,
+                                         (size_t)held * g_rowbytes[q], hipMemcpyDeviceToHost, s),
+                       "copy global buffer back");
+            }
     }
     HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
     return DART_MPC_OK;
@@ -869,11 +963,22 @@ size_t dart_lmpc_train_pop_workspace_bytes(int P, int B, int K, int record_every
     return dartmpc::train_pop_workspace(P, B, K, record_every, epochs, mini_batch_size).bytes;
 }
 
-// dart_lmpc_train_dev's launch sequence, each step issued once for all P learners
-int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
-                            const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
-                            const dart_lmpc_train_config* cfg, int P, const uint64_t* seeds, int B, int reset_rows,
-                            const dart_lmpc_train_buffers* p, void* stream) {
+size_t dart_lmpc_global_pop_workspace_bytes(int P, int n, int capacity, int epochs, int mini_batch_size) {
+    if (P < 1 || P > DART_LMPC_POP_MAX) return 0;
+    if (dart_lmpc_global_workspace_bytes(n, epochs, mini_batch_size) == 0) return 0;
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    if (capacity < G || (long long)P * capacity > 0x7fffffffLL) return 0;
+    return dartmpc::global_pop_workspace(P, n, capacity, epochs, mini_batch_size).bytes;
+}
+
+// dart_lmpc_train_global_dev's launch sequence, each step issued once for all P learners (g == nullptr:
+// dart_lmpc_train_dev's; the P buffers of g are stacked learner-major, g->capacity rows apart)
+int dart_lmpc_train_pop_global_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                                   const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* rcfg,
+                                   const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg, int P,
+                                   const uint64_t* seeds, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                                   const dart_lmpc_global_buffer* g, void* stream) {
     DART_ENTER(h, -1);
     if (int rc = train_check(h, rcfg, ppo, cfg, B, p, true)) return rc;
     if (int rc = pop_check(h, rcfg, cfg, P, seeds, B)) return rc;
@@ -882,6 +987,11 @@ int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, 
     const int NI = P * B;                           // instances, learner-major
     const int K = cfg->steps, R = K / rcfg->record_every, n = R * B, mb = ppo->mini_batch_size;
     const long long rec_total = (long long)R * NI;
+    if (g) {
+        if (int rc = global_check(h, g, n, true)) return rc;
+        if ((long long)P * g->capacity > 0x7fffffffLL) return fail(h, DART_MPC_EINVAL, "too many buffer rows");
+        if (!aligned16(p->rec_obs)) return fail(h, DART_MPC_EINVAL, "rec_obs is not 16-byte aligned");
+    }
     void* s = stream_of(h, stream);
     auto collect = [&](int steps, const float* noise) {
         return lmpc_closed_loop(h, plant, pcfg, rcfg, true, NI, 0, steps, K, R, reset_rows, *p, noise, s, B);
@@ -904,11 +1014,7 @@ int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, 
     int32_t* ep0 = (int32_t*)(ws + L.ep0);
     hipStream_t hs = (hipStream_t)s;
     // the learners' keys travel in the launch arguments: nothing is read from seeds after this loop
-    dartmpc::PopKeys keys{};
-    for (int l = 0; l < P; ++l) {
-        keys.k[l][0] = (uint32_t)(seeds[l] & 0xffffffffu);
-        keys.k[l][1] = (uint32_t)(seeds[l] >> 32);
-    }
+    const dartmpc::PopKeys keys = pop_keys(P, seeds);
     PpoPop pop;
     pop.P = P; pop.ws_stride = L.ppo_stride; pop.idx_stride = (size_t)ppo->epochs * n;
     {
@@ -916,6 +1022,23 @@ int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, 
         sa.P = P; sa.B = B; sa.R = R; sa.out = sample;
         HIPCHK(h, dartmpc_launch_lmpc_pop_sample(&sa, hs), "sample list launch");
     }
+    // the global update's sizes, workspace and running fill, one for all learners (they share n)
+    int gm = 0, gG = 0, g_fill = g ? g->fill : 0;
+    dartmpc::global_rows(n, gm, gG);
+    const int cap = g ? g->capacity : gG;
+    const dartmpc::GlobalPopWorkspace GL = dartmpc::global_pop_workspace(P, n, cap, ppo->epochs, mb);
+    char* gws = g ? (char*)g->workspace : nullptr;
+    auto gp = [&](size_t off) { return gws ? gws + off : nullptr; };
+    int32_t* g_choice = (int32_t*)gp(GL.choice);
+    double* g_adv = (double*)gp(GL.adv);
+    double* g_ret = (double*)gp(GL.ret);
+    float* g_last = (float*)gp(GL.last_value);
+    int32_t* g_sample = (int32_t*)gp(GL.sample);
+    int32_t* g_perm = (int32_t*)gp(GL.perm);
+    double* g_stats = (double*)gp(GL.stats);
+    PpoPop gpop;
+    gpop.P = P; gpop.ws_stride = GL.ppo_stride; gpop.idx_stride = (size_t)ppo->epochs * gG;
+    const long long g_total = (long long)P * cap;
     for (int j = 0; j < cfg->iterations; ++j) {
         const int it = cfg->it0 + j;
         HIPCHK(h, hipMemsetAsync(p->nrec, 0, sizeof(int32_t) * (size_t)NI, hs), "clear nrec");
@@ -937,13 +1060,7 @@ int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, 
         if (dart_lmpc_gae_dev(NI, R, cfg->gamma, cfg->lam, p->nrec, p->rec_reward, p->rec_value, p->rec_done,
                               last_value, adv, ret, s) != DART_MPC_OK)
             return fail(h, DART_MPC_EHIP, "GAE launch");
-        {
-            dartmpc::PermPopArgs pa;
-            pa.a.n = n; pa.a.epochs = ppo->epochs; pa.a.limit = n; pa.a.key0 = pa.a.key1 = 0;
-            pa.a.iteration = (uint32_t)it; pa.a.stream = dartmpc::kStreamPerm; pa.a.perm = perm; pa.a.key_out = nullptr;
-            pa.P = P; pa.keys = keys;
-            HIPCHK(h, dartmpc_launch_lmpc_perms_pop(&pa, hs), "permutation launch");
-        }
+        HIPCHK(h, launch_perms_pop(P, keys, it, ppo->epochs, n, perm, hs, dartmpc::kStreamPerm, n), "permutation launch");
         // dart_lmpc_ppo_update_dev's launches, every learner in each
         HIPCHK(h, ppo_launch_prepare(n, rec_total, sample, adv, ret, nullptr, nullptr, ws + L.ppo, mb, hs, pop),
                "PPO prepare launch");
@@ -959,6 +1076,59 @@ int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, 
                                            p->critic, p->adam, p->adam_step, stats, nullptr, step, ws + L.ppo, mb, hs,
                                            pop), "PPO apply launch");
             }
+        }
+        if (g) {
+            // 6a: every learner draws m of its records and appends them behind the rows it holds
+            HIPCHK(h, launch_perms_pop(P, keys, it, 1, n, g_choice, hs, dartmpc::kStreamChoice, gm), "choice launch");
+            HIPCHK(h, launch_global_append_pop(g, P, g_fill, gm, n, rec_total, sample, g_choice, p->rec_obs,
+                                               p->rec_action, p->rec_logp, p->rec_value, p->rec_reward, p->rec_done,
+                                               hs), "global buffer append launch");
+            g_fill += gm;
+            const int ran = g_fill >= n ? 1 : 0;
+            const int logged_fill = g_fill;
+            if (ran) {
+                // 6b: every buffer holds G rows: one sequence each for GAE, then a full update on the learner's
+                // optimizer -- dart_lmpc_ppo_update_dev's launches on the buffers' rows, every learner in each
+                {
+                    dartmpc::CriticValueStridePopArgs va;
+                    va.a.n = 1; va.a.critic = p->critic; va.a.obs = g->obs + (size_t)(gG - 1) * kHist;
+                    va.a.value = g_last; va.P = P; va.obs_stride = cap;
+                    HIPCHK(h, dartmpc_launch_critic_value_stride_pop(&va, hs), "critic value launch (global buffer)");
+                }
+                HIPCHK(h, launch_gae_seq_pop(P, cap, gG, cfg->gamma, cfg->lam, g->reward, g->value, g->done, g_last,
+                                             g_adv, g_ret, hs), "sequence GAE launch");
+                {
+                    dartmpc::PopGlobalSampleArgs sa;
+                    sa.P = P; sa.G = gG; sa.capacity = cap; sa.out = g_sample;
+                    HIPCHK(h, dartmpc_launch_lmpc_pop_global_sample(&sa, hs), "sample list launch (global buffer)");
+                }
+                if (ppo->epochs == 0)
+                    HIPCHK(h, hipMemsetAsync(g_stats, 0, sizeof(double) * 3 * (size_t)P, hs), "clear stats");
+                HIPCHK(h, launch_perms_pop(P, keys, it, ppo->epochs, gG, g_perm, hs, dartmpc::kStreamGlobalPerm, gG),
+                       "permutation launch (global buffer)");
+                HIPCHK(h, ppo_launch_prepare(gG, g_total, g_sample, g_adv, g_ret, nullptr, nullptr, gws + GL.ppo, mb,
+                                             hs, gpop), "PPO prepare launch (global buffer)");
+                int gstep = 0;
+                for (int ep = 0; ep < ppo->epochs; ++ep) {
+                    const int32_t* row = g_perm + (size_t)ep * gG;
+                    for (int start = 0; start < gG; start += mb, ++gstep) {
+                        const int M = gG - start < mb ? gG - start : mb;
+                        HIPCHK(h, ppo_launch_grad(ppo, gG, g_total, M, g_sample, row + start, g->obs, g->action,
+                                                  g->logp, p->weights, p->critic, gws + GL.ppo, mb, hs, gpop),
+                               "PPO gradient launch (global buffer)");
+                        HIPCHK(h, ppo_launch_apply(ppo, gG, M, true, nullptr, nullptr, true, nullptr, nullptr,
+                                                   p->weights, p->critic, p->adam, p->adam_step, g_stats, nullptr,
+                                                   gstep, gws + GL.ppo, mb, hs, gpop),
+                               "PPO apply launch (global buffer)");
+                    }
+                }
+                g_fill = 0;
+            }
+            dartmpc::GlobalLogPopArgs ga;
+            ga.a.fill = logged_fill; ga.a.ran = ran; ga.a.G = gG; ga.a.stats = g_stats;
+            ga.a.row = g->global_log + (size_t)dartmpc::kGlobalLogCols * j;
+            ga.P = P; ga.row_stride = (long long)dartmpc::kGlobalLogCols * cfg->iterations;
+            HIPCHK(h, dartmpc_launch_lmpc_global_log_pop(&ga, hs), "global log launch");
         }
         if (cfg->mean_update) {
             ma.learner_B = B;
@@ -979,6 +1149,13 @@ int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, 
     return DART_MPC_OK;
 }
 
+int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                            const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                            const dart_lmpc_train_config* cfg, int P, const uint64_t* seeds, int B, int reset_rows,
+                            const dart_lmpc_train_buffers* p, void* stream) {
+    return dart_lmpc_train_pop_global_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, B, reset_rows, p, nullptr, stream);
+}
+
 // (g == nullptr: dart_lmpc_train)
 int dart_lmpc_train_global(dart_mpc_handle* h,const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                            const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
@@ -994,6 +1171,16 @@ int dart_lmpc_train_pop(dart_mpc_handle* h, const dart_plant_config* plant, cons
     DART_ENTER(h, -1);
     if (P < 1) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
     return train_host(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, B, reset_rows, p, nullptr, stream);
+}
+
+// (g == nullptr: dart_lmpc_train_pop)
+int dart_lmpc_train_pop_global(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                               const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                               const dart_lmpc_train_config* cfg, int P, const uint64_t* seeds, int B, int reset_rows,
+                               const dart_lmpc_train_buffers* p, const dart_lmpc_global_buffer* g, void* stream) {
+    DART_ENTER(h, -1);
+    if (P < 1) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+    return train_host(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, B, reset_rows, p, g, stream);
 }
 
 int dart_lmpc_train(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,

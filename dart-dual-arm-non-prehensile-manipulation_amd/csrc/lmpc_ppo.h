@@ -136,9 +136,18 @@ struct CriticValuePopArgs {     // grid (tiles of a.n, P): learner l's critic on
     CriticValueArgs a;
     int P;
 };
+// grid (tiles of a.n, P): learner l's critic on rows l obs_stride .. l obs_stride + a.n - 1 of obs, values [P][a.n]
+// (the bootstrap of a population's global update: a.n = 1, obs at row G - 1 of buffer 0, obs_stride = capacity)
+struct CriticValueStridePopArgs {
+    CriticValueArgs a;
+    int P;
+    long long obs_stride;
+};
 
 }  // namespace dartmpc
 
+extern "C" hipError_t dartmpc_launch_critic_value_stride_pop(const dartmpc::CriticValueStridePopArgs* args,
+                                                             hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_ppo_prepare_pop(const dartmpc::PpoPreparePopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_ppo_grad_pop(const dartmpc::PpoGradPopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_ppo_apply_pop(const dartmpc::PpoApplyPopArgs* args, hipStream_t stream);

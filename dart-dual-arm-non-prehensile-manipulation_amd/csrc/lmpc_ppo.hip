@@ -9,6 +9,8 @@
 // *_pop_kernel         the four above for a population of P learners in one launch (dart_lmpc_train_pop_dev): the
 //                      learner is a grid coordinate, the body is the single kernel's on arguments moved to that
 //                      learner's sample list, permutation rows, nets, Adam state and workspace (lmpc_ppo.h)
+// critic_value_stride_pop_kernel  critic_value_pop_kernel with the learners' observations a given number of rows
+//                      apart: the bootstrap values of a population's global-buffer update (row G - 1 of P buffers)
 //
 // Everything is fp32 as the reference's torch nets are, except the statistics of the normalisation, the sum of
 // squares of the gradient norm, and the running sums of the actor's forward layers and of its log-probability
@@ -459,6 +461,17 @@ __global__ __launch_bounds__(kGradThreads) void critic_value_pop_kernel(CriticVa
     critic_value_body(a);
 }
 
+// grid (tiles of a.n, P): as above, with learner y's observations obs_stride rows behind the ones before (the last
+// rows of P stacked global buffers, `capacity` rows apart); its own entry point, so that critic_value_pop_kernel
+// keeps its instructions
+__global__ __launch_bounds__(kGradThreads) void critic_value_stride_pop_kernel(CriticValueStridePopArgs p) {
+    CriticValueArgs a = p.a;
+    const size_t l = blockIdx.y;
+    a.critic += l * kPopCriticStride;
+    a.obs += l * (size_t)p.obs_stride * kPpoObs; a.value += l * (size_t)a.n;
+    critic_value_body(a);
+}
+
 }  // namespace
 
 }  // namespace dartmpc
@@ -516,5 +529,14 @@ extern "C" hipError_t dartmpc_launch_critic_value_pop(const dartmpc::CriticValue
     const int blocks = (args->a.n + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile;
     hipLaunchKernelGGL(dartmpc::critic_value_pop_kernel, dim3(blocks, args->P), dim3(dartmpc::kGradThreads), 0, stream,
                        *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_critic_value_stride_pop(const dartmpc::CriticValueStridePopArgs* args,
+                                                             hipStream_t stream) {
+    if (args->a.n <= 0 || args->P <= 0) return hipSuccess;
+    const int blocks = (args->a.n + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile;
+    hipLaunchKernelGGL(dartmpc::critic_value_stride_pop_kernel, dim3(blocks, args->P), dim3(dartmpc::kGradThreads), 0,
+                       stream, *args);
     return hipGetLastError();
 }

@@ -175,6 +175,37 @@ struct TrainLogPopArgs {
     long long row_stride;
 };
 
+// ---- the global-buffer update of a population (dart_lmpc_train_pop_global_dev) -----------------------------------
+// P buffers stacked learner-major, `capacity` rows apart: obs [P][capacity][520], ..., reward [P][capacity].  `a`
+// holds learner 0's arguments; the kernels move them to the block's learner and run the single kernel's body.
+
+// the sample lists over the buffers [P][G]: sample_l[i] = l capacity + i, the flat row of learner l's row i in the
+// stacked buffer arrays (and in adv / ret [P][capacity]); grid (ceil(G / 256), P)
+struct PopGlobalSampleArgs {
+    int P, G, capacity;
+    int32_t* out;
+};
+
+// grid (m, P): learner l gathers record sample_l[choice_l[j]] (sample [P][n], choice [P][m]; the record arrays are
+// the stacked ones, shared) into row fill + j of its own buffer
+struct GbufAppendPopArgs {
+    GbufAppendArgs a;
+    int P, capacity;
+};
+
+// one workgroup per learner: GaeSeqArgs on rows l capacity .. l capacity + G - 1, bootstrapped from last_value[l]
+struct GaeSeqPopArgs {
+    GaeSeqArgs a;               // adv, ret [P][capacity]
+    int P, capacity;
+};
+
+// one workgroup per learner: row `a.row + l row_stride` of global_log [P][iterations][6] from stats [P][3]
+struct GlobalLogPopArgs {
+    GlobalLogArgs a;
+    int P;
+    long long row_stride;
+};
+
 // Workspace of dart_lmpc_train_pop_dev (bytes from the base, every block 256-byte aligned): the single run's blocks
 // with P B instances (noise, last_value, adv, ret, ep0), the per-learner sample lists, permutations and statistics,
 // and P workspaces of the update, ppo_stride bytes apart
@@ -252,6 +283,33 @@ inline GlobalWorkspace global_workspace(int n, int epochs, int mb) {
     return w;
 }
 
+// Workspace of a population's global update (bytes from the base, every block 256-byte aligned): the choices [P][m],
+// adv and ret [P][capacity] (addressed by the sample lists, like the buffers' rows: the update's population kernels
+// reach records, adv and ret through one index), the bootstrap values [P], the sample lists [P][G], the permutations
+// [P][epochs][G], the statistics [P][3] and P workspaces of the update over G rows, ppo_stride bytes apart
+struct GlobalPopWorkspace {
+    size_t choice, adv, ret, last_value, sample, perm, stats, ppo, ppo_stride, bytes;
+};
+inline GlobalPopWorkspace global_pop_workspace(int P, int n, int capacity, int epochs, int mb) {
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    int m, Gi;
+    global_rows(n, m, Gi);
+    const size_t G = (size_t)Gi, Pn = (size_t)P, cap = (size_t)capacity;
+    GlobalPopWorkspace w;
+    size_t o = 0;
+    w.choice = o; o += al(sizeof(int32_t) * (size_t)m * Pn);
+    w.adv = o; o += al(sizeof(double) * cap * Pn);
+    w.ret = o; o += al(sizeof(double) * cap * Pn);
+    w.last_value = o; o += al(sizeof(float) * Pn);
+    w.sample = o; o += al(sizeof(int32_t) * G * Pn);
+    w.perm = o; o += al(sizeof(int32_t) * G * Pn * (size_t)(epochs > 0 ? epochs : 1));
+    w.stats = o; o += al(sizeof(double) * 3 * Pn);
+    w.ppo_stride = ppo_workspace(Gi, mb).bytes;
+    w.ppo = o; o += w.ppo_stride * Pn;
+    w.bytes = o;
+    return w;
+}
+
 }  // namespace dartmpc
 
 extern "C" hipError_t dartmpc_launch_philox(const dartmpc::PhiloxArgs* args, hipStream_t stream);
@@ -267,3 +325,7 @@ extern "C" hipError_t dartmpc_launch_lmpc_train_log(const dartmpc::TrainLogArgs*
 extern "C" hipError_t dartmpc_launch_lmpc_gbuf_append(const dartmpc::GbufAppendArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_lmpc_gae_seq(const dartmpc::GaeSeqArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_lmpc_global_log(const dartmpc::GlobalLogArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_pop_global_sample(const dartmpc::PopGlobalSampleArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_gbuf_append_pop(const dartmpc::GbufAppendPopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_gae_seq_pop(const dartmpc::GaeSeqPopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_global_log_pop(const dartmpc::GlobalLogPopArgs* args, hipStream_t stream);

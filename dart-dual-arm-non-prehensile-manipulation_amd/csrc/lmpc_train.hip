@@ -26,6 +26,12 @@
 // of learner b / learner_B, and lmpc_train_log_pop_kernel is one workgroup per learner that visits its entries of the
 // stacked logs in the single run's flat order, so that every fp64 sum has the single run's order.  The kernels of
 // one learner are untouched instantiations: the bodies are shared, the arguments moved to the learner.
+//
+// The population's global-buffer update (dart_lmpc_train_pop_global_dev; P buffers stacked `capacity` rows apart):
+// lmpc_perm_pop_kernel with limit = m draws every learner's choice, lmpc_gbuf_append_pop_kernel (grid (m, P)),
+// lmpc_gae_seq_kernel<GaeSeqPopArgs> (a workgroup per learner) and lmpc_global_log_pop_kernel run the single
+// kernels' bodies on the learner's rows, and lmpc_pop_global_sample_kernel writes the sample lists l capacity + i
+// through which the update's population kernels reach the buffers' rows and adv / ret [P][capacity].
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -315,7 +321,7 @@ constexpr int kAppendThreads = 128;
 constexpr int kObsVec = kObsN / 4;                  // 130 16-byte pieces of an observation row
 static_assert(kObsN % 4 == 0, "an observation row is a whole number of 16-byte pieces");
 
-__global__ __launch_bounds__(kAppendThreads) void lmpc_gbuf_append_kernel(GbufAppendArgs a) {
+__device__ __forceinline__ void gbuf_append_body(const GbufAppendArgs& a) {
     const int j = blockIdx.x, t = threadIdx.x;
     if (j >= a.m) return;                           // block-uniform, as are the two below
     const int c = a.choice[j];
@@ -336,6 +342,25 @@ __global__ __launch_bounds__(kAppendThreads) void lmpc_gbuf_append_kernel(GbufAp
     if (t == 67) reinterpret_cast<uint64_t*>(a.reward)[d] = reinterpret_cast<const uint64_t*>(a.rec_reward)[s];
 }
 
+__global__ __launch_bounds__(kAppendThreads) void lmpc_gbuf_append_kernel(GbufAppendArgs a) { gbuf_append_body(a); }
+
+// grid (m, P): learner y's sample list and choice, its own buffer `capacity` rows behind the one before
+__global__ __launch_bounds__(kAppendThreads) void lmpc_gbuf_append_pop_kernel(GbufAppendPopArgs p) {
+    GbufAppendArgs a = p.a;
+    const size_t l = blockIdx.y, r0 = l * (size_t)p.capacity;
+    a.sample += l * (size_t)a.n; a.choice += l * (size_t)a.m;
+    a.obs += r0 * kObsN; a.action += r0 * PA;
+    a.logp += r0; a.value += r0; a.reward += r0; a.done += r0;
+    gbuf_append_body(a);
+}
+
+// grid (ceil(G / 256), P)
+__global__ __launch_bounds__(kRngThreads) void lmpc_pop_global_sample_kernel(PopGlobalSampleArgs a) {
+    const int i = blockIdx.x * kRngThreads + threadIdx.x, l = blockIdx.y;
+    if (i >= a.G) return;
+    a.out[(size_t)l * a.G + i] = l * a.capacity + i;
+}
+
 constexpr int kSeqThreads = 1024, kSeqWaves = kSeqThreads / 64;
 
 // One workgroup.  Row t is the affine map gae -> delta_t + c_t gae, c_t = gamma lam (1 - done_t); adv_t is the
@@ -343,8 +368,26 @@ constexpr int kSeqThreads = 1024, kSeqWaves = kSeqThreads / 64;
 // Hillis-Steele suffix scan in each wave64 (6 levels of shuffles), the 16 wave totals scanned the same way in wave 0
 // (4 levels), one composition with the later waves' suffix, and one with the carry, the advantage of the first row
 // of the tile behind (0 behind the last tile, where that composition is exact).  Rows past G are the identity map.
-__global__ __launch_bounds__(kSeqThreads) void lmpc_gae_seq_kernel(GaeSeqArgs a) {
+//
+// One statement of the arithmetic, two entry points: lmpc_gae_seq_kernel<GaeSeqArgs> (one sequence, one workgroup)
+// and lmpc_gae_seq_kernel<GaeSeqPopArgs> (a workgroup per learner).  The two are instantiations of the kernel and
+// not callers of a shared __forceinline__ body, as the other kernels of this family are: with the tile loop inlined
+// from a callee the compiler inverts the loop's exit branch (s_cmp_lg / scc0 for s_cmp_eq / scc1), and the single
+// kernel has to keep its instructions; as an instantiation it does.
+__device__ __forceinline__ const GaeSeqArgs& seq_args(const GaeSeqArgs& a) { return a; }
+// learner blockIdx.x: its rows of the stacked buffers, its bootstrap value
+__device__ __forceinline__ GaeSeqArgs seq_args(const GaeSeqPopArgs& p) {
+    GaeSeqArgs a = p.a;
+    const size_t l = blockIdx.x, r0 = l * (size_t)p.capacity;
+    a.reward += r0; a.value += r0; a.done += r0; a.last_value += l;
+    a.adv += r0; a.ret += r0;
+    return a;
+}
+
+template <class Args>
+__global__ __launch_bounds__(kSeqThreads) void lmpc_gae_seq_kernel(Args p) {
 #pragma clang fp contract(off)
+    const GaeSeqArgs a = seq_args(p);
     __shared__ double wa[kSeqWaves], wc[kSeqWaves];
     __shared__ double carry_sh;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -396,13 +439,24 @@ __global__ __launch_bounds__(kSeqThreads) void lmpc_gae_seq_kernel(GaeSeqArgs a)
     }
 }
 
-__global__ __launch_bounds__(64) void lmpc_global_log_kernel(GlobalLogArgs a) {
+__device__ __forceinline__ void global_log_body(const GlobalLogArgs& a) {
     const int t = threadIdx.x;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     if (t == 0) a.row[0] = (double)a.fill;
     if (t == 1) a.row[1] = (double)a.ran;
     if (t == 2) a.row[2] = (double)a.G;
     if (t >= 3 && t < kGlobalLogCols) a.row[t] = a.ran ? a.stats[t - 3] : nan;
+}
+
+__global__ __launch_bounds__(64) void lmpc_global_log_kernel(GlobalLogArgs a) { global_log_body(a); }
+
+// one workgroup per learner: its row of global_log [P][iterations][6], its statistics of stats [P][3]
+__global__ __launch_bounds__(64) void lmpc_global_log_pop_kernel(GlobalLogPopArgs p) {
+    GlobalLogArgs a = p.a;
+    const size_t l = blockIdx.x;
+    a.stats += 3 * l;
+    a.row += l * p.row_stride;
+    global_log_body(a);
 }
 
 inline int blocks_of(long long n, int per) { return (int)((n + per - 1) / per); }
@@ -485,11 +539,36 @@ extern "C" hipError_t dartmpc_launch_lmpc_gbuf_append(const GbufAppendArgs* a, h
 
 extern "C" hipError_t dartmpc_launch_lmpc_gae_seq(const GaeSeqArgs* a, hipStream_t s) {
     if (a->G <= 0) return hipSuccess;
-    hipLaunchKernelGGL(lmpc_gae_seq_kernel, dim3(1), dim3(kSeqThreads), 0, s, *a);
+    hipLaunchKernelGGL(lmpc_gae_seq_kernel<GaeSeqArgs>, dim3(1), dim3(kSeqThreads), 0, s, *a);
     return hipGetLastError();
 }
 
 extern "C" hipError_t dartmpc_launch_lmpc_global_log(const GlobalLogArgs* a, hipStream_t s) {
     hipLaunchKernelGGL(lmpc_global_log_kernel, dim3(1), dim3(64), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_pop_global_sample(const PopGlobalSampleArgs* a, hipStream_t s) {
+    if (a->P <= 0 || a->G <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_pop_global_sample_kernel, dim3(blocks_of(a->G, kRngThreads), a->P), dim3(kRngThreads), 0, s,
+                       *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_gbuf_append_pop(const GbufAppendPopArgs* a, hipStream_t s) {
+    if (a->a.m <= 0 || a->P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_gbuf_append_pop_kernel, dim3(a->a.m, a->P), dim3(kAppendThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_gae_seq_pop(const GaeSeqPopArgs* a, hipStream_t s) {
+    if (a->a.G <= 0 || a->P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_gae_seq_kernel<GaeSeqPopArgs>, dim3(a->P), dim3(kSeqThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_global_log_pop(const GlobalLogPopArgs* a, hipStream_t s) {
+    if (a->P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lmpc_global_log_pop_kernel, dim3(a->P), dim3(64), 0, s, *a);
     return hipGetLastError();
 }

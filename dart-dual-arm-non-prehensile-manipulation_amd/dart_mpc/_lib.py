@@ -57,6 +57,8 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_lmpc_global_append", "dart_lmpc_gae_seq_dev", "dart_lmpc_gae_seq", "dart_lmpc_train_global_dev",
            "dart_lmpc_train_global",
            "dart_lmpc_train_pop_workspace_bytes", "dart_lmpc_train_pop_dev", "dart_lmpc_train_pop",
+           "dart_lmpc_global_pop_workspace_bytes", "dart_lmpc_choice_pop_dev", "dart_lmpc_global_append_pop_dev",
+           "dart_lmpc_gae_seq_pop_dev", "dart_lmpc_train_pop_global_dev", "dart_lmpc_train_pop_global",
            "dart_pmpc_lm_loop_step_dev", "dart_pmpc_lm_rollout_dev", "dart_pmpc_lm_rollout",
            "dart_rmpc_lm_loop_step_dev", "dart_rmpc_lm_rollout_dev", "dart_rmpc_lm_rollout")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
@@ -401,6 +403,18 @@ def lib():
         L.dart_lmpc_train_pop_workspace_bytes.restype = ctypes.c_size_t
         for fn in (L.dart_lmpc_train_pop_dev, L.dart_lmpc_train_pop):
             fn.argtypes = [vp] * 6 + [ci, vp, ci, ci, vp, vp]
+            fn.restype = ctypes.c_int
+    if hasattr(L, "dart_lmpc_train_pop_global_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+        L.dart_lmpc_global_pop_workspace_bytes.argtypes = [ci] * 5
+        L.dart_lmpc_global_pop_workspace_bytes.restype = ctypes.c_size_t
+        L.dart_lmpc_choice_pop_dev.argtypes = [ci, vp, ci, ci, ci, vp, vp]
+        L.dart_lmpc_global_append_pop_dev.argtypes = [vp, ci, ci, ci, ci] + [vp] * 9
+        L.dart_lmpc_gae_seq_pop_dev.argtypes = [ci, ci, ci, cd, cd] + [vp] * 7
+        for fn in (L.dart_lmpc_train_pop_global_dev, L.dart_lmpc_train_pop_global):
+            fn.argtypes = [vp] * 6 + [ci, vp, ci, ci, vp, vp, vp]
+        for fn in (L.dart_lmpc_choice_pop_dev, L.dart_lmpc_global_append_pop_dev, L.dart_lmpc_gae_seq_pop_dev,
+                   L.dart_lmpc_train_pop_global_dev, L.dart_lmpc_train_pop_global):
             fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
@@ -1226,14 +1240,41 @@ class LmpcSolver(Solver):
         if rc != 0:
             self._err(rc, "dart_lmpc_train_pop_dev")
 
+    def train_pop_global_dev(self, P, seeds, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state,
+                             cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, gbuf, pool=None, plant=None,
+                             stream=0):
+        """``train_pop_dev`` with the global-buffer update (dart_lmpc_train_pop_global_dev): ``gbuf`` is a
+        ``global_buffer`` struct of device pointers to P buffers stacked learner-major, ``capacity`` rows apart (obs
+        [P, capacity, 520], ..., ``global_log`` [P, iterations, 6], ``workspace`` of ``global_pop_workspace_bytes``;
+        ``fill`` is one number for all learners), or None for ``train_pop_dev`` itself.  Learner l is bit for bit
+        ``train_global_dev`` on its arrays, its buffer and seed ``seeds[l]``."""
+        plant = plant or plant_config()
+        seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(-1)
+        if seeds is not None and seeds.size != int(P):
+            raise DartMPCError(f"train_pop_global_dev needs {P} seeds, got {seeds.size}")
+        buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
+                             + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
+                             + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
+                             + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
+                             + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
+        rc = lib().dart_lmpc_train_pop_global_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
+                                                  ctypes.byref(ppo_cfg), ctypes.byref(tcfg), int(P), _ptr(seeds),
+                                                  int(B), int(reset_rows), buf,
+                                                  ctypes.byref(gbuf) if gbuf is not None else None, stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_train_pop_global_dev")
+
     def train_pop(self, P, seeds, target, plant_pvec, state, cstate, logs, clogs, rec, pcfg, weights, critic, current_k,
                   adam, adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None,
-                  pool=None, plant=None):
+                  pool=None, plant=None, global_buffer=None, global_log=None):
         """Host arrays (blocking, dart_lmpc_train_pop): ``train`` for ``P`` learners, all arrays stacked as
         ``train_pop_dev`` takes them (``ppo.population_stack`` builds them, ``ppo.train_population`` wraps this) and
         updated in place: ``weights`` [P, 39748], ``critic`` [P, POP_CRITIC_STRIDE], ``current_k`` [P B, 34], ``adam``
         [P, 2, 77317], ``adam_step`` [P], ``train_log`` [P, iterations, 12], ``best_return`` [P], ``best_weights``
-        [P, 77317], ``best_iter`` [P]; ``state`` / ``cstate`` hold P B instances."""
+        [P, 77317], ``best_iter`` [P]; ``state`` / ``cstate`` hold P B instances.  With ``global_buffer`` (a
+        ``ppo.new_population_global_buffer`` dict: P stacked buffers and one ``fill``) every iteration also runs the
+        global-buffer update (dart_lmpc_train_pop_global): the dict's arrays and ``fill`` are updated in place and
+        ``global_log`` [P, iterations, 6] (float64) receives one row per learner and iteration."""
         P, K = int(P), int(tcfg.steps)
         NI = state["x"].shape[0]
         B = NI // max(P, 1)
@@ -1263,6 +1304,15 @@ class LmpcSolver(Solver):
                 + _host_ptrs(LMPC_LOOP_LOGS, logs, (K, NI)) + _host_ptrs(LMPC_COLLECT_LOGS, clogs, (K, NI))
                 + _host_ptrs(LMPC_COLLECT_REC, rec, (R, NI)) + [_ptr(a) for a in tail] + [None])
         buf = _train_buffers([0 if q is None else q.value for q in ptrs])
+        if global_buffer is not None:
+            g = _host_global(global_buffer, nl * int(tcfg.iterations), global_log, learners=nl)
+            rc = lib().dart_lmpc_train_pop_global(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
+                                                  ctypes.byref(ppo_cfg), ctypes.byref(tcfg), P, _ptr(seeds), B,
+                                                  reset_rows, buf, ctypes.byref(g), None)
+            if rc != 0:
+                self._err(rc, "dart_lmpc_train_pop_global")
+            global_buffer["fill"] = global_fill_after(R * B, g.fill, int(tcfg.iterations))
+            return
         rc = lib().dart_lmpc_train_pop(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
                                        ctypes.byref(ppo_cfg), ctypes.byref(tcfg), P, _ptr(seeds), B, reset_rows, buf,
                                        None)
@@ -1662,6 +1712,36 @@ def global_workspace_bytes(n, epochs, mini_batch_size):
     return b
 
 
+def global_pop_workspace_bytes(P, n, capacity, epochs, mini_batch_size):
+    """Bytes of the device workspace of a population's global update (``LmpcSolver.train_pop_global_dev``) for P
+    buffers of ``capacity`` rows; 0 for a bad shape."""
+    return int(lib().dart_lmpc_global_pop_workspace_bytes(int(P), int(n), int(capacity), int(epochs),
+                                                          int(mini_batch_size)))
+
+
+def choice_pop_dev(seeds, iteration, n, m, choice_out, stream=0):
+    """dart_lmpc_choice_pop_dev: ``choice_dev`` for every seed of ``seeds`` in one launch, int32 [P, m]."""
+    seeds = np.ascontiguousarray(seeds, np.uint64).reshape(-1)
+    _rc(lib().dart_lmpc_choice_pop_dev(int(seeds.size), _ptr(seeds), int(iteration), int(n), int(m), _vp(choice_out),
+                                       stream or None), "dart_lmpc_choice_pop_dev")
+
+
+def global_append_pop_dev(g, P, m, n, rec_total, sample, choice, rec, stream=0):
+    """dart_lmpc_global_append_pop_dev: ``global_append_dev`` for P learners in one launch; ``g`` holds the P buffers
+    stacked ``g.capacity`` rows apart, ``sample`` is [P, n] and ``choice`` [P, m]."""
+    _rc(lib().dart_lmpc_global_append_pop_dev(ctypes.byref(g), int(P), int(m), int(n), int(rec_total), _vp(sample),
+                                              _vp(choice), *[_vp(rec[k]) for k, _, _ in LMPC_COLLECT_REC],
+                                              stream or None), "dart_lmpc_global_append_pop_dev")
+
+
+def gae_seq_pop_dev(P, capacity, G, gamma, lam, reward, value, done, last_value, adv, ret, stream=0):
+    """dart_lmpc_gae_seq_pop_dev: ``gae_seq_dev`` for P sequences in one launch, arrays [P, capacity],
+    ``last_value`` [P]."""
+    _rc(lib().dart_lmpc_gae_seq_pop_dev(int(P), int(capacity), int(G), float(gamma), float(lam), _vp(reward),
+                                        _vp(value), _vp(done), _vp(last_value), _vp(adv), _vp(ret), stream or None),
+        "dart_lmpc_gae_seq_pop_dev")
+
+
 def global_buffer(arrays, capacity, fill, global_log=0, workspace=0) -> GlobalBuffer:
     """``struct dart_lmpc_global_buffer`` from addresses (ints): ``arrays`` maps obs, action, logp, value, reward,
     done to device (or host) pointers of ``capacity`` rows."""
@@ -1673,12 +1753,16 @@ def global_buffer(arrays, capacity, fill, global_log=0, workspace=0) -> GlobalBu
     return g
 
 
-def _host_global(buf, need_log_rows=None, global_log=None):
-    """GlobalBuffer over the host arrays of a ``ppo.new_global_buffer`` dict (checked: dtype, size, contiguity)."""
-    cap = int(np.asarray(buf["logp"]).size)
+def _host_global(buf, need_log_rows=None, global_log=None, learners=1):
+    """GlobalBuffer over the host arrays of a ``ppo.new_global_buffer`` dict (checked: dtype, size, contiguity);
+    ``learners`` > 1: of a ``ppo.new_population_global_buffer`` dict, ``learners`` buffers stacked."""
+    total = int(np.asarray(buf["logp"]).size)
+    if learners < 1 or total % learners:
+        raise DartMPCError(f"global_buffer: {total} rows are not {learners} buffers of equal capacity")
+    cap = total // learners
     ptrs = {}
     for name, width, dt in LMPC_GLOBAL_ARRAYS:
-        ptrs[name] = _inplace(buf[name], dt, cap * max(width, 1), "global_buffer[%r]" % name).ctypes.data
+        ptrs[name] = _inplace(buf[name], dt, total * max(width, 1), "global_buffer[%r]" % name).ctypes.data
     log = 0
     if need_log_rows is not None:
         log = _inplace(global_log, np.float64, GLOBAL_LOG_COLS * need_log_rows, "global_log").ctypes.data

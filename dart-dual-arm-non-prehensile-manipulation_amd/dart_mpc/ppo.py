@@ -255,7 +255,10 @@ def population_stack(members):
     (``new_best``), and optionally ``pool`` (dict of [rows, B, ..] arrays), ``current_k`` [B, 34], ``weights`` [39748]
     and ``critic`` [37569].  Returns the same keys with the instances stacked learner-major (instance l B + b), ``adam``
     [P, 2, 77317], ``adam_step`` [P], ``best`` as ``new_population_best``, ``weights`` [P, 39748] and ``critic``
-    [P, POP_CRITIC_STRIDE] (``stack_critics``)."""
+    [P, POP_CRITIC_STRIDE] (``stack_critics``).  Members that carry a ``global_buffer`` (``new_global_buffer``
+    dicts) give the population's: arrays [P, capacity, ..] and the one ``fill`` all learners share; members that
+    differ in fill or capacity raise ``DartMPCError`` (they share n, so a population's buffers fill in step)."""
+    from . import _lib
     cat = lambda arrs, axis=0: np.ascontiguousarray(np.concatenate([np.asarray(a) for a in arrs], axis=axis))
     m0 = members[0]
     out = dict(target=cat([m["target"] for m in members]), plant_pvec=cat([m["plant_pvec"] for m in members]),
@@ -275,6 +278,22 @@ def population_stack(members):
                                                         for m in members]))
     if "critic" in m0:
         out["critic"] = stack_critics([m["critic"] for m in members])
+    if m0.get("global_buffer") is not None:
+        bufs = [m.get("global_buffer") for m in members]
+        if any(b is None for b in bufs):
+            raise _lib.DartMPCError("population_stack: some members have a global_buffer and some have none")
+        fills = {int(b["fill"]) for b in bufs}
+        caps = {int(np.asarray(b["logp"]).size) for b in bufs}
+        if len(fills) != 1:
+            raise _lib.DartMPCError(f"population_stack: members differ in global_buffer fill ({sorted(fills)})")
+        if len(caps) != 1:
+            raise _lib.DartMPCError(f"population_stack: members differ in global_buffer capacity ({sorted(caps)})")
+        cap = caps.pop()
+        gb = {name: np.ascontiguousarray(np.stack(
+                  [np.asarray(b[name], dt).reshape((cap, width) if width else (cap,)) for b in bufs]))
+              for name, width, dt in _lib.LMPC_GLOBAL_ARRAYS}
+        gb["fill"] = fills.pop()
+        out["global_buffer"] = gb
     return out
 
 
@@ -282,7 +301,10 @@ def population_member(l, P, pop):
     """Learner ``l`` of the ``P`` in ``pop`` (a dict as ``population_stack`` returns it; keys it lacks are left out),
     in the shapes ``train_device`` and ``save_checkpoint`` take: views of its slice of every stacked array -- writing
     through them writes the population -- except ``pool``, whose slice is not contiguous and is copied (it is only
-    read).  ``critic`` is the 37569 weights of its row, without the pad."""
+    read).  ``critic`` is the 37569 weights of its row, without the pad.  ``global_buffer`` (when the population
+    has one) is the learner's buffer as views [capacity, ..] plus the shared ``fill``: the dict ``train_device(...,
+    global_buffer=...)`` and ``save_checkpoint(..., global_buffer=...)`` take, so a member can be checkpointed in the
+    middle of a fill period and continued alone."""
     from . import _lib
     l, P = int(l), int(P)
     if not 0 <= l < P:
@@ -305,6 +327,9 @@ def population_member(l, P, pop):
         out["weights"] = pop["weights"][l]
     if "critic" in pop:
         out["critic"] = pop["critic"][l, :_lib.CRITIC_NWEIGHTS]
+    if pop.get("global_buffer") is not None:
+        gb = pop["global_buffer"]
+        out["global_buffer"] = dict({name: gb[name][l] for name, _, _ in _lib.LMPC_GLOBAL_ARRAYS}, fill=int(gb["fill"]))
     return out
 
 
@@ -325,15 +350,19 @@ def population_noise(seeds, iteration, steps, B):
 
 def train_population(solver, policies, target, plant_pvec, state, cstate, adam, adam_step, best, steps, seeds,
                      iterations=1, it0=0, rcfg=None, pool=None, prm=None, gamma=0.99, lam=0.95, mean_update=True,
-                     track_best=True, epochs=8, mini_batch_size=64, out=None, **hyper):
+                     track_best=True, epochs=8, mini_batch_size=64, out=None, global_buffer=None, **hyper):
     """``train_device`` for a population: ``policies`` is a list of P ``LmpcPolicy(B, ...)`` that share one config,
     the other arrays are stacked learner-major as ``population_stack`` lays them out (``target`` [P B, 8], ``state``
     / ``cstate`` of P B instances, ``adam`` [P, 2, 77317], ``adam_step`` [P], ``best`` = ``new_population_best(P)``,
     ``pool`` [rows, P B, ..]), ``seeds`` are P integers.  All learners run in the same launches
     (``LmpcSolver.train_pop``); learner l is bit for bit ``train_device`` on ``population_member(l, ...)`` with
     ``seed=seeds[l]``.  Updated in place: the stacked arrays, and every policy's ``weights``, ``critic_weights`` and
-    ``current_k``.  There is no global-buffer update for a population.  Returns one list of ``TRAIN_LOG_FIELDS``
-    dicts (one per iteration) per learner."""
+    ``current_k``.  Returns one list of ``TRAIN_LOG_FIELDS`` dicts (one per iteration) per learner.
+
+    With ``global_buffer`` (``new_population_global_buffer(P, n)``, or ``population_stack``'s) every iteration also
+    runs the global-buffer update for every learner (``LmpcSolver.train_pop`` with the buffer): learner l is then bit
+    for bit ``train_device(..., global_buffer=population_member(l, ...)["global_buffer"])``.  The dict is updated in
+    place, ``fill`` included, and every returned row gains the keys of ``_lib.GLOBAL_LOG_FIELDS``."""
     from . import _lib
     P = len(policies)
     rcfg = rcfg if rcfg is not None else _lib.reward_config()
@@ -354,16 +383,39 @@ def train_population(solver, policies, target, plant_pvec, state, cstate, adam, 
     logs, clogs = _lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, NI), _lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, NI)
     rec = _lib.loop_logs(_lib.LMPC_COLLECT_REC, R, NI)
     train_log = np.full((P, int(iterations), _lib.TRAIN_LOG_COLS), np.nan)
+    global_log = None if global_buffer is None else np.full((P, int(iterations), _lib.GLOBAL_LOG_COLS), np.nan)
     solver.train_pop(P, seeds, target, plant_pvec, state, cstate, logs, clogs, rec, policies[0].cfg, weights, critic,
                      current_k, adam, adam_step, train_log, best["best_return"], best["best_weights"],
-                     best["best_iter"], cfg, tcfg, rcfg=rcfg, prm=prm, pool=pool)
+                     best["best_iter"], cfg, tcfg, rcfg=rcfg, prm=prm, pool=pool, global_buffer=global_buffer,
+                     global_log=global_log)
     for l, p in enumerate(policies):
         p.weights[...] = weights[l].reshape(p.weights.shape)
         p.critic_weights[...] = critic[l, :_lib.CRITIC_NWEIGHTS].reshape(p.critic_weights.shape)
         p.current_k[...] = current_k[l * B:(l + 1) * B].reshape(p.current_k.shape)
     if out is not None:
         out.update(logs=logs, clogs=clogs, rec=rec, train_log=train_log, weights=weights, critic=critic)
-    return [[dict(zip(_lib.TRAIN_LOG_FIELDS, (float(v) for v in row))) for row in train_log[l]] for l in range(P)]
+    rows = [[dict(zip(_lib.TRAIN_LOG_FIELDS, (float(v) for v in row))) for row in train_log[l]] for l in range(P)]
+    if global_buffer is not None:
+        if out is not None:
+            out.update(global_log=global_log)
+        for l in range(P):
+            for row, grow in zip(rows[l], global_log[l]):
+                row.update(zip(_lib.GLOBAL_LOG_FIELDS, (float(v) for v in grow)))
+    return rows
+
+
+def new_population_global_buffer(P, n):
+    """The global buffers of a fresh population of ``P`` learners with ``n`` samples per iteration each: zeroed
+    arrays [P, G, ..] of capacity G (``_lib.global_rows``), stacked learner-major, and the one ``fill`` = 0 all
+    learners share."""
+    from . import _lib
+    P = int(P)
+    if not 1 <= P <= _lib.POP_MAX:
+        raise _lib.DartMPCError(f"new_population_global_buffer: 1 <= P <= {_lib.POP_MAX}, got {P}")
+    _, G = _lib.global_rows(n)
+    buf = {name: np.zeros((P, G, width) if width else (P, G), dt) for name, width, dt in _lib.LMPC_GLOBAL_ARRAYS}
+    buf["fill"] = 0
+    return buf
 
 
 def new_global_buffer(n):

@@ -1059,8 +1059,8 @@ int dart_mpc_nw(int N);
  *
  * The launch sequence per iteration is dart_lmpc_train_dev's, each step issued once for the whole population (the
  * update: prepare once, then gradient + apply per mini-batch index with every learner in each launch).  Calls chain
- * through it0 as the single entry's do.  There is no population form of the global-buffer update
- * (dart_lmpc_train_global), of dart_lmpc_rollout or of dart_lmpc_collect. */
+ * through it0 as the single entry's do.  The global-buffer update has its population form below
+ * (dart_lmpc_train_pop_global); dart_lmpc_rollout and dart_lmpc_collect have none. */
 #define DART_LMPC_POP_MAX 32
 #define DART_LMPC_POP_CRITIC_STRIDE 37572
 
@@ -1082,6 +1082,64 @@ int dart_lmpc_train_pop(dart_mpc_handle *h, const dart_plant_config *plant, cons
                         const dart_lmpc_reward_config *rcfg, const dart_lmpc_ppo_config *ppo,
                         const dart_lmpc_train_config *cfg, int P, const uint64_t *seeds, int B, int reset_rows,
                         const dart_lmpc_train_buffers *buf, void *hip_stream);
+
+/* The population with the global-buffer update (added within ABI 8: new entries only): learner l is, bit for bit,
+ * the run dart_lmpc_train_global(_dev) gives for its arrays, its buffer and cfg->seed = seeds[l] alone.
+ *
+ * Layout: one dart_lmpc_global_buffer holds the P buffers stacked learner-major, `capacity` rows apart: obs
+ * [P][capacity][520] (capacity * 520 * 4 bytes is a multiple of 16, so every learner's obs is 16-byte aligned when
+ * the base is), action [P][capacity][34], logp, value, done [P][capacity], reward [P][capacity] (fp64), global_log
+ * [P][iterations][6].  All learners share n = R B, so they share m, G and the fill period: fill is one number for the
+ * whole population, known to the host and advanced with dart_lmpc_global_fill_after as for one learner.  The
+ * workspace is dart_lmpc_global_pop_workspace_bytes; it depends on capacity, because the sequences' advantages and
+ * returns are laid out [P][capacity] like the buffers' rows: learner l's sample list over its buffer is
+ * i -> l capacity + i, and the update's kernels reach rows, advantages and returns through that one index.
+ *
+ * Per iteration: dart_lmpc_train_pop_dev's sequence, and between the local update and the parameter write steps 6a
+ * and 6b of dart_lmpc_train_global_dev, each issued once for all learners: the choices [P][m] (learner l's is
+ * dart_lmpc_choice_dev's for seeds[l]), the append of row sample_l[choice_l[j]] of the stacked records into row
+ * fill + j of buffer l, and when the fill reaches n the critics' values on row G - 1 of every buffer, the sequence
+ * GAE with one workgroup per learner, the sample lists, the permutations of stream 3 over G per learner, and the
+ * update's launches on the buffers' rows with every learner's own Adam state and step count. */
+
+/* Bytes of the population's global workspace; 0 for a bad shape (P outside 1 .. DART_LMPC_POP_MAX, capacity < G,
+ * or what dart_lmpc_global_workspace_bytes refuses). */
+size_t dart_lmpc_global_pop_workspace_bytes(int P, int n, int capacity, int epochs, int mini_batch_size);
+
+/* The steps of the population's global update alone, device pointers.  choice_out [P][m]: row l is
+ * dart_lmpc_choice_dev(seeds[l], ...).  Append: g holds P stacked buffers, sample [P][n], choice [P][m]; learner l
+ * writes rows g->fill .. g->fill + m - 1 of its buffer and nothing else.  Sequence GAE: reward, value, done, adv, ret
+ * [P][capacity], last_value [P]; rows >= G of every learner are left untouched.  EINVAL as the single entries', and
+ * for P outside 1 .. DART_LMPC_POP_MAX, null seeds, capacity < G. */
+int dart_lmpc_choice_pop_dev(int P, const uint64_t *seeds, int iteration, int n, int m, int32_t *choice_out,
+                             void *hip_stream);
+int dart_lmpc_global_append_pop_dev(const dart_lmpc_global_buffer *g, int P, int m, int n, int rec_rows_times_PB,
+                                    const int32_t *sample, const int32_t *choice,
+                                    const float *rec_obs, const float *rec_action, const float *rec_logp,
+                                    const float *rec_value, const double *rec_reward, const float *rec_done,
+                                    void *hip_stream);
+int dart_lmpc_gae_seq_pop_dev(int P, int capacity, int G, double gamma, double lam, const double *reward,
+                              const float *value, const float *done, const float *last_value, double *adv,
+                              double *ret, void *hip_stream);
+
+/* Device pointers.  With g == NULL it is dart_lmpc_train_pop_dev, launch for launch.  DART_MPC_EINVAL before any
+ * device work: what dart_lmpc_train_pop_dev refuses, what dart_lmpc_train_global_dev refuses of g (a fill that is
+ * negative, >= n or not a multiple of m, capacity < G, a null field, obs not 16-byte aligned), rec_obs not 16-byte
+ * aligned.  Calls chain: g->fill of the next call is dart_lmpc_global_fill_after(n, g->fill, iterations). */
+int dart_lmpc_train_pop_global_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                                   const dart_lmpc_policy_config *pcfg, const dart_lmpc_reward_config *rcfg,
+                                   const dart_lmpc_ppo_config *ppo, const dart_lmpc_train_config *cfg, int P,
+                                   const uint64_t *seeds, int B, int reset_rows, const dart_lmpc_train_buffers *buf,
+                                   const dart_lmpc_global_buffer *g, void *hip_stream);
+
+/* Host pointers: as dart_lmpc_train_pop, and of every learner's buffer the held rows (0 .. g->fill - 1) are staged in
+ * once and the rows held at the end staged out; other rows of the host arrays are left untouched.  global_log
+ * [P][iterations][6] comes down. */
+int dart_lmpc_train_pop_global(dart_mpc_handle *h, const dart_plant_config *plant,
+                               const dart_lmpc_policy_config *pcfg, const dart_lmpc_reward_config *rcfg,
+                               const dart_lmpc_ppo_config *ppo, const dart_lmpc_train_config *cfg, int P,
+                               const uint64_t *seeds, int B, int reset_rows, const dart_lmpc_train_buffers *buf,
+                               const dart_lmpc_global_buffer *g, void *hip_stream);
 
 /* ABI version (DART_MPC_ABI_VERSION) of the loaded library. */
 int dart_mpc_abi_version(void);

@@ -17,7 +17,10 @@ with the checkpoint, so a run can stop in the middle of a fill period.
 With --population P (resident only) P independent learners -- their own instances, reset pools, initial nets and
 seeds (--seeds a,b,...; default 0 .. P-1) -- train in the launches of one (dart_mpc.ppo.train_population,
 LmpcSolver.train_pop); a line per learner and iteration, and --checkpoint PATH writes one checkpoint per member
-(PATH.member<l>.npz, each of which --resume continues alone).
+(PATH.member<l>.npz, each of which --resume continues alone).  --population with --global-update runs the
+global-buffer update of every learner in the same launches (ppo.new_population_global_buffer); every member's
+checkpoint then holds that member's buffer, so --resume --global-update continues it as a single run, in the middle
+of a fill period too.
 The loop state, the collection state, the targets and the plants carry over from iteration to iteration.
 Prints the mean return of the episodes that ended, per iteration.
 Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps] [--update device|torch|resident]
@@ -62,8 +65,8 @@ if global_update:
         sys.exit("--global-update goes with --update resident")
 ckpt_out, ckpt_in, seed = _option("--checkpoint"), _option("--resume"), int(_option("--seed") or 0)
 population, pop_seeds = int(_option("--population") or 0), _option("--seeds")
-if population and (update != "resident" or global_update or ckpt_in):
-    sys.exit("--population goes with --update resident, without --global-update and --resume")
+if population and (update != "resident" or ckpt_in):
+    sys.exit("--population goes with --update resident, without --resume")
 if (ckpt_out or ckpt_in) and update != "resident":
     sys.exit("--checkpoint and --resume go with --update resident")
 iters = int(argv[0]) if len(argv) > 0 else 5
@@ -102,10 +105,13 @@ def train_population():
                                       "reset_target": np.stack([q["target"][:B] for q in Q]),
                                       "reset_pvec": np.stack([q["pvec"][:B] for q in Q])}))
         H = ppo.population_stack(members)
+        gbuf = ppo.new_population_global_buffer(P_, B * (K // int(rcfg.record_every))) if global_update else None
+        if gbuf is not None:
+            H["global_buffer"] = gbuf
         rows = ppo.train_population(solver, policies, H["target"], H["plant_pvec"], H["state"], H["cstate"], H["adam"],
                                     H["adam_step"], H["best"], K, sd, iterations=iters, rcfg=rcfg, pool=H["pool"],
                                     gamma=GAMMA, lam=LAM, epochs=8, mini_batch_size=64, clip_eps=0.2, vf_coef=0.25,
-                                    ent_coef=0.01)
+                                    ent_coef=0.01, global_buffer=gbuf)
         for j in range(iters):
             for l in range(P_):
                 r = rows[l][j]
@@ -114,13 +120,19 @@ def train_population():
                       f"{r['mean_step_reward']:.3f}, policy loss {r['policy_loss']:.4f}, value loss "
                       f"{r['value_loss']:.4f}, entropy {r['entropy']:.3f}, best return {r['best_return']:.2f}"
                       f"{' (snapshot)' if r['snapshot'] else ''}", flush=True)
+                if gbuf is not None:
+                    tail = (f", update on {int(r['global_rows'])} rows: policy loss {r['global_policy_loss']:.4f}, "
+                            f"value loss {r['global_value_loss']:.4f}, entropy {r['global_entropy']:.3f}"
+                            if r["global_update"] else "")
+                    print(f"        learner {l} global buffer {int(r['global_fill'])} rows{tail}", flush=True)
         if ckpt_out:
             for l in range(P_):
                 m = ppo.population_member(l, P_, H)
                 st = m["state"]
                 path = ppo.save_checkpoint(f"{ckpt_out}.member{l}", policies[l].weights, policies[l].critic_weights,
                                            m["adam"], m["adam_step"], m["best"], iters, st["obs_mean"], st["obs_M2"],
-                                           st["obs_count"], st["history"], policies[l].current_k, st["model_params"])
+                                           st["obs_count"], st["history"], policies[l].current_k, st["model_params"],
+                                           global_buffer=m.get("global_buffer"))
                 print(f"checkpoint: {path} (learner {l}, best return {float(m['best']['best_return'][0]):.2f})",
                       flush=True)
     finally:

@@ -19,9 +19,19 @@ train_pop_dev iteration of all P learners (csrc: the *_pop_kernel launches); `se
 iterations on P separate training states, each ending in its synchronise -- the way a user gets a population without
 the entry; `streams` enqueues the P train_dev iterations on the P solvers' own streams and synchronises once.  Same
 protocol; times are per population.
+Population contenders with the global-buffer update (--population-global): the same shape and P.  One measurement is
+one full fill period (4 iterations at this shape, the last of which carries the update on the G buffer rows),
+reported per iteration.  `population` is one train_pop_global_dev call of a period for all P learners; `sequential`
+is P train_global_dev periods back to back, each ending in its synchronise; `streams` the same on the P solvers' own
+streams, synchronised once.  Sequential and streams run the single-learner entry, whose kernels this change leaves
+instruction-identical: they are the yardstick.  After the rounds learner l's actor must be bit-identical across the
+three contenders (asserted).
 Usage: python tools/train_rate.py [out.json] [rounds]
        python tools/train_rate.py --population [out.json] [rounds]
+       python tools/train_rate.py --population-global [out.json] [rounds]
        python tools/train_rate.py --once-pop P B K [iterations]   (population iterations and nothing else)
+       python tools/train_rate.py --ab-global B K out.npz [periods]   (resident_dev_global alone, per iteration)
+       python tools/train_rate.py --ab-pop P B K out.npz [iterations]   (train_pop_dev alone, per iteration)
        python tools/train_rate.py --ab B K out.npz [iterations]   (resident_dev alone, one time per iteration, and its
                                                                     results for a bit-for-bit check of two builds)
        python tools/train_rate.py --once B K [iterations]   (resident iterations and nothing else: for a kernel trace)
@@ -132,18 +142,19 @@ class Run:
             self.fill, self.G, self.n = 0, G, n
         torch.cuda.synchronize()
 
-    def resident_dev_global(self):
+    def resident_dev_global(self, sync=True, seed=0):
         """One full fill period of the iteration with the global-buffer update, in one call."""
         d = self.dev
         p = lambda g: {k: v.data_ptr() for k, v in d[g].items()}
-        tcfg = _lib.train_config(seed=0, iterations=self.period, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
+        tcfg = _lib.train_config(seed=seed, iterations=self.period, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
         g = _lib.global_buffer(p("gb"), self.G, self.fill, global_log=self.glog.data_ptr(), workspace=self.gws.data_ptr())
         self.solver.train_global_dev(self.B, 4, d["c"]["target"].data_ptr(), d["c"]["prm"].data_ptr(),
                                      d["c"]["pvec"].data_ptr(), d["c"]["current_k"].data_ptr(),
                                      d["c"]["weights"].data_ptr(), d["c"]["critic"].data_ptr(), p("st"), p("cs"), p("lg"),
                                      p("clg"), p("rec"), p("tr"), self.policy.cfg, self.rcfg, self.cfg, tcfg, g,
                                      pool=p("pool"))
-        self.solver.sync()
+        if sync:
+            self.solver.sync()
         self.fill = _lib.global_fill_after(self.n, self.fill, self.period)
         self.it += self.period
 
@@ -163,7 +174,7 @@ class Run:
 class PopRun:
     """P learners of B instances on one solver, device-resident: the members are Run(B, K, member=l), stacked."""
 
-    def __init__(self, P, B, K):
+    def __init__(self, P, B, K, with_global=False):
         self.P, self.B, self.K = P, B, K
         members = [Run(B, K, member=l) for l in range(P)]
         for m in members:
@@ -189,10 +200,34 @@ class PopRun:
                                                   dtype=torch.uint8, device="cuda")
         self.cfg = _lib.ppo_config(epochs=EPOCHS, mini_batch_size=MB, **HYPER)
         self.it = 0
+        if with_global:
+            n = B * R
+            m, G = _lib.global_rows(n)
+            self.n, self.G, self.period, self.fill = n, G, G // m, 0
+            self.dev["gb"] = {f: torch.zeros((P, G, w) if w else (P, G), dtype=getattr(torch, np.dtype(dt).name),
+                                             device="cuda") for f, w, dt in _lib.LMPC_GLOBAL_ARRAYS}
+            self.glog = torch.zeros(P, self.period, _lib.GLOBAL_LOG_COLS, dtype=torch.float64, device="cuda")
+            self.gws = torch.zeros(_lib.global_pop_workspace_bytes(P, n, G, EPOCHS, MB), dtype=torch.uint8,
+                                   device="cuda")
         torch.cuda.synchronize()
 
     def close(self):
         self.solver.close()
+
+    def population_global(self):
+        """One full fill period of all P learners with the global-buffer update, in one call."""
+        d = self.dev
+        p = lambda g: {k: v.data_ptr() for k, v in d[g].items()}
+        tcfg = _lib.train_config(iterations=self.period, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
+        g = _lib.global_buffer(p("gb"), self.G, self.fill, global_log=self.glog.data_ptr(), workspace=self.gws.data_ptr())
+        self.solver.train_pop_global_dev(self.P, list(range(self.P)), self.B, 4, d["c"]["target"].data_ptr(),
+                                         d["c"]["prm"].data_ptr(), d["c"]["pvec"].data_ptr(),
+                                         d["c"]["current_k"].data_ptr(), d["c"]["weights"].data_ptr(),
+                                         d["c"]["critic"].data_ptr(), p("st"), p("cs"), p("lg"), p("clg"), p("rec"),
+                                         p("tr"), self.pcfg, self.rcfg, self.cfg, tcfg, g, pool=p("pool"))
+        self.solver.sync()
+        self.fill = _lib.global_fill_after(self.n, self.fill, self.period)
+        self.it += self.period
 
     def population(self, iterations=1):
         d = self.dev
@@ -206,29 +241,33 @@ class PopRun:
         self.it += iterations
 
 
-def measure_population(P, B, K, rounds):
-    pop = PopRun(P, B, K)
+def measure_population(P, B, K, rounds, with_global=False):
+    """with_global: every call is one full fill period with the global-buffer update; times are per iteration."""
+    pop = PopRun(P, B, K, with_global=with_global)
     seq = [Run(B, K, member=l) for l in range(P)]
     par = [Run(B, K, member=l) for l in range(P)]
     for r in seq + par:
         r.to_device()
+    step = (lambda r, **kw: r.resident_dev_global(**kw)) if with_global else (lambda r, **kw: r.resident_dev(**kw))
+    per = pop.period if with_global else 1
 
     def sequential():
         for l, r in enumerate(seq):
-            r.resident_dev(seed=l)
+            step(r, seed=l)
 
     def streams():
         for l, r in enumerate(par):
-            r.resident_dev(sync=False, seed=l)
+            step(r, sync=False, seed=l)
         for r in par:
             r.solver.sync()
 
-    calls = {"population": pop.population, "sequential": sequential, "streams": streams}
+    calls = {"population": pop.population_global if with_global else pop.population, "sequential": sequential,
+             "streams": streams}
     times = {name: [] for name in calls}
     try:
         for r in range(rounds + 1):                 # round 0 is the warm-up
             for name, fn in calls.items():
-                ms = timed(fn)
+                ms = timed(fn) / per
                 if r:
                     times[name].append(ms)
         # the learners are the same runs in all three: learner l's actor after the rounds, bit for bit
@@ -240,6 +279,9 @@ def measure_population(P, B, K, rounds):
             run.close()
     out = {"P": P, "B": B, "K": K, "instances": P * B, "samples_per_learner": B * (K // 8), "rounds": rounds,
            "learners_bit_identical_across_contenders": bool(same)}
+    if with_global:
+        out.update(fill_period=per, buffer_rows=pop.G, times="ms per iteration (one call is one fill period)")
+        assert same, f"P = {P}: the contenders' learners differ"
     for name, t in times.items():
         out[name] = {"median_ms": float(np.median(t)), "min_ms": float(min(t)), "max_ms": float(max(t)), "all_ms": t}
     for name in ("sequential", "streams"):
@@ -345,14 +387,16 @@ def main():
             with open(argv[3], "w") as fh:
                 json.dump(res, fh, indent=1)
         return
-    if argv and argv[0] == "--population":
-        path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "population", "train_rate.json")
+    if argv and argv[0] in ("--population", "--population-global"):
+        with_global = argv[0] == "--population-global"
+        path = argv[1] if len(argv) > 1 else os.path.join(
+            ROOT, "profiles", "population_global" if with_global else "population", "train_rate.json")
         rounds = int(argv[2]) if len(argv) > 2 else 5
-        res = {"tool": "tools/train_rate.py --population", "device": torch.cuda.get_device_name(0), "N": N,
+        res = {"tool": "tools/train_rate.py " + argv[0], "device": torch.cuda.get_device_name(0), "N": N,
                "episode_steps": EP_STEPS, "epochs": EPOCHS, "mini_batch_size": MB, "library": _lib.LIB_NAME,
                "populations": []}
         for P in (1, 2, 3, 4, 8):
-            r = measure_population(P, 72, 256, rounds)
+            r = measure_population(P, 72, 256, rounds, with_global=with_global)
             res["populations"].append(r)
             print(f"P = {P}: " + ", ".join(f"{n} {r[n]['median_ms']:.1f} ms ({r[n]['min_ms']:.1f}-{r[n]['max_ms']:.1f})"
                                            for n in ("population", "sequential", "streams"))
@@ -383,6 +427,40 @@ def main():
         finally:
             run.close()
         print(f"{_lib.LIB_NAME} resident_dev B = {B}, K = {K}: median {np.median(t):.2f} ms "
+              f"({min(t):.2f}-{max(t):.2f}) over {iters} iterations", flush=True)
+        return
+    if argv and argv[0] == "--ab-global":
+        B, K, periods = int(argv[1]), int(argv[2]), int(argv[4]) if len(argv) > 4 else 3
+        run = Run(B, K)
+        try:
+            run.to_device()
+            run.resident_dev_global()               # warm-up
+            t = [timed(run.resident_dev_global) / run.period for _ in range(periods)]
+            d = run.dev
+            np.savez(argv[3], weights=d["c"]["weights"].cpu().numpy(), critic=d["c"]["critic"].cpu().numpy(),
+                     current_k=d["c"]["current_k"].cpu().numpy(), adam=d["tr"]["adam"].cpu().numpy(),
+                     reward=d["clg"]["reward"].cpu().numpy(), x=d["st"]["x"].cpu().numpy(),
+                     best_return=d["tr"]["best_return"].cpu().numpy(), glog=run.glog.cpu().numpy(),
+                     g_obs=d["gb"]["obs"].cpu().numpy()[:run.fill])
+        finally:
+            run.close()
+        print(f"{_lib.LIB_NAME} resident_dev_global B = {B}, K = {K}: median {np.median(t):.2f} ms per iteration "
+              f"({min(t):.2f}-{max(t):.2f}) over {periods} fill periods of {run.period} iterations", flush=True)
+        return
+    if argv and argv[0] == "--ab-pop":
+        P, B, K, iters = int(argv[1]), int(argv[2]), int(argv[3]), int(argv[5]) if len(argv) > 5 else 5
+        run = PopRun(P, B, K)
+        try:
+            run.population()                        # warm-up
+            t = [timed(run.population) for _ in range(iters)]
+            d = run.dev
+            np.savez(argv[4], weights=d["c"]["weights"].cpu().numpy(), critic=d["c"]["critic"].cpu().numpy(),
+                     current_k=d["c"]["current_k"].cpu().numpy(), adam=d["tr"]["adam"].cpu().numpy(),
+                     reward=d["clg"]["reward"].cpu().numpy(), x=d["st"]["x"].cpu().numpy(),
+                     best_return=d["tr"]["best_return"].cpu().numpy())
+        finally:
+            run.close()
+        print(f"{_lib.LIB_NAME} population P = {P}, B = {B}, K = {K}: median {np.median(t):.2f} ms "
               f"({min(t):.2f}-{max(t):.2f}) over {iters} iterations", flush=True)
         return
     if argv and argv[0] == "--once":
