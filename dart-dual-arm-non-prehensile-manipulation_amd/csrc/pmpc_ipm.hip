@@ -413,7 +413,7 @@ __device__ __forceinline__ bool pmpc_riccati(const int lane, const int N, const 
 // kFlMuDec, all before barrier B; wave 0 reads them after it.  Wave 0 alone writes kFlStop.  Each buffer has one
 // writer, and its next write comes after a barrier that the readers cross only with their reads complete, so single
 // buffers are enough.
-enum PmPt { kPtTh, kPtSn, kPtLp, kPtLv, kPtZl, kPtZu, kPtP, kPtV, kPtZ, kPtMu, kPtRows };      // the point and mu
+enum PmPt { kPtTh, kPtLp, kPtLv, kPtZl, kPtZu, kPtP, kPtV, kPtZ, kPtMu, kPtRows };      // the point and mu
 enum PmFc { kFcP11, kFcP12, kFcP22, kFcW1, kFcW2, kFcIQs, kFcRows };                            // its factors
 // stop; the factor wave's use_scan and ok; the evaluation wave's converged and mu decreased (kFl*Time: the stamps
 // build's helper-wave timers)
@@ -424,7 +424,7 @@ struct PmOvlShared {
     double mu_new;
     int flag[kFlWords];
 };
-__shared__ PmOvlShared g_pm_ovl;       // only the overlapped instantiations name it (8 KB beside PrShared when fused)
+__shared__ PmOvlShared g_pm_ovl;       // only the overlapped instantiations name it (7.5 KB beside PrShared when fused)
 
 // IPOPT's kappa_sigma safeguard of a bound multiplier after its step: z within [1e-10, 1e10] mu / slack
 __device__ __forceinline__ double pm_clamp_mult(const double z, const double mu, const double islack) {
@@ -636,9 +636,13 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
 #ifdef DART_STAMPS
                 const unsigned long long tf0 = __builtin_amdgcn_s_memtime();
 #endif
-                const double th1 = g_pm_ovl.pt[kPtTh][lane], sn1 = g_pm_ovl.pt[kPtSn][lane];
+                const double th1 = g_pm_ovl.pt[kPtTh][lane];
                 const double lp1 = g_pm_ovl.pt[kPtLp][lane], lv1 = g_pm_ovl.pt[kPtLv][lane];
                 const double zl1 = g_pm_ovl.pt[kPtZl][lane], zu1 = g_pm_ovl.pt[kPtZu][lane];
+                // (the sine by the function and the mask of the trial and of the start point: the trial's bits)
+                double s_, sc_;
+                tilt_sincos(poly, th1, s_, sc_);
+                const double sn1 = uon ? s_ : 0.0;
                 const double c_ = tilt_cos_econ(poly, th1);
                 const double cs1 = uon ? c_ : 0.0;
                 const double ln = from_next(lp1), vn = from_next(lv1);
@@ -671,7 +675,7 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
 #ifdef DART_STAMPS
                 const unsigned long long te0 = __builtin_amdgcn_s_memtime();
 #endif
-                const double th1[NAX] = {g_pm_ovl.pt[kPtTh][lane]}, sn1 = g_pm_ovl.pt[kPtSn][lane];
+                const double th1[NAX] = {g_pm_ovl.pt[kPtTh][lane]};
                 const double lp1[NAX] = {g_pm_ovl.pt[kPtLp][lane]}, lv1[NAX] = {g_pm_ovl.pt[kPtLv][lane]};
                 const double zl1[NAX] = {g_pm_ovl.pt[kPtZl][lane]}, zu1[NAX] = {g_pm_ovl.pt[kPtZu][lane]};
                 const double p1[NAX] = {g_pm_ovl.pt[kPtP][lane]}, v1[NAX] = {g_pm_ovl.pt[kPtV][lane]};
@@ -679,6 +683,9 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 double mu1 = wave_uniform(g_pm_ovl.pt[kPtMu][lane]);
                 double g1e[NAX], g2e[NAX], gze[NAX];
                 const double w1 = vz_new(th1);
+                double s_, sc_;       // (the sine as the trial and the start point form it: the same bits)
+                tilt_sincos(poly, th1[0], s_, sc_);
+                const double sn1 = uon ? s_ : 0.0;
                 defects(p1[0], v1[0], sn1, sp[0], sv[0], g1e[0], g2e[0]);
                 gze[0] = zdefect(zz1, w1, 0);
                 bool dec = false;
@@ -747,7 +754,7 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
     bool published = false;
     auto publish = [&]() {
         __builtin_amdgcn_sched_barrier(0);
-        g_pm_ovl.pt[kPtTh][lane] = th[0]; g_pm_ovl.pt[kPtSn][lane] = snc[0];
+        g_pm_ovl.pt[kPtTh][lane] = th[0];
         g_pm_ovl.pt[kPtLp][lane] = lp[0]; g_pm_ovl.pt[kPtLv][lane] = lv[0];
         g_pm_ovl.pt[kPtZl][lane] = zl[0]; g_pm_ovl.pt[kPtZu][lane] = zu[0];
         g_pm_ovl.pt[kPtP][lane] = p[0]; g_pm_ovl.pt[kPtV][lane] = v[0];
@@ -1168,11 +1175,6 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
         double snt[NAX], g1t[NAX], g2t[NAX], gzt[NAX];     // the trial's sines and defects (carried on acceptance)
         double lgt[NAX];                                   // OVL: and its barrier logarithm
         (void)lgt;
-        // OVL: the sine of the first trial point, formed with the speculative hand-over below (sn_pre_on: the next
-        // trial takes it in place of its own tilt_sincos of the same angle, so the factor wave gets the trial's bits)
-        double sn_pre = 0.0;
-        bool sn_pre_on = false;
-        (void)sn_pre; (void)sn_pre_on;
         // trial point x + al d: defects, wave-summed theta and barrier objective
         auto trial = [&](double al) {
             double thl = 0.0, phl = 0.0, tt[NAX];
@@ -1205,13 +1207,9 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             for (int j = 0; j < NAX; ++j) {
                 const double pt = fma(al, dp[j], p[j]), vt = fma(al, dv[j], v[j]);
                 tt[j] = fma(al, dth[j], th[j]);
-                if (OVL && PM_EXPECT(sn_pre_on, 1)) {
-                    snt[j] = sn_pre; sn_pre_on = false;
-                } else {
-                    double s_, c_;
-                    tilt_sincos(poly, tt[j], s_, c_);
-                    snt[j] = uon ? s_ : 0.0;
-                }
+                double s_, c_;
+                tilt_sincos(poly, tt[j], s_, c_);
+                snt[j] = uon ? s_ : 0.0;
                 defects(pt, vt, snt[j], sp[j], sv[j], g1t[j], g2t[j]);
                 const double ep = pt - rp[j], ev = vt - rv[j];
                 thl += xon ? fabs(g1t[j]) + fabs(g2t[j]) : 0.0;
@@ -1266,6 +1264,35 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             if (PM_EXPECT(soc != 0, 0)) { wmin2f(am_lf, az_lf); frac_set(); }
             STAMP(4);
             if (PM_EXPECT(soc == 0, 1)) {
+                if constexpr (OVL) {
+                    // (the fraction minima alone come first: of the preparation the hand-over needs amax and az only.
+                    // The sums, the tiny-step maximum and what follows from them feed the acceptance test after the
+                    // first trial, so they are formed behind barrier A, where their reduction no longer stands
+                    // between direction() and the helper waves' start; the scheduling barrier there keeps them from
+                    // moving back up.  DESIGN §5.R12.)
+                    wmin2f(am_lf, az_lf);
+                    frac_set();
+                    alpha = amax; amain = amax;
+                    // The speculative hand-over.  The first trial is the Newton step at alpha = amax, and where it
+                    // is accepted (most iterations) the accepted point is this trial point: theta, lambda and z by
+                    // the expressions of the accepted update below, operand for operand.  The trial's sine is not
+                    // handed over: the helper waves form it from theta as the trial does.  The factor wave starts
+                    // on the point here (barrier A), so the trial, the acceptance test, the update, the evaluation
+                    // and the mu update all run in its shadow.  This branch runs once per Newton iteration
+                    // (soc == 0 is entered with ls == 0 only), always after this iteration's barrier B.
+                    const double thc = fma(alpha, dth[0], th[0]);
+                    const double il = frcp(thc - lo), iu = frcp(hi - thc);
+                    const double zln = pm_clamp_mult(fma(az, dzl[0], zl[0]), mu, il);
+                    const double zun = pm_clamp_mult(fma(az, dzu[0], zu[0]), mu, iu);
+                    __builtin_amdgcn_sched_barrier(0);
+                    g_pm_ovl.pt[kPtTh][lane] = thc;
+                    g_pm_ovl.pt[kPtLp][lane] = fma(alpha, dlp[0], lp[0]); g_pm_ovl.pt[kPtLv][lane] = fma(alpha, dlv[0], lv[0]);
+                    g_pm_ovl.pt[kPtZl][lane] = uon ? zln : 0.0; g_pm_ovl.pt[kPtZu][lane] = uon ? zun : 0.0;
+                    g_pm_ovl.pt[kPtP][lane] = fma(alpha, dp[0], p[0]); g_pm_ovl.pt[kPtV][lane] = fma(alpha, dv[0], v[0]);
+                    g_pm_ovl.pt[kPtZ][lane] = fma(alpha, dz[0], zz[0]); g_pm_ovl.pt[kPtMu][lane] = mu;
+                    __syncthreads();                                        // barrier A
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 double phil = 0.0, gtdl = 0.0;
 #pragma unroll
                 for (int j = 0; j < NAX; ++j) {
@@ -1288,8 +1315,13 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                     tn_w = fmaxf(tn_w, xon ? fabsf((float)dz[j]) * __builtin_amdgcn_rcpf(1.0f + fabsf((float)zz[j])) : 0.0f);
                     tn_w = fmaxf(tn_w, uon ? fabsf((float)dth[j]) * __builtin_amdgcn_rcpf(1.0f + fabsf((float)th[j])) : 0.0f);
                 }
-                wsum2_maxf_min2f(phil, gtdl, tn_w, am_lf, az_lf);      // (the fraction minima ride along)
+                // (the fraction minima ride along; OVL: they were reduced ahead of the hand-over, and each chain takes
+                // its own steps either way: the same bits)
+                if constexpr (OVL) wsum2_maxf(phil, gtdl, tn_w);
+                else {
+                wsum2_maxf_min2f(phil, gtdl, tn_w, am_lf, az_lf);
                 frac_set();
+                }
                 phi = phil; gTd = gtdl;
                 // switching condition alpha (-gTd)^s_ph > delta theta^s_th, compared in log2 space
                 const float lg_th = theta > 0.0 ? lg2(theta) : -3.0e38f;
@@ -1300,29 +1332,6 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 amin *= gam_al;
                 tiny = tn_w < 2.2e-15f;
                 alpha = amax; amain = amax;
-                if constexpr (OVL) {
-                    // The speculative hand-over.  The first trial is the Newton step at alpha = amax, and where it
-                    // is accepted (most iterations) the accepted point is this trial point: theta, lambda and z by
-                    // the expressions of the accepted update below, operand for operand, and the trial's sine.  The
-                    // factor wave starts on it here (barrier A), so the trial, the acceptance test, the update, the
-                    // evaluation and the mu update all run in its shadow.  This branch runs once per Newton
-                    // iteration (soc == 0 is entered with ls == 0 only), always after this iteration's barrier B.
-                    const double thc = fma(alpha, dth[0], th[0]);
-                    double s_, c_;
-                    tilt_sincos(poly, thc, s_, c_);
-                    sn_pre = uon ? s_ : 0.0; sn_pre_on = true;
-                    const double il = frcp(thc - lo), iu = frcp(hi - thc);
-                    const double zln = pm_clamp_mult(fma(az, dzl[0], zl[0]), mu, il);
-                    const double zun = pm_clamp_mult(fma(az, dzu[0], zu[0]), mu, iu);
-                    __builtin_amdgcn_sched_barrier(0);
-                    g_pm_ovl.pt[kPtTh][lane] = thc; g_pm_ovl.pt[kPtSn][lane] = sn_pre;
-                    g_pm_ovl.pt[kPtLp][lane] = fma(alpha, dlp[0], lp[0]); g_pm_ovl.pt[kPtLv][lane] = fma(alpha, dlv[0], lv[0]);
-                    g_pm_ovl.pt[kPtZl][lane] = uon ? zln : 0.0; g_pm_ovl.pt[kPtZu][lane] = uon ? zun : 0.0;
-                    g_pm_ovl.pt[kPtP][lane] = fma(alpha, dp[0], p[0]); g_pm_ovl.pt[kPtV][lane] = fma(alpha, dv[0], v[0]);
-                    g_pm_ovl.pt[kPtZ][lane] = fma(alpha, dz[0], zz[0]); g_pm_ovl.pt[kPtMu][lane] = mu;
-                    __syncthreads();                                        // barrier A
-                    __builtin_amdgcn_sched_barrier(0);
-                }
             } else if (soc > 0) {
                 alpha = amax;                 // alpha_soc: fraction to the boundary of the corrected step
             }
