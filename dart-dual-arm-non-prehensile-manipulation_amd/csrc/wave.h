@@ -357,7 +357,10 @@ struct OpMinF { __device__ float operator()(float a, float b) const { return fmi
 __device__ __forceinline__ float wsumf(float x) { return wreducef(x, OpSumF()); }
 // max / min over the wave of NON-NEGATIVE floats (+0, positive, inf; a NaN propagates as the
 // largest): on such values the IEEE order is the unsigned order of the bit patterns, so the steps
-// run on v_max_u32 / v_min_u32, without the NaN-quieting canonicalize fmaxf needs on DPP results
+// run on v_max_u32 / v_min_u32, without the NaN-quieting canonicalize fmaxf needs on DPP results.
+// A NaN (sign clear) is thus the maximum if any lane holds one and the minimum only if every lane does; -0 is
+// outside the domain -- its bit pattern orders above every value of it, a NaN included
+// (tests/test_gpu_wave_primitives.py pins both)
 struct OpMaxU { __device__ unsigned operator()(unsigned a, unsigned b) const { return a > b ? a : b; } };
 struct OpMinU { __device__ unsigned operator()(unsigned a, unsigned b) const { return a < b ? a : b; } };
 template <class Op>
@@ -519,6 +522,8 @@ __device__ __forceinline__ void wred_errors(float& mx0, float& mx1, float& mx2, 
 #endif
 }
 
+// (wmax / wmin: fmax / fmin on v_max_f64 / v_min_f64 -- +-inf are ordinary values and -0 orders below +0, so the
+// maximum of +-0 is +0 and the minimum -0, in both builds; tests/test_gpu_wave_primitives.py)
 __device__ __forceinline__ double wsum(double x) { return wreduce(x, OpSum()); }
 __device__ __forceinline__ double wmax(double x) { return wreduce(x, OpMax()); }
 __device__ __forceinline__ double wmin(double x) { return wreduce(x, OpMin()); }
@@ -618,8 +623,11 @@ __device__ __forceinline__ bool wany(bool p) {
 // entries, one per lane, set from wave-uniform values): the wave's own ballot decides, no exchange
 __device__ __forceinline__ bool wany_rep(bool p) { return __ballot(p) != 0ull; }
 
-// reciprocal: v_rcp_f64 (measured max relative error 2e-8 on gfx950, tests/test_gpu_pmpc.py
-// selftest) + one Newton step -> ~4e-16 relative; operands are well scaled, no denormals
+// reciprocal: v_rcp_f64 + one Newton step; operands are well scaled, no denormals.  Measured on the device
+// (tests/test_gpu_wave_math.py, 2.6e5 arguments over exponents -300 .. 300): the raw v_rcp_f64 is up to
+// delta = 4.6e-8 relative off (the 64 arguments of the self-test in tests/test_gpu_pmpc.py only show 2e-8),
+// and the Newton step leaves up to delta^2: frcp is within 10.8 ulp (1.2e-15 relative), not the 4e-16 that
+// delta = 2e-8 would give.  Its users need 1e-14 (delta <= 1e-7).
 __device__ __forceinline__ double frcp(double x) {
     const double r = __builtin_amdgcn_rcp(x);
     return fma(r, fma(-x, r, 1.0), r);
@@ -627,6 +635,8 @@ __device__ __forceinline__ double frcp(double x) {
 
 // log2 of a positive double to ~1e-7 relative: exponent + f32 log2 of the mantissa.  Used only in
 // the filter's switching condition / minimum step heuristics, never in a quantity that is solved for.
+// Measured on the device over all normal exponents and near 1: |lg2(x) - log2 x| <= 0.29 x 2^-21 max(1, |log2 x|)
+// (tests/test_gpu_wave_math.py holds it to 2^-21: three f32 roundings and the mantissa's f32 rounding).
 __device__ __forceinline__ float lg2(double x) {
     const int e = __builtin_amdgcn_frexp_exp(x);
     const float m = (float)__builtin_amdgcn_frexp_mant(x);
@@ -680,6 +690,8 @@ __device__ __forceinline__ double cos_small(double x) {       // the cosine half
 // checks the error).  Used by the LMPC kernel (+1 % on C5) and for PMPC's cosine at the iterate
 // (+0.4 % on C2); PMPC's line-search sincos and RMPC keep the Taylor form, which their register
 // allocation prefers (A/B: -0.6 % / -0.4 % with this one).
+// Measured on the device against longdouble on [-1, 1] (tests/test_gpu_wave_math.py, bound 1.1 ulp): sincos_small
+// 0.79 (sin) / 0.94 (cos) ulp, sincos_econ 0.74 / 0.95 ulp; the library branch of tilt_* 0.62 ulp on [-3, 3].
 #define DART_SIN_COEFFS -0.16666666666666663, 0.00833333333333285, -0.0001984126984096554, 2.755731912250289e-06, \
                         -2.505208918178363e-08, 1.6056973209300557e-10, -7.52855132478024e-13
 #define DART_COS_COEFFS -0.5, 0.041666666666666664, -0.0013888888888888367, 2.480158730131862e-05, \
@@ -731,7 +743,14 @@ __device__ __forceinline__ void tilt_sincos_econ(bool poly, double x, double& s,
 // degree-19 Taylor polynomial economised by Chebyshev polynomials on |r| <= 0.3467 to degree 10 (one term
 // fewer than the degree-11 Taylor P the kernels used before; the same 0.99 ulp for exp and 1.08 ulp for
 // expm1 in double, tests/test_math.py).  tanh(x) = em / (em + 2), em = expm1(2x); exp underflows to the
-// subnormals and 0 like libm.
+// subnormals like libm (arguments below -745 give the value at -745, 2^-1074, above 709 the value at 709).
+// Measured on the device against longdouble (tests/test_gpu_wave_math.py): exp_econ 0.86 ulp on normal results
+// and 0.86 units of 2^-1074 on subnormal ones; tanh_econ 20.3 ulp (4.5e-15 relative; |T| <= 1 everywhere) -- a
+// host emulation with an exact reciprocal gives 3.2 ulp for the form itself (around |x| = 0.2), the rest is
+// frcp's delta^2 (see there); the test's bound is 3.5 + delta^2 2^53 ulp with the measured delta.
+// A NaN argument does not come back: fmin(fmax(., lo), hi) returns the bound, so tanh_econ(NaN) = -1 and
+// exp_econ(NaN) = 2^-1074.  The callers' results still turn NaN, through the linear terms that carry the same
+// argument beside these functions (p.B * v in strb, a[1] * y[1] in rm_f).
 #define DART_EXPM1_COEFFS 0.5, 0.1666666666666667, 0.04166666666666668, 0.008333333333326119, \
                           0.0013888888888879054, 0.0001984126987487566, 2.4801587336499025e-05, \
                           2.7557255330683724e-06, 2.755726321849137e-07, 2.5105245845597674e-08, 2.0918160101597142e-09
@@ -784,7 +803,10 @@ struct RcpTwoPlus {     // 1 / (2 + f) for f in [-0.3, 0.42]: v_rcp_f64 + one Ne
 };
 // log for the barrier terms (positive normal arguments; NaN for x <= 0 or non-finite x, so a
 // trial outside the box is rejected by the filter like with the library log).  About half the
-// instructions of the library log; < 1 ulp (host check).
+// instructions of the library log; < 1 ulp in the host check with an exact reciprocal, and 0.75 ulp measured
+// on the device (tests/test_gpu_wave_math.py: all exponents, [0.5, 1.5], 1 +- 2^-k, the mantissa switch; frcp's
+// 10.8 ulp enter only through s (hfsq + R), a small part of the result).  Subnormal arguments are not in the
+// contract but measured 0.5 ulp there too.
 __device__ __forceinline__ double log_fast(double x) {
     const double m = __builtin_amdgcn_frexp_mant(x);
     const int e = __builtin_amdgcn_frexp_exp(x);

@@ -457,6 +457,91 @@ def wave_selftest():
     return out
 
 
+# -- device probes of csrc/wave.h and csrc/ocp_wave.h (csrc/wave_probe.hip; internal like dartmpc_selftest) --------
+PROBE_MATH_FN = {"frcp": 0, "rcp_raw": 1, "lg2": 2, "log_fast": 3, "exp_econ": 4, "tanh_econ": 5, "sincos_small": 6,
+                 "cos_small": 7, "sincos_econ": 8, "cos_econ": 9, "tilt_sincos": 10, "tilt_cos": 11,
+                 "tilt_sincos_econ": 12, "tilt_cos_econ": 13}
+
+
+def _probe_entry(name, waves):
+    if waves not in (1, 2):
+        raise DartMPCError(f"probe builds have one or two waves per instance, not {waves}")
+    fn = getattr(lib(), f"{name}_wg{waves}")
+    fn.restype = ctypes.c_int
+    return fn
+
+
+def probe_layout(waves=1):
+    """Sizes compiled into the probes of the ``waves``-wave build (no GPU needed): threads, result rows of the
+    primitive probe, doubles of the node-array images and the node slots of both engine forms, LDS struct bytes."""
+    o = np.zeros(10, np.int32)
+    fn = _probe_entry("dartmpc_probe_layout", waves)
+    fn.restype = None
+    fn(_ptr(o))
+    keys = ("threads", "prim_slots", "aug_M", "aug_G", "s_M", "s_G", "aug_nmaxs", "s_nmaxs", "aug_bytes", "s_bytes")
+    return dict(zip(keys, (int(v) for v in o)))
+
+
+def probe_math(name, x, poly=True):
+    """``name`` of wave.h (PROBE_MATH_FN) applied elementwise to ``x`` on device 0: (first, second) results as
+    float64 arrays (second: the cosine of the sincos forms, else zeros)."""
+    x = np.ascontiguousarray(x, np.float64).ravel()
+    o0, o1 = np.empty_like(x), np.empty_like(x)
+    L = lib()
+    L.dartmpc_probe_math.restype = ctypes.c_int
+    rc = L.dartmpc_probe_math(ctypes.c_int(PROBE_MATH_FN[name]), ctypes.c_int(int(bool(poly))), ctypes.c_int(x.size),
+                              _ptr(x), _ptr(o0), _ptr(o1))
+    if rc != 0:
+        raise DartMPCError(f"dartmpc_probe_math({name}) failed ({rc})")
+    return o0, o1
+
+
+def probe_prims(d, f, p, waves=1):
+    """Every wave primitive on one instance of the ``waves``-wave build: d [8, T] float64, f [8, T] float32,
+    p [T] predicate -> [rows, T] float64 (T = 64 waves; the rows as numbered in csrc/wave_probe.hip)."""
+    lay = probe_layout(waves)
+    T = lay["threads"]
+    d = np.ascontiguousarray(d, np.float64)
+    f = np.ascontiguousarray(f, np.float32)
+    p = np.ascontiguousarray(p, np.int32)
+    if d.shape != (8, T) or f.shape != (8, T) or p.shape != (T,):
+        raise DartMPCError(f"probe_prims takes [8, {T}] doubles, [8, {T}] floats and [{T}] predicates")
+    out = np.zeros((lay["prim_slots"], T))
+    rc = _probe_entry("dartmpc_probe_prims", waves)(_ptr(d), _ptr(f), _ptr(p), _ptr(out))
+    if rc != 0:
+        raise DartMPCError(f"dartmpc_probe_prims failed ({rc})")
+    return out
+
+
+def probe_riccati(form, N, M, H, G, dx0, waves=1):
+    """The Riccati engine of csrc/ocp_wave.h on one instance: ``form`` "aug" (OcpLds<6>: sweep_aug), "s" or "sp"
+    (OcpLdsS<5>, two subsystems: riccati_s_sweep / riccati_s_sweep_p).  M, H, G: the images of the node arrays
+    (NodeArr strides, sizes of ``probe_layout``); dx0 [6] or [2, 5].  Returns dict(G, dx, du, lam, ok)."""
+    lay = probe_layout(waves)
+    aug = form == "aug"
+    if form not in ("aug", "s", "sp"):
+        raise DartMPCError(f"unknown engine form {form!r}")
+    msz, gsz = (lay["aug_M"], lay["aug_G"]) if aug else (lay["s_M"], lay["s_G"])
+    nmaxs = lay["aug_nmaxs"] if aug else lay["s_nmaxs"]
+    nxa, nu, slots = (6, 2, nmaxs) if aug else (5, 1, 2 * nmaxs)
+    M, H, G = (np.ascontiguousarray(a, np.float64).ravel() for a in (M, H, G))
+    dx0 = np.ascontiguousarray(dx0, np.float64).ravel()
+    if M.size != msz or H.size != gsz or G.size != gsz or dx0.size != (6 if aug else 10) or not 1 <= N < nmaxs:
+        raise DartMPCError("probe_riccati: array sizes or N do not match the build's layout")
+    Go, dx, du, lam = np.zeros(gsz), np.zeros((slots, nxa)), np.zeros((slots, nu)), np.zeros((slots, nxa))
+    ok = np.zeros(lay["threads"], np.int32)
+    if aug:
+        rc = _probe_entry("dartmpc_probe_riccati_aug", waves)(ctypes.c_int(N), _ptr(M), _ptr(H), _ptr(G), _ptr(dx0),
+                                                              _ptr(Go), _ptr(dx), _ptr(du), _ptr(lam), _ptr(ok))
+    else:
+        rc = _probe_entry("dartmpc_probe_riccati_s", waves)(ctypes.c_int(int(form == "sp")), ctypes.c_int(N), _ptr(M),
+                                                            _ptr(H), _ptr(G), _ptr(dx0), _ptr(Go), _ptr(dx), _ptr(du),
+                                                            _ptr(lam), _ptr(ok))
+    if rc != 0:
+        raise DartMPCError(f"dartmpc_probe_riccati({form}) failed ({rc})")
+    return dict(G=Go, dx=dx, du=du, lam=lam, ok=ok)
+
+
 def default_config(**over) -> Config:
     c = Config()
     lib().dart_mpc_config_default(ctypes.byref(c))

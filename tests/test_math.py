@@ -13,7 +13,9 @@ WAVE_H = os.path.join(ROOT, "dart-dual-arm-non-prehensile-manipulation_amd", "cs
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_log_core_within_one_ulp(tmp_path):
     """log_fast's core (fdlibm reduction + Lg1..Lg7) against libm: < 1 ulp with the exact 1/(2+f),
-    < 1.5 ulp with a reciprocal 2 ulps off (the device's v_rcp_f64 + Newton step is closer)."""
+    < 1.5 ulp with a reciprocal 2 ulps off.  (The device's v_rcp_f64 + Newton step is not closer than that: it
+    was measured up to 10.8 ulp off, from a raw reciprocal 4.6e-8 off.  log_fast on the device still measured
+    0.75 ulp against longdouble, tests/test_gpu_wave_math.py, which holds the 1.5 ulp bound there.)"""
     src = open(WAVE_H).read()
     m = re.search(r"template <class Rcp>\n__host__ __device__ __forceinline__ double log_core.*?\n}\n", src, re.S)
     assert m, "log_core not found in wave.h"
