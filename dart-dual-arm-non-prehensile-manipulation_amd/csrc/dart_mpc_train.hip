@@ -2,16 +2,27 @@
 // (lmpc_ppo.hip), the generator entries, the global buffer and whole training iterations (lmpc_train.hip).
 #include "abi_internal.h"
 
+namespace {
+
+hipError_t launch_gae(int B, int rec_rows, double gamma, double lam, const int32_t* nrec, const double* rec_reward,
+                      const float* rec_value, const float* rec_done, const float* last_value, double* adv, double* ret,
+                      hipStream_t s) {
+    dartmpc::GaeArgs a;
+    a.B = B; a.rec_rows = rec_rows; a.gamma = gamma; a.lam = lam; a.nrec = nrec; a.rec_reward = rec_reward;
+    a.rec_value = rec_value; a.rec_done = rec_done; a.last_value = last_value; a.adv = adv; a.ret = ret;
+    return dartmpc_launch_lmpc_gae(&a, s);
+}
+
+}  // namespace
+
 int dart_lmpc_gae_dev(int B, int rec_rows, double gamma, double lam, const int32_t* nrec, const double* rec_reward,
                       const float* rec_value, const float* rec_done, const float* last_value, double* adv, double* ret,
                       void* stream) {
     if (B < 0 || rec_rows < 0) return DART_MPC_EINVAL;
     if (B == 0 || rec_rows == 0) return DART_MPC_OK;
     if (any_null({nrec, rec_reward, rec_value, rec_done, last_value, adv, ret})) return DART_MPC_EINVAL;
-    dartmpc::GaeArgs a;
-    a.B = B; a.rec_rows = rec_rows; a.gamma = gamma; a.lam = lam; a.nrec = nrec; a.rec_reward = rec_reward;
-    a.rec_value = rec_value; a.rec_done = rec_done; a.last_value = last_value; a.adv = adv; a.ret = ret;
-    return dartmpc_launch_lmpc_gae(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+    return launch_gae(B, rec_rows, gamma, lam, nrec, rec_reward, rec_value, rec_done, last_value, adv, ret,
+                      (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
 }
 
 int dart_lmpc_gae(int B, int rec_rows, double gamma, double lam, const int32_t* nrec, const double* rec_reward,
@@ -24,12 +35,14 @@ int dart_lmpc_gae(int B, int rec_rows, double gamma, double lam, const int32_t* 
     if (S.reserve(sizeof(double) * 3 * n + sizeof(float) * (2 * n + B) + sizeof(int32_t) * B + 8 * 256, 0) != hipSuccess)
         return DART_MPC_EHIP;
     S.begin();
-    dartmpc::GaeArgs a;
-    a.B = B; a.rec_rows = rec_rows; a.gamma = gamma; a.lam = lam;
-    a.nrec = S.in(nrec, (size_t)B); a.rec_reward = S.in(rec_reward, n); a.rec_value = S.in(rec_value, n);
-    a.rec_done = S.in(rec_done, n); a.last_value = S.in(last_value, (size_t)B);
-    a.adv = S.inout(adv, n); a.ret = S.inout(ret, n);      // (rows >= nrec[b] keep the caller's contents)
-    if (!D->run([&](hipStream_t s) { return dartmpc_launch_lmpc_gae(&a, s); })) return DART_MPC_EHIP;
+    const int32_t* d_nrec = S.in(nrec, (size_t)B);
+    const double* d_rw = S.in(rec_reward, n);
+    const float *d_vl = S.in(rec_value, n), *d_dn = S.in(rec_done, n), *d_lv = S.in(last_value, (size_t)B);
+    double *d_adv = S.inout(adv, n), *d_ret = S.inout(ret, n);      // (rows >= nrec[b] keep the caller's contents)
+    auto launch = [&](hipStream_t s) {
+        return launch_gae(B, rec_rows, gamma, lam, d_nrec, d_rw, d_vl, d_dn, d_lv, d_adv, d_ret, s);
+    };
+    if (!D->run(launch)) return DART_MPC_EHIP;
     return DART_MPC_OK;
 }
 
@@ -177,6 +190,31 @@ int ppo_update_check(const dart_lmpc_ppo_config* cfg, int n, int rec_total, cons
     return DART_MPC_OK;
 }
 
+// The update's launch sequence, stated here alone: prepare, then for every epoch the mini-batches of its permutation
+// (perm [epochs][n]; the last one ragged), each a grad and an apply.  ws is laid out for (n, mini_batch_size); with
+// pop every launch is the population's (sample [P][n], perm [P][epochs][n], the nets, adam and stats per learner).
+hipError_t ppo_launch_update(const dart_lmpc_ppo_config* c, int n, long long total, const int32_t* sample,
+                             const int32_t* perm, const float* rec_obs, const float* rec_action,
+                             const float* rec_logp, const double* adv, const double* ret, float* weights,
+                             float* critic, float* adam, int32_t* adam_step, double* stats, float* step_log,
+                             float* adv_out, float* ret_out, char* ws, hipStream_t s, PpoPop pop = {}) {
+    const int mb = c->mini_batch_size;
+    hipError_t e = ppo_launch_prepare(n, total, sample, adv, ret, adv_out, ret_out, ws, mb, s, pop);
+    int step = 0;
+    for (int ep = 0; ep < c->epochs && e == hipSuccess; ++ep) {
+        const int32_t* row = perm + (size_t)ep * n;
+        for (int start = 0; start < n && e == hipSuccess; start += mb, ++step) {
+            const int M = n - start < mb ? n - start : mb;
+            e = ppo_launch_grad(c, n, total, M, sample, row + start, rec_obs, rec_action, rec_logp, weights, critic, ws,
+                                mb, s, pop);
+            if (e == hipSuccess)
+                e = ppo_launch_apply(c, n, M, true, nullptr, nullptr, true, nullptr, nullptr, weights, critic, adam,
+                                     adam_step, stats, step_log, step, ws, mb, s, pop);
+        }
+    }
+    return e;
+}
+
 }  // namespace
 
 int dart_lmpc_ppo_update_dev(const dart_lmpc_ppo_config* cfg, int n, int rec_total, const int32_t* sample,
@@ -187,23 +225,9 @@ int dart_lmpc_ppo_update_dev(const dart_lmpc_ppo_config* cfg, int n, int rec_tot
     if (int rc = ppo_update_check(cfg, n, rec_total, sample, perm, rec_obs, rec_action, rec_logp, adv, ret, weights,
                                   critic, adam, adam_step, stats)) return rc;
     if (!workspace) return DART_MPC_EINVAL;
-    char* ws = (char*)workspace;
-    hipStream_t s = (hipStream_t)stream;
-    const int mb = cfg->mini_batch_size;
-    hipError_t e = ppo_launch_prepare(n, rec_total, sample, adv, ret, adv_norm_out, ret_norm_out, ws, mb, s);
-    int step = 0;
-    for (int ep = 0; ep < cfg->epochs && e == hipSuccess; ++ep) {
-        const int32_t* row = perm + (size_t)ep * n;
-        for (int start = 0; start < n && e == hipSuccess; start += mb, ++step) {
-            const int M = n - start < mb ? n - start : mb;
-            e = ppo_launch_grad(cfg, n, rec_total, M, sample, row + start, rec_obs, rec_action, rec_logp, weights,
-                                critic, ws, mb, s);
-            if (e == hipSuccess)
-                e = ppo_launch_apply(cfg, n, M, true, nullptr, nullptr, true, nullptr, nullptr, weights, critic, adam,
-                                     adam_step, stats, step_log, step, ws, mb, s);
-        }
-    }
-    return e == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+    return ppo_launch_update(cfg, n, rec_total, sample, perm, rec_obs, rec_action, rec_logp, adv, ret, weights, critic,
+                             adam, adam_step, stats, step_log, adv_norm_out, ret_norm_out, (char*)workspace,
+                             (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
 }
 
 int dart_lmpc_ppo_update(const dart_lmpc_ppo_config* cfg, int n, int rec_total, const int32_t* sample,
@@ -265,8 +289,7 @@ int dart_lmpc_critic_value_dev(int n, const float* critic, const float* obs, flo
     if (n < 0) return DART_MPC_EINVAL;
     if (n == 0) return DART_MPC_OK;
     if (!critic || !obs || !value_out) return DART_MPC_EINVAL;
-    dartmpc::CriticValueArgs a;
-    a.n = n; a.critic = critic; a.obs = obs; a.value = value_out;
+    const dartmpc::CriticValueArgs a{n, critic, obs, value_out};
     return dartmpc_launch_critic_value(&a, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
 }
 
@@ -463,7 +486,9 @@ int dart_lmpc_global_fill_after(int n, int fill, int iterations) {
 size_t dart_lmpc_global_workspace_bytes(int n, int epochs, int mini_batch_size) {
     if (n < 1 || epochs < 0 || mini_batch_size < 1 || mini_batch_size > dartmpc::kPpoMaxBatch) return 0;
     if ((long long)n + n / 4 > 0x7fffffffLL) return 0;
-    return dartmpc::global_workspace(n, epochs, mini_batch_size).bytes;
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    return dartmpc::global_workspace(1, n, G, epochs, mini_batch_size).bytes;
 }
 
 namespace {
@@ -665,7 +690,7 @@ size_t dart_lmpc_train_workspace_bytes(int B, int K, int record_every, int epoch
     if (B < 1 || record_every < 1 || K < record_every || K % record_every != 0 || epochs < 0 || mini_batch_size < 1 ||
         mini_batch_size > dartmpc::kPpoMaxBatch) return 0;
     if ((long long)(K / record_every) * B > 0x7fffffffLL) return 0;
-    return dartmpc::train_workspace(B, K, record_every, epochs, mini_batch_size).bytes;
+    return dartmpc::train_workspace(1, B, K, record_every, epochs, mini_batch_size).bytes;
 }
 
 namespace {
@@ -701,30 +726,152 @@ int global_check(dart_mpc_handle* h, const dart_lmpc_global_buffer* g, int n, bo
     return DART_MPC_OK;
 }
 
-}  // namespace
+// the checks of a population's shape: P learners of B instances each, R records per instance
+int pop_check(dart_mpc_handle* h, const dart_lmpc_reward_config* rcfg, const dart_lmpc_train_config* cfg, int P,
+              const uint64_t* seeds, int B) {
+    if (P < 1 || P > DART_LMPC_POP_MAX) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+    if (!seeds) return fail(h, DART_MPC_EINVAL, "population: null seeds");
+    if ((long long)P * B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "population: P * B larger than B_max");
+    if ((long long)(cfg->steps / rcfg->record_every) * P * B > 0x7fffffffLL)
+        return fail(h, DART_MPC_EINVAL, "too many samples");
+    return DART_MPC_OK;
+}
 
-// (g == nullptr: dart_lmpc_train_dev)
-int dart_lmpc_train_global_dev(dart_mpc_handle* h, const dart_plant_config* plant,
-                               const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* rcfg,
-                               const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg, int B,
-                               int reset_rows, const dart_lmpc_train_buffers* p, const dart_lmpc_global_buffer* g,
-                               void* stream) {
+// Who trains.  P = 0: one learner of B instances in the single-learner launches, its generator keyed by `seed`;
+// P >= 1: P learners of B instances each, stacked learner-major, in the population's launches, keyed by `keys`.  (A
+// population of one is not the single learner: the kernels differ, and the launch sequence is part of the entries.)
+struct Learners {
+    int P, B;
+    uint64_t seed;
+    dartmpc::PopKeys keys;
+    int count() const { return P > 0 ? P : 1; }
+};
+
+// rows between the learners' blocks of the global workspace: the buffers' capacity; the single learner's workspace
+// is addressed by its buffer's rows, all below G
+int global_stride(int P, int n, const dart_lmpc_global_buffer* g) {
+    int m, G;
+    dartmpc::global_rows(n, m, G);
+    return P > 0 && g ? g->capacity : G;
+}
+
+// ---- the steps of an iteration whose launch depends on the form, each stated once (with ppo_launch_* above) ----
+
+// the sample lists [count][R B]: the flat indices of a learner's records in the record arrays
+hipError_t launch_sample(const Learners& w, int R, int32_t* out, hipStream_t s) {
+    if (w.P > 0) {
+        const dartmpc::PopSampleArgs a{w.P, w.B, R, out};
+        return dartmpc_launch_lmpc_pop_sample(&a, s);
+    }
+    const dartmpc::IotaArgs a{R * w.B, out};
+    return dartmpc_launch_iota(&a, s);
+}
+
+// the sample lists [count][G] over the buffers' rows, the buffers `stride` rows apart
+hipError_t launch_global_sample(const Learners& w, int G, int stride, int32_t* out, hipStream_t s) {
+    if (w.P > 0) {
+        const dartmpc::PopGlobalSampleArgs a{w.P, G, stride, out};
+        return dartmpc_launch_lmpc_pop_global_sample(&a, s);
+    }
+    const dartmpc::IotaArgs a{G, out};
+    return dartmpc_launch_iota(&a, s);
+}
+
+hipError_t launch_noise(const Learners& w, int iteration, int steps, float* out, hipStream_t s) {
+    if (w.P == 0) return launch_noise(w.seed, iteration, steps, w.B, out, s);
+    dartmpc::NoisePopArgs a;
+    a.n = (long long)steps * w.B * kAct; a.B = w.B; a.P = w.P; a.iteration = (uint32_t)iteration; a.keys = w.keys;
+    a.out = out;
+    return dartmpc_launch_lmpc_noise_pop(&a, s);
+}
+
+// every learner's critic on its n rows of obs: the learners' rows follow one another (obs_stride = 0) or start
+// obs_stride rows apart
+hipError_t launch_value(const Learners& w, int n, const float* critic, const float* obs, long long obs_stride,
+                        float* value, hipStream_t s) {
+    const dartmpc::CriticValueArgs a{n, critic, obs, value};
+    if (w.P == 0) return dartmpc_launch_critic_value(&a, s);
+    if (obs_stride == 0) {
+        const dartmpc::CriticValuePopArgs q{a, w.P};
+        return dartmpc_launch_critic_value_pop(&q, s);
+    }
+    const dartmpc::CriticValueStridePopArgs q{a, w.P, obs_stride};
+    return dartmpc_launch_critic_value_stride_pop(&q, s);
+}
+
+hipError_t launch_perms(const Learners& w, int iteration, int epochs, int n, int32_t* perm, hipStream_t s,
+                        uint32_t rng_stream, int limit) {
+    if (w.P > 0) return launch_perms_pop(w.P, w.keys, iteration, epochs, n, perm, s, rng_stream, limit);
+    return launch_perms(w.seed, iteration, epochs, n, perm, nullptr, s, rng_stream, limit);
+}
+
+hipError_t launch_global_append(const Learners& w, const dart_lmpc_global_buffer* g, int fill, int m, int n,
+                                long long rec_total, const int32_t* sample, const int32_t* choice,
+                                const dart_lmpc_train_buffers& p, hipStream_t s) {
+    if (w.P > 0)
+        return launch_global_append_pop(g, w.P, fill, m, n, rec_total, sample, choice, p.rec_obs, p.rec_action,
+                                        p.rec_logp, p.rec_value, p.rec_reward, p.rec_done, s);
+    return launch_global_append(g, fill, m, n, (int)rec_total, sample, choice, p.rec_obs, p.rec_action, p.rec_logp,
+                                p.rec_value, p.rec_reward, p.rec_done, s);
+}
+
+hipError_t launch_gae_seq(const Learners& w, const dart_lmpc_global_buffer* g, int G, double gamma, double lam,
+                          const float* last_value, double* adv, double* ret, hipStream_t s) {
+    if (w.P > 0)
+        return launch_gae_seq_pop(w.P, g->capacity, G, gamma, lam, g->reward, g->value, g->done, last_value, adv, ret, s);
+    return launch_gae_seq(G, gamma, lam, g->reward, g->value, g->done, last_value, adv, ret, s);
+}
+
+// the log rows: `a` is learner 0's, row j of its `iterations`
+hipError_t launch_train_log(const Learners& w, const dartmpc::TrainLogArgs& a, int iterations, hipStream_t s) {
+    if (w.P == 0) return dartmpc_launch_lmpc_train_log(&a, s);
+    const dartmpc::TrainLogPopArgs q{a, w.P, (long long)dartmpc::kTrainLogCols * iterations};
+    return dartmpc_launch_lmpc_train_log_pop(&q, s);
+}
+
+hipError_t launch_global_log(const Learners& w, const dartmpc::GlobalLogArgs& a, int iterations, hipStream_t s) {
+    if (w.P == 0) return dartmpc_launch_lmpc_global_log(&a, s);
+    const dartmpc::GlobalLogPopArgs q{a, w.P, (long long)dartmpc::kGlobalLogCols * iterations};
+    return dartmpc_launch_lmpc_global_log_pop(&q, s);
+}
+
+// The device form of the training entries: whole iterations enqueued on one stream.  P = 0:
+// dart_lmpc_train_global_dev (g == nullptr: dart_lmpc_train_dev); P >= 1: dart_lmpc_train_pop_global_dev, every step
+// issued once for all P learners (the P buffers of g are stacked learner-major, g->capacity rows apart).  Every check
+// runs before the first launch.
+int train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+              const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg,
+              int P, const uint64_t* seeds, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+              const dart_lmpc_global_buffer* g, void* stream) {
     DART_ENTER(h, -1);
     if (int rc = train_check(h, rcfg, ppo, cfg, B, p, true)) return rc;
+    if (P > 0)
+        if (int rc = pop_check(h, rcfg, cfg, P, seeds, B)) return rc;
+    if (!aligned16(p->weights) || !aligned16(p->critic))
+        return fail(h, DART_MPC_EINVAL, "policy and critic weights must be 16-byte aligned");
+    // the learners' keys travel in the launch arguments: nothing is read from seeds after this
+    const Learners w{P, B, cfg->seed, P > 0 ? pop_keys(P, seeds) : dartmpc::PopKeys{}};
+    const int NI = w.count() * B;                   // instances, learner-major
     const int K = cfg->steps, R = K / rcfg->record_every, n = R * B, mb = ppo->mini_batch_size;
+    const long long rec_total = (long long)R * NI;
     if (g) {
         if (int rc = global_check(h, g, n, true)) return rc;
+        if ((long long)w.count() * g->capacity > 0x7fffffffLL) return fail(h, DART_MPC_EINVAL, "too many buffer rows");
         if (!aligned16(p->rec_obs)) return fail(h, DART_MPC_EINVAL, "rec_obs is not 16-byte aligned");
     }
     void* s = stream_of(h, stream);
     auto collect = [&](int steps, const float* noise) {
-        return lmpc_closed_loop(h, plant, pcfg, rcfg, true, B, 0, steps, K, R, reset_rows, *p, noise, s);
+        return lmpc_closed_loop(h, plant, pcfg, rcfg, true, NI, 0, steps, K, R, reset_rows, *p, noise, s, P > 0 ? B : 0);
     };
-    // every check of the collection (configs, null pointers, B <= B_max) before any device work: zero steps
+    // every check of the collection (configs, null pointers, B <= B_max, the handle's variant): zero steps
     if (int rc = collect(0, nullptr)) return rc;
+    dartmpc::MeanUpdateArgs ma;
+    if (mean_update_args(pcfg, NI, p->weights, ma) != DART_MPC_OK) return fail(h, DART_MPC_EINVAL, "bad policy config");
+    ma.learner_B = P > 0 ? B : 0;
+    ma.history = p->history; ma.model_params = p->model_params; ma.current_k = p->current_k; ma.mean_out = nullptr;
     if (cfg->iterations == 0) return DART_MPC_OK;
     HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    const dartmpc::TrainWorkspace L = dartmpc::train_workspace(B, K, rcfg->record_every, ppo->epochs, mb);
+    const dartmpc::TrainWorkspace L = dartmpc::train_workspace(w.count(), B, K, rcfg->record_every, ppo->epochs, mb);
     char* ws = (char*)p->workspace;
     float* noise = (float*)(ws + L.noise);
     float* last_value = (float*)(ws + L.last_value);
@@ -735,10 +882,13 @@ int dart_lmpc_train_global_dev(dart_mpc_handle* h, const dart_plant_config* plan
     double* stats = (double*)(ws + L.stats);
     int32_t* ep0 = (int32_t*)(ws + L.ep0);
     hipStream_t hs = (hipStream_t)s;
-    // the global update's sizes, workspace and running fill (the host knows every launch from n and g->fill)
+    const PpoPop pop{P, L.ppo_stride, (size_t)ppo->epochs * n};
+    // the global update's sizes, workspace and running fill, one for all learners (they share n; the host knows
+    // every launch from n and g->fill)
     int gm = 0, gG = 0, g_fill = g ? g->fill : 0;
     dartmpc::global_rows(n, gm, gG);
-    const dartmpc::GlobalWorkspace GL = dartmpc::global_workspace(n, ppo->epochs, mb);
+    const int g_stride = global_stride(P, n, g);
+    const dartmpc::GlobalWorkspace GL = dartmpc::global_workspace(w.count(), n, g_stride, ppo->epochs, mb);
     char* gws = g ? (char*)g->workspace : nullptr;
     auto gp = [&](size_t off) { return gws ? gws + off : nullptr; };
     int32_t* g_choice = (int32_t*)gp(GL.choice);
@@ -748,69 +898,57 @@ int dart_lmpc_train_global_dev(dart_mpc_handle* h, const dart_plant_config* plan
     int32_t* g_sample = (int32_t*)gp(GL.sample);
     int32_t* g_perm = (int32_t*)gp(GL.perm);
     double* g_stats = (double*)gp(GL.stats);
-    {
-        dartmpc::IotaArgs ia;
-        ia.n = n; ia.out = sample;
-        HIPCHK(h, dartmpc_launch_iota(&ia, hs), "sample list launch");
-    }
+    const PpoPop gpop{P, GL.ppo_stride, (size_t)ppo->epochs * gG};
+    const size_t stats_bytes = sizeof(double) * 3 * (size_t)w.count();
+    HIPCHK(h, launch_sample(w, R, sample, hs), "sample list launch");
     for (int j = 0; j < cfg->iterations; ++j) {
         const int it = cfg->it0 + j;
-        HIPCHK(h, hipMemsetAsync(p->nrec, 0, sizeof(int32_t) * (size_t)B, hs), "clear nrec");
-        HIPCHK(h, hipMemcpyAsync(ep0, p->episodes, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, hs),
+        HIPCHK(h, hipMemsetAsync(p->nrec, 0, sizeof(int32_t) * (size_t)NI, hs), "clear nrec");
+        HIPCHK(h, hipMemcpyAsync(ep0, p->episodes, sizeof(int32_t) * (size_t)NI, hipMemcpyDeviceToDevice, hs),
                "copy episodes");
         // (with epochs = 0 the update leaves its statistics untouched)
-        if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(double) * 3, hs), "clear stats");
-        HIPCHK(h, launch_noise(cfg->seed, it, K, B, noise, hs), "noise launch");
+        if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(stats, 0, stats_bytes, hs), "clear stats");
+        HIPCHK(h, launch_noise(w, it, K, noise, hs), "noise launch");
         if (int rc = collect(K, noise)) return rc;
-        if (dart_lmpc_critic_value_dev(B, p->critic, p->history, last_value, s) != DART_MPC_OK)
-            return fail(h, DART_MPC_EHIP, "critic value launch");
-        if (dart_lmpc_gae_dev(B, R, cfg->gamma, cfg->lam, p->nrec, p->rec_reward, p->rec_value, p->rec_done,
-                              last_value, adv, ret, s) != DART_MPC_OK)
-            return fail(h, DART_MPC_EHIP, "GAE launch");
-        HIPCHK(h, launch_perms(cfg->seed, it, ppo->epochs, n, perm, nullptr, hs), "permutation launch");
-        if (int rc = dart_lmpc_ppo_update_dev(ppo, n, n, sample, perm, p->rec_obs, p->rec_action, p->rec_logp, adv,
-                                              ret, p->weights, p->critic, p->adam, p->adam_step, stats, nullptr,
-                                              nullptr, nullptr, ws + L.ppo, s))
-            return fail(h, rc, "PPO update");
+        HIPCHK(h, launch_value(w, B, p->critic, p->history, 0, last_value, hs), "critic value launch");
+        HIPCHK(h, launch_gae(NI, R, cfg->gamma, cfg->lam, p->nrec, p->rec_reward, p->rec_value, p->rec_done, last_value,
+                             adv, ret, hs), "GAE launch");
+        HIPCHK(h, launch_perms(w, it, ppo->epochs, n, perm, hs, dartmpc::kStreamPerm, n), "permutation launch");
+        HIPCHK(h, ppo_launch_update(ppo, n, rec_total, sample, perm, p->rec_obs, p->rec_action, p->rec_logp, adv, ret,
+                                    p->weights, p->critic, p->adam, p->adam_step, stats, nullptr, nullptr, nullptr,
+                                    ws + L.ppo, hs, pop), "PPO update launch");
         if (g) {
-            // 6a: m of this iteration's records, drawn without replacement, behind the rows held
-            HIPCHK(h, launch_perms(cfg->seed, it, 1, n, g_choice, nullptr, hs, dartmpc::kStreamChoice, gm),
-                   "choice launch");
-            HIPCHK(h, launch_global_append(g, g_fill, gm, n, n, sample, g_choice, p->rec_obs, p->rec_action,
-                                           p->rec_logp, p->rec_value, p->rec_reward, p->rec_done, hs),
+            // 6a: every learner draws m of this iteration's records without replacement and appends them behind the
+            // rows it holds
+            HIPCHK(h, launch_perms(w, it, 1, n, g_choice, hs, dartmpc::kStreamChoice, gm), "choice launch");
+            HIPCHK(h, launch_global_append(w, g, g_fill, gm, n, rec_total, sample, g_choice, *p, hs),
                    "global buffer append launch");
             g_fill += gm;
             const int ran = g_fill >= n ? 1 : 0;
             const int logged_fill = g_fill;
             if (ran) {
-                // 6b: the buffer holds G rows: one sequence for GAE, then a full update on the same optimizer
-                if (dart_lmpc_critic_value_dev(1, p->critic, g->obs + (size_t)(gG - 1) * kHist, g_last, s) != DART_MPC_OK)
-                    return fail(h, DART_MPC_EHIP, "critic value launch (global buffer)");
-                HIPCHK(h, launch_gae_seq(gG, cfg->gamma, cfg->lam, g->reward, g->value, g->done, g_last, g_adv, g_ret,
-                                         hs), "sequence GAE launch");
-                {
-                    dartmpc::IotaArgs ia;
-                    ia.n = gG; ia.out = g_sample;
-                    HIPCHK(h, dartmpc_launch_iota(&ia, hs), "sample list launch (global buffer)");
-                }
-                if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(g_stats, 0, sizeof(double) * 3, hs), "clear stats");
-                HIPCHK(h, launch_perms(cfg->seed, it, ppo->epochs, gG, g_perm, nullptr, hs,
-                                       dartmpc::kStreamGlobalPerm), "permutation launch (global buffer)");
-                if (int rc = dart_lmpc_ppo_update_dev(ppo, gG, gG, g_sample, g_perm, g->obs, g->action, g->logp, g_adv,
-                                                      g_ret, p->weights, p->critic, p->adam, p->adam_step, g_stats,
-                                                      nullptr, nullptr, nullptr, gws + GL.ppo, s))
-                    return fail(h, rc, "PPO update (global buffer)");
+                // 6b: every buffer holds G rows: one sequence each for GAE, then a full update on the learner's
+                // optimizer
+                HIPCHK(h, launch_value(w, 1, p->critic, g->obs + (size_t)(gG - 1) * kHist, g_stride, g_last, hs),
+                       "critic value launch (global buffer)");
+                HIPCHK(h, launch_gae_seq(w, g, gG, cfg->gamma, cfg->lam, g_last, g_adv, g_ret, hs),
+                       "sequence GAE launch");
+                HIPCHK(h, launch_global_sample(w, gG, g_stride, g_sample, hs), "sample list launch (global buffer)");
+                if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(g_stats, 0, stats_bytes, hs), "clear stats");
+                HIPCHK(h, launch_perms(w, it, ppo->epochs, gG, g_perm, hs, dartmpc::kStreamGlobalPerm, gG),
+                       "permutation launch (global buffer)");
+                HIPCHK(h, ppo_launch_update(ppo, gG, (long long)w.count() * g_stride, g_sample, g_perm, g->obs,
+                                            g->action, g->logp, g_adv, g_ret, p->weights, p->critic, p->adam,
+                                            p->adam_step, g_stats, nullptr, nullptr, nullptr, gws + GL.ppo, hs, gpop),
+                       "PPO update launch (global buffer)");
                 g_fill = 0;
             }
             dartmpc::GlobalLogArgs ga;
             ga.fill = logged_fill; ga.ran = ran; ga.G = gG; ga.stats = g_stats;
             ga.row = g->global_log + (size_t)dartmpc::kGlobalLogCols * j;
-            HIPCHK(h, dartmpc_launch_lmpc_global_log(&ga, hs), "global log launch");
+            HIPCHK(h, launch_global_log(w, ga, cfg->iterations, hs), "global log launch");
         }
-        if (cfg->mean_update)
-            if (dart_lmpc_mean_param_update_dev(pcfg, B, p->weights, p->history, p->model_params, p->current_k,
-                                                nullptr, s) != DART_MPC_OK)
-                return fail(h, DART_MPC_EHIP, "mean parameter update launch");
+        if (cfg->mean_update) HIPCHK(h, dartmpc_launch_lmpc_mean_update(&ma, hs), "mean parameter update launch");
         dartmpc::TrainLogArgs la;
         la.B = B; la.K = K; la.R = R; la.n = n; la.iteration = it; la.track_best = cfg->track_best ? 1 : 0;
         la.ep0 = ep0; la.episodes = p->episodes; la.last_return = p->last_return; la.nrec = p->nrec;
@@ -818,28 +956,8 @@ int dart_lmpc_train_global_dev(dart_mpc_handle* h, const dart_plant_config* plan
         la.actor = p->weights; la.critic = p->critic;
         la.row = p->train_log + (size_t)dartmpc::kTrainLogCols * j;
         la.best_return = p->best_return; la.best_weights = p->best_weights; la.best_iter = p->best_iter;
-        HIPCHK(h, dartmpc_launch_lmpc_train_log(&la, hs), "training log launch");
+        HIPCHK(h, launch_train_log(w, la, cfg->iterations, hs), "training log launch");
     }
-    return DART_MPC_OK;
-}
-
-int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
-                        const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
-                        const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
-                        void* stream) {
-    return dart_lmpc_train_global_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, nullptr, stream);
-}
-
-namespace {
-
-// the checks of a population's shape: P learners of B instances each, R records per instance
-int pop_check(dart_mpc_handle* h, const dart_lmpc_reward_config* rcfg, const dart_lmpc_train_config* cfg, int P,
-              const uint64_t* seeds, int B) {
-    if (P < 1 || P > DART_LMPC_POP_MAX) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
-    if (!seeds) return fail(h, DART_MPC_EINVAL, "population: null seeds");
-    if ((long long)P * B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "population: P * B larger than B_max");
-    if ((long long)(cfg->steps / rcfg->record_every) * P * B > 0x7fffffffLL)
-        return fail(h, DART_MPC_EINVAL, "too many samples");
     return DART_MPC_OK;
 }
 
@@ -857,8 +975,8 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
     if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, "handle is not an LMPC handle");
     if (P > 0)
         if (int rc = pop_check(h, rcfg, cfg, P, seeds, B)) return rc;
-    const int learner_B = B;
-    B *= P > 0 ? P : 1;                            // every instance from here on
+    const int learner_B = B, nl = P > 0 ? P : 1;
+    B *= nl;                                       // every instance from here on
     if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
     if (reset_rows < 0) return fail(h, DART_MPC_EINVAL, "negative reset_rows");
     if (lmpc_null(*p, kLoop) || lmpc_null(*p, kPolicy) || lmpc_null(*p, kCollect) || lmpc_null(*p, kCollect, kRec))
@@ -881,19 +999,18 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
     RollStage S;
     int idx[kLmpcArrays];
     lmpc_stage(S, *p, m, idx);
-    const size_t log_rows = (size_t)cfg->iterations * (size_t)(P > 0 ? P : 1);
+    const size_t log_rows = (size_t)cfg->iterations * (size_t)nl;
     const int i_log = S.add_log(p->train_log, log_rows, dartmpc::kTrainLogCols * D, 0, log_rows, false);
     // the workspace: a block of the arena that does not travel
     const size_t ws_bytes =
-        P > 0 ? dartmpc::train_pop_workspace(P, learner_B, (int)K, rcfg->record_every, ppo->epochs, ppo->mini_batch_size).bytes
-              : dartmpc::train_workspace(B, (int)K, rcfg->record_every, ppo->epochs, ppo->mini_batch_size).bytes;
+        dartmpc::train_workspace(nl, learner_B, (int)K, rcfg->record_every, ppo->epochs, ppo->mini_batch_size).bytes;
     const int i_ws = S.add_log(nullptr, 1, ws_bytes, 0, 0, false);
     // the global buffer: blocks of the arena whose held rows travel by hand (those held at the start go up, those
     // held at the end come down), its log, and its workspace
     dart_lmpc_global_buffer gd;
     int gi[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     size_t g_rowbytes[6] = {kHist * F, kAct * F, F, F, D, F};
-    const size_t g_bufs = P > 0 ? (size_t)P : 1;     // buffers, g->capacity rows apart
+    const size_t g_bufs = (size_t)nl;                // buffers, g->capacity rows apart
     const int g_n = (int)R * learner_B;
     if (g) {
         gd = *g;
@@ -902,8 +1019,7 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
         for (int q = 0; q < 6; ++q) gi[q] = S.add_log(nullptr, 1, g_bufs * cap * g_rowbytes[q], 0, 0, false);
         gi[6] = S.add_log(g->global_log, log_rows, dartmpc::kGlobalLogCols * D, 0, log_rows, false);
         gi[7] = S.add_log(nullptr, 1,
-                          P > 0 ? dartmpc::global_pop_workspace(P, g_n, g->capacity, ppo->epochs, ppo->mini_batch_size).bytes
-                                : dartmpc::global_workspace(g_n, ppo->epochs, ppo->mini_batch_size).bytes,
+                          dartmpc::global_workspace(nl, g_n, global_stride(P, g_n, g), ppo->epochs, ppo->mini_batch_size).bytes,
                           0, 0, false);
     }
     if (int rc = S.reserve(h)) return rc;
@@ -927,10 +1043,7 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
                        "copy global buffer");
             }
     }
-    if (int rc = P > 0 ? dart_lmpc_train_pop_global_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, learner_B, reset_rows,
-                                                        &d, g ? &gd : nullptr, s)
-                       : dart_lmpc_train_global_dev(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, &d,
-                                                    g ? &gd : nullptr, s)) {
+    if (int rc = train_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, learner_B, reset_rows, &d, g ? &gd : nullptr, s)) {
         (void)hipStreamSynchronize(s);
         return rc;
     }
@@ -960,7 +1073,7 @@ size_t dart_lmpc_train_pop_workspace_bytes(int P, int B, int K, int record_every
     if (P < 1 || P > DART_LMPC_POP_MAX) return 0;
     if (dart_lmpc_train_workspace_bytes(B, K, record_every, epochs, mini_batch_size) == 0) return 0;
     if ((long long)(K / record_every) * P * B > 0x7fffffffLL) return 0;
-    return dartmpc::train_pop_workspace(P, B, K, record_every, epochs, mini_batch_size).bytes;
+    return dartmpc::train_workspace(P, B, K, record_every, epochs, mini_batch_size).bytes;
 }
 
 size_t dart_lmpc_global_pop_workspace_bytes(int P, int n, int capacity, int epochs, int mini_batch_size) {
@@ -969,184 +1082,34 @@ size_t dart_lmpc_global_pop_workspace_bytes(int P, int n, int capacity, int epoc
     int m, G;
     dartmpc::global_rows(n, m, G);
     if (capacity < G || (long long)P * capacity > 0x7fffffffLL) return 0;
-    return dartmpc::global_pop_workspace(P, n, capacity, epochs, mini_batch_size).bytes;
+    return dartmpc::global_workspace(P, n, capacity, epochs, mini_batch_size).bytes;
 }
 
-// dart_lmpc_train_global_dev's launch sequence, each step issued once for all P learners (g == nullptr:
-// dart_lmpc_train_dev's; the P buffers of g are stacked learner-major, g->capacity rows apart)
+// (g == nullptr: dart_lmpc_train_dev)
+int dart_lmpc_train_global_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                               const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* rcfg,
+                               const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg, int B,
+                               int reset_rows, const dart_lmpc_train_buffers* p, const dart_lmpc_global_buffer* g,
+                               void* stream) {
+    return train_dev(h, plant, pcfg, rcfg, ppo, cfg, 0, nullptr, B, reset_rows, p, g, stream);
+}
+
+int dart_lmpc_train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                        const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                        const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                        void* stream) {
+    return train_dev(h, plant, pcfg, rcfg, ppo, cfg, 0, nullptr, B, reset_rows, p, nullptr, stream);
+}
+
+// (g == nullptr: dart_lmpc_train_pop_dev)
 int dart_lmpc_train_pop_global_dev(dart_mpc_handle* h, const dart_plant_config* plant,
                                    const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* rcfg,
                                    const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg, int P,
                                    const uint64_t* seeds, int B, int reset_rows, const dart_lmpc_train_buffers* p,
                                    const dart_lmpc_global_buffer* g, void* stream) {
     DART_ENTER(h, -1);
-    if (int rc = train_check(h, rcfg, ppo, cfg, B, p, true)) return rc;
-    if (int rc = pop_check(h, rcfg, cfg, P, seeds, B)) return rc;
-    if (!aligned16(p->weights) || !aligned16(p->critic))
-        return fail(h, DART_MPC_EINVAL, "policy and critic weights must be 16-byte aligned");
-    const int NI = P * B;                           // instances, learner-major
-    const int K = cfg->steps, R = K / rcfg->record_every, n = R * B, mb = ppo->mini_batch_size;
-    const long long rec_total = (long long)R * NI;
-    if (g) {
-        if (int rc = global_check(h, g, n, true)) return rc;
-        if ((long long)P * g->capacity > 0x7fffffffLL) return fail(h, DART_MPC_EINVAL, "too many buffer rows");
-        if (!aligned16(p->rec_obs)) return fail(h, DART_MPC_EINVAL, "rec_obs is not 16-byte aligned");
-    }
-    void* s = stream_of(h, stream);
-    auto collect = [&](int steps, const float* noise) {
-        return lmpc_closed_loop(h, plant, pcfg, rcfg, true, NI, 0, steps, K, R, reset_rows, *p, noise, s, B);
-    };
-    // every check of the collection (configs, null pointers, the handle's variant) before any device work: zero steps
-    if (int rc = collect(0, nullptr)) return rc;
-    dartmpc::MeanUpdateArgs ma;
-    if (mean_update_args(pcfg, NI, p->weights, ma) != DART_MPC_OK) return fail(h, DART_MPC_EINVAL, "bad policy config");
-    if (cfg->iterations == 0) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    const dartmpc::TrainPopWorkspace L = dartmpc::train_pop_workspace(P, B, K, rcfg->record_every, ppo->epochs, mb);
-    char* ws = (char*)p->workspace;
-    float* noise = (float*)(ws + L.noise);
-    float* last_value = (float*)(ws + L.last_value);
-    double* adv = (double*)(ws + L.adv);
-    double* ret = (double*)(ws + L.ret);
-    int32_t* sample = (int32_t*)(ws + L.sample);
-    int32_t* perm = (int32_t*)(ws + L.perm);
-    double* stats = (double*)(ws + L.stats);
-    int32_t* ep0 = (int32_t*)(ws + L.ep0);
-    hipStream_t hs = (hipStream_t)s;
-    // the learners' keys travel in the launch arguments: nothing is read from seeds after this loop
-    const dartmpc::PopKeys keys = pop_keys(P, seeds);
-    PpoPop pop;
-    pop.P = P; pop.ws_stride = L.ppo_stride; pop.idx_stride = (size_t)ppo->epochs * n;
-    {
-        dartmpc::PopSampleArgs sa;
-        sa.P = P; sa.B = B; sa.R = R; sa.out = sample;
-        HIPCHK(h, dartmpc_launch_lmpc_pop_sample(&sa, hs), "sample list launch");
-    }
-    // the global update's sizes, workspace and running fill, one for all learners (they share n)
-    int gm = 0, gG = 0, g_fill = g ? g->fill : 0;
-    dartmpc::global_rows(n, gm, gG);
-    const int cap = g ? g->capacity : gG;
-    const dartmpc::GlobalPopWorkspace GL = dartmpc::global_pop_workspace(P, n, cap, ppo->epochs, mb);
-    char* gws = g ? (char*)g->workspace : nullptr;
-    auto gp = [&](size_t off) { return gws ? gws + off : nullptr; };
-    int32_t* g_choice = (int32_t*)gp(GL.choice);
-    double* g_adv = (double*)gp(GL.adv);
-    double* g_ret = (double*)gp(GL.ret);
-    float* g_last = (float*)gp(GL.last_value);
-    int32_t* g_sample = (int32_t*)gp(GL.sample);
-    int32_t* g_perm = (int32_t*)gp(GL.perm);
-    double* g_stats = (double*)gp(GL.stats);
-    PpoPop gpop;
-    gpop.P = P; gpop.ws_stride = GL.ppo_stride; gpop.idx_stride = (size_t)ppo->epochs * gG;
-    const long long g_total = (long long)P * cap;
-    for (int j = 0; j < cfg->iterations; ++j) {
-        const int it = cfg->it0 + j;
-        HIPCHK(h, hipMemsetAsync(p->nrec, 0, sizeof(int32_t) * (size_t)NI, hs), "clear nrec");
-        HIPCHK(h, hipMemcpyAsync(ep0, p->episodes, sizeof(int32_t) * (size_t)NI, hipMemcpyDeviceToDevice, hs),
-               "copy episodes");
-        if (ppo->epochs == 0) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(double) * 3 * (size_t)P, hs), "clear stats");
-        {
-            dartmpc::NoisePopArgs na;
-            na.n = (long long)K * B * kAct; na.B = B; na.P = P; na.iteration = (uint32_t)it; na.keys = keys;
-            na.out = noise;
-            HIPCHK(h, dartmpc_launch_lmpc_noise_pop(&na, hs), "noise launch");
-        }
-        if (int rc = collect(K, noise)) return rc;
-        {
-            dartmpc::CriticValuePopArgs va;
-            va.a.n = B; va.a.critic = p->critic; va.a.obs = p->history; va.a.value = last_value; va.P = P;
-            HIPCHK(h, dartmpc_launch_critic_value_pop(&va, hs), "critic value launch");
-        }
-        if (dart_lmpc_gae_dev(NI, R, cfg->gamma, cfg->lam, p->nrec, p->rec_reward, p->rec_value, p->rec_done,
-                              last_value, adv, ret, s) != DART_MPC_OK)
-            return fail(h, DART_MPC_EHIP, "GAE launch");
-        HIPCHK(h, launch_perms_pop(P, keys, it, ppo->epochs, n, perm, hs, dartmpc::kStreamPerm, n), "permutation launch");
-        // dart_lmpc_ppo_update_dev's launches, every learner in each
-        HIPCHK(h, ppo_launch_prepare(n, rec_total, sample, adv, ret, nullptr, nullptr, ws + L.ppo, mb, hs, pop),
-               "PPO prepare launch");
-        int step = 0;
-        for (int ep = 0; ep < ppo->epochs; ++ep) {
-            const int32_t* row = perm + (size_t)ep * n;
-            for (int start = 0; start < n; start += mb, ++step) {
-                const int M = n - start < mb ? n - start : mb;
-                HIPCHK(h, ppo_launch_grad(ppo, n, rec_total, M, sample, row + start, p->rec_obs, p->rec_action,
-                                          p->rec_logp, p->weights, p->critic, ws + L.ppo, mb, hs, pop),
-                       "PPO gradient launch");
-                HIPCHK(h, ppo_launch_apply(ppo, n, M, true, nullptr, nullptr, true, nullptr, nullptr, p->weights,
-                                           p->critic, p->adam, p->adam_step, stats, nullptr, step, ws + L.ppo, mb, hs,
-                                           pop), "PPO apply launch");
-            }
-        }
-        if (g) {
-            // 6a: every learner draws m of its records and appends them behind the rows it holds
-            HIPCHK(h, launch_perms_pop(P, keys, it, 1, n, g_choice, hs, dartmpc::kStreamChoice, gm), "choice launch");
-            HIPCHK(h, launch_global_append_pop(g, P, g_fill, gm, n, rec_total, sample, g_choice, p->rec_obs,
-                                               p->rec_action, p->rec_logp, p->rec_value, p->rec_reward, p->rec_done,
-                                               hs), "global buffer append launch");
-            g_fill += gm;
-            const int ran = g_fill >= n ? 1 : 0;
-            const int logged_fill = g_fill;
-            if (ran) {
-                // 6b: every buffer holds G rows: one sequence each for GAE, then a full update on the learner's
-                // optimizer -- dart_lmpc_ppo_update_dev's launches on the buffers' rows, every learner in each
-                {
-                    dartmpc::CriticValueStridePopArgs va;
-                    va.a.n = 1; va.a.critic = p->critic; va.a.obs = g->obs + (size_t)(gG - 1) * kHist;
-                    va.a.value = g_last; va.P = P; va.obs_stride = cap;
-                    HIPCHK(h, dartmpc_launch_critic_value_stride_pop(&va, hs), "critic value launch (global buffer)");
-                }
-                HIPCHK(h, launch_gae_seq_pop(P, cap, gG, cfg->gamma, cfg->lam, g->reward, g->value, g->done, g_last,
-                                             g_adv, g_ret, hs), "sequence GAE launch");
-                {
-                    dartmpc::PopGlobalSampleArgs sa;
-                    sa.P = P; sa.G = gG; sa.capacity = cap; sa.out = g_sample;
-                    HIPCHK(h, dartmpc_launch_lmpc_pop_global_sample(&sa, hs), "sample list launch (global buffer)");
-                }
-                if (ppo->epochs == 0)
-                    HIPCHK(h, hipMemsetAsync(g_stats, 0, sizeof(double) * 3 * (size_t)P, hs), "clear stats");
-                HIPCHK(h, launch_perms_pop(P, keys, it, ppo->epochs, gG, g_perm, hs, dartmpc::kStreamGlobalPerm, gG),
-                       "permutation launch (global buffer)");
-                HIPCHK(h, ppo_launch_prepare(gG, g_total, g_sample, g_adv, g_ret, nullptr, nullptr, gws + GL.ppo, mb,
-                                             hs, gpop), "PPO prepare launch (global buffer)");
-                int gstep = 0;
-                for (int ep = 0; ep < ppo->epochs; ++ep) {
-                    const int32_t* row = g_perm + (size_t)ep * gG;
-                    for (int start = 0; start < gG; start += mb, ++gstep) {
-                        const int M = gG - start < mb ? gG - start : mb;
-                        HIPCHK(h, ppo_launch_grad(ppo, gG, g_total, M, g_sample, row + start, g->obs, g->action,
-                                                  g->logp, p->weights, p->critic, gws + GL.ppo, mb, hs, gpop),
-                               "PPO gradient launch (global buffer)");
-                        HIPCHK(h, ppo_launch_apply(ppo, gG, M, true, nullptr, nullptr, true, nullptr, nullptr,
-                                                   p->weights, p->critic, p->adam, p->adam_step, g_stats, nullptr,
-                                                   gstep, gws + GL.ppo, mb, hs, gpop),
-                               "PPO apply launch (global buffer)");
-                    }
-                }
-                g_fill = 0;
-            }
-            dartmpc::GlobalLogPopArgs ga;
-            ga.a.fill = logged_fill; ga.a.ran = ran; ga.a.G = gG; ga.a.stats = g_stats;
-            ga.a.row = g->global_log + (size_t)dartmpc::kGlobalLogCols * j;
-            ga.P = P; ga.row_stride = (long long)dartmpc::kGlobalLogCols * cfg->iterations;
-            HIPCHK(h, dartmpc_launch_lmpc_global_log_pop(&ga, hs), "global log launch");
-        }
-        if (cfg->mean_update) {
-            ma.learner_B = B;
-            ma.history = p->history; ma.model_params = p->model_params; ma.current_k = p->current_k;
-            ma.mean_out = nullptr;
-            HIPCHK(h, dartmpc_launch_lmpc_mean_update(&ma, hs), "mean parameter update launch");
-        }
-        dartmpc::TrainLogPopArgs la;
-        la.a.B = B; la.a.K = K; la.a.R = R; la.a.n = n; la.a.iteration = it; la.a.track_best = cfg->track_best ? 1 : 0;
-        la.a.ep0 = ep0; la.a.episodes = p->episodes; la.a.last_return = p->last_return; la.a.nrec = p->nrec;
-        la.a.log_reward = p->log_reward; la.a.log_status = p->log_status; la.a.stats = stats;
-        la.a.actor = p->weights; la.a.critic = p->critic;
-        la.a.row = p->train_log + (size_t)dartmpc::kTrainLogCols * j;
-        la.a.best_return = p->best_return; la.a.best_weights = p->best_weights; la.a.best_iter = p->best_iter;
-        la.P = P; la.row_stride = (long long)dartmpc::kTrainLogCols * cfg->iterations;
-        HIPCHK(h, dartmpc_launch_lmpc_train_log_pop(&la, hs), "training log launch");
-    }
-    return DART_MPC_OK;
+    if (P < 1) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+    return train_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, B, reset_rows, p, g, stream);
 }
 
 int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,

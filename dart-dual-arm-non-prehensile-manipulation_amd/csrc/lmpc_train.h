@@ -206,16 +206,24 @@ struct GlobalLogPopArgs {
     long long row_stride;
 };
 
-// Workspace of dart_lmpc_train_pop_dev (bytes from the base, every block 256-byte aligned): the single run's blocks
-// with P B instances (noise, last_value, adv, ret, ep0), the per-learner sample lists, permutations and statistics,
-// and P workspaces of the update, ppo_stride bytes apart
-struct TrainPopWorkspace {
+// rows of the global buffer for n samples per iteration: m = max(1, n / 4) are drawn per iteration, and the buffer
+// is updated on when it holds G = ceil(n / m) m >= n rows
+inline void global_rows(int n, int& m, int& G) {
+    m = n / 4 > 1 ? n / 4 : 1;
+    G = (n + m - 1) / m * m;
+}
+
+// Workspace of a training iteration of P learners of B instances each (bytes from the base, every block 256-byte
+// aligned): noise, last_value, adv, ret and ep0 over the P B instances, the per-learner sample lists, permutations
+// and statistics, and P workspaces of the update, ppo_stride bytes apart.  P = 1 is dart_lmpc_train_dev's workspace,
+// block for block.
+struct TrainWorkspace {
     size_t noise, last_value, adv, ret, sample, perm, stats, ep0, ppo, ppo_stride, bytes;
 };
-inline TrainPopWorkspace train_pop_workspace(int P, int B, int K, int record_every, int epochs, int mb) {
+inline TrainWorkspace train_workspace(int P, int B, int K, int record_every, int epochs, int mb) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t PB_ = (size_t)P * B, R = (size_t)(K / record_every), n = R * (size_t)B;
-    TrainPopWorkspace w;
+    TrainWorkspace w;
     size_t o = 0;
     w.noise = o; o += al(sizeof(float) * (size_t)K * PB_ * 34);
     w.last_value = o; o += al(sizeof(float) * PB_);
@@ -231,71 +239,21 @@ inline TrainPopWorkspace train_pop_workspace(int P, int B, int K, int record_eve
     return w;
 }
 
-// Workspace of dart_lmpc_train_dev (bytes from the base, every block 256-byte aligned)
-struct TrainWorkspace {
-    size_t noise, last_value, adv, ret, sample, perm, stats, ep0, ppo, bytes;
-};
-inline TrainWorkspace train_workspace(int B, int K, int record_every, int epochs, int mb) {
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t R = (size_t)(K / record_every), n = R * (size_t)B;
-    TrainWorkspace w;
-    size_t o = 0;
-    w.noise = o; o += al(sizeof(float) * (size_t)K * B * 34);
-    w.last_value = o; o += al(sizeof(float) * (size_t)B);
-    w.adv = o; o += al(sizeof(double) * n);
-    w.ret = o; o += al(sizeof(double) * n);
-    w.sample = o; o += al(sizeof(int32_t) * n);
-    w.perm = o; o += al(sizeof(int32_t) * n * (size_t)(epochs > 0 ? epochs : 1));
-    w.stats = o; o += al(sizeof(double) * 3);
-    w.ep0 = o; o += al(sizeof(int32_t) * (size_t)B);
-    w.ppo = o; o += ppo_workspace((int)n, mb).bytes;
-    w.bytes = o;
-    return w;
-}
-
-// rows of the global buffer for n samples per iteration: m = max(1, n / 4) are drawn per iteration, and the buffer
-// is updated on when it holds G = ceil(n / m) m >= n rows
-inline void global_rows(int n, int& m, int& G) {
-    m = n / 4 > 1 ? n / 4 : 1;
-    G = (n + m - 1) / m * m;
-}
-
-// Workspace of the global update (bytes from the base, every block 256-byte aligned)
+// Workspace of the global update of P learners, their buffers `capacity` rows apart (bytes from the base, every block
+// 256-byte aligned): the choices [P][m], adv and ret [P][capacity] (addressed by the sample lists, like the buffers'
+// rows: the update's population kernels reach records, adv and ret through one index), the bootstrap values [P], the
+// sample lists [P][G], the permutations [P][epochs][G], the statistics [P][3] and P workspaces of the update over G
+// rows, ppo_stride bytes apart.  P = 1 with capacity = G is dart_lmpc_train_global_dev's workspace, block for block
+// (one buffer is addressed by its rows below G, whatever its capacity).
 struct GlobalWorkspace {
-    size_t choice, adv, ret, last_value, sample, perm, stats, ppo, bytes;
-};
-inline GlobalWorkspace global_workspace(int n, int epochs, int mb) {
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    int m, Gi;
-    global_rows(n, m, Gi);
-    const size_t G = (size_t)Gi;
-    GlobalWorkspace w;
-    size_t o = 0;
-    w.choice = o; o += al(sizeof(int32_t) * (size_t)m);
-    w.adv = o; o += al(sizeof(double) * G);
-    w.ret = o; o += al(sizeof(double) * G);
-    w.last_value = o; o += al(sizeof(float));
-    w.sample = o; o += al(sizeof(int32_t) * G);
-    w.perm = o; o += al(sizeof(int32_t) * G * (size_t)(epochs > 0 ? epochs : 1));
-    w.stats = o; o += al(sizeof(double) * 3);
-    w.ppo = o; o += ppo_workspace(Gi, mb).bytes;
-    w.bytes = o;
-    return w;
-}
-
-// Workspace of a population's global update (bytes from the base, every block 256-byte aligned): the choices [P][m],
-// adv and ret [P][capacity] (addressed by the sample lists, like the buffers' rows: the update's population kernels
-// reach records, adv and ret through one index), the bootstrap values [P], the sample lists [P][G], the permutations
-// [P][epochs][G], the statistics [P][3] and P workspaces of the update over G rows, ppo_stride bytes apart
-struct GlobalPopWorkspace {
     size_t choice, adv, ret, last_value, sample, perm, stats, ppo, ppo_stride, bytes;
 };
-inline GlobalPopWorkspace global_pop_workspace(int P, int n, int capacity, int epochs, int mb) {
+inline GlobalWorkspace global_workspace(int P, int n, int capacity, int epochs, int mb) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     int m, Gi;
     global_rows(n, m, Gi);
     const size_t G = (size_t)Gi, Pn = (size_t)P, cap = (size_t)capacity;
-    GlobalPopWorkspace w;
+    GlobalWorkspace w;
     size_t o = 0;
     w.choice = o; o += al(sizeof(int32_t) * (size_t)m * Pn);
     w.adv = o; o += al(sizeof(double) * cap * Pn);

@@ -1270,17 +1270,8 @@ class LmpcSolver(Solver):
         ``current_k`` are updated in place; ``train`` maps the names of LMPC_TRAIN_ARRAYS (adam, adam_step,
         train_log [iterations, 12], best_return, best_weights, best_iter, workspace of ``train_workspace_bytes``) to
         device pointers.  The logs have ``tcfg.steps`` rows and the records steps / record_every."""
-        plant = plant or plant_config()
-        buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
-                             + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
-                             + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
-                             + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
-                             + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
-        rc = lib().dart_lmpc_train_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
-                                       ctypes.byref(ppo_cfg), ctypes.byref(tcfg), int(B), int(reset_rows), buf,
-                                       stream or None)
-        if rc != 0:
-            self._err(rc, "dart_lmpc_train_dev")
+        _train_dev(self, "train_dev", (), (), B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state,
+                        cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant, stream)
 
     def train_global_dev(self, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state, cstate, logs,
                          clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, gbuf, pool=None, plant=None, stream=0):
@@ -1288,17 +1279,8 @@ class LmpcSolver(Solver):
         struct of device pointers (capacity >= G of ``global_rows``, ``fill`` the rows held now, ``global_log``
         [iterations, 6], ``workspace`` of ``global_workspace_bytes``), or None for ``train_dev`` itself.  The next
         call's fill is ``global_fill_after(n, gbuf.fill, tcfg.iterations)``."""
-        plant = plant or plant_config()
-        buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
-                             + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
-                             + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
-                             + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
-                             + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
-        rc = lib().dart_lmpc_train_global_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
-                                              ctypes.byref(ppo_cfg), ctypes.byref(tcfg), int(B), int(reset_rows), buf,
-                                              ctypes.byref(gbuf) if gbuf is not None else None, stream or None)
-        if rc != 0:
-            self._err(rc, "dart_lmpc_train_global_dev")
+        _train_dev(self, "train_global_dev", (), (gbuf,), B, reset_rows, target, prm, plant_pvec, current_k, weights,
+                        critic, state, cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant, stream)
 
     # -- a population of learners in one device-resident iteration (dart_lmpc_train_pop_dev / dart_lmpc_train_pop) ----
     def train_pop_dev(self, P, seeds, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state, cstate,
@@ -1310,20 +1292,8 @@ class LmpcSolver(Solver):
         best_return [P], best_weights [P, 77317], best_iter [P]; the workspace has ``train_pop_workspace_bytes``.
         ``seeds`` are P integers (``tcfg.seed`` is ignored); learner l is bit for bit ``train_dev`` on its arrays with
         seed ``seeds[l]``."""
-        plant = plant or plant_config()
-        seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(-1)
-        if seeds is not None and seeds.size != int(P):
-            raise DartMPCError(f"train_pop_dev needs {P} seeds, got {seeds.size}")
-        buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
-                             + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
-                             + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
-                             + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
-                             + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
-        rc = lib().dart_lmpc_train_pop_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
-                                           ctypes.byref(ppo_cfg), ctypes.byref(tcfg), int(P), _ptr(seeds), int(B),
-                                           int(reset_rows), buf, stream or None)
-        if rc != 0:
-            self._err(rc, "dart_lmpc_train_pop_dev")
+        _train_dev(self, "train_pop_dev", (P, seeds), (), B, reset_rows, target, prm, plant_pvec, current_k, weights,
+                        critic, state, cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant, stream)
 
     def train_pop_global_dev(self, P, seeds, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state,
                              cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, gbuf, pool=None, plant=None,
@@ -1333,21 +1303,46 @@ class LmpcSolver(Solver):
         [P, capacity, 520], ..., ``global_log`` [P, iterations, 6], ``workspace`` of ``global_pop_workspace_bytes``;
         ``fill`` is one number for all learners), or None for ``train_pop_dev`` itself.  Learner l is bit for bit
         ``train_global_dev`` on its arrays, its buffer and seed ``seeds[l]``."""
+        _train_dev(self, "train_pop_global_dev", (P, seeds), (gbuf,), B, reset_rows, target, prm, plant_pvec, current_k,
+                        weights, critic, state, cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant,
+                        stream)
+
+    def _train_host(self, entry, who, B, nl, nets, target, plant_pvec, state, cstate, logs, clogs, rec, pcfg, adam,
+                    adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg, prm, pool, plant,
+                    global_buffer, global_log):
+        """``train`` and ``train_pop``: ``nl`` learners of ``B`` instances each, their arrays stacked; ``nets`` are
+        the checked current_k, actor and critic arrays, ``who`` is () or (P, the seeds' pointer).  With
+        ``global_buffer`` the entry is ``entry`` + "_global"."""
+        NI, K = state["x"].shape[0], int(tcfg.steps)
+        rcfg = rcfg if rcfg is not None else reward_config()
+        R = K // max(int(rcfg.record_every), 1)
+        reset_rows = 0 if not pool else pool["reset_x"].shape[0]
+        prm = np.ascontiguousarray(np.tile(LMPC_PRM_DEFAULT, (NI, 1)) if prm is None else prm, np.float64).reshape(NI, 22)
         plant = plant or plant_config()
-        seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(-1)
-        if seeds is not None and seeds.size != int(P):
-            raise DartMPCError(f"train_pop_global_dev needs {P} seeds, got {seeds.size}")
-        buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
-                             + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
-                             + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
-                             + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
-                             + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
-        rc = lib().dart_lmpc_train_pop_global_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
-                                                  ctypes.byref(ppo_cfg), ctypes.byref(tcfg), int(P), _ptr(seeds),
-                                                  int(B), int(reset_rows), buf,
-                                                  ctypes.byref(gbuf) if gbuf is not None else None, stream or None)
+        head = [("target", 8, np.float64), ("plant_pvec", 34, np.float64)]
+        tg, pp = _host_ptrs(head, {"target": target, "plant_pvec": plant_pvec}, (NI,))
+        tail = [_inplace(adam, np.float32, nl * 2 * PPO_NPARAMS, "adam"), _inplace(adam_step, np.int32, nl, "adam_step"),
+                _inplace(train_log, np.float64, nl * TRAIN_LOG_COLS * int(tcfg.iterations), "train_log"),
+                _inplace(best_return, np.float64, nl, "best_return"),
+                _inplace(best_weights, np.float32, nl * PPO_NPARAMS, "best_weights"),
+                _inplace(best_iter, np.int32, nl, "best_iter")]
+        ptrs = ([tg, _ptr(prm), pp] + [_ptr(a) for a in nets]
+                + _host_ptrs(LMPC_LOOP_STATE, state, (NI,), nw=self.nw) + _host_ptrs(LMPC_COLLECT_STATE, cstate, (NI,))
+                + (_host_ptrs(LMPC_COLLECT_POOL, pool, (reset_rows, NI)) if reset_rows else [None] * 3)
+                + _host_ptrs(LMPC_LOOP_LOGS, logs, (K, NI)) + _host_ptrs(LMPC_COLLECT_LOGS, clogs, (K, NI))
+                + _host_ptrs(LMPC_COLLECT_REC, rec, (R, NI)) + [_ptr(a) for a in tail] + [None])
+        buf = _train_buffers([0 if q is None else q.value for q in ptrs])
+        g = []
+        if global_buffer is not None:
+            g = [_host_global(global_buffer, nl * int(tcfg.iterations), global_log, learners=nl)]
+            entry += "_global"
+        rc = getattr(lib(), entry)(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
+                                   ctypes.byref(ppo_cfg), ctypes.byref(tcfg), *who, B, reset_rows, buf,
+                                   *[ctypes.byref(q) for q in g], None)
         if rc != 0:
-            self._err(rc, "dart_lmpc_train_pop_global_dev")
+            self._err(rc, entry)
+        if g:
+            global_buffer["fill"] = global_fill_after(R * B, g[0].fill, int(tcfg.iterations))
 
     def train_pop(self, P, seeds, target, plant_pvec, state, cstate, logs, clogs, rec, pcfg, weights, critic, current_k,
                   adam, adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None,
@@ -1360,49 +1355,20 @@ class LmpcSolver(Solver):
         ``ppo.new_population_global_buffer`` dict: P stacked buffers and one ``fill``) every iteration also runs the
         global-buffer update (dart_lmpc_train_pop_global): the dict's arrays and ``fill`` are updated in place and
         ``global_log`` [P, iterations, 6] (float64) receives one row per learner and iteration."""
-        P, K = int(P), int(tcfg.steps)
-        NI = state["x"].shape[0]
+        P, NI = int(P), state["x"].shape[0]
         B = NI // max(P, 1)
         if P >= 1 and B * P != NI:
             raise DartMPCError(f"train_pop: {NI} instances are not {P} learners of equal size")
-        rcfg = rcfg if rcfg is not None else reward_config()
-        R = K // max(int(rcfg.record_every), 1)
-        reset_rows = 0 if not pool else pool["reset_x"].shape[0]
-        prm = np.ascontiguousarray(np.tile(LMPC_PRM_DEFAULT, (NI, 1)) if prm is None else prm, np.float64).reshape(NI, 22)
-        plant = plant or plant_config()
         seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(-1)
         if seeds is not None and seeds.size != P:
             raise DartMPCError(f"train_pop needs {P} seeds, got {seeds.size}")
         nl = max(P, 1)
-        head = [("target", 8, np.float64), ("plant_pvec", 34, np.float64)]
-        tg, pp = _host_ptrs(head, {"target": target, "plant_pvec": plant_pvec}, (NI,))
-        tail = [_inplace(adam, np.float32, nl * 2 * PPO_NPARAMS, "adam"), _inplace(adam_step, np.int32, nl, "adam_step"),
-                _inplace(train_log, np.float64, nl * TRAIN_LOG_COLS * int(tcfg.iterations), "train_log"),
-                _inplace(best_return, np.float64, nl, "best_return"),
-                _inplace(best_weights, np.float32, nl * PPO_NPARAMS, "best_weights"),
-                _inplace(best_iter, np.int32, nl, "best_iter")]
-        ptrs = ([tg, _ptr(prm), pp, _ptr(_inplace(current_k, np.float64, 34 * NI, "current_k")),
-                 _ptr(_inplace(weights, np.float32, nl * ACTOR_NWEIGHTS, "weights")),
-                 _ptr(_inplace(critic, np.float32, nl * POP_CRITIC_STRIDE, "critic"))]
-                + _host_ptrs(LMPC_LOOP_STATE, state, (NI,), nw=self.nw) + _host_ptrs(LMPC_COLLECT_STATE, cstate, (NI,))
-                + (_host_ptrs(LMPC_COLLECT_POOL, pool, (reset_rows, NI)) if reset_rows else [None] * 3)
-                + _host_ptrs(LMPC_LOOP_LOGS, logs, (K, NI)) + _host_ptrs(LMPC_COLLECT_LOGS, clogs, (K, NI))
-                + _host_ptrs(LMPC_COLLECT_REC, rec, (R, NI)) + [_ptr(a) for a in tail] + [None])
-        buf = _train_buffers([0 if q is None else q.value for q in ptrs])
-        if global_buffer is not None:
-            g = _host_global(global_buffer, nl * int(tcfg.iterations), global_log, learners=nl)
-            rc = lib().dart_lmpc_train_pop_global(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
-                                                  ctypes.byref(ppo_cfg), ctypes.byref(tcfg), P, _ptr(seeds), B,
-                                                  reset_rows, buf, ctypes.byref(g), None)
-            if rc != 0:
-                self._err(rc, "dart_lmpc_train_pop_global")
-            global_buffer["fill"] = global_fill_after(R * B, g.fill, int(tcfg.iterations))
-            return
-        rc = lib().dart_lmpc_train_pop(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
-                                       ctypes.byref(ppo_cfg), ctypes.byref(tcfg), P, _ptr(seeds), B, reset_rows, buf,
-                                       None)
-        if rc != 0:
-            self._err(rc, "dart_lmpc_train_pop")
+        nets = (_inplace(current_k, np.float64, 34 * NI, "current_k"),
+                _inplace(weights, np.float32, nl * ACTOR_NWEIGHTS, "weights"),
+                _inplace(critic, np.float32, nl * POP_CRITIC_STRIDE, "critic"))
+        self._train_host("dart_lmpc_train_pop", (P, _ptr(seeds)), B, nl, nets, target, plant_pvec, state, cstate, logs,
+                         clogs, rec, pcfg, adam, adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg,
+                         tcfg, rcfg, prm, pool, plant, global_buffer, global_log)
 
     def train(self, target, plant_pvec, state, cstate, logs, clogs, rec, policy, adam, adam_step, train_log,
               best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None, pool=None, plant=None,
@@ -1416,43 +1382,15 @@ class LmpcSolver(Solver):
         ``global_buffer`` (a ``ppo.new_global_buffer`` dict) every iteration also runs the global-buffer update
         (dart_lmpc_train_global): the dict's arrays and ``fill`` are updated in place and ``global_log``
         [iterations, 6] (float64) receives one row per iteration."""
-        B, K = state["x"].shape[0], int(tcfg.steps)
-        rcfg = rcfg if rcfg is not None else reward_config()
-        R = K // max(int(rcfg.record_every), 1)
-        reset_rows = 0 if not pool else pool["reset_x"].shape[0]
-        prm = np.ascontiguousarray(np.tile(LMPC_PRM_DEFAULT, (B, 1)) if prm is None else prm, np.float64).reshape(B, 22)
-        plant = plant or plant_config()
+        B = state["x"].shape[0]
         if policy.critic_weights is None:
             raise DartMPCError("training needs a policy with critic_weights")
         policy.current_k = _inplace(policy.current_k, np.float64, 34 * B, "policy.current_k")
-        head = [("target", 8, np.float64), ("plant_pvec", 34, np.float64)]
-        tg, pp = _host_ptrs(head, {"target": target, "plant_pvec": plant_pvec}, (B,))
-        tail = [_inplace(adam, np.float32, 2 * PPO_NPARAMS, "adam"), _inplace(adam_step, np.int32, 1, "adam_step"),
-                _inplace(train_log, np.float64, TRAIN_LOG_COLS * int(tcfg.iterations), "train_log"),
-                _inplace(best_return, np.float64, 1, "best_return"),
-                _inplace(best_weights, np.float32, PPO_NPARAMS, "best_weights"),
-                _inplace(best_iter, np.int32, 1, "best_iter")]
-        ptrs = ([tg, _ptr(prm), pp, _ptr(policy.current_k),
-                 _ptr(_inplace(policy.weights, np.float32, ACTOR_NWEIGHTS, "policy.weights")),
-                 _ptr(_inplace(policy.critic_weights, np.float32, CRITIC_NWEIGHTS, "policy.critic_weights"))]
-                + _host_ptrs(LMPC_LOOP_STATE, state, (B,), nw=self.nw) + _host_ptrs(LMPC_COLLECT_STATE, cstate, (B,))
-                + (_host_ptrs(LMPC_COLLECT_POOL, pool, (reset_rows, B)) if reset_rows else [None] * 3)
-                + _host_ptrs(LMPC_LOOP_LOGS, logs, (K, B)) + _host_ptrs(LMPC_COLLECT_LOGS, clogs, (K, B))
-                + _host_ptrs(LMPC_COLLECT_REC, rec, (R, B)) + [_ptr(a) for a in tail] + [None])
-        buf = _train_buffers([0 if q is None else q.value for q in ptrs])
-        if global_buffer is not None:
-            g = _host_global(global_buffer, int(tcfg.iterations), global_log)
-            rc = lib().dart_lmpc_train_global(self._h, ctypes.byref(plant), ctypes.byref(policy.cfg),
-                                              ctypes.byref(rcfg), ctypes.byref(ppo_cfg), ctypes.byref(tcfg), B,
-                                              reset_rows, buf, ctypes.byref(g), None)
-            if rc != 0:
-                self._err(rc, "dart_lmpc_train_global")
-            global_buffer["fill"] = global_fill_after(R * B, g.fill, int(tcfg.iterations))
-            return
-        rc = lib().dart_lmpc_train(self._h, ctypes.byref(plant), ctypes.byref(policy.cfg), ctypes.byref(rcfg),
-                                   ctypes.byref(ppo_cfg), ctypes.byref(tcfg), B, reset_rows, buf, None)
-        if rc != 0:
-            self._err(rc, "dart_lmpc_train")
+        nets = (policy.current_k, _inplace(policy.weights, np.float32, ACTOR_NWEIGHTS, "policy.weights"),
+                _inplace(policy.critic_weights, np.float32, CRITIC_NWEIGHTS, "policy.critic_weights"))
+        self._train_host("dart_lmpc_train", (), B, 1, nets, target, plant_pvec, state, cstate, logs, clogs, rec,
+                         policy.cfg, adam, adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg, tcfg,
+                         rcfg, prm, pool, plant, global_buffer, global_log)
 
     @staticmethod
     def collect_state(u_prev):
@@ -1673,6 +1611,31 @@ def _train_buffers(values):
     if len(values) != _TRAIN_NPTR:
         raise DartMPCError(f"dart_lmpc_train_buffers has {_TRAIN_NPTR} pointers, got {len(values)}")
     return (ctypes.c_void_p * _TRAIN_NPTR)(*[int(v) if v else None for v in values])
+
+
+def _train_dev(solver, entry, who, gbuf, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state,
+               cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant, stream):
+    """The four device training entries of ``LmpcSolver``: ``entry`` names the C function, ``who`` is () or (P, seeds)
+    and ``gbuf`` () or (the ``global_buffer`` struct or None,), each passed where the entry takes it.  (``solver`` is
+    any handle's wrapper: the library refuses one that is not an LMPC handle.)"""
+    if who:
+        P, seeds = who
+        seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(-1)
+        if seeds is not None and seeds.size != int(P):
+            raise DartMPCError(f"{entry} needs {P} seeds, got {seeds.size}")
+        who = (int(P), _ptr(seeds))
+    plant = plant or plant_config()
+    buf = _train_buffers([target, prm, plant_pvec, current_k, weights, critic]
+                         + [state[n] for n, _, _ in LMPC_LOOP_STATE] + [cstate[n] for n, _, _ in LMPC_COLLECT_STATE]
+                         + [(pool or {}).get(n, 0) for n, _, _ in LMPC_COLLECT_POOL]
+                         + [logs[n] for n, _, _ in LMPC_LOOP_LOGS] + [clogs[n] for n, _, _ in LMPC_COLLECT_LOGS]
+                         + [rec[n] for n, _, _ in LMPC_COLLECT_REC] + [train[n] for n in LMPC_TRAIN_ARRAYS])
+    rc = getattr(lib(), "dart_lmpc_" + entry)(
+        solver._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg), ctypes.byref(ppo_cfg),
+        ctypes.byref(tcfg), *who, int(B), int(reset_rows), buf,
+        *[ctypes.byref(g) if g is not None else None for g in gbuf], stream or None)
+    if rc != 0:
+        solver._err(rc, "dart_lmpc_" + entry)
 
 
 def train_config(**over) -> TrainConfig:

@@ -394,12 +394,15 @@ def test_population_refusals(L, torch):
         M = _members(L, s)
         pcfg = M[0]["pcfg"]
         r = _Run(L, torch, ppo.population_stack(M), C, 1, P)
+        r.tr["workspace"].fill_(0xA5)
+        r.cs["nrec"].fill_(-3)
         torch.cuda.synchronize()
         before = r.member_snapshot(1)
         many = tuple(range(L.POP_MAX + 1))
         cases = [("P = 0", s, dict(P_=0, seeds=())), ("P = POP_MAX + 1", s, dict(P_=L.POP_MAX + 1, seeds=many, B_=1)),
                  ("P B = B_max + 1", small, dict(seeds=SEEDS)), ("null seeds", s, dict(seeds=None)),
                  ("critic off by 4 bytes", s, dict(seeds=SEEDS, over=dict(critic=r.c["critic"].data_ptr() + 4))),
+                 ("weights off by 4 bytes", s, dict(seeds=SEEDS, over=dict(weights=r.c["weights"].data_ptr() + 4))),
                  ("K = 25", s, dict(seeds=SEEDS, steps=25)), ("an RMPC handle", rm, dict(seeds=SEEDS))]
         for what, solver, kw in cases:
             seeds = kw.pop("seeds")
@@ -407,7 +410,17 @@ def test_population_refusals(L, torch):
                 r.train(L, solver, C, pcfg, stream, 1, seeds, **kw)
             torch.cuda.synchronize()
             _assert_same(before, r.member_snapshot(1), what)
+            assert bool((r.tr["workspace"] == 0xA5).all()), what     # nothing was launched
             print("refused:", what)
+        # the same two pointers through the entry with the global buffer (here without one)
+        for name in ("weights", "critic"):
+            tcfg = L.train_config(iterations=1, steps=C["K"])
+            a = r.args(C, pcfg, tcfg, {name: r.c[name].data_ptr() + 4})
+            with pytest.raises(L.DartMPCError, match=r"\(-1\)"):
+                s.train_pop_global_dev(P, SEEDS, B, 2, gbuf=None, stream=stream, **a)
+            torch.cuda.synchronize()
+            _assert_same(before, r.member_snapshot(1), name)
+            assert bool((r.tr["workspace"] == 0xA5).all()), name
         assert L.train_pop_workspace_bytes(P, B, 25, EVERY, EPOCHS, MB) == 0
         # the host entry: one instance's timestep advanced
         ts = np.zeros(P * B, np.int32)

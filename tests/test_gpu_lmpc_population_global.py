@@ -450,6 +450,9 @@ def test_population_global_refusals(L, torch):
         M = TP._members(L, s)
         pcfg = M[0]["pcfg"]
         r = _GRun(L, torch, ppo.population_stack(M), C, 1, P)
+        r.tr["workspace"].fill_(0xA5)
+        r.gws.fill_(0xA5)
+        r.cs["nrec"].fill_(-3)
         torch.cuda.synchronize()
         before = r.member_snapshot(1, rows=r.cap)
         many = tuple(range(L.POP_MAX + 1))
@@ -458,6 +461,8 @@ def test_population_global_refusals(L, torch):
                  ("capacity = G - 1", s, dict(cap=G - 1)), ("a null reward", s, dict(gover=dict(reward=0))),
                  ("obs off by 4 bytes", s, dict(gover=dict(obs=r.gb["obs"].data_ptr() + 4))),
                  ("rec_obs off by 4 bytes", s, dict(over=dict(rec=rec_odd))),
+                 ("weights off by 4 bytes", s, dict(over=dict(weights=r.c["weights"].data_ptr() + 4))),
+                 ("critic off by 4 bytes", s, dict(over=dict(critic=r.c["critic"].data_ptr() + 4))),
                  ("P = POP_MAX + 1", s, dict(P_=L.POP_MAX + 1, seeds=many, B_=1)),
                  ("P B = B_max + 1", small, dict())]
         for what, solver, kw in cases:
@@ -468,9 +473,80 @@ def test_population_global_refusals(L, torch):
             torch.cuda.synchronize()
             r.fill = 0
             _assert_same(before, r.member_snapshot(1, rows=r.cap), what)
+            assert bool((r.tr["workspace"] == 0xA5).all()) and bool((r.gws == 0xA5).all()), what   # nothing launched
             print("refused:", what)
         assert L.global_pop_workspace_bytes(0, n, G, EPOCHS, MB) == 0
         assert L.global_pop_workspace_bytes(P, n, G, EPOCHS, MB) > 0
     finally:
         s.close()
         small.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Test 10: the switches of the iteration (no other training test sets them), each alone and all three together
+SWITCHES = {"epochs = 0": dict(epochs=0), "mean_update = 0": dict(mean_update=0), "track_best = 0": dict(track_best=0),
+            "all three": dict(epochs=0, mean_update=0, track_best=0)}
+
+
+@pytest.mark.parametrize("with_global", [True, False])
+@pytest.mark.parametrize("what", list(SWITCHES))
+def test_switches_population_equals_single_runs(L, torch, what, with_global):
+    """K = 8: n = 20 (one full and one ragged mini-batch of 16), m = 5, G = 20, period 4; period + 1 iterations, so
+    that the update on the buffers runs once.  Learner l of train_pop_global_dev is train_global_dev on its member bit
+    for bit, and each switch does what it says."""
+    from dart_mpc import ppo
+    sw = dict(epochs=EPOCHS, mean_update=1, track_best=1) | SWITCHES[what]
+    K = 8
+    C = TP._cfgs(L, K)
+    n, m, G, period = _period(L, K)
+    assert (n, m, G, period) == (20, 5, 20, 4)
+    its = period + 1
+    over = lambda seed: dict(ppo_cfg=L.ppo_config(epochs=sw["epochs"], mini_batch_size=MB, **HYPER),
+                             tcfg=L.train_config(seed=seed, iterations=its, steps=K, mean_update=sw["mean_update"],
+                                                 track_best=sw["track_best"]))
+    s = L.LmpcSolver(N=NH, Ts=0.002, B_max=P * B)
+    stream = torch.cuda.current_stream().cuda_stream
+    try:
+        init = TP._members(L, s)
+        single = []
+        for l, mem in enumerate(TP._members(L, s)):
+            r = _GRun(L, torch, ppo.population_stack([mem]) | dict(critic=mem["critic"], weights=mem["weights"]), C, its, 0)
+            torch.cuda.synchronize()
+            r.train(L, s, C, mem["pcfg"], stream, its, (SEEDS[l],), use_global=with_global, over=over(SEEDS[l]))
+            single.append(r.member_snapshot(0, rows=None if with_global else r.cap))
+        r = _GRun(L, torch, ppo.population_stack(TP._members(L, s)), C, its, P, pad=PAD)
+        torch.cuda.synchronize()
+        r.train(L, s, C, init[0]["pcfg"], stream, its, SEEDS, use_global=with_global, over=over(0))
+        pop = [r.member_snapshot(l, rows=None if with_global else r.cap) for l in range(P)]
+        assert (r.pads() == PAD).all()
+    finally:
+        s.close()
+    steps = sw["epochs"] * -(-n // MB) * its + (sw["epochs"] * -(-G // MB) if with_global else 0)
+    for l in range(P):
+        b, start = pop[l], init[l]
+        _assert_same(single[l], b, f"{what}: learner {l} alone against learner {l} of the population")
+        log = b["tr.train_log"]
+        print(f"{what}, buffer {with_global}, learner {l}: train_log {np.array2string(log, precision=4)}")
+        assert log[:, 0].tolist() == [n] * its and b["tr.adam_step"].tolist() == [steps]
+        nets_kept = _same(b["c.weights"], start["weights"]) and _same(b["c.critic"], start["critic"])
+        if sw["epochs"] == 0:
+            assert (log[:, 6:9] == 0).all() and nets_kept
+        else:
+            assert np.isfinite(log[:, 6:9]).all() and (log[:, 6:9] != 0).any() and not nets_kept
+        if sw["mean_update"] == 0:
+            # nothing but the parameter write sets current_k; model_params stays what the last step's policy left
+            assert _same(b["c.current_k"], start["current_k"]) and _same(b["st.model_params"], b["lg.pvec"][-1])
+        else:
+            assert _same(b["c.current_k"], b["st.model_params"]) and not _same(b["c.current_k"], start["current_k"])
+        if sw["track_best"] == 0:
+            assert b["tr.best_return"].tolist() == [-np.inf] and b["tr.best_iter"].tolist() == [-1]
+            assert not b["tr.best_weights"].any() and (log[:, 11] == 0).all()
+        else:
+            assert log[:, 11].sum() >= 1 and b["tr.best_iter"][0] >= 0 and b["tr.best_weights"].any()
+        if with_global:
+            glog = b["glog"]
+            assert glog[:, 1].tolist() == [0.0] * (period - 1) + [1.0, 0.0] and b["gb.fill"].tolist() == [m]
+            if sw["epochs"] == 0:
+                assert (glog[period - 1, 3:] == 0).all()
+        else:
+            assert all(_is_pattern(b["gb." + f]) for f in FIELDS) and np.isnan(b["glog"]).all()

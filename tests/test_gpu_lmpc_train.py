@@ -470,5 +470,33 @@ def test_train_entry_rejects_bad_shapes(L, torch):
             _host_run(L, s, I, 1, timestep=np.array([0, 0, 1, 0, 0]))
         torch.cuda.synchronize()
         assert r.tr["adam_step"].cpu().tolist() == [0]                                  # nothing ran
+        # weights or critic off by 4 bytes: refused with every other check, before the first launch (not by the
+        # update, behind iteration 0's noise and collection): the state arrays, nrec and the workspaces keep
+        # what they held, with and without a global buffer
+        stream = torch.cuda.current_stream().cuda_stream
+        m, G = L.global_rows(r.n)
+        gb = {f: torch.zeros((G, w) if w else (G,), dtype=getattr(torch, np.dtype(dt).name), device="cuda")
+              for f, w, dt in L.LMPC_GLOBAL_ARRAYS}
+        glog = torch.full((1, 6), float("nan"), dtype=torch.float64, device="cuda")
+        gws = torch.full((L.global_workspace_bytes(r.n, EPOCHS, MB),), 0xA5, dtype=torch.uint8, device="cuda")
+        g = L.global_buffer(_ptrs(gb), G, 0, global_log=glog.data_ptr(), workspace=gws.data_ptr())
+        r.tr["workspace"].fill_(0xA5)
+        r.cs["nrec"].fill_(-3)
+        torch.cuda.synchronize()
+        before = r.snapshot()
+        tcfg = L.train_config(seed=SEED, iterations=1, steps=I["K"])
+        for name in ("weights", "critic"):
+            c = {k: v.data_ptr() + (4 if k == name else 0) for k, v in r.c.items()}
+            args = (B, 2, c["target"], c["prm"], c["pvec"], c["current_k"], c["weights"], c["critic"], _ptrs(r.st),
+                    _ptrs(r.cs), _ptrs(r.lg), _ptrs(r.clg), _ptrs(r.rec), _ptrs(r.tr), I["policy"].cfg, I["rcfg"],
+                    I["cfg"], tcfg)
+            for entry, extra in ((s.train_dev, ()), (s.train_global_dev, (g,))):
+                with pytest.raises(L.DartMPCError, match=r"\(-1\)"):
+                    entry(*args, *extra, pool=_ptrs(r.pool), stream=stream)
+                torch.cuda.synchronize()
+                after = r.snapshot()
+                assert [k for k in before if not _same(before[k], after[k])] == [], (name, len(extra))
+                assert bool((r.tr["workspace"] == 0xA5).all()) and bool((gws == 0xA5).all()), (name, len(extra))
+                assert all(bool((v == 0).all()) for v in gb.values()) and bool(glog.isnan().all())
     finally:
         s.close()

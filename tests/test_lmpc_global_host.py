@@ -91,6 +91,22 @@ def test_global_rows_and_fill_arithmetic():
     assert ctypes.sizeof(_lib.train_config()) == 48 and _lib.TRAIN_LOG_COLS == 12      # ABI 8 as it was
 
 
+def test_population_of_one_has_the_single_global_workspace():
+    """The single global update's workspace is the population's layout with one learner and capacity G, block for
+    block: the byte counts agree on the grid of tests/test_lmpc_population_host.py (n = K / record_every B)."""
+    import itertools
+    from dart_mpc import _lib
+    from test_lmpc_population_host import GRID
+    for b, k, every, epochs, mb in itertools.product(*(GRID[q] for q in ("B", "K", "every", "epochs", "mb"))):
+        n = k // every * b
+        G = _lib.global_rows(n)[1]
+        one = _lib.global_workspace_bytes(n, epochs, mb)
+        sizes = [_lib.global_pop_workspace_bytes(p, n, G, epochs, mb) for p in GRID["P"]]
+        assert one > 0 and sizes[0] == one, (n, G, epochs, mb)
+        assert sizes == sorted(set(sizes)) and all(q % 256 == 0 for q in sizes), (n, G, epochs, mb)
+        assert _lib.global_pop_workspace_bytes(1, n, G + 3, epochs, mb) >= one       # spare capacity never needs less
+
+
 def test_global_entries_validate_before_any_device_work():
     from dart_mpc import _lib
     L = _lib.lib()

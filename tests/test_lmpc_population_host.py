@@ -38,6 +38,21 @@ def test_workspace_bytes(L):
     assert sizes == sorted(sizes) and len(set(sizes)) == len(sizes)
 
 
+# the shapes on which the layouts are compared: one instance, the tests', the benchmark's; one record row; epochs = 0
+GRID = dict(B=(1, 5, 18, 72), K=(2, 24, 36, 256), every=(1, 2), epochs=(0, 1, 8), mb=(1, 16, 64), P=(1, 2, 3, 8))
+
+
+def test_population_of_one_has_the_single_workspace(L):
+    """The single iteration's workspace is the population's layout with one learner, block for block: the byte counts
+    agree on the whole grid."""
+    import itertools
+    for b, k, every, epochs, mb in itertools.product(*(GRID[q] for q in ("B", "K", "every", "epochs", "mb"))):
+        one = L.train_workspace_bytes(b, k, every, epochs, mb)
+        sizes = [L.train_pop_workspace_bytes(p, b, k, every, epochs, mb) for p in GRID["P"]]
+        assert one > 0 and sizes[0] == one, (b, k, every, epochs, mb)
+        assert sizes == sorted(set(sizes)) and all(q % 256 == 0 for q in sizes), (b, k, every, epochs, mb)
+
+
 def _random_member(L, rng, nw=17):
     f32 = lambda *s: rng.standard_normal(s).astype(np.float32)
     f64 = lambda *s: rng.standard_normal(s)

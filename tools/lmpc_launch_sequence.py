@@ -2,7 +2,9 @@
 
 `run` makes, with the restoration phases on and then off, one rollout_dev, one collect_dev and one train_global_dev
 call of two iterations at B = 2, N = 4, steps = 4 (record_every = 2, a reset pool of one row; the global buffer
-starts one draw short of full, so the first iteration runs the global update), all on the handle's stream.  Under a kernel trace (run alone, the program after `--`):
+starts one draw short of full, so the first iteration runs the global update), all on the handle's stream; then, on
+a second handle, one train_pop_global_dev call of the same shape for P = 2 learners (their buffers one draw short of
+full as well).  Under a kernel trace (run alone, the program after `--`):
 
     rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/lmpc_launch_sequence.py run
     python tools/lmpc_launch_sequence.py list <dir> profiles/abi_split/launch_sequence_<build>.txt
@@ -19,13 +21,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dart-dual-arm-non-prehensile-manipulation_amd"))
 
-B, N, STEPS, EVERY, EPOCHS, MB, ITERATIONS = 2, 4, 4, 2, 1, 4, 2
+B, N, STEPS, EVERY, EPOCHS, MB, ITERATIONS, P = 2, 4, 4, 2, 1, 4, 2, 2
 
 
 def run():
     import numpy as np
     import torch
-    from dart_mpc import _lib
+    from dart_mpc import _lib, ppo
     from dart_mpc.lmpc import LmpcPolicy
     from dart_mpc.workload import lmpc_batch
 
@@ -74,6 +76,40 @@ def run():
         torch.cuda.synchronize()
         print(f"restoration {int(restoration)}: library {_lib.LIB_NAME}, train_log n = "
               f"{tr['train_log'].cpu().numpy()[:, 0].tolist()}, global fill = {glog.cpu().numpy()[:, 0].tolist()}",
+              flush=True)
+        s.close()
+        # the population's form of the same call: P learners of B instances, stacked learner-major
+        NI = P * B
+        s = _lib.LmpcSolver(N=N, B_max=NI, restoration=restoration)
+        pol = LmpcPolicy(NI, seed=0, critic_weights=pol.critic_weights)
+        c = up(dict(target=D["target"][:NI], prm=np.tile(_lib.LMPC_PRM_DEFAULT, (NI, 1)), pvec=D["pvec"][:NI],
+                    current_k=pol.current_k, weights=np.stack([pol.weights] * P),
+                    critic=ppo.stack_critics([pol.critic_weights] * P)))
+        st = up(s.loop_state(D["state"][:NI], policy=pol))
+        cs = up(s.collect_state(np.zeros((NI, 2))))
+        pool = up({"reset_x": D["state"][None, NI:2 * NI], "reset_target": D["target"][None, NI:2 * NI],
+                   "reset_pvec": D["pvec"][None, NI:2 * NI]})
+        lg, clg = up(_lib.loop_logs(_lib.LMPC_LOOP_LOGS, STEPS, NI)), up(_lib.loop_logs(_lib.LMPC_COLLECT_LOGS, STEPS, NI))
+        rec = up(_lib.loop_logs(_lib.LMPC_COLLECT_REC, R, NI))
+        tr = up(dict(adam=np.zeros((P, 2, _lib.PPO_NPARAMS), np.float32), adam_step=np.zeros(P, np.int32),
+                     train_log=np.zeros((P, ITERATIONS, _lib.TRAIN_LOG_COLS)), best_return=np.full(P, -np.inf),
+                     best_weights=np.zeros((P, _lib.PPO_NPARAMS), np.float32), best_iter=np.zeros(P, np.int32)))
+        tr["workspace"] = torch.zeros(_lib.train_pop_workspace_bytes(P, B, STEPS, EVERY, EPOCHS, MB), dtype=torch.uint8,
+                                      device="cuda")
+        gb = {f: torch.zeros((P, G, w) if w else (P, G), dtype=getattr(torch, np.dtype(dt).name), device="cuda")
+              for f, w, dt in _lib.LMPC_GLOBAL_ARRAYS}
+        glog = torch.zeros(P, ITERATIONS, _lib.GLOBAL_LOG_COLS, dtype=torch.float64, device="cuda")
+        gws = torch.zeros(_lib.global_pop_workspace_bytes(P, n, G, EPOCHS, MB), dtype=torch.uint8, device="cuda")
+        g = _lib.global_buffer(ptr(gb), G, n - m, global_log=glog.data_ptr(), workspace=gws.data_ptr())
+        torch.cuda.synchronize()
+        s.train_pop_global_dev(P, [5, 6], B, 1, c["target"].data_ptr(), c["prm"].data_ptr(), c["pvec"].data_ptr(),
+                               c["current_k"].data_ptr(), c["weights"].data_ptr(), c["critic"].data_ptr(), ptr(st),
+                               ptr(cs), ptr(lg), ptr(clg), ptr(rec), ptr(tr), pol.cfg, rcfg,
+                               _lib.ppo_config(epochs=EPOCHS, mini_batch_size=MB), tcfg, g, pool=ptr(pool))
+        s.sync()
+        torch.cuda.synchronize()
+        print(f"restoration {int(restoration)}: population of {P}, train_log n = "
+              f"{tr['train_log'].cpu().numpy()[:, :, 0].tolist()}, global fill = {glog.cpu().numpy()[:, :, 0].tolist()}",
               flush=True)
         s.close()
 

@@ -32,6 +32,7 @@ Usage: python tools/train_rate.py [out.json] [rounds]
        python tools/train_rate.py --once-pop P B K [iterations]   (population iterations and nothing else)
        python tools/train_rate.py --ab-global B K out.npz [periods]   (resident_dev_global alone, per iteration)
        python tools/train_rate.py --ab-pop P B K out.npz [iterations]   (train_pop_dev alone, per iteration)
+       python tools/train_rate.py --ab-pop-global P B K out.npz [periods]   (train_pop_global_dev alone, per iteration)
        python tools/train_rate.py --ab B K out.npz [iterations]   (resident_dev alone, one time per iteration, and its
                                                                     results for a bit-for-bit check of two builds)
        python tools/train_rate.py --once B K [iterations]   (resident iterations and nothing else: for a kernel trace)
@@ -462,6 +463,23 @@ def main():
             run.close()
         print(f"{_lib.LIB_NAME} population P = {P}, B = {B}, K = {K}: median {np.median(t):.2f} ms "
               f"({min(t):.2f}-{max(t):.2f}) over {iters} iterations", flush=True)
+        return
+    if argv and argv[0] == "--ab-pop-global":
+        P, B, K, periods = int(argv[1]), int(argv[2]), int(argv[3]), int(argv[5]) if len(argv) > 5 else 3
+        run = PopRun(P, B, K, with_global=True)
+        try:
+            run.population_global()                 # warm-up
+            t = [timed(run.population_global) / run.period for _ in range(periods)]
+            d = run.dev
+            np.savez(argv[4], weights=d["c"]["weights"].cpu().numpy(), critic=d["c"]["critic"].cpu().numpy(),
+                     current_k=d["c"]["current_k"].cpu().numpy(), adam=d["tr"]["adam"].cpu().numpy(),
+                     reward=d["clg"]["reward"].cpu().numpy(), x=d["st"]["x"].cpu().numpy(),
+                     best_return=d["tr"]["best_return"].cpu().numpy(), glog=run.glog.cpu().numpy(),
+                     g_obs=d["gb"]["obs"].cpu().numpy())
+        finally:
+            run.close()
+        print(f"{_lib.LIB_NAME} population_global P = {P}, B = {B}, K = {K}: median {np.median(t):.2f} ms per iteration "
+              f"({min(t):.2f}-{max(t):.2f}) over {periods} fill periods of {run.period} iterations", flush=True)
         return
     if argv and argv[0] == "--once":
         B, K = int(argv[1]), int(argv[2])
