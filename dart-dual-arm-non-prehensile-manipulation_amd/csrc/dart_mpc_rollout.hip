@@ -22,29 +22,14 @@ dartmpc::PlantArgs plant_args(const dart_mpc_handle* h, const dart_plant_config*
     return a;
 }
 
-// the checks every rollout / loop-step entry shares: the call writes the log rows k .. k + steps - 1
-int loop_check(dart_mpc_handle* h, int variant, const dart_plant_config* plant, int B, int k, int steps, int log_rows) {
-    if (h->cfg.variant != variant) return fail(h, DART_MPC_EINVAL, variant_text(variant));
+// the checks every LMPC rollout / loop-step entry shares: the call writes the log rows k .. k + steps - 1.  (The
+// LMPC plant does not use mu_c / v_c.)
+int loop_check(dart_mpc_handle* h, const dart_plant_config* plant, int B, int k, int steps, int log_rows) {
+    if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, variant_text(DART_MPC_LMPC));
     if (!plant) return fail(h, DART_MPC_EINVAL, "null plant config");
-    // (the LMPC plant does not use mu_c / v_c)
-    if (variant != DART_MPC_LMPC && (!(plant->v_c > 0.0) || !(plant->mu_c >= 0.0)))
-        return fail(h, DART_MPC_EINVAL, "plant config: v_c > 0, mu_c >= 0");
     if (B < 0 || k < 0 || steps < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
     if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
     if ((long long)k + steps > log_rows) return fail(h, DART_MPC_EINVAL, "k0 + steps exceeds log_rows");
-    return DART_MPC_OK;
-}
-
-// loop_check, RMPC's loop config, then the entry's pointers: what a PMPC / RMPC entry and its host twin both check
-int loop_entry_check(dart_mpc_handle* h, int variant, const dart_plant_config* plant, const dart_rmpc_loop_config* c,
-                     int B, int k, int steps, int log_rows, std::initializer_list<const void*> ptrs) {
-    if (int rc = loop_check(h, variant, plant, B, k, steps, log_rows)) return rc;
-    if (variant == DART_MPC_RMPC) {
-        if (!c) return fail(h, DART_MPC_EINVAL, "null loop config");
-        if (!(c->rls_lambda > 0.0) || !(c->dr_max >= 0.0) || !(c->step_fraction >= 0.0 && c->step_fraction <= 1.0))
-            return fail(h, DART_MPC_EINVAL, "loop config: rls_lambda > 0, dr_max >= 0, 0 <= step_fraction <= 1");
-    }
-    if (any_null(ptrs)) return fail(h, DART_MPC_EINVAL, "null pointer");
     return DART_MPC_OK;
 }
 
@@ -70,13 +55,17 @@ int scratch_blocks(dart_mpc_handle* h, int n, const size_t* cnt, int zero_from, 
     return DART_MPC_OK;
 }
 
-// the solve's per-step arrays of a PMPC / RMPC rollout
-struct LoopScratch {
+// (the entries never write through what they take const: the views' members are not const)
+template <class T> T* mut(const T* p) { return const_cast<T*>(p); }
+
+// the solve's per-step arrays of a PMPC / RMPC loop step: pre writes x0 (RMPC: and Rref, phi, y), post reads the rest
+struct LoopIo {
     double *x0, *Rref, *phi, *y, *u0, *f;
     int32_t *status, *iters;
 };
 
-int loop_scratch(dart_mpc_handle* h, LoopScratch& L) {
+// a rollout's own, in the handle's scratch
+int loop_scratch(dart_mpc_handle* h, LoopIo& L) {
     const size_t N1 = (size_t)h->cfg.N + 1;
     const bool rm = h->cfg.variant == DART_MPC_RMPC;
     const size_t r = rm ? 1 : 0;         // (Rref, phi and y are RMPC's)
@@ -87,6 +76,258 @@ int loop_scratch(dart_mpc_handle* h, LoopScratch& L) {
     L.x0 = (double*)p[0]; L.Rref = (double*)p[1]; L.phi = (double*)p[2]; L.y = (double*)p[3];
     L.u0 = (double*)p[4]; L.f = (double*)p[5]; L.status = (int32_t*)p[6]; L.iters = (int32_t*)p[7];
     return DART_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// PMPC and RMPC closed loops (pmpc_loop_kernel / rmpc_loop_kernel between the unchanged solves), on the tray plant
+// (dart_pmpc_* / dart_rmpc_*) and on the LMPC plant with streaming metrics (dart_pmpc_lm_* / dart_rmpc_lm_*).  The
+// entries build one LoopBuf from their positional arguments; everything below the entries takes that.  One table,
+// kLoopArr, describes each array once.
+struct LoopBuf {
+    const double *target, *prm, *mu, *plant_pvec, *pz_vz;
+    double *x, *tilt, *prev, *u_prev, *r_v, *theta, *P, *w;
+    int32_t *done, *nlog;
+    double* metrics;
+    double *log_pos_err, *log_pos_err_norm, *log_u_cmd, *log_timestep;     // RMPC's episode rows
+    double *log_x, *log_theta, *log_r_v, *log_f;                          // RMPC's step rows
+    double *log_X, *log_U, *log_quat, *log_loss;                          // PMPC's step rows
+    int32_t *log_status, *log_iters;
+    double* log_rot;
+};
+
+enum LoopKind : uint8_t {
+    cUp,        // [B][width], up only
+    cBoth,      // [B][width], both ways
+    cEpisode,   // [log_rows][B][width], RMPC's episode rows: the rows the call can write travel both ways
+    cStep       // [log_rows][B][width], the call's step rows come down
+};
+// A loop is one bit, 1 << (2 lm + rm); the masks of a controller's and of a plant's loops, so that kPm & kTray is
+// PMPC on the tray plant
+constexpr uint8_t kPm = 0x5, kRm = 0xA, kTray = 0x3, kLm = 0xC, kAny = 0xF;
+constexpr uint8_t loop_bit(bool rm, bool lm) { return (rm ? kRm : kPm) & (lm ? kLm : kTray); }
+constexpr int kNw = -1, kNxPlant = -2;      // widths: the solve's nw; the plant's state, 6 (tray) or 8 (LMPC plant)
+struct LoopArr {
+    size_t member;        // offsetof(LoopBuf, ...)
+    int wp, wr;           // elements per instance under PMPC / RMPC; 0: not an array of that controller
+    uint8_t size, kind;
+    uint8_t plants;       // kTray, kLm or kAny: the plants whose loops have the array
+    uint8_t solve_only;   // loops whose loop-step launch does not take the array (only the solve reads it)
+};
+#define ARR(member, wp, wr, type, kind, plants, solve_only) \
+    {offsetof(LoopBuf, member), wp, wr, sizeof(type), kind, plants, solve_only}
+const LoopArr kLoopArr[] = {
+    ARR(target, 6, 4, double, cUp, kAny, kPm & kTray), ARR(prm, 6, 10, double, cUp, kAny, kPm & kLm),
+    ARR(mu, 0, 1, double, cUp, kTray, 0), ARR(plant_pvec, 34, 34, double, cUp, kLm, 0), ARR(pz_vz, 2, 0, double, cUp, kLm, 0),
+    ARR(x, kNxPlant, kNxPlant, double, cBoth, kAny, 0), ARR(tilt, 2, 2, double, cBoth, kAny, 0),
+    ARR(prev, 0, 4, double, cBoth, kAny, 0), ARR(u_prev, 0, 2, double, cBoth, kAny, 0), ARR(r_v, 0, 4, double, cBoth, kAny, 0),
+    ARR(theta, 0, 14, double, cBoth, kAny, 0), ARR(P, 0, 98, double, cBoth, kAny, kRm), ARR(w, 0, kNw, double, cBoth, kAny, kRm),
+    ARR(done, 0, 1, int32_t, cBoth, kAny, 0), ARR(nlog, 0, 1, int32_t, cBoth, kAny, 0),
+    ARR(metrics, 8, 8, double, cBoth, kLm, 0),
+    ARR(log_pos_err, 0, 2, double, cEpisode, kAny, 0), ARR(log_pos_err_norm, 0, 1, double, cEpisode, kAny, 0),
+    ARR(log_u_cmd, 0, 2, double, cEpisode, kAny, 0), ARR(log_timestep, 0, 1, double, cEpisode, kAny, 0),
+    ARR(log_x, 0, 4, double, cStep, kAny, 0), ARR(log_theta, 0, 14, double, cStep, kAny, 0),
+    ARR(log_r_v, 0, 4, double, cStep, kAny, 0), ARR(log_f, 0, 1, double, cStep, kAny, 0),
+    ARR(log_X, 6, 0, double, cStep, kAny, 0), ARR(log_U, 2, 0, double, cStep, kAny, 0), ARR(log_quat, 4, 0, double, cStep, kAny, 0),
+    ARR(log_loss, 1, 0, double, cStep, kAny, 0),
+    ARR(log_status, 1, 1, int32_t, cStep, kAny, 0), ARR(log_iters, 1, 1, int32_t, cStep, kAny, 0),
+    ARR(log_rot, 4, 4, double, cStep, kLm, 0),
+};
+#undef ARR
+constexpr int kLoopArrays = sizeof kLoopArr / sizeof kLoopArr[0];
+
+// (every member of LoopBuf is an object pointer)
+void*& member(LoopBuf& d, const LoopArr& a) { return *reinterpret_cast<void**>(reinterpret_cast<char*>(&d) + a.member); }
+const void* member(const LoopBuf& d, const LoopArr& a) {
+    return *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(&d) + a.member);
+}
+
+// elements per instance of `a` in the loop `bit`; 0: not an array of that loop
+size_t loop_width(const LoopArr& a, uint8_t bit, size_t nw) {
+    const int w = !(a.plants & bit) ? 0 : (bit & kRm) ? a.wr : a.wp;
+    return w == kNw ? nw : w == kNxPlant ? ((bit & kLm) ? 8 : 6) : (size_t)w;
+}
+
+// Every argument check of the PMPC / RMPC loop entries, host and device forms alike (`step`: a loop-step entry, which
+// does not take the arrays that only the solve reads).  LMPC plant: *logs is 1 with every log given, 0 in
+// metrics-only mode (every log null, log_rows not consulted), and mu_c / v_c of the plant config are not used, as
+// in the LMPC loop.  Tray plant: every log is required.
+int loop_buf_check(dart_mpc_handle* h, int variant, bool lm, const dart_plant_config* plant, const dart_rmpc_loop_config* c,
+               int B, int k, int steps, int log_rows, const LoopBuf& p, bool step, int* logs) {
+    if (h->cfg.variant != variant) return fail(h, DART_MPC_EINVAL, variant_text(variant));
+    if (!plant) return fail(h, DART_MPC_EINVAL, "null plant config");
+    if (!lm && (!(plant->v_c > 0.0) || !(plant->mu_c >= 0.0)))
+        return fail(h, DART_MPC_EINVAL, "plant config: v_c > 0, mu_c >= 0");
+    const bool rm = variant == DART_MPC_RMPC;
+    if (rm) {
+        if (!c) return fail(h, DART_MPC_EINVAL, "null loop config");
+        if (!(c->rls_lambda > 0.0) || !(c->dr_max >= 0.0) || !(c->step_fraction >= 0.0 && c->step_fraction <= 1.0))
+            return fail(h, DART_MPC_EINVAL, "loop config: rls_lambda > 0, dr_max >= 0, 0 <= step_fraction <= 1");
+    }
+    if (B < 0 || k < 0 || steps < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
+    if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
+    const uint8_t bit = loop_bit(rm, lm);
+    int given = 0, absent = 0;
+    for (const LoopArr& a : kLoopArr) {
+        if (!loop_width(a, bit, 1) || (step && (a.solve_only & bit))) continue;
+        const bool log = a.kind == cEpisode || a.kind == cStep;
+        if (!member(p, a) && !(log && lm)) return fail(h, DART_MPC_EINVAL, "null pointer");
+        if (log) ++(member(p, a) ? given : absent);
+    }
+    if (given && absent) return fail(h, DART_MPC_EINVAL, "null and non-null log pointers (metrics-only mode: every log null)");
+    if (given && (long long)k + steps > log_rows) return fail(h, DART_MPC_EINVAL, "k0 + steps exceeds log_rows");
+    *logs = given ? 1 : 0;
+    return DART_MPC_OK;
+}
+
+// one loop-step launch (the checks made)
+int loop_step(dart_mpc_handle* h, bool rm, bool lm, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+              int B, int k, int do_post, int do_pre, int log_rows, int logs, const LoopBuf& p, const LoopIo& io,
+              void* stream) {
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const dartmpc::PlantArgs pa = plant_args(h, plant);
+    if (rm) {
+        dartmpc::RmpcLoopArgs a;
+        a.B = B; a.N = h->cfg.N; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+        a.logs = logs; a.plant = pa; a.a_lag = pa.a_lag;
+        a.Ts = h->cfg.Ts; a.dr_max = loop->dr_max; a.alpha_rg = loop->alpha_rg; a.step_fraction = loop->step_fraction;
+        a.pos_tol = loop->pos_tol;
+        a.target = p.target; a.prm = p.prm; a.mu = p.mu; a.plant_pvec = p.plant_pvec;
+        a.x = p.x; a.tilt = p.tilt; a.prev = p.prev; a.u_prev = p.u_prev; a.r_v = p.r_v; a.theta = p.theta;
+        a.done = p.done; a.nlog = p.nlog; a.metrics = p.metrics;
+        a.x0 = io.x0; a.Rref = io.Rref; a.phi = io.phi; a.y = io.y; a.u0 = io.u0; a.f = io.f; a.status = io.status;
+        a.iters = io.iters;
+        a.log_pos_err = p.log_pos_err; a.log_pos_err_norm = p.log_pos_err_norm; a.log_u_cmd = p.log_u_cmd;
+        a.log_timestep = p.log_timestep; a.log_x = p.log_x; a.log_theta = p.log_theta; a.log_r_v = p.log_r_v;
+        a.log_f = p.log_f; a.log_status = p.log_status; a.log_iters = p.log_iters; a.log_rot = p.log_rot;
+        HIPCHK(h, dartmpc_launch_rmpc_loop(&a, lm, stream_of(h, stream)), "loop-step kernel launch");
+    } else {
+        dartmpc::PmpcLoopArgs a;
+        a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows; a.logs = logs;
+        a.plant = pa; a.a_lag = pa.a_lag; a.Ts = h->cfg.Ts;
+        a.prm = p.prm; a.target = p.target; a.plant_pvec = p.plant_pvec; a.pz_vz = p.pz_vz; a.x = p.x; a.tilt = p.tilt;
+        a.metrics = p.metrics; a.x0 = io.x0; a.u0 = io.u0; a.f = io.f; a.status = io.status; a.iters = io.iters;
+        a.log_X = p.log_X; a.log_U = p.log_U; a.log_quat = p.log_quat; a.log_loss = p.log_loss;
+        a.log_status = p.log_status; a.log_iters = p.log_iters; a.log_rot = p.log_rot;
+        HIPCHK(h, dartmpc_launch_pmpc_loop(&a, lm, stream_of(h, stream)), "loop-step kernel launch");
+    }
+    return DART_MPC_OK;
+}
+
+// a loop-step entry: the checks of the buffer and of the solve's per-step arrays, then the launch
+int loop_step_entry(dart_mpc_handle* h, int variant, bool lm, const dart_plant_config* plant,
+                    const dart_rmpc_loop_config* loop, int B, int k, int do_post, int do_pre, int log_rows,
+                    const LoopBuf& p, const LoopIo& io, void* stream) {
+    int logs = 0;
+    if (int rc = loop_buf_check(h, variant, lm, plant, loop, B, k, do_post ? 1 : 0, log_rows, p, true, &logs)) return rc;
+    const bool rm = variant == DART_MPC_RMPC;
+    if (any_null({io.x0, io.u0, io.f, io.status, io.iters}) || (rm && any_null({io.Rref, io.phi, io.y})))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    return loop_step(h, rm, lm, plant, loop, B, k, do_post, do_pre, log_rows, logs, p, io, stream);
+}
+
+// the closed loop on device pointers, the handle's lock held: every check, then the launches (RMPC warm-started in
+// place with the fused RLS, PMPC cold-started)
+int closed_loop(dart_mpc_handle* h, int variant, bool lm, const dart_plant_config* plant,
+                const dart_rmpc_loop_config* loop, int B, int k0, int steps, int log_rows, const LoopBuf& p, void* stream) {
+    int logs = 0;
+    if (int rc = loop_buf_check(h, variant, lm, plant, loop, B, k0, steps, log_rows, p, false, &logs)) return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const bool rm = variant == DART_MPC_RMPC;
+    LoopIo L;
+    if (int rc = loop_scratch(h, L)) return rc;
+    void* s = stream_of(h, stream);
+    auto step = [&](int k, int post, int pre) {
+        return loop_step(h, rm, lm, plant, loop, B, k, post, pre, log_rows, logs, p, L, s);
+    };
+    if (int rc = step(k0, 0, 1)) return rc;
+    for (int j = 0; j < steps; ++j) {
+        // RMPC's warm start in place: every element of w's row is read (at the solve's start) and written (at its
+        // end) by the same wave, and an instance handed to the restoration kernel has not written its row
+        const int rc = rm ? dart_rmpc_solve_batch_dev(h, B, L.x0, p.u_prev, p.theta, p.P, L.phi, L.y, loop->rls_lambda, L.Rref,
+                                                      p.prm, p.w, L.u0, L.f, p.w, L.status, L.iters, s)
+                          : dart_mpc_solve_batch_dev(h, B, L.x0, p.target, p.prm, nullptr, L.u0, L.f, nullptr, L.status,
+                                                     L.iters, s);
+        if (rc) return rc;
+        if (int rc2 = step(k0 + j, 1, j + 1 < steps)) return rc2;
+    }
+    return DART_MPC_OK;
+}
+
+// the host form: the arrays of `p` staged into the handle's arena around closed_loop; in metrics-only mode no log
+// is laid out or moved
+int closed_loop_host(dart_mpc_handle* h, int variant, bool lm, const dart_plant_config* plant,
+                     const dart_rmpc_loop_config* loop, int B, int k0, int steps, int log_rows, const LoopBuf& p,
+                     void* stream) {
+    int logs = 0;
+    if (int rc = loop_buf_check(h, variant, lm, plant, loop, B, k0, steps, log_rows, p, false, &logs)) return rc;
+    if (B == 0 || steps == 0) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    const bool rm = variant == DART_MPC_RMPC;
+    if (!rm)
+        if (int rc = settle_pending(h)) return rc;
+    hipStream_t s = stream_of(h, stream);
+    const size_t nB = (size_t)B, nw = rm ? (size_t)dart_rmpc_nw(h->cfg.N) : 0;
+    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
+    // episode rows: an instance writes rows nlog[b] .. nlog[b] + steps - 1 at most
+    int e0 = log_rows, e1 = 0;
+    if (rm && logs) {
+        for (int b = 0; b < B; ++b) {
+            if (p.nlog[b] < 0) return fail(h, DART_MPC_EINVAL, "negative nlog");
+            e0 = p.nlog[b] < e0 ? p.nlog[b] : e0;
+            e1 = p.nlog[b] > e1 ? p.nlog[b] : e1;
+        }
+        e1 = (long long)e1 + steps < log_rows ? e1 + steps : log_rows;
+        e0 = e0 < e1 ? e0 : e1;
+    }
+    RollStage S;
+    int idx[kLoopArrays];
+    for (int i = 0; i < kLoopArrays; ++i) {
+        const LoopArr& a = kLoopArr[i];
+        const size_t row = loop_width(a, loop_bit(rm, lm), nw) * a.size * nB;
+        idx[i] = -1;
+        if (!row) continue;
+        switch (a.kind) {
+        case cUp: idx[i] = S.add(member(p, a), row, false); break;
+        case cBoth: idx[i] = S.add(member(p, a), row, true); break;
+        case cEpisode: if (logs) idx[i] = S.add_log(const_cast<void*>(member(p, a)), R, row, e0, e1, true); break;
+        case cStep: if (logs) idx[i] = S.add_log(const_cast<void*>(member(p, a)), R, row, r0, r1, false); break;
+        }
+    }
+    if (int rc = S.reserve(h)) return rc;
+    if (int rc = S.upload(h, s)) return rc;
+    LoopBuf d{};
+    for (int i = 0; i < kLoopArrays; ++i) member(d, kLoopArr[i]) = S.dev<char>(h, idx[i]);
+    if (int rc = closed_loop(h, variant, lm, plant, loop, B, k0, steps, log_rows, d, s)) return rc;
+    if (int rc = S.download(h, s)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
+    return DART_MPC_OK;
+}
+
+// (the tray plant's entries leave plant_pvec, pz_vz, metrics and log_rot null, the LMPC plant's mu)
+LoopBuf pmpc_buf(const double* target, const double* prm, const double* plant_pvec, const double* pz_vz, double* x,
+                 double* tilt, double* metrics, double* log_X, double* log_U, double* log_quat, double* log_loss,
+                 int32_t* log_status, int32_t* log_iters, double* log_rot) {
+    LoopBuf p{};
+    p.target = target; p.prm = prm; p.plant_pvec = plant_pvec; p.pz_vz = pz_vz; p.x = x; p.tilt = tilt;
+    p.metrics = metrics; p.log_X = log_X; p.log_U = log_U; p.log_quat = log_quat; p.log_loss = log_loss;
+    p.log_status = log_status; p.log_iters = log_iters; p.log_rot = log_rot;
+    return p;
+}
+
+LoopBuf rmpc_buf(const double* target, const double* prm, const double* mu, const double* plant_pvec, double* x,
+                 double* tilt, double* prev, double* u_prev, double* r_v, double* theta, double* P, double* w,
+                 int32_t* done, int32_t* nlog, double* metrics, double* log_pos_err, double* log_pos_err_norm,
+                 double* log_u_cmd, double* log_timestep, double* log_x, double* log_theta, double* log_r_v,
+                 double* log_f, int32_t* log_status, int32_t* log_iters, double* log_rot) {
+    LoopBuf p{};
+    p.target = target; p.prm = prm; p.mu = mu; p.plant_pvec = plant_pvec; p.x = x; p.tilt = tilt; p.prev = prev;
+    p.u_prev = u_prev; p.r_v = r_v; p.theta = theta; p.P = P; p.w = w; p.done = done; p.nlog = nlog; p.metrics = metrics;
+    p.log_pos_err = log_pos_err; p.log_pos_err_norm = log_pos_err_norm; p.log_u_cmd = log_u_cmd;
+    p.log_timestep = log_timestep; p.log_x = log_x; p.log_theta = log_theta; p.log_r_v = log_r_v; p.log_f = log_f;
+    p.log_status = log_status; p.log_iters = log_iters; p.log_rot = log_rot;
+    return p;
 }
 
 }  // namespace
@@ -102,26 +343,11 @@ int dart_rmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant, 
                             double* log_x, double* log_theta, double* log_r_v, double* log_f,
                             int32_t* log_status, int32_t* log_iters, void* stream) {
     DART_ENTER(h, -1);
-    if (int rc = loop_entry_check(h, DART_MPC_RMPC, plant, loop, B, k, do_post ? 1 : 0, log_rows,
-                                  {target, prm, mu, x, tilt, prev, u_prev, r_v, theta, done, nlog, x0, Rref, phi, y, u0,
-                                   f, status, iters, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x,
-                                   log_theta, log_r_v, log_f, log_status, log_iters}))
-        return rc;
-    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    dartmpc::RmpcLoopArgs a;
-    a.B = B; a.N = h->cfg.N; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
-    a.plant = plant_args(h, plant);
-    a.Ts = h->cfg.Ts; a.dr_max = loop->dr_max; a.alpha_rg = loop->alpha_rg; a.step_fraction = loop->step_fraction;
-    a.pos_tol = loop->pos_tol;
-    a.target = target; a.prm = prm; a.mu = mu;
-    a.x = x; a.tilt = tilt; a.prev = prev; a.u_prev = u_prev; a.r_v = r_v; a.theta = theta; a.done = done; a.nlog = nlog;
-    a.x0 = x0; a.Rref = Rref; a.phi = phi; a.y = y; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
-    a.log_pos_err = log_pos_err; a.log_pos_err_norm = log_pos_err_norm; a.log_u_cmd = log_u_cmd;
-    a.log_timestep = log_timestep; a.log_x = log_x; a.log_theta = log_theta; a.log_r_v = log_r_v; a.log_f = log_f;
-    a.log_status = log_status; a.log_iters = log_iters;
-    HIPCHK(h, dartmpc_launch_rmpc_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
-    return DART_MPC_OK;
+    return loop_step_entry(h, DART_MPC_RMPC, false, plant, loop, B, k, do_post, do_pre, log_rows,
+                           rmpc_buf(target, prm, mu, nullptr, x, tilt, prev, u_prev, r_v, mut(theta), nullptr, nullptr, done,
+                                    nlog, nullptr, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta,
+                                    log_r_v, log_f, log_status, log_iters, nullptr),
+                           {x0, Rref, phi, y, mut(u0), mut(f), mut(status), mut(iters)}, stream);
 }
 
 int dart_pmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
@@ -131,20 +357,10 @@ int dart_pmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
                             double* log_X, double* log_U, double* log_quat, double* log_loss,
                             int32_t* log_status, int32_t* log_iters, void* stream) {
     DART_ENTER(h, -1);
-    if (int rc = loop_entry_check(h, DART_MPC_PMPC, plant, nullptr, B, k, do_post ? 1 : 0, log_rows,
-                                  {prm, x, tilt, x0, u0, f, status, iters, log_X, log_U, log_quat, log_loss, log_status,
-                                   log_iters}))
-        return rc;
-    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    dartmpc::PmpcLoopArgs a;
-    a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
-    a.plant = plant_args(h, plant);
-    a.prm = prm; a.x = x; a.tilt = tilt; a.x0 = x0; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
-    a.log_X = log_X; a.log_U = log_U; a.log_quat = log_quat; a.log_loss = log_loss; a.log_status = log_status;
-    a.log_iters = log_iters;
-    HIPCHK(h, dartmpc_launch_pmpc_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
-    return DART_MPC_OK;
+    return loop_step_entry(h, DART_MPC_PMPC, false, plant, nullptr, B, k, do_post, do_pre, log_rows,
+                           pmpc_buf(nullptr, prm, nullptr, nullptr, x, tilt, nullptr, log_X, log_U, log_quat, log_loss,
+                                    log_status, log_iters, nullptr),
+                           {x0, nullptr, nullptr, nullptr, mut(u0), mut(f), mut(status), mut(iters)}, stream);
 }
 
 int dart_rmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
@@ -156,32 +372,10 @@ int dart_rmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, co
                           double* log_x, double* log_theta, double* log_r_v, double* log_f,
                           int32_t* log_status, int32_t* log_iters, void* stream) {
     DART_ENTER(h, -1);
-    if (int rc = loop_entry_check(h, DART_MPC_RMPC, plant, loop, B, k0, steps, log_rows,
-                                  {target, prm, mu, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog, log_pos_err,
-                                   log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v, log_f,
-                                   log_status, log_iters}))
-        return rc;
-    if (B == 0 || steps == 0) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    LoopScratch L;
-    if (int rc = loop_scratch(h, L)) return rc;
-    void* s = stream_of(h, stream);
-    auto step = [&](int k, int post, int pre) {
-        return dart_rmpc_loop_step_dev(h, plant, loop, B, k, post, pre, log_rows, target, prm, mu, x, tilt, prev, u_prev,
-                                       r_v, theta, done, nlog, L.x0, L.Rref, L.phi, L.y, L.u0, L.f, L.status, L.iters,
-                                       log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v,
-                                       log_f, log_status, log_iters, s);
-    };
-    if (int rc = step(k0, 0, 1)) return rc;
-    for (int j = 0; j < steps; ++j) {
-        // warm start in place: every element of w's row is read (at the solve's start) and written (at its end)
-        // by the same wave, and an instance handed to the restoration kernel has not written its row
-        if (int rc = dart_rmpc_solve_batch_dev(h, B, L.x0, u_prev, theta, P, L.phi, L.y, loop->rls_lambda, L.Rref, prm, w,
-                                               L.u0, L.f, w, L.status, L.iters, s))
-            return rc;
-        if (int rc = step(k0 + j, 1, j + 1 < steps)) return rc;
-    }
-    return DART_MPC_OK;
+    return closed_loop(h, DART_MPC_RMPC, false, plant, loop, B, k0, steps, log_rows,
+                       rmpc_buf(target, prm, mu, nullptr, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog, nullptr,
+                                log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v, log_f,
+                                log_status, log_iters, nullptr), stream);
 }
 
 int dart_pmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant,
@@ -190,25 +384,9 @@ int dart_pmpc_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant,
                           double* log_X, double* log_U, double* log_quat, double* log_loss,
                           int32_t* log_status, int32_t* log_iters, void* stream) {
     DART_ENTER(h, -1);
-    if (int rc = loop_entry_check(h, DART_MPC_PMPC, plant, nullptr, B, k0, steps, log_rows,
-                                  {target, prm, x, tilt, log_X, log_U, log_quat, log_loss, log_status, log_iters}))
-        return rc;
-    if (B == 0 || steps == 0) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    LoopScratch L;
-    if (int rc = loop_scratch(h, L)) return rc;
-    void* s = stream_of(h, stream);
-    auto step = [&](int k, int post, int pre) {
-        return dart_pmpc_loop_step_dev(h, plant, B, k, post, pre, log_rows, prm, x, tilt, L.x0, L.u0, L.f, L.status, L.iters,
-                                       log_X, log_U, log_quat, log_loss, log_status, log_iters, s);
-    };
-    if (int rc = step(k0, 0, 1)) return rc;
-    for (int j = 0; j < steps; ++j) {
-        if (int rc = dart_mpc_solve_batch_dev(h, B, L.x0, target, prm, nullptr, L.u0, L.f, nullptr, L.status, L.iters, s))
-            return rc;
-        if (int rc = step(k0 + j, 1, j + 1 < steps)) return rc;
-    }
-    return DART_MPC_OK;
+    return closed_loop(h, DART_MPC_PMPC, false, plant, nullptr, B, k0, steps, log_rows,
+                       pmpc_buf(target, prm, nullptr, nullptr, x, tilt, nullptr, log_X, log_U, log_quat, log_loss,
+                                log_status, log_iters, nullptr), stream);
 }
 
 int dart_rmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
@@ -220,48 +398,10 @@ int dart_rmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const 
                       double* log_x, double* log_theta, double* log_r_v, double* log_f,
                       int32_t* log_status, int32_t* log_iters, void* stream) {
     DART_ENTER(h, -1);
-    if (int rc = loop_entry_check(h, DART_MPC_RMPC, plant, loop, B, k0, steps, log_rows,
-                                  {target, prm, mu, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog, log_pos_err,
-                                   log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v, log_f,
-                                   log_status, log_iters}))
-        return rc;
-    if (B == 0 || steps == 0) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    hipStream_t s = stream_of(h, stream);
-    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t), nw = (size_t)dart_rmpc_nw(h->cfg.N);
-    // episode rows: an instance writes rows nlog[b] .. nlog[b] + steps - 1 at most
-    int e0 = log_rows, e1 = 0;
-    for (int b = 0; b < B; ++b) {
-        if (nlog[b] < 0) return fail(h, DART_MPC_EINVAL, "negative nlog");
-        e0 = nlog[b] < e0 ? nlog[b] : e0;
-        e1 = nlog[b] > e1 ? nlog[b] : e1;
-    }
-    e1 = (long long)e1 + steps < log_rows ? e1 + steps : log_rows;
-    e0 = e0 < e1 ? e0 : e1;
-    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
-    RollStage S;
-    const int i_tg = S.add(target, 4 * nB * D, false), i_prm = S.add(prm, 10 * nB * D, false), i_mu = S.add(mu, nB * D, false);
-    const int i_x = S.add(x, 6 * nB * D, true), i_tilt = S.add(tilt, 2 * nB * D, true), i_prev = S.add(prev, 4 * nB * D, true);
-    const int i_up = S.add(u_prev, 2 * nB * D, true), i_rv = S.add(r_v, 4 * nB * D, true), i_th = S.add(theta, 14 * nB * D, true);
-    const int i_P = S.add(P, 98 * nB * D, true), i_w = S.add(w, nw * nB * D, true);
-    const int i_done = S.add(done, nB * I, true), i_nlog = S.add(nlog, nB * I, true);
-    const int l_pe = S.add_log(log_pos_err, R, 2 * nB * D, e0, e1, true), l_pn = S.add_log(log_pos_err_norm, R, nB * D, e0, e1, true);
-    const int l_uc = S.add_log(log_u_cmd, R, 2 * nB * D, e0, e1, true), l_ts = S.add_log(log_timestep, R, nB * D, e0, e1, true);
-    const int l_x = S.add_log(log_x, R, 4 * nB * D, r0, r1, false), l_th = S.add_log(log_theta, R, 14 * nB * D, r0, r1, false);
-    const int l_rv = S.add_log(log_r_v, R, 4 * nB * D, r0, r1, false), l_f = S.add_log(log_f, R, nB * D, r0, r1, false);
-    const int l_st = S.add_log(log_status, R, nB * I, r0, r1, false), l_it = S.add_log(log_iters, R, nB * I, r0, r1, false);
-    if (int rc = S.reserve(h)) return rc;
-    if (int rc = S.upload(h, s)) return rc;
-    auto dd = [&](int i) { return S.dev<double>(h, i); };
-    auto di = [&](int i) { return S.dev<int32_t>(h, i); };
-    if (int rc = dart_rmpc_rollout_dev(h, plant, loop, B, k0, steps, log_rows, dd(i_tg), dd(i_prm), dd(i_mu), dd(i_x),
-                                       dd(i_tilt), dd(i_prev), dd(i_up), dd(i_rv), dd(i_th), dd(i_P), dd(i_w), di(i_done),
-                                       di(i_nlog), dd(l_pe), dd(l_pn), dd(l_uc), dd(l_ts), dd(l_x), dd(l_th), dd(l_rv),
-                                       dd(l_f), di(l_st), di(l_it), s))
-        return rc;
-    if (int rc = S.download(h, s)) return rc;
-    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
-    return DART_MPC_OK;
+    return closed_loop_host(h, DART_MPC_RMPC, false, plant, loop, B, k0, steps, log_rows,
+                            rmpc_buf(target, prm, mu, nullptr, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog, nullptr,
+                                     log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v,
+                                     log_f, log_status, log_iters, nullptr), stream);
 }
 
 int dart_pmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant,
@@ -270,31 +410,95 @@ int dart_pmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant,
                       double* log_X, double* log_U, double* log_quat, double* log_loss,
                       int32_t* log_status, int32_t* log_iters, void* stream) {
     DART_ENTER(h, -1);
-    if (int rc = loop_entry_check(h, DART_MPC_PMPC, plant, nullptr, B, k0, steps, log_rows,
-                                  {target, prm, x, tilt, log_X, log_U, log_quat, log_loss, log_status, log_iters}))
-        return rc;
-    if (B == 0 || steps == 0) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    if (int rc = settle_pending(h)) return rc;
-    hipStream_t s = stream_of(h, stream);
-    const size_t nB = (size_t)B, D = sizeof(double), I = sizeof(int32_t);
-    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
-    RollStage S;
-    const int i_tg = S.add(target, 6 * nB * D, false), i_prm = S.add(prm, 6 * nB * D, false);
-    const int i_x = S.add(x, 6 * nB * D, true), i_tilt = S.add(tilt, 2 * nB * D, true);
-    const int l_X = S.add_log(log_X, R, 6 * nB * D, r0, r1, false), l_U = S.add_log(log_U, R, 2 * nB * D, r0, r1, false);
-    const int l_Q = S.add_log(log_quat, R, 4 * nB * D, r0, r1, false), l_L = S.add_log(log_loss, R, nB * D, r0, r1, false);
-    const int l_st = S.add_log(log_status, R, nB * I, r0, r1, false), l_it = S.add_log(log_iters, R, nB * I, r0, r1, false);
-    if (int rc = S.reserve(h)) return rc;
-    if (int rc = S.upload(h, s)) return rc;
-    if (int rc = dart_pmpc_rollout_dev(h, plant, B, k0, steps, log_rows, S.dev<double>(h, i_tg), S.dev<double>(h, i_prm),
-                                       S.dev<double>(h, i_x), S.dev<double>(h, i_tilt), S.dev<double>(h, l_X),
-                                       S.dev<double>(h, l_U), S.dev<double>(h, l_Q), S.dev<double>(h, l_L),
-                                       S.dev<int32_t>(h, l_st), S.dev<int32_t>(h, l_it), s))
-        return rc;
-    if (int rc = S.download(h, s)) return rc;
-    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
-    return DART_MPC_OK;
+    return closed_loop_host(h, DART_MPC_PMPC, false, plant, nullptr, B, k0, steps, log_rows,
+                            pmpc_buf(target, prm, nullptr, nullptr, x, tilt, nullptr, log_X, log_U, log_quat, log_loss,
+                                     log_status, log_iters, nullptr), stream);
+}
+
+int dart_pmpc_lm_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                               int B, int k, int do_post, int do_pre, int log_rows,
+                               const double* target, const double* plant_pvec, const double* pz_vz,
+                               double* x, double* tilt, double* metrics, double* x0,
+                               const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                               double* log_X, double* log_U, double* log_quat, double* log_loss,
+                               int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return loop_step_entry(h, DART_MPC_PMPC, true, plant, nullptr, B, k, do_post, do_pre, log_rows,
+                           pmpc_buf(target, nullptr, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat, log_loss,
+                                    log_status, log_iters, log_rot),
+                           {x0, nullptr, nullptr, nullptr, mut(u0), mut(f), mut(status), mut(iters)}, stream);
+}
+
+int dart_rmpc_lm_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                               int B, int k, int do_post, int do_pre, int log_rows,
+                               const double* target, const double* prm, const double* plant_pvec,
+                               double* x, double* tilt, double* prev, double* u_prev, double* r_v, const double* theta,
+                               int32_t* done, int32_t* nlog, double* metrics,
+                               double* x0, double* Rref, double* phi, double* y,
+                               const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                               double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                               double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                               int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return loop_step_entry(h, DART_MPC_RMPC, true, plant, loop, B, k, do_post, do_pre, log_rows,
+                           rmpc_buf(target, prm, nullptr, plant_pvec, x, tilt, prev, u_prev, r_v, mut(theta), nullptr,
+                                    nullptr, done, nlog, metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep,
+                                    log_x, log_theta, log_r_v, log_f, log_status, log_iters, log_rot),
+                           {x0, Rref, phi, y, mut(u0), mut(f), mut(status), mut(iters)}, stream);
+}
+
+int dart_pmpc_lm_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                             int B, int k0, int steps, int log_rows,
+                             const double* target, const double* prm, const double* plant_pvec, const double* pz_vz,
+                             double* x, double* tilt, double* metrics,
+                             double* log_X, double* log_U, double* log_quat, double* log_loss,
+                             int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return closed_loop(h, DART_MPC_PMPC, true, plant, nullptr, B, k0, steps, log_rows,
+                       pmpc_buf(target, prm, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat, log_loss,
+                                log_status, log_iters, log_rot), stream);
+}
+
+int dart_pmpc_lm_rollout(dart_mpc_handle* h, const dart_plant_config* plant,
+                         int B, int k0, int steps, int log_rows,
+                         const double* target, const double* prm, const double* plant_pvec, const double* pz_vz,
+                         double* x, double* tilt, double* metrics,
+                         double* log_X, double* log_U, double* log_quat, double* log_loss,
+                         int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return closed_loop_host(h, DART_MPC_PMPC, true, plant, nullptr, B, k0, steps, log_rows,
+                            pmpc_buf(target, prm, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat, log_loss,
+                                     log_status, log_iters, log_rot), stream);
+}
+
+int dart_rmpc_lm_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                             int B, int k0, int steps, int log_rows,
+                             const double* target, const double* prm, const double* plant_pvec,
+                             double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
+                             double* P, double* w, int32_t* done, int32_t* nlog, double* metrics,
+                             double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                             double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                             int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return closed_loop(h, DART_MPC_RMPC, true, plant, loop, B, k0, steps, log_rows,
+                       rmpc_buf(target, prm, nullptr, plant_pvec, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog,
+                                metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta, log_r_v,
+                                log_f, log_status, log_iters, log_rot), stream);
+}
+
+int dart_rmpc_lm_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
+                         int B, int k0, int steps, int log_rows,
+                         const double* target, const double* prm, const double* plant_pvec,
+                         double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
+                         double* P, double* w, int32_t* done, int32_t* nlog, double* metrics,
+                         double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
+                         double* log_x, double* log_theta, double* log_r_v, double* log_f,
+                         int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
+    DART_ENTER(h, -1);
+    return closed_loop_host(h, DART_MPC_RMPC, true, plant, loop, B, k0, steps, log_rows,
+                            rmpc_buf(target, prm, nullptr, plant_pvec, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog,
+                                     metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x, log_theta,
+                                     log_r_v, log_f, log_status, log_iters, log_rot), stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -463,7 +667,7 @@ int experience_ptrs(dart_mpc_handle* h, int rec_rows, int reset_rows, const dart
 int lmpc_loop_check(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                     const dart_lmpc_reward_config* rcfg, int B, int k0, int steps, int log_rows, int rec_rows,
                     int reset_rows, const dart_lmpc_train_buffers& p, dartmpc::ExperienceArgs* ea) {
-    if (int rc = loop_check(h, DART_MPC_LMPC, plant, B, k0, steps, log_rows)) return rc;
+    if (int rc = loop_check(h, plant, B, k0, steps, log_rows)) return rc;
     if (ea)
         if (int rc = experience_cfg(h, pcfg, rcfg, B, rec_rows, reset_rows, p.weights, p.critic, *ea)) return rc;
     if (lmpc_null(p, kLoop)) return fail(h, DART_MPC_EINVAL, "null pointer");
@@ -485,15 +689,15 @@ int dart_lmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
                             double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
                             int32_t* log_status, int32_t* log_iters, void* stream) {
     DART_ENTER(h, -1);
-    if (int rc = loop_entry_check(h, DART_MPC_LMPC, plant, nullptr, B, k, do_post ? 1 : 0, log_rows,
-                                  {target, plant_pvec, x, tilt, u_prev, model_params, state, u0, f, status, iters, log_X,
-                                   log_U, log_pos_error, log_pvec, log_loss, log_status, log_iters}))
-        return rc;
+    if (int rc = loop_check(h, plant, B, k, do_post ? 1 : 0, log_rows)) return rc;
+    if (any_null({target, plant_pvec, x, tilt, u_prev, model_params, state, u0, f, status, iters, log_X, log_U,
+                  log_pos_error, log_pvec, log_loss, log_status, log_iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
     if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
     HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
     dartmpc::LmpcLoopArgs a;
     a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
-    a.a_lag = plant->tau > 0.0 ? 1.0 - std::exp(-h->cfg.Ts / plant->tau) : 1.0;
+    a.a_lag = plant_args(h, plant).a_lag;
     a.Ts = h->cfg.Ts;
     a.target = target; a.plant_pvec = plant_pvec; a.x = x; a.tilt = tilt; a.u_prev = u_prev;
     a.model_params = model_params; a.state = state; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
@@ -613,9 +817,6 @@ int lmpc_closed_loop_host(dart_mpc_handle* h, const dart_plant_config* plant, co
     HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
     return DART_MPC_OK;
 }
-
-// (the entries never write through what they take const: the view's members are not const)
-template <class T> T* mut(const T* p) { return const_cast<T*>(p); }
 
 }  // namespace
 
@@ -752,326 +953,3 @@ int dart_lmpc_collect(dart_mpc_handle* h, const dart_plant_config* plant, const 
                                  stream);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Cross-plant closed loops: the PMPC and RMPC loops on the LMPC plant (pmpc_lm_loop_kernel / rmpc_lm_loop_kernel
-// between the unchanged solves), with streaming metrics.  The entries build one CrossBuf from their positional
-// arguments; everything below the entries takes that.  One table, kCrossArr, describes each array once.
-namespace {
-
-struct CrossBuf {
-    const double *target, *prm, *plant_pvec, *pz_vz;
-    double *x, *tilt, *prev, *u_prev, *r_v, *theta, *P, *w;
-    int32_t *done, *nlog;
-    double* metrics;
-    double *log_pos_err, *log_pos_err_norm, *log_u_cmd, *log_timestep;     // RMPC's episode rows
-    double *log_x, *log_theta, *log_r_v, *log_f;                          // RMPC's step rows
-    double *log_X, *log_U, *log_quat, *log_loss;                          // PMPC's step rows
-    int32_t *log_status, *log_iters;
-    double* log_rot;
-};
-
-// the solve's per-step arrays of one loop-step launch
-struct CrossIo {
-    double *x0, *Rref, *phi, *y;
-    const double *u0, *f;
-    const int32_t *status, *iters;
-};
-
-enum CrossKind : uint8_t {
-    cUp,        // [B][width], up only
-    cBoth,      // [B][width], both ways
-    cEpisode,   // [log_rows][B][width], RMPC's episode rows: the rows the call can write travel both ways
-    cStep       // [log_rows][B][width], the call's step rows come down
-};
-constexpr uint8_t kPm = 1, kRm = 2;     // bits of the controllers
-struct CrossArr {
-    size_t member;        // offsetof(CrossBuf, ...)
-    int wp, wr;           // elements per instance under PMPC / RMPC; 0: not an array of that controller, -1: nw
-    uint8_t size, kind;
-    uint8_t solve_only;   // controllers whose loop-step launch does not take the array (only the solve reads it)
-};
-#define ARR(member, wp, wr, type, kind, solve_only) {offsetof(CrossBuf, member), wp, wr, sizeof(type), kind, solve_only}
-const CrossArr kCrossArr[] = {
-    ARR(target, 6, 4, double, cUp, 0), ARR(prm, 6, 10, double, cUp, kPm), ARR(plant_pvec, 34, 34, double, cUp, 0),
-    ARR(pz_vz, 2, 0, double, cUp, 0),
-    ARR(x, 8, 8, double, cBoth, 0), ARR(tilt, 2, 2, double, cBoth, 0), ARR(prev, 0, 4, double, cBoth, 0),
-    ARR(u_prev, 0, 2, double, cBoth, 0), ARR(r_v, 0, 4, double, cBoth, 0), ARR(theta, 0, 14, double, cBoth, 0),
-    ARR(P, 0, 98, double, cBoth, kRm), ARR(w, 0, -1, double, cBoth, kRm),
-    ARR(done, 0, 1, int32_t, cBoth, 0), ARR(nlog, 0, 1, int32_t, cBoth, 0), ARR(metrics, 8, 8, double, cBoth, 0),
-    ARR(log_pos_err, 0, 2, double, cEpisode, 0), ARR(log_pos_err_norm, 0, 1, double, cEpisode, 0),
-    ARR(log_u_cmd, 0, 2, double, cEpisode, 0), ARR(log_timestep, 0, 1, double, cEpisode, 0),
-    ARR(log_x, 0, 4, double, cStep, 0), ARR(log_theta, 0, 14, double, cStep, 0), ARR(log_r_v, 0, 4, double, cStep, 0),
-    ARR(log_f, 0, 1, double, cStep, 0),
-    ARR(log_X, 6, 0, double, cStep, 0), ARR(log_U, 2, 0, double, cStep, 0), ARR(log_quat, 4, 0, double, cStep, 0),
-    ARR(log_loss, 1, 0, double, cStep, 0),
-    ARR(log_status, 1, 1, int32_t, cStep, 0), ARR(log_iters, 1, 1, int32_t, cStep, 0), ARR(log_rot, 4, 4, double, cStep, 0),
-};
-#undef ARR
-constexpr int kCrossArrays = sizeof kCrossArr / sizeof kCrossArr[0];
-
-// (every member of CrossBuf is an object pointer)
-void*& member(CrossBuf& d, const CrossArr& a) { return *reinterpret_cast<void**>(reinterpret_cast<char*>(&d) + a.member); }
-const void* member(const CrossBuf& d, const CrossArr& a) {
-    return *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(&d) + a.member);
-}
-
-// Every argument check of the cross-plant entries, host and device forms alike (`step`: a loop-step entry, which
-// does not take the arrays that only the solve reads).  *logs: 1 with every log given, 0 in metrics-only mode
-// (every log null, log_rows not consulted).  mu_c / v_c of the plant config are not used, as in the LMPC loop.
-int cross_check(dart_mpc_handle* h, int variant, const dart_plant_config* plant, const dart_rmpc_loop_config* c, int B,
-                int k, int steps, int log_rows, const CrossBuf& p, bool step, int* logs) {
-    if (h->cfg.variant != variant) return fail(h, DART_MPC_EINVAL, variant_text(variant));
-    if (!plant) return fail(h, DART_MPC_EINVAL, "null plant config");
-    const bool rm = variant == DART_MPC_RMPC;
-    if (rm) {
-        if (!c) return fail(h, DART_MPC_EINVAL, "null loop config");
-        if (!(c->rls_lambda > 0.0) || !(c->dr_max >= 0.0) || !(c->step_fraction >= 0.0 && c->step_fraction <= 1.0))
-            return fail(h, DART_MPC_EINVAL, "loop config: rls_lambda > 0, dr_max >= 0, 0 <= step_fraction <= 1");
-    }
-    if (B < 0 || k < 0 || steps < 0 || log_rows < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
-    if (B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "batch larger than B_max");
-    int given = 0, absent = 0;
-    for (const CrossArr& a : kCrossArr) {
-        if (!(rm ? a.wr : a.wp) || (step && (a.solve_only & (rm ? kRm : kPm)))) continue;
-        const bool log = a.kind == cEpisode || a.kind == cStep;
-        if (!log && !member(p, a)) return fail(h, DART_MPC_EINVAL, "null pointer");
-        if (log) ++(member(p, a) ? given : absent);
-    }
-    if (given && absent) return fail(h, DART_MPC_EINVAL, "null and non-null log pointers (metrics-only mode: every log null)");
-    if (given && (long long)k + steps > log_rows) return fail(h, DART_MPC_EINVAL, "k0 + steps exceeds log_rows");
-    *logs = given ? 1 : 0;
-    return DART_MPC_OK;
-}
-
-// one loop-step launch (the checks made)
-int cross_loop_step(dart_mpc_handle* h, bool rm, const dart_plant_config* plant, const dart_rmpc_loop_config* loop, int B,
-                    int k, int do_post, int do_pre, int log_rows, int logs, const CrossBuf& p, const CrossIo& io,
-                    void* stream) {
-    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    const double a_lag = plant->tau > 0.0 ? 1.0 - std::exp(-h->cfg.Ts / plant->tau) : 1.0;
-    if (rm) {
-        dartmpc::RmpcLmLoopArgs a;
-        a.B = B; a.N = h->cfg.N; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
-        a.logs = logs; a.a_lag = a_lag;
-        a.Ts = h->cfg.Ts; a.dr_max = loop->dr_max; a.alpha_rg = loop->alpha_rg; a.step_fraction = loop->step_fraction;
-        a.pos_tol = loop->pos_tol;
-        a.target = p.target; a.prm = p.prm; a.plant_pvec = p.plant_pvec;
-        a.x = p.x; a.tilt = p.tilt; a.prev = p.prev; a.u_prev = p.u_prev; a.r_v = p.r_v; a.theta = p.theta;
-        a.done = p.done; a.nlog = p.nlog; a.metrics = p.metrics;
-        a.x0 = io.x0; a.Rref = io.Rref; a.phi = io.phi; a.y = io.y; a.u0 = io.u0; a.f = io.f; a.status = io.status;
-        a.iters = io.iters;
-        a.log_pos_err = p.log_pos_err; a.log_pos_err_norm = p.log_pos_err_norm; a.log_u_cmd = p.log_u_cmd;
-        a.log_timestep = p.log_timestep; a.log_x = p.log_x; a.log_theta = p.log_theta; a.log_r_v = p.log_r_v;
-        a.log_f = p.log_f; a.log_status = p.log_status; a.log_iters = p.log_iters; a.log_rot = p.log_rot;
-        HIPCHK(h, dartmpc_launch_rmpc_lm_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
-    } else {
-        dartmpc::PmpcLmLoopArgs a;
-        a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows; a.logs = logs;
-        a.a_lag = a_lag; a.Ts = h->cfg.Ts;
-        a.target = p.target; a.plant_pvec = p.plant_pvec; a.pz_vz = p.pz_vz; a.x = p.x; a.tilt = p.tilt;
-        a.metrics = p.metrics; a.x0 = io.x0; a.u0 = io.u0; a.f = io.f; a.status = io.status; a.iters = io.iters;
-        a.log_X = p.log_X; a.log_U = p.log_U; a.log_quat = p.log_quat; a.log_loss = p.log_loss;
-        a.log_status = p.log_status; a.log_iters = p.log_iters; a.log_rot = p.log_rot;
-        HIPCHK(h, dartmpc_launch_pmpc_lm_loop(&a, stream_of(h, stream)), "loop-step kernel launch");
-    }
-    return DART_MPC_OK;
-}
-
-// the closed loop on device pointers, the handle's lock held: every check, then the launches of the tray-plant
-// rollouts (RMPC warm-started in place with the fused RLS, PMPC cold-started)
-int cross_closed_loop(dart_mpc_handle* h, int variant, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
-                      int B, int k0, int steps, int log_rows, const CrossBuf& p, void* stream) {
-    int logs = 0;
-    if (int rc = cross_check(h, variant, plant, loop, B, k0, steps, log_rows, p, false, &logs)) return rc;
-    if (B == 0 || steps == 0) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    const bool rm = variant == DART_MPC_RMPC;
-    LoopScratch L;
-    if (int rc = loop_scratch(h, L)) return rc;
-    const CrossIo io = {L.x0, L.Rref, L.phi, L.y, L.u0, L.f, L.status, L.iters};
-    void* s = stream_of(h, stream);
-    auto step = [&](int k, int post, int pre) {
-        return cross_loop_step(h, rm, plant, loop, B, k, post, pre, log_rows, logs, p, io, s);
-    };
-    if (int rc = step(k0, 0, 1)) return rc;
-    for (int j = 0; j < steps; ++j) {
-        const int rc = rm ? dart_rmpc_solve_batch_dev(h, B, L.x0, p.u_prev, p.theta, p.P, L.phi, L.y, loop->rls_lambda, L.Rref,
-                                                      p.prm, p.w, L.u0, L.f, p.w, L.status, L.iters, s)
-                          : dart_mpc_solve_batch_dev(h, B, L.x0, p.target, p.prm, nullptr, L.u0, L.f, nullptr, L.status,
-                                                     L.iters, s);
-        if (rc) return rc;
-        if (int rc2 = step(k0 + j, 1, j + 1 < steps)) return rc2;
-    }
-    return DART_MPC_OK;
-}
-
-// the host form: the arrays of `p` staged into the handle's arena around cross_closed_loop; in metrics-only mode
-// no log is laid out or moved
-int cross_closed_loop_host(dart_mpc_handle* h, int variant, const dart_plant_config* plant,
-                           const dart_rmpc_loop_config* loop, int B, int k0, int steps, int log_rows, const CrossBuf& p,
-                           void* stream) {
-    int logs = 0;
-    if (int rc = cross_check(h, variant, plant, loop, B, k0, steps, log_rows, p, false, &logs)) return rc;
-    if (B == 0 || steps == 0) return DART_MPC_OK;
-    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
-    const bool rm = variant == DART_MPC_RMPC;
-    if (!rm)
-        if (int rc = settle_pending(h)) return rc;
-    hipStream_t s = stream_of(h, stream);
-    const size_t nB = (size_t)B, nw = rm ? (size_t)dart_rmpc_nw(h->cfg.N) : 0;
-    const size_t R = (size_t)log_rows, r0 = (size_t)k0, r1 = (size_t)k0 + steps;
-    // episode rows: an instance writes rows nlog[b] .. nlog[b] + steps - 1 at most
-    int e0 = log_rows, e1 = 0;
-    if (rm && logs) {
-        for (int b = 0; b < B; ++b) {
-            if (p.nlog[b] < 0) return fail(h, DART_MPC_EINVAL, "negative nlog");
-            e0 = p.nlog[b] < e0 ? p.nlog[b] : e0;
-            e1 = p.nlog[b] > e1 ? p.nlog[b] : e1;
-        }
-        e1 = (long long)e1 + steps < log_rows ? e1 + steps : log_rows;
-        e0 = e0 < e1 ? e0 : e1;
-    }
-    RollStage S;
-    int idx[kCrossArrays];
-    for (int i = 0; i < kCrossArrays; ++i) {
-        const CrossArr& a = kCrossArr[i];
-        const int width = rm ? a.wr : a.wp;
-        idx[i] = -1;
-        if (!width) continue;
-        const size_t row = (width < 0 ? nw : (size_t)width) * a.size * nB;
-        switch (a.kind) {
-        case cUp: idx[i] = S.add(member(p, a), row, false); break;
-        case cBoth: idx[i] = S.add(member(p, a), row, true); break;
-        case cEpisode: if (logs) idx[i] = S.add_log(const_cast<void*>(member(p, a)), R, row, e0, e1, true); break;
-        case cStep: if (logs) idx[i] = S.add_log(const_cast<void*>(member(p, a)), R, row, r0, r1, false); break;
-        }
-    }
-    if (int rc = S.reserve(h)) return rc;
-    if (int rc = S.upload(h, s)) return rc;
-    CrossBuf d{};
-    for (int i = 0; i < kCrossArrays; ++i) member(d, kCrossArr[i]) = S.dev<char>(h, idx[i]);
-    if (int rc = cross_closed_loop(h, variant, plant, loop, B, k0, steps, log_rows, d, s)) return rc;
-    if (int rc = S.download(h, s)) return rc;
-    HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
-    return DART_MPC_OK;
-}
-
-CrossBuf pmpc_cross_buf(const double* target, const double* prm, const double* plant_pvec, const double* pz_vz, double* x,
-                        double* tilt, double* metrics, double* log_X, double* log_U, double* log_quat, double* log_loss,
-                        int32_t* log_status, int32_t* log_iters, double* log_rot) {
-    CrossBuf p{};
-    p.target = target; p.prm = prm; p.plant_pvec = plant_pvec; p.pz_vz = pz_vz; p.x = x; p.tilt = tilt;
-    p.metrics = metrics; p.log_X = log_X; p.log_U = log_U; p.log_quat = log_quat; p.log_loss = log_loss;
-    p.log_status = log_status; p.log_iters = log_iters; p.log_rot = log_rot;
-    return p;
-}
-
-CrossBuf rmpc_cross_buf(const double* target, const double* prm, const double* plant_pvec, double* x, double* tilt,
-                        double* prev, double* u_prev, double* r_v, double* theta, double* P, double* w, int32_t* done,
-                        int32_t* nlog, double* metrics, double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd,
-                        double* log_timestep, double* log_x, double* log_theta, double* log_r_v, double* log_f,
-                        int32_t* log_status, int32_t* log_iters, double* log_rot) {
-    CrossBuf p{};
-    p.target = target; p.prm = prm; p.plant_pvec = plant_pvec; p.x = x; p.tilt = tilt; p.prev = prev; p.u_prev = u_prev;
-    p.r_v = r_v; p.theta = theta; p.P = P; p.w = w; p.done = done; p.nlog = nlog; p.metrics = metrics;
-    p.log_pos_err = log_pos_err; p.log_pos_err_norm = log_pos_err_norm; p.log_u_cmd = log_u_cmd;
-    p.log_timestep = log_timestep; p.log_x = log_x; p.log_theta = log_theta; p.log_r_v = log_r_v; p.log_f = log_f;
-    p.log_status = log_status; p.log_iters = log_iters; p.log_rot = log_rot;
-    return p;
-}
-
-}  // namespace
-
-int dart_pmpc_lm_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
-                               int B, int k, int do_post, int do_pre, int log_rows,
-                               const double* target, const double* plant_pvec, const double* pz_vz,
-                               double* x, double* tilt, double* metrics, double* x0,
-                               const double* u0, const double* f, const int32_t* status, const int32_t* iters,
-                               double* log_X, double* log_U, double* log_quat, double* log_loss,
-                               int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
-    DART_ENTER(h, -1);
-    const CrossBuf p = pmpc_cross_buf(target, nullptr, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat,
-                                      log_loss, log_status, log_iters, log_rot);
-    int logs = 0;
-    if (int rc = cross_check(h, DART_MPC_PMPC, plant, nullptr, B, k, do_post ? 1 : 0, log_rows, p, true, &logs)) return rc;
-    if (any_null({x0, u0, f, status, iters})) return fail(h, DART_MPC_EINVAL, "null pointer");
-    const CrossIo io = {x0, nullptr, nullptr, nullptr, u0, f, status, iters};
-    return cross_loop_step(h, false, plant, nullptr, B, k, do_post, do_pre, log_rows, logs, p, io, stream);
-}
-
-int dart_rmpc_lm_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
-                               int B, int k, int do_post, int do_pre, int log_rows,
-                               const double* target, const double* prm, const double* plant_pvec,
-                               double* x, double* tilt, double* prev, double* u_prev, double* r_v, const double* theta,
-                               int32_t* done, int32_t* nlog, double* metrics,
-                               double* x0, double* Rref, double* phi, double* y,
-                               const double* u0, const double* f, const int32_t* status, const int32_t* iters,
-                               double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
-                               double* log_x, double* log_theta, double* log_r_v, double* log_f,
-                               int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
-    DART_ENTER(h, -1);
-    const CrossBuf p = rmpc_cross_buf(target, prm, plant_pvec, x, tilt, prev, u_prev, r_v, mut(theta), nullptr, nullptr, done,
-                                      nlog, metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x,
-                                      log_theta, log_r_v, log_f, log_status, log_iters, log_rot);
-    int logs = 0;
-    if (int rc = cross_check(h, DART_MPC_RMPC, plant, loop, B, k, do_post ? 1 : 0, log_rows, p, true, &logs)) return rc;
-    if (any_null({x0, Rref, phi, y, u0, f, status, iters})) return fail(h, DART_MPC_EINVAL, "null pointer");
-    const CrossIo io = {x0, Rref, phi, y, u0, f, status, iters};
-    return cross_loop_step(h, true, plant, loop, B, k, do_post, do_pre, log_rows, logs, p, io, stream);
-}
-
-int dart_pmpc_lm_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant,
-                             int B, int k0, int steps, int log_rows,
-                             const double* target, const double* prm, const double* plant_pvec, const double* pz_vz,
-                             double* x, double* tilt, double* metrics,
-                             double* log_X, double* log_U, double* log_quat, double* log_loss,
-                             int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
-    DART_ENTER(h, -1);
-    return cross_closed_loop(h, DART_MPC_PMPC, plant, nullptr, B, k0, steps, log_rows,
-                             pmpc_cross_buf(target, prm, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat, log_loss,
-                                            log_status, log_iters, log_rot), stream);
-}
-
-int dart_pmpc_lm_rollout(dart_mpc_handle* h, const dart_plant_config* plant,
-                         int B, int k0, int steps, int log_rows,
-                         const double* target, const double* prm, const double* plant_pvec, const double* pz_vz,
-                         double* x, double* tilt, double* metrics,
-                         double* log_X, double* log_U, double* log_quat, double* log_loss,
-                         int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
-    DART_ENTER(h, -1);
-    return cross_closed_loop_host(h, DART_MPC_PMPC, plant, nullptr, B, k0, steps, log_rows,
-                                  pmpc_cross_buf(target, prm, plant_pvec, pz_vz, x, tilt, metrics, log_X, log_U, log_quat,
-                                                 log_loss, log_status, log_iters, log_rot), stream);
-}
-
-int dart_rmpc_lm_rollout_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
-                             int B, int k0, int steps, int log_rows,
-                             const double* target, const double* prm, const double* plant_pvec,
-                             double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
-                             double* P, double* w, int32_t* done, int32_t* nlog, double* metrics,
-                             double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
-                             double* log_x, double* log_theta, double* log_r_v, double* log_f,
-                             int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
-    DART_ENTER(h, -1);
-    return cross_closed_loop(h, DART_MPC_RMPC, plant, loop, B, k0, steps, log_rows,
-                             rmpc_cross_buf(target, prm, plant_pvec, x, tilt, prev, u_prev, r_v, theta, P, w, done, nlog,
-                                            metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep, log_x,
-                                            log_theta, log_r_v, log_f, log_status, log_iters, log_rot), stream);
-}
-
-int dart_rmpc_lm_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const dart_rmpc_loop_config* loop,
-                         int B, int k0, int steps, int log_rows,
-                         const double* target, const double* prm, const double* plant_pvec,
-                         double* x, double* tilt, double* prev, double* u_prev, double* r_v, double* theta,
-                         double* P, double* w, int32_t* done, int32_t* nlog, double* metrics,
-                         double* log_pos_err, double* log_pos_err_norm, double* log_u_cmd, double* log_timestep,
-                         double* log_x, double* log_theta, double* log_r_v, double* log_f,
-                         int32_t* log_status, int32_t* log_iters, double* log_rot, void* stream) {
-    DART_ENTER(h, -1);
-    return cross_closed_loop_host(h, DART_MPC_RMPC, plant, loop, B, k0, steps, log_rows,
-                                  rmpc_cross_buf(target, prm, plant_pvec, x, tilt, prev, u_prev, r_v, theta, P, w, done,
-                                                 nlog, metrics, log_pos_err, log_pos_err_norm, log_u_cmd, log_timestep,
-                                                 log_x, log_theta, log_r_v, log_f, log_status, log_iters, log_rot),
-                                  stream);
-}

@@ -1,6 +1,8 @@
 // loop_step.h -- launch arguments of the closed-loop glue kernels (loop_step.hip): what the drivers do between
-// two solves (RMPC/dev_dual/rob_ctrl.py:331-416, PMPC/main_parallel_enhanced.py:290-419) and the tray plant of
-// dart_mpc/harness.py, so that a K-step rollout stays on one stream without the host.
+// two solves (RMPC/dev_dual/rob_ctrl.py:331-416, PMPC/main_parallel_enhanced.py:290-419, LMPC/src/run.py:256-286)
+// and the plant, so that a K-step rollout stays on one stream without the host.  One kernel and one argument struct
+// per controller; the PMPC and RMPC kernels are compiled for two plants (harness.TrayPlant, harness.LmpcPlant), and
+// their structs hold the members of both: "tray:" / "LM:" marks a member that only that plant's instantiation reads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,26 +16,45 @@ struct PlantArgs {
     double dt, g;
 };
 
+// Cross-plant loops (LM): the PMPC / RMPC closed loops on harness.LmpcPlant, with streaming metrics.  The plant state
+// is LmpcPlant's x [B][8] = [px vx py vy th_x om_x th_y om_y], stepped by the LMPC model with plant_pvec.  tilt [B][2]
+// is the lagged PMPC / RMPC command (a = g sin(theta), g = -9.81, mpc_3d.py:91-92); the LMPC model has
+// G = m g sin(a) with g = +9.81 (rlmpc2.py:353-357), so its input is sin(-tilt) (run.py:257 flips the command for the
+// same reason): the next state is bit for bit what lmpc_loop_kernel computes for (x, -tilt, -u, pvec).  mu_c / v_c
+// of the plant are not used.
+//
+// metrics [B][8], in/out, updated by every post with e_k = |X_k[[0, 2]] - target[[0, 2]]| of the state that solve k
+// saw: 0 e of the last step, 1 first k with e_k < 0.01 (-1 while there is none), 2 sum |u_k| Ts, 3 max e_k,
+// 4 steps with status != 0, 5 sum of iters, 6 max of |th_x|, |th_y| over the states the solves saw, 7 steps
+// accumulated.  A fresh run starts from zeros with slot 1 = -1.
+//
+// logs == 0 (LM only; every log pointer null): no log row is written and log_rows is not consulted.  The tray
+// plant's loops always log.
+
 // One launch = post(k) and / or pre(next step) for B instances.  All arrays are device memory.
 struct RmpcLoopArgs {
     int B, N;
     int k;                      // step (log row) of the post half; timestep = k Ts
     int do_post, do_pre;
     int log_rows;
-    PlantArgs plant;
+    int logs;                   // LM
+    PlantArgs plant;            // tray
+    double a_lag;               // LM
     double Ts, dr_max, alpha_rg, step_fraction, pos_tol;
     const double* target;       // [B][4]
     const double* prm;          // [B][10] (v_eps = prm[9] scales the RLS features)
-    const double* mu;           // [B] viscous friction of the plant
+    const double* mu;           // tray: [B] viscous friction of the plant
+    const double* plant_pvec;   // LM: [B][34] the plant's parameter vector
     // loop state, in/out
-    double* x;                  // [B][6]
+    double* x;                  // tray: [B][6], LM: [B][8]
     double* tilt;               // [B][2]
     double* prev;               // [B][4]
     double* u_prev;             // [B][2]
     double* r_v;                // [B][4]
     const double* theta;        // [B][14] (updated by the solve's fused RLS; logged here)
     int32_t* done;              // [B]
-    int32_t* nlog;              // [B] episode rows written so far
+    int32_t* nlog;              // [B] episode rows written so far (advances in metrics-only mode too)
+    double* metrics;            // LM: [B][8]
     // the solve's per-step inputs (written by pre) and outputs (read by post)
     double* x0;                 // [B][4]
     double* Rref;               // [B][4(N+1)]
@@ -48,32 +69,40 @@ struct RmpcLoopArgs {
     double* log_pos_err_norm;   // [..]
     double* log_u_cmd;          // [..][2]
     double* log_timestep;       // [..]
-    double* log_x;              // [..][4]
+    double* log_x;              // [..][4] = x[0..3]
     double* log_theta;          // [..][14]
     double* log_r_v;            // [..][4]
     double* log_f;              // [..]
     int32_t* log_status;        // [..]
     int32_t* log_iters;         // [..]
+    double* log_rot;            // LM: [..][4] = x[4..7]
 };
 
 struct PmpcLoopArgs {
     int B;
     int k, do_post, do_pre, log_rows;
-    PlantArgs plant;
-    const double* prm;          // [B][6] (mu = prm[0] is the plant's viscous friction)
-    double* x;                  // [B][6] in/out
+    int logs;                   // LM
+    PlantArgs plant;            // tray
+    double a_lag, Ts;           // LM
+    const double* prm;          // tray: [B][6] (mu = prm[0] is the plant's viscous friction)
+    const double* target;       // LM: [B][6] (the metrics' error)
+    const double* plant_pvec;   // LM: [B][34]
+    const double* pz_vz;        // LM: [B][2] the solve's x0[4..5] (no plant moves them; the tray's are x[4..5])
+    double* x;                  // tray: [B][6], LM: [B][8], in/out
     double* tilt;               // [B][2] in/out
-    double* x0;                 // [B][6] the solve's input (written by pre)
+    double* metrics;            // LM: [B][8] in/out
+    double* x0;                 // [B][6] the solve's input (written by pre): [x[0..3], pz, vz]
     const double* u0;           // [B][2]
     const double* f;            // [B]
     const int32_t* status;      // [B]
     const int32_t* iters;       // [B]
-    double* log_X;              // [log_rows][B][6]
+    double* log_X;              // [log_rows][B][6] = [x[0..3], pz, vz]
     double* log_U;              // [..][2]
     double* log_quat;           // [..][4]
     double* log_loss;           // [..]
     int32_t* log_status;        // [..]
     int32_t* log_iters;         // [..]
+    double* log_rot;            // LM: [..][4] = x[4..7]
 };
 
 // harness.LmpcPlant: the same tilt lag, then one RK4 step at Ts of the LMPC model itself (safe_dynamics,
@@ -105,85 +134,9 @@ struct LmpcLoopArgs {
     int32_t* log_iters;         // [..]
 };
 
-// Cross-plant loops: the PMPC / RMPC closed loops of pmpc_loop_kernel / rmpc_loop_kernel on harness.LmpcPlant, with
-// streaming metrics.  The plant state is LmpcPlant's x [B][8] = [px vx py vy th_x om_x th_y om_y], stepped by the
-// LMPC model with plant_pvec.  tilt [B][2] is the lagged PMPC / RMPC command (a = g sin(theta), g = -9.81,
-// mpc_3d.py:91-92); the LMPC model has G = m g sin(a) with g = +9.81 (rlmpc2.py:353-357), so its input is
-// sin(-tilt) (run.py:257 flips the command for the same reason): the next state is bit for bit what
-// lmpc_loop_kernel computes for (x, -tilt, -u, pvec).
-//
-// metrics [B][8], in/out, updated by every post with e_k = |X_k[[0, 2]] - target[[0, 2]]| of the state that solve k
-// saw: 0 e of the last step, 1 first k with e_k < 0.01 (-1 while there is none), 2 sum |u_k| Ts, 3 max e_k,
-// 4 steps with status != 0, 5 sum of iters, 6 max of |th_x|, |th_y| over the states the solves saw, 7 steps
-// accumulated.  A fresh run starts from zeros with slot 1 = -1.
-//
-// logs == 0 (every log pointer null): no log row is written and log_rows is not consulted.
-struct PmpcLmLoopArgs {
-    int B;
-    int k, do_post, do_pre, log_rows, logs;
-    double a_lag, Ts;
-    const double* target;       // [B][6]
-    const double* plant_pvec;   // [B][34]
-    const double* pz_vz;        // [B][2] the solve's x0[4..5] (no plant moves them)
-    double* x;                  // [B][8] in/out
-    double* tilt;               // [B][2] in/out
-    double* metrics;            // [B][8] in/out
-    double* x0;                 // [B][6] the solve's input (written by pre): [x[0..3], pz_vz]
-    const double* u0;           // [B][2]
-    const double* f;            // [B]
-    const int32_t* status;      // [B]
-    const int32_t* iters;       // [B]
-    double* log_X;              // [log_rows][B][6] = [x[0..3], pz_vz]
-    double* log_U;              // [..][2]
-    double* log_quat;           // [..][4]
-    double* log_loss;           // [..]
-    int32_t* log_status;        // [..]
-    int32_t* log_iters;         // [..]
-    double* log_rot;            // [..][4] = x[4..7]
-};
-
-struct RmpcLmLoopArgs {
-    int B, N;
-    int k, do_post, do_pre, log_rows, logs;
-    double a_lag;
-    double Ts, dr_max, alpha_rg, step_fraction, pos_tol;
-    const double* target;       // [B][4]
-    const double* prm;          // [B][10]
-    const double* plant_pvec;   // [B][34]
-    double* x;                  // [B][8] in/out
-    double* tilt;               // [B][2]
-    double* prev;               // [B][4]
-    double* u_prev;             // [B][2]
-    double* r_v;                // [B][4]
-    const double* theta;        // [B][14]
-    int32_t* done;              // [B]
-    int32_t* nlog;              // [B] (advances in metrics-only mode too)
-    double* metrics;            // [B][8] in/out
-    double* x0;                 // [B][4]
-    double* Rref;               // [B][4(N+1)]
-    double* phi;                // [B][7]
-    double* y;                  // [B][2]
-    const double* u0;           // [B][2]
-    const double* f;            // [B]
-    const int32_t* status;      // [B]
-    const int32_t* iters;       // [B]
-    double* log_pos_err;        // as RmpcLoopArgs
-    double* log_pos_err_norm;
-    double* log_u_cmd;
-    double* log_timestep;
-    double* log_x;              // [..][4] = x[0..3]
-    double* log_theta;
-    double* log_r_v;
-    double* log_f;
-    int32_t* log_status;
-    int32_t* log_iters;
-    double* log_rot;            // [..][4] = x[4..7]
-};
-
 }  // namespace dartmpc
 
+// (lm: 0 the tray plant's instantiation, 1 the LMPC plant's)
 extern "C" hipError_t dartmpc_launch_lmpc_loop(const dartmpc::LmpcLoopArgs* args, hipStream_t stream);
-extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, hipStream_t stream);
-extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args, hipStream_t stream);
-extern "C" hipError_t dartmpc_launch_pmpc_lm_loop(const dartmpc::PmpcLmLoopArgs* args, hipStream_t stream);
-extern "C" hipError_t dartmpc_launch_rmpc_lm_loop(const dartmpc::RmpcLmLoopArgs* args, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, int lm, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args, int lm, hipStream_t stream);

@@ -1,12 +1,14 @@
-// loop_step.hip -- the closed-loop glue between two solves, on the device.
+// loop_step.hip -- the closed-loop glue between two solves, on the device.  One kernel per controller.
 //
-// rmpc_loop_kernel: post(k) = the log rows, the episode end and the plant step of harness.run_rmpc; pre(k+1) =
+// rmpc_loop_kernel<LM>: post(k) = the log rows, the episode end and the plant step of harness.run_rmpc; pre(k+1) =
 // the RLS features / targets, the reference governor and the staged reference of the next solve
-// (RMPC/dev_dual/rob_ctrl.py:335-351).  pmpc_loop_kernel: the same for harness.run_pmpc
-// (PMPC/main_parallel_enhanced.py:333-348: log, tilt -> quaternion, plant step, next state).  lmpc_loop_kernel:
-// the same for harness.run_lmpc (LMPC/src/run.py:256-286: log, plant step of the LMPC model, next state); its
-// lane mapping is described at the kernel.  pmpc_lm_loop_kernel / rmpc_lm_loop_kernel: the PMPC / RMPC glue on the
-// LMPC plant, with streaming metrics (harness.run_pmpc / run_rmpc with plant_pvec), at the end of the file.
+// (RMPC/dev_dual/rob_ctrl.py:335-351).  pmpc_loop_kernel<LM>: the same for harness.run_pmpc
+// (PMPC/main_parallel_enhanced.py:333-348: log, tilt -> quaternion, plant step, next state).  Both are compiled for
+// two plants: LM = false steps harness.TrayPlant (x [6]), LM = true harness.LmpcPlant (x [8], harness.run_pmpc /
+// run_rmpc with plant_pvec) and also keeps the streaming metrics and the rotation log of loop_step.h; what a plant
+// does not have is under `if constexpr (LM)` and is not in the other instantiation.  lmpc_loop_kernel: the same glue
+// for harness.run_lmpc (LMPC/src/run.py:256-286: log, plant step of the LMPC model, next state); its lane mapping is
+// described at the kernel.
 //
 // RMPC / PMPC: one wave64 per instance, kLoopWaves instances per block; lane i owns horizon node i (the staged
 // reference), the per-instance scalars are computed by every lane and stored by one.  All three: plain fp64 in the
@@ -44,124 +46,6 @@ __host__ __device__ __forceinline__ void tray_plant_step(const PlantArgs& p, dou
     x[2] = x[2] + h6 * (k1y + 2 * k2y + 2 * k3y + k4y);
     x[3] = x[3] + h6 * (a1y + 2 * a2y + 2 * a3y + a4y);
     // (pz, vz: zero derivative)
-}
-
-__global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_loop_kernel(RmpcLoopArgs a) {
-    const int lane = threadIdx.x & (kLoopWave - 1);
-    const int b = blockIdx.x * kLoopWaves + (threadIdx.x >> 6);
-    if (b >= a.B) return;                    // wave-uniform
-    const size_t B = (size_t)a.B;
-    const double* tg = a.target + 4 * b;
-    const double t0 = tg[0], t2 = tg[2];
-    double x[6], tilt[2], prev[4], rv[4];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) x[i] = a.x[6 * b + i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rv[i] = a.r_v[4 * b + i];
-
-    if (a.do_post) {
-        tilt[0] = a.tilt[2 * b]; tilt[1] = a.tilt[2 * b + 1];
-        const double u[2] = {a.u0[2 * b], a.u0[2 * b + 1]};
-        const size_t row = (size_t)a.k * B + b;
-        const double dx = x[0] - t0, dy = x[2] - t2;
-        const double en = sqrt(dx * dx + dy * dy);
-        if (lane < 14) a.log_theta[14 * row + lane] = a.theta[14 * b + lane];
-        if (lane == 0) {
-            const int nl = a.nlog[b];
-            if (!a.done[b]) {
-                if (nl >= 0 && nl < a.log_rows) {
-                    const size_t er = (size_t)nl * B + b;
-                    a.log_pos_err[2 * er] = t0 - x[0]; a.log_pos_err[2 * er + 1] = t2 - x[2];
-                    a.log_pos_err_norm[er] = en;
-                    a.log_u_cmd[2 * er] = u[0]; a.log_u_cmd[2 * er + 1] = u[1];
-                    a.log_timestep[er] = a.k * a.Ts;
-                }
-                a.nlog[b] = nl + 1;
-                if (en < a.pos_tol) a.done[b] = 1;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                a.log_x[4 * row + i] = x[i];
-                a.log_r_v[4 * row + i] = rv[i];
-                a.prev[4 * b + i] = x[i];
-            }
-            a.log_status[row] = a.status[b];
-            a.log_iters[row] = a.iters[b];
-            a.log_f[row] = a.f[b];
-            a.u_prev[2 * b] = u[0]; a.u_prev[2 * b + 1] = u[1];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) prev[i] = x[i];
-        tray_plant_step(a.plant, a.mu[b], u, x, tilt);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a.x[6 * b + i] = x[i];
-            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) prev[i] = a.prev[4 * b + i];
-    }
-
-    if (a.do_pre) {
-        const double veps = a.prm[10 * b + 9];
-        // reference governor (rob_ctrl.py:346-348) on the two position entries
-        rv[0] = rv[0] + a.alpha_rg * fmin(fmax(t0 - rv[0], -a.dr_max), a.dr_max);
-        rv[2] = rv[2] + a.alpha_rg * fmin(fmax(t2 - rv[2], -a.dr_max), a.dr_max);
-        if (lane <= a.N) {      // staged reference, node `lane` (np_mpc...:201-210)
-            const double wgt = 1.0 - pow(1.0 - a.step_fraction, (double)(lane + 1));
-            double* R = a.Rref + 4 * ((size_t)(a.N + 1) * b + lane);
-            R[0] = rv[0] + wgt * (t0 - rv[0]); R[1] = 0.0;
-            R[2] = rv[2] + wgt * (t2 - rv[2]); R[3] = 0.0;
-        }
-        if (lane == 0) {
-            a.r_v[4 * b] = rv[0]; a.r_v[4 * b + 2] = rv[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { a.x0[4 * b + i] = x[i]; a.phi[7 * b + i] = prev[i]; }
-            a.phi[7 * b + 4] = tanh(prev[1] / veps);
-            a.phi[7 * b + 5] = tanh(prev[3] / veps);
-            a.phi[7 * b + 6] = 1.0;
-            a.y[2 * b] = (x[1] - prev[1]) / a.Ts;
-            a.y[2 * b + 1] = (x[3] - prev[3]) / a.Ts;
-        }
-    }
-}
-
-__global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_loop_kernel(PmpcLoopArgs a) {
-    const int lane = threadIdx.x & (kLoopWave - 1);
-    const int b = blockIdx.x * kLoopWaves + (threadIdx.x >> 6);
-    if (b >= a.B) return;                    // wave-uniform
-    double x[6], tilt[2];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) x[i] = a.x[6 * b + i];
-
-    if (a.do_post) {
-        tilt[0] = a.tilt[2 * b]; tilt[1] = a.tilt[2 * b + 1];
-        const double u[2] = {a.u0[2 * b], a.u0[2 * b + 1]};
-        const size_t row = (size_t)a.k * a.B + b;
-        // pmpc.tilt_to_quat: Euler xyz [u1, -u0, 0] -> (w, x, y, z)
-        const double ax = u[1] / 2.0, ay = -u[0] / 2.0;
-        const double cx = cos(ax), cy = cos(ay), cz = 1.0, sx = sin(ax), sy = sin(ay), sz = 0.0;
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) a.log_X[6 * row + i] = x[i];
-            a.log_U[2 * row] = u[0]; a.log_U[2 * row + 1] = u[1];
-            a.log_quat[4 * row] = cx * cy * cz + sx * sy * sz;
-            a.log_quat[4 * row + 1] = sx * cy * cz - cx * sy * sz;
-            a.log_quat[4 * row + 2] = cx * sy * cz + sx * cy * sz;
-            a.log_quat[4 * row + 3] = cx * cy * sz - sx * sy * cz;
-            a.log_loss[row] = a.f[b];
-            a.log_status[row] = a.status[b];
-            a.log_iters[row] = a.iters[b];
-        }
-        tray_plant_step(a.plant, a.prm[6 * b], u, x, tilt);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a.x[6 * b + i] = x[i];
-            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
-        }
-    }
-    if (a.do_pre && lane < 6) a.x0[6 * b + lane] = x[lane];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -281,12 +165,10 @@ __global__ __launch_bounds__(kLmLoopThreads) void lmpc_loop_kernel(LmpcLoopArgs 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Cross-plant loops (harness.run_pmpc / run_rmpc with plant_pvec): pmpc_loop_kernel / rmpc_loop_kernel on the LMPC
-// plant, with streaming metrics (loop_step.h).  One wave64 per instance as there: lane i owns node i of RMPC's
-// staged reference, and every aligned group of kLmGroup lanes runs the plant step the way lmpc_loop_kernel's
-// group does (lane r = lane & 7 evaluates Stribeck term r; the shuffles stay inside the group), so all 64 lanes
-// hold the same next state.  The plant step is lmpc_loop_kernel's text again, not shared with it, so that kernel
-// keeps its instructions.
+// The LMPC plant under the PMPC / RMPC kernels (LM = true), one wave64 per instance as on the tray: every aligned
+// group of kLmGroup lanes runs the plant step the way lmpc_loop_kernel's group does (lane r = lane & 7 evaluates
+// Stribeck term r; the shuffles stay inside the group).  The plant step is lmpc_loop_kernel's text again, not shared
+// with it, so that kernel keeps its instructions.
 constexpr double kMetricTol = 0.01;     // logger.py:162
 
 // harness.LmpcPlant.step with the command -u: tilt is the lagged PMPC / RMPC command, the model's input sin(-tilt)
@@ -321,7 +203,8 @@ __device__ __forceinline__ void lm_cross_plant_step(const double* pv, int r, dou
     for (int i = 0; i < 8; ++i) x[i] = x[i] + h * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) / 6;
 }
 
-// harness.rollout_metrics, one step: m [8] in/out (one lane per instance)
+// harness.rollout_metrics, one step: m [8] in/out, the instance's row in memory, read whole before it is written
+// (one lane per instance)
 __device__ __forceinline__ void loop_metrics_step(double* m, int k, double Ts, double e, const double* u, int status,
                                                   int iters, double th_x, double th_y) {
     const double first = m[1], eff = m[2], emax = m[3], bad = m[4], its = m[5], rot = m[6], n = m[7];
@@ -337,16 +220,35 @@ __device__ __forceinline__ void loop_metrics_step(double* m, int k, double Ts, d
     m[7] = n + 1.0;
 }
 
-__global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_lm_loop_kernel(RmpcLmLoopArgs a) {
+// One plant step of instance b with the command u, and the new state stored by lane 0.  Tray: mu is the instance's
+// viscous friction, and x[0..3] are stored (pz, vz do not move).  LMPC plant: every aligned group of kLmGroup lanes
+// runs the step the way lmpc_loop_kernel's group does, so all 64 lanes hold the same next state; x[0..7] are stored.
+template <bool LM, class Args>
+__device__ __forceinline__ void loop_plant_step(const Args& a, int b, int lane, const double* mu, const double* u,
+                                                double* x, double* tilt) {
+    if constexpr (LM) lm_cross_plant_step(a.plant_pvec + 34 * b, lane & (kLmGroup - 1), a.a_lag, a.Ts, u, x, tilt);
+    else tray_plant_step(a.plant, *mu, u, x, tilt);
+    if (lane == 0) {
+        constexpr int NX = LM ? 8 : 6;
+#pragma unroll
+        for (int i = 0; i < (LM ? 8 : 4); ++i) a.x[NX * b + i] = x[i];
+        a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
+    }
+}
+
+template <bool LM>
+__global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_loop_kernel(RmpcLoopArgs a) {
+    constexpr int NX = LM ? 8 : 6;
     const int lane = threadIdx.x & (kLoopWave - 1);
     const int b = blockIdx.x * kLoopWaves + (threadIdx.x >> 6);
     if (b >= a.B) return;                    // wave-uniform
     const size_t B = (size_t)a.B;
+    const int logs = LM ? a.logs : 1;        // (the tray plant's loop always logs)
     const double* tg = a.target + 4 * b;
     const double t0 = tg[0], t2 = tg[2];
-    double x[8], tilt[2], prev[4], rv[4];
+    double x[NX], tilt[2], prev[4], rv[4];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = a.x[8 * b + i];
+    for (int i = 0; i < NX; ++i) x[i] = a.x[NX * b + i];
 #pragma unroll
     for (int i = 0; i < 4; ++i) rv[i] = a.r_v[4 * b + i];
 
@@ -356,11 +258,11 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_lm_loop_kernel(Rmp
         const size_t row = (size_t)a.k * B + b;
         const double dx = x[0] - t0, dy = x[2] - t2;
         const double en = sqrt(dx * dx + dy * dy);
-        if (a.logs && lane < 14) a.log_theta[14 * row + lane] = a.theta[14 * b + lane];
+        if (logs && lane < 14) a.log_theta[14 * row + lane] = a.theta[14 * b + lane];
         if (lane == 0) {
             const int nl = a.nlog[b];
             if (!a.done[b]) {
-                if (a.logs && nl >= 0 && nl < a.log_rows) {
+                if (logs && nl >= 0 && nl < a.log_rows) {
                     const size_t er = (size_t)nl * B + b;
                     a.log_pos_err[2 * er] = t0 - x[0]; a.log_pos_err[2 * er + 1] = t2 - x[2];
                     a.log_pos_err_norm[er] = en;
@@ -371,12 +273,12 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_lm_loop_kernel(Rmp
                 if (en < a.pos_tol) a.done[b] = 1;
             }
             const int status = a.status[b], iters = a.iters[b];
-            if (a.logs) {
+            if (logs) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     a.log_x[4 * row + i] = x[i];
                     a.log_r_v[4 * row + i] = rv[i];
-                    a.log_rot[4 * row + i] = x[4 + i];
+                    if constexpr (LM) a.log_rot[4 * row + i] = x[4 + i];
                 }
                 a.log_status[row] = status;
                 a.log_iters[row] = iters;
@@ -385,21 +287,11 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_lm_loop_kernel(Rmp
 #pragma unroll
             for (int i = 0; i < 4; ++i) a.prev[4 * b + i] = x[i];
             a.u_prev[2 * b] = u[0]; a.u_prev[2 * b + 1] = u[1];
-            double m[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) m[i] = a.metrics[8 * b + i];
-            loop_metrics_step(m, a.k, a.Ts, en, u, status, iters, x[4], x[6]);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) a.metrics[8 * b + i] = m[i];
+            if constexpr (LM) loop_metrics_step(a.metrics + 8 * b, a.k, a.Ts, en, u, status, iters, x[4], x[6]);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) prev[i] = x[i];
-        lm_cross_plant_step(a.plant_pvec + 34 * b, lane & (kLmGroup - 1), a.a_lag, a.Ts, u, x, tilt);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) a.x[8 * b + i] = x[i];
-            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
-        }
+        loop_plant_step<LM>(a, b, lane, LM ? nullptr : a.mu + b, u, x, tilt);
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) prev[i] = a.prev[4 * b + i];
@@ -408,8 +300,9 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_lm_loop_kernel(Rmp
     if (a.do_pre) {
         const double veps = a.prm[10 * b + 9];
         // reference governor (rob_ctrl.py:346-348) on the two position entries
-        rv[0] = rv[0] + a.alpha_rg * fmin(fmax(t0 - rv[0], -a.dr_max), a.dr_max);
-        rv[2] = rv[2] + a.alpha_rg * fmin(fmax(t2 - rv[2], -a.dr_max), a.dr_max);
+        auto govern = [&](double r, double t) { return r + a.alpha_rg * fmin(fmax(t - r, -a.dr_max), a.dr_max); };
+        rv[0] = govern(rv[0], t0);
+        rv[2] = govern(rv[2], t2);
         if (lane <= a.N) {      // staged reference, node `lane` (np_mpc...:201-210)
             const double wgt = 1.0 - pow(1.0 - a.step_fraction, (double)(lane + 1));
             double* R = a.Rref + 4 * ((size_t)(a.N + 1) * b + lane);
@@ -429,14 +322,18 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void rmpc_lm_loop_kernel(Rmp
     }
 }
 
-__global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_lm_loop_kernel(PmpcLmLoopArgs a) {
+template <bool LM>
+__global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_loop_kernel(PmpcLoopArgs a) {
+    constexpr int NX = LM ? 8 : 6;
     const int lane = threadIdx.x & (kLoopWave - 1);
     const int b = blockIdx.x * kLoopWaves + (threadIdx.x >> 6);
     if (b >= a.B) return;                    // wave-uniform
-    double x[8], tilt[2];
+    const int logs = LM ? a.logs : 1;        // (the tray plant's loop always logs)
+    double x[NX], tilt[2];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = a.x[8 * b + i];
-    const double pz = a.pz_vz[2 * b], vz = a.pz_vz[2 * b + 1];
+    for (int i = 0; i < NX; ++i) x[i] = a.x[NX * b + i];
+    // the solve's x0[4..5]: the tray's own x[4..5]; the LMPC plant has none, so the caller's pz_vz
+    const double pz = LM ? a.pz_vz[2 * b] : x[4], vz = LM ? a.pz_vz[2 * b + 1] : x[5];
 
     if (a.do_post) {
         tilt[0] = a.tilt[2 * b]; tilt[1] = a.tilt[2 * b + 1];
@@ -447,9 +344,12 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_lm_loop_kernel(Pmp
         const double cx = cos(ax), cy = cos(ay), cz = 1.0, sx = sin(ax), sy = sin(ay), sz = 0.0;
         if (lane == 0) {
             const int status = a.status[b], iters = a.iters[b];
-            if (a.logs) {
+            if (logs) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { a.log_X[6 * row + i] = x[i]; a.log_rot[4 * row + i] = x[4 + i]; }
+                for (int i = 0; i < 4; ++i) {
+                    a.log_X[6 * row + i] = x[i];
+                    if constexpr (LM) a.log_rot[4 * row + i] = x[4 + i];
+                }
                 a.log_X[6 * row + 4] = pz; a.log_X[6 * row + 5] = vz;
                 a.log_U[2 * row] = u[0]; a.log_U[2 * row + 1] = u[1];
                 a.log_quat[4 * row] = cx * cy * cz + sx * sy * sz;
@@ -460,20 +360,12 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_lm_loop_kernel(Pmp
                 a.log_status[row] = status;
                 a.log_iters[row] = iters;
             }
-            const double dx = x[0] - a.target[6 * b], dy = x[2] - a.target[6 * b + 2];
-            double m[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) m[i] = a.metrics[8 * b + i];
-            loop_metrics_step(m, a.k, a.Ts, sqrt(dx * dx + dy * dy), u, status, iters, x[4], x[6]);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) a.metrics[8 * b + i] = m[i];
+            if constexpr (LM) {
+                const double dx = x[0] - a.target[6 * b], dy = x[2] - a.target[6 * b + 2];
+                loop_metrics_step(a.metrics + 8 * b, a.k, a.Ts, sqrt(dx * dx + dy * dy), u, status, iters, x[4], x[6]);
+            }
         }
-        lm_cross_plant_step(a.plant_pvec + 34 * b, lane & (kLmGroup - 1), a.a_lag, a.Ts, u, x, tilt);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) a.x[8 * b + i] = x[i];
-            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
-        }
+        loop_plant_step<LM>(a, b, lane, LM ? nullptr : a.prm + 6 * b, u, x, tilt);
     }
     if (a.do_pre && lane == 0) {
 #pragma unroll
@@ -482,46 +374,30 @@ __global__ __launch_bounds__(kLoopWave* kLoopWaves) void pmpc_lm_loop_kernel(Pmp
     }
 }
 
+// the early return of an empty launch, the block count (`per_block` instances in a block of 256 threads), the launch
+template <class Args>
+hipError_t launch_loop(void (*kernel)(Args), const Args& a, int per_block, hipStream_t stream, bool valid = true) {
+    static_assert(kLoopWave * kLoopWaves == kLmLoopThreads, "one block size for the three kernels");
+    if (a.B <= 0 || (!a.do_post && !a.do_pre)) return hipSuccess;
+    if (!valid) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3((a.B + per_block - 1) / per_block), dim3(kLmLoopThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
 }  // namespace dartmpc
 
-extern "C" hipError_t dartmpc_launch_rmpc_lm_loop(const dartmpc::RmpcLmLoopArgs* args, hipStream_t stream) {
-    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
-    if (args->N < 1 || args->N > 63) return hipErrorInvalidValue;
-    const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
-    hipLaunchKernelGGL(dartmpc::rmpc_lm_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0,
-                       stream, *args);
-    return hipGetLastError();
+using namespace dartmpc;
+
+extern "C" hipError_t dartmpc_launch_rmpc_loop(const RmpcLoopArgs* args, int lm, hipStream_t stream) {
+    // (lane i owns node i of the staged reference)
+    return launch_loop(lm ? rmpc_loop_kernel<true> : rmpc_loop_kernel<false>, *args, kLoopWaves, stream,
+                       args->N >= 1 && args->N <= 63);
 }
 
-extern "C" hipError_t dartmpc_launch_pmpc_lm_loop(const dartmpc::PmpcLmLoopArgs* args, hipStream_t stream) {
-    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
-    const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
-    hipLaunchKernelGGL(dartmpc::pmpc_lm_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0,
-                       stream, *args);
-    return hipGetLastError();
+extern "C" hipError_t dartmpc_launch_pmpc_loop(const PmpcLoopArgs* args, int lm, hipStream_t stream) {
+    return launch_loop(lm ? pmpc_loop_kernel<true> : pmpc_loop_kernel<false>, *args, kLoopWaves, stream);
 }
 
-extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, hipStream_t stream) {
-    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
-    if (args->N < 1 || args->N > 63) return hipErrorInvalidValue;
-    const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
-    hipLaunchKernelGGL(dartmpc::rmpc_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0, stream,
-                       *args);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args, hipStream_t stream) {
-    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
-    const int blocks = (args->B + dartmpc::kLoopWaves - 1) / dartmpc::kLoopWaves;
-    hipLaunchKernelGGL(dartmpc::pmpc_loop_kernel, dim3(blocks), dim3(dartmpc::kLoopWave * dartmpc::kLoopWaves), 0, stream,
-                       *args);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t dartmpc_launch_lmpc_loop(const dartmpc::LmpcLoopArgs* args, hipStream_t stream) {
-    if (args->B <= 0 || (!args->do_post && !args->do_pre)) return hipSuccess;
-    const int per = dartmpc::kLmLoopThreads / dartmpc::kLmGroup;
-    const int blocks = (args->B + per - 1) / per;
-    hipLaunchKernelGGL(dartmpc::lmpc_loop_kernel, dim3(blocks), dim3(dartmpc::kLmLoopThreads), 0, stream, *args);
-    return hipGetLastError();
+extern "C" hipError_t dartmpc_launch_lmpc_loop(const LmpcLoopArgs* args, hipStream_t stream) {
+    return launch_loop(lmpc_loop_kernel, *args, kLmLoopThreads / kLmGroup, stream);
 }

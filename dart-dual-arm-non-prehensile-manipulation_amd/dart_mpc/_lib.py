@@ -751,78 +751,68 @@ class Solver:
         if rc != 0:
             self._err(rc, "dart_mpc_solve_batch_dev")
 
-    # -- device-resident closed loop (dart_pmpc_loop_step_dev / dart_pmpc_rollout_dev / dart_pmpc_rollout) ----
+    # -- device-resident closed loops: every dart_{pmpc,rmpc}[_lm]_{loop_step_dev,rollout_dev,rollout} entry goes
+    # through these two
+    def _loop_dev(self, entry, cfgs, dims, lead, specs, stream):
+        """A device loop-step or rollout entry: the config structs, the int dimensions, the leading device pointers,
+        then the pointers of every (spec, mapping) of ``specs``."""
+        rc = getattr(lib(), entry)(self._h, *map(ctypes.byref, cfgs), *map(int, dims), *lead,
+                                   *[q for spec, arrays in specs for q in _dev_ptrs(spec, arrays)], stream or None)
+        if rc != 0:
+            self._err(rc, entry)
+
+    def _loop_host(self, entry, cfgs, k0, steps, rows, lead, state_spec, state, logs_spec, logs, **sizes):
+        """A host rollout entry: ``lead`` is the (array, width) pairs of the leading inputs, [B, width] each."""
+        B = state["x"].shape[0]
+        lead = [np.ascontiguousarray(a, np.float64).reshape(_loop_shape(B, width)) for a, width in lead]
+        rc = getattr(lib(), entry)(self._h, *map(ctypes.byref, cfgs), B, int(k0), int(steps), rows, *map(_ptr, lead),
+                                   *_host_ptrs(state_spec, state, (B,), **sizes),
+                                   *_host_ptrs(logs_spec, logs, (rows, B)), None)
+        if rc != 0:
+            self._err(rc, entry)
+
+    # -- dart_pmpc_loop_step_dev / dart_pmpc_rollout_dev / dart_pmpc_rollout ----
     def loop_step_dev(self, B, k, do_post, do_pre, log_rows, prm, state, io, logs, plant=None, stream=0):
         """One loop-step launch: post(k) and / or the next step's pre.  ``state`` / ``io`` / ``logs`` map the names
         of PMPC_LOOP_STATE / PMPC_LOOP_IO / PMPC_LOOP_LOGS to device pointers (ints).  Asynchronous."""
-        plant = plant or plant_config()
-        rc = lib().dart_pmpc_loop_step_dev(self._h, ctypes.byref(plant), int(B), int(k), int(do_post), int(do_pre),
-                                           int(log_rows), prm, *_dev_ptrs(PMPC_LOOP_STATE, state),
-                                           *_dev_ptrs(PMPC_LOOP_IO, io), *_dev_ptrs(PMPC_LOOP_LOGS, logs), stream or None)
-        if rc != 0:
-            self._err(rc, "dart_pmpc_loop_step_dev")
+        self._loop_dev("dart_pmpc_loop_step_dev", (plant or plant_config(),), (B, k, do_post, do_pre, log_rows), (prm,),
+                       ((PMPC_LOOP_STATE, state), (PMPC_LOOP_IO, io), (PMPC_LOOP_LOGS, logs)), stream)
 
     def rollout_dev(self, B, k0, steps, log_rows, target, prm, state, logs, plant=None, stream=0):
         """``steps`` closed-loop steps from step ``k0`` on the device, no host synchronisation in between
         (device pointers as in ``loop_step_dev``; asynchronous on ``stream``)."""
-        plant = plant or plant_config()
-        rc = lib().dart_pmpc_rollout_dev(self._h, ctypes.byref(plant), int(B), int(k0), int(steps), int(log_rows),
-                                         target, prm, *_dev_ptrs(PMPC_LOOP_STATE, state),
-                                         *_dev_ptrs(PMPC_LOOP_LOGS, logs), stream or None)
-        if rc != 0:
-            self._err(rc, "dart_pmpc_rollout_dev")
+        self._loop_dev("dart_pmpc_rollout_dev", (plant or plant_config(),), (B, k0, steps, log_rows), (target, prm),
+                       ((PMPC_LOOP_STATE, state), (PMPC_LOOP_LOGS, logs)), stream)
 
     def rollout(self, k0, steps, target, prm, state, logs, plant=None):
         """Host arrays (blocking): ``state`` (PMPC_LOOP_STATE) is advanced and ``logs`` (``loop_logs``) rows
         k0 .. k0+steps-1 are filled in place."""
-        x = state["x"]
-        B, rows = x.shape[0], logs["X"].shape[0]
-        c = lambda a: np.ascontiguousarray(a, np.float64).reshape(B, 6)
-        target, prm = c(target), c(prm)
-        plant = plant or plant_config()
-        rc = lib().dart_pmpc_rollout(self._h, ctypes.byref(plant), B, int(k0), int(steps), rows, _ptr(target), _ptr(prm),
-                                     *_host_ptrs(PMPC_LOOP_STATE, state, (B,)),
-                                     *_host_ptrs(PMPC_LOOP_LOGS, logs, (rows, B)), None)
-        if rc != 0:
-            self._err(rc, "dart_pmpc_rollout")
+        self._loop_host("dart_pmpc_rollout", (plant or plant_config(),), k0, steps, logs["X"].shape[0],
+                        ((target, 6), (prm, 6)), PMPC_LOOP_STATE, state, PMPC_LOOP_LOGS, logs)
 
     # -- the same loop on the LMPC plant (dart_pmpc_lm_loop_step_dev / dart_pmpc_lm_rollout_dev / dart_pmpc_lm_rollout) ----
     def loop_step_lm_dev(self, B, k, do_post, do_pre, log_rows, target, plant_pvec, pz_vz, state, io, logs, plant=None,
                          stream=0):
         """``loop_step_dev`` on the LMPC plant: ``state`` maps PMPC_LM_LOOP_STATE, ``logs`` PMPC_LM_LOOP_LOGS (None:
         metrics-only) to device pointers."""
-        plant = plant or plant_config()
-        rc = lib().dart_pmpc_lm_loop_step_dev(self._h, ctypes.byref(plant), int(B), int(k), int(do_post), int(do_pre),
-                                              int(log_rows), target, plant_pvec, pz_vz,
-                                              *_dev_ptrs(PMPC_LM_LOOP_STATE, state), *_dev_ptrs(PMPC_LOOP_IO, io),
-                                              *_dev_ptrs(PMPC_LM_LOOP_LOGS, logs), stream or None)
-        if rc != 0:
-            self._err(rc, "dart_pmpc_lm_loop_step_dev")
+        self._loop_dev("dart_pmpc_lm_loop_step_dev", (plant or plant_config(),), (B, k, do_post, do_pre, log_rows),
+                       (target, plant_pvec, pz_vz),
+                       ((PMPC_LM_LOOP_STATE, state), (PMPC_LOOP_IO, io), (PMPC_LM_LOOP_LOGS, logs)), stream)
 
     def rollout_lm_dev(self, B, k0, steps, log_rows, target, prm, plant_pvec, pz_vz, state, logs, plant=None, stream=0):
         """``rollout_dev`` on the LMPC plant with the true parameters ``plant_pvec`` [B, 34]: ``state`` maps
         PMPC_LM_LOOP_STATE (x [B, 8], tilt, metrics [B, 8], see ``loop_metrics``), ``logs`` PMPC_LM_LOOP_LOGS to device
         pointers; ``logs`` None is the metrics-only mode (no log row is written)."""
-        plant = plant or plant_config()
-        rc = lib().dart_pmpc_lm_rollout_dev(self._h, ctypes.byref(plant), int(B), int(k0), int(steps), int(log_rows),
-                                            target, prm, plant_pvec, pz_vz, *_dev_ptrs(PMPC_LM_LOOP_STATE, state),
-                                            *_dev_ptrs(PMPC_LM_LOOP_LOGS, logs), stream or None)
-        if rc != 0:
-            self._err(rc, "dart_pmpc_lm_rollout_dev")
+        self._loop_dev("dart_pmpc_lm_rollout_dev", (plant or plant_config(),), (B, k0, steps, log_rows),
+                       (target, prm, plant_pvec, pz_vz), ((PMPC_LM_LOOP_STATE, state), (PMPC_LM_LOOP_LOGS, logs)), stream)
 
     def rollout_lm(self, k0, steps, target, prm, plant_pvec, pz_vz, state, logs, plant=None):
         """Host arrays (blocking): ``state`` (PMPC_LM_LOOP_STATE) is advanced and ``logs`` (``loop_logs`` of
         PMPC_LM_LOOP_LOGS) rows k0 .. k0+steps-1 are filled in place; ``logs`` None moves no log."""
-        B = state["x"].shape[0]
-        rows = logs["X"].shape[0] if logs is not None else 0
-        c = lambda a, n: np.ascontiguousarray(a, np.float64).reshape(B, n)
-        target, prm, plant_pvec, pz_vz = c(target, 6), c(prm, 6), c(plant_pvec, 34), c(pz_vz, 2)
-        plant = plant or plant_config()
-        rc = lib().dart_pmpc_lm_rollout(self._h, ctypes.byref(plant), B, int(k0), int(steps), rows, _ptr(target), _ptr(prm),
-                                        _ptr(plant_pvec), _ptr(pz_vz), *_host_ptrs(PMPC_LM_LOOP_STATE, state, (B,)),
-                                        *_host_ptrs(PMPC_LM_LOOP_LOGS, logs, (rows, B)), None)
-        if rc != 0:
-            self._err(rc, "dart_pmpc_lm_rollout")
+        self._loop_host("dart_pmpc_lm_rollout", (plant or plant_config(),), k0, steps,
+                        logs["X"].shape[0] if logs is not None else 0,
+                        ((target, 6), (prm, 6), (plant_pvec, 34), (pz_vz, 2)), PMPC_LM_LOOP_STATE, state,
+                        PMPC_LM_LOOP_LOGS, logs)
 
     def sync(self):
         rc = lib().dart_mpc_sync(self._h)
@@ -958,81 +948,52 @@ class RmpcSolver(Solver):
                       stream=0):
         """One loop-step launch: post(k) and / or the next step's pre.  ``state`` / ``io`` / ``logs`` map the names
         of RMPC_LOOP_STATE (P and w are not needed) / RMPC_LOOP_IO / RMPC_LOOP_LOGS to device pointers (ints)."""
-        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
         spec = tuple(e for e in RMPC_LOOP_STATE if e[0] not in ("P", "w"))
-        rc = lib().dart_rmpc_loop_step_dev(self._h, ctypes.byref(plant), ctypes.byref(loop), int(B), int(k), int(do_post),
-                                           int(do_pre), int(log_rows), target, prm, mu, *_dev_ptrs(spec, state),
-                                           *_dev_ptrs(RMPC_LOOP_IO, io), *_dev_ptrs(RMPC_LOOP_LOGS, logs), stream or None)
-        if rc != 0:
-            self._err(rc, "dart_rmpc_loop_step_dev")
+        self._loop_dev("dart_rmpc_loop_step_dev", (plant or plant_config(), loop or rmpc_loop_config()),
+                       (B, k, do_post, do_pre, log_rows), (target, prm, mu),
+                       ((spec, state), (RMPC_LOOP_IO, io), (RMPC_LOOP_LOGS, logs)), stream)
 
     def rollout_dev(self, B, k0, steps, log_rows, target, prm, mu, state, logs, plant=None, loop=None, stream=0):
         """``steps`` closed-loop steps from step ``k0`` on the device, no host synchronisation in between: RLS
         features, governor, staged reference, warm-started solve with the fused RLS update, logs, plant step
         (device pointers as in ``loop_step_dev``; asynchronous on ``stream``).  Calling again with ``k0`` advanced
         continues the rollout."""
-        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
-        rc = lib().dart_rmpc_rollout_dev(self._h, ctypes.byref(plant), ctypes.byref(loop), int(B), int(k0), int(steps),
-                                         int(log_rows), target, prm, mu, *_dev_ptrs(RMPC_LOOP_STATE, state),
-                                         *_dev_ptrs(RMPC_LOOP_LOGS, logs), stream or None)
-        if rc != 0:
-            self._err(rc, "dart_rmpc_rollout_dev")
+        self._loop_dev("dart_rmpc_rollout_dev", (plant or plant_config(), loop or rmpc_loop_config()),
+                       (B, k0, steps, log_rows), (target, prm, mu), ((RMPC_LOOP_STATE, state), (RMPC_LOOP_LOGS, logs)),
+                       stream)
 
     def rollout(self, k0, steps, target, prm, mu, state, logs, plant=None, loop=None):
         """Host arrays (blocking): ``state`` (RMPC_LOOP_STATE, see ``loop_state``) is advanced and ``logs``
         (``loop_logs``) are filled in place."""
-        B, rows = state["x"].shape[0], logs["x"].shape[0]
-        target = np.ascontiguousarray(target, np.float64).reshape(B, 4)
-        prm = np.ascontiguousarray(prm, np.float64).reshape(B, 10)
-        mu = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, np.float64), (B,)))
-        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
-        rc = lib().dart_rmpc_rollout(self._h, ctypes.byref(plant), ctypes.byref(loop), B, int(k0), int(steps), rows,
-                                     _ptr(target), _ptr(prm), _ptr(mu),
-                                     *_host_ptrs(RMPC_LOOP_STATE, state, (B,), nw=self.nw),
-                                     *_host_ptrs(RMPC_LOOP_LOGS, logs, (rows, B)), None)
-        if rc != 0:
-            self._err(rc, "dart_rmpc_rollout")
+        mu = np.broadcast_to(np.asarray(mu, np.float64), (state["x"].shape[0],))
+        self._loop_host("dart_rmpc_rollout", (plant or plant_config(), loop or rmpc_loop_config()), k0, steps,
+                        logs["x"].shape[0], ((target, 4), (prm, 10), (mu, 0)), RMPC_LOOP_STATE, state, RMPC_LOOP_LOGS,
+                        logs, nw=self.nw)
 
     # -- the same loop on the LMPC plant (dart_rmpc_lm_loop_step_dev / dart_rmpc_lm_rollout_dev / dart_rmpc_lm_rollout) ----
     def loop_step_lm_dev(self, B, k, do_post, do_pre, log_rows, target, prm, plant_pvec, state, io, logs, plant=None,
                          loop=None, stream=0):
         """``loop_step_dev`` on the LMPC plant: ``state`` maps RMPC_LM_LOOP_STATE (P and w are not needed), ``logs``
         RMPC_LM_LOOP_LOGS (None: metrics-only) to device pointers."""
-        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
         spec = tuple(e for e in RMPC_LM_LOOP_STATE if e[0] not in ("P", "w"))
-        rc = lib().dart_rmpc_lm_loop_step_dev(self._h, ctypes.byref(plant), ctypes.byref(loop), int(B), int(k), int(do_post),
-                                              int(do_pre), int(log_rows), target, prm, plant_pvec, *_dev_ptrs(spec, state),
-                                              *_dev_ptrs(RMPC_LOOP_IO, io), *_dev_ptrs(RMPC_LM_LOOP_LOGS, logs),
-                                              stream or None)
-        if rc != 0:
-            self._err(rc, "dart_rmpc_lm_loop_step_dev")
+        self._loop_dev("dart_rmpc_lm_loop_step_dev", (plant or plant_config(), loop or rmpc_loop_config()),
+                       (B, k, do_post, do_pre, log_rows), (target, prm, plant_pvec),
+                       ((spec, state), (RMPC_LOOP_IO, io), (RMPC_LM_LOOP_LOGS, logs)), stream)
 
     def rollout_lm_dev(self, B, k0, steps, log_rows, target, prm, plant_pvec, state, logs, plant=None, loop=None, stream=0):
         """``rollout_dev`` on the LMPC plant with the true parameters ``plant_pvec`` [B, 34]: ``state`` maps
         RMPC_LM_LOOP_STATE (x [B, 8], ..., metrics [B, 8]), ``logs`` RMPC_LM_LOOP_LOGS to device pointers; ``logs`` None
         is the metrics-only mode (done / nlog still advance)."""
-        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
-        rc = lib().dart_rmpc_lm_rollout_dev(self._h, ctypes.byref(plant), ctypes.byref(loop), int(B), int(k0), int(steps),
-                                            int(log_rows), target, prm, plant_pvec, *_dev_ptrs(RMPC_LM_LOOP_STATE, state),
-                                            *_dev_ptrs(RMPC_LM_LOOP_LOGS, logs), stream or None)
-        if rc != 0:
-            self._err(rc, "dart_rmpc_lm_rollout_dev")
+        self._loop_dev("dart_rmpc_lm_rollout_dev", (plant or plant_config(), loop or rmpc_loop_config()),
+                       (B, k0, steps, log_rows), (target, prm, plant_pvec),
+                       ((RMPC_LM_LOOP_STATE, state), (RMPC_LM_LOOP_LOGS, logs)), stream)
 
     def rollout_lm(self, k0, steps, target, prm, plant_pvec, state, logs, plant=None, loop=None):
         """Host arrays (blocking): ``state`` (RMPC_LM_LOOP_STATE, see ``loop_state_lm``) is advanced and ``logs``
         (``loop_logs`` of RMPC_LM_LOOP_LOGS) are filled in place; ``logs`` None moves no log."""
-        B = state["x"].shape[0]
-        rows = logs["x"].shape[0] if logs is not None else 0
-        target = np.ascontiguousarray(target, np.float64).reshape(B, 4)
-        prm = np.ascontiguousarray(prm, np.float64).reshape(B, 10)
-        plant_pvec = np.ascontiguousarray(plant_pvec, np.float64).reshape(B, 34)
-        plant, loop = plant or plant_config(), loop or rmpc_loop_config()
-        rc = lib().dart_rmpc_lm_rollout(self._h, ctypes.byref(plant), ctypes.byref(loop), B, int(k0), int(steps), rows,
-                                        _ptr(target), _ptr(prm), _ptr(plant_pvec),
-                                        *_host_ptrs(RMPC_LM_LOOP_STATE, state, (B,), nw=self.nw),
-                                        *_host_ptrs(RMPC_LM_LOOP_LOGS, logs, (rows, B)), None)
-        if rc != 0:
-            self._err(rc, "dart_rmpc_lm_rollout")
+        self._loop_host("dart_rmpc_lm_rollout", (plant or plant_config(), loop or rmpc_loop_config()), k0, steps,
+                        logs["x"].shape[0] if logs is not None else 0, ((target, 4), (prm, 10), (plant_pvec, 34)),
+                        RMPC_LM_LOOP_STATE, state, RMPC_LM_LOOP_LOGS, logs, nw=self.nw)
 
     def loop_state_lm(self, x0, x_rot0=None, P0=1e3):
         """The state of a fresh cross-plant rollout from the measured states ``x0`` [B, 4] and the rotation states

@@ -1,5 +1,5 @@
-"""The PMPC and RMPC closed loops on the LMPC plant, with streaming metrics (csrc/loop_step.hip pmpc_lm_loop_kernel /
-rmpc_lm_loop_kernel, dart_pmpc_lm_* / dart_rmpc_lm_*).
+"""The PMPC and RMPC closed loops on the LMPC plant, with streaming metrics (csrc/loop_step.hip pmpc_loop_kernel<true> /
+rmpc_loop_kernel<true>, dart_pmpc_lm_* / dart_rmpc_lm_*).
 
 Bars:
   * one loop step against the numpy code it restates (harness.LmpcPlant.step with -u, rollout_metrics, the RMPC glue
@@ -24,12 +24,13 @@ the first 4 rows ends at status 0 (18 rows: 718 of 720; the velocity cap binds t
 import numpy as np
 import pytest
 
+from loop_harness import (RMPC_PRM, TS, X_LO, L, torch, _bits, _close, _host, _metrics_midrun, _nan_io, _ptrs,  # noqa: F401
+                          _rmpc_case, _rmpc_expected, _same, _to_dev)
+from loop_harness import _lm_step as _plant_step
+
 pytestmark = pytest.mark.gpu
 
-TS = 0.002
 N = 10
-RMPC_PRM = np.array([80.0, 2.0, 0.02, 1.0, -0.6, 0.6, -0.06, 0.06, 0.2, 0.1])       # rob_ctrl.py:280-283
-X_LO = np.array([-0.18, -0.15, -0.13, -0.15, -0.05, -0.05, -0.05, -0.05])       # workload.lmpc_batch's state ranges
 
 # largest differences between the resident loops and the host loops (harness.run_pmpc / run_rmpc with plant_pvec) over
 # 40 steps x 4 experiments, and between the point-mass LMPC plant and the tray plant in closed loop over 40 steps x 18
@@ -39,18 +40,6 @@ MEASURED_PMPC_DX = 0.0
 MEASURED_RMPC_DU_CMD = 6.120e-15
 MEASURED_RMPC_DPOS_ERR = 2.776e-17
 MEASURED_REDUCTION_DU_CMD = 4.721e-08
-
-
-@pytest.fixture(scope="module")
-def L():
-    from dart_mpc import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -72,74 +61,6 @@ def lmpc_solver(L):
     s = L.LmpcSolver(N=N, Ts=TS, B_max=70)
     yield s
     s.close()
-
-
-def _to_dev(torch, arrays):
-    d = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in arrays.items()}
-    torch.cuda.synchronize()
-    return d
-
-
-def _ptrs(d):
-    return None if d is None else {k: v.data_ptr() for k, v in d.items()}
-
-
-def _host(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
-def _same(torch, a, b):
-    """Bit-for-bit equality (NaN prefill included)."""
-    if a.dtype == torch.float64:
-        return torch.equal(a.view(torch.int64), b.view(torch.int64))
-    return torch.equal(a, b)
-
-
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _shape(B, width, **sizes):
-    width = sizes[width] if isinstance(width, str) else width
-    return (B, width) if width else (B,)
-
-
-def _nan_io(L, spec, B, **sizes):
-    return {n: (np.full(_shape(B, w, **sizes), np.nan) if dt is np.float64 else np.full(B, L.LOG_INT_FILL, np.int32))
-            for n, w, dt in spec}
-
-
-def _close(got, want, what):
-    """|got - want| <= 1e-13 with the NaN prefill in the same places (floats); equality (ints)."""
-    worst = 0.0
-    for k in want:
-        if want[k].dtype == np.float64:
-            assert np.array_equal(np.isnan(got[k]), np.isnan(want[k])), f"{what}: {k} (prefill)"
-            if np.isfinite(want[k]).any():
-                worst = max(worst, float(np.nanmax(np.abs(got[k] - want[k]))))
-            np.testing.assert_allclose(got[k], want[k], rtol=0, atol=1e-13, equal_nan=True, err_msg=f"{what}: {k}")
-        else:
-            np.testing.assert_array_equal(got[k], want[k], err_msg=f"{what}: {k}")
-    return worst
-
-
-def _metrics_midrun(L, B):
-    """Metrics of a fresh run (even instances) and of runs under way (odd: not yet converged; every fourth: converged
-    at step 0)."""
-    m = L.loop_metrics(B)
-    odd = np.arange(B) % 2 == 1
-    m[odd] = [0.03, -1.0, 0.2, 0.09, 2.0, 55.0, 0.02, 7.0]
-    m[np.arange(B) % 4 == 3, 1] = 0.0
-    return m
-
-
-def _plant_step(harness, x8, tilt, u, pvec):
-    """harness.LmpcPlant.step with the flipped command: (next x, next tilt in the PMPC / RMPC convention)."""
-    plant = harness.LmpcPlant(x8, pvec, dt=TS)          # tau 0.03, as dart_plant_config's default
-    plant.tilt = -tilt
-    xn = plant.step(-u)
-    return xn, -plant.tilt
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -205,69 +126,16 @@ def test_pmpc_lm_loop_step_matches_numpy(L, torch, pmpc_solver, B, do_post, do_p
     assert np.all(g["status"][untouched] == L.LOG_INT_FILL)
 
 
-def _rmpc_case(L, rng, B):
-    x = rng.uniform(X_LO, -X_LO, (B, 8))
-    state = dict(x=x, tilt=rng.uniform(-0.3, 0.3, (B, 2)), prev=x[:, :4] + rng.uniform(-1e-3, 1e-3, (B, 4)),
-                 u_prev=rng.uniform(-0.5, 0.5, (B, 2)), r_v=rng.uniform(-0.1, 0.1, (B, 4)),
-                 theta=rng.uniform(-1, 1, (B, 14)), done=(rng.uniform(size=B) < 0.3).astype(np.int32),
-                 nlog=rng.integers(0, 3, B).astype(np.int32), metrics=_metrics_midrun(L, B))
-    target = np.zeros((B, 4)); target[:, [0, 2]] = rng.uniform(-0.1, 0.1, (B, 2))
-    near = np.arange(B) % 4 == 1            # within the tolerance: the episode closes at this step
-    target[near, 0] = x[near, 0] + 1e-3; target[near, 2] = x[near, 2] - 2e-3
-    io = _nan_io(L, L.RMPC_LOOP_IO, B, nref=4 * (N + 1))
-    io.update(u0=rng.uniform(-0.5, 0.5, (B, 2)), f=rng.uniform(0, 1, B), status=rng.integers(-2, 3, B).astype(np.int32),
-              iters=rng.integers(1, 60, B).astype(np.int32))
-    return state, target, np.tile(RMPC_PRM, (B, 1)), rng.uniform(0.01, 1.9, (B, 34)), io
-
-
-def _rmpc_expected(L, harness, state, target, prm, pvec, io, logs, k, do_post, do_pre):
-    from dart_mpc.rmpc import AdaptiveNPMPCSmooth, rls_features
-    s = {n: v.copy() for n, v in state.items()}
-    io = {n: v.copy() for n, v in io.items()}
-    lg = None if logs is None else {n: v.copy() for n, v in logs.items()}
-    B = s["x"].shape[0]
-    c = L.rmpc_loop_config()
-    if do_post:
-        xk, u = s["x"][:, :4].copy(), io["u0"]
-        en = np.linalg.norm(xk[:, [0, 2]] - target[:, [0, 2]], axis=1)
-        for b in np.where(s["done"] == 0)[0]:
-            r = s["nlog"][b]
-            if lg is not None:
-                lg["pos_err"][r, b] = [target[b, 0] - xk[b, 0], target[b, 2] - xk[b, 2]]
-                lg["pos_err_norm"][r, b] = float(en[b])
-                lg["u_cmd"][r, b] = u[b]
-                lg["timestep"][r, b] = k * TS
-            s["nlog"][b] += 1
-            if en[b] < c.pos_tol:
-                s["done"][b] = 1
-        if lg is not None:
-            lg["x"][k], lg["theta"][k], lg["r_v"][k], lg["rot"][k] = xk, s["theta"], s["r_v"], s["x"][:, 4:]
-            lg["f"][k], lg["status"][k], lg["iters"][k] = io["f"], io["status"], io["iters"]
-        s["metrics"] = harness.rollout_metrics(xk[None], target, u[None], io["status"][None], io["iters"][None],
-                                               s["x"][None, :, 4:], TS, metrics=s["metrics"], k0=k)
-        s["prev"], s["u_prev"] = xk, u.copy()
-        s["x"], s["tilt"] = _plant_step(harness, s["x"], s["tilt"], u, pvec)
-    if do_pre:
-        xk, prev = s["x"][:, :4].copy(), s["prev"]
-        io["y"] = (xk[:, [1, 3]] - prev[:, [1, 3]]) / TS
-        io["phi"] = np.stack([rls_features(p, prm[0, 9]) for p in prev])
-        err = np.stack([target[:, 0] - s["r_v"][:, 0], np.zeros(B), target[:, 2] - s["r_v"][:, 2], np.zeros(B)], axis=1)
-        s["r_v"] = s["r_v"] + c.alpha_rg * np.clip(err, -c.dr_max, c.dr_max) * np.array([1.0, 0.0, 1.0, 0.0])
-        io["Rref"] = np.stack([AdaptiveNPMPCSmooth.build_ref_traj(xk[b], s["r_v"][b], target[b], N, 4, step_fraction=0.2)
-                               for b in range(B)])
-        io["x0"] = xk
-    return s, io, lg
-
-
 @pytest.mark.parametrize("do_post,do_pre", [(1, 0), (0, 1), (1, 1)])
 @pytest.mark.parametrize("B", [1, 5, 70])
 def test_rmpc_lm_loop_step_matches_numpy(L, torch, rmpc_solver, B, do_post, do_pre):
     from dart_mpc import harness
     rng = np.random.default_rng(5200 + 10 * B + 2 * do_post + do_pre)
-    state, target, prm, pvec, io = _rmpc_case(L, rng, B)
+    state, target, prm, pvec, io = _rmpc_case(L, rng, B, N, lm=True)
     rows, k = 4, 3
     logs = L.loop_logs(L.RMPC_LM_LOOP_LOGS, rows, B)
-    want = _rmpc_expected(L, harness, state, target, prm, pvec, io, logs, k, do_post, do_pre)
+    want = _rmpc_expected(L, harness, state, target, prm, lambda x, tilt, u: _plant_step(harness, x, tilt, u, pvec),
+                          io, logs, N, k, do_post, do_pre)
     ds, dio, dl = _to_dev(torch, state), _to_dev(torch, io), _to_dev(torch, logs)
     c = _to_dev(torch, dict(target=target, prm=prm, pvec=pvec))
     rmpc_solver.loop_step_lm_dev(B, k, do_post, do_pre, rows, c["target"].data_ptr(), c["prm"].data_ptr(),
@@ -308,8 +176,9 @@ def test_loop_steps_in_metrics_only_mode(L, torch, pmpc_solver, rmpc_solver, do_
         for n in a:
             assert _same(torch, a[n], b[n]), n
 
-    state, target, prm, pvec, io = _rmpc_case(L, rng, B)
-    want = _rmpc_expected(L, harness, state, target, prm, pvec, io, None, k, do_post, do_pre)
+    state, target, prm, pvec, io = _rmpc_case(L, rng, B, N, lm=True)
+    want = _rmpc_expected(L, harness, state, target, prm, lambda x, tilt, u: _plant_step(harness, x, tilt, u, pvec),
+                          io, None, N, k, do_post, do_pre)
     c = _to_dev(torch, dict(target=target, prm=prm, pvec=pvec))
     cp = (c["target"].data_ptr(), c["prm"].data_ptr(), c["pvec"].data_ptr())
     ds, dio = _to_dev(torch, state), _to_dev(torch, io)
@@ -350,7 +219,7 @@ def test_plant_step_is_bitwise_the_lmpc_loop_steps(L, torch, pmpc_solver, rmpc_s
                                  _ptrs(dps), _ptrs(dpio), None)
     pmpc_solver.sync()
     # RMPC's post, same x, tilt and command
-    rs, _, _, _, rio = _rmpc_case(L, rng, B)
+    rs, _, _, _, rio = _rmpc_case(L, rng, B, N, lm=True)
     rs.update(x=x, tilt=tilt)
     rio.update(u0=u)
     drs, drio = _to_dev(torch, rs), _to_dev(torch, rio)
@@ -361,6 +230,56 @@ def test_plant_step_is_bitwise_the_lmpc_loop_steps(L, torch, pmpc_solver, rmpc_s
     for what, d in (("PMPC", dps), ("RMPC", drs)):
         assert _same(torch, d["x"], ls["x"]), what
         assert _same(torch, d["tilt"], -ls["tilt"]), what
+
+
+def test_glue_is_the_same_on_both_plants(L, torch, pmpc_solver):
+    """The two instantiations of each glue kernel, given the same x[:, :4], prev, r_v, theta, done, nlog, target, prm
+    and solve outputs, write the same bits to everything that does not pass through the plant step: from a pre-only
+    launch the next solve's inputs and r_v, from a post + pre launch the episode and step rows and what the post
+    hands to the next step.  RMPC at B = 5 (two blocks) with N = 1 and N = 63 (the ends of the staged reference's
+    lanes), PMPC at B = 5; no solve runs."""
+    B, rows, k = 5, 4, 3
+    for N in (1, 63):
+        with L.RmpcSolver(N=N, Ts=TS, B_max=B) as s:
+            for do_post, do_pre in ((0, 1), (1, 1)):
+                rng = np.random.default_rng(8800 + 10 * N + do_post)
+                lm_state, target, prm, pvec, io = _rmpc_case(L, rng, B, N, lm=True)
+                tray_state = {n: v for n, v in lm_state.items() if n != "metrics"}
+                tray_state["x"] = np.concatenate([lm_state["x"][:, :4], np.full((B, 1), 0.43), np.zeros((B, 1))], axis=1)
+                c = _to_dev(torch, dict(target=target, prm=prm, pvec=pvec, mu=rng.uniform(0.05, 0.3, B)))
+                ts, tio, tl = (_to_dev(torch, d) for d in (tray_state, io, L.loop_logs(L.RMPC_LOOP_LOGS, rows, B)))
+                ls, lio, ll = (_to_dev(torch, d) for d in (lm_state, io, L.loop_logs(L.RMPC_LM_LOOP_LOGS, rows, B)))
+                s.loop_step_dev(B, k, do_post, do_pre, rows, c["target"].data_ptr(), c["prm"].data_ptr(), c["mu"].data_ptr(),
+                                _ptrs(ts), _ptrs(tio), _ptrs(tl))
+                s.loop_step_lm_dev(B, k, do_post, do_pre, rows, c["target"].data_ptr(), c["prm"].data_ptr(),
+                                   c["pvec"].data_ptr(), _ptrs(ls), _ptrs(lio), _ptrs(ll))
+                s.sync()
+                if do_post:
+                    pairs = [(tl[n], ll[n], "log " + n) for n, _, _ in L.RMPC_LOOP_LOGS]
+                    pairs += [(ts[n], ls[n], n) for n in ("prev", "u_prev", "done", "nlog")]
+                    assert not torch.isnan(tl["x"][k]).any() and not torch.isnan(tl["u_cmd"]).all()
+                    assert not torch.equal(ts["nlog"], torch.from_numpy(tray_state["nlog"]).cuda())
+                else:
+                    pairs = [(tio[n], lio[n], n) for n in ("x0", "Rref", "phi", "y")] + [(ts["r_v"], ls["r_v"], "r_v")]
+                    assert not torch.isnan(tio["Rref"]).any() and not torch.isnan(tio["phi"]).any()
+                for a, b, what in pairs:
+                    assert _same(torch, a, b), (N, do_post, do_pre, what)
+
+    rng = np.random.default_rng(8900)
+    lm_state, target, pvec, pz_vz, io = _pmpc_case(L, rng, B)
+    tray_state = dict(x=np.concatenate([lm_state["x"][:, :4], pz_vz], axis=1), tilt=lm_state["tilt"])
+    prm = np.tile([0.4, 100.0, 0.0, 0.1, -0.5, 0.5], (B, 1))
+    c = _to_dev(torch, dict(target=target, prm=prm, pvec=pvec, pz_vz=pz_vz))
+    ts, tio, tl = (_to_dev(torch, d) for d in (tray_state, io, L.loop_logs(L.PMPC_LOOP_LOGS, rows, B)))
+    ls, lio, ll = (_to_dev(torch, d) for d in (lm_state, io, L.loop_logs(L.PMPC_LM_LOOP_LOGS, rows, B)))
+    pmpc_solver.loop_step_dev(B, k, 1, 1, rows, c["prm"].data_ptr(), _ptrs(ts), _ptrs(tio), _ptrs(tl))
+    pmpc_solver.loop_step_lm_dev(B, k, 1, 1, rows, c["target"].data_ptr(), c["pvec"].data_ptr(), c["pz_vz"].data_ptr(),
+                                 _ptrs(ls), _ptrs(lio), _ptrs(ll))
+    pmpc_solver.sync()
+    for n in ("U_cmd", "quat_tray", "loss", "status", "iters"):
+        assert _same(torch, tl[n], ll[n]), n
+    assert _same(torch, tl["X"][:, :, :4].contiguous(), ll["X"][:, :, :4].contiguous())
+    assert not torch.isnan(tl["quat_tray"][k]).any() and not torch.isnan(tl["X"][k]).any()
 
 
 # ------------------------------------------------------------------------------------------------------------------

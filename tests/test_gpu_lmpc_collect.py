@@ -20,6 +20,8 @@ import sys
 import numpy as np
 import pytest
 
+from loop_harness import _host, _ptrs, _same, _to_dev
+
 pytestmark = pytest.mark.gpu
 
 TS = 0.002
@@ -50,29 +52,6 @@ def solvers(L):
     yield get
     for s in made.values():
         s.close()
-
-
-def _to_dev(torch, arrays):
-    d = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in arrays.items()}
-    torch.cuda.synchronize()
-    return d
-
-
-def _ptrs(d):
-    return {k: v.data_ptr() for k, v in d.items()}
-
-
-def _host(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
-def _same(torch, a, b):
-    """Bit-for-bit equality (NaN prefill included)."""
-    if a.dtype == torch.float64:
-        return torch.equal(a.view(torch.int64), b.view(torch.int64))
-    if a.dtype == torch.float32:
-        return torch.equal(a.view(torch.int32), b.view(torch.int32))
-    return torch.equal(a, b)
 
 
 def _biased(w, sl, rng, scale=0.1):

@@ -21,22 +21,10 @@ import pytest
 import oracle_lib
 import rmpc_nlp
 
+from loop_harness import (RMPC_PRM, TS, L, torch, _close, _host, _nan_io, _ptrs, _rmpc_case, _rmpc_expected,  # noqa: F401
+                          _same, _to_dev, _tray_step)
+
 pytestmark = pytest.mark.gpu
-
-TS = 0.002
-RMPC_PRM = np.array([80.0, 2.0, 0.02, 1.0, -0.6, 0.6, -0.06, 0.06, 0.2, 0.1])       # rob_ctrl.py:280-283
-
-
-@pytest.fixture(scope="module")
-def L():
-    from dart_mpc import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -60,101 +48,8 @@ def pmpc_solver(L):
     s.close()
 
 
-def _to_dev(torch, arrays):
-    d = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in arrays.items()}
-    torch.cuda.synchronize()
-    return d
-
-
-def _ptrs(d):
-    return {k: v.data_ptr() for k, v in d.items()}
-
-
-def _host(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
-def _same(torch, a, b):
-    """Bit-for-bit equality (NaN prefill included)."""
-    if a.dtype == torch.float64:
-        return torch.equal(a.view(torch.int64), b.view(torch.int64))
-    return torch.equal(a, b)
-
-
-def _shape(B, width, **sizes):
-    width = sizes[width] if isinstance(width, str) else width
-    return (B, width) if width else (B,)
-
-
-def _nan_io(L, spec, B, **sizes):
-    return {n: (np.full(_shape(B, w, **sizes), np.nan) if dt is np.float64 else np.full(B, L.LOG_INT_FILL, np.int32))
-            for n, w, dt in spec}
-
-
-def _close(got, want, what):
-    """|got - want| <= 1e-13 with the NaN prefill in the same places (floats); equality (ints)."""
-    for k in want:
-        if want[k].dtype == np.float64:
-            np.testing.assert_allclose(got[k], want[k], rtol=0, atol=1e-13, equal_nan=True, err_msg=f"{what}: {k}")
-        else:
-            np.testing.assert_array_equal(got[k], want[k], err_msg=f"{what}: {k}")
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # Test 1: one loop-step launch against numpy
-def _rmpc_case(L, rng, B, N):
-    x = np.zeros((B, 6)); x[:, :4] = rng.uniform(-0.3, 0.3, (B, 4)); x[:, 4] = 0.43
-    state = dict(x=x, tilt=rng.uniform(-0.3, 0.3, (B, 2)), prev=x[:, :4] + rng.uniform(-1e-3, 1e-3, (B, 4)),
-                 u_prev=rng.uniform(-0.5, 0.5, (B, 2)), r_v=rng.uniform(-0.1, 0.1, (B, 4)),
-                 theta=rng.uniform(-1, 1, (B, 14)), done=(rng.uniform(size=B) < 0.3).astype(np.int32),
-                 nlog=rng.integers(0, 3, B).astype(np.int32))
-    target = np.zeros((B, 4)); target[:, [0, 2]] = rng.uniform(-0.1, 0.1, (B, 2))
-    near = np.arange(B) % 4 == 1            # within the tolerance: the episode closes at this step
-    target[near, 0] = x[near, 0] + 1e-3; target[near, 2] = x[near, 2] - 2e-3
-    io = _nan_io(L, L.RMPC_LOOP_IO, B, nref=4 * (N + 1))
-    io.update(u0=rng.uniform(-0.5, 0.5, (B, 2)), f=rng.uniform(0, 1, B), status=rng.integers(-2, 3, B).astype(np.int32),
-              iters=rng.integers(1, 60, B).astype(np.int32))
-    return state, target, np.tile(RMPC_PRM, (B, 1)), rng.uniform(0.05, 0.3, B), io
-
-
-def _rmpc_expected(L, harness, state, target, prm, mu, io, logs, N, k, do_post, do_pre):
-    from dart_mpc.rmpc import AdaptiveNPMPCSmooth, rls_features
-    s = {n: v.copy() for n, v in state.items()}
-    io = {n: v.copy() for n, v in io.items()}
-    lg = {n: v.copy() for n, v in logs.items()}
-    B = s["x"].shape[0]
-    c = L.rmpc_loop_config()
-    if do_post:
-        xk, u = s["x"][:, :4].copy(), io["u0"]
-        en = np.linalg.norm(xk[:, [0, 2]] - target[:, [0, 2]], axis=1)
-        for b in np.where(s["done"] == 0)[0]:
-            r = s["nlog"][b]
-            lg["pos_err"][r, b] = [target[b, 0] - xk[b, 0], target[b, 2] - xk[b, 2]]
-            lg["pos_err_norm"][r, b] = float(en[b])
-            lg["u_cmd"][r, b] = u[b]
-            lg["timestep"][r, b] = k * TS
-            s["nlog"][b] += 1
-            if en[b] < c.pos_tol:
-                s["done"][b] = 1
-        lg["x"][k], lg["theta"][k], lg["r_v"][k] = xk, s["theta"], s["r_v"]
-        lg["f"][k], lg["status"][k], lg["iters"][k] = io["f"], io["status"], io["iters"]
-        s["prev"], s["u_prev"] = xk, u.copy()
-        plant = harness.TrayPlant(s["x"], mu, dt=TS)
-        plant.tilt = s["tilt"].copy()
-        s["x"] = plant.step(u)
-        s["tilt"] = plant.tilt
-    if do_pre:
-        xk, prev = s["x"][:, :4].copy(), s["prev"]
-        io["y"] = (xk[:, [1, 3]] - prev[:, [1, 3]]) / TS
-        io["phi"] = np.stack([rls_features(p, prm[0, 9]) for p in prev])
-        err = np.stack([target[:, 0] - s["r_v"][:, 0], np.zeros(B), target[:, 2] - s["r_v"][:, 2], np.zeros(B)], axis=1)
-        s["r_v"] = s["r_v"] + c.alpha_rg * np.clip(err, -c.dr_max, c.dr_max) * np.array([1.0, 0.0, 1.0, 0.0])
-        io["Rref"] = np.stack([AdaptiveNPMPCSmooth.build_ref_traj(xk[b], s["r_v"][b], target[b], N, 4, step_fraction=0.2)
-                               for b in range(B)])
-        io["x0"] = xk
-    return s, io, lg
-
-
 @pytest.mark.parametrize("do_post,do_pre", [(0, 1), (1, 1), (1, 0)])
 @pytest.mark.parametrize("B", [1, 5, 67])
 @pytest.mark.parametrize("N", [1, 20, 31, 32, 63])
@@ -164,7 +59,8 @@ def test_rmpc_loop_step_matches_numpy(L, torch, rmpc_solvers, N, B, do_post, do_
     state, target, prm, mu, io = _rmpc_case(L, rng, B, N)
     rows, k = 4, 3
     logs = L.loop_logs(L.RMPC_LOOP_LOGS, rows, B)
-    want = _rmpc_expected(L, harness, state, target, prm, mu, io, logs, N, k, do_post, do_pre)
+    want = _rmpc_expected(L, harness, state, target, prm, lambda x, tilt, u: _tray_step(harness, x, tilt, u, mu), io, logs,
+                          N, k, do_post, do_pre)
     ds, dio, dl = _to_dev(torch, state), _to_dev(torch, io), _to_dev(torch, logs)
     c = _to_dev(torch, dict(target=target, prm=prm, mu=mu))
     s = rmpc_solvers(N)
@@ -202,10 +98,7 @@ def test_pmpc_loop_step_matches_numpy(L, torch, pmpc_solver, B, do_post, do_pre)
         wl["X"][k], wl["U_cmd"][k], wl["loss"][k] = state["x"], io["u0"], io["f"]
         wl["quat_tray"][k] = np.stack([tilt_to_quat(u) for u in io["u0"]])
         wl["status"][k], wl["iters"][k] = io["status"], io["iters"]
-        plant = harness.TrayPlant(state["x"], prm[:, 0], dt=TS)
-        plant.tilt = state["tilt"].copy()
-        ws["x"] = plant.step(io["u0"])
-        ws["tilt"] = plant.tilt
+        ws["x"], ws["tilt"] = _tray_step(harness, state["x"], state["tilt"], io["u0"], prm[:, 0])
     if do_pre:
         wio["x0"] = ws["x"].copy()
     ds, dio, dl = _to_dev(torch, state), _to_dev(torch, io), _to_dev(torch, logs)
