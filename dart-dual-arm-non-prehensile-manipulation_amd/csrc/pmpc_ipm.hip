@@ -409,21 +409,24 @@ __device__ __forceinline__ bool pmpc_riccati(const int lane, const int N, const 
 // (wave 2).  [field][lane]: every access is one conflict-free 8-byte access per lane.
 // Ownership: wave 0 writes pt (the point; mu is the same value in every lane, one unmasked write) before barrier A,
 // the helper waves read it after it (the factor wave the rows up to kPtZu only), and wave 0 reads its own zl, zu
-// back when the speculated point is taken.  Wave 1 writes fc, kFlUseScan and kFlOk, wave 2 mu_new, kFlConverged and
-// kFlMuDec, all before barrier B; wave 0 reads them after it.  Wave 0 alone writes kFlStop.  Each buffer has one
-// writer, and its next write comes after a barrier that the readers cross only with their reads complete, so single
-// buffers are enough.
+// back when the speculated point is taken.  Wave 1 writes fc and the verdict record's word x (use_scan, ok), wave 2
+// its words y (converged, mu decreased) and z, w (the updated mu), all before barrier B; wave 0 reads the record after
+// it with one 16-byte access beside the six factor rows, every read issued before the first wait.
+// Wave 0 alone writes kFlStop.  Each buffer, and each word of the record, has one writer, and its next write comes
+// after a barrier that the readers cross only with their reads complete, so single buffers are enough.
 enum PmPt { kPtTh, kPtLp, kPtLv, kPtZl, kPtZu, kPtP, kPtV, kPtZ, kPtMu, kPtRows };      // the point and mu
 enum PmFc { kFcP11, kFcP12, kFcP22, kFcW1, kFcW2, kFcIQs, kFcRows };                            // its factors
-// stop; the factor wave's use_scan and ok; the evaluation wave's converged and mu decreased (kFl*Time: the stamps
-// build's helper-wave timers)
-enum PmFlag { kFlStop, kFlUseScan, kFlOk, kFlFactorTime, kFlConverged, kFlMuDec, kFlEvalTime, kFlWords = 8 };
+// stop (kFl*Time: the stamps build's helper-wave timers)
+enum PmFlag { kFlStop, kFlFactorTime, kFlEvalTime, kFlWords = 4 };
+// the bits of the verdict record's words x (the factor wave's) and y (the evaluation wave's)
+enum PmVerdict : int { kVdUseScan = 1, kVdOk = 2, kVdConverged = 1, kVdMuDec = 2 };
 struct PmOvlShared {
     double pt[kPtRows][kWave];
     double fc[kFcRows][kWave];
-    double mu_new;
+    int4 vd;       // the verdict record: x, y the helper waves' flag words, z and w the low and high half of the updated mu
     int flag[kFlWords];
 };
+static_assert(offsetof(PmOvlShared, vd) % 16 == 0, "the verdict record is read with one 16-byte access");
 __shared__ PmOvlShared g_pm_ovl;       // only the overlapped instantiations name it (7.5 KB beside PrShared when fused)
 
 // IPOPT's kappa_sigma safeguard of a bound multiplier after its step: z within [1e-10, 1e10] mu / slack
@@ -658,7 +661,7 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                                                                          W2, iQs, us);
                 g_pm_ovl.fc[kFcP11][lane] = P11[0]; g_pm_ovl.fc[kFcP12][lane] = P12[0]; g_pm_ovl.fc[kFcP22][lane] = P22[0];
                 g_pm_ovl.fc[kFcW1][lane] = W1[0]; g_pm_ovl.fc[kFcW2][lane] = W2[0]; g_pm_ovl.fc[kFcIQs][lane] = iQs[0];
-                if (lane == 0) { g_pm_ovl.flag[kFlUseScan] = us ? 1 : 0; g_pm_ovl.flag[kFlOk] = okf ? 1 : 0; }
+                if (lane == 0) g_pm_ovl.vd.x = (us ? kVdUseScan : 0) | (okf ? kVdOk : 0);
 #ifdef DART_STAMPS
                 // the factor wave's own time from barrier A to its arrival at barrier B, summed (slot 13 of wave 0)
                 t_acc_[13] += __builtin_amdgcn_s_memtime() - tf0;
@@ -690,7 +693,10 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                 gze[0] = zdefect(zz1, w1, 0);
                 bool dec = false;
                 const bool conv = point_verdict(p1, v1, th1, lp1, lv1, zl1, zu1, g1e, g2e, gze, mu1, dec);
-                if (lane == 0) { g_pm_ovl.mu_new = mu1; g_pm_ovl.flag[kFlConverged] = conv ? 1 : 0; g_pm_ovl.flag[kFlMuDec] = dec ? 1 : 0; }
+                if (lane == 0) {
+                    g_pm_ovl.vd.y = (conv ? kVdConverged : 0) | (dec ? kVdMuDec : 0);
+                    g_pm_ovl.vd.z = __double2loint(mu1); g_pm_ovl.vd.w = __double2hiint(mu1);
+                }
 #ifdef DART_STAMPS
                 // the evaluation wave's own time from barrier A to its arrival at barrier B, summed (slot 17 of wave 0)
                 t_acc_[17] += __builtin_amdgcn_s_memtime() - te0;
@@ -871,20 +877,27 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
             // and whether it decreased (BacktrackingLineSearch::Reset, as in the one-wave mu update).
             if (!lsm) {
                 __builtin_amdgcn_sched_barrier(0);      // everything above is done before this wave waits
+                // (lgkmcnt(0): this wave's own LDS reads of the iteration before, the multipliers read back on a
+                // hit, have long returned; stated here so that the compiler puts no guard of their registers
+                // between the reads that follow the barrier)
+                __builtin_amdgcn_s_waitcnt(0xc07f);
                 SPAN_BEGIN(t_b);
                 __syncthreads();                                            // barrier B
                 SPAN_END(14, t_b);                      // (stamps build, slot 14: the wait alone)
-                // (the six values are read with the flags, not after the branch on them: one LDS round trip)
-                const int usf = g_pm_ovl.flag[kFlUseScan], okff = g_pm_ovl.flag[kFlOk];
-                const int cvf = g_pm_ovl.flag[kFlConverged], mdf = g_pm_ovl.flag[kFlMuDec];
-                const double mun = g_pm_ovl.mu_new;
+                // One LDS round trip: the verdict record (one 16-byte read) and the six factor rows are all issued
+                // ahead of the scheduling barrier; the scalars are taken and the branch on converged is made behind
+                // it, so the first wait is for the record alone, with the factor rows on their way
+                const int4 vd = g_pm_ovl.vd;
                 P11[0] = g_pm_ovl.fc[kFcP11][lane]; P12[0] = g_pm_ovl.fc[kFcP12][lane]; P22[0] = g_pm_ovl.fc[kFcP22][lane];
                 W1[0] = g_pm_ovl.fc[kFcW1][lane]; W2[0] = g_pm_ovl.fc[kFcW2][lane]; iQs[0] = g_pm_ovl.fc[kFcIQs][lane];
-                const bool us = __builtin_amdgcn_readfirstlane(usf) != 0;
-                const bool okf = __builtin_amdgcn_readfirstlane(okff) != 0;
-                if (__builtin_amdgcn_readfirstlane(cvf)) { status = 0; break; }
-                mu = wave_uniform(mun);
-                if (__builtin_amdgcn_readfirstlane(mdf)) { nfilt = 0; in_soft = 0; }
+                __builtin_amdgcn_sched_barrier(0);
+                const int vdf = __builtin_amdgcn_readfirstlane(vd.x), vde = __builtin_amdgcn_readfirstlane(vd.y);
+                const double mun = __hiloint2double(__builtin_amdgcn_readfirstlane(vd.w), __builtin_amdgcn_readfirstlane(vd.z));
+                const bool us = (vdf & kVdUseScan) != 0;
+                const bool okf = (vdf & kVdOk) != 0;
+                if (vde & kVdConverged) { status = 0; break; }
+                mu = mun;
+                if (vde & kVdMuDec) { nfilt = 0; in_soft = 0; }
                 tau = fmax(0.99, 1.0 - mu);
                 rt[0] = uon ? fma(r2, th[0], mu * (isu[0] - isl[0])) : 0.0;
                 if (PM_EXPECT(us && okf, 1)) {
@@ -1284,6 +1297,20 @@ __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
                     const double il = frcp(thc - lo), iu = frcp(hi - thc);
                     const double zln = pm_clamp_mult(fma(az, dzl[0], zl[0]), mu, il);
                     const double zun = pm_clamp_mult(fma(az, dzu[0], zu[0]), mu, iu);
+#ifdef DART_STAMPS
+                    {
+                        // Newton iterations (slot 18) in which no lane's primal fraction binds (19), no lane's dual
+                        // fraction binds (20), neither (21), and no lane's multiplier comes within a factor 2 of a
+                        // clamp bound at the hand-over (22): tools/stamps_pmpc_fractions.py, DESIGN §5.R13
+                        const double cl = fma(az, dzl[0], zl[0]) * (thc - lo), cu = fma(az, dzu[0], zu[0]) * (hi - thc);
+                        const bool near = uon && !(cl >= 2e-10 * mu && cl <= 0.5e10 * mu && cu >= 2e-10 * mu && cu <= 0.5e10 * mu);
+                        STAMP_ADD(18, 1);
+                        STAMP_ADD(19, am_lf == 1.0f ? 1 : 0);
+                        STAMP_ADD(20, az_lf == 1.0f ? 1 : 0);
+                        STAMP_ADD(21, am_lf == 1.0f && az_lf == 1.0f ? 1 : 0);
+                        STAMP_ADD(22, wany(near) ? 0 : 1);
+                    }
+#endif
                     __builtin_amdgcn_sched_barrier(0);
                     g_pm_ovl.pt[kPtTh][lane] = thc;
                     g_pm_ovl.pt[kPtLp][lane] = fma(alpha, dlp[0], lp[0]); g_pm_ovl.pt[kPtLv][lane] = fma(alpha, dlv[0], lv[0]);
