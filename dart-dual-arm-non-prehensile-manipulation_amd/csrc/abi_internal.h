@@ -389,6 +389,7 @@ struct LmpcStagePlan {
     size_t reset_rows;
     size_t learners;                              // a population's host entry: B = learners * B each, the nets and the
                                                   // training arrays stacked per learner; 0: one learner
+    bool no_logs;                                 // an evaluation in metrics-only mode: the loop's logs are not laid out
 };
 
 // true if a pointer of `group` (kind kAnyState: its state and log arrays; kRec / kPool: those) is null
@@ -401,10 +402,18 @@ void lmpc_bind(const RollStage& S, const dart_mpc_handle* h, const int idx[kLmpc
 // The closed loop of dart_lmpc_rollout_dev (collect false: no experience launches, weights may be null, rcfg unused)
 // and of dart_lmpc_collect_dev on device pointers, the handle's lock held: every check, then the launches.
 // learner_B > 0 (a population's collection): instance b acts and is valued with the nets of learner b / learner_B
-// (weights [learners][39748], critic [learners][kPopCriticStride]); 0: one policy for all
+// (weights [learners][39748], critic [learners][kPopCriticStride]); 0: one policy for all.
+// ev != nullptr (dart_lmpc_eval*, never with collect): the loop step is lmpc_eval_loop_kernel's, which keeps
+// ev->metrics [B][8]; the seven logs of `p` are all null (metrics-only) or all set; one score launch over the P
+// learners (B = P * B each) follows the last post when ev->scores is set
+struct LmpcEval {
+    double* metrics;
+    double* scores;
+    int P;
+};
 int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                      const dart_lmpc_reward_config* rcfg, bool collect, int B, int k0, int steps, int log_rows,
                      int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise, void* stream,
-                     int learner_B = 0);
+                     int learner_B = 0, const LmpcEval* ev = nullptr);
 
 #pragma GCC visibility pop

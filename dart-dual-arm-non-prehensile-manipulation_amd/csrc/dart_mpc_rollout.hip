@@ -1,6 +1,7 @@
 // dart_mpc_rollout.hip -- the closed-loop entries of include/dart_mpc.h (host side): the loop-step and rollout entries
-// of the three controllers (loop_step.hip between the unchanged solves), LMPC experience step and collection
-// (lmpc_experience.hip after every post of the LMPC closed loop).
+// of the three controllers (loop_step.hip between the unchanged solves), the LMPC evaluation (the LMPC loop with
+// metrics, optional logs and P weight sets), LMPC experience step and collection (lmpc_experience.hip after every
+// post of the LMPC closed loop).
 #include "abi_internal.h"
 
 void dart_plant_config_default(dart_plant_config* c) {
@@ -580,7 +581,9 @@ void lmpc_stage(RollStage& S, const dart_lmpc_train_buffers& host, const LmpcSta
         case kBothTrain: idx[i] = S.add(p, row, m.train); break;
         case kNet: idx[i] = S.add(p, call, m.train); break;
         case kCall: idx[i] = S.add(p, call, true); break;
-        case kLog: idx[i] = S.add_rows(p, m.log_rows, row, m.r0, m.r1, false, true); break;
+        case kLog:
+            if (!(m.no_logs && a.group == kLoop)) idx[i] = S.add_rows(p, m.log_rows, row, m.r0, m.r1, false, true);
+            break;
         // (collection: both ways, since an instance that records less leaves its entries of the rows untouched)
         case kRec: if (m.rec_rows) idx[i] = S.add_rows(p, m.rec_rows, row, m.q0, m.q1, !m.train, true); break;
         case kPool: if (m.reset_rows) idx[i] = S.add(p, m.reset_rows * row, false); break;
@@ -662,15 +665,32 @@ int experience_ptrs(dart_mpc_handle* h, int rec_rows, int reset_rows, const dart
     return DART_MPC_OK;
 }
 
-// every argument check of the rollout (ea == nullptr) and collection entries, host and device forms alike; a
-// collection's experience arguments are left in *ea
+// the loop's logs of an evaluation: 1 all given, 0 all null (metrics-only), -1 some of each
+int lmpc_logs_given(const dart_lmpc_train_buffers& p) {
+    int given = 0, absent = 0;
+    for (const LmpcArr& a : kLmpcArr)
+        if (a.group == kLoop && a.kind == kLog) ++(member(p, a) ? given : absent);
+    return given && absent ? -1 : given ? 1 : 0;
+}
+
+// every argument check of the rollout (ea == nullptr), collection and evaluation (ev != nullptr) entries, host and
+// device forms alike; a collection's experience arguments are left in *ea
 int lmpc_loop_check(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                     const dart_lmpc_reward_config* rcfg, int B, int k0, int steps, int log_rows, int rec_rows,
-                    int reset_rows, const dart_lmpc_train_buffers& p, dartmpc::ExperienceArgs* ea) {
+                    int reset_rows, const dart_lmpc_train_buffers& p, dartmpc::ExperienceArgs* ea,
+                    const LmpcEval* ev = nullptr) {
     if (int rc = loop_check(h, plant, B, k0, steps, log_rows)) return rc;
     if (ea)
         if (int rc = experience_cfg(h, pcfg, rcfg, B, rec_rows, reset_rows, p.weights, p.critic, *ea)) return rc;
-    if (lmpc_null(p, kLoop)) return fail(h, DART_MPC_EINVAL, "null pointer");
+    if (ev) {
+        if (lmpc_logs_given(p) < 0)
+            return fail(h, DART_MPC_EINVAL, "null and non-null log pointers (metrics-only mode: every log null)");
+        if (!ev->metrics) return fail(h, DART_MPC_EINVAL, "null metrics");
+        if (lmpc_null(p, kLoop, kUp) || lmpc_null(p, kLoop, kBoth) || lmpc_null(p, kLoop, kBothCollect))
+            return fail(h, DART_MPC_EINVAL, "null pointer");
+    } else if (lmpc_null(p, kLoop)) {
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    }
     if (p.weights) {
         dartmpc::PolicyArgs chk;
         if (policy_args(pcfg, B, p.weights, chk) != DART_MPC_OK) return fail(h, DART_MPC_EINVAL, "bad policy config");
@@ -707,15 +727,64 @@ int dart_lmpc_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
     return DART_MPC_OK;
 }
 
+namespace {
+
+// one launch of the evaluation's loop step, the checks made (lg: the seven logs, all set or all null)
+int lmpc_eval_step(dart_mpc_handle* h, const dart_plant_config* plant, int B, int k, int do_post, int do_pre,
+                   int log_rows, const double* target, const double* plant_pvec, double* x, double* tilt, double* u_prev,
+                   const double* model_params, double* state, const double* u0, const double* f, const int32_t* status,
+                   const int32_t* iters, double* metrics, const dart_lmpc_train_buffers& lg, void* stream) {
+    if (B == 0 || (!do_post && !do_pre)) return DART_MPC_OK;
+    HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
+    dartmpc::LmpcEvalLoopArgs e;
+    dartmpc::LmpcLoopArgs& a = e.l;
+    a.B = B; a.k = k; a.do_post = do_post ? 1 : 0; a.do_pre = do_pre ? 1 : 0; a.log_rows = log_rows;
+    a.a_lag = plant_args(h, plant).a_lag;
+    a.Ts = h->cfg.Ts;
+    a.target = target; a.plant_pvec = plant_pvec; a.x = x; a.tilt = tilt; a.u_prev = u_prev;
+    a.model_params = model_params; a.state = state; a.u0 = u0; a.f = f; a.status = status; a.iters = iters;
+    a.log_X = lg.log_X; a.log_U = lg.log_U; a.log_pos_error = lg.log_pos_error; a.log_pvec = lg.log_pvec;
+    a.log_loss = lg.log_loss; a.log_status = lg.log_status; a.log_iters = lg.log_iters;
+    e.logs = lg.log_X ? 1 : 0;
+    e.metrics = metrics;
+    HIPCHK(h, dartmpc_launch_lmpc_eval_loop(&e, stream_of(h, stream)), "loop-step kernel launch");
+    return DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_eval_loop_step_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                                 int B, int k, int do_post, int do_pre, int log_rows,
+                                 const double* target, const double* plant_pvec,
+                                 double* x, double* tilt, double* u_prev, const double* model_params, double* state,
+                                 const double* u0, const double* f, const int32_t* status, const int32_t* iters,
+                                 double* metrics,
+                                 double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                                 int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    if (int rc = loop_check(h, plant, B, k, do_post ? 1 : 0, log_rows)) return rc;
+    dart_lmpc_train_buffers lg{};
+    lg.log_X = log_X; lg.log_U = log_U; lg.log_pos_error = log_pos_error; lg.log_pvec = log_pvec; lg.log_loss = log_loss;
+    lg.log_status = log_status; lg.log_iters = log_iters;
+    if (lmpc_logs_given(lg) < 0)
+        return fail(h, DART_MPC_EINVAL, "null and non-null log pointers (metrics-only mode: every log null)");
+    if (!metrics) return fail(h, DART_MPC_EINVAL, "null metrics");
+    if (any_null({target, plant_pvec, x, tilt, u_prev, model_params, state, u0, f, status, iters}))
+        return fail(h, DART_MPC_EINVAL, "null pointer");
+    return lmpc_eval_step(h, plant, B, k, do_post, do_pre, log_rows, target, plant_pvec, x, tilt, u_prev, model_params,
+                          state, u0, f, status, iters, metrics, lg, stream);
+}
+
 int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                      const dart_lmpc_reward_config* rcfg, bool collect, int B, int k0, int steps, int log_rows,
                      int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise, void* stream,
-                     int learner_B) {
+                     int learner_B, const LmpcEval* ev) {
     dartmpc::ExperienceArgs ea;
     if (int rc = lmpc_loop_check(h, plant, pcfg, rcfg, B, k0, steps, log_rows, rec_rows, reset_rows, p,
-                                 collect ? &ea : nullptr))
+                                 collect ? &ea : nullptr, ev))
         return rc;
     if (learner_B < 0) return fail(h, DART_MPC_EINVAL, "negative learner block size");
+    if (ev && collect) return fail(h, DART_MPC_EINVAL, "an evaluation collects no experience");
     ea.learner_B = learner_B;
     if (B == 0 || steps == 0) return DART_MPC_OK;
     HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
@@ -728,6 +797,9 @@ int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const d
     ea.action = action; ea.mean_out = nullptr;
     void* s = stream_of(h, stream);
     auto step = [&](int k, int post, int pre) {
+        if (ev)
+            return lmpc_eval_step(h, plant, B, k, post, pre, log_rows, p.target, p.plant_pvec, p.x, p.tilt, p.u_prev,
+                                  p.model_params, L.state, L.u0, L.f, L.status, L.iters, ev->metrics, p, s);
         return dart_lmpc_loop_step_dev(h, plant, B, k, post, pre, log_rows, p.target, p.plant_pvec, p.x, p.tilt, p.u_prev,
                                        p.model_params, L.state, L.u0, L.f, L.status, L.iters, p.log_X, p.log_U,
                                        p.log_pos_error, p.log_pvec, p.log_loss, p.log_status, p.log_iters, s);
@@ -765,20 +837,25 @@ int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const d
             HIPCHK(h, dartmpc_launch_lmpc_experience(&ea, (hipStream_t)s), "experience kernel launch");
         }
     }
+    if (ev && ev->scores)
+        HIPCHK(h, dartmpc_launch_lmpc_eval_scores(ev->P, B / ev->P, ev->metrics, ev->scores, (hipStream_t)s),
+               "score kernel launch");
     return DART_MPC_OK;
 }
 
 namespace {
 
 // the host form of the rollout and collection entries: the arrays of `p` staged into the handle's arena around
-// lmpc_closed_loop (the step rows [k0, k0 + steps) of the logs and of the noise travel)
+// lmpc_closed_loop (the step rows [k0, k0 + steps) of the logs and of the noise travel).  An evaluation (ev, host
+// pointers): P weight rows go up, the metrics travel both ways, the scores come down, and in metrics-only mode no
+// log is laid out or moved
 int lmpc_closed_loop_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                           const dart_lmpc_reward_config* rcfg, bool collect, int B, int k0, int steps, int log_rows,
                           int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise,
-                          void* stream) {
+                          void* stream, int learner_B = 0, const LmpcEval* ev = nullptr) {
     dartmpc::ExperienceArgs chk;
     if (int rc = lmpc_loop_check(h, plant, pcfg, rcfg, B, k0, steps, log_rows, rec_rows, reset_rows, p,
-                                 collect ? &chk : nullptr))
+                                 collect ? &chk : nullptr, ev))
         return rc;
     if (B == 0 || steps == 0) return DART_MPC_OK;
     HIPCHK(h, hipSetDevice(h->device), "hipSetDevice");
@@ -788,6 +865,10 @@ int lmpc_closed_loop_host(dart_mpc_handle* h, const dart_plant_config* plant, co
     m.B = (size_t)B; m.nw = (size_t)dart_lmpc_nw(h->cfg.N);
     m.log_rows = (size_t)log_rows; m.r0 = (size_t)k0; m.r1 = (size_t)k0 + steps;
     m.reset_rows = collect ? (size_t)reset_rows : 0;
+    if (ev) {
+        m.learners = (size_t)ev->P;
+        m.no_logs = lmpc_logs_given(p) == 0;
+    }
     if (collect && rec_rows > 0) {
         // record rows: an instance writes rows nrec[b] .. nrec[b] + ceil(steps / record_every) - 1 at most
         long long e0 = rec_rows, e1 = 0;
@@ -806,12 +887,15 @@ int lmpc_closed_loop_host(dart_mpc_handle* h, const dart_plant_config* plant, co
     lmpc_stage(S, p, m, idx);
     const int i_nz = (m.policy && noise) ? S.add_rows(noise, m.log_rows, kAct * m.B * sizeof(float), m.r0, m.r1, true, false)
                                          : -1;
+    const int i_met = ev ? S.add(ev->metrics, 8 * sizeof(double) * m.B, true) : -1;
+    const int i_sc = (ev && ev->scores) ? S.add_rows(ev->scores, 1, 8 * sizeof(double) * m.learners, 0, 1, false, true) : -1;
     if (int rc = S.reserve(h)) return rc;
     if (int rc = S.upload(h, s)) return rc;
     dart_lmpc_train_buffers d{};
     lmpc_bind(S, h, idx, d);
+    LmpcEval dev_ev{S.dev<double>(h, i_met), S.dev<double>(h, i_sc), ev ? ev->P : 0};
     if (int rc = lmpc_closed_loop(h, plant, pcfg, rcfg, collect, B, k0, steps, log_rows, rec_rows, reset_rows, d,
-                                  S.dev<float>(h, i_nz), s))
+                                  S.dev<float>(h, i_nz), s, learner_B, ev ? &dev_ev : nullptr))
         return rc;
     if (int rc = S.download(h, s)) return rc;
     HIPCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize");
@@ -852,6 +936,93 @@ int dart_lmpc_rollout(dart_mpc_handle* h, const dart_plant_config* plant, const 
     p.log_X = log_X; p.log_U = log_U; p.log_pos_error = log_pos_error; p.log_pvec = log_pvec; p.log_loss = log_loss;
     p.log_status = log_status; p.log_iters = log_iters;
     return lmpc_closed_loop_host(h, plant, pcfg, nullptr, false, B, k0, steps, log_rows, 0, 0, p, noise, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// LMPC evaluation: the rollout's loop with the metrics kept on the device, logs that may be absent and P weight sets
+// in one call (P learners of B instances each, stacked learner-major)
+namespace {
+
+// the shape checks of an evaluation, then the closed loop on device (host false) or host pointers
+int lmpc_eval(dart_mpc_handle* h, bool host, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg, int P,
+              int B, int k0, int steps, int log_rows, const dart_lmpc_train_buffers& p, const float* noise,
+              double* metrics, double* scores, void* stream) {
+    if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, variant_text(DART_MPC_LMPC));
+    if (P < 1 || P > DART_LMPC_POP_MAX) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+    if (B < 0) return fail(h, DART_MPC_EINVAL, "negative batch, step or row count");
+    if ((long long)P * B > h->cfg.B_max) return fail(h, DART_MPC_EINVAL, "population: P * B larger than B_max");
+    const LmpcEval ev{metrics, scores, P};
+    // (a population of one runs the single-policy launches)
+    const int learner_B = P > 1 ? B : 0;
+    return host ? lmpc_closed_loop_host(h, plant, pcfg, nullptr, false, P * B, k0, steps, log_rows, 0, 0, p, noise, stream,
+                                        learner_B, &ev)
+                : lmpc_closed_loop(h, plant, pcfg, nullptr, false, P * B, k0, steps, log_rows, 0, 0, p, noise, stream,
+                                   learner_B, &ev);
+}
+
+}  // namespace
+
+int dart_lmpc_eval_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                       int P, int B, int k0, int steps, int log_rows,
+                       const double* target, const double* prm, const double* plant_pvec, const double* current_k,
+                       const float* weights, const float* noise,
+                       double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                       int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                       double* metrics, double* scores,
+                       double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                       int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    // (the view's members in their order, up to model_params)
+    dart_lmpc_train_buffers p = {mut(target), prm, mut(plant_pvec), mut(current_k), mut(weights), nullptr, x, tilt, u_prev, w,
+                                 obs_mean, obs_M2, obs_count, history, timestep, model_params};
+    p.log_X = log_X; p.log_U = log_U; p.log_pos_error = log_pos_error; p.log_pvec = log_pvec; p.log_loss = log_loss;
+    p.log_status = log_status; p.log_iters = log_iters;
+    return lmpc_eval(h, false, plant, pcfg, P, B, k0, steps, log_rows, p, noise, metrics, scores, stream);
+}
+
+int dart_lmpc_eval(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                   int P, int B, int k0, int steps, int log_rows,
+                   const double* target, const double* prm, const double* plant_pvec, const double* current_k,
+                   const float* weights, const float* noise,
+                   double* x, double* tilt, double* u_prev, double* w, double* obs_mean, double* obs_M2,
+                   int32_t* obs_count, float* history, int32_t* timestep, double* model_params,
+                   double* metrics, double* scores,
+                   double* log_X, double* log_U, double* log_pos_error, double* log_pvec, double* log_loss,
+                   int32_t* log_status, int32_t* log_iters, void* stream) {
+    DART_ENTER(h, -1);
+    // (the view's members in their order, up to model_params)
+    dart_lmpc_train_buffers p = {mut(target), prm, mut(plant_pvec), mut(current_k), mut(weights), nullptr, x, tilt, u_prev, w,
+                                 obs_mean, obs_M2, obs_count, history, timestep, model_params};
+    p.log_X = log_X; p.log_U = log_U; p.log_pos_error = log_pos_error; p.log_pvec = log_pvec; p.log_loss = log_loss;
+    p.log_status = log_status; p.log_iters = log_iters;
+    return lmpc_eval(h, true, plant, pcfg, P, B, k0, steps, log_rows, p, noise, metrics, scores, stream);
+}
+
+namespace {
+
+int eval_scores_check(int P, int B, const double* metrics, const double* scores) {
+    return (P < 1 || P > DART_LMPC_POP_MAX || B < 1 || !metrics || !scores) ? DART_MPC_EINVAL : DART_MPC_OK;
+}
+
+}  // namespace
+
+int dart_lmpc_eval_scores_dev(int P, int B, const double* metrics, double* scores, void* stream) {
+    if (int rc = eval_scores_check(P, B, metrics, scores)) return rc;
+    return dartmpc_launch_lmpc_eval_scores(P, B, metrics, scores, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK
+                                                                                                     : DART_MPC_EHIP;
+}
+
+int dart_lmpc_eval_scores(int P, int B, const double* metrics, double* scores) {
+    if (int rc = eval_scores_check(P, B, metrics, scores)) return rc;
+    DART_DEVICE_STAGE(D, S);
+    const size_t n = 8 * (size_t)P * B;
+    if (S.reserve(sizeof(double) * n + 256, sizeof(double) * 8 * P + 256) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    const double* d_m = S.in(metrics, n);
+    double* d_s = S.out<double>(8 * (size_t)P);
+    if (!D->run([&](hipStream_t s) { return dartmpc_launch_lmpc_eval_scores(P, B, d_m, d_s, s); })) return DART_MPC_EHIP;
+    S.take(scores, d_s, 8 * (size_t)P);
+    return DART_MPC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -134,9 +134,32 @@ struct LmpcLoopArgs {
     int32_t* log_iters;         // [..]
 };
 
+// LMPC evaluation (lmpc_eval_loop_kernel): the LMPC loop step above with the streaming metrics of the cross-plant
+// loops, metrics [B][8] in/out (same slots, e_k of the state that solve k saw, th_x = x[4], th_y = x[6]).  logs == 0:
+// the seven log pointers of `l` are null and no log row is written (metrics-only); logs == 1: they are all set and
+// the rows are lmpc_loop_kernel's.  B counts all instances of a population (P learners of B each, learner-major);
+// the kernel does not know about learners.
+struct LmpcEvalLoopArgs {
+    LmpcLoopArgs l;
+    int logs;
+    double* metrics;            // [B][8] in/out
+};
+
+// Scores (lmpc_eval_scores_kernel): metrics [P][B][8] -> scores [P][8], per learner over its instances b = 0 .. B-1 in
+// that order, sequential fp64 sums:
+//   0 mean steady-state error  (sum m[0]) / B           4 max error        max m[3]
+//   1 converged fraction       #(m[1] >= 0) / B         5 status nonzero   sum m[4]
+//   2 mean convergence step    sum of the m[1] >= 0 over their count; -1 when none
+//   3 mean control effort      (sum m[2]) / B           6 iters per solve  (sum m[5]) / (sum m[7]); 0 when that is 0
+//                                                       7 max rotation     max m[6]
+
 }  // namespace dartmpc
 
 // (lm: 0 the tray plant's instantiation, 1 the LMPC plant's)
 extern "C" hipError_t dartmpc_launch_lmpc_loop(const dartmpc::LmpcLoopArgs* args, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_rmpc_loop(const dartmpc::RmpcLoopArgs* args, int lm, hipStream_t stream);
 extern "C" hipError_t dartmpc_launch_pmpc_loop(const dartmpc::PmpcLoopArgs* args, int lm, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_lmpc_eval_loop(const dartmpc::LmpcEvalLoopArgs* args, hipStream_t stream);
+// (B >= 1; P <= 0 launches nothing)
+extern "C" hipError_t dartmpc_launch_lmpc_eval_scores(int P, int B, const double* metrics, double* scores,
+                                                      hipStream_t stream);

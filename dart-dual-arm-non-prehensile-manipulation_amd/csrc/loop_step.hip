@@ -8,7 +8,8 @@
 // run_rmpc with plant_pvec) and also keeps the streaming metrics and the rotation log of loop_step.h; what a plant
 // does not have is under `if constexpr (LM)` and is not in the other instantiation.  lmpc_loop_kernel: the same glue
 // for harness.run_lmpc (LMPC/src/run.py:256-286: log, plant step of the LMPC model, next state); its lane mapping is
-// described at the kernel.
+// described at the kernel.  lmpc_eval_loop_kernel: that step with the streaming metrics and optional logs, for the
+// evaluation of P policies in one call (dart_lmpc_eval*); lmpc_eval_scores_kernel reduces its metrics per learner.
 //
 // RMPC / PMPC: one wave64 per instance, kLoopWaves instances per block; lane i owns horizon node i (the staged
 // reference), the per-instance scalars are computed by every lane and stored by one.  All three: plain fp64 in the
@@ -220,6 +221,117 @@ __device__ __forceinline__ void loop_metrics_step(double* m, int k, double Ts, d
     m[7] = n + 1.0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// LMPC evaluation (dart_lmpc_eval*): lmpc_loop_kernel's step with the streaming metrics and with logs that may be
+// absent.  Same lane mapping (kLmGroup lanes per instance, lane r evaluates Stribeck term r), same post(k) / pre(k+1)
+// split, the same expressions in the same order, so x, tilt, u_prev, state and (a.logs) the log rows are bit for bit
+// lmpc_loop_kernel's.  The step is that kernel's text again, not shared with it, so that kernel keeps its
+// instructions.  Lane 0 of the group feeds loop_metrics_step what harness.rollout_metrics takes from the logs: e of
+// the state the solve saw (x as loaded, before the plant step), u0, status, iters, th_x = x[4], th_y = x[6].
+__global__ __launch_bounds__(kLmLoopThreads) void lmpc_eval_loop_kernel(LmpcEvalLoopArgs ea) {
+    const LmpcLoopArgs& a = ea.l;
+    const int r = threadIdx.x & (kLmGroup - 1);
+    const int b = (blockIdx.x * kLmLoopThreads + threadIdx.x) / kLmGroup;
+    if (b >= a.B) return;                    // uniform over the group (the shuffles stay inside it)
+    double x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = a.x[8 * b + i];
+
+    if (a.do_post) {
+        double tilt[2] = {a.tilt[2 * b], a.tilt[2 * b + 1]};
+        const double u[2] = {a.u0[2 * b], a.u0[2 * b + 1]};
+        const size_t row = (size_t)a.k * a.B + b;
+        if (ea.logs)
+            for (int i = r; i < 34; i += kLmGroup) a.log_pvec[34 * row + i] = a.model_params[34 * b + i];
+        if (r == 0) {
+            const int status = a.status[b], iters = a.iters[b];
+            if (ea.logs) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) a.log_X[8 * row + i] = x[i];
+                a.log_U[2 * row] = u[0]; a.log_U[2 * row + 1] = u[1];
+                a.log_loss[row] = a.f[b];
+                a.log_status[row] = status;
+                a.log_iters[row] = iters;
+            }
+            a.u_prev[2 * b] = u[0]; a.u_prev[2 * b + 1] = u[1];
+            const double ex = x[0] - a.target[8 * b], ey = x[2] - a.target[8 * b + 2];
+            loop_metrics_step(ea.metrics + 8 * b, a.k, a.Ts, sqrt(ex * ex + ey * ey), u, status, iters, x[4], x[6]);
+        }
+        // harness.LmpcPlant.step
+        tilt[0] += a.a_lag * (u[0] - tilt[0]);
+        tilt[1] += a.a_lag * (u[1] - tilt[1]);
+        const double* pv = a.plant_pvec + 34 * b;
+        LmPlantPrm P;
+        P.m_x = lm_squash(pv[0]); P.m_y = lm_squash(pv[1]); P.c_x = lm_squash(pv[2]); P.c_y = lm_squash(pv[3]);
+        P.k_x = lm_squash(pv[4]); P.k_y = lm_squash(pv[5]); P.I_x = lm_squash(pv[16]); P.I_y = lm_squash(pv[17]);
+        P.r_x = lm_squash(pv[18]); P.r_y = lm_squash(pv[19]); P.c_rot_x = lm_squash(pv[20]); P.c_rot_y = lm_squash(pv[21]);
+        P.h_com_x = lm_squash(pv[32]); P.h_com_y = lm_squash(pv[33]);
+        {       // Stribeck rows [F_s, F_c, B, v_s, eps] (:301-334): x 6.., y 11.., rot x 22.., rot y 27..
+            const int t = r < 6 ? r : r - 6;
+            const int o = t == 0 || t == 2 ? 6 : t == 1 || t == 3 ? 11 : t == 4 ? 22 : 27;
+            P.Fs = pv[o]; P.Fc = pv[o + 1]; P.Bv = pv[o + 2]; P.vs = lm_squash(pv[o + 3]); P.eps = lm_squash(pv[o + 4]);
+        }
+        const double st = sin((r & 1) ? tilt[1] : tilt[0]);
+        const double sa = __shfl(st, 0, kLmGroup), sb = __shfl(st, 1, kLmGroup);
+        const double h = a.Ts;
+        double k1[8], k2[8], k3[8], k4[8], y[8];
+        lm_plant_dyn(P, r, x, sa, sb, k1);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[i] = x[i] + 0.5 * h * k1[i];
+        lm_plant_dyn(P, r, y, sa, sb, k2);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[i] = x[i] + 0.5 * h * k2[i];
+        lm_plant_dyn(P, r, y, sa, sb, k3);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[i] = x[i] + h * k3[i];
+        lm_plant_dyn(P, r, y, sa, sb, k4);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = x[i] + h * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) / 6;
+        if (r == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a.x[8 * b + i] = x[i];
+            a.tilt[2 * b] = tilt[0]; a.tilt[2 * b + 1] = tilt[1];
+            if (ea.logs) {
+                const double dx = x[0] - a.target[8 * b], dy = x[2] - a.target[8 * b + 2];
+                a.log_pos_error[row] = sqrt(dx * dx + dy * dy);
+            }
+        }
+    }
+    if (a.do_pre && r == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a.state[8 * b + i] = x[i];
+    }
+}
+
+// metrics [P][B][8] -> scores [P][8] (loop_step.h): one work-group per learner, lane s owns score slot s and walks
+// its learner's instances b = 0 .. B-1 in that order, so every sum is the sequential fp64 sum that
+// harness.population_scores restates (B >= 1)
+constexpr int kScoreThreads = 64;
+__global__ __launch_bounds__(kScoreThreads) void lmpc_eval_scores_kernel(int B, const double* metrics, double* scores) {
+    const int l = blockIdx.x, s = threadIdx.x;
+    if (s >= 8) return;
+    const double* m = metrics + 8 * (size_t)l * B;
+    // the metrics slot a score reads: 0 e, 1 and 2 the convergence step, 3 effort, 4 max e, 5 bad steps, 6 iters (over
+    // the steps, slot 7), 7 rotation
+    const int c = s == 0 ? 0 : s <= 2 ? 1 : s - 1;
+    double acc = 0.0, cnt = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const double v = m[8 * (size_t)b + c];
+        if (s == 1) { if (v >= 0.0) acc += 1.0; }
+        else if (s == 2) { if (v >= 0.0) { acc += v; cnt += 1.0; } }
+        else if (s == 4 || s == 7) { if (b == 0 || v > acc) acc = v; }
+        else {
+            acc += v;
+            if (s == 6) cnt += m[8 * (size_t)b + 7];
+        }
+    }
+    double out = acc;
+    if (s == 0 || s == 1 || s == 3) out = acc / (double)B;
+    else if (s == 2) out = cnt > 0.0 ? acc / cnt : -1.0;
+    else if (s == 6) out = cnt != 0.0 ? acc / cnt : 0.0;
+    scores[8 * (size_t)l + s] = out;
+}
+
 // One plant step of instance b with the command u, and the new state stored by lane 0.  Tray: mu is the instance's
 // viscous friction, and x[0..3] are stored (pz, vz do not move).  LMPC plant: every aligned group of kLmGroup lanes
 // runs the step the way lmpc_loop_kernel's group does, so all 64 lanes hold the same next state; x[0..7] are stored.
@@ -400,4 +512,21 @@ extern "C" hipError_t dartmpc_launch_pmpc_loop(const PmpcLoopArgs* args, int lm,
 
 extern "C" hipError_t dartmpc_launch_lmpc_loop(const LmpcLoopArgs* args, hipStream_t stream) {
     return launch_loop(lmpc_loop_kernel, *args, kLmLoopThreads / kLmGroup, stream);
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_eval_loop(const LmpcEvalLoopArgs* args, hipStream_t stream) {
+    const LmpcLoopArgs& a = args->l;
+    if (a.B <= 0 || (!a.do_post && !a.do_pre)) return hipSuccess;
+    const int per_block = kLmLoopThreads / kLmGroup;
+    hipLaunchKernelGGL(lmpc_eval_loop_kernel, dim3((a.B + per_block - 1) / per_block), dim3(kLmLoopThreads), 0, stream,
+                       *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dartmpc_launch_lmpc_eval_scores(int P, int B, const double* metrics, double* scores,
+                                                      hipStream_t stream) {
+    if (P <= 0) return hipSuccess;
+    if (B <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmpc_eval_scores_kernel, dim3(P), dim3(kScoreThreads), 0, stream, B, metrics, scores);
+    return hipGetLastError();
 }

@@ -60,7 +60,9 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_lmpc_global_pop_workspace_bytes", "dart_lmpc_choice_pop_dev", "dart_lmpc_global_append_pop_dev",
            "dart_lmpc_gae_seq_pop_dev", "dart_lmpc_train_pop_global_dev", "dart_lmpc_train_pop_global",
            "dart_pmpc_lm_loop_step_dev", "dart_pmpc_lm_rollout_dev", "dart_pmpc_lm_rollout",
-           "dart_rmpc_lm_loop_step_dev", "dart_rmpc_lm_rollout_dev", "dart_rmpc_lm_rollout")
+           "dart_rmpc_lm_loop_step_dev", "dart_rmpc_lm_rollout_dev", "dart_rmpc_lm_rollout",
+           "dart_lmpc_eval_loop_step_dev", "dart_lmpc_eval_dev", "dart_lmpc_eval", "dart_lmpc_eval_scores_dev",
+           "dart_lmpc_eval_scores")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -154,6 +156,11 @@ RMPC_LM_LOOP_STATE = (("x", 8, np.float64),) + RMPC_LOOP_STATE[1:] + (("metrics"
 RMPC_LM_LOOP_LOGS = RMPC_LOOP_LOGS + (("rot", 4, np.float64),)
 METRIC_SLOTS = ("steady_state_error", "convergence_step", "control_effort", "max_error", "status_nonzero", "iters",
                 "max_rotation", "steps")
+# LMPC evaluation (dart_lmpc_eval*): the rollout's state plus the streaming metrics [P B, 8] (METRIC_SLOTS), P learners
+# of B instances stacked learner-major; the scores [P, 8] reduce a learner's metrics over its instances
+LMPC_EVAL_STATE = LMPC_LOOP_STATE + (("metrics", 8, np.float64),)
+SCORE_SLOTS = ("mean_steady_state_error", "converged_fraction", "mean_convergence_step", "mean_control_effort",
+               "max_error", "status_nonzero", "iters_per_solve", "max_rotation")
 # experience collection (dart_lmpc_collect): the collection state [B, width], the reset pool [reset_rows, B, width],
 # the per-step logs [rows, B] and the records [rec_rows, B, width]
 LMPC_COLLECT_STATE = (("prev_cmd", 2, np.float64), ("control_seen", 2, np.float64), ("ep_step", 0, np.int32),
@@ -328,6 +335,17 @@ def lib():
         for fn in (L.dart_pmpc_lm_loop_step_dev, L.dart_rmpc_lm_loop_step_dev, L.dart_pmpc_lm_rollout_dev,
                    L.dart_pmpc_lm_rollout, L.dart_rmpc_lm_rollout_dev, L.dart_rmpc_lm_rollout):
             fn.restype = ctypes.c_int
+    if hasattr(L, "dart_lmpc_eval_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_lmpc_eval_loop_step_dev.argtypes = [vp, vp] + [ci] * 5 + [vp] * 20
+        L.dart_lmpc_eval_loop_step_dev.restype = ctypes.c_int
+        for fn in (L.dart_lmpc_eval_dev, L.dart_lmpc_eval):
+            fn.argtypes = [vp, vp, vp] + [ci] * 5 + [vp] * 26
+            fn.restype = ctypes.c_int
+        L.dart_lmpc_eval_scores_dev.argtypes = [ci, ci, vp, vp, vp]
+        L.dart_lmpc_eval_scores_dev.restype = ctypes.c_int
+        L.dart_lmpc_eval_scores.argtypes = [ci, ci, vp, vp]
+        L.dart_lmpc_eval_scores.restype = ctypes.c_int
     if hasattr(L, "dart_lmpc_collect_dev"):  # (absent only in older in-tree builds used for A/B timing)
         vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
         L.dart_lmpc_reward_config_default.argtypes = [ctypes.POINTER(RewardConfig)]
@@ -1136,6 +1154,78 @@ class LmpcSolver(Solver):
                                      *_host_ptrs(LMPC_LOOP_LOGS, logs, (rows, B)), None)
         if rc != 0:
             self._err(rc, "dart_lmpc_rollout")
+
+    # -- evaluation (dart_lmpc_eval_loop_step_dev / dart_lmpc_eval_dev / dart_lmpc_eval / dart_lmpc_eval_scores*) ----
+    def eval_loop_step_dev(self, B, k, do_post, do_pre, log_rows, target, plant_pvec, state, io, logs, plant=None,
+                           stream=0):
+        """``loop_step_dev`` with the streaming metrics: ``state`` also maps ``metrics`` [B, 8]; ``logs`` None is the
+        metrics-only mode (no log row is written)."""
+        plant = plant or plant_config()
+        rc = lib().dart_lmpc_eval_loop_step_dev(
+            self._h, ctypes.byref(plant), int(B), int(k), int(do_post), int(do_pre), int(log_rows), target, plant_pvec,
+            *[ctypes.c_void_p(int(state[n])) for n in ("x", "tilt", "u_prev", "model_params")],
+            *_dev_ptrs(LMPC_LOOP_IO, io), ctypes.c_void_p(int(state["metrics"])), *_dev_ptrs(LMPC_LOOP_LOGS, logs),
+            stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_eval_loop_step_dev")
+
+    def evaluate_dev(self, P, B, k0, steps, log_rows, target, prm, plant_pvec, state, logs, pcfg=None, weights=0,
+                     current_k=0, noise=0, scores=0, plant=None, stream=0):
+        """``rollout_dev`` for P policies at once, with metrics: P learners of B instances each, stacked learner-major
+        (every array [P B, ..], logs and noise [log_rows, P B, ..], ``weights`` [P, 39748]); ``state`` maps
+        LMPC_EVAL_STATE (``metrics`` [P B, 8], see ``loop_metrics``) to device pointers; ``logs`` None is the
+        metrics-only mode; ``scores`` [P, 8] (SCORE_SLOTS) is written after the last step when given."""
+        plant = plant or plant_config()
+        rc = lib().dart_lmpc_eval_dev(self._h, ctypes.byref(plant), ctypes.byref(pcfg) if pcfg is not None else None,
+                                      int(P), int(B), int(k0), int(steps), int(log_rows), target, prm, plant_pvec,
+                                      current_k or None, weights or None, noise or None,
+                                      *_dev_ptrs(LMPC_EVAL_STATE, state), scores or None,
+                                      *_dev_ptrs(LMPC_LOOP_LOGS, logs), stream or None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_eval_dev")
+
+    def evaluate(self, P, k0, steps, target, plant_pvec, state, logs, pcfg=None, weights=None, current_k=None, prm=None,
+                 noise=None, scores=None, rows=None, plant=None):
+        """Host arrays (blocking): ``state`` (LMPC_EVAL_STATE, [P B, ..]) is advanced, ``scores`` [P, 8] (or None)
+        written, and rows k0 .. k0+steps-1 of ``logs`` (``loop_logs`` of LMPC_LOOP_LOGS over P B instances) filled in
+        place; ``logs`` None is the metrics-only mode, which moves no log (``rows`` then bounds k0 + steps, default
+        k0 + steps).  ``weights`` [P, 39748] fp32 with ``pcfg`` and ``current_k`` [P B, 34], or None for the loop
+        without a policy; ``noise`` [rows, P B, 34] fp32 or None (zero noise)."""
+        PB = state["x"].shape[0]
+        if P < 1 or PB % P:
+            raise DartMPCError(f"{PB} instances do not divide into {P} learners")
+        B = PB // P
+        rows = logs["X"].shape[0] if logs is not None else (int(k0) + int(steps) if rows is None else int(rows))
+        c = lambda a, n: np.ascontiguousarray(a, np.float64).reshape(PB, n)
+        target, plant_pvec = c(target, 8), c(plant_pvec, 34)
+        prm = c(np.tile(LMPC_PRM_DEFAULT, (PB, 1)) if prm is None else prm, 22)
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, np.float32)
+            if noise.shape != (rows, PB, 34):
+                raise DartMPCError(f"evaluation noise must have shape {(rows, PB, 34)}")
+        wt = ck = None
+        if weights is not None:
+            wt = np.ascontiguousarray(weights, np.float32).reshape(P, ACTOR_NWEIGHTS)
+            ck = c(current_k, 34)
+        if scores is not None:
+            _inplace(scores, np.float64, 8 * P, "scores")
+        plant = plant or plant_config()
+        rc = lib().dart_lmpc_eval(self._h, ctypes.byref(plant), ctypes.byref(pcfg) if pcfg is not None else None, P, B,
+                                  int(k0), int(steps), rows, _ptr(target), _ptr(prm), _ptr(plant_pvec), _ptr(ck), _ptr(wt),
+                                  _ptr(noise), *_host_ptrs(LMPC_EVAL_STATE, state, (PB,), nw=self.nw), _ptr(scores),
+                                  *_host_ptrs(LMPC_LOOP_LOGS, logs, (rows, PB)), None)
+        if rc != 0:
+            self._err(rc, "dart_lmpc_eval")
+
+    @staticmethod
+    def eval_scores(metrics):
+        """The score kernel alone on host arrays: metrics [P, B, 8] -> scores [P, 8] (SCORE_SLOTS)."""
+        m = np.ascontiguousarray(metrics, np.float64)
+        if m.ndim != 3 or m.shape[2] != 8:
+            raise DartMPCError("metrics must have shape [P, B, 8]")
+        out = np.empty((m.shape[0], 8))
+        _rc(lib().dart_lmpc_eval_scores(m.shape[0], m.shape[1], _ptr(m), _ptr(out)), "dart_lmpc_eval_scores")
+        return out
 
     def loop_state(self, x0, policy=None, model_params=None):
         """The state of a fresh rollout from the states ``x0`` [B, 8]: ``model_params`` starts at the policy's (its

@@ -125,6 +125,37 @@ def rollout_metrics(X, target, U, status, iters, rot, Ts, metrics=None, k0=0):
     return M[0] if one else M
 
 
+def population_scores(metrics):
+    """The score kernel (csrc/loop_step.hip lmpc_eval_scores_kernel, _lib.SCORE_SLOTS) restated in numpy with plain
+    loops: metrics [P, B, 8] (_lib.METRIC_SLOTS per instance) -> scores [P, 8], every sum sequential over b = 0 .. B-1
+    in fp64, so the kernel gives the same bits.  0 mean steady-state error, 1 converged fraction (slot 1 >= 0),
+    2 mean convergence step over the converged (-1 when none), 3 mean control effort, 4 max error, 5 steps with
+    status != 0, 6 iterations per solve (0 when no step was taken), 7 max rotation."""
+    M = np.asarray(metrics, float)
+    P, B = M.shape[:2]
+    S = np.zeros((P, 8))
+    for l in range(P):
+        sse = conv = conv_sum = effort = bad = its = n = 0.0
+        emax = rot = 0.0
+        for b in range(B):
+            m = M[l, b]
+            sse = sse + m[0]
+            if m[1] >= 0.0:
+                conv = conv + 1.0
+                conv_sum = conv_sum + m[1]
+            effort = effort + m[2]
+            if b == 0 or m[3] > emax:
+                emax = m[3]
+            bad = bad + m[4]
+            its = its + m[5]
+            if b == 0 or m[6] > rot:
+                rot = m[6]
+            n = n + m[7]
+        S[l] = [sse / float(B), conv / float(B), conv_sum / conv if conv > 0.0 else -1.0, effort / float(B), emax, bad,
+                its / n if n != 0.0 else 0.0, rot]
+    return S
+
+
 def save_npz(logs: dict, metrics: dict, log_dir, experiment_name: str, object_name: str, mass, friction) -> str:
     """np.savez(logs + metrics) at ``{log_dir}/{object}/mass={m}_friction={f}/{name}_{timestamp}.npz``
     (logger.py:186-196)."""
@@ -609,16 +640,74 @@ def rollout_lmpc(x0, targets, plant_pvec, steps: int, N: int = 30, policy_seed=0
     return _lmpc_result(B, steps, Ts, targets, lg, state["x"], state, wall, return_logs)
 
 
+def evaluate_lmpc(x0, targets, plant_pvec, steps: int, policies, N: int = 30, noise_seed=None,
+                  metrics_only: bool = True, Ts: float = 0.002, prm=None, device: int = 0,
+                  plant_kw: dict | None = None, model_params=None):
+    """P LMPC policies on the same B experiments in one device-resident rollout (dart_lmpc_eval): ``policies`` is a
+    list of P ``LmpcPolicy(B)`` (sharing one policy config), or one, or None for the loop without a policy (every solve
+    uses ``model_params``, default ``plant_pvec``).  ``x0``, ``targets`` [B, 8] and ``plant_pvec`` [B, 34] are one
+    learner's and are used for every learner.  The evaluation runs on copies of the policies' state (observation
+    statistics, history, timestep, model_params): a policy passed in is not advanced.  ``noise_seed`` None is zero
+    noise -- the policy's mean action, the deterministic evaluation; otherwise every learner sees the draws of
+    ``lmpc_noise(noise_seed, steps, B)``.
+
+    Returns {"metrics": [P, B, 8] (_lib.METRIC_SLOTS), "scores": [P, 8] (_lib.SCORE_SLOTS)}; ``metrics_only`` False
+    also logs every step and adds "logs" and "status": per learner what ``rollout_lmpc`` returns."""
+    from . import _lib
+    if policies is not None and not isinstance(policies, (list, tuple)):
+        policies = [policies]
+    x0, B, targets, plant_pvec, prm, _, model_params = _lmpc_setup(x0, targets, plant_pvec, prm, None, model_params)
+    P = len(policies) if policies is not None else 1
+    if policies is not None:
+        if P < 1 or any(p.B != B for p in policies):
+            raise ValueError(f"policies: a list of LmpcPolicy({B})")
+        if any(bytes(p.cfg) != bytes(policies[0].cfg) for p in policies):
+            raise ValueError("policies: one policy config for the whole population")
+    tile = lambda a: np.ascontiguousarray(np.tile(a, (P,) + (1,) * (a.ndim - 1)))
+    noise = None
+    if policies is not None and noise_seed is not None:
+        noise = np.ascontiguousarray(np.tile(lmpc_noise(noise_seed, steps, B), (1, P, 1)))
+    plant = _lib.plant_config(**{k: v for k, v in (plant_kw or {}).items()})
+    solver = _lib.LmpcSolver(N=N, Ts=Ts, B_max=max(P * B, 1), device=device)
+    try:
+        members = [solver.loop_state(x0, policy=p) for p in policies] if policies is not None \
+            else [solver.loop_state(x0, model_params=model_params)]
+        state = {name: np.concatenate([m[name] for m in members], axis=0) for name in members[0]}
+        state["metrics"] = _lib.loop_metrics(P * B)
+        lg = None if metrics_only else _lib.loop_logs(_lib.LMPC_LOOP_LOGS, steps, P * B)
+        scores = np.zeros((P, 8))
+        t0 = time.perf_counter()
+        solver.evaluate(P, 0, steps, tile(targets), tile(plant_pvec), state, lg,
+                        pcfg=policies[0].cfg if policies is not None else None,
+                        weights=np.stack([p.weights for p in policies]) if policies is not None else None,
+                        current_k=np.concatenate([p.current_k for p in policies]) if policies is not None else None,
+                        prm=tile(prm), noise=noise, scores=scores, plant=plant)
+        wall = time.perf_counter() - t0
+    finally:
+        solver.close()
+    out = {"metrics": state["metrics"].reshape(P, B, 8), "scores": scores}
+    if not metrics_only:
+        out["logs"], out["status"] = [], []
+        for l in range(P):
+            sl = slice(l * B, (l + 1) * B)
+            logs, st = _lmpc_result(B, steps, Ts, targets, {k: v[:, sl] for k, v in lg.items()}, state["x"][sl], None, wall,
+                                    False)
+            out["logs"].append(logs); out["status"].append(st)
+    return out
+
+
 def compare_controllers(x0, target_xy, plant_pvec, steps: int, N: int = 20, lmpc_N: int = 30, Ts: float = 0.002,
                         pmpc_prm=None, pz_vz=(0.4, 0.0), lmpc_policy_seed=None, device: int = 0,
-                        plant_kw: dict | None = None):
+                        plant_kw: dict | None = None, lmpc_policies=None):
     """PMPC, RMPC and LMPC on the same objects: B experiments from the states ``x0`` [B, 8] (LmpcPlant's layout) to the
     targets ``target_xy`` [B, 2] on ``LmpcPlant`` with the true parameters ``plant_pvec`` [B, 34], ``steps`` steps each.
     PMPC and RMPC run through the cross-plant rollouts in metrics-only mode; LMPC runs through ``rollout_lmpc``
     (``lmpc_policy_seed`` None: every solve uses ``plant_pvec`` as its model) and ``rollout_metrics`` of its logs.
     ``pmpc_prm`` [B, 6]: PMPC's parameter rows, default [c_x / m_x of the plant, 600, 5, 0.1, -0.6, 0.6] (the cube's
     weights, main_parallel_enhanced.py:171-179).  Returns {"PMPC", "RMPC", "LMPC"}: metrics [B, 8] each
-    (_lib.METRIC_SLOTS)."""
+    (_lib.METRIC_SLOTS).  ``lmpc_policies`` (one ``LmpcPolicy(B)`` or a list of P) routes LMPC through
+    ``evaluate_lmpc`` instead, its metrics made on the device and no log moved: "LMPC" is then [B, 8] for one policy and
+    [P, B, 8] for a list."""
     x0 = np.asarray(x0, float).reshape(-1, 8)
     B = x0.shape[0]
     txy = np.asarray(target_xy, float).reshape(B, 2)
@@ -634,6 +723,11 @@ def compare_controllers(x0, target_xy, plant_pvec, steps: int, N: int = 20, lmpc
                                 plant_pvec=plant_pvec, x_rot0=x0[:, 4:], metrics_only=True),
            "RMPC": rollout_rmpc(x0[:, :4], t4, steps, N=N, Ts=Ts, device=device, plant_kw=plant_kw, pos_tol=0.0,
                                 plant_pvec=plant_pvec, x_rot0=x0[:, 4:], metrics_only=True)}
+    if lmpc_policies is not None:
+        m = evaluate_lmpc(x0, t8, plant_pvec, steps, lmpc_policies, N=lmpc_N, Ts=Ts, device=device,
+                          plant_kw={k: v for k, v in (plant_kw or {}).items() if k == "tau"})["metrics"]
+        out["LMPC"] = m if isinstance(lmpc_policies, (list, tuple)) else m[0]
+        return out
     logs, st, X = rollout_lmpc(x0, t8, plant_pvec, steps, N=lmpc_N, policy_seed=lmpc_policy_seed, Ts=Ts, device=device,
                                plant_kw={k: v for k, v in (plant_kw or {}).items() if k == "tau"}, return_logs=True)
     U = np.stack([lg["u_cmd"] for lg in logs], axis=1)

@@ -404,6 +404,44 @@ def train_population(solver, policies, target, plant_pvec, state, cstate, adam, 
     return rows
 
 
+def evaluate_population(solver, pop, x0, targets, plant_pvec, steps, which="latest", pcfg=None, prm=None, noise=None,
+                        plant=None):
+    """Which learner of a population controls best: one device-resident rollout of all P (``LmpcSolver.evaluate``,
+    metrics-only) on the B experiments ``x0``, ``targets`` [B, 8], ``plant_pvec`` [B, 34], the same for every learner.
+    ``pop`` is a ``population_stack`` dict with ``weights``, ``current_k`` and ``state``; ``which`` = "latest" evaluates
+    the members' weights, "best" the actor halves of their ``best["best_weights"]`` snapshots (every member needs one).
+    The run starts from copies of the members' observation statistics, history, timestep and model_params, so ``pop``
+    is not advanced.  ``noise`` None is zero noise: the policies' mean actions.  ``pcfg`` defaults to
+    ``lmpc.policy_config()``.  Returns {"scores": [P, 8] (_lib.SCORE_SLOTS), "metrics": [P, B, 8], "best": the learner
+    with the lowest mean steady-state error (slot 0; ties go to the lowest index)}."""
+    from . import _lib
+    from .lmpc import policy_config
+    if which not in ("latest", "best"):
+        raise _lib.DartMPCError(f"evaluate_population: which = {which!r} (\"latest\" or \"best\")")
+    weights = np.asarray(pop["weights"], np.float32)
+    P = weights.shape[0]
+    NI = np.asarray(pop["state"]["x"]).shape[0]
+    if P < 1 or NI % P:
+        raise _lib.DartMPCError(f"evaluate_population: {NI} instances are not {P} learners of equal size")
+    B = NI // P
+    if which == "best":
+        if np.any(np.asarray(pop["best"]["best_iter"]) < 0):
+            raise _lib.DartMPCError("evaluate_population: a member has no best-policy snapshot yet")
+        weights = np.asarray(pop["best"]["best_weights"], np.float32).reshape(P, -1)[:, :_lib.ACTOR_NWEIGHTS]
+    tile = lambda a, n: np.ascontiguousarray(np.tile(np.asarray(a, np.float64).reshape(B, n), (P, 1)))
+    state = {name: np.zeros(_lib._loop_shape(NI, width, nw=solver.nw), dt) for name, width, dt in _lib.LMPC_LOOP_STATE}
+    state["x"][:] = tile(x0, 8)
+    for name in ("obs_mean", "obs_M2", "obs_count", "history", "timestep", "model_params"):
+        state[name][:] = np.asarray(pop["state"][name]).reshape(state[name].shape)
+    state["metrics"] = _lib.loop_metrics(NI)
+    scores = np.zeros((P, 8))
+    solver.evaluate(P, 0, int(steps), tile(targets, 8), tile(plant_pvec, 34), state, None,
+                    pcfg=pcfg if pcfg is not None else policy_config(), weights=np.ascontiguousarray(weights),
+                    current_k=pop["current_k"], prm=None if prm is None else tile(prm, 22), noise=noise, scores=scores,
+                    plant=plant)
+    return {"scores": scores, "metrics": state["metrics"].reshape(P, B, 8), "best": int(np.argmin(scores[:, 0]))}
+
+
 def new_population_global_buffer(P, n):
     """The global buffers of a fresh population of ``P`` learners with ``n`` samples per iteration each: zeroed
     arrays [P, G, ..] of capacity G (``_lib.global_rows``), stacked learner-major, and the one ``fill`` = 0 all

@@ -605,6 +605,72 @@ int dart_lmpc_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const 
                       double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
                       int32_t *log_status, int32_t *log_iters, void *hip_stream);
 
+/* LMPC evaluation (added within ABI 8: new entries only): the loop of dart_lmpc_rollout, unchanged in what it
+ * computes per step (policy step, warm-started solve, plant step), with
+ *   - the streaming metrics of the cross-plant loops, metrics [.][8] (fp64, in/out; same slots, see above; a fresh
+ *     run starts from zeros with slot 1 = -1), updated by every post from what the logs would hold: e_k of the state
+ *     that solve k saw (log_X row k) against target[[0, 2]], u0, status, iters, th_x = x[4], th_y = x[6];
+ *   - logs that may be absent: the seven log pointers all NULL is the metrics-only mode (no log row is written, the
+ *     host entry reserves and moves no log buffer), all set gives bit for bit the rows of dart_lmpc_rollout; some NULL
+ *     and others not is DART_MPC_EINVAL.  log_rows still bounds k0 + steps (and the rows of the noise);
+ *   - P weight sets in one call: P learners of B instances each, stacked learner-major (instance i = l B + b, as in
+ *     dart_lmpc_train_pop), every per-instance array [P B][..], logs and noise [log_rows][P B][..], weights
+ *     [P][39748]; learner l's instances step with weight row l.  P = 1 runs the single-policy launches, so a
+ *     population of one is dart_lmpc_rollout bit for bit.  weights == NULL: no policy, as in dart_lmpc_rollout, on
+ *     all P B instances.  h needs B_max >= P B.
+ * Launch sequence: dart_lmpc_rollout_dev's with the evaluation's loop-step kernel in the place of the rollout's, and
+ * when scores is not NULL one score launch after the last post.  Two calls of K1 and K2 steps give bit for bit what
+ * one call of K1 + K2 steps gives, metrics included (k0 carries the step index into slot 1).
+ *
+ * scores [P][8] (fp64, out): per learner over its B instances in their order, sequential fp64 sums:
+ *     0 mean steady-state error  (sum m[0]) / B       4 max error        max m[3]
+ *     1 converged fraction       #(m[1] >= 0) / B     5 status nonzero   sum m[4]
+ *     2 mean convergence step    sum of the m[1] >= 0 over their count; -1 when there is none
+ *     3 mean control effort      (sum m[2]) / B       6 iters per solve  (sum m[5]) / (sum m[7]); 0 when that is 0
+ *                                                     7 max rotation     max m[6]
+ *
+ * DART_MPC_EINVAL with a message, nothing enqueued: P < 1 or P > DART_LMPC_POP_MAX, P B > B_max, a negative count,
+ * k0 + steps > log_rows, logs partly NULL, metrics NULL, a NULL among the required arrays, policy state NULL while
+ * weights is set. */
+
+/* One loop-step launch: dart_lmpc_loop_step_dev plus metrics [B][8], with the logs all set or all NULL. */
+int dart_lmpc_eval_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                                 int B, int k, int do_post, int do_pre, int log_rows,
+                                 const double *target, const double *plant_pvec,
+                                 double *x, double *tilt, double *u_prev, const double *model_params, double *state,
+                                 const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                                 double *metrics,
+                                 double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
+                                 int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+/* Device pointers, asynchronous on hip_stream (NULL = the handle's own). */
+int dart_lmpc_eval_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                       int P, int B, int k0, int steps, int log_rows,
+                       const double *target, const double *prm, const double *plant_pvec, const double *current_k,
+                       const float *weights, const float *noise,
+                       double *x, double *tilt, double *u_prev, double *w, double *obs_mean, double *obs_M2,
+                       int32_t *obs_count, float *history, int32_t *timestep, double *model_params,
+                       double *metrics, double *scores,
+                       double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
+                       int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+/* Host pointers: staged through device memory; blocks until state, metrics, scores (when not NULL) and, unless
+ * metrics-only, rows k0 .. k0+steps-1 of the logs are back.  Of the noise only those rows travel. */
+int dart_lmpc_eval(dart_mpc_handle *h, const dart_plant_config *plant, const dart_lmpc_policy_config *pcfg,
+                   int P, int B, int k0, int steps, int log_rows,
+                   const double *target, const double *prm, const double *plant_pvec, const double *current_k,
+                   const float *weights, const float *noise,
+                   double *x, double *tilt, double *u_prev, double *w, double *obs_mean, double *obs_M2,
+                   int32_t *obs_count, float *history, int32_t *timestep, double *model_params,
+                   double *metrics, double *scores,
+                   double *log_X, double *log_U, double *log_pos_error, double *log_pvec, double *log_loss,
+                   int32_t *log_status, int32_t *log_iters, void *hip_stream);
+
+/* The score reduction alone: metrics [P][B][8] -> scores [P][8] (1 <= P <= DART_LMPC_POP_MAX, B >= 1; else
+ * DART_MPC_EINVAL).  Device pointers, asynchronous; host pointers, blocking. */
+int dart_lmpc_eval_scores_dev(int P, int B, const double *metrics, double *scores, void *hip_stream);
+int dart_lmpc_eval_scores(int P, int B, const double *metrics, double *scores);
+
 /* LMPC experience collection (handle of variant DART_MPC_LMPC; added within ABI 8): the training half of
  * RLMPC._rl_worker (rlmpc2.py:537-938) up to the PPO update, on the device.  dart_lmpc_collect is
  * dart_lmpc_rollout with one experience launch after every post(k) (+ pre(k+1)) launch:
@@ -1060,7 +1126,7 @@ int dart_mpc_nw(int N);
  * The launch sequence per iteration is dart_lmpc_train_dev's, each step issued once for the whole population (the
  * update: prepare once, then gradient + apply per mini-batch index with every learner in each launch).  Calls chain
  * through it0 as the single entry's do.  The global-buffer update has its population form below
- * (dart_lmpc_train_pop_global); dart_lmpc_rollout and dart_lmpc_collect have none. */
+ * (dart_lmpc_train_pop_global); the rollout's population form is dart_lmpc_eval; dart_lmpc_collect has none. */
 #define DART_LMPC_POP_MAX 32
 #define DART_LMPC_POP_CRITIC_STRIDE 37572
 
