@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "dart_mpc.h"
+#include "launch_plan.h"
 #include "pmpc_ipm.h"
 #include "pmpc_model.h"
 #include "wave.h"

@@ -84,8 +84,9 @@ int pmpc_resto_mode(const dart_mpc_handle* h, int mode) {
 // IPOPT's soft restoration phase in the register kernel: with the restoration phases on, on IPOPT's path, at every N
 int pmpc_soft(const dart_mpc_handle* h) { return (h->cfg.restoration && h->cfg.pmpc_path == 0) ? 1 : 0; }
 
-// the mode of a host-entry launch of B instances: in the solving wave (small batches), else host-driven
-int host_resto_mode(const dart_mpc_handle* h, int B) { return pmpc_resto_mode(h, B <= 32 ? 1 : 2); }
+// the mode of a host-entry launch of B instances: in the solving wave (small batches: one XCD), else host-driven
+int host_mode_of(int B) { return dartmpc::xcd_pack(B) == 8 ? 1 : 2; }
+int host_resto_mode(const dart_mpc_handle* h, int B) { return pmpc_resto_mode(h, host_mode_of(B)); }
 
 // After the completion words of a host-driven (mode 2) launch: pmpc_resto_kernel for the handed-over
 // instances (status kPmNeedResto, read from mapped host memory), only if there is one -- no restoration
@@ -123,11 +124,7 @@ int pmpc_resto_buf(dart_mpc_handle* h, int B, hipStream_t s, dartmpc::PmpcArgs& 
     // turns that into different iteration counts on ~19 % of the restored instances (the same statuses, u0
     // within 1.3e-11; tools/pmpc_resume_check.py, profiles/r05/pmpc_resume.txt).  By default the restoration
     // solve starts over on the LDS engine and takes the oracle's iterations exactly.
-    static const bool resume = [] {
-        const char* e = getenv("DART_PMPC_RESUME");
-        return e && e[0] == '1';
-    }();
-    if (!a.resto || !resume) return DART_MPC_OK;
+    if (!a.resto || !dartmpc::launch_knobs().pmpc_resume) return DART_MPC_OK;
     int xcd = 0;
     return stream_state(h, B, s, &a.resto_buf, &xcd);
 }
@@ -178,7 +175,7 @@ int stream_state(dart_mpc_handle* h, int B, hipStream_t s, double** out, int* xc
     // per instance: PMPC's hand-off state, LMPC's hand-off state (N > 31: and the two-wave build's second-order-
     // correction and restoration state, needed with or without the restoration phases), RMPC's two-wave
     // restoration state
-    const bool wg2 = h->cfg.N > 31 || dartmpc::force_wg2();
+    const bool wg2 = dartmpc::two_wave(h->cfg.N, dartmpc::launch_knobs());
     const size_t per = h->cfg.variant == DART_MPC_PMPC   ? (size_t)dartmpc::kPmHo
                        : h->cfg.variant == DART_MPC_RMPC ? (dartmpc_rmpc_wg2_resto_bytes() + 7) / 8
                        : wg2                             ? dartmpc_lmpc_wg2_area_doubles()
@@ -333,7 +330,7 @@ int served_request(dart_mpc_handle* h, int B, bool ww, bool wo) {
 // one launch over the I/O area (no resident server), completion words as the host entry
 int bound_launch(dart_mpc_handle* h, int B, bool ww, bool wo) {
     next_seq(h);
-    dartmpc::PmpcArgs a = io_args(h, B, ww, wo, B <= 32 ? 1 : 2);
+    dartmpc::PmpcArgs a = io_args(h, B, ww, wo, host_mode_of(B));
     if (int rc = pmpc_resto_buf(h, B, h->stream, a)) return rc;
     HIPCHK(h, dartmpc_launch_pmpc(&a, h->stream), "kernel launch");
     int rc = wait_done(h, h->stream, h->hdone, B, a.seq);
@@ -553,7 +550,7 @@ int dart_rmpc_solve_batch_dev(dart_mpc_handle* h, int B, const double* x0, const
     a.u0 = u0; a.f = f; a.w_out = w_out; a.status = status; a.iters = iters;
     a.resto_buf = nullptr;
     hipStream_t s = stream_of(h, stream);
-    if ((a.N > 31 || dartmpc::force_wg2()) && a.resto) {      // the two-wave build's restoration state, one area per stream
+    if (dartmpc::two_wave(a.N, dartmpc::launch_knobs()) && a.resto) {      // the two-wave build's restoration state, one area per stream
         int xcd = 0;
         if (int rc = stream_state(h, B, s, &a.resto_buf, &xcd)) return rc;
     }

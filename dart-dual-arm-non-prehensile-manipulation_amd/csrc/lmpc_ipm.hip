@@ -38,7 +38,9 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <utility>
 
+#include "launch_plan.h"
 #include "lmpc_ipm.h"
 #include "ocp_wave.h"
 #include "stamps.h"
@@ -2092,6 +2094,107 @@ __global__ __launch_bounds__(kWave * kWaves) void lmpc_ipm_kernel(LmpcArgs a) {
 
 }  // namespace dartmpc
 
+// The launchers of the two objects built from this file launch what lmpc_plan (launch_plan.h) names.
+namespace dartmpc {
+
+// the only launch of lmpc_ipm_kernel
+template <bool RESTO, bool FUSE, bool POP>
+static hipError_t lm_launch(unsigned grid, size_t lds, hipStream_t stream, const LmpcArgs& a) {
+    hipLaunchKernelGGL((lmpc_ipm_kernel<RESTO, FUSE, POP>), dim3(grid), dim3(kWave * kWaves), lds, stream, a);
+    return hipGetLastError();
+}
+
+// the kernels of this object: one entry per row of its list in launch_plan.h (which is what instantiates them)
+#if DART_WG == 2
+constexpr auto& kLmBuilds = kLmpcWg2Builds;
+#else
+constexpr auto& kLmBuilds = kLmpcMainBuilds;
+#endif
+constexpr size_t kLmBuildCount = sizeof(kLmBuilds) / sizeof(kLmBuilds[0]);
+struct LmEntry {
+    LmpcBuild build;
+    const void* kernel;
+    hipError_t (*launch)(unsigned grid, size_t lds, hipStream_t stream, const LmpcArgs& a);
+};
+template <size_t I>
+static LmEntry lm_entry() {
+    constexpr LmpcBuild b = kLmBuilds[I];
+    return {b, (const void*)lmpc_ipm_kernel<b.resto, b.fuse, b.pop>, lm_launch<b.resto, b.fuse, b.pop>};
+}
+template <size_t... I>
+static const LmEntry* lm_entries(std::index_sequence<I...>) {
+    static const LmEntry table[] = {lm_entry<I>()...};
+    return table;
+}
+// a build the object does not hold is an error
+static hipError_t lm_launch_build(bool resto, bool fuse, bool pop, unsigned grid, size_t lds, hipStream_t stream,
+                                  const LmpcArgs& a) {
+    const LmEntry* t = lm_entries(std::make_index_sequence<kLmBuildCount>{});
+    for (size_t i = 0; i < kLmBuildCount; ++i)
+        if (t[i].build.resto == resto && t[i].build.fuse == fuse && t[i].build.pop == pop)
+            return t[i].launch(grid, lds, stream, a);
+    return hipErrorInvalidValue;
+}
+
+// the dynamic-LDS opt-in (the maximum any launch takes) is per device: set once, for every kernel of the list, for
+// every device a launch goes to (thread-safe)
+static hipError_t lm_lds_opt_in(const LmEntry* t, size_t n) {
+    static std::mutex mu;
+    static bool attr_set[64] = {};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> g(mu);
+    if (attr_set[dev]) return hipSuccess;
+    for (size_t i = 0; i < n; ++i) {
+        e = hipFuncSetAttribute(t[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLmLdsBytes);
+        if (e != hipSuccess) return e;
+    }
+    attr_set[dev] = true;
+    return hipSuccess;
+}
+
+static size_t lm_lds_bytes(LmpcLds l) {
+#if DART_WG == 1
+    constexpr size_t pol = kLmPolicyLdsOff + sizeof(PolicyLds), res = kLmRestoOff + sizeof(LmResto);
+    static_assert(res >= sizeof(LmShared), "kLdsResto is also the larger of LmShared alone and the restoration state");
+    switch (l) {
+    case kLdsShared: return sizeof(LmShared);
+    case kLdsPolicy: return pol;
+    case kLdsResto: return res;
+    case kLdsPolicyOrResto: return pol > res ? pol : res;
+    default: break;
+    }
+#endif
+    (void)l;
+    return kLmLdsBytes;
+}
+
+static hipError_t lmpc_launch_planned(const LmpcArgs& args, const LmpcPlan& p, hipStream_t stream) {
+    hipError_t e = lm_lds_opt_in(lm_entries(std::make_index_sequence<kLmBuildCount>{}), kLmBuildCount);
+    if (e != hipSuccess) return e;
+    LmpcArgs a = args;
+    if (p.policy_first) {        // the policy step of every instance first (its own launch, same stream)
+        e = dartmpc_launch_policy(&a.pol, stream);
+        if (e != hipSuccess) return e;
+        a.pvec = a.pol.model_params;
+        a.fuse_policy = 0;
+    }
+    a.pack = p.pack;
+    if (p.wg2) a.xcd = 0;
+    const unsigned grid = (unsigned)(a.B * a.pack);
+    e = lm_launch_build(false, p.fuse, p.pop, grid, lm_lds_bytes(p.lds_first), stream, a);
+    if (e != hipSuccess || !p.second) return e;
+    return lm_launch_build(true, false, false, grid, lm_lds_bytes(p.lds_second), stream, a);
+}
+
+static LmpcPlan lmpc_plan_of(const LmpcArgs& a) {
+    return lmpc_plan(a.N, a.B, a.resto, a.resto_buf != nullptr, a.fuse_policy, a.pol.learner_B, launch_knobs());
+}
+
+}  // namespace dartmpc
+
 #if DART_WG == 2
 // N = 32..63 (dartmpc_launch_lmpc forwards here): one instance per two-wave workgroup.  Device area per instance:
 // the hand-off state of its 128 lanes, then LmAux (second-order-correction scratch, restoration state).
@@ -2099,42 +2202,10 @@ extern "C" size_t dartmpc_lmpc_wg2_area_doubles() {
     return (size_t)dartmpc::kWave * dartmpc::kWaves * dartmpc::kLmNst + (sizeof(dartmpc::LmAux) + 7) / 8;
 }
 extern "C" hipError_t dartmpc_launch_lmpc_wg2(const void* args, hipStream_t stream) {
-    dartmpc::LmpcArgs a = *static_cast<const dartmpc::LmpcArgs*>(args);
-    if (a.N < (dartmpc::force_wg2() ? 1 : 32) || a.N >= dartmpc::LM_NMAXS) return hipErrorInvalidValue;
-    if (!a.resto_buf) return hipErrorInvalidValue;          // the device area is needed with or without resto
-    static std::mutex mu;
-    static bool attr_set[64] = {};
-    const size_t lds = dartmpc::kLmLdsBytes;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    {
-        std::lock_guard<std::mutex> g(mu);
-        if (!attr_set[dev]) {
-            e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            attr_set[dev] = true;
-        }
-    }
-    if (a.fuse_policy) {        // the policy step of every instance first (its own launch, same stream)
-        e = dartmpc_launch_policy(&a.pol, stream);
-        if (e != hipSuccess) return e;
-        a.pvec = a.pol.model_params;
-        a.fuse_policy = 0;
-    }
-    a.pack = 1; a.xcd = 0;
-    const dim3 block(dartmpc::kWave * dartmpc::kWaves);
-    hipLaunchKernelGGL(dartmpc::lmpc_ipm_kernel<false>, dim3(a.B), block, lds, stream, a);
-    if (a.resto) {
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(dartmpc::lmpc_ipm_kernel<true>, dim3(a.B), block, lds, stream, a);
-    }
-    return hipGetLastError();
+    const dartmpc::LmpcArgs& a = *static_cast<const dartmpc::LmpcArgs*>(args);
+    const dartmpc::LmpcPlan p = dartmpc::lmpc_plan_of(a);
+    if (!p.valid || !p.wg2) return hipErrorInvalidValue;
+    return dartmpc::lmpc_launch_planned(a, p, stream);
 }
 #else
 
@@ -2154,65 +2225,10 @@ extern "C" size_t dartmpc_lmpc_shared_bytes(void) { return sizeof(dartmpc::LmSha
 
 extern "C" hipError_t dartmpc_launch_lmpc(const dartmpc::LmpcArgs* args, hipStream_t stream) {
     if (args->B <= 0) return hipSuccess;
-    if ((args->N >= dartmpc::LM_NMAXS || dartmpc::force_wg2()) && args->N < 2 * dartmpc::LM_NMAXS)
-        return dartmpc_launch_lmpc_wg2(args, stream);
-    if (args->N < 1 || args->N >= dartmpc::LM_NMAXS) return hipErrorInvalidValue;
-    if (args->resto && !args->resto_buf) return hipErrorInvalidValue;
-    // the dynamic-LDS opt-in is per device: set once for every device a launch goes to (thread-safe)
-    static std::mutex mu;
-    static bool attr_set[64] = {};
-    const size_t lds = dartmpc::kLmLdsBytes;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    {
-        std::lock_guard<std::mutex> g(mu);
-        if (!attr_set[dev]) {
-            e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<false, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<false, false, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)dartmpc::lmpc_ipm_kernel<false, true, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            attr_set[dev] = true;
-        }
-    }
-    dartmpc::LmpcArgs a = *args;
-    a.pack = (a.B <= 32) ? 8 : 1;            // one XCD (and its L2) for the code of a small batch
-    // the policy prologue's LDS only when the launch runs it (the opt-in above covers the maximum)
-    const size_t lds_launch = a.fuse_policy ? dartmpc::kLmPolicyLdsOff + sizeof(dartmpc::PolicyLds) : sizeof(dartmpc::LmShared);
-    const bool pop = a.fuse_policy && a.pol.learner_B > 0;      // a population's policies in the prologue
-    if (a.resto && a.pack == 8 && dartmpc::resto_fuse_enabled()) {   // restoration in the solving wave: one launch
-        const size_t lds_r = dartmpc::kLmRestoOff + sizeof(dartmpc::LmResto);
-        const size_t lds_f = lds_launch > lds_r ? lds_launch : lds_r;
-        if (pop)
-            hipLaunchKernelGGL((dartmpc::lmpc_ipm_kernel<false, true, true>), dim3(a.B * a.pack), dim3(dartmpc::kWave),
-                               lds_f, stream, a);
-        else
-            hipLaunchKernelGGL((dartmpc::lmpc_ipm_kernel<false, true>), dim3(a.B * a.pack), dim3(dartmpc::kWave), lds_f,
-                               stream, a);
-        return hipGetLastError();
-    }
-    if (pop)
-        hipLaunchKernelGGL((dartmpc::lmpc_ipm_kernel<false, false, true>), dim3(a.B * a.pack), dim3(dartmpc::kWave),
-                           lds_launch, stream, a);
-    else
-        hipLaunchKernelGGL(dartmpc::lmpc_ipm_kernel<false>, dim3(a.B * a.pack), dim3(dartmpc::kWave), lds_launch, stream, a);
-    // IPOPT's restoration phases for the instances the first launch handed off (the others return at once)
-    if (a.resto)
-        hipLaunchKernelGGL(dartmpc::lmpc_ipm_kernel<true>, dim3(a.B * a.pack), dim3(dartmpc::kWave),
-                           dartmpc::kLmRestoOff + sizeof(dartmpc::LmResto), stream, a);
-    return hipGetLastError();
+    const dartmpc::LmpcPlan p = dartmpc::lmpc_plan_of(*args);
+    if (p.wg2) return dartmpc_launch_lmpc_wg2(args, stream);
+    if (!p.valid) return hipErrorInvalidValue;
+    return dartmpc::lmpc_launch_planned(*args, p, stream);
 }
 
 #ifdef DART_STAMPS

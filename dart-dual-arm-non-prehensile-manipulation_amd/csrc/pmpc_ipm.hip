@@ -37,6 +37,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <utility>
+
+#include "launch_plan.h"
 #include "pmpc_ipm.h"
 #include "pmpc_model.h"
 #include "pmpc_resto.h"
@@ -434,9 +437,8 @@ __device__ __forceinline__ double pm_clamp_mult(const double z, const double mu,
     return fmax(fmin(z, 1e10 * mu * islack), 1e-10 * mu * islack);
 }
 
-// The build of the kernel as one mask (the template argument of pmpc_ipm_kernel, pmpc_serve_kernel and pmpc_solve);
-// the comment above PM_EXPECT says what each selects.  kOcc2 and kFuse concern the kernels only.
-enum : unsigned { kScan = 1u, kOneRow = 2u, kShort2 = 4u, kRed = 8u, kOcc2 = 16u, kFuse = 32u, kOvl = 64u };
+// The build of the kernel as one mask F (kScan | kShort2 | ...: launch_plan.h, the template argument of pmpc_ipm_kernel,
+// pmpc_serve_kernel and pmpc_solve); the comment above PM_EXPECT says what each flag selects.
 
 template <int NAX, unsigned F>
 __device__ __forceinline__ bool pmpc_solve(const PmpcArgs& a, const int b) {
@@ -1774,56 +1776,54 @@ __global__ __launch_bounds__(kWave) void wave_selftest_kernel(double* out) {
 
 #endif  // PMPC_SEQ
 
+// The launchers launch what a plan names (launch_plan.h: pmpc_plan, pmpc_serve_plan); the two helpers below hold the
+// only launches of the two kernels.
+struct IpmKernel {
+    template <int NAX, unsigned F>
+    static hipError_t launch(unsigned grid, unsigned block, hipStream_t stream, const PmpcArgs& a) {
+        hipLaunchKernelGGL((pmpc_ipm_kernel<NAX, F>), dim3(grid), dim3(block), 0, stream, a);
+        return hipGetLastError();
+    }
+};
+struct ServeKernel {
+    template <int NAX, unsigned F>
+    static hipError_t launch(unsigned grid, unsigned block, hipStream_t stream, const PmpcArgs& a, const PmpcServe& sv) {
+        hipLaunchKernelGGL((pmpc_serve_kernel<NAX, F>), dim3(grid), dim3(block), 0, stream, a, sv);
+        return hipGetLastError();
+    }
+};
+// kernel K's instantiation <nax, f> of list L, which is what instantiates the list for this object; a build the
+// list does not hold is an error
+template <class K, const auto& L, size_t... I, class... A>
+static hipError_t launch_build_at(std::index_sequence<I...>, int nax, unsigned f, const A&... args) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((L[I].nax == nax && L[I].f == f && (e = K::template launch<L[I].nax, L[I].f>(args...), true)) || ...);
+    return e;
+}
+template <class K, const auto& L, class... A>
+static hipError_t launch_build(int nax, unsigned f, const A&... args) {
+    return launch_build_at<K, L>(std::make_index_sequence<sizeof(L) / sizeof(L[0])>{}, nax, f, args...);
+}
+
 }  // namespace dartmpc
 
-// the launchers name the builds by their flags
-using dartmpc::kScan; using dartmpc::kOneRow; using dartmpc::kShort2; using dartmpc::kRed; using dartmpc::kOcc2;
-using dartmpc::kFuse; using dartmpc::kOvl;
-
 #if DART_WG == 2
-// N = 32..63 on IPOPT's path (dartmpc_launch_pmpc forwards here): the scan build, one instance per two-wave
-// workgroup; grid = B x pack blocks as for the one-wave builds
-extern "C" hipError_t dartmpc_launch_pmpc_wg2(const void* args, unsigned grid, hipStream_t stream) {
-    const dartmpc::PmpcArgs& a = *static_cast<const dartmpc::PmpcArgs*>(args);
-    if (a.N < 32 || a.N > 63 || a.reduced || a.resto) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan>), dim3(grid), dim3(dartmpc::kWave * dartmpc::kWaves), 0,
-                       stream, a);
-    return hipGetLastError();
+// N = 32..63 on IPOPT's path: the scan build, one instance per two-wave workgroup; grid = B x pack blocks as for the
+// one-wave builds
+extern "C" hipError_t dartmpc_launch_pmpc_wg2(const void* args, int nax, unsigned f, unsigned grid, unsigned block,
+                                              hipStream_t stream) {
+    return dartmpc::launch_build<dartmpc::IpmKernel, dartmpc::kPmpcWg2Ipm>(
+        nax, f, grid, block, stream, *static_cast<const dartmpc::PmpcArgs*>(args));
 }
 #elif defined(PMPC_SEQ)
-// one-row scan build (onerow != 0, N <= 15), else the sequential (throughput) builds: two waves per
-// SIMD, used once B exceeds the scan limit or N > 31
-template <bool RED>
-static void launch_seq(const dartmpc::PmpcArgs* a, unsigned grid, hipStream_t stream, int onerow) {
-    constexpr unsigned red = RED ? kRed : 0u;
-    if (onerow && !RED && a->resto == 3)
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kOneRow | kFuse>), dim3(grid),
-                           dim3(dartmpc::kWave), 0, stream, *a);
-    else if (onerow)
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kOneRow | red>), dim3(grid), dim3(dartmpc::kWave), 0,
-                           stream, *a);
-    else if (a->N <= 31)
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, red>), dim3(grid), dim3(dartmpc::kWave), 0,
-                           stream, *a);
-    else
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<2, red>), dim3(grid), dim3(dartmpc::kWave), 0,
-                           stream, *a);
+// the one-row scan builds (N <= 15) and the sequential (throughput) builds
+extern "C" hipError_t dartmpc_launch_pmpc_seq(const dartmpc::PmpcArgs* a, int nax, unsigned f, unsigned grid,
+                                              unsigned block, hipStream_t stream) {
+    return dartmpc::launch_build<dartmpc::IpmKernel, dartmpc::kPmpcSeqIpm>(nax, f, grid, block, stream, *a);
 }
-extern "C" hipError_t dartmpc_launch_pmpc_seq(const dartmpc::PmpcArgs* a, unsigned grid, hipStream_t stream,
-                                              int onerow) {
-    if (a->reduced) launch_seq<true>(a, grid, stream, onerow);
-    else launch_seq<false>(a, grid, stream, onerow);
-    return hipGetLastError();
-}
-extern "C" hipError_t dartmpc_launch_pmpc_serve_onerow(const dartmpc::PmpcArgs* a, const dartmpc::PmpcServe* sv,
-                                                      unsigned grid, hipStream_t stream) {
-    if (a->resto == 3)
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kOneRow | kFuse>), dim3(grid), dim3(dartmpc::kWave), 0,
-                           stream, *a, *sv);
-    else
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kOneRow>), dim3(grid), dim3(dartmpc::kWave), 0, stream,
-                           *a, *sv);
-    return hipGetLastError();
+extern "C" hipError_t dartmpc_launch_pmpc_serve_seq(const dartmpc::PmpcArgs* a, const dartmpc::PmpcServe* sv, int nax,
+                                                   unsigned f, unsigned grid, unsigned block, hipStream_t stream) {
+    return dartmpc::launch_build<dartmpc::ServeKernel, dartmpc::kPmpcSeqServe>(nax, f, grid, block, stream, *a, *sv);
 }
 #ifdef DART_STAMPS
 // diagnostic build only: the stamps of the one-row (N <= 15) and sequential builds of this object
@@ -1833,132 +1833,61 @@ extern "C" hipError_t dartmpc_read_stamps_seq(unsigned long long* host_out) {
 }
 #endif
 #else
-extern "C" hipError_t dartmpc_launch_pmpc_seq(const dartmpc::PmpcArgs* a, unsigned grid, hipStream_t stream,
-                                              int onerow);
-extern "C" hipError_t dartmpc_launch_pmpc_serve_onerow(const dartmpc::PmpcArgs* a, const dartmpc::PmpcServe* sv,
-                                                      unsigned grid, hipStream_t stream);
-extern "C" hipError_t dartmpc_launch_pmpc_wg2(const void* args, unsigned grid, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_pmpc_seq(const dartmpc::PmpcArgs* a, int nax, unsigned f, unsigned grid,
+                                              unsigned block, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_pmpc_serve_seq(const dartmpc::PmpcArgs* a, const dartmpc::PmpcServe* sv, int nax,
+                                                   unsigned f, unsigned grid, unsigned block, hipStream_t stream);
+extern "C" hipError_t dartmpc_launch_pmpc_wg2(const void* args, int nax, unsigned f, unsigned grid, unsigned block,
+                                              hipStream_t stream);
 
-// the resident server for B_serve slots (IPOPT's path, N <= 31): one wave per slot, one XCD when it fits
+// the resident server for B_serve slots (IPOPT's path, N <= 31)
 extern "C" hipError_t dartmpc_launch_pmpc_serve(const dartmpc::PmpcArgs* args, const dartmpc::PmpcServe* sv,
                                                hipStream_t stream) {
-    if (args->B <= 0 || args->N > 31) return hipErrorInvalidValue;
+    const dartmpc::PmpcPlan p = dartmpc::pmpc_serve_plan(args->N, args->B, args->resto, dartmpc::launch_knobs());
+    if (!p.valid) return hipErrorInvalidValue;
     dartmpc::PmpcArgs a = *args;
-    a.pack = (a.B <= 32) ? 8 : 1;
-    // B_serve <= 32: the restoration phases run in the wave that handed the instance over (mode 3); larger
-    // servers hand it to the host (mode 2: dart_mpc_abi.hip served_resto)
-    if (a.resto && a.pack == 8 && dartmpc::resto_fuse_enabled()) a.resto = 3;
-    else if (a.resto) a.resto = 2;
-    const unsigned grid = (unsigned)(a.B * a.pack);
-    if (a.N <= 15) return dartmpc_launch_pmpc_serve_onerow(&a, sv, grid, stream);
-    if (a.N <= 23 && a.resto == 3)
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kShort2 | kFuse>), dim3(grid), dim3(dartmpc::kWave), 0,
-                           stream, a, *sv);
-    else if (a.N <= 23)
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kShort2>), dim3(grid), dim3(dartmpc::kWave), 0, stream, a,
-                           *sv);
-    else if (a.resto == 3)
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan | kFuse>), dim3(grid), dim3(dartmpc::kWave), 0,
-                           stream, a, *sv);
-    else
-        hipLaunchKernelGGL((dartmpc::pmpc_serve_kernel<1, kScan>), dim3(grid), dim3(dartmpc::kWave), 0, stream, a,
-                           *sv);
-    return hipGetLastError();
+    a.pack = p.pack;
+    a.resto = p.resto;
+    const unsigned grid = (unsigned)(a.B * a.pack), block = dartmpc::kWave * p.waves;
+    if (p.object == dartmpc::kPmpcSeq) return dartmpc_launch_pmpc_serve_seq(&a, sv, p.nax, p.f, grid, block, stream);
+    return dartmpc::launch_build<dartmpc::ServeKernel, dartmpc::kPmpcMainServe>(p.nax, p.f, grid, block, stream, a, *sv);
+}
+
+// DART_PMPC_OCC2_MIN_B, or two instances per SIMD of the device that is current at the first use
+static int pmpc_occ2_min_b() {
+    static const int v = [] {
+        if (dartmpc::launch_knobs().occ2_min_b != dartmpc::LaunchKnobs::kNotSet) return dartmpc::launch_knobs().occ2_min_b;
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            cus = 0;
+        return dartmpc::occ2_min_b_of(cus);
+    }();
+    return v;
 }
 
 extern "C" hipError_t dartmpc_launch_pmpc(const dartmpc::PmpcArgs* args, hipStream_t stream) {
     if (args->B <= 0) return hipSuccess;
+    const dartmpc::PmpcPlan p = dartmpc::pmpc_plan(args->N, args->B, args->reduced, args->resto, dartmpc::launch_knobs(),
+                                                   pmpc_occ2_min_b());
+    if (!p.valid) return hipErrorInvalidValue;
     dartmpc::PmpcArgs a = *args;
-    a.pack = (a.B <= 32) ? 8 : 1;          // <= 32 waves fit one XCD's CUs
-    // The quadratic scan shortens the dependent chain but needs more registers (one wave per SIMD
-    // instead of two).  On IPOPT's path (z rows, second-order correction) the sequential build no
-    // longer fits two waves per SIMD without scratch spills, and the scan build is faster at every
-    // batch size measured (B = 4096: 15.9 against 14.7 M solves/s; 18432: 18.1 against 17.4 M), so
-    // it serves every N <= 31 batch; the sequential builds remain for N > 31 and for the
-    // DART_PMPC_QSCAN_MAX_B experiment knob (the round-2 crossover was ~1.7 k instances).
-    const dim3 grid(a.B * a.pack);
-    static const int qscan_max_b = [] {
-        const char* e = getenv("DART_PMPC_QSCAN_MAX_B");
-        return e ? atoi(e) : (1 << 30);
-    }();
-    // From two instances per SIMD of the device on (2048 on MI355X), batches of N <= 31 take the scan build
-    // compiled for two waves per SIMD (40 VGPRs spilled, 164 B of scratch): the second wave fills the
-    // first's dependency stalls (VALU busy ~63 % alone).  Below that, one wave per SIMD and no spills win
-    // (N = 20, B = 1152: 10.8 against 9.4 M solves/s; even at 1536; B = 2048: 15.2 against 13.7 M; 18432:
-    // 20.5-20.9 against 17.8 M; N = 31, 18432: 6.4 against 6.1 M).  N <= 15 takes the short-scan build there
-    // (the one-row build loses at two waves, 19.4-19.7 against 19.9 M; the short-scan one wins, 2048: 15.4-15.5
-    // against 15.0 M, 18432: 22.2-22.8 against 20.0 M).  profiles/r04/occ2_ab.txt; DART_PMPC_OCC2_MIN_B
-    // overrides the threshold (experiments).
-    static const int occ2_min_b = [] {
-        if (const char* e = getenv("DART_PMPC_OCC2_MIN_B")) return atoi(e);
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            return 1 << 30;
-        return 2 * 4 * cus;
-    }();
-    const bool occ2 = !a.reduced && a.B >= occ2_min_b && a.B <= qscan_max_b;
-    // N = 32..63 on IPOPT's path: the scan build on two waves per instance (DART_PMPC_SEQ_LONG=1: the one-wave
-    // sequential build, NAX = 2, for A/B)
-    static const bool long_wg2 = [] {
-        const char* e = getenv("DART_PMPC_SEQ_LONG");
-        return !(e && e[0] == '1');
-    }();
-    // batches of at most 32 (one XCD, one instance per CU): IPOPT's restoration phases run in the wave that
-    // handed the instance over (resto mode 3, pmpc_resto_tail), so no restoration launch follows the solve.
-    // Only the branches below that launch a FUSE instantiation take mode 3 (not the two-waves-per-SIMD build, not
-    // the sequential builds past DART_PMPC_QSCAN_MAX_B): everywhere else the queued pmpc_resto_kernel (mode 1) stays
-    if (a.resto == 1 && a.pack == 8 && !a.reduced && a.N <= 31 && !occ2 && a.B <= qscan_max_b &&
-        dartmpc::resto_fuse_enabled())
-        a.resto = 3;
-    const bool fuse = a.resto == 3;
-    // The overlapped builds (three waves per instance: the second factors the Riccati scan of the point and the third
-    // forms its error measures, tests convergence and updates mu while the first runs the line search's trial and
-    // the update) where a CU has SIMDs to spare: batches of at most 32 (one instance per
-    // CU of one XCD) on IPOPT's path at N = 16..31.  Larger batches, the resident server and the rollout
-    // kernels keep the one-wave builds.  DART_PMPC_OVERLAP=0: the one-wave builds here too (A/B).
-    const bool ovl = a.pack == 8 && !a.reduced && !occ2 && a.N >= 16 && a.N <= 31 && a.B <= qscan_max_b &&
-                     dartmpc::pmpc_overlap_enabled();
-    const dim3 block3(3 * dartmpc::kWave);
-    if (ovl && a.N <= 23) {
-        if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kFuse | kOvl>), grid, block3, 0, stream, a);
-        else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kOvl>), grid, block3, 0, stream, a);
-    } else if (ovl) {
-        if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kFuse | kOvl>), grid, block3, 0, stream, a);
-        else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kOvl>), grid, block3, 0, stream, a);
-    } else if (a.N <= 23 && occ2) {        // (N <= 15 too: the short-scan build at two waves beats the one-row build at one)
-        hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kOcc2>), grid, dim3(dartmpc::kWave), 0, stream, a);
-    } else if (a.N <= 15 && a.B <= qscan_max_b) {
-        if (hipError_t e = dartmpc_launch_pmpc_seq(&a, grid.x, stream, 1)) return e;
-    } else if (a.N <= 23 && a.B <= qscan_max_b) {
-        if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kFuse>), grid, dim3(dartmpc::kWave), 0, stream, a);
-        else if (a.reduced)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2 | kRed>), grid, dim3(dartmpc::kWave), 0, stream, a);
-        else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kShort2>), grid, dim3(dartmpc::kWave), 0, stream, a);
-    } else if (a.N <= 31 && a.B <= qscan_max_b) {
-        if (occ2)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kOcc2>), grid, dim3(dartmpc::kWave), 0, stream, a);
-        else if (fuse)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kFuse>), grid, dim3(dartmpc::kWave), 0, stream, a);
-        else if (a.reduced)
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan | kRed>), grid, dim3(dartmpc::kWave), 0, stream, a);
-        else
-            hipLaunchKernelGGL((dartmpc::pmpc_ipm_kernel<1, kScan>), grid, dim3(dartmpc::kWave), 0, stream, a);
-    } else if (a.N > 31 && !a.reduced && !a.resto && long_wg2) {
-        if (hipError_t e = dartmpc_launch_pmpc_wg2(&a, grid.x, stream)) return e;
-    } else {
-        if (hipError_t e = dartmpc_launch_pmpc_seq(&a, grid.x, stream, 0)) return e;
-    }
-    if (a.resto == 1) {       // the instances whose line search failed, with IPOPT's restoration phases
-        if (hipError_t e = hipGetLastError()) return e;
-        return dartmpc_launch_pmpc_resto(&a, stream);
-    }
-    return hipGetLastError();
+    a.pack = p.pack;
+    a.resto = p.resto;
+    const unsigned grid = (unsigned)(a.B * a.pack), block = dartmpc::kWave * p.waves;
+    const hipError_t e =
+        p.object == dartmpc::kPmpcSeq   ? dartmpc_launch_pmpc_seq(&a, p.nax, p.f, grid, block, stream)
+        : p.object == dartmpc::kPmpcWg2 ? dartmpc_launch_pmpc_wg2(&a, p.nax, p.f, grid, block, stream)
+                                        : dartmpc::launch_build<dartmpc::IpmKernel, dartmpc::kPmpcMainIpm>(
+                                              p.nax, p.f, grid, block, stream, a);
+    if (e != hipSuccess || !p.resto_queued) return e;
+    return dartmpc_launch_pmpc_resto(&a, stream);
+}
+
+// internal (not part of include/dart_mpc.h), for tests: the plan the launcher of `solver` would use in this process
+// for the inputs `in`, as launch_plan.h's plan_query writes it; the number of ints written, -1 for an unknown solver
+extern "C" int dartmpc_plan_query(int solver, const int* in, int* out) {
+    return dartmpc::plan_query(solver, in, out, dartmpc::launch_knobs(), pmpc_occ2_min_b());
 }
 
 // internal (not part of include/dart_mpc.h): runs the wave-primitive self-test into device buffer d_out[131]

@@ -2,6 +2,7 @@
 // instances of a PMPC launch of more than 32 instances (smaller ones run them in the register kernel's own
 // wave, pmpc_ipm.hip).  One wave64 per instance slot; every slot whose status word is not kPmNeedResto
 // returns at once.
+#include "launch_plan.h"
 #include "pmpc_resto.h"
 
 namespace dartmpc {
@@ -20,7 +21,7 @@ extern "C" hipError_t dartmpc_launch_pmpc_resto(const dartmpc::PmpcArgs* args, h
     if (args->B <= 0) return hipSuccess;
     if (args->N < 1 || args->N >= dartmpc::PR_NMAXS) return hipErrorInvalidValue;
     dartmpc::PmpcArgs a = *args;
-    a.pack = (a.B <= 32) ? 8 : 1;
+    a.pack = dartmpc::xcd_pack(a.B);
     a.resto = 1;
     hipLaunchKernelGGL(dartmpc::pmpc_resto_kernel, dim3(a.B * a.pack), dim3(dartmpc::kWave), 0, stream, a);
     return hipGetLastError();

@@ -44,6 +44,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_plan.h"
 #include "ocp_wave.h"
 #include "rmpc_ipm.h"
 #include "stamps.h"
@@ -2183,21 +2184,32 @@ __global__ __launch_bounds__(kWave) void rls_update_kernel(int B, double* theta,
 
 }  // namespace dartmpc
 
+// What rmpc_plan (launch_plan.h) names, for either object built from this file: rmpc_ipm_kernel<false> for every
+// instance, then rmpc_ipm_kernel<true> for the instances whose line search failed, with IPOPT's restoration phases
+static hipError_t rmpc_launch_planned(const dartmpc::RmpcArgs& args, const dartmpc::RmpcPlan& p, hipStream_t stream) {
+    const dim3 block(dartmpc::kWave * dartmpc::kWaves);
+    dartmpc::RmpcArgs a = args;
+    a.pack = p.pack;
+    hipLaunchKernelGGL(dartmpc::rmpc_ipm_kernel<false>, dim3(a.B * a.pack), block, 0, stream, a);
+    if (p.second) {
+        if (hipError_t e = hipGetLastError()) return e;
+        // one block per instance (not B x pack; the blocks of the instances that were not handed over return at
+        // once): 4.39 -> 4.40 us per launch, the dispatch itself.  Inlining the restoration behind the solve instead
+        // costs C3 10.5 % (profiles/r05/rmpc_inline_ab.txt), a non-inlined call 4.7 % (fuse_ab.txt).
+        a.pack = 1;
+        hipLaunchKernelGGL(dartmpc::rmpc_ipm_kernel<true>, dim3(a.B), block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
 #if DART_WG == 2
 // N = 32..63 (dartmpc_launch_rmpc forwards here): one instance per two-wave workgroup
 extern "C" size_t dartmpc_rmpc_wg2_resto_bytes() { return sizeof(dartmpc::RmResto); }
 extern "C" hipError_t dartmpc_launch_rmpc_wg2(const void* args, hipStream_t stream) {
-    dartmpc::RmpcArgs a = *static_cast<const dartmpc::RmpcArgs*>(args);
-    if (a.N < (dartmpc::force_wg2() ? 1 : 32) || a.N >= dartmpc::RM_NMAXS) return hipErrorInvalidValue;
-    if (a.resto && !a.resto_buf) return hipErrorInvalidValue;
-    a.pack = 1;
-    const dim3 block(dartmpc::kWave * dartmpc::kWaves);
-    hipLaunchKernelGGL(dartmpc::rmpc_ipm_kernel<false>, dim3(a.B), block, 0, stream, a);
-    if (a.resto) {
-        if (hipError_t e = hipGetLastError()) return e;
-        hipLaunchKernelGGL(dartmpc::rmpc_ipm_kernel<true>, dim3(a.B), block, 0, stream, a);
-    }
-    return hipGetLastError();
+    const dartmpc::RmpcArgs& a = *static_cast<const dartmpc::RmpcArgs*>(args);
+    const dartmpc::RmpcPlan p = dartmpc::rmpc_plan(a.N, a.B, a.resto, a.resto_buf != nullptr, dartmpc::launch_knobs());
+    if (!p.valid || !p.wg2) return hipErrorInvalidValue;
+    return rmpc_launch_planned(a, p, stream);
 }
 #else
 
@@ -2219,22 +2231,11 @@ extern "C" int dartmpc_rmpc_blocks_per_cu(void) {
 
 extern "C" hipError_t dartmpc_launch_rmpc(const dartmpc::RmpcArgs* args, hipStream_t stream) {
     if (args->B <= 0) return hipSuccess;
-    if ((args->N >= dartmpc::RM_NMAXS || dartmpc::force_wg2()) && args->N < 2 * dartmpc::RM_NMAXS)
-        return dartmpc_launch_rmpc_wg2(args, stream);
-    if (args->N < 1 || args->N >= dartmpc::RM_NMAXS) return hipErrorInvalidValue;
-    dartmpc::RmpcArgs a = *args;
-    a.pack = (a.B <= 32) ? 8 : 1;            // blocks go round-robin over the 8 XCDs: one XCD, one L2 for the code
-    hipLaunchKernelGGL(dartmpc::rmpc_ipm_kernel<false>, dim3(a.B * a.pack), dim3(dartmpc::kWave), 0, stream, a);
-    if (a.resto) {      // the instances whose line search failed, with IPOPT's restoration phases
-        if (hipError_t e = hipGetLastError()) return e;
-        // one block per instance (not B x pack; the blocks of the instances that were not handed over return at
-        // once): 4.39 -> 4.40 us per launch, the dispatch itself.  Inlining the restoration behind the solve instead
-        // costs C3 10.5 % (profiles/r05/rmpc_inline_ab.txt), a non-inlined call 4.7 % (fuse_ab.txt).
-        dartmpc::RmpcArgs r = a;
-        r.pack = 1;
-        hipLaunchKernelGGL(dartmpc::rmpc_ipm_kernel<true>, dim3(r.B), dim3(dartmpc::kWave), 0, stream, r);
-    }
-    return hipGetLastError();
+    const dartmpc::RmpcPlan p =
+        dartmpc::rmpc_plan(args->N, args->B, args->resto, args->resto_buf != nullptr, dartmpc::launch_knobs());
+    if (p.wg2) return dartmpc_launch_rmpc_wg2(args, stream);
+    if (!p.valid) return hipErrorInvalidValue;
+    return rmpc_launch_planned(*args, p, stream);
 }
 
 #ifdef DART_STAMPS

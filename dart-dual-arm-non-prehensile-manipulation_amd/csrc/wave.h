@@ -25,34 +25,6 @@ __device__ __forceinline__ unsigned long long kernarg_addr() {
     return 0;
 #endif
 }
-// host: the fused restoration (restoration in the solving wave for B <= 32) unless DART_RESTO_FUSE=0 (A/B
-// experiments: the round-4 form, a queued restoration kernel behind every launch)
-inline bool resto_fuse_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DART_RESTO_FUSE");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-// host: PMPC batches of at most 32 at N = 16..31 take the overlapped builds (a second wave factors the Riccati
-// scan while the solving wave evaluates the point, pmpc_ipm.hip) unless DART_PMPC_OVERLAP=0 (the one-wave
-// builds everywhere, for A/B)
-inline bool pmpc_overlap_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DART_PMPC_OVERLAP");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-// host, diagnostic: DART_FORCE_WG2=1 runs RMPC and LMPC on their two-wave builds at every N (A/B of the two-wave
-// machinery against the one-wave kernels on the same instances; tools/wg2_ab.py)
-inline bool force_wg2() {
-    static const bool on = [] {
-        const char* e = getenv("DART_FORCE_WG2");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
 template <class T>
 __device__ __forceinline__ T kernarg_load(unsigned long long addr) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -63,16 +63,20 @@ def back_to_back(s, S, T, P, nw, launches):
                 w=WO.cpu().numpy())
 
 
-def run_settings(tmp_path_factory, script, tag, args=()):
-    """{setting: {name: array}} of a fresh child per setting: "0" (one-wave builds) and "default" (overlap on).  The
-    child is `script` run with an output directory and `args`."""
+OVERLAP_SETTINGS = {"0": {"DART_PMPC_OVERLAP": "0"}, "default": {}}
+# the launchers' knobs (csrc/launch_plan.h knobs_from_env): a child starts with none of them set
+KNOBS = ("DART_PMPC_OVERLAP", "DART_PMPC_OCC2_MIN_B", "DART_PMPC_QSCAN_MAX_B", "DART_PMPC_SEQ_LONG", "DART_RESTO_FUSE",
+         "DART_FORCE_WG2", "DART_PMPC_RESUME")
+
+
+def run_settings(tmp_path_factory, script, tag, args=(), settings=OVERLAP_SETTINGS):
+    """{setting: {name: array}} of a fresh child per setting ({name: its knobs}): by default "0" (one-wave builds) and
+    "default" (overlap on).  The child is `script` run with an output directory and `args`."""
     res = {}
-    for setting in ("0", "default"):
+    for setting, knobs in settings.items():
         outdir = str(tmp_path_factory.mktemp(f"{tag}_{setting}"))
-        env = dict(os.environ)
-        env.pop("DART_PMPC_OVERLAP", None)
-        if setting == "0":
-            env["DART_PMPC_OVERLAP"] = "0"
+        env = {k: v for k, v in os.environ.items() if k not in KNOBS}
+        env.update(knobs)
         r = subprocess.run([sys.executable, os.path.abspath(script), outdir] + list(args), env=env,
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, (setting, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
