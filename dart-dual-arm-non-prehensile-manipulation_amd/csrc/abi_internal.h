@@ -28,6 +28,7 @@
 #include "lmpc_experience.h"
 #include "lmpc_ppo.h"
 #include "lmpc_train.h"
+#include "lmpc_pbt.h"
 #include "arm_qp.h"
 #include "loop_step.h"
 

@@ -1,5 +1,7 @@
 // dart_mpc_train.hip -- the training entries of include/dart_mpc.h (host side): GAE, the PPO update
 // (lmpc_ppo.hip), the generator entries, the global buffer and whole training iterations (lmpc_train.hip).
+#include <limits>
+
 #include "abi_internal.h"
 
 namespace {
@@ -74,7 +76,14 @@ bool ppo_cfg_ok(const dart_lmpc_ppo_config* c) {
 struct PpoPop {
     int P = 0;
     size_t ws_stride = 0, idx_stride = 0;
+    const double* hyper = nullptr;      // device table [P][kHyperCols] (lmpc_ppo.h); null: the shared config
 };
+
+// the shared config as a row of the hyper-parameter table: its first nine doubles
+static_assert(offsetof(dart_lmpc_ppo_config, clip_eps) == 0 &&
+              offsetof(dart_lmpc_ppo_config, weight_decay) == sizeof(double) * (dartmpc::kHyperCols - 1) &&
+              DART_LMPC_HYPER_COLS == dartmpc::kHyperCols, "a config starts with a row of the table");
+const double* hyper_row(const dart_lmpc_ppo_config* c) { return &c->clip_eps; }
 
 // the launches of the PPO entries; ws is laid out for (n, mb) with M <= mb
 hipError_t ppo_launch_prepare(int n, long long total, const int32_t* sample, const double* adv, const double* ret,
@@ -98,15 +107,14 @@ hipError_t ppo_launch_grad(const dart_lmpc_ppo_config* c, int n, long long total
     const dartmpc::PpoWorkspace L = dartmpc::ppo_workspace(n, mb);
     dartmpc::PpoGradArgs a;
     a.n = n; a.M = M; a.rec_total = total;
-    a.clip_lo = (float)(1.0 - c->clip_eps); a.clip_hi = (float)(1.0 + c->clip_eps);
-    a.vf_coef = (float)c->vf_coef; a.ent_coef = (float)c->ent_coef;
+    dartmpc::ppo_hyper_set(a, dartmpc::ppo_hyper(hyper_row(c)));
     a.log_std_min = (float)c->log_std_min; a.log_std_max = (float)c->log_std_max;
     a.sample = sample; a.idx = idx; a.rec_obs = rec_obs; a.rec_action = rec_action; a.rec_logp = rec_logp;
     a.adv_n = reinterpret_cast<const float*>(ws + L.adv_n); a.ret_n = reinterpret_cast<const float*>(ws + L.ret_n);
     a.actor = weights; a.critic = critic;
     a.part = reinterpret_cast<float*>(ws + L.part); a.loss_part = reinterpret_cast<float*>(ws + L.loss_part);
     if (pop.P > 0) {
-        const dartmpc::PpoGradPopArgs q{a, pop.P, pop.ws_stride, pop.idx_stride};
+        const dartmpc::PpoGradPopArgs q{a, pop.P, pop.ws_stride, pop.idx_stride, pop.hyper};
         return dartmpc_launch_ppo_grad_pop(&q, s);
     }
     return dartmpc_launch_ppo_grad(&a, s);
@@ -121,9 +129,8 @@ hipError_t ppo_launch_apply(const dart_lmpc_ppo_config* c, int n, int M, bool fr
     dartmpc::PpoApplyArgs a;
     a.tiles = from_tiles ? (M + dartmpc::kPpoTile - 1) / dartmpc::kPpoTile : 1;
     a.M = M; a.do_step = do_step ? 1 : 0; a.step_in_call = step_in_call;
-    a.max_grad_norm = (float)c->max_grad_norm; a.lr = c->lr; a.beta1 = c->beta1;
-    a.beta2 = c->beta2; a.adam_eps = (float)c->adam_eps; a.weight_decay = (float)c->weight_decay;
-    a.ent_coef = (float)c->ent_coef; a.log_std_min = (float)c->log_std_min; a.log_std_max = (float)c->log_std_max;
+    dartmpc::ppo_hyper_set(a, dartmpc::ppo_hyper(hyper_row(c)));
+    a.log_std_min = (float)c->log_std_min; a.log_std_max = (float)c->log_std_max;
     a.part = from_tiles ? reinterpret_cast<const float*>(ws + L.part) : grad;
     a.loss_part = from_tiles ? reinterpret_cast<const float*>(ws + L.loss_part) : nullptr;
     a.terms_in = terms_in;
@@ -132,7 +139,7 @@ hipError_t ppo_launch_apply(const dart_lmpc_ppo_config* c, int n, int M, bool fr
     a.actor = weights; a.critic = critic; a.adam = adam; a.adam_step = adam_step;
     a.step_log = step_log; a.stat_sum = reinterpret_cast<double*>(ws + L.stat_sum); a.stats = stats;
     if (pop.P > 0) {
-        const dartmpc::PpoApplyPopArgs q{a, pop.P, pop.ws_stride};
+        const dartmpc::PpoApplyPopArgs q{a, pop.P, pop.ws_stride, pop.hyper};
         return dartmpc_launch_ppo_apply_pop(&q, s);
     }
     return dartmpc_launch_ppo_apply(&a, s);
@@ -837,14 +844,16 @@ hipError_t launch_global_log(const Learners& w, const dartmpc::GlobalLogArgs& a,
 
 // The device form of the training entries: whole iterations enqueued on one stream.  P = 0:
 // dart_lmpc_train_global_dev (g == nullptr: dart_lmpc_train_dev); P >= 1: dart_lmpc_train_pop_global_dev, every step
-// issued once for all P learners (the P buffers of g are stacked learner-major, g->capacity rows apart).  Every check
-// runs before the first launch.
+// issued once for all P learners (the P buffers of g are stacked learner-major, g->capacity rows apart), and with
+// `hyper` (device, [P][kHyperCols]) dart_lmpc_train_pop_hyper_dev: both updates' kernels read learner l's row when
+// they run, the host never does.  Every check runs before the first launch.
 int train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
               const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg,
               int P, const uint64_t* seeds, int B, int reset_rows, const dart_lmpc_train_buffers* p,
-              const dart_lmpc_global_buffer* g, void* stream) {
+              const dart_lmpc_global_buffer* g, void* stream, const double* hyper = nullptr) {
     DART_ENTER(h, -1);
     if (int rc = train_check(h, rcfg, ppo, cfg, B, p, true)) return rc;
+    if (hyper && P < 1) return fail(h, DART_MPC_EINVAL, "a hyper-parameter table needs a population");
     if (P > 0)
         if (int rc = pop_check(h, rcfg, cfg, P, seeds, B)) return rc;
     if (!aligned16(p->weights) || !aligned16(p->critic))
@@ -882,7 +891,7 @@ int train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmp
     double* stats = (double*)(ws + L.stats);
     int32_t* ep0 = (int32_t*)(ws + L.ep0);
     hipStream_t hs = (hipStream_t)s;
-    const PpoPop pop{P, L.ppo_stride, (size_t)ppo->epochs * n};
+    const PpoPop pop{P, L.ppo_stride, (size_t)ppo->epochs * n, hyper};
     // the global update's sizes, workspace and running fill, one for all learners (they share n; the host knows
     // every launch from n and g->fill)
     int gm = 0, gG = 0, g_fill = g ? g->fill : 0;
@@ -898,7 +907,7 @@ int train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmp
     int32_t* g_sample = (int32_t*)gp(GL.sample);
     int32_t* g_perm = (int32_t*)gp(GL.perm);
     double* g_stats = (double*)gp(GL.stats);
-    const PpoPop gpop{P, GL.ppo_stride, (size_t)ppo->epochs * gG};
+    const PpoPop gpop{P, GL.ppo_stride, (size_t)ppo->epochs * gG, hyper};
     const size_t stats_bytes = sizeof(double) * 3 * (size_t)w.count();
     HIPCHK(h, launch_sample(w, R, sample, hs), "sample list launch");
     for (int j = 0; j < cfg->iterations; ++j) {
@@ -967,9 +976,18 @@ int train_dev(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmp
 int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg,
                int P, const uint64_t* seeds, int B, int reset_rows, const dart_lmpc_train_buffers* p,
-               const dart_lmpc_global_buffer* g, void* stream) {
+               const dart_lmpc_global_buffer* g, void* stream, const double* hyper = nullptr) {
     DART_ENTER(h, -1);
     if (int rc = train_check(h, rcfg, ppo, cfg, B, p, false)) return rc;
+    if (hyper) {
+        // every row must be a config the entries would take: the shared one with the row in place of its first nine
+        if (P < 1 || P > DART_LMPC_POP_MAX) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+        for (int l = 0; l < P; ++l) {
+            dart_lmpc_ppo_config c = *ppo;
+            std::memcpy(&c, hyper + (size_t)l * dartmpc::kHyperCols, sizeof(double) * dartmpc::kHyperCols);
+            if (!ppo_cfg_ok(&c)) return fail(h, DART_MPC_EINVAL, "bad row of the hyper-parameter table");
+        }
+    }
     if (g)
         if (int rc = global_check(h, g, cfg->steps / rcfg->record_every * B, false)) return rc;
     if (h->cfg.variant != DART_MPC_LMPC) return fail(h, DART_MPC_EINVAL, "handle is not an LMPC handle");
@@ -1005,6 +1023,7 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
     const size_t ws_bytes =
         dartmpc::train_workspace(nl, learner_B, (int)K, rcfg->record_every, ppo->epochs, ppo->mini_batch_size).bytes;
     const int i_ws = S.add_log(nullptr, 1, ws_bytes, 0, 0, false);
+    const int i_hyper = hyper ? S.add(hyper, sizeof(double) * dartmpc::kHyperCols * (size_t)P, false) : -1;
     // the global buffer: blocks of the arena whose held rows travel by hand (those held at the start go up, those
     // held at the end come down), its log, and its workspace
     dart_lmpc_global_buffer gd;
@@ -1043,7 +1062,8 @@ int train_host(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lm
                        "copy global buffer");
             }
     }
-    if (int rc = train_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, learner_B, reset_rows, &d, g ? &gd : nullptr, s)) {
+    if (int rc = train_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, learner_B, reset_rows, &d, g ? &gd : nullptr, s,
+                           S.dev<double>(h, i_hyper))) {
         (void)hipStreamSynchronize(s);
         return rc;
     }
@@ -1119,6 +1139,27 @@ int dart_lmpc_train_pop_dev(dart_mpc_handle* h, const dart_plant_config* plant, 
     return dart_lmpc_train_pop_global_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, B, reset_rows, p, nullptr, stream);
 }
 
+// the population with a table of per-learner hyper-parameters (hyper == nullptr: dart_lmpc_train_pop_global_dev)
+int dart_lmpc_train_pop_hyper_dev(dart_mpc_handle* h, const dart_plant_config* plant,
+                                  const dart_lmpc_policy_config* pcfg, const dart_lmpc_reward_config* rcfg,
+                                  const dart_lmpc_ppo_config* ppo, const dart_lmpc_train_config* cfg, int P,
+                                  const uint64_t* seeds, int B, int reset_rows, const dart_lmpc_train_buffers* p,
+                                  const dart_lmpc_global_buffer* g, const double* hyper, void* stream) {
+    DART_ENTER(h, -1);
+    if (P < 1) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+    return train_dev(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, B, reset_rows, p, g, stream, hyper);
+}
+
+int dart_lmpc_train_pop_hyper(dart_mpc_handle* h, const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
+                              const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
+                              const dart_lmpc_train_config* cfg, int P, const uint64_t* seeds, int B, int reset_rows,
+                              const dart_lmpc_train_buffers* p, const dart_lmpc_global_buffer* g, const double* hyper,
+                              void* stream) {
+    DART_ENTER(h, -1);
+    if (P < 1) return fail(h, DART_MPC_EINVAL, "population: 1 <= P <= DART_LMPC_POP_MAX");
+    return train_host(h, plant, pcfg, rcfg, ppo, cfg, P, seeds, B, reset_rows, p, g, stream, hyper);
+}
+
 // (g == nullptr: dart_lmpc_train)
 int dart_lmpc_train_global(dart_mpc_handle* h,const dart_plant_config* plant, const dart_lmpc_policy_config* pcfg,
                            const dart_lmpc_reward_config* rcfg, const dart_lmpc_ppo_config* ppo,
@@ -1151,4 +1192,90 @@ int dart_lmpc_train(dart_mpc_handle* h, const dart_plant_config* plant, const da
                     const dart_lmpc_train_config* cfg, int B, int reset_rows, const dart_lmpc_train_buffers* p,
                     void* stream) {
     return dart_lmpc_train_global(h, plant, pcfg, rcfg, ppo, cfg, B, reset_rows, p, nullptr, stream);
+}
+
+// ---- the exploit/explore step of population-based training (lmpc_pbt.hip) ----------------------------------------
+
+void dart_lmpc_pbt_config_default(dart_lmpc_pbt_config* c) {
+    if (!c) return;
+    const double inf = std::numeric_limits<double>::infinity();
+    c->seed = 0; c->generation = 0; c->n_replace = 0; c->higher_is_better = 0;
+    c->explore_mask = (1u << 4) | (1u << 0) | (1u << 2);            // lr | clip_eps | ent_coef
+    c->factor_down = 0.8; c->factor_up = 1.25;
+    // clip_eps, vf_coef, ent_coef, max_grad_norm, lr, beta1, beta2, adam_eps, weight_decay
+    const double lo[DART_LMPC_HYPER_COLS] = {0.01, -inf, 0.0, 0.0, 1e-6, 0.0, 0.0, 0.0, -inf};
+    const double hi[DART_LMPC_HYPER_COLS] = {0.5, inf, 0.1, inf, 1e-2, 0.999999, 0.999999, inf, inf};
+    for (int i = 0; i < DART_LMPC_HYPER_COLS; ++i) { c->lo[i] = lo[i]; c->hi[i] = hi[i]; }
+}
+
+namespace {
+
+// k of the step (0: P / 4), or -1 for a config or shape the entries refuse
+int pbt_check(const dart_lmpc_pbt_config* c, int P, int fitness_stride) {
+    if (!c || P < 1 || P > DART_LMPC_POP_MAX || fitness_stride < 1 || c->generation < 0 || c->n_replace < 0) return -1;
+    const int k = c->n_replace == 0 ? P / 4 : c->n_replace;
+    if (2 * (long long)k > P) return -1;
+    if (!(c->factor_down > 0.0) || !(c->factor_up > 0.0)) return -1;
+    for (int i = 0; i < DART_LMPC_HYPER_COLS; ++i)
+        if (!(c->lo[i] <= c->hi[i])) return -1;                     // (a NaN bound fails the comparison)
+    return k;
+}
+
+hipError_t pbt_launch(const dart_lmpc_pbt_config* c, int P, int k, const double* fitness, int fitness_stride,
+                      float* weights, float* critic, float* adam, int32_t* adam_step, double* hyper,
+                      int32_t* rank_out, int32_t* parent_out, hipStream_t s) {
+    dartmpc::PbtRankArgs r;
+    r.P = P; r.k = k; r.higher_is_better = c->higher_is_better; r.fitness_stride = fitness_stride;
+    r.key0 = (uint32_t)(c->seed & 0xffffffffu); r.key1 = (uint32_t)(c->seed >> 32);
+    r.generation = (uint32_t)c->generation; r.explore_mask = c->explore_mask;
+    r.factor_down = c->factor_down; r.factor_up = c->factor_up;
+    for (int i = 0; i < DART_LMPC_HYPER_COLS; ++i) { r.lo[i] = c->lo[i]; r.hi[i] = c->hi[i]; }
+    r.fitness = fitness; r.hyper = hyper; r.rank_out = rank_out; r.parent_out = parent_out;
+    hipError_t e = dartmpc_launch_lmpc_pbt_rank(&r, s);
+    if (e != hipSuccess || k == 0) return e;                        // (no child: nothing to copy)
+    const dartmpc::PbtCopyArgs q{P, parent_out, weights, critic, adam, adam_step};
+    return dartmpc_launch_lmpc_pbt_copy(&q, s);
+}
+
+}  // namespace
+
+int dart_lmpc_pbt_step_dev(const dart_lmpc_pbt_config* cfg, int P, const double* fitness, int fitness_stride,
+                           float* weights, float* critic, float* adam, int32_t* adam_step, double* hyper,
+                           int32_t* rank_out, int32_t* parent_out, void* stream) {
+    const int k = pbt_check(cfg, P, fitness_stride);
+    if (k < 0 || any_null({fitness, weights, critic, adam, adam_step, hyper, rank_out, parent_out}))
+        return DART_MPC_EINVAL;
+    if (!aligned16(weights) || !aligned16(critic)) return DART_MPC_EINVAL;
+    return pbt_launch(cfg, P, k, fitness, fitness_stride, weights, critic, adam, adam_step, hyper, rank_out,
+                      parent_out, (hipStream_t)stream) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
+int dart_lmpc_pbt_step(const dart_lmpc_pbt_config* cfg, int P, const double* fitness, int fitness_stride,
+                       float* weights, float* critic, float* adam, int32_t* adam_step, double* hyper,
+                       int32_t* rank_out, int32_t* parent_out) {
+    const int k = pbt_check(cfg, P, fitness_stride);
+    if (k < 0 || any_null({fitness, weights, critic, adam, adam_step, hyper, rank_out, parent_out}))
+        return DART_MPC_EINVAL;
+    DART_DEVICE_STAGE(D, S);
+    const size_t nP = (size_t)P, F = sizeof(float);
+    const size_t bytes = sizeof(double) * nP * (1 + DART_LMPC_HYPER_COLS) + 3 * sizeof(int32_t) * nP +
+                         F * nP * (dartmpc::kPpoActorN + dartmpc::kPopCriticStride + 2 * (size_t)dartmpc::kPpoParams);
+    if (S.reserve(bytes + 10 * 256, 0) != hipSuccess) return DART_MPC_EHIP;
+    S.begin();
+    // only the learners' own entries of the fitness travel (the device entry is handed stride 1)
+    const double* d_fit = S.in_with<double>(nP, [&](double* q) {
+        for (size_t l = 0; l < nP; ++l) q[l] = fitness[l * (size_t)fitness_stride];
+    });
+    float* d_w = S.inout(weights, nP * dartmpc::kPpoActorN);        // (every block of the stage is 256-byte aligned)
+    float* d_c = S.inout(critic, nP * dartmpc::kPopCriticStride);
+    float* d_adam = S.inout(adam, nP * 2 * dartmpc::kPpoParams);
+    int32_t* d_step = S.inout(adam_step, nP);
+    double* d_hyper = S.inout(hyper, nP * DART_LMPC_HYPER_COLS);
+    int32_t* d_rank = S.inout(rank_out, nP);
+    int32_t* d_par = S.inout(parent_out, nP);
+    auto launch = [&](hipStream_t s) {
+        return pbt_launch(cfg, P, k, d_fit, 1, d_w, d_c, d_adam, d_step, d_hyper, d_rank, d_par, s);
+    };
+    if (!D->run(launch)) return DART_MPC_EHIP;
+    return DART_MPC_OK;
 }

@@ -104,6 +104,33 @@ struct PpoApplyArgs {
     double* stats;              // [3] running means, nullable
 };
 
+// The hyper-parameters a learner may own (dart_lmpc_train_pop_hyper): a row of kHyperCols doubles, the first nine of
+// dart_lmpc_ppo_config in the struct's order (clip_eps, vf_coef, ent_coef, max_grad_norm, lr, beta1, beta2, adam_eps,
+// weight_decay), and what the kernels take of them.  The conversion is stated here alone: the host launchers apply it
+// to the shared config and the population's kernels to row l of the table, so a row that equals a config gives that
+// config's launch arguments bit for bit.  The values enter arithmetic only, never an index or a trip count.
+constexpr int kHyperCols = 9;
+struct PpoHyper {
+    float clip_lo, clip_hi;     // 1 - clip_eps, 1 + clip_eps, formed in fp64
+    float vf_coef, ent_coef, max_grad_norm, adam_eps, weight_decay;
+    double lr, beta1, beta2;
+};
+__host__ __device__ inline PpoHyper ppo_hyper(const double* row) {
+    PpoHyper h;
+    h.clip_lo = (float)(1.0 - row[0]); h.clip_hi = (float)(1.0 + row[0]);
+    h.vf_coef = (float)row[1]; h.ent_coef = (float)row[2]; h.max_grad_norm = (float)row[3];
+    h.lr = row[4]; h.beta1 = row[5]; h.beta2 = row[6];
+    h.adam_eps = (float)row[7]; h.weight_decay = (float)row[8];
+    return h;
+}
+__host__ __device__ inline void ppo_hyper_set(PpoGradArgs& a, const PpoHyper& h) {
+    a.clip_lo = h.clip_lo; a.clip_hi = h.clip_hi; a.vf_coef = h.vf_coef; a.ent_coef = h.ent_coef;
+}
+__host__ __device__ inline void ppo_hyper_set(PpoApplyArgs& a, const PpoHyper& h) {
+    a.max_grad_norm = h.max_grad_norm; a.lr = h.lr; a.beta1 = h.beta1; a.beta2 = h.beta2;
+    a.adam_eps = h.adam_eps; a.weight_decay = h.weight_decay; a.ent_coef = h.ent_coef;
+}
+
 struct CriticValueArgs {
     int n;
     const float* critic;
@@ -122,15 +149,19 @@ struct PpoPreparePopArgs {      // one workgroup per learner
     int P;
     size_t ws_stride;
 };
+// hyper (device, nullable): the table [P][kHyperCols]; learner l takes ppo_hyper(row l) in place of a's values, read
+// when the kernel runs.  Null: every learner runs with a's.
 struct PpoGradPopArgs {         // grid (tiles, 2, P)
     PpoGradArgs a;
     int P;
     size_t ws_stride, idx_stride;
+    const double* hyper;
 };
 struct PpoApplyPopArgs {        // one workgroup per learner
     PpoApplyArgs a;             // terms_in, step_log: null
     int P;
     size_t ws_stride;
+    const double* hyper;
 };
 struct CriticValuePopArgs {     // grid (tiles of a.n, P): learner l's critic on rows l a.n .. (l + 1) a.n - 1
     CriticValueArgs a;

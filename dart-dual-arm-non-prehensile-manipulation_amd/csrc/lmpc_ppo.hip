@@ -8,7 +8,9 @@
 // critic_value_kernel  value_net on [n][520] observations (the bootstrap value of :776-779)
 // *_pop_kernel         the four above for a population of P learners in one launch (dart_lmpc_train_pop_dev): the
 //                      learner is a grid coordinate, the body is the single kernel's on arguments moved to that
-//                      learner's sample list, permutation rows, nets, Adam state and workspace (lmpc_ppo.h)
+//                      learner's sample list, permutation rows, nets, Adam state and workspace (lmpc_ppo.h); with a
+//                      hyper-parameter table (dart_lmpc_train_pop_hyper_dev) the gradient and the apply kernel also
+//                      take the learner's row of it in place of the shared config's values (ppo_hyper)
 // critic_value_stride_pop_kernel  critic_value_pop_kernel with the learners' observations a given number of rows
 //                      apart: the bootstrap values of a population's global-buffer update (row G - 1 of P buffers)
 //
@@ -291,6 +293,7 @@ __global__ __launch_bounds__(kGradThreads) void ppo_grad_pop_kernel(PpoGradPopAr
     a.adv_n = moved(a.adv_n, ws); a.ret_n = moved(a.ret_n, ws);
     a.actor += l * kPpoActorN; a.critic += l * kPopCriticStride;
     a.part = moved(a.part, ws); a.loss_part = moved(a.loss_part, ws);
+    if (p.hyper) ppo_hyper_set(a, ppo_hyper(p.hyper + l * kHyperCols));     // block-uniform
     ppo_grad_body(a);
 }
 
@@ -435,6 +438,7 @@ __global__ __launch_bounds__(kOneWg) void ppo_apply_pop_kernel(PpoApplyPopArgs p
     a.actor += l * kPpoActorN; a.critic += l * kPopCriticStride;
     a.adam += l * 2 * (size_t)kPpoParams; a.adam_step += l;
     if (a.stats) a.stats += 3 * l;
+    if (p.hyper) ppo_hyper_set(a, ppo_hyper(p.hyper + l * kHyperCols));     // block-uniform
     ppo_apply_body(a);
 }
 

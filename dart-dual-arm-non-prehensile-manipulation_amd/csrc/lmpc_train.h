@@ -25,6 +25,8 @@ constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 constexpr uint32_t kStreamNoise = 0, kStreamPerm = 1;
 // the global-buffer update (rlmpc2.py:823-874): its draw without replacement and its mini-batch permutations
 constexpr uint32_t kStreamChoice = 2, kStreamGlobalPerm = 3;
+// the exploit/explore step of a population (lmpc_pbt.h): counter (learner, generation, 4, block)
+constexpr uint32_t kStreamPbt = 4;
 
 struct Philox4 { uint32_t w[4]; };
 

@@ -62,7 +62,9 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_pmpc_lm_loop_step_dev", "dart_pmpc_lm_rollout_dev", "dart_pmpc_lm_rollout",
            "dart_rmpc_lm_loop_step_dev", "dart_rmpc_lm_rollout_dev", "dart_rmpc_lm_rollout",
            "dart_lmpc_eval_loop_step_dev", "dart_lmpc_eval_dev", "dart_lmpc_eval", "dart_lmpc_eval_scores_dev",
-           "dart_lmpc_eval_scores")
+           "dart_lmpc_eval_scores",
+           "dart_lmpc_train_pop_hyper_dev", "dart_lmpc_train_pop_hyper", "dart_lmpc_pbt_config_default",
+           "dart_lmpc_pbt_step_dev", "dart_lmpc_pbt_step")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -109,6 +111,19 @@ class PpoConfig(ctypes.Structure):
                 ("beta2", ctypes.c_double), ("adam_eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
                 ("log_std_min", ctypes.c_double), ("log_std_max", ctypes.c_double), ("epochs", ctypes.c_int32),
                 ("mini_batch_size", ctypes.c_int32)]
+
+
+HYPER_COLS = 9                  # DART_LMPC_HYPER_COLS: columns of a population's hyper-parameter table
+# the table's columns: the first nine doubles of dart_lmpc_ppo_config in the struct's order
+HYPER_FIELDS = tuple(f[0] for f in PpoConfig._fields_[:HYPER_COLS])
+
+
+class PbtConfig(ctypes.Structure):
+    """Mirror of ``struct dart_lmpc_pbt_config`` (the exploit/explore step of population-based training)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("generation", ctypes.c_int32), ("n_replace", ctypes.c_int32),
+                ("higher_is_better", ctypes.c_int32), ("explore_mask", ctypes.c_uint32),
+                ("factor_down", ctypes.c_double), ("factor_up", ctypes.c_double),
+                ("lo", ctypes.c_double * HYPER_COLS), ("hi", ctypes.c_double * HYPER_COLS)]
 
 
 class TrainConfig(ctypes.Structure):
@@ -434,6 +449,16 @@ def lib():
         for fn in (L.dart_lmpc_choice_pop_dev, L.dart_lmpc_global_append_pop_dev, L.dart_lmpc_gae_seq_pop_dev,
                    L.dart_lmpc_train_pop_global_dev, L.dart_lmpc_train_pop_global):
             fn.restype = ctypes.c_int
+    if hasattr(L, "dart_lmpc_pbt_step_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        for fn in (L.dart_lmpc_train_pop_hyper_dev, L.dart_lmpc_train_pop_hyper):
+            fn.argtypes = [vp] * 6 + [ci, vp, ci, ci, vp, vp, vp, vp]
+            fn.restype = ctypes.c_int
+        L.dart_lmpc_pbt_config_default.argtypes = [ctypes.POINTER(PbtConfig)]
+        L.dart_lmpc_pbt_config_default.restype = None
+        L.dart_lmpc_pbt_step_dev.argtypes = [vp, ci, vp, ci] + [vp] * 8
+        L.dart_lmpc_pbt_step.argtypes = [vp, ci, vp, ci] + [vp] * 7
+        L.dart_lmpc_pbt_step_dev.restype = L.dart_lmpc_pbt_step.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
         L.dart_mpc_bind.restype = ctypes.c_int
@@ -1358,12 +1383,37 @@ class LmpcSolver(Solver):
                         weights, critic, state, cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant,
                         stream)
 
+    def train_pop_hyper_dev(self, P, seeds, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state,
+                            cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, gbuf=None, hyper=0, pool=None,
+                            plant=None, stream=0):
+        """``train_pop_global_dev`` with per-learner hyper-parameters (dart_lmpc_train_pop_hyper_dev): ``hyper`` is
+        the device pointer of a float64 table [P, HYPER_COLS] (``hyper_table``), row l the first nine fields of
+        ``ppo_cfg`` for learner l (HYPER_FIELDS), read by the update's kernels when they run -- a table rewritten on
+        the same stream between two calls takes effect.  ``hyper`` 0 is ``train_pop_global_dev``, ``gbuf`` None no
+        global update.  Learner l is bit for bit ``train_global_dev`` with ``ppo_config(**row l)``."""
+        _train_dev(self, "train_pop_hyper_dev", (P, seeds), (gbuf,), B, reset_rows, target, prm, plant_pvec, current_k,
+                   weights, critic, state, cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant,
+                   stream, hyper=(hyper,))
+
+    @staticmethod
+    def pbt_step_dev(cfg, P, fitness, fitness_stride, weights, critic, adam, adam_step, hyper, rank_out, parent_out,
+                     stream=0):
+        """The exploit/explore step of population-based training on device pointers (dart_lmpc_pbt_step_dev;
+        asynchronous): ``cfg`` is a ``pbt_config``, ``fitness`` + l ``fitness_stride`` learner l's figure of merit
+        (float64; ``scores + 8 * slot, 8`` reads a column of ``evaluate_dev``'s scores), the other arrays those of
+        ``train_pop_dev`` and the table of ``train_pop_hyper_dev``; ``rank_out`` and ``parent_out`` are int32 [P].
+        ``ppo.pbt_plan`` states the rule in numpy."""
+        _rc(lib().dart_lmpc_pbt_step_dev(ctypes.byref(cfg), int(P), _vp(fitness), int(fitness_stride), _vp(weights),
+                                         _vp(critic), _vp(adam), _vp(adam_step), _vp(hyper), _vp(rank_out),
+                                         _vp(parent_out), stream or None), "dart_lmpc_pbt_step_dev")
+
     def _train_host(self, entry, who, B, nl, nets, target, plant_pvec, state, cstate, logs, clogs, rec, pcfg, adam,
                     adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg, prm, pool, plant,
-                    global_buffer, global_log):
+                    global_buffer, global_log, hyper=None):
         """``train`` and ``train_pop``: ``nl`` learners of ``B`` instances each, their arrays stacked; ``nets`` are
         the checked current_k, actor and critic arrays, ``who`` is () or (P, the seeds' pointer).  With
-        ``global_buffer`` the entry is ``entry`` + "_global"."""
+        ``global_buffer`` the entry is ``entry`` + "_global"; with ``hyper`` (a checked table) it is ``entry`` +
+        "_hyper", which takes the buffer (or NULL) and the table."""
         NI, K = state["x"].shape[0], int(tcfg.steps)
         rcfg = rcfg if rcfg is not None else reward_config()
         R = K // max(int(rcfg.record_every), 1)
@@ -1387,9 +1437,13 @@ class LmpcSolver(Solver):
         if global_buffer is not None:
             g = [_host_global(global_buffer, nl * int(tcfg.iterations), global_log, learners=nl)]
             entry += "_global"
+        tail = [ctypes.byref(q) for q in g]
+        if hyper is not None:
+            entry = entry[:-len("_global")] if g else entry
+            entry += "_hyper"
+            tail = (tail or [None]) + [_ptr(hyper)]
         rc = getattr(lib(), entry)(self._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg),
-                                   ctypes.byref(ppo_cfg), ctypes.byref(tcfg), *who, B, reset_rows, buf,
-                                   *[ctypes.byref(q) for q in g], None)
+                                   ctypes.byref(ppo_cfg), ctypes.byref(tcfg), *who, B, reset_rows, buf, *tail, None)
         if rc != 0:
             self._err(rc, entry)
         if g:
@@ -1397,7 +1451,7 @@ class LmpcSolver(Solver):
 
     def train_pop(self, P, seeds, target, plant_pvec, state, cstate, logs, clogs, rec, pcfg, weights, critic, current_k,
                   adam, adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None,
-                  pool=None, plant=None, global_buffer=None, global_log=None):
+                  pool=None, plant=None, global_buffer=None, global_log=None, hyper=None):
         """Host arrays (blocking, dart_lmpc_train_pop): ``train`` for ``P`` learners, all arrays stacked as
         ``train_pop_dev`` takes them (``ppo.population_stack`` builds them, ``ppo.train_population`` wraps this) and
         updated in place: ``weights`` [P, 39748], ``critic`` [P, POP_CRITIC_STRIDE], ``current_k`` [P B, 34], ``adam``
@@ -1405,8 +1459,14 @@ class LmpcSolver(Solver):
         [P, 77317], ``best_iter`` [P]; ``state`` / ``cstate`` hold P B instances.  With ``global_buffer`` (a
         ``ppo.new_population_global_buffer`` dict: P stacked buffers and one ``fill``) every iteration also runs the
         global-buffer update (dart_lmpc_train_pop_global): the dict's arrays and ``fill`` are updated in place and
-        ``global_log`` [P, iterations, 6] (float64) receives one row per learner and iteration."""
+        ``global_log`` [P, iterations, 6] (float64) receives one row per learner and iteration.  With ``hyper`` (a
+        float64 table [P, HYPER_COLS], ``hyper_table``; read only) learner l trains with row l in place of the first
+        nine fields of ``ppo_cfg`` (dart_lmpc_train_pop_hyper); None takes the entries above, unchanged."""
         P, NI = int(P), state["x"].shape[0]
+        if hyper is not None:
+            hyper = np.ascontiguousarray(hyper, np.float64)
+            if hyper.shape != (P, HYPER_COLS):
+                raise DartMPCError(f"train_pop: hyper must have shape {(P, HYPER_COLS)}, got {hyper.shape}")
         B = NI // max(P, 1)
         if P >= 1 and B * P != NI:
             raise DartMPCError(f"train_pop: {NI} instances are not {P} learners of equal size")
@@ -1419,7 +1479,7 @@ class LmpcSolver(Solver):
                 _inplace(critic, np.float32, nl * POP_CRITIC_STRIDE, "critic"))
         self._train_host("dart_lmpc_train_pop", (P, _ptr(seeds)), B, nl, nets, target, plant_pvec, state, cstate, logs,
                          clogs, rec, pcfg, adam, adam_step, train_log, best_return, best_weights, best_iter, ppo_cfg,
-                         tcfg, rcfg, prm, pool, plant, global_buffer, global_log)
+                         tcfg, rcfg, prm, pool, plant, global_buffer, global_log, hyper=hyper)
 
     def train(self, target, plant_pvec, state, cstate, logs, clogs, rec, policy, adam, adam_step, train_log,
               best_return, best_weights, best_iter, ppo_cfg, tcfg, rcfg=None, prm=None, pool=None, plant=None,
@@ -1505,6 +1565,80 @@ def ppo_config(**over) -> PpoConfig:
             raise DartMPCError(f"PpoConfig has no field {k!r} (fields: {names})")
         setattr(c, k, int(v) if k in ("epochs", "mini_batch_size") else float(v))
     return c
+
+
+def hyper_table(P, **over):
+    """A population's hyper-parameter table, float64 [P, HYPER_COLS]: every row the library's defaults for
+    HYPER_FIELDS (the first nine fields of ``ppo_config()``, in its order), each field overridden by keyword with a
+    scalar (all learners) or a sequence of P values (one per learner)."""
+    P = int(P)
+    if not 1 <= P <= POP_MAX:
+        raise DartMPCError(f"hyper_table: 1 <= P <= {POP_MAX}, got {P}")
+    c = ppo_config()
+    t = np.tile(np.array([getattr(c, f) for f in HYPER_FIELDS], np.float64), (P, 1))
+    for k, v in over.items():
+        if k not in HYPER_FIELDS:
+            raise DartMPCError(f"hyper_table has no column {k!r} (columns: {HYPER_FIELDS})")
+        v = np.asarray(v, np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.size != P):
+            raise DartMPCError(f"hyper_table: {k!r} takes a scalar or {P} values, got shape {v.shape}")
+        t[:, HYPER_FIELDS.index(k)] = v
+    return t
+
+
+def pbt_config(**over) -> PbtConfig:
+    """``dart_lmpc_pbt_config`` with the library's defaults, fields overridden by keyword: ``lo`` / ``hi`` take
+    HYPER_COLS values or a dict column name -> bound, ``explore_mask`` an integer or a sequence of column names."""
+    c = PbtConfig()
+    lib().dart_lmpc_pbt_config_default(ctypes.byref(c))
+    names = [f[0] for f in c._fields_]
+    for k, v in over.items():
+        if k not in names:
+            raise DartMPCError(f"PbtConfig has no field {k!r} (fields: {names})")
+        if k in ("lo", "hi"):
+            arr = getattr(c, k)
+            if isinstance(v, dict):
+                for name, b in v.items():
+                    if name not in HYPER_FIELDS:
+                        raise DartMPCError(f"pbt_config: no column {name!r} (columns: {HYPER_FIELDS})")
+                    arr[HYPER_FIELDS.index(name)] = float(b)
+            else:
+                v = np.asarray(v, np.float64).reshape(-1)
+                if v.size != HYPER_COLS:
+                    raise DartMPCError(f"pbt_config: {k} takes {HYPER_COLS} values, got {v.size}")
+                for i in range(HYPER_COLS):
+                    arr[i] = float(v[i])
+        elif k == "explore_mask" and not isinstance(v, (int, np.integer)):
+            bad = [n for n in v if n not in HYPER_FIELDS]
+            if bad:
+                raise DartMPCError(f"pbt_config: no column {bad[0]!r} (columns: {HYPER_FIELDS})")
+            c.explore_mask = sum(1 << HYPER_FIELDS.index(n) for n in set(v))
+        elif k in ("factor_down", "factor_up"):
+            setattr(c, k, float(v))
+        else:
+            setattr(c, k, int(v))
+    return c
+
+
+def pbt_step(cfg, fitness, weights, critic, adam, adam_step, hyper, fitness_stride=1):
+    """The exploit/explore step on host arrays (blocking, dart_lmpc_pbt_step): ``weights`` [P, 39748], ``critic``
+    [P, POP_CRITIC_STRIDE], ``adam`` [P, 2, 77317], ``adam_step`` [P] and ``hyper`` [P, HYPER_COLS] are updated in
+    place; ``fitness`` (float64) is read at ``l * fitness_stride``.  Returns (rank, parent), int32 [P]."""
+    hyper_a = np.asarray(hyper)
+    P = hyper_a.shape[0] if hyper_a.ndim == 2 else 0
+    fitness = np.ascontiguousarray(fitness, np.float64).reshape(-1)
+    if P >= 1 and int(fitness_stride) >= 1 and fitness.size < (P - 1) * int(fitness_stride) + 1:
+        raise DartMPCError(f"pbt_step: fitness holds {fitness.size} values, stride {fitness_stride} needs "
+                           f"{(P - 1) * int(fitness_stride) + 1}")
+    nl = max(P, 1)
+    arrs = (_inplace(weights, np.float32, nl * ACTOR_NWEIGHTS, "weights"),
+            _inplace(critic, np.float32, nl * POP_CRITIC_STRIDE, "critic"),
+            _inplace(adam, np.float32, nl * 2 * PPO_NPARAMS, "adam"), _inplace(adam_step, np.int32, nl, "adam_step"),
+            _inplace(hyper, np.float64, nl * HYPER_COLS, "hyper"))
+    rank, parent = np.full(nl, -1, np.int32), np.full(nl, -1, np.int32)
+    _rc(lib().dart_lmpc_pbt_step(ctypes.byref(cfg), P, _ptr(fitness), int(fitness_stride), *[_ptr(a) for a in arrs],
+                                 _ptr(rank), _ptr(parent)), "dart_lmpc_pbt_step")
+    return rank, parent
 
 
 def ppo_workspace_bytes(n, mini_batch_size):
@@ -1665,10 +1799,11 @@ def _train_buffers(values):
 
 
 def _train_dev(solver, entry, who, gbuf, B, reset_rows, target, prm, plant_pvec, current_k, weights, critic, state,
-               cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant, stream):
-    """The four device training entries of ``LmpcSolver``: ``entry`` names the C function, ``who`` is () or (P, seeds)
-    and ``gbuf`` () or (the ``global_buffer`` struct or None,), each passed where the entry takes it.  (``solver`` is
-    any handle's wrapper: the library refuses one that is not an LMPC handle.)"""
+               cstate, logs, clogs, rec, train, pcfg, rcfg, ppo_cfg, tcfg, pool, plant, stream, hyper=()):
+    """The device training entries of ``LmpcSolver``: ``entry`` names the C function, ``who`` is () or (P, seeds),
+    ``gbuf`` () or (the ``global_buffer`` struct or None,) and ``hyper`` () or (the table's device pointer or 0,), each
+    passed where the entry takes it.  (``solver`` is any handle's wrapper: the library refuses one that is not an LMPC
+    handle.)"""
     if who:
         P, seeds = who
         seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(-1)
@@ -1684,7 +1819,7 @@ def _train_dev(solver, entry, who, gbuf, B, reset_rows, target, prm, plant_pvec,
     rc = getattr(lib(), "dart_lmpc_" + entry)(
         solver._h, ctypes.byref(plant), ctypes.byref(pcfg), ctypes.byref(rcfg), ctypes.byref(ppo_cfg),
         ctypes.byref(tcfg), *who, int(B), int(reset_rows), buf,
-        *[ctypes.byref(g) if g is not None else None for g in gbuf], stream or None)
+        *[ctypes.byref(g) if g is not None else None for g in gbuf], *[_vp(q) for q in hyper], stream or None)
     if rc != 0:
         solver._err(rc, "dart_lmpc_" + entry)
 

@@ -12,6 +12,10 @@ GAE, permutations, update, the mean-based parameter write, log row and best-poli
 the iterations also contain the loop's second update on the global buffer (:823-874).  ``save_checkpoint`` /
 ``load_checkpoint`` keep a training state, the global buffer included when given, in one ``.npz`` of plain arrays (no
 pickle); its fields stand in for the reference's ``best_agent.pth`` / ``latest_agent.pth``, which are not loaded.
+A population (``train_population``) may train with one row of hyper-parameters per learner (``hyper_table=``,
+``_lib.hyper_table``); ``pbt_plan`` states the exploit/explore step of population-based training in numpy, ``pbt_step``
+runs it through the library on host arrays, and ``train_pbt`` chains training, evaluation and the step on one stream
+(csrc/lmpc_pbt.hip).
 """
 from __future__ import annotations
 
@@ -350,7 +354,8 @@ def population_noise(seeds, iteration, steps, B):
 
 def train_population(solver, policies, target, plant_pvec, state, cstate, adam, adam_step, best, steps, seeds,
                      iterations=1, it0=0, rcfg=None, pool=None, prm=None, gamma=0.99, lam=0.95, mean_update=True,
-                     track_best=True, epochs=8, mini_batch_size=64, out=None, global_buffer=None, **hyper):
+                     track_best=True, epochs=8, mini_batch_size=64, out=None, global_buffer=None, hyper_table=None,
+                     **hyper):
     """``train_device`` for a population: ``policies`` is a list of P ``LmpcPolicy(B, ...)`` that share one config,
     the other arrays are stacked learner-major as ``population_stack`` lays them out (``target`` [P B, 8], ``state``
     / ``cstate`` of P B instances, ``adam`` [P, 2, 77317], ``adam_step`` [P], ``best`` = ``new_population_best(P)``,
@@ -362,7 +367,11 @@ def train_population(solver, policies, target, plant_pvec, state, cstate, adam, 
     With ``global_buffer`` (``new_population_global_buffer(P, n)``, or ``population_stack``'s) every iteration also
     runs the global-buffer update for every learner (``LmpcSolver.train_pop`` with the buffer): learner l is then bit
     for bit ``train_device(..., global_buffer=population_member(l, ...)["global_buffer"])``.  The dict is updated in
-    place, ``fill`` included, and every returned row gains the keys of ``_lib.GLOBAL_LOG_FIELDS``."""
+    place, ``fill`` included, and every returned row gains the keys of ``_lib.GLOBAL_LOG_FIELDS``.
+
+    With ``hyper_table`` (float64 [P, HYPER_COLS], ``_lib.hyper_table``; read only) learner l trains with row l in
+    place of the first nine fields of the shared config (``_lib.HYPER_FIELDS``): it is bit for bit ``train_device``
+    with those values as ``hyper``.  None takes the entries above, unchanged."""
     from . import _lib
     P = len(policies)
     rcfg = rcfg if rcfg is not None else _lib.reward_config()
@@ -387,7 +396,7 @@ def train_population(solver, policies, target, plant_pvec, state, cstate, adam, 
     solver.train_pop(P, seeds, target, plant_pvec, state, cstate, logs, clogs, rec, policies[0].cfg, weights, critic,
                      current_k, adam, adam_step, train_log, best["best_return"], best["best_weights"],
                      best["best_iter"], cfg, tcfg, rcfg=rcfg, prm=prm, pool=pool, global_buffer=global_buffer,
-                     global_log=global_log)
+                     global_log=global_log, **({} if hyper_table is None else dict(hyper=hyper_table)))
     for l, p in enumerate(policies):
         p.weights[...] = weights[l].reshape(p.weights.shape)
         p.critic_weights[...] = critic[l, :_lib.CRITIC_NWEIGHTS].reshape(p.critic_weights.shape)
@@ -442,6 +451,268 @@ def evaluate_population(solver, pop, x0, targets, plant_pvec, steps, which="late
     return {"scores": scores, "metrics": state["metrics"].reshape(P, B, 8), "best": int(np.argmin(scores[:, 0]))}
 
 
+# ---- population-based training: per-learner hyper-parameters and the exploit/explore step -------------------------
+# the defaults of dart_lmpc_pbt_config_default, restated so that ``pbt_plan`` needs no library
+PBT_STREAM = 4                  # the generator stream of the step (streams 0-3: noise, permutations, choice, global)
+PBT_DEFAULTS = dict(
+    seed=0, generation=0, n_replace=0, higher_is_better=0, explore_mask=0b10101, factor_down=0.8, factor_up=1.25,
+    # clip_eps, vf_coef, ent_coef, max_grad_norm, lr, beta1, beta2, adam_eps, weight_decay
+    lo=(0.01, -np.inf, 0.0, 0.0, 1e-6, 0.0, 0.0, 0.0, -np.inf),
+    hi=(0.5, np.inf, 0.1, np.inf, 1e-2, 0.999999, 0.999999, np.inf, np.inf))
+
+
+def _pbt_settings(over):
+    from . import _lib
+    s = dict(PBT_DEFAULTS)
+    for k, v in over.items():
+        if k not in s:
+            raise _lib.DartMPCError(f"pbt settings have no field {k!r} (fields: {sorted(s)})")
+        s[k] = v
+    for k in ("lo", "hi"):
+        if isinstance(s[k], dict):
+            b = list(PBT_DEFAULTS[k])
+            for name, x in s[k].items():
+                b[_lib.HYPER_FIELDS.index(name)] = float(x)
+            s[k] = b
+        s[k] = np.asarray(s[k], np.float64).reshape(-1)
+        if s[k].size != _lib.HYPER_COLS:
+            raise _lib.DartMPCError(f"pbt settings: {k} takes {_lib.HYPER_COLS} values")
+    if not isinstance(s["explore_mask"], (int, np.integer)):
+        s["explore_mask"] = sum(1 << _lib.HYPER_FIELDS.index(n) for n in set(s["explore_mask"]))
+    return s
+
+
+def pbt_check(P, **settings):
+    """What dart_lmpc_pbt_step refuses of a config and a population size, checked on the host: raises ``DartMPCError``
+    or returns the effective k (``n_replace``, 0 meaning P // 4)."""
+    from . import _lib
+    s = _pbt_settings(settings)
+    P, k = int(P), int(s["n_replace"])
+    if not 1 <= P <= _lib.POP_MAX:
+        raise _lib.DartMPCError(f"pbt: 1 <= P <= {_lib.POP_MAX}, got {P}")
+    if k < 0 or int(s["generation"]) < 0:
+        raise _lib.DartMPCError("pbt: n_replace >= 0 and generation >= 0")
+    k = k or P // 4
+    if 2 * k > P:
+        raise _lib.DartMPCError(f"pbt: 2 k <= P (k = {k}, P = {P}): no donor may be replaced")
+    if not (s["factor_down"] > 0.0 and s["factor_up"] > 0.0):
+        raise _lib.DartMPCError("pbt: the factors must be positive")
+    if not np.all(s["lo"] <= s["hi"]):
+        raise _lib.DartMPCError("pbt: lo[c] <= hi[c] for every column, no NaN bound")
+    return k
+
+
+def pbt_plan(fitness, hyper, seed=0, generation=0, fitness_stride=1, **settings):
+    """The numpy statement of the exploit/explore step (dart_lmpc_pbt_step, csrc/lmpc_pbt.hip), bit for bit.
+    ``fitness`` is read at ``l * fitness_stride``; ``hyper`` is the table [P, HYPER_COLS]; ``settings`` override
+    PBT_DEFAULTS (``n_replace``, ``higher_is_better``, ``explore_mask``, ``factor_down``, ``factor_up``, ``lo``, ``hi``).
+
+    Ranking: a is better than b if its fitness is strictly better in the configured direction, or the two compare
+    equal and a < b; a NaN is worse than every non-NaN, NaNs are ordered by index.  Children are the learners of rank
+    >= P - k, donors ranks 0 .. k - 1.  Child l's parent is the learner of rank word0 % k of the Philox block at counter
+    (l, generation, 4, 0); column c of its row is the parent's, times factor_up / factor_down by the top bit of word
+    c % 4 of block (l, generation, 4, 1 + c // 4) where the mask has bit c, then clamped to [lo[c], hi[c]] by
+    comparisons a NaN passes through.  Returns (rank int32 [P], parent int32 [P], the new table)."""
+    from . import harness
+    hyper = np.array(hyper, np.float64)
+    P = hyper.shape[0]
+    s = _pbt_settings(dict(settings, seed=seed, generation=generation))
+    k = pbt_check(P, **s)
+    f = np.asarray(fitness, np.float64).reshape(-1)[::int(fitness_stride)][:P]
+    higher = bool(s["higher_is_better"])
+
+    def better(a, b):
+        na, nb = np.isnan(f[a]), np.isnan(f[b])
+        if na or nb:
+            return (nb and a < b) if na else True
+        strict = f[a] > f[b] if higher else f[a] < f[b]
+        return bool(strict or (f[a] == f[b] and a < b))
+
+    rank = np.array([sum(better(j, l) for j in range(P)) for l in range(P)], np.int32)
+    by_rank = np.argsort(rank)
+    parent = np.arange(P, dtype=np.int32)
+    key = (int(s["seed"]) & 0xffffffff, (int(s["seed"]) >> 32) & 0xffffffff)
+    gen, mask = int(s["generation"]), int(s["explore_mask"])
+    out = hyper.copy()
+    for l in range(P):
+        if k == 0 or rank[l] < P - k:
+            continue
+        word0 = int(harness.philox4x32_10((l, gen, PBT_STREAM, 0), key)[0])
+        parent[l] = by_rank[word0 % k]
+        for c in range(hyper.shape[1]):
+            v = hyper[parent[l], c]
+            if (mask >> c) & 1:
+                w = int(harness.philox4x32_10((l, gen, PBT_STREAM, 1 + c // 4), key)[c % 4])
+                v = v * np.float64(s["factor_up"] if w >> 31 else s["factor_down"])
+            lo, hi = s["lo"][c], s["hi"][c]
+            out[l, c] = lo if v < lo else (hi if v > hi else v)
+    return rank, parent, out
+
+
+def pbt_apply(parent, weights, critic, adam, adam_step):
+    """The copy half of the step on host arrays, in place: child l (``parent[l] != l``) receives its parent's actor
+    row, its 37569 critic weights (the pad floats stay), both Adam moments and ``adam_step``."""
+    from . import _lib
+    for l, p in enumerate(np.asarray(parent)):
+        if p != l:
+            weights[l] = weights[p]
+            critic[l, :_lib.CRITIC_NWEIGHTS] = critic[p, :_lib.CRITIC_NWEIGHTS]
+            adam[l] = adam[p]
+            adam_step[l] = adam_step[p]
+
+
+def pbt_step(pop, hyper, fitness, seed=0, generation=0, fitness_stride=1, **settings):
+    """The exploit/explore step through the host entry (dart_lmpc_pbt_step) on a ``population_stack`` dict with
+    ``weights`` and ``critic``: its ``weights``, ``critic``, ``adam`` and ``adam_step`` and the table ``hyper``
+    [P, HYPER_COLS] are updated in place.  Returns {"rank", "parent"} (int32 [P]); ``pbt_plan`` predicts them and
+    the table."""
+    from . import _lib
+    s = _pbt_settings(dict(settings, seed=seed, generation=generation))
+    cfg = _lib.pbt_config(**{k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in s.items()})
+    rank, parent = _lib.pbt_step(cfg, fitness, pop["weights"], pop["critic"], pop["adam"], pop["adam_step"], hyper,
+                                 fitness_stride=fitness_stride)
+    return {"rank": rank, "parent": parent}
+
+
+def train_pbt(solver, policies, pop, hyper, x0, targets, plant_pvec, eval_steps, generations,
+              iterations_per_generation, seeds, fitness_slot=0, steps=256, it0=0, generation0=0, rcfg=None, prm=None,
+              gamma=0.99, lam=0.95, mean_update=True, track_best=True, epochs=8, mini_batch_size=64, pbt=None,
+              **shared):
+    """Population-based training with nothing on the host between the steps: per generation three calls are enqueued
+    on one stream -- ``train_pop_hyper_dev`` for ``iterations_per_generation`` iterations of ``steps`` closed-loop
+    steps, ``evaluate_dev`` (metrics only, zero noise) of every learner on the experiments ``x0``, ``targets`` [B, 8],
+    ``plant_pvec`` [B, 34] from copies of the learners' policy state as ``evaluate_population`` makes them, and
+    ``pbt_step_dev`` on column ``fitness_slot`` of the scores (``_lib.SCORE_SLOTS``) -- and the stream is synchronised
+    once, after the last generation.
+
+    ``policies`` is a list of P ``LmpcPolicy`` that share one config, ``pop`` a ``population_stack`` dict (``target``,
+    ``plant_pvec``, ``state``, ``cstate``, ``adam``, ``adam_step``, ``best`` and optionally ``pool``) and ``hyper`` the
+    table [P, HYPER_COLS] (``_lib.hyper_table``): all are updated in place, as are the policies' ``weights``,
+    ``critic_weights`` and ``current_k``.  ``pbt`` overrides PBT_DEFAULTS (``seed``, ``n_replace``,
+    ``higher_is_better``, ...; generation g of the call steps with ``generation0 + g``); ``shared`` overrides the shared
+    fields of ``_lib.ppo_config`` (the table's columns are taken from ``hyper``).  Iteration indices run on from
+    ``it0``.  Returns {"rows": per learner one ``TRAIN_LOG_FIELDS`` dict per iteration, "train_log"
+    [P, generations * iterations_per_generation, 12], "rank" and "parent" [generations, P], "hyper"
+    [generations, P, HYPER_COLS] (the table after each step), "scores" [generations, P, 8] (the last row: the final
+    scores)}."""
+    from . import _lib
+    P, G, I, K = len(policies), int(generations), int(iterations_per_generation), int(steps)
+    rcfg = rcfg if rcfg is not None else _lib.reward_config()
+    NI = pop["state"]["x"].shape[0]
+    if P < 1 or NI % P:
+        raise _lib.DartMPCError(f"train_pbt: {NI} instances are not {P} learners of equal size")
+    if G < 1 or I < 1 or int(eval_steps) < 1:
+        raise _lib.DartMPCError("train_pbt: generations, iterations_per_generation and eval_steps must be positive")
+    if not 0 <= int(fitness_slot) < 8:
+        raise _lib.DartMPCError(f"train_pbt: fitness_slot in 0 .. 7 ({_lib.SCORE_SLOTS}), got {fitness_slot}")
+    if any(p.critic_weights is None for p in policies):
+        raise _lib.DartMPCError("training needs policies with critic_weights")
+    if any(k in _lib.HYPER_FIELDS for k in shared):
+        raise _lib.DartMPCError("train_pbt: the table's columns are set in hyper, not by keyword")
+    B = NI // P
+    hyper_h = _lib._inplace(hyper, np.float64, P * _lib.HYPER_COLS, "hyper").reshape(P, _lib.HYPER_COLS)
+    seeds = np.ascontiguousarray(seeds, np.uint64).reshape(-1)
+    s = _pbt_settings(dict(pbt or {}))
+    pbt_check(P, **s)
+    cfg = _lib.ppo_config(**dict(shared, epochs=epochs, mini_batch_size=mini_batch_size))
+    R = K // max(int(rcfg.record_every), 1)
+    ws_bytes = _lib.train_pop_workspace_bytes(P, B, K, int(rcfg.record_every), int(epochs), int(mini_batch_size))
+    if ws_bytes == 0:
+        raise _lib.DartMPCError("train_pbt: no training workspace for this shape (steps a multiple of record_every)")
+    x0 = np.asarray(x0, np.float64).reshape(B, 8)
+    tile = lambda a, n: np.ascontiguousarray(np.tile(np.asarray(a, np.float64).reshape(B, n), (P, 1)))
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    ptrs = lambda d: {k: v.data_ptr() for k, v in d.items()}
+    # the training arrays, as train_pop_dev takes them
+    weights = np.ascontiguousarray(np.stack([np.asarray(p.weights, np.float32).reshape(-1) for p in policies]))
+    current_k = np.ascontiguousarray(np.concatenate([np.asarray(p.current_k, np.float64).reshape(B, 34)
+                                                     for p in policies]))
+    c = {k: dev(v) for k, v in dict(
+        target=pop["target"], plant_pvec=pop["plant_pvec"], current_k=current_k, weights=weights,
+        critic=stack_critics([p.critic_weights for p in policies]),
+        prm=np.tile(_lib.LMPC_PRM_DEFAULT, (NI, 1)) if prm is None else np.asarray(prm, np.float64).reshape(NI, 22)).items()}
+    st, cs = {k: dev(v) for k, v in pop["state"].items()}, {k: dev(v) for k, v in pop["cstate"].items()}
+    lg = {k: dev(v) for k, v in _lib.loop_logs(_lib.LMPC_LOOP_LOGS, K, NI).items()}
+    clg = {k: dev(v) for k, v in _lib.loop_logs(_lib.LMPC_COLLECT_LOGS, K, NI).items()}
+    rec = {k: dev(v) for k, v in _lib.loop_logs(_lib.LMPC_COLLECT_REC, R, NI).items()}
+    pool = {k: dev(v) for k, v in (pop.get("pool") or {}).items()}
+    reset_rows = pop["pool"]["reset_x"].shape[0] if pool else 0
+    nan64 = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device="cuda")
+    tlog = nan64(G, P, I, _lib.TRAIN_LOG_COLS)
+    tr = dict(adam=dev(pop["adam"]), adam_step=dev(pop["adam_step"]), best_return=dev(pop["best"]["best_return"]),
+              best_weights=dev(pop["best"]["best_weights"]), best_iter=dev(pop["best"]["best_iter"]),
+              workspace=torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda"))
+    hyper_d = dev(hyper_h)
+    # the evaluation's arrays: every learner on the same B experiments, from copies of its policy state
+    e_state = {name: torch.zeros(_lib._loop_shape(NI, width, nw=solver.nw), device="cuda",
+                                  dtype={np.float64: torch.float64, np.float32: torch.float32,
+                                         np.int32: torch.int32}[dt])
+               for name, width, dt in _lib.LMPC_LOOP_STATE}
+    e_state["metrics"] = torch.zeros((NI, 8), dtype=torch.float64, device="cuda")
+    e_x0, e_metrics0 = dev(tile(x0, 8)), dev(_lib.loop_metrics(NI))
+    e_target, e_pvec = dev(tile(targets, 8)), dev(tile(plant_pvec, 34))
+    e_prm = dev(np.tile(_lib.LMPC_PRM_DEFAULT, (NI, 1)))
+    scores, hyper_log = nan64(G, P, 8), nan64(G, P, _lib.HYPER_COLS)
+    rank = torch.full((G, P), -1, dtype=torch.int32, device="cuda")
+    parent = torch.full((G, P), -1, dtype=torch.int32, device="cuda")
+    pcfg = policies[0].cfg
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()           # the uploads above ran on the current stream
+    with torch.cuda.stream(stream):
+        for g in range(G):
+            tcfg = _lib.train_config(seed=0, iterations=I, it0=int(it0) + g * I, steps=K, gamma=gamma, lam=lam,
+                                     mean_update=int(bool(mean_update)), track_best=int(bool(track_best)))
+            train = dict(ptrs(tr), train_log=tlog[g].data_ptr())
+            solver.train_pop_hyper_dev(P, seeds, B, reset_rows, c["target"].data_ptr(), c["prm"].data_ptr(),
+                                       c["plant_pvec"].data_ptr(), c["current_k"].data_ptr(), c["weights"].data_ptr(),
+                                       c["critic"].data_ptr(), ptrs(st), ptrs(cs), ptrs(lg), ptrs(clg), ptrs(rec), train,
+                                       pcfg, rcfg, cfg, tcfg, gbuf=None, hyper=hyper_d.data_ptr(), pool=ptrs(pool),
+                                       stream=stream.cuda_stream)
+            for name, t in e_state.items():
+                if name in ("obs_mean", "obs_M2", "obs_count", "history", "timestep", "model_params"):
+                    t.copy_(st[name].reshape(t.shape), non_blocking=True)
+                elif name == "x":
+                    t.copy_(e_x0, non_blocking=True)
+                elif name == "metrics":
+                    t.copy_(e_metrics0, non_blocking=True)
+                else:
+                    t.zero_()
+            solver.evaluate_dev(P, B, 0, int(eval_steps), int(eval_steps), e_target.data_ptr(), e_prm.data_ptr(),
+                                e_pvec.data_ptr(), ptrs(e_state), None, pcfg=pcfg, weights=c["weights"].data_ptr(),
+                                current_k=c["current_k"].data_ptr(), scores=scores[g].data_ptr(),
+                                stream=stream.cuda_stream)
+            pcf = _lib.pbt_config(**{k: (v.tolist() if isinstance(v, np.ndarray) else v)
+                                     for k, v in dict(s, generation=int(generation0) + g).items()})
+            solver.pbt_step_dev(pcf, P, scores[g].data_ptr() + 8 * int(fitness_slot), 8, c["weights"].data_ptr(),
+                                c["critic"].data_ptr(), tr["adam"].data_ptr(), tr["adam_step"].data_ptr(),
+                                hyper_d.data_ptr(), rank[g].data_ptr(), parent[g].data_ptr(),
+                                stream=stream.cuda_stream)
+            hyper_log[g].copy_(hyper_d, non_blocking=True)
+    stream.synchronize()
+    # everything back into the caller's arrays
+    h = lambda t: t.cpu().numpy()
+    pop["target"][...], pop["plant_pvec"][...] = h(c["target"]), h(c["plant_pvec"])
+    for d_host, d_dev in ((pop["state"], st), (pop["cstate"], cs)):
+        for k, v in d_dev.items():
+            d_host[k][...] = h(v).reshape(d_host[k].shape)
+    pop["adam"][...], pop["adam_step"][...] = h(tr["adam"]).reshape(pop["adam"].shape), h(tr["adam_step"])
+    for k in ("best_return", "best_weights", "best_iter"):
+        pop["best"][k][...] = h(tr[k]).reshape(pop["best"][k].shape)
+    w_h, c_h, k_h = h(c["weights"]), h(c["critic"]), h(c["current_k"])
+    for name, arr in (("weights", w_h), ("critic", c_h), ("current_k", k_h)):
+        if name in pop:
+            pop[name][...] = arr.reshape(pop[name].shape)
+    for l, p in enumerate(policies):
+        p.weights[...] = w_h[l].reshape(p.weights.shape)
+        p.critic_weights[...] = c_h[l, :_lib.CRITIC_NWEIGHTS].reshape(p.critic_weights.shape)
+        p.current_k[...] = k_h[l * B:(l + 1) * B].reshape(p.current_k.shape)
+    hyper_h[...] = h(hyper_d)
+    train_log = np.ascontiguousarray(h(tlog).transpose(1, 0, 2, 3).reshape(P, G * I, _lib.TRAIN_LOG_COLS))
+    rows = [[dict(zip(_lib.TRAIN_LOG_FIELDS, (float(v) for v in row))) for row in train_log[l]] for l in range(P)]
+    return {"rows": rows, "train_log": train_log, "rank": h(rank), "parent": h(parent), "hyper": h(hyper_log),
+            "scores": h(scores)}
+
+
 def new_population_global_buffer(P, n):
     """The global buffers of a fresh population of ``P`` learners with ``n`` samples per iteration each: zeroed
     arrays [P, G, ..] of capacity G (``_lib.global_rows``), stacked learner-major, and the one ``fill`` = 0 all
@@ -490,14 +761,20 @@ CHECKPOINT_GLOBAL_FIELDS = {
 }
 
 
+# the optional row of a population's hyper-parameter table: (dtype, shape)
+CHECKPOINT_HYPER_FIELD = (np.float64, (9,))
+
+
 def save_checkpoint(path, actor, critic, adam, adam_step, best, iteration, obs_mean, obs_M2, obs_count, history,
-                    current_k, model_params, global_buffer=None):
+                    current_k, model_params, global_buffer=None, hyper=None):
     """One ``.npz`` of plain arrays (``CHECKPOINT_FIELDS``; readable with ``allow_pickle=False``): the packed actor
     and critic, Adam's state, the best-policy snapshot (``best`` as ``train_device`` takes it), the number of
     iterations done and the policy's Welford state, history, ``current_k`` and ``model_params`` for B controllers.
     With ``global_buffer`` (the dict of ``new_global_buffer``) the file also holds the plain arrays ``g_obs`` ..
     ``g_done`` and ``g_fill`` (``CHECKPOINT_GLOBAL_FIELDS``), so that a training can resume in the middle of a fill
-    period.  Returns the path written (numpy appends ``.npz`` to a path without it)."""
+    period.  With ``hyper`` (a member's row of a population's hyper-parameter table, ``_lib.HYPER_COLS`` values) the
+    file also holds the plain array ``hyper``.  Returns the path written (numpy appends ``.npz`` to a path without
+    it)."""
     from ._lib import DartMPCError
     B = np.asarray(obs_count).reshape(-1).size
     given = dict(actor=actor, critic=critic, adam=adam, adam_step=adam_step, best_weights=best["best_weights"],
@@ -521,6 +798,11 @@ def save_checkpoint(path, actor, critic, adam, adam_step, best, iteration, obs_m
             arrays[name] = np.ascontiguousarray(a, dt).reshape(want)
         if not 0 <= int(arrays["g_fill"][0]) <= cap:
             raise DartMPCError(f"checkpoint field 'g_fill' must lie in [0, {cap}]")
+    if hyper is not None:
+        a = np.asarray(hyper)
+        if a.size != CHECKPOINT_HYPER_FIELD[1][0]:
+            raise DartMPCError(f"checkpoint field 'hyper' must have shape {CHECKPOINT_HYPER_FIELD[1]}, got {a.shape}")
+        arrays["hyper"] = np.ascontiguousarray(a, CHECKPOINT_HYPER_FIELD[0]).reshape(CHECKPOINT_HYPER_FIELD[1])
     path = str(path)
     path = path if path.endswith(".npz") else path + ".npz"
     with open(path, "wb") as fh:
@@ -532,7 +814,9 @@ def load_checkpoint(path):
     """The arrays ``save_checkpoint`` wrote, as a dict name -> array (``allow_pickle=False``: a file that holds
     pickled objects is refused).  A missing field, a wrong dtype or a wrong shape raises ``DartMPCError``.  The
     arrays of a global buffer (``CHECKPOINT_GLOBAL_FIELDS``) are returned when the file holds them -- all of them or
-    none; ``global_buffer_from_checkpoint`` turns them back into the dict ``train_device`` takes."""
+    none; ``global_buffer_from_checkpoint`` turns them back into the dict ``train_device`` takes.  ``hyper`` (a
+    member's hyper-parameters, float64 [9]) is returned when the file holds it; files written without it load as
+    before."""
     from ._lib import DartMPCError
     try:
         with np.load(str(path), allow_pickle=False) as z:
@@ -569,6 +853,11 @@ def load_checkpoint(path):
                 if have != want:
                     raise DartMPCError(f"{path}: checkpoint field {name!r} has shape {a.shape}")
             out[name] = np.ascontiguousarray(a)
+    if "hyper" in got:
+        a = got["hyper"]
+        if a.dtype != np.dtype(CHECKPOINT_HYPER_FIELD[0]) or a.shape != CHECKPOINT_HYPER_FIELD[1]:
+            raise DartMPCError(f"{path}: checkpoint field 'hyper' must be float64 with shape {CHECKPOINT_HYPER_FIELD[1]}")
+        out["hyper"] = np.ascontiguousarray(a)
     return out
 
 

@@ -1126,7 +1126,9 @@ int dart_mpc_nw(int N);
  * The launch sequence per iteration is dart_lmpc_train_dev's, each step issued once for the whole population (the
  * update: prepare once, then gradient + apply per mini-batch index with every learner in each launch).  Calls chain
  * through it0 as the single entry's do.  The global-buffer update has its population form below
- * (dart_lmpc_train_pop_global); the rollout's population form is dart_lmpc_eval; dart_lmpc_collect has none. */
+ * (dart_lmpc_train_pop_global); the rollout's population form is dart_lmpc_eval; per-learner hyper-parameters and
+ * the exploit/explore step of population-based training follow it (dart_lmpc_train_pop_hyper, dart_lmpc_pbt_step);
+ * dart_lmpc_collect has no population form. */
 #define DART_LMPC_POP_MAX 32
 #define DART_LMPC_POP_CRITIC_STRIDE 37572
 
@@ -1206,6 +1208,95 @@ int dart_lmpc_train_pop_global(dart_mpc_handle *h, const dart_plant_config *plan
                                const dart_lmpc_ppo_config *ppo, const dart_lmpc_train_config *cfg, int P,
                                const uint64_t *seeds, int B, int reset_rows, const dart_lmpc_train_buffers *buf,
                                const dart_lmpc_global_buffer *g, void *hip_stream);
+
+/* Per-learner hyper-parameters of a population (added within ABI 8: new entries only).  hyper
+ * [P][DART_LMPC_HYPER_COLS], fp64: row l holds, for learner l, the first nine doubles of dart_lmpc_ppo_config in the
+ * struct's order -- clip_eps, vf_coef, ent_coef, max_grad_norm, lr, beta1, beta2, adam_eps, weight_decay -- and takes
+ * their place in both updates (local and global buffer) of every iteration.  epochs and mini_batch_size (the host
+ * computes the launch sequence from them), log_std_min / log_std_max and gamma / lam stay shared and come from ppo and
+ * cfg.  Learner l is, bit for bit, the run dart_lmpc_train_global(_dev) gives for its arrays, seeds[l] and ppo with row
+ * l in place of its first nine fields: the update's kernels convert a row exactly as the host converts a config
+ * (clip bounds (float)(1 -+ clip_eps) formed in fp64; vf_coef, ent_coef, max_grad_norm, adam_eps, weight_decay cast to
+ * fp32; lr, beta1, beta2 kept in fp64).
+ *
+ * The device entry never reads the table on the host: the kernels read row l when they run, so a table rewritten on
+ * the same stream between two chained calls (by dart_lmpc_pbt_step_dev, or a copy) takes effect, and any contents,
+ * NaN included, are safe (they enter arithmetic only).  With hyper == NULL it is dart_lmpc_train_pop_global_dev,
+ * launch for launch; with g == NULL there is no global update.  DART_MPC_EINVAL as dart_lmpc_train_pop_global_dev.
+ *
+ * The host entry stages the table in (read only) with the other arrays, and refuses with DART_MPC_EINVAL, before any
+ * device work, a row that would be refused as a config (a negative or NaN clip_eps, lr, adam_eps or max_grad_norm, a
+ * beta outside [0, 1)). */
+#define DART_LMPC_HYPER_COLS 9
+
+int dart_lmpc_train_pop_hyper_dev(dart_mpc_handle *h, const dart_plant_config *plant,
+                                  const dart_lmpc_policy_config *pcfg, const dart_lmpc_reward_config *rcfg,
+                                  const dart_lmpc_ppo_config *ppo, const dart_lmpc_train_config *cfg, int P,
+                                  const uint64_t *seeds, int B, int reset_rows, const dart_lmpc_train_buffers *buf,
+                                  const dart_lmpc_global_buffer *g, const double *hyper, void *hip_stream);
+int dart_lmpc_train_pop_hyper(dart_mpc_handle *h, const dart_plant_config *plant,
+                              const dart_lmpc_policy_config *pcfg, const dart_lmpc_reward_config *rcfg,
+                              const dart_lmpc_ppo_config *ppo, const dart_lmpc_train_config *cfg, int P,
+                              const uint64_t *seeds, int B, int reset_rows, const dart_lmpc_train_buffers *buf,
+                              const dart_lmpc_global_buffer *g, const double *hyper, void *hip_stream);
+
+/* The exploit/explore step of population-based training (added within ABI 8: new entries only): the k worst of P
+ * learners restart from the nets, the optimizer state and the hyper-parameters of one of the k best, and their
+ * hyper-parameters are perturbed -- on the device, in two launches on the caller's stream (a rank kernel of one wave,
+ * then a copy kernel), so that train -> evaluate -> step -> train needs no host work in between.
+ *
+ * fitness[l * fitness_stride] is learner l's figure of merit: dart_lmpc_eval's scores + slot with stride 8 reads a
+ * column of the scores where they lie, a column of train_log works the same way.  Layouts are dart_lmpc_train_pop's:
+ * weights [P][39748], critic [P][DART_LMPC_POP_CRITIC_STRIDE], adam [P][2][77317], adam_step [P]; hyper
+ * [P][DART_LMPC_HYPER_COLS]; rank_out, parent_out [P].
+ *
+ * The rule, exact:
+ *   Ranking.  Learner a is better than b if its fitness is strictly better in the configured direction
+ *     (higher_is_better != 0: greater), or if the two compare equal and a < b.  A NaN is worse than every non-NaN,
+ *     NaNs are ordered among themselves by index, +-inf are ordinary values.  rank_out[l] is the number of learners
+ *     better than l: 0 is the best.
+ *   Exploit.  With k = n_replace (0: P / 4), the children are the learners of rank >= P - k and the donors those of
+ *     ranks 0 .. k - 1; 2 k <= P, so no donor is ever written.  Child l takes the Philox4x32-10 block at counter
+ *     (l, generation, 4, 0), key (seed & 0xffffffff, seed >> 32) as dart_lmpc_noise forms it; its parent is the learner
+ *     of rank word0 % k.  parent_out[l] = l for everyone else.  The child receives, bit for bit, the parent's actor
+ *     row, its 37569 critic weights (the three pad floats of a row are never read or written), both Adam moments and
+ *     adam_step.
+ *   Explore, children only.  For column c, v = hyper[parent][c]; if bit c of explore_mask is set,
+ *     v = v * (w >> 31 ? factor_up : factor_down) with w = word c % 4 of the block at counter
+ *     (l, generation, 4, 1 + c / 4), one fp64 product; then v < lo[c] ? lo[c] : (v > hi[c] ? hi[c] : v) for every
+ *     column, so a NaN passes through; hyper[l][c] = v.
+ * Left alone: everything of a surviving learner, and of a child its instances' controller and environment state,
+ * observation statistics (they are per controller instance and describe the child's own trajectories, not the net),
+ * history, current_k, reset pool, seed, logs and best-policy snapshot.
+ *
+ * P = 1, or an effective k = 0 (P < 4 with n_replace = 0), writes rank_out and parent_out = self and nothing else.
+ * DART_MPC_EINVAL before any device work: P outside 1 .. DART_LMPC_POP_MAX, n_replace < 0 or 2 k > P,
+ * fitness_stride < 1, generation < 0, lo[c] > hi[c] or a NaN bound, a factor <= 0 or NaN, a null pointer, weights or
+ * critic not 16-byte aligned. */
+typedef struct dart_lmpc_pbt_config {
+    uint64_t seed;                 /* 0: the generator key of the parent draws and the perturbations */
+    int32_t generation;            /* 0: the counter's second word; advance it by one per step */
+    int32_t n_replace;             /* 0 = P / 4: learners replaced (k) */
+    int32_t higher_is_better;      /* 0: a lower fitness is better (steady-state error); 1 for returns */
+    uint32_t explore_mask;         /* bit c: column c is perturbed; default lr | clip_eps | ent_coef = 0x15 */
+    double factor_down, factor_up; /* 0.8, 1.25 */
+    double lo[DART_LMPC_HYPER_COLS]; /* clamp of every column of a child's row; the defaults lie inside what the */
+    double hi[DART_LMPC_HYPER_COLS]; /* training entries accept: clip_eps [0.01, 0.5], ent_coef [0, 0.1],
+                                      * lr [1e-6, 1e-2], beta1, beta2 [0, 0.999999], max_grad_norm, adam_eps
+                                      * [0, inf], vf_coef, weight_decay [-inf, inf] */
+} dart_lmpc_pbt_config;
+
+void dart_lmpc_pbt_config_default(dart_lmpc_pbt_config *cfg);
+
+/* Device pointers, asynchronous on hip_stream (NULL: the default stream). */
+int dart_lmpc_pbt_step_dev(const dart_lmpc_pbt_config *cfg, int P, const double *fitness, int fitness_stride,
+                           float *weights, float *critic, float *adam, int32_t *adam_step, double *hyper,
+                           int32_t *rank_out, int32_t *parent_out, void *hip_stream);
+
+/* Host pointers (fitness [(P - 1) fitness_stride + 1] read at the stride): staged in, the step, staged out; blocks. */
+int dart_lmpc_pbt_step(const dart_lmpc_pbt_config *cfg, int P, const double *fitness, int fitness_stride,
+                       float *weights, float *critic, float *adam, int32_t *adam_step, double *hyper,
+                       int32_t *rank_out, int32_t *parent_out);
 
 /* ABI version (DART_MPC_ABI_VERSION) of the loaded library. */
 int dart_mpc_abi_version(void);

@@ -21,11 +21,20 @@ LmpcSolver.train_pop); a line per learner and iteration, and --checkpoint PATH w
 global-buffer update of every learner in the same launches (ppo.new_population_global_buffer); every member's
 checkpoint then holds that member's buffer, so --resume --global-update continues it as a single run, in the middle
 of a fill period too.
+With --hyper FIELD=v[,v...] (with --population; repeatable) the learners differ in hyper-parameters: FIELD is a column
+of the population's table (_lib.HYPER_FIELDS: clip_eps, vf_coef, ent_coef, max_grad_norm, lr, beta1, beta2, adam_eps,
+weight_decay) and takes one value for all learners or P values, one per learner -- a fixed sweep in the launches of
+one run (ppo.train_population(..., hyper_table=...)).  With --pbt GENERATIONS the population is trained by
+population-based training (ppo.train_pbt): per generation `iterations` training iterations, an evaluation of every
+learner on held-out experiments (K steps, mean steady-state error) and the exploit/explore step, all on the device;
+--pbt-replace k sets how many learners restart from the best per generation (default P / 4).  Every member's
+checkpoint then holds its row of the table.
 The loop state, the collection state, the targets and the plants carry over from iteration to iteration.
 Prints the mean return of the episodes that ended, per iteration.
 Usage: python tools/lmpc_train.py [iterations] [B] [K] [max_episode_steps] [--update device|torch|resident]
                                   [--global-update] [--checkpoint PATH] [--resume PATH] [--seed S]
-                                  [--population P [--seeds a,b,...]]
+                                  [--population P [--seeds a,b,...] [--hyper FIELD=v[,v...]]...
+                                   [--pbt GENERATIONS [--pbt-replace k]]]
 """
 import os
 import sys
@@ -69,6 +78,28 @@ if population and (update != "resident" or ckpt_in):
     sys.exit("--population goes with --update resident, without --resume")
 if (ckpt_out or ckpt_in) and update != "resident":
     sys.exit("--checkpoint and --resume go with --update resident")
+hyper_over = {}
+while "--hyper" in argv:
+    spec = _option("--hyper")
+    name, _, values = spec.partition("=")
+    if name not in _lib.HYPER_FIELDS or not values:
+        sys.exit(f"--hyper takes FIELD=v[,v...] with FIELD one of {', '.join(_lib.HYPER_FIELDS)}")
+    try:
+        vals = [float(v) for v in values.split(",")]
+    except ValueError:
+        sys.exit(f"--hyper {spec}: the values must be numbers")
+    if len(vals) not in (1, population):
+        sys.exit(f"--hyper {name} takes one value or {population} (one per learner), got {len(vals)}")
+    hyper_over[name] = vals[0] if len(vals) == 1 else vals
+pbt_generations, pbt_replace = int(_option("--pbt") or 0), _option("--pbt-replace")
+if (hyper_over or pbt_generations or pbt_replace is not None) and not population:
+    sys.exit("--hyper, --pbt and --pbt-replace go with --population")
+if pbt_replace is not None and not pbt_generations:
+    sys.exit("--pbt-replace goes with --pbt")
+if pbt_generations < 0 or (pbt_replace is not None and not 0 <= 2 * int(pbt_replace) <= population):
+    sys.exit("--pbt takes a positive number of generations, --pbt-replace k with 2 k <= P")
+if pbt_generations and global_update:
+    sys.exit("--pbt runs without --global-update")
 iters = int(argv[0]) if len(argv) > 0 else 5
 B = int(argv[1]) if len(argv) > 1 else 72
 K = int(argv[2]) if len(argv) > 2 else 256
@@ -108,11 +139,22 @@ def train_population():
         gbuf = ppo.new_population_global_buffer(P_, B * (K // int(rcfg.record_every))) if global_update else None
         if gbuf is not None:
             H["global_buffer"] = gbuf
-        rows = ppo.train_population(solver, policies, H["target"], H["plant_pvec"], H["state"], H["cstate"], H["adam"],
-                                    H["adam_step"], H["best"], K, sd, iterations=iters, rcfg=rcfg, pool=H["pool"],
-                                    gamma=GAMMA, lam=LAM, epochs=8, mini_batch_size=64, clip_eps=0.2, vf_coef=0.25,
-                                    ent_coef=0.01, global_buffer=gbuf)
-        for j in range(iters):
+        table = _lib.hyper_table(P_, **hyper_over) if hyper_over or pbt_generations else None
+        total = iters
+        if pbt_generations:
+            E = lmpc_batch(ns, seed0=777)               # held-out experiments, the same for every learner
+            res = ppo.train_pbt(solver, policies, H, table, E["state"][:B], E["target"][:B], E["pvec"][:B], K,
+                                pbt_generations, iters, sd, fitness_slot=0, steps=K, rcfg=rcfg, gamma=GAMMA, lam=LAM,
+                                epochs=8, mini_batch_size=64,
+                                pbt=dict(seed=seed, n_replace=int(pbt_replace or 0)))
+            rows, total = res["rows"], iters * pbt_generations
+        else:
+            extra = dict(clip_eps=0.2, vf_coef=0.25, ent_coef=0.01) if table is None else dict(hyper_table=table)
+            rows = ppo.train_population(solver, policies, H["target"], H["plant_pvec"], H["state"], H["cstate"],
+                                        H["adam"], H["adam_step"], H["best"], K, sd, iterations=iters, rcfg=rcfg,
+                                        pool=H["pool"], gamma=GAMMA, lam=LAM, epochs=8, mini_batch_size=64,
+                                        global_buffer=gbuf, **extra)
+        for j in range(total):
             for l in range(P_):
                 r = rows[l][j]
                 print(f"iter {j} learner {l} (seed {sd[l]}): samples {int(r['n'])}, episodes ended "
@@ -125,6 +167,13 @@ def train_population():
                             f"value loss {r['global_value_loss']:.4f}, entropy {r['global_entropy']:.3f}"
                             if r["global_update"] else "")
                     print(f"        learner {l} global buffer {int(r['global_fill'])} rows{tail}", flush=True)
+            if pbt_generations and (j + 1) % iters == 0:
+                g = j // iters
+                print(f"generation {g}: steady-state error {np.array2string(res['scores'][g][:, 0], precision=8)}, "
+                      f"rank {res['rank'][g].tolist()}, parent {res['parent'][g].tolist()}", flush=True)
+                for l in range(P_):
+                    print(f"        learner {l}: " + ", ".join(f"{n} {v:.3g}" for n, v in
+                                                                  zip(_lib.HYPER_FIELDS, res["hyper"][g][l])), flush=True)
         if ckpt_out:
             for l in range(P_):
                 m = ppo.population_member(l, P_, H)
@@ -132,7 +181,8 @@ def train_population():
                 path = ppo.save_checkpoint(f"{ckpt_out}.member{l}", policies[l].weights, policies[l].critic_weights,
                                            m["adam"], m["adam_step"], m["best"], iters, st["obs_mean"], st["obs_M2"],
                                            st["obs_count"], st["history"], policies[l].current_k, st["model_params"],
-                                           global_buffer=m.get("global_buffer"))
+                                           global_buffer=m.get("global_buffer"),
+                                           hyper=None if table is None else table[l])
                 print(f"checkpoint: {path} (learner {l}, best return {float(m['best']['best_return'][0]):.2f})",
                       flush=True)
     finally:

@@ -26,9 +26,17 @@ is P train_global_dev periods back to back, each ending in its synchronise; `str
 streams, synchronised once.  Sequential and streams run the single-learner entry, whose kernels this change leaves
 instruction-identical: they are the yardstick.  After the rounds learner l's actor must be bit-identical across the
 three contenders (asserted).
+Per-learner hyper-parameters (--population-hyper): the same shape, P in {2, 3, 4, 8}, one iteration of the whole
+population through train_pop_dev and through train_pop_hyper_dev with no table, a table of equal rows and a table of
+distinct rows, interleaved round by round on one stream; with the file name of another build of the library beside
+libdartmpc.so, that build's train_pop_dev in a process of its own before and after.  Then, for P = 8 and k = 2: one
+pbt_step_dev against one training iteration, one evaluation and the host alternative (wait, the nets and the
+optimizer state down, plan and copy in numpy, back up), and one train_pbt generation enqueued without a wait against
+its three parts with a wait after each.
 Usage: python tools/train_rate.py [out.json] [rounds]
        python tools/train_rate.py --population [out.json] [rounds]
        python tools/train_rate.py --population-global [out.json] [rounds]
+       python tools/train_rate.py --population-hyper [out.json] [rounds] [other-library.so]
        python tools/train_rate.py --once-pop P B K [iterations]   (population iterations and nothing else)
        python tools/train_rate.py --ab-global B K out.npz [periods]   (resident_dev_global alone, per iteration)
        python tools/train_rate.py --ab-pop P B K out.npz [iterations]   (train_pop_dev alone, per iteration)
@@ -242,6 +250,193 @@ class PopRun:
         self.it += iterations
 
 
+def hyper_rows(P, distinct):
+    """The table of the --population-hyper contenders: the shared config's row for everyone, or rows that differ in
+    all nine columns (learner 0 keeps the shared config's)."""
+    l = np.arange(P) if distinct else np.zeros(P)
+    return _lib.hyper_table(P, clip_eps=0.2 + 0.02 * l, vf_coef=0.25 + 0.05 * l, ent_coef=0.01 * (1 + 0.5 * l),
+                            max_grad_norm=0.5 + 0.1 * l, lr=3e-4 * (1 + 0.25 * l), beta1=0.9 - 0.01 * l,
+                            beta2=0.999 - 0.0005 * l, adam_eps=1e-8 * (1 + l), weight_decay=1e-5 * (1 + l))
+
+
+class PbtRun(PopRun):
+    """PopRun with a hyper-parameter table, the evaluation's arrays and the step's outputs on the device: one
+    generation of ppo.train_pbt in parts."""
+
+    def __init__(self, P, B, K, table=None):
+        super().__init__(P, B, K)
+        NI = P * B
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        self.table = None if table is None else up(table)
+        E = lmpc_batch(-(-B // 18), seed0=777)
+        tile = lambda a: np.ascontiguousarray(np.tile(np.asarray(a, np.float64)[:B], (P, 1)))
+        st = {name: np.zeros(_lib._loop_shape(NI, width, nw=self.solver.nw), dt)
+              for name, width, dt in _lib.LMPC_LOOP_STATE}
+        st["metrics"] = _lib.loop_metrics(NI)
+        self.e_state = {k: up(v) for k, v in st.items()}
+        self.e_x0, self.e_metrics0 = up(tile(E["state"])), up(_lib.loop_metrics(NI))
+        self.e_target, self.e_pvec = up(tile(E["target"])), up(tile(E["pvec"]))
+        self.scores = torch.zeros(P, 8, dtype=torch.float64, device="cuda")
+        self.rank = torch.zeros(P, dtype=torch.int32, device="cuda")
+        self.parent = torch.zeros(P, dtype=torch.int32, device="cuda")
+        self.generation = 0
+        self.ts = torch.cuda.Stream()               # every part is enqueued on this one stream
+        torch.cuda.synchronize()
+
+    def train(self, sync=True, plain=False):
+        """One iteration through the table's entry (table None: hyper = NULL); plain: through train_pop_dev."""
+        d = self.dev
+        p = lambda g: {k: v.data_ptr() for k, v in d[g].items()}
+        tcfg = _lib.train_config(iterations=1, it0=self.it, steps=self.K, gamma=GAMMA, lam=LAM)
+        args = (self.P, list(range(self.P)), self.B, 4, d["c"]["target"].data_ptr(), d["c"]["prm"].data_ptr(),
+                d["c"]["pvec"].data_ptr(), d["c"]["current_k"].data_ptr(), d["c"]["weights"].data_ptr(),
+                d["c"]["critic"].data_ptr(), p("st"), p("cs"), p("lg"), p("clg"), p("rec"), p("tr"), self.pcfg,
+                self.rcfg, self.cfg, tcfg)
+        if plain:
+            self.solver.train_pop_dev(*args, pool=p("pool"), stream=self.ts.cuda_stream)
+        else:
+            self.solver.train_pop_hyper_dev(*args, gbuf=None, hyper=0 if self.table is None else self.table.data_ptr(),
+                                            pool=p("pool"), stream=self.ts.cuda_stream)
+        if sync:
+            self.ts.synchronize()
+        self.it += 1
+
+    def train_plain(self):
+        self.train(plain=True)
+
+    def evaluate(self, sync=True):
+        with torch.cuda.stream(self.ts):
+            for name, t in self.e_state.items():
+                if name in ("obs_mean", "obs_M2", "obs_count", "history", "timestep", "model_params"):
+                    t.copy_(self.dev["st"][name].reshape(t.shape), non_blocking=True)
+                elif name == "x":
+                    t.copy_(self.e_x0, non_blocking=True)
+                elif name == "metrics":
+                    t.copy_(self.e_metrics0, non_blocking=True)
+                else:
+                    t.zero_()
+        d = self.dev["c"]
+        self.solver.evaluate_dev(self.P, self.B, 0, self.K, self.K, self.e_target.data_ptr(), d["prm"].data_ptr(),
+                                 self.e_pvec.data_ptr(), {k: v.data_ptr() for k, v in self.e_state.items()}, None,
+                                 pcfg=self.pcfg, weights=d["weights"].data_ptr(), current_k=d["current_k"].data_ptr(),
+                                 scores=self.scores.data_ptr(), stream=self.ts.cuda_stream)
+        if sync:
+            self.ts.synchronize()
+
+    def step(self, k, sync=True):
+        d = self.dev
+        cfg = _lib.pbt_config(seed=1, generation=self.generation, n_replace=k)
+        self.solver.pbt_step_dev(cfg, self.P, self.scores.data_ptr(), 8, d["c"]["weights"].data_ptr(),
+                                 d["c"]["critic"].data_ptr(), d["tr"]["adam"].data_ptr(), d["tr"]["adam_step"].data_ptr(),
+                                 self.table.data_ptr(), self.rank.data_ptr(), self.parent.data_ptr(),
+                                 stream=self.ts.cuda_stream)
+        self.generation += 1
+        if sync:
+            self.ts.synchronize()
+
+    def step_on_host(self, k):
+        """What the step replaces: wait, bring the nets and the optimizer state down, plan and copy in numpy, put
+        them back."""
+        d = self.dev
+        torch.cuda.synchronize()
+        h = {n: d[g][n].cpu().numpy() for g, n in (("c", "weights"), ("c", "critic"), ("tr", "adam"), ("tr", "adam_step"))}
+        table = self.table.cpu().numpy()
+        _, parent, new = ppo.pbt_plan(self.scores.cpu().numpy()[:, 0], table, seed=1, generation=self.generation,
+                                      n_replace=k)
+        ppo.pbt_apply(parent, h["weights"], h["critic"], h["adam"].reshape(self.P, 2, -1), h["adam_step"])
+        for g, n in (("c", "weights"), ("c", "critic"), ("tr", "adam"), ("tr", "adam_step")):
+            d[g][n].copy_(torch.from_numpy(h[n]))
+        self.table.copy_(torch.from_numpy(new))
+        self.generation += 1
+        torch.cuda.synchronize()
+
+    def generation_chained(self, k):
+        self.train(sync=False)
+        self.evaluate(sync=False)
+        self.step(k, sync=True)
+
+    def generation_in_parts(self, k):
+        self.train()
+        self.evaluate()
+        self.step(k)
+
+
+def _spread(t):
+    return {"median_ms": float(np.median(t)), "min_ms": float(min(t)), "max_ms": float(max(t)), "all_ms": list(t)}
+
+
+def _parent_times(lib_name, P, B, K, rounds):
+    """train_pop_dev of another build of the library (a file beside libdartmpc.so), in a process of its own."""
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "ab.npz")
+        env = dict(os.environ, DART_MPC_LIB=lib_name, DART_MPC_AB="1")
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--ab-pop", str(P), str(B), str(K), out, str(rounds)],
+                       env=env, check=True, timeout=600)
+        with np.load(out) as z:
+            return [float(v) for v in z["times_ms"]], z["weights"].copy()
+
+
+def measure_population_hyper(P, B, K, rounds, parent_lib=None):
+    """One iteration of P learners: train_pop_dev, and the table's entry with no table, a table of equal rows and a
+    table of distinct rows, interleaved round by round; with parent_lib, that build's train_pop_dev before and after
+    (its own process).  The first three train the same learners bit for bit."""
+    runs = {"train_pop_dev": PbtRun(P, B, K), "hyper_null": PbtRun(P, B, K),
+            "hyper_equal_rows": PbtRun(P, B, K, hyper_rows(P, False)),
+            "hyper_distinct_rows": PbtRun(P, B, K, hyper_rows(P, True))}
+    calls = {n: (r.train_plain if n == "train_pop_dev" else r.train) for n, r in runs.items()}
+    times = {n: [] for n in calls}
+    out = {"P": P, "B": B, "K": K, "rounds": rounds}
+    try:
+        if parent_lib:
+            before, w_parent = _parent_times(parent_lib, P, B, K, rounds)
+        for r in range(rounds + 1):                 # round 0 is the warm-up
+            for name, fn in calls.items():
+                ms = timed(fn)
+                if r:
+                    times[name].append(ms)
+        w = {n: r.dev["c"]["weights"].cpu().numpy().view(np.int32) for n, r in runs.items()}
+        out["shared_config_runs_bit_identical"] = bool(np.array_equal(w["train_pop_dev"], w["hyper_null"]) and
+                                                       np.array_equal(w["train_pop_dev"], w["hyper_equal_rows"]))
+        if parent_lib:
+            after, _ = _parent_times(parent_lib, P, B, K, rounds)
+            out["parent_train_pop_dev"] = dict(_spread(before + after), library=parent_lib)
+            out["parent_run_bit_identical"] = bool(np.array_equal(w_parent.view(np.int32), w["train_pop_dev"]))
+    finally:
+        for r in runs.values():
+            r.close()
+    for name, t in times.items():
+        out[name] = _spread(t)
+    return out
+
+
+def measure_pbt_step(P, B, K, k, rounds):
+    """One pbt_step_dev against one training iteration and against the host alternative; one generation enqueued
+    without a wait against its three parts with a wait after each."""
+    run = PbtRun(P, B, K, hyper_rows(P, True))
+    out = {"P": P, "B": B, "K": K, "k": k, "rounds": rounds, "eval_steps": K}
+    try:
+        run.train()
+        run.evaluate()
+        run.step(k)                                 # warm-up
+        out["train_iteration"] = _spread([timed(run.train) for _ in range(rounds)])
+        out["evaluate"] = _spread([timed(run.evaluate) for _ in range(rounds)])
+        out["pbt_step_dev"] = _spread([timed(lambda: run.step(k)) for _ in range(6 * rounds)])
+        run.step_on_host(k)
+        out["step_on_host"] = _spread([timed(lambda: run.step_on_host(k)) for _ in range(rounds)])
+        out["step_on_host"]["bytes_per_child"] = 4 * (39748 + 37569 + 2 * 77317 + 1)
+        chained, parts = [], []
+        run.generation_chained(k)
+        for _ in range(rounds):
+            chained.append(timed(lambda: run.generation_chained(k)))
+            parts.append(timed(lambda: run.generation_in_parts(k)))
+        out["generation_chained"], out["generation_in_parts"] = _spread(chained), _spread(parts)
+    finally:
+        run.close()
+    return out
+
+
 def measure_population(P, B, K, rounds, with_global=False):
     """with_global: every call is one full fill period with the global-buffer update; times are per iteration."""
     pop = PopRun(P, B, K, with_global=with_global)
@@ -406,6 +601,29 @@ def main():
             with open(path, "w") as fh:
                 json.dump(res, fh, indent=1)
         return
+    if argv and argv[0] == "--population-hyper":
+        path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "pbt", "train_rate.json")
+        rounds = int(argv[2]) if len(argv) > 2 else 5
+        parent_lib = argv[3] if len(argv) > 3 else None
+        res = {"tool": "tools/train_rate.py --population-hyper", "device": torch.cuda.get_device_name(0), "N": N,
+               "episode_steps": EP_STEPS, "epochs": EPOCHS, "mini_batch_size": MB, "library": _lib.LIB_NAME,
+               "times": "ms, wall clock of the call and the wait for its stream", "populations": []}
+        names = ("train_pop_dev", "hyper_null", "hyper_equal_rows", "hyper_distinct_rows")
+        for P in (2, 3, 4, 8):
+            r = measure_population_hyper(P, 72, 256, rounds, parent_lib)
+            res["populations"].append(r)
+            print(f"P = {P}: " + ", ".join(f"{n} {r[n]['median_ms']:.1f} ms ({r[n]['min_ms']:.1f}-{r[n]['max_ms']:.1f})"
+                                           for n in (("parent_train_pop_dev",) if parent_lib else ()) + names)
+                  + f", shared-config runs bit-identical: {r['shared_config_runs_bit_identical']}", flush=True)
+        res["step"] = r = measure_pbt_step(8, 72, 256, 2, rounds)
+        print("P = 8, k = 2: " + ", ".join(
+            f"{n} {r[n]['median_ms']:.3f} ms ({r[n]['min_ms']:.3f}-{r[n]['max_ms']:.3f})"
+            for n in ("train_iteration", "evaluate", "pbt_step_dev", "step_on_host", "generation_chained",
+                      "generation_in_parts")), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fh:
+            json.dump(res, fh, indent=1)
+        return
     if argv and argv[0] == "--once-pop":
         run = PopRun(int(argv[1]), int(argv[2]), int(argv[3]))
         try:
@@ -458,7 +676,7 @@ def main():
             np.savez(argv[4], weights=d["c"]["weights"].cpu().numpy(), critic=d["c"]["critic"].cpu().numpy(),
                      current_k=d["c"]["current_k"].cpu().numpy(), adam=d["tr"]["adam"].cpu().numpy(),
                      reward=d["clg"]["reward"].cpu().numpy(), x=d["st"]["x"].cpu().numpy(),
-                     best_return=d["tr"]["best_return"].cpu().numpy())
+                     best_return=d["tr"]["best_return"].cpu().numpy(), times_ms=np.array(t))
         finally:
             run.close()
         print(f"{_lib.LIB_NAME} population P = {P}, B = {B}, K = {K}: median {np.median(t):.2f} ms "
