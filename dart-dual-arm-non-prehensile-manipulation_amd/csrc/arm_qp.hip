@@ -521,11 +521,24 @@ __global__ __launch_bounds__(kWave) void arm_qp_kernel(ArmArgs a) {
     __syncthreads();
 
     // ---------------- outputs (arm.py:428-437) -------------------------------------------------
+    // A non-finite (NaN / inf) snapshot or parameter row is a breakdown (include/dart_mpc.h), whatever the loop made
+    // of it: every reduction of its convergence test is fmax-based and fmax drops a NaN operand, so the lanes that
+    // are left can report SOLVED at iteration 0.  ``guard`` is 0 x (everything the loop read and everything
+    // returned): it stays +-0, and adds nothing to the loss, unless one of them is NaN or inf; then it is NaN, the
+    // loss reduction below carries it to lane 0 and the status becomes BREAKDOWN.  It covers tau (so M, h and qdd),
+    // c_r, the constant term of the position row (qd dt + q is finite only if q, qd and dt are; with h and the bounds
+    // that are on, gu and gl are finite), H and M entry by entry, and the loss itself (e0, beta, qdd_prev, the
+    // weights).  It rides on the reduction the outputs need anyway: no ballot, no test of its own before or inside
+    // the loop (a wave-uniform test before the loop cost 0.3-0.7 % of the 36-arm launch, this costs none that the
+    // benchmark resolves); the loop, bounded by max_iter, runs on the bad row and its result is discarded.
     const size_t ob = (size_t)n * b;
+    double guard = 0.0;
     if (l < n) {
         double t = 0.0;
         _Pragma("unroll") for (int k = 0; k < n; ++k) t = fma(M[l * n + k], SH.X[k], t);
         a.tau[ob + l] = t + hb[l];
+        guard = 0.0 * (t + hb[l]);
+        guard = fma(0.0, SH.c[l], fma(0.0, qd[l] * dt + q[l], guard));
         a.qdd[ob + l] = SH.X[l];
         SH.epos[l] = SH.X[l] - SH.beta[l];
         SH.qddd[l] = (SH.X[l] - qp[l]) / dt;
@@ -541,12 +554,14 @@ __global__ __launch_bounds__(kWave) void arm_qp_kernel(ArmArgs a) {
     if (l < n * n) {
         const int r = l / n, cc = l % n;
         lt += SH.epos[r] * Wp[l] * SH.epos[cc] + SH.qddd[r] * Ws[l] * SH.qddd[cc];
+        guard = fma(0.0, SH.H[r * 8 + cc], fma(0.0, M[l], guard));
     }
-    lt = wsum(lt);
+    lt = wsum(lt + guard);
     if (l == 0) {
+        const bool fin = isfinite(lt);      // (NaN for a non-finite row: the guard; also an overflowed loss)
         a.loss[b] = lt;
-        a.status[b] = status;
-        a.iters[b] = it;
+        a.status[b] = fin ? status : -2;
+        a.iters[b] = fin ? it : 0;
     }
     STAMP(7);
     STAMP_FLUSH_TO(g_stamp_arm, b);

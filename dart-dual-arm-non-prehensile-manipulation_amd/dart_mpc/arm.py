@@ -14,6 +14,10 @@ Snapshot / parameter row layouts are those of include/dart_mpc.h (``pack_snapsho
 ``pack_params``).  The kernel cold-starts the bound multipliers and warm-starts qdd from
 qdd_prev; the QP is strictly convex, so the answer does not depend on the reference's IPOPT
 warm-start duals (:401-417).
+
+Non-finite input: a NaN or inf in a snapshot or in the parameter row (a NaN bound aside, which is an absent bound)
+returns ``BREAKDOWN`` (-2) with ``iters`` 0 and a NaN ``loss``, never a status >= 0; ``qdd`` and ``tau`` are then not
+meaningful (``ArmControl`` keeps them as they come: check ``last_status``).  The reference worker would raise in ``np.linalg.pinv`` on such a snapshot.
 """
 from __future__ import annotations
 

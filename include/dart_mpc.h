@@ -348,7 +348,11 @@ enum dart_arm_status {
     DART_ARM_SOLVED = 0,
     DART_ARM_ACCEPTABLE = 1,     /* normal matrix lost definiteness with the KKT error <= acceptable_tol */
     DART_ARM_MAXITER = -1,
-    DART_ARM_BREAKDOWN = -2,
+    DART_ARM_BREAKDOWN = -2,     /* a pivot of the normal matrix not positive above acceptable_tol (indefinite H), or a
+                                  * non-finite (NaN / inf) entry in the snapshot or in the parameter row that reaches
+                                  * the QP or the outputs: never a status >= 0.  iters is then 0, loss is NaN and qdd,
+                                  * tau are not meaningful.  (A NaN bound is an absent bound.)  Other instances of the
+                                  * batch are not affected. */
     DART_ARM_INFEASIBLE = -3     /* multipliers diverging: the bounds admit no qdd */
 };
 

@@ -131,7 +131,8 @@ def qp_ipm(H, c, A, b, lo, hi, x0=None, tol=1e-10, acc_tol=1e-7, max_iter=60):
     one common step 0.99 x the fraction to the boundary for (x, s, z).
     Converged when max(|rd|/sd, |rp|/sp, mu/sd) <= tol (sd = 1 + |c|max, sp = 1 + |g|max).
     Status: 0 converged, 1 acceptable (factorisation lost definiteness with the test met at
-    acc_tol), -1 max_iter, -2 breakdown, -3 diverging multipliers (infeasible bounds).
+    acc_tol), -1 max_iter, -2 breakdown (also what solve_arm returns for non-finite input), -3 diverging multipliers
+    (infeasible bounds).
     Returns (x, status, iterations, z_hi, z_lo).
     """
     n = H.shape[0]
@@ -206,7 +207,17 @@ def kkt_certificate(H, c, A, b, lo, hi, x, zu, zl):
 
 
 def solve_arm(snap: dict, prm: dict, tol: float = 1e-10):
-    """One ARMCONTROL solve: returns dict(qdd, tau, loss, status, iters, kkt)."""
+    """One ARMCONTROL solve: returns dict(qdd, tau, loss, status, iters, kkt).
+
+    A non-finite (NaN / inf) entry in the snapshot or in the parameters (the bounds aside: a NaN bound is an absent
+    bound) is a breakdown, as include/dart_mpc.h states it for the kernel: status -2, iters 0, loss NaN; qdd and tau
+    are not meaningful (here qdd_prev and NaN).  (The reference worker would raise in np.linalg.pinv.)"""
+    bounds = ("Qmin", "Qmax", "Qdotmin", "Qdotmax", "taumin", "taumax")
+    if not (all(np.all(np.isfinite(v)) for v in snap.values()) and
+            all(np.all(np.isfinite(v)) for k, v in prm.items() if k not in bounds)):
+        n = np.shape(snap["q"])[0]
+        return {"qdd": np.array(snap.get("qdd_prev", np.zeros(n)), dtype=float), "tau": np.full(n, np.nan),
+                "loss": float("nan"), "status": -2, "iters": 0, "kkt": None, "qp": None}
     H, c, const, A, b, lo, hi, aux = build_qp(snap, prm)
     x, st, it, zu, zl = qp_ipm(H, c, A, b, lo, hi, x0=snap.get("qdd_prev"), tol=tol)
     return {"qdd": x, "tau": snap["M"] @ x + snap["h"], "loss": reference_cost(x, snap, prm, aux),
