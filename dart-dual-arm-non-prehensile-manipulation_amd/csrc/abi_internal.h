@@ -3,6 +3,7 @@
 //   dart_mpc_abi.hip      handles, the solve entries of the three controllers, the policy entries, arm QP, RLS
 //   dart_mpc_rollout.hip  loop-step and rollout entries, LMPC experience step and collection
 //   dart_mpc_train.hip    GAE, PPO, generator entries, the global buffer and the training entries
+//   dart_mpc_arm.hip      arm dynamics, dynamics + QP, the dual-arm coordinator and the arm layer's closed loop
 // Nothing here is part of the library's surface (include/dart_mpc.h): everything below has hidden visibility.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -28,9 +28,10 @@ from .batch_server import mpc_batch_server  # noqa: F401
 from .rmpc import AdaptiveNPMPCSmooth, RLS, RMPCStep  # noqa: F401
 from .lmpc import RLMPC, LmpcPolicy, init_critic_weights, init_policy_weights, policy_solve_batch  # noqa: F401
 from .lmpc_shm import RLMPCAsync, lmpc_policy_worker, lmpc_solver_worker  # noqa: F401
-from .arm import ArmControl, ArmSolver  # noqa: F401
+from .arm import ArmControl, ArmDynamics, ArmSolver, DualArmControl  # noqa: F401
+from .arm_model import ArmModel  # noqa: F401
 from .mjdata import BodyData  # noqa: F401
 from . import harness, workload  # noqa: F401
 
-__all__ = ["PMPC", "mpc_worker", "mpc_batch_server", "Solver", "RmpcSolver", "LmpcSolver", "RLMPC", "LmpcPolicy", "init_policy_weights", "policy_solve_batch", "RLMPCAsync", "lmpc_solver_worker", "lmpc_policy_worker", "ArmControl", "ArmSolver", "AdaptiveNPMPCSmooth", "RLS", "RMPCStep", "DartMPCError",
+__all__ = ["PMPC", "mpc_worker", "mpc_batch_server", "Solver", "RmpcSolver", "LmpcSolver", "RLMPC", "LmpcPolicy", "init_policy_weights", "policy_solve_batch", "RLMPCAsync", "lmpc_solver_worker", "lmpc_policy_worker", "ArmControl", "ArmSolver", "ArmDynamics", "DualArmControl", "ArmModel", "AdaptiveNPMPCSmooth", "RLS", "RMPCStep", "DartMPCError",
            "build", "lib", "rls_update_batch", "plant_config", "rmpc_loop_config", "reward_config", "gae", "init_critic_weights", "tilt_to_quat", "workload", "harness", "BodyData"]

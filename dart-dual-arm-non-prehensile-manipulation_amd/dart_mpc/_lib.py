@@ -64,7 +64,11 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_lmpc_eval_loop_step_dev", "dart_lmpc_eval_dev", "dart_lmpc_eval", "dart_lmpc_eval_scores_dev",
            "dart_lmpc_eval_scores",
            "dart_lmpc_train_pop_hyper_dev", "dart_lmpc_train_pop_hyper", "dart_lmpc_pbt_config_default",
-           "dart_lmpc_pbt_step_dev", "dart_lmpc_pbt_step")
+           "dart_lmpc_pbt_step_dev", "dart_lmpc_pbt_step",
+           "dart_arm_dyn_config_default", "dart_arm_model_len", "dart_arm_state_len", "dart_arm_dynamics_batch_dev",
+           "dart_arm_dynamics_batch", "dart_arm_control_batch_dev", "dart_arm_control_batch",
+           "dart_dual_arm_control_dev", "dart_dual_arm_control", "dart_dual_arm_work_len",
+           "dart_dual_arm_rollout_dev", "dart_dual_arm_rollout")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -459,6 +463,26 @@ def lib():
         L.dart_lmpc_pbt_step_dev.argtypes = [vp, ci, vp, ci] + [vp] * 8
         L.dart_lmpc_pbt_step.argtypes = [vp, ci, vp, ci] + [vp] * 7
         L.dart_lmpc_pbt_step_dev.restype = L.dart_lmpc_pbt_step.restype = ctypes.c_int
+    if hasattr(L, "dart_arm_dynamics_batch_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_arm_dyn_config_default.argtypes = [vp]
+        L.dart_arm_dyn_config_default.restype = None
+        L.dart_arm_model_len.argtypes = [ci]
+        L.dart_arm_state_len.argtypes = [ci]
+        L.dart_dual_arm_work_len.argtypes = [ci, ci]
+        L.dart_arm_dynamics_batch_dev.argtypes = [vp, ci, ci, vp, ci] + [vp] * 4
+        L.dart_arm_dynamics_batch.argtypes = [vp, ci, ci, vp, ci] + [vp] * 3
+        L.dart_arm_control_batch_dev.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, ci] + [vp] * 7
+        L.dart_arm_control_batch.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, ci] + [vp] * 6
+        L.dart_dual_arm_control_dev.argtypes = [vp, vp, ci, ci] + [vp] * 7 + [ci] + [vp] * 8
+        L.dart_dual_arm_control.argtypes = [vp, vp, ci, ci] + [vp] * 7 + [ci] + [vp] * 7
+        L.dart_dual_arm_rollout_dev.argtypes = [vp, vp, ci, ci, ci, ci] + [vp] * 5 + [ci] + [vp] * 12
+        L.dart_dual_arm_rollout.argtypes = [vp, vp, ci, ci, ci, ci] + [vp] * 5 + [ci] + [vp] * 10
+        for fn in (L.dart_arm_model_len, L.dart_arm_state_len, L.dart_dual_arm_work_len, L.dart_arm_dynamics_batch_dev,
+                   L.dart_arm_dynamics_batch, L.dart_arm_control_batch_dev, L.dart_arm_control_batch,
+                   L.dart_dual_arm_control_dev, L.dart_dual_arm_control, L.dart_dual_arm_rollout_dev,
+                   L.dart_dual_arm_rollout):
+            fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
         L.dart_mpc_bind.restype = ctypes.c_int

@@ -1059,3 +1059,63 @@ def collect_lmpc(x0, targets, plant_pvec, steps: int, N: int = 30, policy_seed=0
         solver.close()
     res = _lmpc_result(B, steps, Ts, targets, lg, state["x"], state, wall, True)
     return _collect_result(res, cs, clogs, rec, targets, plant_pvec)
+
+
+# ---- the arm layer's closed loop (dart_dual_arm_rollout) ------------------------------------------------------------
+def tray_poses_from_tilt(u_log, tray_pos):
+    """Tray poses [K, E, 7] (pos | quat wxyz) from a tilt log ``u_log`` [K, E, 2] of the MPC rollouts and the tray
+    position(s) ``tray_pos`` [3] or [E, 3]: the tilt -> quaternion step of PMPC/main.py:106-116 (``tilt_to_quat``)."""
+    u = np.asarray(u_log, dtype=np.float64)
+    K, E = u.shape[:2]
+    out = np.empty((K, E, 7))
+    out[..., :3] = np.broadcast_to(np.asarray(tray_pos, dtype=np.float64), (E, 3))
+    for k in range(K):
+        for e in range(E):
+            out[k, e, 3:] = tilt_to_quat(u[k, e])
+    return out
+
+
+def rollout_dual_arm(q0, qd0, tray_poses, models, params, steps: int, plant_models=None, metrics_only: bool = False,
+                     qdd_prev0=None, metrics0=None, grasp=None, jacdot_point: int = 0, **cfg):
+    """``steps`` steps of E dual-arm experiments resident on the device (``dart_dual_arm_rollout``): per step the tray
+    pose -> mocap targets, the dynamics of ``models`` (ArmModels or rows, left and right), the impedance QP and one
+    step of the plant ``plant_models`` (default: the controller's models; a heavier last link is a payload).
+
+    q0, qd0 [E, 2, n]; tray_poses [steps, E, 7] or [1, E, 7] (held); params: the reference's parameter dict for both
+    arms, or a pair (left, right).  ``qdd_prev0`` / ``metrics0`` continue an earlier call.  Returns dict(q, qd,
+    qdd_prev, metrics [2 E, 6] (arm.ARM_METRIC_SLOTS), logs (None with ``metrics_only``), wall_s)."""
+    import ctypes
+
+    from . import arm as A
+    from ._lib import _ptr, lib
+    q = np.ascontiguousarray(q0, dtype=np.float64).copy()
+    qd = np.ascontiguousarray(qd0, dtype=np.float64).copy()
+    if q.ndim != 3 or q.shape[1] != 2 or qd.shape != q.shape:
+        raise A.DartMPCError("q0 and qd0 are [E, 2, n]")
+    E, _, n = q.shape
+    tray = np.ascontiguousarray(tray_poses, dtype=np.float64)
+    if tray.ndim != 3 or tray.shape[1:] != (E, 7) or tray.shape[0] not in (1, steps):
+        raise A.DartMPCError(f"tray_poses are [{steps} or 1, {E}, 7]")
+    rows = A._model_rows(models, n, 2)
+    plant = rows if plant_models is None else A._model_rows(plant_models, n, 2)
+    pl, pr = params if isinstance(params, (tuple, list)) else (params, params)
+    prm = np.ascontiguousarray(np.tile(np.stack([A.pack_params(pl), A.pack_params(pr)]), (E, 1)))
+    g = np.ascontiguousarray(A.DACTL_GRASP if grasp is None else grasp, dtype=np.float64)
+    qp = np.zeros_like(q) if qdd_prev0 is None else np.ascontiguousarray(qdd_prev0, dtype=np.float64).copy()
+    met = np.zeros((2 * E, A.NMETRIC)) if metrics0 is None else np.ascontiguousarray(metrics0, dtype=np.float64).copy()
+    B = 2 * E
+    logs = None
+    if not metrics_only:
+        logs = {"q": np.full((steps, B, n), np.nan), "qd": np.full((steps, B, n), np.nan),
+                "tau": np.full((steps, B, n), np.nan), "ee_pos": np.full((steps, B, 3), np.nan),
+                "loss": np.full((steps, B), np.nan), "status": np.zeros((steps, B), dtype=np.int32)}
+    lp = [None] * 6 if logs is None else [_ptr(logs[k]) for k in ("q", "qd", "tau", "ee_pos", "loss", "status")]
+    dcfg, qcfg = A.arm_dyn_config(jacdot_point=int(jacdot_point)), A.arm_config(**cfg)
+    t0 = time.perf_counter()
+    rc = lib().dart_dual_arm_rollout(ctypes.byref(dcfg), ctypes.byref(qcfg), E, n, int(steps), tray.shape[0], _ptr(tray),
+                                     _ptr(g), _ptr(rows), _ptr(plant), _ptr(prm), prm.shape[1], _ptr(q), _ptr(qd),
+                                     _ptr(qp), _ptr(met), *lp)
+    wall = time.perf_counter() - t0
+    if rc != 0:
+        raise A.DartMPCError(f"dart_dual_arm_rollout failed ({rc})")
+    return {"q": q, "qd": qd, "qdd_prev": qp, "metrics": met, "logs": logs, "wall_s": wall}

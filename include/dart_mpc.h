@@ -376,6 +376,92 @@ int dart_arm_solve_batch_dev(const dart_arm_config *cfg, int B, int n, const dou
 int dart_arm_solve_batch(const dart_arm_config *cfg, int B, int n, const double *snap, const double *prm,
                          int prm_stride, double *qdd, double *tau, double *loss, int32_t *status, int32_t *iters);
 
+/* Arm rigid-body dynamics on the device (added within ABI 8: new entries only): ARMCONTROL.compute_dynamics
+ * (PMPC/src/controller/arm.py:111-199) without MuJoCo, for a serial chain of n <= DART_ARM_NMAX hinge joints.
+ *   model [B or 1][dart_arm_model_len(n) = 22 n + 18] (model_stride 0 shares one row):
+ *        base_pos[3] base_quat[4] | per link: pos[3] quat[4] axis[3] armature damping mass com[3]
+ *        inertia[6] (xx yy zz xy xz yz about the com, body frame) | ee_pos[3] ee_quat[4] offset gravity[3];
+ *        quaternions (w, x, y, z) and axes are unit (dart_mpc.arm_model.ArmModel.row() normalises them)
+ *   state [B][dart_arm_state_len(n) = 3 n + 7] = q[n] qd[n] qdd_prev[n] mocap_pos[3] mocap_quat[4]
+ *   snap  [B][dart_arm_snapshot_len(n)] the row dart_arm_solve_batch reads; ee_quat [B][4] nullable.
+ * jac is taken at the EE body's origin, ee_pos at origin + offset z; M is bit-symmetric; Mx_inv = J M^-1 J' by a
+ * Cholesky factor (NaN on a non-positive pivot, which the QP reports as DART_ARM_BREAKDOWN); h is the bias force at
+ * qdd = 0 (Coriolis, centrifugal, gravity; no damping).  jacdot_point selects the point jacDot differentiates:
+ * DART_ARM_JACDOT_REFERENCE the world point (0, 0, offset) attached to the EE body (the reference's mj_jacDot call
+ * read literally), DART_ARM_JACDOT_BODY the EE body origin.  Stateless; EINVAL before any device work for n < 1,
+ * n > DART_ARM_NMAX, B < 1, a null pointer, a model_stride that is neither 0 nor the row length, an unknown
+ * jacdot_point. */
+#define DART_ARM_JACDOT_REFERENCE 0
+#define DART_ARM_JACDOT_BODY 1
+#define DART_ARM_NMETRIC 6
+
+typedef struct dart_arm_dyn_config {
+    int32_t jacdot_point;        /* DART_ARM_JACDOT_*, default DART_ARM_JACDOT_REFERENCE */
+    int32_t reserved[7];
+} dart_arm_dyn_config;
+
+void dart_arm_dyn_config_default(dart_arm_dyn_config *cfg);
+int dart_arm_model_len(int n);
+int dart_arm_state_len(int n);
+
+int dart_arm_dynamics_batch_dev(const dart_arm_dyn_config *dcfg, int B, int n, const double *model, int model_stride,
+                                const double *state, double *snap, double *ee_quat, void *hip_stream);
+int dart_arm_dynamics_batch(const dart_arm_dyn_config *dcfg, int B, int n, const double *model, int model_stride,
+                            const double *state, double *snap, double *ee_quat);
+
+/* Dynamics, then the unchanged QP launch on the same stream: state -> qdd, tau, loss, status, iters (as
+ * dart_arm_solve_batch).  snap [B][dart_arm_snapshot_len(n)]: the snapshots in between (device entry: required, it
+ * is the QP's input; host entry: nullable, copied back when set). */
+int dart_arm_control_batch_dev(const dart_arm_dyn_config *dcfg, const dart_arm_config *cfg, int B, int n,
+                               const double *model, int model_stride, const double *state, const double *prm,
+                               int prm_stride, double *snap, double *qdd, double *tau, double *loss,
+                               int32_t *status, int32_t *iters, void *hip_stream);
+int dart_arm_control_batch(const dart_arm_dyn_config *dcfg, const dart_arm_config *cfg, int B, int n,
+                           const double *model, int model_stride, const double *state, const double *prm,
+                           int prm_stride, double *snap, double *qdd, double *tau, double *loss, int32_t *status,
+                           int32_t *iters);
+
+/* DACTL.control (PMPC/src/dualctl.py:22-66) for E experiments; instance 2 e + a is arm a (0 left, 1 right) of
+ * experiment e.  tray_pose [E][7] (pos, quat); grasp [2][7] the grasp transforms (pos, quat) in the tray frame; the
+ * mocap target of arm a is tray_pose o grasp[a], by quaternion products.  q, qd, qdd_prev [E][2][n]; models
+ * [2][dart_arm_model_len(n)]; prm as dart_arm_solve_batch over the 2 E instances.  Outputs over the 2 E instances;
+ * snap as dart_arm_control_batch; mocap [2 E][7] nullable: the targets. */
+int dart_dual_arm_control_dev(const dart_arm_dyn_config *dcfg, const dart_arm_config *cfg, int E, int n,
+                              const double *tray_pose, const double *grasp, const double *q, const double *qd,
+                              const double *qdd_prev, const double *models, const double *prm, int prm_stride,
+                              double *snap, double *mocap, double *qdd, double *tau, double *loss, int32_t *status,
+                              int32_t *iters, void *hip_stream);
+int dart_dual_arm_control(const dart_arm_dyn_config *dcfg, const dart_arm_config *cfg, int E, int n,
+                          const double *tray_pose, const double *grasp, const double *q, const double *qd,
+                          const double *qdd_prev, const double *models, const double *prm, int prm_stride,
+                          double *snap, double *mocap, double *qdd, double *tau, double *loss, int32_t *status,
+                          int32_t *iters);
+
+/* Device-resident closed loop of the arm layer: `steps` steps of E dual-arm experiments on one stream, nothing on the
+ * host in between.  Per step: tray pose -> mocap targets, dynamics with `models`, the QP, then this library's own
+ * plant step with `plant_models` ([2][model_len]; not MuJoCo's integrator):
+ *   (M_p + dt diag(d)) a = tau - h_p - d o qd,  qd += dt a,  q += dt qd      (d: the plant rows' damping)
+ * with tau the QP's where status >= 0 and zero otherwise; qdd_prev becomes the QP's solution where status >= 0.
+ *   tray_poses [tray_rows][E][7], tray_rows == steps or 1 (held)
+ *   q, qd, qdd_prev [E][2][n] in / out;  metrics [2 E][DART_ARM_NMETRIC] in / out (zeros to start): final and largest
+ *   |ee_pos - mocap_pos|, final |rotvec|, steps with status != 0, QP iterations, largest |tau_i| / taumax_i
+ *   logs, all NULL (metrics only) or all set: q_log, qd_log, tau_log [steps][2 E][n] (the state the step's dynamics
+ *   saw, the applied torque), ee_log [steps][2 E][3], loss_log [steps][2 E], status_log [steps][2 E]
+ *   work (device entry): dart_dual_arm_work_len(E, n) doubles of device memory.
+ * Two calls of K1 and K2 steps give the bits of one call of K1 + K2 steps. */
+int dart_dual_arm_work_len(int E, int n);
+int dart_dual_arm_rollout_dev(const dart_arm_dyn_config *dcfg, const dart_arm_config *cfg, int E, int n, int steps,
+                              int tray_rows, const double *tray_poses, const double *grasp, const double *models,
+                              const double *plant_models, const double *prm, int prm_stride, double *q, double *qd,
+                              double *qdd_prev, double *metrics, double *work, double *q_log, double *qd_log,
+                              double *tau_log, double *ee_log, double *loss_log, int32_t *status_log,
+                              void *hip_stream);
+int dart_dual_arm_rollout(const dart_arm_dyn_config *dcfg, const dart_arm_config *cfg, int E, int n, int steps,
+                          int tray_rows, const double *tray_poses, const double *grasp, const double *models,
+                          const double *plant_models, const double *prm, int prm_stride, double *q, double *qd,
+                          double *qdd_prev, double *metrics, double *q_log, double *qd_log, double *tau_log,
+                          double *ee_log, double *loss_log, int32_t *status_log);
+
 /* Device-resident closed-loop rollouts (added within ABI 8: new entries only, nothing existing changes).
  * A K-step closed loop of B experiments on one stream with no host synchronisation between the steps: per step
  * one loop-step kernel (csrc/loop_step.hip) and the unchanged solve.  They do what the drivers do around a
