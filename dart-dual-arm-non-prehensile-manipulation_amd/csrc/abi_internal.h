@@ -4,6 +4,7 @@
 //   dart_mpc_rollout.hip  loop-step and rollout entries, LMPC experience step and collection
 //   dart_mpc_train.hip    GAE, PPO, generator entries, the global buffer and the training entries
 //   dart_mpc_arm.hip      arm dynamics, dynamics + QP, the dual-arm coordinator and the arm layer's closed loop
+//   dart_mpc_stack.hip    the PMPC closed loop through the dual-arm layer (stack_step.hip between the two)
 // Nothing here is part of the library's surface (include/dart_mpc.h): everything below has hidden visibility.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -418,5 +419,26 @@ int lmpc_closed_loop(dart_mpc_handle* h, const dart_plant_config* plant, const d
                      const dart_lmpc_reward_config* rcfg, bool collect, int B, int k0, int steps, int log_rows,
                      int rec_rows, int reset_rows, const dart_lmpc_train_buffers& p, const float* noise, void* stream,
                      int learner_B = 0, const LmpcEval* ev = nullptr);
+
+// ---- what the stack entries (dart_mpc_stack.hip) take from the PMPC loop and from the arm layer -----------------
+// the solve's per-step arrays of a PMPC / RMPC loop step: pre writes x0 (RMPC: and Rref, phi, y), post reads the rest
+struct LoopIo {
+    double *x0, *Rref, *phi, *y, *u0, *f;
+    int32_t *status, *iters;
+};
+// dart_mpc_rollout.hip: the plant of a loop step; a rollout's own LoopIo in the handle's scratch (B_max instances)
+dartmpc::PlantArgs plant_args(const dart_mpc_handle* h, const dart_plant_config* p);
+int loop_scratch(dart_mpc_handle* h, LoopIo& L);
+// dart_mpc_arm.hip: the configuration checks of the arm entries, and one step of the arm layer's loop on device
+// pointers (the checks made): dynamics against the tray poses `tray` [E][7], the QP, the plant step.  `work` is
+// dart_dual_arm_work_len(E, n) doubles and starts with the step's snapshot rows; ee_quat [2 E][4] or null; the logs
+// [rows][2 E][.] all given or all null, row `log_row` is written.
+bool arm_dyn_ok(const dart_arm_dyn_config* c, int B, int n);
+bool arm_qp_ok(const dart_arm_config* c, int n, int prm_stride);
+int dual_arm_step(const dart_arm_dyn_config* dcfg, const dart_arm_config* cfg, int E, int n, const double* tray,
+                  const double* grasp, const double* models, const double* plant_models, const double* prm,
+                  int prm_stride, double* q, double* qd, double* qdd_prev, double* metrics, double* work,
+                  double* ee_quat, size_t log_row, double* q_log, double* qd_log, double* tau_log, double* ee_log,
+                  double* loss_log, int32_t* status_log, hipStream_t s);
 
 #pragma GCC visibility pop

@@ -16,20 +16,23 @@ int dart_dual_arm_work_len(int E, int n) {
     return 2 * E * (dartmpc::arm_snap_len(n) + 2 * n + 3);
 }
 
-namespace {
-
 using dartmpc::ArmDynArgs;
 using dartmpc::ArmPlantArgs;
 
-bool dyn_ok(const dart_arm_dyn_config* c, int B, int n) {
+bool arm_dyn_ok(const dart_arm_dyn_config* c, int B, int n) {
     return c && B >= 1 && n >= 1 && n <= DART_ARM_NMAX &&
            (c->jacdot_point == DART_ARM_JACDOT_REFERENCE || c->jacdot_point == DART_ARM_JACDOT_BODY);
 }
 // the QP configuration, as dart_arm_solve_batch checks it
-bool qp_ok(const dart_arm_config* c, int n, int prm_stride) {
+bool arm_qp_ok(const dart_arm_config* c, int n, int prm_stride) {
     return c && (prm_stride == 0 || prm_stride == dartmpc::arm_prm_len(n)) && c->tol > 0.0 &&
            c->acceptable_tol >= c->tol && c->max_iter >= 1 && c->max_iter <= 100000;
 }
+
+namespace {
+
+bool dyn_ok(const dart_arm_dyn_config* c, int B, int n) { return arm_dyn_ok(c, B, n); }
+bool qp_ok(const dart_arm_config* c, int n, int prm_stride) { return arm_qp_ok(c, n, prm_stride); }
 int hip_rc(hipError_t e) { return e == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP; }
 hipError_t as_hip(int rc) { return rc == DART_MPC_OK ? hipSuccess : hipErrorUnknown; }
 
@@ -201,6 +204,36 @@ bool rollout_ok(const dart_arm_dyn_config* dcfg, const dart_arm_config* cfg, int
 
 }  // namespace
 
+int dual_arm_step(const dart_arm_dyn_config* dcfg, const dart_arm_config* cfg, int E, int n, const double* tray,
+                  const double* grasp, const double* models, const double* plant_models, const double* prm,
+                  int prm_stride, double* q, double* qd, double* qdd_prev, double* metrics, double* work,
+                  double* ee_quat, size_t log_row, double* q_log, double* qd_log, double* tau_log, double* ee_log,
+                  double* loss_log, int32_t* status_log, hipStream_t s) {
+    const size_t B = 2 * (size_t)E, SL = dartmpc::arm_snap_len(n);
+    double* snap = work;
+    double* qdd = snap + SL * B;
+    double* tau = qdd + n * B;
+    double* loss = tau + n * B;
+    int32_t* status = reinterpret_cast<int32_t*>(loss + B);
+    int32_t* iters = reinterpret_cast<int32_t*>(loss + 2 * B);
+    ArmDynArgs a = dual_args(dcfg, E, n, tray, grasp, q, qd, qdd_prev, models, snap, nullptr);
+    a.ee_quat = ee_quat;
+    if (dartmpc_launch_arm_dyn(&a, s) != hipSuccess) return DART_MPC_EHIP;
+    if (int rc = dart_arm_solve_batch_dev(cfg, (int)B, n, snap, prm, prm_stride, qdd, tau, loss, status, iters, s)) return rc;
+    ArmPlantArgs p{};
+    p.B = (int)B; p.n = n;
+    p.model = plant_models; p.model_stride = dartmpc::arm_model_len(n); p.model_mod = 2;
+    p.prm = prm; p.prm_stride = prm_stride; p.snap = snap;
+    p.qdd = qdd; p.tau = tau; p.loss = loss; p.status = status; p.iters = iters;
+    p.q = q; p.qd = qd; p.qp = qdd_prev; p.metrics = metrics;
+    if (q_log) {
+        const size_t r = log_row * B;
+        p.q_log = q_log + r * n; p.qd_log = qd_log + r * n; p.tau_log = tau_log + r * n;
+        p.ee_log = ee_log + r * 3; p.loss_log = loss_log + r; p.status_log = status_log + r;
+    }
+    return dartmpc_launch_arm_plant(&p, s) == hipSuccess ? DART_MPC_OK : DART_MPC_EHIP;
+}
+
 int dart_dual_arm_rollout_dev(const dart_arm_dyn_config* dcfg, const dart_arm_config* cfg, int E, int n, int steps,
                               int tray_rows, const double* tray_poses, const double* grasp, const double* models,
                               const double* plant_models, const double* prm, int prm_stride, double* q, double* qd,
@@ -210,32 +243,12 @@ int dart_dual_arm_rollout_dev(const dart_arm_dyn_config* dcfg, const dart_arm_co
                     {tray_poses, grasp, models, plant_models, prm, q, qd, qdd_prev, metrics, work},
                     {q_log, qd_log, tau_log, ee_log, loss_log, status_log}))
         return DART_MPC_EINVAL;
-    const size_t B = 2 * (size_t)E, SL = dartmpc::arm_snap_len(n);
-    double* snap = work;
-    double* qdd = snap + SL * B;
-    double* tau = qdd + n * B;
-    double* loss = tau + n * B;
-    int32_t* status = reinterpret_cast<int32_t*>(loss + B);
-    int32_t* iters = reinterpret_cast<int32_t*>(loss + 2 * B);
-    hipStream_t s = (hipStream_t)stream;
     for (int k = 0; k < steps; ++k) {
         const double* tray = tray_poses + (tray_rows == 1 ? 0 : (size_t)k * 7 * E);
-        const ArmDynArgs a = dual_args(dcfg, E, n, tray, grasp, q, qd, qdd_prev, models, snap, nullptr);
-        if (dartmpc_launch_arm_dyn(&a, s) != hipSuccess) return DART_MPC_EHIP;
-        if (int rc = dart_arm_solve_batch_dev(cfg, (int)B, n, snap, prm, prm_stride, qdd, tau, loss, status, iters, s))
+        if (int rc = dual_arm_step(dcfg, cfg, E, n, tray, grasp, models, plant_models, prm, prm_stride, q, qd, qdd_prev,
+                                   metrics, work, nullptr, (size_t)k, q_log, qd_log, tau_log, ee_log, loss_log, status_log,
+                                   (hipStream_t)stream))
             return rc;
-        ArmPlantArgs p{};
-        p.B = (int)B; p.n = n;
-        p.model = plant_models; p.model_stride = dartmpc::arm_model_len(n); p.model_mod = 2;
-        p.prm = prm; p.prm_stride = prm_stride; p.snap = snap;
-        p.qdd = qdd; p.tau = tau; p.loss = loss; p.status = status; p.iters = iters;
-        p.q = q; p.qd = qd; p.qp = qdd_prev; p.metrics = metrics;
-        if (q_log) {
-            const size_t r = (size_t)k * B;
-            p.q_log = q_log + r * n; p.qd_log = qd_log + r * n; p.tau_log = tau_log + r * n;
-            p.ee_log = ee_log + r * 3; p.loss_log = loss_log + r; p.status_log = status_log + r;
-        }
-        if (dartmpc_launch_arm_plant(&p, s) != hipSuccess) return DART_MPC_EHIP;
     }
     return DART_MPC_OK;
 }

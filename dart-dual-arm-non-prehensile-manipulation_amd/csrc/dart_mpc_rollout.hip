@@ -14,14 +14,14 @@ void dart_rmpc_loop_config_default(dart_rmpc_loop_config* c) {
     c->dr_max = 0.01; c->alpha_rg = 0.5; c->step_fraction = 0.2; c->rls_lambda = 0.995; c->pos_tol = 0.01;
 }
 
-namespace {
-
 dartmpc::PlantArgs plant_args(const dart_mpc_handle* h, const dart_plant_config* p) {
     dartmpc::PlantArgs a;
     a.a_lag = p->tau > 0.0 ? 1.0 - std::exp(-h->cfg.Ts / p->tau) : 1.0;
     a.mu_c = p->mu_c; a.v_c = p->v_c; a.dt = h->cfg.Ts; a.g = h->cfg.gravity;
     return a;
 }
+
+namespace {
 
 // the checks every LMPC rollout / loop-step entry shares: the call writes the log rows k .. k + steps - 1.  (The
 // LMPC plant does not use mu_c / v_c.)
@@ -59,13 +59,9 @@ int scratch_blocks(dart_mpc_handle* h, int n, const size_t* cnt, int zero_from, 
 // (the entries never write through what they take const: the views' members are not const)
 template <class T> T* mut(const T* p) { return const_cast<T*>(p); }
 
-// the solve's per-step arrays of a PMPC / RMPC loop step: pre writes x0 (RMPC: and Rref, phi, y), post reads the rest
-struct LoopIo {
-    double *x0, *Rref, *phi, *y, *u0, *f;
-    int32_t *status, *iters;
-};
+}  // namespace
 
-// a rollout's own, in the handle's scratch
+// a rollout's own per-step arrays of the solve (abi_internal.h LoopIo), in the handle's scratch
 int loop_scratch(dart_mpc_handle* h, LoopIo& L) {
     const size_t N1 = (size_t)h->cfg.N + 1;
     const bool rm = h->cfg.variant == DART_MPC_RMPC;
@@ -78,6 +74,8 @@ int loop_scratch(dart_mpc_handle* h, LoopIo& L) {
     L.u0 = (double*)p[4]; L.f = (double*)p[5]; L.status = (int32_t*)p[6]; L.iters = (int32_t*)p[7];
     return DART_MPC_OK;
 }
+
+namespace {
 
 // ---------------------------------------------------------------------------------------------
 // PMPC and RMPC closed loops (pmpc_loop_kernel / rmpc_loop_kernel between the unchanged solves), on the tray plant

@@ -68,7 +68,10 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_arm_dyn_config_default", "dart_arm_model_len", "dart_arm_state_len", "dart_arm_dynamics_batch_dev",
            "dart_arm_dynamics_batch", "dart_arm_control_batch_dev", "dart_arm_control_batch",
            "dart_dual_arm_control_dev", "dart_dual_arm_control", "dart_dual_arm_work_len",
-           "dart_dual_arm_rollout_dev", "dart_dual_arm_rollout")
+           "dart_dual_arm_rollout_dev", "dart_dual_arm_rollout",
+           "dart_stack_config_default", "dart_stack_work_len", "dart_tray_from_arms_dev", "dart_tray_from_arms",
+           "dart_pmpc_stack_loop_step_dev", "dart_pmpc_stack_lm_loop_step_dev", "dart_pmpc_stack_rollout_dev",
+           "dart_pmpc_stack_lm_rollout_dev", "dart_pmpc_stack_rollout", "dart_pmpc_stack_lm_rollout")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -143,6 +146,28 @@ class GlobalBuffer(ctypes.Structure):
                 ("value", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p),
                 ("capacity", ctypes.c_int32), ("fill", ctypes.c_int32), ("global_log", ctypes.c_void_p),
                 ("workspace", ctypes.c_void_p)]
+
+
+class StackConfig(ctypes.Structure):
+    """Mirror of ``struct dart_stack_config`` (the PMPC loop through the dual-arm layer)."""
+    _fields_ = [("couple", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+
+
+STACK_RIDE, STACK_ACHIEVED = 0, 1               # dart_stack_config.couple
+STACK_COMMAND, STACK_COUPLE = 0, 1              # phase of a stack loop-step launch
+STACK_METRIC_SLOTS = ("tilt_deviation", "max_tilt_deviation", "max_yaw", "max_grasp_gap", "max_disagreement_angle",
+                      "max_tray_pos_error", "held_steps", "steps")
+# pointer arguments of the stack entries in the argument order of include/dart_mpc.h ("lm": the LMPC plant's entries)
+STACK_STEP_ARGS = {False: ("target", "prm", "tray_pos", "grasp", "snap", "ee_quat", "x", "tilt", "metrics", "stack_metrics",
+                           "x0", "tray_cmd", "u0", "f", "status", "iters"),
+                   True: ("target", "plant_pvec", "pz_vz", "tray_pos", "grasp", "snap", "ee_quat", "x", "tilt", "metrics",
+                          "stack_metrics", "x0", "tray_cmd", "u0", "f", "status", "iters")}
+STACK_ROLLOUT_ARGS = {False: ("target", "prm", "x", "tilt", "metrics", "grasp", "models", "plant_models", "arm_prm", "q", "qd",
+                              "qdd_prev", "arm_metrics", "work", "tray_pos", "stack_metrics"),
+                      True: ("target", "prm", "plant_pvec", "pz_vz", "x", "tilt", "metrics", "grasp", "models", "plant_models",
+                             "arm_prm", "q", "qd", "qdd_prev", "arm_metrics", "work", "tray_pos", "stack_metrics")}
+STACK_LOGS = (("tilt", 2, np.float64), ("tray", 7, np.float64))
+ARM_LOOP_LOGS = ("q", "qd", "tau", "ee_pos", "loss", "status")         # [rows, 2 E, .]; status int32
 
 
 # Arrays of the closed-loop rollouts in the argument order of include/dart_mpc.h: (name, row width, dtype);
@@ -483,6 +508,23 @@ def lib():
                    L.dart_dual_arm_control_dev, L.dart_dual_arm_control, L.dart_dual_arm_rollout_dev,
                    L.dart_dual_arm_rollout):
             fn.restype = ctypes.c_int
+    if hasattr(L, "dart_pmpc_stack_rollout_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_stack_config_default.argtypes = [ctypes.POINTER(StackConfig)]
+        L.dart_stack_config_default.restype = None
+        L.dart_stack_work_len.argtypes = [ci, ci]
+        L.dart_tray_from_arms_dev.argtypes = [ci] + [vp] * 7
+        L.dart_tray_from_arms.argtypes = [ci] + [vp] * 6
+        L.dart_pmpc_stack_loop_step_dev.argtypes = [vp, vp, vp] + [ci] * 7 + [vp] * 25
+        L.dart_pmpc_stack_lm_loop_step_dev.argtypes = [vp, vp, vp] + [ci] * 7 + [vp] * 27
+        L.dart_pmpc_stack_rollout_dev.argtypes = [vp] * 5 + [ci] * 6 + [vp] * 31
+        L.dart_pmpc_stack_lm_rollout_dev.argtypes = [vp] * 5 + [ci] * 6 + [vp] * 34
+        L.dart_pmpc_stack_rollout.argtypes = [vp] * 5 + [ci] * 6 + [vp] * 30
+        L.dart_pmpc_stack_lm_rollout.argtypes = [vp] * 5 + [ci] * 6 + [vp] * 33
+        for fn in (L.dart_stack_work_len, L.dart_tray_from_arms_dev, L.dart_tray_from_arms,
+                   L.dart_pmpc_stack_loop_step_dev, L.dart_pmpc_stack_lm_loop_step_dev, L.dart_pmpc_stack_rollout_dev,
+                   L.dart_pmpc_stack_lm_rollout_dev, L.dart_pmpc_stack_rollout, L.dart_pmpc_stack_lm_rollout):
+            fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
         L.dart_mpc_bind.restype = ctypes.c_int
@@ -642,6 +684,21 @@ def rmpc_loop_config(**over) -> RmpcLoopConfig:
     c = RmpcLoopConfig()
     lib().dart_rmpc_loop_config_default(ctypes.byref(c))
     return _set_fields(c, over)
+
+
+def stack_config(couple=STACK_ACHIEVED) -> StackConfig:
+    """``dart_stack_config`` with the library's defaults; ``couple``: STACK_RIDE / STACK_ACHIEVED or "ride" / "achieved"."""
+    c = StackConfig()
+    lib().dart_stack_config_default(ctypes.byref(c))
+    c.couple = {"ride": STACK_RIDE, "achieved": STACK_ACHIEVED}.get(couple, couple)
+    return c
+
+
+def _any_ptr(v):
+    """A pointer argument from None, a device pointer (int) or a numpy array."""
+    if v is None:
+        return None
+    return ctypes.c_void_p(v.ctypes.data) if isinstance(v, np.ndarray) else ctypes.c_void_p(int(v))
 
 
 def _loop_shape(B, width, **sizes):
@@ -880,6 +937,58 @@ class Solver:
                         logs["X"].shape[0] if logs is not None else 0,
                         ((target, 6), (prm, 6), (plant_pvec, 34), (pz_vz, 2)), PMPC_LM_LOOP_STATE, state,
                         PMPC_LM_LOOP_LOGS, logs)
+
+    # -- the loop through the dual-arm layer (dart_pmpc_stack[_lm]_loop_step_dev / _rollout_dev / _rollout) ----
+    def _stack_logs(self, lm, logs, stack_logs, arm_logs=False):
+        spec = PMPC_LM_LOOP_LOGS if lm else PMPC_LOOP_LOGS
+        out = [_any_ptr(logs[name]) if logs is not None else None for name, _, _ in spec]
+        out += [_any_ptr(stack_logs[name]) if stack_logs is not None else None for name, _, _ in STACK_LOGS]
+        if arm_logs is not False:
+            out += [_any_ptr(arm_logs[name]) if arm_logs is not None else None for name in ARM_LOOP_LOGS]
+        return out
+
+    def stack_loop_step_dev(self, E, n, k, phase, do_post, do_pre, log_rows, arrays, logs=None, stack_logs=None,
+                            plant=None, scfg=None, lm=False, stream=0):
+        """One launch of the loop through the arms: ``phase`` STACK_COMMAND (tray_cmd from u0 and tray_pos) or
+        STACK_COUPLE (couple + post(k) and / or pre).  ``arrays`` maps the names of STACK_STEP_ARGS[lm] to device
+        pointers (absent: null); ``logs`` (PMPC_[LM_]LOOP_LOGS) and ``stack_logs`` (STACK_LOGS) likewise, or None."""
+        entry = "dart_pmpc_stack_lm_loop_step_dev" if lm else "dart_pmpc_stack_loop_step_dev"
+        rc = getattr(lib(), entry)(self._h, ctypes.byref(plant or plant_config()), ctypes.byref(scfg or stack_config()),
+                                   int(E), int(n), int(k), int(phase), int(do_post), int(do_pre), int(log_rows),
+                                   *[_any_ptr(arrays.get(a)) for a in STACK_STEP_ARGS[bool(lm)]],
+                                   *self._stack_logs(lm, logs, stack_logs), stream or None)
+        if rc != 0:
+            self._err(rc, entry)
+
+    def _stack_rollout(self, entry, host, E, n, k0, steps, log_rows, arm_prm_stride, arrays, logs, stack_logs, arm_logs,
+                       plant, scfg, dcfg, qcfg, lm, stream):
+        from .arm import arm_config, arm_dyn_config
+        names = [a for a in STACK_ROLLOUT_ARGS[bool(lm)] if not (host and a == "work")]
+        rc = getattr(lib(), entry)(self._h, ctypes.byref(plant or plant_config()), ctypes.byref(scfg or stack_config()),
+                                   ctypes.byref(dcfg or arm_dyn_config()), ctypes.byref(qcfg or arm_config()),
+                                   int(E), int(n), int(k0), int(steps), int(log_rows), int(arm_prm_stride),
+                                   *[_any_ptr(arrays.get(a)) for a in names],
+                                   *self._stack_logs(lm, logs, stack_logs, arm_logs), stream or None)
+        if rc != 0:
+            self._err(rc, entry)
+
+    def stack_rollout_dev(self, E, n, k0, steps, log_rows, arm_prm_stride, arrays, logs=None, stack_logs=None,
+                          arm_logs=None, plant=None, scfg=None, dcfg=None, qcfg=None, lm=False, stream=0):
+        """``steps`` steps of the loop through the arms from step ``k0`` on the device, asynchronous on ``stream``:
+        ``arrays`` maps STACK_ROLLOUT_ARGS[lm] to device pointers; the three log groups are mappings or None."""
+        self._stack_rollout("dart_pmpc_stack_lm_rollout_dev" if lm else "dart_pmpc_stack_rollout_dev", False, E, n, k0,
+                            steps, log_rows, arm_prm_stride, arrays, logs, stack_logs, arm_logs, plant, scfg, dcfg, qcfg,
+                            lm, stream)
+
+    def stack_rollout(self, E, n, k0, steps, log_rows, arm_prm_stride, arrays, logs=None, stack_logs=None, arm_logs=None,
+                      plant=None, scfg=None, dcfg=None, qcfg=None, lm=False):
+        """The same on host arrays (C-contiguous numpy, no ``work``; blocking): state and metrics are advanced and the
+        rows k0 .. k0+steps-1 of the logs given are filled in place."""
+        for name, a in list(arrays.items()) + [kv for g in (logs, stack_logs, arm_logs) if g for kv in g.items()]:
+            if a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous):
+                raise DartMPCError(f"stack rollout array {name!r} must be a C-contiguous numpy array")
+        self._stack_rollout("dart_pmpc_stack_lm_rollout" if lm else "dart_pmpc_stack_rollout", True, E, n, k0, steps,
+                            log_rows, arm_prm_stride, arrays, logs, stack_logs, arm_logs, plant, scfg, dcfg, qcfg, lm, 0)
 
     def sync(self):
         rc = lib().dart_mpc_sync(self._h)

@@ -291,6 +291,27 @@ def unpack_snapshot(rows, n) -> dict:
     return out
 
 
+def tray_from_arms(ee_pos, ee_quat, grasp=None) -> dict:
+    """The tray two arms hold (``dart_tray_from_arms``, the coupling of the loop through the arms): ee_pos [E, 2, 3] the
+    EE points, ee_quat [E, 2, 4] the EE orientations (wxyz, either sign), ``grasp`` [2, 7] (default ``DACTL_GRASP``).
+    Returns dict(tray [E, 7] pos | quat, tilt [E, 2] = [-pitch, roll], yaw, gap, angle [E]); one experiment ([2, 3],
+    [2, 4]) gives the same without the E axis."""
+    one = np.ndim(ee_pos) == 2
+    pos = np.ascontiguousarray(np.reshape(np.asarray(ee_pos, dtype=np.float64), (-1, 2, 3)))
+    quat = np.ascontiguousarray(np.reshape(np.asarray(ee_quat, dtype=np.float64), (-1, 2, 4)))
+    E = pos.shape[0]
+    if quat.shape[0] != E:
+        raise DartMPCError("ee_pos [E, 2, 3] and ee_quat [E, 2, 4] differ in E")
+    g = np.ascontiguousarray(DACTL_GRASP if grasp is None else grasp, dtype=np.float64)
+    if g.shape != (2, 7):
+        raise DartMPCError("grasp transforms are [2, 7] (pos | quat)")
+    tray, tilt, diag = np.zeros((E, 7)), np.zeros((E, 2)), np.zeros((E, 3))
+    _check(lib().dart_tray_from_arms(E, _ptr(pos), _ptr(quat), _ptr(g), _ptr(tray), _ptr(tilt), _ptr(diag)),
+           "dart_tray_from_arms")
+    out = {"tray": tray, "tilt": tilt, "yaw": diag[:, 0].copy(), "gap": diag[:, 1].copy(), "angle": diag[:, 2].copy()}
+    return {k: v[0] for k, v in out.items()} if one else out
+
+
 class DualArmControl:
     """``DACTL.control`` (PMPC/src/dualctl.py) with dynamics and solve on the device: tray pose -> both arms' torques.
 

@@ -1119,3 +1119,118 @@ def rollout_dual_arm(q0, qd0, tray_poses, models, params, steps: int, plant_mode
     if rc != 0:
         raise A.DartMPCError(f"dart_dual_arm_rollout failed ({rc})")
     return {"q": q, "qd": qd, "qdd_prev": qp, "metrics": met, "logs": logs, "wall_s": wall}
+
+
+# ---- the PMPC loop closed through the dual-arm layer (dart_pmpc_stack_rollout) --------------------------------------
+def stack_arrays(states0, targets, prm, q0, qd0, models, params, tray_pos, plant_models=None, plant_pvec=None,
+                 x_rot0=None, grasp=None, Ts: float = 0.002):
+    """The host arrays of a fresh stack run in the names of ``_lib.STACK_ROLLOUT_ARGS`` (without ``work``): inputs and
+    the in/out state and metrics (metrics zeros with slot 1 = -1; stack and arm metrics zeros).  Returns
+    (arrays, E, n, lm)."""
+    from . import arm as A
+    from ._lib import loop_metrics
+    states0 = np.asarray(states0, float).reshape(-1, 6)
+    E = states0.shape[0]
+    q = np.ascontiguousarray(q0, dtype=np.float64).copy()
+    qd = np.ascontiguousarray(qd0, dtype=np.float64).copy()
+    if q.ndim != 3 or q.shape[:2] != (E, 2) or qd.shape != q.shape:
+        raise A.DartMPCError(f"q0 and qd0 are [{E}, 2, n]")
+    n = q.shape[2]
+    rows = A._model_rows(models, n, 2)
+    pl, pr = params if isinstance(params, (tuple, list)) else (params, params)
+    lm = plant_pvec is not None
+    arrays = {
+        "target": np.ascontiguousarray(np.asarray(targets, float).reshape(E, 6)),
+        "prm": np.ascontiguousarray(np.asarray(prm, float).reshape(E, 6)),
+        "x": _cross_plant(states0[:, :4], x_rot0, plant_pvec, Ts, None).x if lm else states0.copy(),
+        "tilt": np.zeros((E, 2)), "metrics": loop_metrics(E),
+        "grasp": np.ascontiguousarray(A.DACTL_GRASP if grasp is None else grasp, dtype=np.float64),
+        "models": rows, "plant_models": rows if plant_models is None else A._model_rows(plant_models, n, 2),
+        "arm_prm": np.ascontiguousarray(np.tile(np.stack([A.pack_params(pl), A.pack_params(pr)]), (E, 1))),
+        "q": q.reshape(2 * E, n), "qd": qd.reshape(2 * E, n), "qdd_prev": np.zeros((2 * E, n)),
+        "arm_metrics": np.zeros((2 * E, A.NMETRIC)),
+        "tray_pos": np.ascontiguousarray(np.broadcast_to(np.asarray(tray_pos, dtype=np.float64), (E, 3))),
+        "stack_metrics": np.zeros((E, 8)),
+    }
+    if lm:
+        arrays["plant_pvec"] = np.ascontiguousarray(np.asarray(plant_pvec, float).reshape(E, 34))
+        arrays["pz_vz"] = np.ascontiguousarray(states0[:, 4:6])
+    if arrays["grasp"].shape != (2, 7):
+        raise A.DartMPCError("grasp transforms are [2, 7] (pos | quat)")
+    return arrays, E, n, lm
+
+
+def stack_logs(rows, E, n, lm):
+    """The three log groups of a stack run, prefilled: (PMPC logs, stack logs, arm logs)."""
+    from ._lib import PMPC_LOOP_LOGS, PMPC_LM_LOOP_LOGS, STACK_LOGS, LOG_INT_FILL, loop_logs
+    B = 2 * E
+    arm = {"q": np.full((rows, B, n), np.nan), "qd": np.full((rows, B, n), np.nan), "tau": np.full((rows, B, n), np.nan),
+           "ee_pos": np.full((rows, B, 3), np.nan), "loss": np.full((rows, B), np.nan),
+           "status": np.full((rows, B), LOG_INT_FILL, dtype=np.int32)}
+    return loop_logs(PMPC_LM_LOOP_LOGS if lm else PMPC_LOOP_LOGS, rows, E), loop_logs(STACK_LOGS, rows, E), arm
+
+
+def rollout_stack(states0, targets, prm, q0, qd0, models, params, steps: int, tray_pos, couple="achieved",
+                  plant_models=None, plant_pvec=None, metrics_only: bool = False, x_rot0=None, settle_steps: int = 0,
+                  N: int = 20, Ts: float = 0.002, tol: float = 1e-8, device: int = 0, plant_kw: dict | None = None,
+                  grasp=None, jacdot_point: int = 0, **cfg):
+    """E PMPC experiments closed through two arms each, resident on the device (``dart_pmpc_stack_rollout``): per step
+    the solve, the tray pose commanded by its tilt, both arms' dynamics, impedance QP and plant step, the tray the arms
+    then hold, and the object's plant step -- with ``couple="achieved"`` on the achieved tilt (the arms are the lag),
+    with ``"ride"`` on the lagged command as in ``rollout_pmpc`` (the arms are measured only).
+
+    states0, targets, prm, ``plant_pvec`` / ``x_rot0`` as ``rollout_pmpc``; q0, qd0 [E, 2, n], models, params,
+    ``plant_models`` (a heavier last link is a payload) as ``rollout_dual_arm``; ``tray_pos`` [3] or [E, 3].  The arms
+    should start near the grasp pose of a level tray: ``settle_steps`` > 0 first runs ``rollout_dual_arm`` for that many
+    steps against the level pose at ``tray_pos`` and starts from where it ends.
+
+    Returns dict(logs: the per-experiment log dicts of ``rollout_pmpc`` (None with ``metrics_only``), status, iters
+    [steps, E], metrics [E, 8] (_lib.METRIC_SLOTS), x, tilt (the final state), arm: what ``rollout_dual_arm`` returns,
+    stack_metrics [E, 8] (_lib.STACK_METRIC_SLOTS), tilt_log [steps, E, 2], tray_log [steps, E, 7], wall_s)."""
+    from . import arm as A
+    from ._lib import plant_config, stack_config
+    if settle_steps:
+        E0 = np.asarray(q0).shape[0]
+        level = np.zeros((1, E0, 7))
+        level[0, :, :3] = np.broadcast_to(np.asarray(tray_pos, dtype=np.float64), (E0, 3))
+        level[0, :, 3] = 1.0
+        st = rollout_dual_arm(q0, qd0, level, models, params, int(settle_steps), plant_models=plant_models,
+                              metrics_only=True, grasp=grasp, jacdot_point=jacdot_point, **cfg)
+        q0, qd0 = st["q"], st["qd"]
+    arrays, E, n, lm = stack_arrays(states0, targets, prm, q0, qd0, models, params, tray_pos, plant_models, plant_pvec,
+                                    x_rot0, grasp, Ts)
+    lg, sl, al = (None, None, None) if metrics_only else stack_logs(steps, E, n, lm)
+    solver = Solver(N=N, Ts=Ts, tol=tol, B_max=max(E, 1), device=device)
+    try:
+        t0 = time.perf_counter()
+        solver.stack_rollout(E, n, 0, steps, 0 if metrics_only else steps, arrays["arm_prm"].shape[1], arrays, lg, sl, al,
+                             plant=plant_config(**(plant_kw or {})), scfg=stack_config(couple),
+                             dcfg=A.arm_dyn_config(jacdot_point=int(jacdot_point)), qcfg=A.arm_config(**cfg), lm=lm)
+        wall = time.perf_counter() - t0
+    finally:
+        solver.close()
+    out = {"logs": None, "status": None, "iters": None, "metrics": arrays["metrics"], "x": arrays["x"],
+           "tilt": arrays["tilt"], "stack_metrics": arrays["stack_metrics"], "tilt_log": None, "tray_log": None,
+           "arm": {"q": arrays["q"].reshape(E, 2, n), "qd": arrays["qd"].reshape(E, 2, n),
+                   "qdd_prev": arrays["qdd_prev"].reshape(E, 2, n), "metrics": arrays["arm_metrics"], "logs": al,
+                   "wall_s": wall},
+           "wall_s": wall}
+    if metrics_only:
+        return out
+    t = np.arange(steps) * Ts
+    tg = arrays["target"]
+    logs = []
+    for b in range(E):
+        d = {"t": t, "X": lg["X"][:, b], "X_target": np.tile(tg[b], (steps, 1)), "U_cmd": lg["U_cmd"][:, b],
+             "quat_tray": lg["quat_tray"][:, b], "loss": lg["loss"][:, b], "solve_time": np.full(steps, wall / max(steps, 1))}
+        for a, side in enumerate("LR"):
+            d[side + "_torques"], d[side + "_qpos"] = al["tau"][:, 2 * b + a], al["q"][:, 2 * b + a]
+            d[side + "_qvel"], d[side + "_ee_pos"] = al["qd"][:, 2 * b + a], al["ee_pos"][:, 2 * b + a]
+            d[side + "_ee_vel"] = np.zeros((steps, 6))      # (not kept by the arm loop)
+        d.update(logger_metrics(d, Ts))
+        d["metrics"] = arrays["metrics"][b]
+        if lm:
+            d["rot"] = lg["rot"][:, b]
+        logs.append(d)
+    out.update(logs=logs, status=lg["status"], iters=lg["iters"], tilt_log=sl["tilt"], tray_log=sl["tray"])
+    return out

@@ -1388,6 +1388,150 @@ int dart_lmpc_pbt_step(const dart_lmpc_pbt_config *cfg, int P, const double *fit
                        float *weights, float *critic, float *adam, int32_t *adam_step, double *hyper,
                        int32_t *rank_out, int32_t *parent_out);
 
+/* The PMPC closed loop through the dual-arm layer (added within ABI 8: new entries only).  One device-resident loop
+ * for E experiments of two arms each (arm instances 2 e, 2 e + 1), the reference's driver loop
+ * (PMPC/main_parallel_enhanced.py:290-419: u_cmd -> quaternion -> DACTL.control -> torques -> step).  Per step k, six
+ * launches on one stream:
+ *   solve        dart_mpc_solve_batch_dev                                     x0 -> u0
+ *   command      tray_cmd[e] = (tray_pos[e] | quaternion of u0[e]), the expressions of the rollouts' log_quat
+ *   arm dynamics of the joint state q_k against tray_cmd (dart_dual_arm_control_dev's), EE orientations kept
+ *   arm QP       dart_arm_solve_batch_dev
+ *   arm plant    dart_dual_arm_rollout_dev's plant step, arm metrics and logs   q_k -> q_{k+1}
+ *   couple + object   the tray the two arms hold at q_k, then post(k) / pre(k+1) of dart_pmpc[_lm]_loop_step_dev
+ *
+ * Coupling (dart_tray_from_arms): with grasp [2][7] (pos | quat wxyz, tray frame) and the arms' EE points ee_pos and
+ * orientations ee_quat, q_a = unit(ee_quat_a (x) conj(g_q_a)), q_R flipped into q_L's hemisphere, q_t = unit(q_L + q_R)
+ * with w >= 0, p_t = 1/2 sum_a (ee_pos_a - rot(q_t, g_p_a)); roll = atan2(2(wx + yz), 1 - 2(x^2 + y^2)),
+ * pitch = asin(clamp(2(wy - zx), -1, 1)), yaw = atan2(2(wz + xy), 1 - 2(y^2 + z^2)) (the inverse of the command's
+ * Euler xyz [u1, -u0, 0]); achieved tilt = [-pitch, roll]; diag = yaw, grasp gap | |ee_R - ee_L| - |g_R - g_L| |,
+ * disagreement angle 2 atan2(|v|, |w|) of q_L (x) conj(q_R).  The result does not change under a sign flip of either
+ * ee_quat.  Non-finite input gives non-finite output, never a fault.
+ *
+ * couple selects the tilt the object plant sees:
+ *   DART_STACK_RIDE      the lagged command, exactly dart_pmpc[_lm]_rollout; the arms ride along and are measured
+ *   DART_STACK_ACHIEVED  tilt := the achieved tilt of q_k, held over the step; no lag, plant->tau is not used.  A
+ *                        non-finite achieved tilt is not passed on: the last tilt is held and the step counted.
+ *
+ * Arrays.  The PMPC loop's: target, prm [E][6], x [E][6] (LMPC plant: x [E][8], plant_pvec [E][34], pz_vz [E][2]), tilt
+ * [E][2], metrics [E][8] (the cross-plant loops' slots, kept for the tray plant too, whose slot 6 stays 0; in/out, a
+ * fresh run starts from zeros with slot 1 = -1).  The arm rollout's: grasp, models, plant_models [2][model_len], arm_prm
+ * (arm_prm_stride 0 or the row length), q, qd, qdd_prev [2 E][n], arm_metrics [2 E][6], all as dart_dual_arm_rollout;
+ * work: dart_stack_work_len(E, n) doubles of device memory (it starts with the arm rollout's work, so the step's
+ * snapshot rows are its first 2 E dart_arm_snapshot_len(n) doubles).  tray_pos [E][3].  stack_metrics [E][8], in/out, a
+ * fresh run starts from zeros: 0 max_i |tilt_achieved - u0|_i of the last step with a finite achieved tilt, 1 its
+ * maximum over the steps, 2 max |yaw|, 3 max grasp gap, 4 max disagreement angle, 5 max |p_t - tray_pos|, 6 steps with
+ * a held tilt, 7 steps.  A maximum ignores a NaN.  Every metric is in/out: two calls of K1 and K2 steps (k0 = 0, then
+ * k0 = K1) give the bits of one call of K1 + K2.
+ *
+ * Logs [log_rows][.]..., row k0 + j for step j, in three groups, each given whole or all null: the PMPC rollout's
+ * (log_X, log_U, log_quat, log_loss, log_status, log_iters; LMPC plant: and log_rot); log_tilt [..][E][2] (the achieved
+ * tilt as measured) and log_tray [..][E][7] (the achieved pose); the arm rollout's six ([..][2 E][.]).  With no group
+ * given log_rows is not consulted (metrics-only), on both plants.
+ *
+ * DART_MPC_EINVAL before any HIP call: a handle that is not PMPC's, a null config or required pointer, a group of logs
+ * given in part, k0 + steps > log_rows with a group given, E < 1 or E > B_max, couple neither of the two, and what
+ * dart_dual_arm_rollout refuses of n, arm_prm_stride and the two arm configs. */
+#define DART_STACK_RIDE 0
+#define DART_STACK_ACHIEVED 1
+#define DART_STACK_COMMAND 0 /* phase of a loop-step launch: the command kernel ... */
+#define DART_STACK_COUPLE 1  /* ... or couple + object */
+
+typedef struct dart_stack_config {
+    int32_t couple;        /* DART_STACK_ACHIEVED */
+    int32_t reserved[7];   /* 0 */
+} dart_stack_config;
+
+void dart_stack_config_default(dart_stack_config *cfg);
+int dart_stack_work_len(int E, int n); /* doubles; DART_MPC_EINVAL as dart_dual_arm_work_len */
+
+/* The coupling alone: ee_pos [2 E][3], ee_quat [2 E][4], grasp [2][7] -> tray [E][7], tilt [E][2], diag [E][3].
+ * DART_MPC_EINVAL: E < 1 or > 2^20, a null pointer. */
+int dart_tray_from_arms_dev(int E, const double *ee_pos, const double *ee_quat, const double *grasp, double *tray,
+                            double *tilt, double *diag, void *hip_stream);
+int dart_tray_from_arms(int E, const double *ee_pos, const double *ee_quat, const double *grasp, double *tray,
+                        double *tilt, double *diag);
+
+/* One launch of the loop (device pointers, asynchronous), the pattern of dart_pmpc_loop_step_dev.  phase
+ * DART_STACK_COMMAND: tray_cmd [E][7] from u0 and tray_pos (only these three are read; do_post / do_pre are not
+ * consulted).  phase DART_STACK_COUPLE: couple + post(k) and / or pre; snap [2 E][dart_arm_snapshot_len(n)] and ee_quat
+ * [2 E][4] are what the step's arm dynamics wrote (read by post only); x0, u0, f, status, iters are the solve's
+ * per-step arrays; tray_cmd is not read. */
+int dart_pmpc_stack_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_stack_config *scfg,
+                                  int E, int n, int k, int phase, int do_post, int do_pre, int log_rows,
+                                  const double *target, const double *prm, const double *tray_pos, const double *grasp,
+                                  const double *snap, const double *ee_quat,
+                                  double *x, double *tilt, double *metrics, double *stack_metrics,
+                                  double *x0, double *tray_cmd,
+                                  const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                                  double *log_X, double *log_U, double *log_quat, double *log_loss,
+                                  int32_t *log_status, int32_t *log_iters, double *log_tilt, double *log_tray,
+                                  void *hip_stream);
+int dart_pmpc_stack_lm_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_stack_config *scfg,
+                                     int E, int n, int k, int phase, int do_post, int do_pre, int log_rows,
+                                     const double *target, const double *plant_pvec, const double *pz_vz,
+                                     const double *tray_pos, const double *grasp,
+                                     const double *snap, const double *ee_quat,
+                                     double *x, double *tilt, double *metrics, double *stack_metrics,
+                                     double *x0, double *tray_cmd,
+                                     const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                                     double *log_X, double *log_U, double *log_quat, double *log_loss,
+                                     int32_t *log_status, int32_t *log_iters, double *log_rot,
+                                     double *log_tilt, double *log_tray, void *hip_stream);
+
+/* `steps` steps from step k0, no host synchronisation in between.  Device pointers, asynchronous on hip_stream
+ * (NULL: the handle's stream). */
+int dart_pmpc_stack_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_stack_config *scfg,
+                                const dart_arm_dyn_config *dcfg, const dart_arm_config *qcfg,
+                                int E, int n, int k0, int steps, int log_rows, int arm_prm_stride,
+                                const double *target, const double *prm, double *x, double *tilt, double *metrics,
+                                const double *grasp, const double *models, const double *plant_models,
+                                const double *arm_prm, double *q, double *qd, double *qdd_prev, double *arm_metrics,
+                                double *work, const double *tray_pos, double *stack_metrics,
+                                double *log_X, double *log_U, double *log_quat, double *log_loss,
+                                int32_t *log_status, int32_t *log_iters, double *log_tilt, double *log_tray,
+                                double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
+                                int32_t *status_log, void *hip_stream);
+int dart_pmpc_stack_lm_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_stack_config *scfg,
+                                   const dart_arm_dyn_config *dcfg, const dart_arm_config *qcfg,
+                                   int E, int n, int k0, int steps, int log_rows, int arm_prm_stride,
+                                   const double *target, const double *prm, const double *plant_pvec,
+                                   const double *pz_vz, double *x, double *tilt, double *metrics,
+                                   const double *grasp, const double *models, const double *plant_models,
+                                   const double *arm_prm, double *q, double *qd, double *qdd_prev, double *arm_metrics,
+                                   double *work, const double *tray_pos, double *stack_metrics,
+                                   double *log_X, double *log_U, double *log_quat, double *log_loss,
+                                   int32_t *log_status, int32_t *log_iters, double *log_rot,
+                                   double *log_tilt, double *log_tray,
+                                   double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
+                                   int32_t *status_log, void *hip_stream);
+
+/* Host pointers: the arrays are staged through the handle's arena around the device form (no work argument; the rows
+ * k0 .. k0 + steps - 1 of the logs given come down); blocks. */
+int dart_pmpc_stack_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const dart_stack_config *scfg,
+                            const dart_arm_dyn_config *dcfg, const dart_arm_config *qcfg,
+                            int E, int n, int k0, int steps, int log_rows, int arm_prm_stride,
+                            const double *target, const double *prm, double *x, double *tilt, double *metrics,
+                            const double *grasp, const double *models, const double *plant_models,
+                            const double *arm_prm, double *q, double *qd, double *qdd_prev, double *arm_metrics,
+                            const double *tray_pos, double *stack_metrics,
+                            double *log_X, double *log_U, double *log_quat, double *log_loss,
+                            int32_t *log_status, int32_t *log_iters, double *log_tilt, double *log_tray,
+                            double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
+                            int32_t *status_log, void *hip_stream);
+int dart_pmpc_stack_lm_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const dart_stack_config *scfg,
+                               const dart_arm_dyn_config *dcfg, const dart_arm_config *qcfg,
+                               int E, int n, int k0, int steps, int log_rows, int arm_prm_stride,
+                               const double *target, const double *prm, const double *plant_pvec,
+                               const double *pz_vz, double *x, double *tilt, double *metrics,
+                               const double *grasp, const double *models, const double *plant_models,
+                               const double *arm_prm, double *q, double *qd, double *qdd_prev, double *arm_metrics,
+                               const double *tray_pos, double *stack_metrics,
+                               double *log_X, double *log_U, double *log_quat, double *log_loss,
+                               int32_t *log_status, int32_t *log_iters, double *log_rot,
+                               double *log_tilt, double *log_tray,
+                               double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
+                               int32_t *status_log, void *hip_stream);
+
 /* ABI version (DART_MPC_ABI_VERSION) of the loaded library. */
 int dart_mpc_abi_version(void);
 
