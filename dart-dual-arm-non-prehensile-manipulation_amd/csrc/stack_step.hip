@@ -13,56 +13,11 @@
 
 #include "arm_dyn.h"
 #include "loop_plant.h"
+#include "stack_couple.h"
 
 #pragma clang fp contract(off)
 
 namespace dartmpc {
-
-constexpr int kStackWave = 64;
-constexpr int kStackWaves = 4;
-
-__device__ __forceinline__ Q4 qconj(Q4 a) { return Q4{a.w, -a.x, -a.y, -a.z}; }
-__device__ __forceinline__ Q4 qneg(Q4 a) { return Q4{-a.w, -a.x, -a.y, -a.z}; }
-__device__ __forceinline__ double norm3(V3 a) { return sqrt(a.x * a.x + a.y * a.y + a.z * a.z); }
-
-// pmpc.tilt_to_quat, the expressions of pmpc_loop_kernel's log_quat: Euler xyz [u1, -u0, 0] -> (w, x, y, z)
-__device__ __forceinline__ Q4 tilt_quat(const double* u) {
-    const double ax = u[1] / 2.0, ay = -u[0] / 2.0;
-    const double cx = cos(ax), cy = cos(ay), cz = 1.0, sx = sin(ax), sy = sin(ay), sz = 0.0;
-    return Q4{cx * cy * cz + sx * sy * sz, sx * cy * cz - cx * sy * sz, cx * sy * cz + sx * cy * sz,
-              cx * cy * sz - sx * sy * cz};
-}
-
-// the tray two arms hold (stack_step.h): EE points eL, eR, EE orientations, grasp [2][7]
-struct TrayMeasure {
-    V3 p;
-    Q4 q;
-    double tilt[2], yaw, gap, angle;
-};
-
-__device__ __forceinline__ TrayMeasure tray_from_arms(const double* ee_L, const double* ee_R, const double* eq_L,
-                                                      const double* eq_R, const double* grasp) {
-    TrayMeasure m;
-    const V3 eL = ld3(ee_L), eR = ld3(ee_R), gL = ld3(grasp), gR = ld3(grasp + 7);
-    const Q4 qL = qunit(qmul(ld4(eq_L), qconj(ld4(grasp + 3))));
-    Q4 qR = qunit(qmul(ld4(eq_R), qconj(ld4(grasp + 10))));
-    if (qL.w * qR.w + qL.x * qR.x + qL.y * qR.y + qL.z * qR.z < 0.0) qR = qneg(qR);
-    Q4 qt = qunit(Q4{qL.w + qR.w, qL.x + qR.x, qL.y + qR.y, qL.z + qR.z});
-    if (qt.w < 0.0) qt = qneg(qt);
-    m.q = qt;
-    m.p = 0.5 * ((eL - qrot(qt, gL)) + (eR - qrot(qt, gR)));
-    // Euler xyz angles of qt, the inverse of tilt_quat (a NaN passes the clamp)
-    const double roll = atan2(2.0 * (qt.w * qt.x + qt.y * qt.z), 1.0 - 2.0 * (qt.x * qt.x + qt.y * qt.y));
-    const double sp = 2.0 * (qt.w * qt.y - qt.z * qt.x);
-    const double pitch = asin(sp > 1.0 ? 1.0 : sp < -1.0 ? -1.0 : sp);
-    m.yaw = atan2(2.0 * (qt.w * qt.z + qt.x * qt.y), 1.0 - 2.0 * (qt.y * qt.y + qt.z * qt.z));
-    m.tilt[0] = -pitch;
-    m.tilt[1] = roll;
-    m.gap = fabs(norm3(eR - eL) - norm3(gR - gL));
-    const Q4 d = qmul(qL, qconj(qR));
-    m.angle = 2.0 * atan2(norm3(V3{d.x, d.y, d.z}), fabs(d.w));
-    return m;
-}
 
 __global__ __launch_bounds__(kStackWave* kStackWaves) void tray_from_arms_kernel(TrayFromArmsArgs a) {
     const int lane = threadIdx.x & (kStackWave - 1);
@@ -148,23 +103,7 @@ __global__ __launch_bounds__(kStackWave* kStackWaves) void stack_step_kernel(Sta
             const double dx = x[0] - a.target[6 * b], dy = x[2] - a.target[6 * b + 2];
             loop_metrics_step(a.metrics + 8 * b, a.k, a.Ts, sqrt(dx * dx + dy * dy), u, status, iters, LM ? x[4] : 0.0,
                               LM ? x[6] : 0.0);
-            {   // stack_metrics: the row read whole before it is written
-                double* s = a.stack_metrics + STACK_NMETRIC * b;
-                const double last = s[0], dmax = s[1], yaw = s[2], gap = s[3], ang = s[4], perr = s[5], nheld = s[6],
-                             n = s[7];
-                const double d0 = fabs(m.tilt[0] - u[0]), d1 = fabs(m.tilt[1] - u[1]);
-                const double dev = d0 > d1 ? d0 : d1;
-                const double ay = fabs(m.yaw);
-                const double pe = norm3(m.p - ld3(a.tray_pos + 3 * b));
-                s[0] = held ? last : dev;
-                s[1] = (!held && dev > dmax) ? dev : dmax;
-                s[2] = ay > yaw ? ay : yaw;
-                s[3] = m.gap > gap ? m.gap : gap;
-                s[4] = m.angle > ang ? m.angle : ang;
-                s[5] = pe > perr ? pe : perr;
-                s[6] = held ? nheld + 1.0 : nheld;
-                s[7] = n + 1.0;
-            }
+            stack_metrics_step(a.stack_metrics + STACK_NMETRIC * b, m, u, a.tray_pos + 3 * b);
             if (a.stack_logs) {
                 a.log_tilt[2 * row] = m.tilt[0]; a.log_tilt[2 * row + 1] = m.tilt[1];
                 double* t = a.log_tray + 7 * row;

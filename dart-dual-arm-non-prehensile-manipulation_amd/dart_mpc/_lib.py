@@ -71,7 +71,9 @@ EXPORTS = ("dart_mpc_config_default", "dart_mpc_create", "dart_mpc_solve_batch",
            "dart_dual_arm_rollout_dev", "dart_dual_arm_rollout",
            "dart_stack_config_default", "dart_stack_work_len", "dart_tray_from_arms_dev", "dart_tray_from_arms",
            "dart_pmpc_stack_loop_step_dev", "dart_pmpc_stack_lm_loop_step_dev", "dart_pmpc_stack_rollout_dev",
-           "dart_pmpc_stack_lm_rollout_dev", "dart_pmpc_stack_rollout", "dart_pmpc_stack_lm_rollout")
+           "dart_pmpc_stack_lm_rollout_dev", "dart_pmpc_stack_rollout", "dart_pmpc_stack_lm_rollout",
+           "dart_rmpc_stack_loop_step_dev", "dart_rmpc_stack_lm_loop_step_dev", "dart_rmpc_stack_rollout_dev",
+           "dart_rmpc_stack_lm_rollout_dev", "dart_rmpc_stack_rollout", "dart_rmpc_stack_lm_rollout")
 VARIANT_PMPC, VARIANT_RMPC, VARIANT_LMPC = 0, 1, 2
 ABI_VERSION = 8
 
@@ -168,6 +170,17 @@ STACK_ROLLOUT_ARGS = {False: ("target", "prm", "x", "tilt", "metrics", "grasp", 
                              "arm_prm", "q", "qd", "qdd_prev", "arm_metrics", "work", "tray_pos", "stack_metrics")}
 STACK_LOGS = (("tilt", 2, np.float64), ("tray", 7, np.float64))
 ARM_LOOP_LOGS = ("q", "qd", "tau", "ee_pos", "loss", "status")         # [rows, 2 E, .]; status int32
+# the RMPC loop through the dual-arm layer (dart_rmpc_stack_*): pointer arguments in the argument order of
+# include/dart_mpc.h, and its stack log group (the command, its quaternion, the achieved tilt and pose)
+_RMPC_STACK_STEP = ("tray_pos", "grasp", "snap", "ee_quat", "x", "tilt", "prev", "u_prev", "r_v", "theta", "done", "nlog",
+                    "metrics", "stack_metrics", "x0", "Rref", "phi", "y", "tray_cmd", "u0", "f", "status", "iters")
+_RMPC_STACK_ROLLOUT = ("x", "tilt", "prev", "u_prev", "r_v", "theta", "P", "w", "done", "nlog", "metrics", "grasp", "models",
+                       "plant_models", "arm_prm", "q", "qd", "qdd_prev", "arm_metrics", "work", "tray_pos", "stack_metrics")
+RMPC_STACK_STEP_ARGS = {False: ("target", "prm", "mu") + _RMPC_STACK_STEP,
+                        True: ("target", "prm", "plant_pvec") + _RMPC_STACK_STEP}
+RMPC_STACK_ROLLOUT_ARGS = {False: ("target", "prm", "mu") + _RMPC_STACK_ROLLOUT,
+                           True: ("target", "prm", "plant_pvec") + _RMPC_STACK_ROLLOUT}
+RMPC_STACK_LOGS = (("U_cmd", 2, np.float64), ("quat_tray", 4, np.float64), ("tilt", 2, np.float64), ("tray", 7, np.float64))
 
 
 # Arrays of the closed-loop rollouts in the argument order of include/dart_mpc.h: (name, row width, dtype);
@@ -524,6 +537,17 @@ def lib():
         for fn in (L.dart_stack_work_len, L.dart_tray_from_arms_dev, L.dart_tray_from_arms,
                    L.dart_pmpc_stack_loop_step_dev, L.dart_pmpc_stack_lm_loop_step_dev, L.dart_pmpc_stack_rollout_dev,
                    L.dart_pmpc_stack_lm_rollout_dev, L.dart_pmpc_stack_rollout, L.dart_pmpc_stack_lm_rollout):
+            fn.restype = ctypes.c_int
+    if hasattr(L, "dart_rmpc_stack_rollout_dev"):  # (absent only in older in-tree builds used for A/B timing)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.dart_rmpc_stack_loop_step_dev.argtypes = [vp] * 4 + [ci] * 7 + [vp] * 41
+        L.dart_rmpc_stack_lm_loop_step_dev.argtypes = [vp] * 4 + [ci] * 7 + [vp] * 42
+        L.dart_rmpc_stack_rollout_dev.argtypes = [vp] * 6 + [ci] * 6 + [vp] * 46
+        L.dart_rmpc_stack_lm_rollout_dev.argtypes = [vp] * 6 + [ci] * 6 + [vp] * 47
+        L.dart_rmpc_stack_rollout.argtypes = [vp] * 6 + [ci] * 6 + [vp] * 45
+        L.dart_rmpc_stack_lm_rollout.argtypes = [vp] * 6 + [ci] * 6 + [vp] * 46
+        for fn in (L.dart_rmpc_stack_loop_step_dev, L.dart_rmpc_stack_lm_loop_step_dev, L.dart_rmpc_stack_rollout_dev,
+                   L.dart_rmpc_stack_lm_rollout_dev, L.dart_rmpc_stack_rollout, L.dart_rmpc_stack_lm_rollout):
             fn.restype = ctypes.c_int
     if hasattr(L, "dart_mpc_bind"):        # (absent only in older in-tree builds used for A/B timing)
         L.dart_mpc_bind.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 9
@@ -1170,6 +1194,64 @@ class RmpcSolver(Solver):
         self._loop_host("dart_rmpc_lm_rollout", (plant or plant_config(), loop or rmpc_loop_config()), k0, steps,
                         logs["x"].shape[0] if logs is not None else 0, ((target, 4), (prm, 10), (plant_pvec, 34)),
                         RMPC_LM_LOOP_STATE, state, RMPC_LM_LOOP_LOGS, logs, nw=self.nw)
+
+    # -- the loop through the dual-arm layer (dart_rmpc_stack[_lm]_loop_step_dev / _rollout_dev / _rollout) ----
+    def _rmpc_stack_logs(self, lm, rmpc_logs, stack_logs, arm_logs=False):
+        spec = RMPC_LM_LOOP_LOGS if lm else RMPC_LOOP_LOGS
+        out = [_any_ptr(rmpc_logs[name]) if rmpc_logs is not None else None for name, _, _ in spec]
+        out += [_any_ptr(stack_logs[name]) if stack_logs is not None else None for name, _, _ in RMPC_STACK_LOGS]
+        if arm_logs is not False:
+            out += [_any_ptr(arm_logs[name]) if arm_logs is not None else None for name in ARM_LOOP_LOGS]
+        return out
+
+    def rmpc_stack_loop_step_dev(self, E, n, k, phase, do_post, do_pre, log_rows, arrays, rmpc_logs=None, stack_logs=None,
+                                 plant=None, loop=None, scfg=None, lm=False, stream=0):
+        """One launch of the RMPC loop through the arms: ``phase`` STACK_COMMAND (tray_cmd from u0 and tray_pos) or
+        STACK_COUPLE (couple + post(k) and / or pre).  ``arrays`` maps the names of RMPC_STACK_STEP_ARGS[lm] to device
+        pointers (absent: null); ``rmpc_logs`` (RMPC_[LM_]LOOP_LOGS) and ``stack_logs`` (RMPC_STACK_LOGS) likewise, or
+        None."""
+        entry = "dart_rmpc_stack_lm_loop_step_dev" if lm else "dart_rmpc_stack_loop_step_dev"
+        rc = getattr(lib(), entry)(self._h, ctypes.byref(plant or plant_config()), ctypes.byref(loop or rmpc_loop_config()),
+                                   ctypes.byref(scfg or stack_config()),
+                                   int(E), int(n), int(k), int(phase), int(do_post), int(do_pre), int(log_rows),
+                                   *[_any_ptr(arrays.get(a)) for a in RMPC_STACK_STEP_ARGS[bool(lm)]],
+                                   *self._rmpc_stack_logs(lm, rmpc_logs, stack_logs), stream or None)
+        if rc != 0:
+            self._err(rc, entry)
+
+    rmpc_stack_loop_step = rmpc_stack_loop_step_dev
+
+    def _rmpc_stack_rollout(self, entry, host, E, n, k0, steps, log_rows, arm_prm_stride, arrays, rmpc_logs, stack_logs,
+                            arm_logs, plant, loop, scfg, dcfg, qcfg, lm, stream):
+        from .arm import arm_config, arm_dyn_config
+        names = [a for a in RMPC_STACK_ROLLOUT_ARGS[bool(lm)] if not (host and a == "work")]
+        rc = getattr(lib(), entry)(self._h, ctypes.byref(plant or plant_config()), ctypes.byref(loop or rmpc_loop_config()),
+                                   ctypes.byref(scfg or stack_config()), ctypes.byref(dcfg or arm_dyn_config()),
+                                   ctypes.byref(qcfg or arm_config()),
+                                   int(E), int(n), int(k0), int(steps), int(log_rows), int(arm_prm_stride),
+                                   *[_any_ptr(arrays.get(a)) for a in names],
+                                   *self._rmpc_stack_logs(lm, rmpc_logs, stack_logs, arm_logs), stream or None)
+        if rc != 0:
+            self._err(rc, entry)
+
+    def rmpc_stack_rollout_dev(self, E, n, k0, steps, log_rows, arm_prm_stride, arrays, rmpc_logs=None, stack_logs=None,
+                               arm_logs=None, plant=None, loop=None, scfg=None, dcfg=None, qcfg=None, lm=False, stream=0):
+        """``steps`` steps of the RMPC loop through the arms from step ``k0`` on the device, asynchronous on ``stream``:
+        ``arrays`` maps RMPC_STACK_ROLLOUT_ARGS[lm] to device pointers; the three log groups are mappings or None."""
+        self._rmpc_stack_rollout("dart_rmpc_stack_lm_rollout_dev" if lm else "dart_rmpc_stack_rollout_dev", False, E, n, k0,
+                                 steps, log_rows, arm_prm_stride, arrays, rmpc_logs, stack_logs, arm_logs, plant, loop, scfg,
+                                 dcfg, qcfg, lm, stream)
+
+    def rmpc_stack_rollout(self, E, n, k0, steps, rows, arm_prm_stride, arrays, rmpc_logs=None, stack_logs=None,
+                           arm_logs=None, plant=None, loop=None, scfg=None, dcfg=None, qcfg=None, lm=False):
+        """The same on host arrays (C-contiguous numpy, no ``work``; blocking): state and metrics are advanced, the step
+        rows k0 .. k0+steps-1 of the logs given and the episode rows from ``nlog`` on are filled in place."""
+        for name, a in list(arrays.items()) + [kv for g in (rmpc_logs, stack_logs, arm_logs) if g for kv in g.items()]:
+            if a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous):
+                raise DartMPCError(f"stack rollout array {name!r} must be a C-contiguous numpy array")
+        self._rmpc_stack_rollout("dart_rmpc_stack_lm_rollout" if lm else "dart_rmpc_stack_rollout", True, E, n, k0, steps,
+                                 rows, arm_prm_stride, arrays, rmpc_logs, stack_logs, arm_logs, plant, loop, scfg, dcfg,
+                                 qcfg, lm, 0)
 
     def loop_state_lm(self, x0, x_rot0=None, P0=1e3):
         """The state of a fresh cross-plant rollout from the measured states ``x0`` [B, 4] and the rotation states

@@ -1234,3 +1234,143 @@ def rollout_stack(states0, targets, prm, q0, qd0, models, params, steps: int, tr
         logs.append(d)
     out.update(logs=logs, status=lg["status"], iters=lg["iters"], tilt_log=sl["tilt"], tray_log=sl["tray"])
     return out
+
+
+# ---- the RMPC loop closed through the dual-arm layer (dart_rmpc_stack_rollout) --------------------------------------
+def rmpc_stack_arrays(x0, targets, q0, qd0, models, params, tray_pos, mu=0.1, prm=None, plant_models=None,
+                      plant_pvec=None, x_rot0=None, grasp=None, N: int = 20, Ts: float = 0.002, P0: float = 1e3):
+    """The host arrays of a fresh RMPC stack run in the names of ``_lib.RMPC_STACK_ROLLOUT_ARGS`` (without ``work``):
+    inputs, the RMPC loop state of ``RmpcSolver.loop_state`` (``loop_state_lm`` with ``plant_pvec``), the arm state and
+    the in/out metrics (metrics zeros with slot 1 = -1; stack and arm metrics zeros).  x0, targets [E, 4]; q0, qd0
+    [E, 2, n]; ``prm`` [E, 10] (default: rob_ctrl.py's parameter row).  Returns (arrays, E, n, lm)."""
+    from . import arm as A
+    from ._lib import RMPC_LOOP_STATE, RMPC_LM_LOOP_STATE, _loop_shape, lib, loop_metrics
+    x0 = np.asarray(x0, float).reshape(-1, 4)
+    E = x0.shape[0]
+    q = np.ascontiguousarray(q0, dtype=np.float64).copy()
+    qd = np.ascontiguousarray(qd0, dtype=np.float64).copy()
+    if q.ndim != 3 or q.shape[:2] != (E, 2) or qd.shape != q.shape:
+        raise A.DartMPCError(f"q0 and qd0 are [{E}, 2, n]")
+    n = q.shape[2]
+    rows = A._model_rows(models, n, 2)
+    pl, pr = params if isinstance(params, (tuple, list)) else (params, params)
+    lm = plant_pvec is not None
+    if prm is None:
+        ctl = AdaptiveNPMPCSmooth(None, None, Ts=Ts, N=N, Qp=80.0, Qv=2.0, Ru=0.02, Rdu=1.0, u_bounds=(-0.6, 0.6),
+                                  du_bounds=(-0.06, 0.06), vmax=0.2, v_eps=0.1)          # rob_ctrl.py:280-283
+        prm = np.tile(ctl.params(), (E, 1))
+    nw = lib().dart_rmpc_nw(int(N))
+    arrays = {name: np.zeros(_loop_shape(E, width, nw=nw), dt) for name, width, dt in (RMPC_LM_LOOP_STATE if lm else RMPC_LOOP_STATE)}
+    arrays["x"][:, :4] = x0
+    if lm and x_rot0 is not None:
+        arrays["x"][:, 4:] = np.asarray(x_rot0, float).reshape(E, 4)
+    arrays["prev"][:] = x0
+    arrays["P"][:] = np.tile(np.eye(7) * float(P0), (2, 1, 1)).reshape(98)
+    arrays.update({
+        "target": np.ascontiguousarray(np.asarray(targets, float).reshape(E, 4)),
+        "prm": np.ascontiguousarray(np.asarray(prm, float).reshape(E, 10)),
+        "metrics": loop_metrics(E),
+        "grasp": np.ascontiguousarray(A.DACTL_GRASP if grasp is None else grasp, dtype=np.float64),
+        "models": rows, "plant_models": rows if plant_models is None else A._model_rows(plant_models, n, 2),
+        "arm_prm": np.ascontiguousarray(np.tile(np.stack([A.pack_params(pl), A.pack_params(pr)]), (E, 1))),
+        "q": q.reshape(2 * E, n), "qd": qd.reshape(2 * E, n), "qdd_prev": np.zeros((2 * E, n)),
+        "arm_metrics": np.zeros((2 * E, A.NMETRIC)),
+        "tray_pos": np.ascontiguousarray(np.broadcast_to(np.asarray(tray_pos, dtype=np.float64), (E, 3))),
+        "stack_metrics": np.zeros((E, 8)),
+    })
+    if lm:
+        arrays["plant_pvec"] = np.ascontiguousarray(np.asarray(plant_pvec, float).reshape(E, 34))
+    else:
+        arrays["mu"] = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, np.float64), (E,)))
+    if arrays["grasp"].shape != (2, 7):
+        raise A.DartMPCError("grasp transforms are [2, 7] (pos | quat)")
+    return arrays, E, n, lm
+
+
+def rmpc_stack_logs(rows, E, n, lm):
+    """The three log groups of an RMPC stack run, prefilled: (RMPC logs, stack logs, arm logs)."""
+    from ._lib import RMPC_LOOP_LOGS, RMPC_LM_LOOP_LOGS, RMPC_STACK_LOGS, loop_logs
+    return (loop_logs(RMPC_LM_LOOP_LOGS if lm else RMPC_LOOP_LOGS, rows, E), loop_logs(RMPC_STACK_LOGS, rows, E),
+            stack_logs(rows, E, n, lm)[2])
+
+
+def rollout_stack_rmpc(x0, targets, q0, qd0, models, params, steps: int, tray_pos, couple="achieved", mu=0.1, prm=None,
+                       plant_models=None, plant_pvec=None, x_rot0=None, metrics_only: bool = False,
+                       settle_steps: int = 0, check_every: int = 0, N: int = 20, Ts: float = 0.002, device: int = 0,
+                       pos_tol: float = ERROR_THRESHOLD, plant_kw: dict | None = None, dr_max: float = 0.01,
+                       alpha_rg: float = 0.5, lam: float = 0.995, P0: float = 1e3, grasp=None, jacdot_point: int = 0,
+                       **cfg):
+    """E RMPC experiments closed through two arms each, resident on the device (``dart_rmpc_stack_rollout``;
+    rob_ctrl.py:331-416): per step the RLS update fused into the warm-started solve, the tray pose commanded by its tilt,
+    both arms' dynamics, impedance QP and plant step, the tray the arms then hold, and the object's plant step -- with
+    ``couple="achieved"`` on the achieved tilt, with ``"ride"`` on the lagged command as in ``rollout_rmpc`` (the arms are
+    measured only) -- then the governor and the staged reference of the next solve.
+
+    x0, targets, ``mu``, ``prm``, ``plant_pvec`` / ``x_rot0``, ``check_every`` and the loop's keywords as
+    ``rollout_rmpc``; q0, qd0, models, params, ``plant_models``, ``tray_pos``, ``settle_steps`` as ``rollout_stack``.
+    ``check_every`` > 0 runs chunks of that many steps and stops once every episode has closed; state and metrics are
+    in/out, so the chunks are the bits of one call.
+
+    Returns dict(episodes, status [steps run, E], done, extra: what ``rollout_rmpc(..., return_logs=True)`` returns, each
+    episode row's ``torque`` being the 2 n torques [L | R] the arms applied in that step (the reference's torques_log);
+    metrics [E, 8], stack_metrics [E, 8], arm: what ``rollout_dual_arm`` returns, tilt_log, tray_log, U_log
+    [steps run, E, .], steps, wall_s).  ``metrics_only``: no log is written or moved; episodes, status, extra and the
+    three logs are None."""
+    from . import arm as A
+    from ._lib import plant_config, rmpc_loop_config, stack_config
+    if settle_steps:
+        E0 = np.asarray(q0).shape[0]
+        level = np.zeros((1, E0, 7))
+        level[0, :, :3] = np.broadcast_to(np.asarray(tray_pos, dtype=np.float64), (E0, 3))
+        level[0, :, 3] = 1.0
+        st = rollout_dual_arm(q0, qd0, level, models, params, int(settle_steps), plant_models=plant_models,
+                              metrics_only=True, grasp=grasp, jacdot_point=jacdot_point, **cfg)
+        q0, qd0 = st["q"], st["qd"]
+    arrays, E, n, lm = rmpc_stack_arrays(x0, targets, q0, qd0, models, params, tray_pos, mu, prm, plant_models, plant_pvec,
+                                         x_rot0, grasp, N, Ts, P0)
+    lg, sl, al = (None, None, None) if metrics_only else rmpc_stack_logs(steps, E, n, lm)
+    loop = rmpc_loop_config(dr_max=dr_max, alpha_rg=alpha_rg, rls_lambda=lam, pos_tol=pos_tol)
+    solver = RmpcSolver(N=N, Ts=Ts, B_max=max(E, 1), device=device)
+    chunk = int(check_every) if check_every and check_every > 0 else max(steps, 1)
+    k = 0
+    try:
+        t0 = time.perf_counter()
+        while k < steps:
+            m = min(chunk, steps - k)
+            solver.rmpc_stack_rollout(E, n, k, m, 0 if metrics_only else steps, arrays["arm_prm"].shape[1], arrays, lg, sl,
+                                      al, plant=plant_config(**(plant_kw or {})), loop=loop, scfg=stack_config(couple),
+                                      dcfg=A.arm_dyn_config(jacdot_point=int(jacdot_point)), qcfg=A.arm_config(**cfg), lm=lm)
+            k += m
+            if arrays["done"].all():
+                break
+        wall = time.perf_counter() - t0
+    finally:
+        solver.close()
+    out = {"episodes": None, "status": None, "done": arrays["done"].astype(bool), "extra": None,
+           "metrics": arrays["metrics"], "stack_metrics": arrays["stack_metrics"],
+           "arm": {"q": arrays["q"].reshape(E, 2, n), "qd": arrays["qd"].reshape(E, 2, n),
+                   "qdd_prev": arrays["qdd_prev"].reshape(E, 2, n), "metrics": arrays["arm_metrics"],
+                   "logs": None if al is None else {name: a[:k] for name, a in al.items()}, "wall_s": wall},
+           "tilt_log": None, "tray_log": None, "U_log": None, "steps": k, "wall_s": wall}
+    if metrics_only:
+        return out
+    episodes = []
+    for b in range(E):
+        nl = min(int(arrays["nlog"][b]), steps)
+        # a fresh run's open episode logs one row per step from step 0: row j's torques are step j's tau
+        eps = {}
+        add_episode(eps, "ep1", lg["pos_err"][:nl, b].tolist(), lg["pos_err_norm"][:nl, b].tolist(),
+                    list(lg["u_cmd"][:nl, b]), [al["tau"][j, 2 * b:2 * b + 2].reshape(2 * n).copy() for j in range(nl)],
+                    lg["timestep"][:nl, b].tolist())
+        eps["metrics"] = arrays["metrics"][b]
+        if lm:
+            eps["rot"] = lg["rot"][:k, b]
+        episodes.append(eps)
+    state = {name: arrays[name] for name in ("x", "tilt", "prev", "u_prev", "r_v", "theta", "P", "w", "done", "nlog",
+                                             "metrics")}
+    extra = {name: lg[name][:k] for name in ("x", "theta", "r_v", "f", "status", "iters")}
+    extra.update(state=state, solve_time=wall / max(k, 1),
+                 episode_rows={name: lg[name] for name in ("pos_err", "pos_err_norm", "u_cmd", "timestep")})
+    out.update(episodes=episodes, status=lg["status"][:k], extra=extra, tilt_log=sl["tilt"][:k], tray_log=sl["tray"][:k],
+               U_log=sl["U_cmd"][:k])
+    return out

@@ -1532,6 +1532,135 @@ int dart_pmpc_stack_lm_rollout(dart_mpc_handle *h, const dart_plant_config *plan
                                double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
                                int32_t *status_log, void *hip_stream);
 
+/* ---- The RMPC loop closed through the dual-arm layer (added within ABI 8) ------------------------------------------
+ * RMPC/dev_dual/rob_ctrl.py:331-416 on one stream without the host: per step k of E experiments (arm instances 2 e, 2 e + 1)
+ *   solve        dart_rmpc_solve_batch_dev, warm-started in place on w, with the fused RLS on theta, P, phi, y
+ *   command      tray_cmd[e] = (tray_pos[e] | quaternion of u0[e]), the launch of the PMPC stack loop
+ *   arm dynamics, arm QP, arm plant     as in the PMPC stack loop                 q_k -> q_{k+1}
+ *   couple + object   the tray the two arms hold at q_k (dart_tray_from_arms), then post(k) / pre(k+1) of
+ *                     dart_rmpc[_lm]_loop_step_dev
+ * One pre launch precedes the first solve: six launches per step.  couple as above: DART_STACK_RIDE is exactly
+ * dart_rmpc[_lm]_rollout on the object side (the arms ride along and are measured); DART_STACK_ACHIEVED sets tilt := the
+ * achieved tilt of q_k and drives the plant with it (a non-finite one is not passed on: the last tilt is held and the
+ * step counted).  u_prev := u0 in both modes: the controller's own last command (rob_ctrl.py:416).  The RLS sees the
+ * measured states either way, so in achieved mode it identifies the object on the tray the arms hold.
+ *
+ * Arrays.  The RMPC loop's, as dart_rmpc[_lm]_rollout: target [E][4], prm [E][10], mu [E] (LMPC plant: plant_pvec
+ * [E][34]), x [E][6] (LMPC plant: [E][8]), tilt, prev, u_prev, r_v, theta, P, w, done, nlog; metrics [E][8] kept on both
+ * plants (the tray plant's slot 6 stays 0).  The arm rollout's, work (dart_stack_work_len(E, n)), tray_pos and
+ * stack_metrics [E][8] as dart_pmpc_stack_rollout.  All state and metrics are in/out: two calls of K1 and K2 steps give
+ * the bits of one call of K1 + K2.
+ *
+ * Logs [log_rows][.]..., in three groups, each given whole or all null; with none given log_rows is not consulted
+ * (metrics-only; done and nlog still advance), on both plants:
+ *   the RMPC rollout's ten (LMPC plant: and log_rot): episode rows at nlog[e] while !done[e], step rows at k0 + j;
+ *   log_U [..][E][2] the command u0, log_quat [..][E][4] its quaternion (the bits of tray_cmd[:, 3:]), log_tilt
+ *   [..][E][2] the achieved tilt as measured, log_tray [..][E][7] the achieved pose;
+ *   the arm rollout's six ([..][2 E][.]); tau_log rows [2 e | 2 e + 1] are the reference's torques_log of experiment e.
+ *
+ * DART_MPC_EINVAL before any HIP call: a handle that is not RMPC's, a null config or required pointer, what
+ * dart_rmpc_rollout refuses of the plant and loop configs, a group of logs given in part, k0 + steps > log_rows with a
+ * group given, E < 1 or E > B_max, couple neither of the two, what dart_dual_arm_rollout refuses of n, arm_prm_stride
+ * and the two arm configs, and (host form) a negative nlog. */
+
+/* One launch (device pointers, asynchronous).  phase DART_STACK_COMMAND: tray_cmd from u0 and tray_pos (only these
+ * three are read).  phase DART_STACK_COUPLE: couple + post(k) and / or pre; snap and ee_quat are what the step's arm
+ * dynamics wrote; x0, Rref [E][4 (N + 1)], phi [E][7], y [E][2], u0, f, status, iters are the solve's per-step arrays. */
+int dart_rmpc_stack_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                                  const dart_stack_config *scfg,
+                                  int E, int n, int k, int phase, int do_post, int do_pre, int log_rows,
+                                  const double *target, const double *prm, const double *mu,
+                                  const double *tray_pos, const double *grasp, const double *snap, const double *ee_quat,
+                                  double *x, double *tilt, double *prev, double *u_prev, double *r_v, const double *theta,
+                                  int32_t *done, int32_t *nlog, double *metrics, double *stack_metrics,
+                                  double *x0, double *Rref, double *phi, double *y, double *tray_cmd,
+                                  const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                                  double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                                  double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                                  int32_t *log_status, int32_t *log_iters,
+                                  double *log_U, double *log_quat, double *log_tilt, double *log_tray, void *hip_stream);
+int dart_rmpc_stack_lm_loop_step_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                                     const dart_stack_config *scfg,
+                                     int E, int n, int k, int phase, int do_post, int do_pre, int log_rows,
+                                     const double *target, const double *prm, const double *plant_pvec,
+                                     const double *tray_pos, const double *grasp, const double *snap, const double *ee_quat,
+                                     double *x, double *tilt, double *prev, double *u_prev, double *r_v, const double *theta,
+                                     int32_t *done, int32_t *nlog, double *metrics, double *stack_metrics,
+                                     double *x0, double *Rref, double *phi, double *y, double *tray_cmd,
+                                     const double *u0, const double *f, const int32_t *status, const int32_t *iters,
+                                     double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                                     double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                                     int32_t *log_status, int32_t *log_iters, double *log_rot,
+                                     double *log_U, double *log_quat, double *log_tilt, double *log_tray, void *hip_stream);
+
+/* `steps` steps from step k0, no host synchronisation in between.  Device pointers, asynchronous on hip_stream
+ * (NULL: the handle's stream). */
+int dart_rmpc_stack_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                                const dart_stack_config *scfg, const dart_arm_dyn_config *dcfg, const dart_arm_config *qcfg,
+                                int E, int n, int k0, int steps, int log_rows, int arm_prm_stride,
+                                const double *target, const double *prm, const double *mu,
+                                double *x, double *tilt, double *prev, double *u_prev, double *r_v, double *theta,
+                                double *P, double *w, int32_t *done, int32_t *nlog, double *metrics,
+                                const double *grasp, const double *models, const double *plant_models,
+                                const double *arm_prm, double *q, double *qd, double *qdd_prev, double *arm_metrics,
+                                double *work, const double *tray_pos, double *stack_metrics,
+                                double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                                double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                                int32_t *log_status, int32_t *log_iters,
+                                double *log_U, double *log_quat, double *log_tilt, double *log_tray,
+                                double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
+                                int32_t *status_log, void *hip_stream);
+int dart_rmpc_stack_lm_rollout_dev(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                                   const dart_stack_config *scfg, const dart_arm_dyn_config *dcfg,
+                                   const dart_arm_config *qcfg,
+                                   int E, int n, int k0, int steps, int log_rows, int arm_prm_stride,
+                                   const double *target, const double *prm, const double *plant_pvec,
+                                   double *x, double *tilt, double *prev, double *u_prev, double *r_v, double *theta,
+                                   double *P, double *w, int32_t *done, int32_t *nlog, double *metrics,
+                                   const double *grasp, const double *models, const double *plant_models,
+                                   const double *arm_prm, double *q, double *qd, double *qdd_prev, double *arm_metrics,
+                                   double *work, const double *tray_pos, double *stack_metrics,
+                                   double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                                   double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                                   int32_t *log_status, int32_t *log_iters, double *log_rot,
+                                   double *log_U, double *log_quat, double *log_tilt, double *log_tray,
+                                   double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
+                                   int32_t *status_log, void *hip_stream);
+
+/* Host pointers: the arrays are staged through the handle's arena around the device form (no work argument); the step
+ * rows k0 .. k0 + steps - 1 of the logs given come down, the episode rows travel both ways over the rows
+ * min nlog .. max nlog + steps; blocks. */
+int dart_rmpc_stack_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                            const dart_stack_config *scfg, const dart_arm_dyn_config *dcfg, const dart_arm_config *qcfg,
+                            int E, int n, int k0, int steps, int log_rows, int arm_prm_stride,
+                            const double *target, const double *prm, const double *mu,
+                            double *x, double *tilt, double *prev, double *u_prev, double *r_v, double *theta,
+                            double *P, double *w, int32_t *done, int32_t *nlog, double *metrics,
+                            const double *grasp, const double *models, const double *plant_models,
+                            const double *arm_prm, double *q, double *qd, double *qdd_prev, double *arm_metrics,
+                            const double *tray_pos, double *stack_metrics,
+                            double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                            double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                            int32_t *log_status, int32_t *log_iters,
+                            double *log_U, double *log_quat, double *log_tilt, double *log_tray,
+                            double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
+                            int32_t *status_log, void *hip_stream);
+int dart_rmpc_stack_lm_rollout(dart_mpc_handle *h, const dart_plant_config *plant, const dart_rmpc_loop_config *loop,
+                               const dart_stack_config *scfg, const dart_arm_dyn_config *dcfg, const dart_arm_config *qcfg,
+                               int E, int n, int k0, int steps, int log_rows, int arm_prm_stride,
+                               const double *target, const double *prm, const double *plant_pvec,
+                               double *x, double *tilt, double *prev, double *u_prev, double *r_v, double *theta,
+                               double *P, double *w, int32_t *done, int32_t *nlog, double *metrics,
+                               const double *grasp, const double *models, const double *plant_models,
+                               const double *arm_prm, double *q, double *qd, double *qdd_prev, double *arm_metrics,
+                               const double *tray_pos, double *stack_metrics,
+                               double *log_pos_err, double *log_pos_err_norm, double *log_u_cmd, double *log_timestep,
+                               double *log_x, double *log_theta, double *log_r_v, double *log_f,
+                               int32_t *log_status, int32_t *log_iters, double *log_rot,
+                               double *log_U, double *log_quat, double *log_tilt, double *log_tray,
+                               double *q_log, double *qd_log, double *tau_log, double *ee_log, double *loss_log,
+                               int32_t *status_log, void *hip_stream);
+
 /* ABI version (DART_MPC_ABI_VERSION) of the loaded library. */
 int dart_mpc_abi_version(void);
 
